@@ -12,7 +12,9 @@ wall times, the encoder kernels' full lines -- goes to bench_detail.json (writte
 gpurun_out/ when that exists, else to the working directory; --detail names it).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4k|1080p|720p]
-                  [--content dense|smooth|mixed] [--streams-per-gpu S]
+                  [--content dense|smooth|mixed] [--streams-per-gpu S] [--dump-outputs DIR]
+The headline times exactly K steps, after W warm-up steps, in one window: ms_per_step is the window over K.
+--dump-outputs writes the pictures the K-th step decoded (seeded inputs: the same arguments, the same pictures).
 For N>1 launch with  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
 Streams are sharded whole across ranks (no data-path collective); RCCL is used for the
 barriers, the max-over-ranks time and the checksum gather.
@@ -105,6 +107,23 @@ def _npz_save(path, d):
 def _npz_load(path):
     with np.load(path) as z:
         return {k: (z[k] if z[k].ndim else z[k].item()) for k in z.files}
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_arrays(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=20251015):
+    """--dump-outputs: every array of `arrays` ({name: ndarray}) as <outdir>/<name>.npy in float32.  When they do not fit in
+    `budget` bytes together, each is replaced by the same share of its elements, at positions drawn from `seed` (fixed: the same
+    shapes give the same positions in every run, so two builds' files compare element for element), in index order, as a 1-D array."""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.size for a in arrays.values())
+    room = (budget - 256 * len(arrays)) // 4          # (an .npy header is 128 bytes)
+    for k, (name, a) in enumerate(sorted(arrays.items())):
+        a = np.asarray(a)
+        if total > room:
+            a = a.reshape(-1)[np.sort(np.random.default_rng([seed, k]).choice(a.size, a.size * room // total, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float32))
 
 
 def _oracle_decode(ost, fr):
@@ -536,8 +555,11 @@ def parse_args():
     ap.add_argument("--cpu-frames", type=int, default=160, help="frames of stream 0 the scalar CPU oracle decodes for cpu_baseline (~6 s at 4K)")
     ap.add_argument("--parity-frames", type=int, default=40, help="frames every timed stream is decoded and compared with the oracle before timing")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of the timed batch (profiling runs)")
-    ap.add_argument("--repeats", type=int, default=15, help="minimum number of K-step blocks timed")
-    ap.add_argument("--min-time", type=float, default=0.3, help="keep timing blocks until this many seconds have been measured")
+    ap.add_argument("--repeats", type=int, default=15, help="blocks timed for each keyed entry (clamped to 5..15)")
+    ap.add_argument("--min-time", type=float, default=0.3, help="(kept for old command lines: the headline times exactly --steps steps now)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the pictures the last timed step decoded (every stream's three planes) to DIR/<name>.npy, float32, "
+                         "at most 64 MB (a fixed, seeded sample of each plane when they are larger)")
     ap.add_argument("--second-content", default="smooth", help="content class of the second keyed entry ('' = none)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-late", action="store_true", help="(kept for old command lines: the CPU baseline is always timed behind the GPU's timed regions now)")
@@ -1003,6 +1025,8 @@ def main():
     args, rest = parse_args()
     if args.pmc_child:
         return pmc_child(args.pmc_child)
+    if args.dump_outputs and args.mode != "decode":
+        raise SystemExit("--dump-outputs: the decode mode's timed batch only")
     if args.mode == "enc":
         return main_enc()
     if args.mode == "e2e":
@@ -1182,38 +1206,36 @@ def main():
     wall.mark("upload_and_parity")
 
     # ---- timed region ---------------------------------------------------------------------
-    # Pass A: blocks of exactly K steps, each bracketed by synchronize + barrier on both sides, no
-    # instrumentation inside.  One block at the driver's --steps 20 is 0.8 ms, too short to be a stable
-    # number, so the block is repeated (at least `repeats` times and until ~0.3 s of GPU time has been
-    # measured); `value` comes from the MEDIAN block, min and max are reported beside it.
+    # Pass A: exactly --steps steps, bracketed by synchronize + barrier on both sides, no instrumentation inside;
+    # `ms_per_step` is their time over their number.  The bracket is a fixed cost, so a short window (the
+    # driver's --steps 20 is about 1 ms) measures it as much as the steps: the caller picks --steps from a
+    # first run's ms_per_step.
     step0 = nparity
     run(args.warmup, first=step0)
     step0 += args.warmup
     sync()
-    elapsed_blocks, submit_times, total_t = [], [], 0.0
-    while len(elapsed_blocks) < args.repeats or (total_t < args.min_time and len(elapsed_blocks) < 4096):
-        sync()
-        barrier()
-        t0 = time.perf_counter()
-        run(args.steps, first=step0)
-        t_sub = time.perf_counter() - t0   # (diagnostic: the host's part, all K steps submitted)
-        sync()
-        dt = time.perf_counter() - t0      # this rank's K steps, start aligned by the barrier; the MAX over ranks is taken below
-        submit_times.append(t_sub)
-        barrier()                          # (outside the clock: a trailing collective would add its own latency to every 0.8 ms block)
-        elapsed_blocks.append(dt)
-        total_t += dt
-        step0 += args.steps
-        if dist.is_initialized():   # every rank must run the same number of blocks
-            total_t = shard.reduce_max([total_t], dev)[0]
-    # (diagnostic: what the bracket itself costs -- sync() on an idle device, part of every block's time)
+    barrier()
+    t0 = time.perf_counter()
+    run(args.steps, first=step0)
+    t_sub = time.perf_counter() - t0       # (diagnostic: the host's part, all K steps submitted)
+    sync()
+    dt = time.perf_counter() - t0          # this rank's K steps, start aligned by the barrier; the MAX over ranks is taken below
+    barrier()                              # (outside the clock: a trailing collective would add its own latency)
+    step0 += args.steps
+    if args.dump_outputs:
+        # what a caller of thip_decode_frames holds after the last timed step: every stream's picture, read outside the clock
+        # (the profiling pass below decodes further frames into the same states)
+        dump_arrays(args.dump_outputs, {"stream%d_%s" % (gids[s], pn): st.read_plane(st.ref_idx(theora_amd.FRAME_PREV), pli)
+                                        for s, st in enumerate(states) for pli, pn in enumerate(("y", "cb", "cr"))},
+                    budget=DUMP_BUDGET_BYTES // world)
+    # (diagnostic: what the bracket itself costs -- sync() on an idle device, part of the window's time)
     idle_sync = []
     for _ in range(20):
         t0 = time.perf_counter()
         sync()
         idle_sync.append(time.perf_counter() - t0)
     idle_sync_us = 1e6 * sorted(idle_sync)[len(idle_sync) // 2]
-    submit_us = 1e6 * sorted(submit_times)[len(submit_times) // 2]
+    submit_us = 1e6 * t_sub
     # Pass B: steps with every kernel bracketed by HIP events on the stream it runs on -> per-kernel durations for the
     # roofline.  Kept out of pass A because four event records per step cost ~15 % of the step.  Two shapes:
     #   (1) ONE stream, one launch per step carrying all S streams: the kernel has the chip to itself -- the roofline of the
@@ -1250,8 +1272,8 @@ def main():
         for pli in range(3):
             c = zlib.crc32(st.read_plane(st.ref_idx(theora_amd.FRAME_PREV), pli).tobytes(), c)
         crcs.append(c)
-    blocks = shard.reduce_max(elapsed_blocks, dev)          # per block: the slowest rank
-    per_rank_ms = [round(1e3 * v / args.steps, 5) for v in shard.gather_floats(float(np.median(elapsed_blocks)), dev)]   # every rank's own median
+    elapsed = shard.reduce_max([dt], dev)[0]                # the slowest rank
+    per_rank_ms = [round(1e3 * v / args.steps, 5) for v in shard.gather_floats(dt, dev)]   # every rank's own
     pg = {"initialized": bool(dist.is_initialized()), "world_size": dist.get_world_size() if dist.is_initialized() else 1,
           "backend": dist.get_backend() if dist.is_initialized() else None}
     _, crcs = shard.reduce_results(0.0, crcs, dev)
@@ -1259,7 +1281,6 @@ def main():
         _, parity_crcs = shard.reduce_results(0.0, parity_crcs, dev)
     kms = shard.reduce_max(kms, dev)
     kms_t = shard.reduce_max(kms_t, dev)
-    elapsed = float(np.median(blocks))
     main_desc_bytes = sum(r["desc_bytes"][args.form] for r in main_res)
     main_ws = ws_mb(main_desc_bytes, states)
     wall.mark("timed_region_and_profile_pass")
@@ -1524,8 +1545,7 @@ def main():
 
     if rank == 0:
         first_timed = nparity + args.warmup
-        med_i = int(np.argsort(blocks)[len(blocks) // 2])
-        rng_steps = range(first_timed + med_i * args.steps, first_timed + (med_i + 1) * args.steps)
+        rng_steps = range(first_timed, first_timed + args.steps)
         steps_b_alg = sum(alg_of_step(i, 0) for i in rng_steps)
         steps_b_read = sum(alg_of_step(i, 1) for i in rng_steps)
         prof_b_alg = sum(alg_of_step(i, 0) for i in range(first_prof, first_prof + prof_steps))
@@ -1553,12 +1573,9 @@ def main():
                        "parallelism": "stream-sharded x%d" % world,
                        "process_group": ("nccl (RCCL %s), world %d" % (".".join(map(str, torch.cuda.nccl.version())), world))
                        if dist.is_initialized() else None},
-            "timing": {"blocks": len(blocks), "statistic": "median block", "ms_per_step_min": round(1e3 * min(blocks) / args.steps, 5),
-                       "ms_per_step_max": round(1e3 * max(blocks) / args.steps, 5), "ms_per_step_by_rank": per_rank_ms},
+            "timing": {"statistic": "one window of --steps steps, the slowest rank", "ms_per_step_by_rank": per_rank_ms},
         }
-        detail["timing"] = {"blocks": len(blocks), "steps_per_block": args.steps, "statistic": "median block",
-                            "ms_per_step_first_block": round(1e3 * blocks[0] / args.steps, 5),
-                            "host_submit_us_per_block": round(submit_us, 1), "idle_sync_us": round(idle_sync_us, 1)}
+        detail["timing"] = {"steps": args.steps, "host_submit_us": round(submit_us, 1), "idle_sync_us": round(idle_sync_us, 1)}
         detail["process_group"] = pg
         td_ = traffic_of(_pmc_flat(pmc), kname) or (traffic_of(_pmc_flat(pmc), KERNEL_NAMES[0]) if pmc else None)
         if profiling and kms[0] > 0:

@@ -62,7 +62,8 @@ def test_default_line_fits_the_drivers_tail(monkeypatch, tmp_path, capsys):
     monkeypatch.setattr(synth, "upload_frame", lambda packed, device="cuda": (dict(nslots=packed["nslots"]), None))
     detail = tmp_path / "detail.json"
     monkeypatch.setattr(sys, "argv", ["bench.py", "--size", "qcif", "--all-entries", "--no-parity", "--no-cpu-baseline", "--no-pmc", "--no-enc", "--no-e2e",
-                                      "--steps", "20", "--repeats", "3", "--min-time", "0", "--detail", str(detail)])
+                                      "--steps", "20", "--repeats", "3", "--min-time", "0", "--detail", str(detail),
+                                      "--dump-outputs", str(tmp_path / "dump")])
     bench.main()
     out = capsys.readouterr().out.strip().splitlines()[-1]
     if os.environ.get("THIP_SHOW_LINE"):
@@ -86,3 +87,32 @@ def test_default_line_fits_the_drivers_tail(monkeypatch, tmp_path, capsys):
     assert d["entries"]["1080p_single_gop16"]["distinct_descriptors"] == 16 * 7
     assert d["line"]["value"] == line["value"] and "wall_s" in d and d["wall_s"]["total"] > 0
     assert _FakePlan.submitted > 1000
+    # the last timed step's pictures: three planes of each of the four streams, whole at this size
+    dumped = sorted(os.listdir(tmp_path / "dump"))
+    assert dumped == sorted("stream%d_%s.npy" % (s, p) for s in range(4) for p in ("y", "cb", "cr")), dumped
+    for s in range(4):
+        for p, shape in (("y", (144, 176)), ("cb", (72, 88)), ("cr", (72, 88))):
+            a = np.load(tmp_path / "dump" / ("stream%d_%s.npy" % (s, p)))
+            assert a.dtype == np.float32 and a.shape == shape
+
+
+def test_dump_outputs_stay_in_budget_and_repeat(tmp_path):
+    """bench.dump_arrays: whole arrays in float32 when they fit; else the same seeded sample of every array in every run, the files
+    together within the budget."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    arrays = {"stream0_y": rng.integers(0, 256, (96, 128), dtype=np.uint8), "stream0_cb": rng.integers(0, 256, (48, 64), dtype=np.uint8)}
+    bench.dump_arrays(str(tmp_path / "whole"), arrays)
+    for name, a in arrays.items():
+        b = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert b.dtype == np.float32 and np.array_equal(b, a)
+    budget = 8192
+    for run in ("first", "second"):
+        bench.dump_arrays(str(tmp_path / run), arrays, budget=budget)
+        assert sum(os.path.getsize(tmp_path / run / (name + ".npy")) for name in arrays) <= budget
+    for name, a in arrays.items():
+        b = np.load(tmp_path / "first" / (name + ".npy"))
+        assert b.dtype == np.float32 and b.ndim == 1 and 0 < b.size < a.size
+        assert np.array_equal(b, np.load(tmp_path / "second" / (name + ".npy")))
+        assert set(b.astype(np.uint8).tolist()) <= set(a.reshape(-1).tolist())

@@ -124,16 +124,12 @@ def test_packet_spanning_a_lost_page_is_dropped_whole():
     assert [g[1] for g in got] == [small[0], small[1], small[2]] and gaps == 1
 
 
-def test_real_world_ogg_file_if_the_image_has_one():
-    """Pages written by the real libogg: a Vorbis sound that ships inside MathJax in this image
-    (not copied into the repository, so the test skips where the file is absent, e.g. on the GPU
-    box).  Every page checksum must verify, the first packet is the Vorbis identification header,
-    the last packet carries e_o_s and the final granule position."""
-    import glob
-    cands = glob.glob("/usr/local/lib/python3*/dist-packages/**/invalid_keypress.ogg", recursive=True)
-    if not cands:
-        pytest.skip("no libogg-made file in this image")
-    data = open(cands[0], "rb").read()
+def test_real_world_ogg_file():
+    """Pages written by the real libogg: a Vorbis sound that ships with MathJax (Apache License 2.0,
+    extensions/a11y/invalid_keypress.ogg), kept as tests/golden/mathjax_invalid_keypress.ogg.  Every
+    page checksum must verify, the first packet is the Vorbis identification header, the last packet
+    carries e_o_s and the final granule position."""
+    data = open(os.path.join(ROOT, "tests", "golden", "mathjax_invalid_keypress.ogg"), "rb").read()
     got, (bad, gaps) = demux(data)
     assert (bad, gaps) == (0, 0) and len(got) > 3
     assert got[0][1].startswith(b"\x01vorbis") and got[0][2] == 1
