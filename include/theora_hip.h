@@ -128,6 +128,65 @@ int thip_state_postprocess(thip_state *st, int level, const uint8_t *dc_qis, con
 int thip_state_read_pp_plane(thip_state *st, int pli, uint8_t *host_out);
 
 /* ------------------------------------------------------------------------------------
+ * Pictures that stay on the device: a state's finished picture cropped, turned top row first and written to caller DEVICE
+ * memory, as planar Y'CbCr or as R'G'B' (k_picture_out; up to THIP_MAX_BATCH requests a launch, larger calls are chunked).
+ *
+ *   THIP_PIC_YCBCR       planar Y'CbCr at the stream's own subsampling, dst[0..2].  The chroma rectangle follows the raw rule
+ *                        of the reference's dump_video: columns [x >> hdec, (x + width + hdec) >> hdec), rows likewise with vdec
+ *                        (odd offsets allowed); `chroma` is ignored.
+ *   THIP_PIC_RGB24       interleaved R, G, B (HWC, 3 bytes a pixel), dst[0]
+ *   THIP_PIC_RGBA32      interleaved R, G, B, A = 255 (HWC, 4 bytes a pixel), dst[0]
+ *   THIP_PIC_RGB_PLANAR  three planes R, G, B (CHW), dst[0..2]
+ *
+ * Colour conversion.  The specification gives it as real-valued formulas (offsets 16 / 128, excursions 219 / 224, Kr = 0.299,
+ * Kb = 0.114: one matrix for all three Theora colour spaces); this library's exact integer form is
+ *     y = Y - 16,  u = Cb - 128,  v = Cr - 128                     (int32; >> is an arithmetic shift)
+ *     R = clamp255((76309*y            + 104597*v + 32768) >> 16)
+ *     G = clamp255((76309*y - 25675*u  -  53279*v + 32768) >> 16)
+ *     B = clamp255((76309*y + 132201*u            + 32768) >> 16)
+ * within 1 LSB of round(255 * clamp(formula)) for every (Y, Cb, Cr).
+ * Chroma of an RGB pixel (x, y) (display coordinates):
+ *   THIP_CHROMA_NEAREST  the sample (x >> hdec, y >> vdec)
+ *   THIP_CHROMA_LINEAR   Theora's centred siting: on each decimated axis an even index 2k takes 3/4 c[k] + 1/4 c[k-1], an odd
+ *                        index 2k+1 takes 3/4 c[k] + 1/4 c[k+1], indices clamped at the edge of the full coded chroma plane (not
+ *                        at the crop); one rounding for both axes: (9a + 3b + 3c + d + 8) >> 4 on two axes, (3a + b + 2) >> 2 on
+ *                        one (a the sample itself, b its neighbour along x, c along y, d the diagonal one).
+ *
+ * The contract:
+ *   - asynchronous: the call never waits on the host;
+ *   - ordered behind the frame: the output is ordered behind the kernels that decoded (and post-processed) the picture;
+ *   - visible on the caller's stream: work queued on `stream` after the call sees the output;
+ *   - later frames do not affect it: the next launch that writes the buffer read -- a frame decoded or post-processed after the
+ *     call -- waits for the conversion (the same ordering that chains a state's frames across streams);
+ *   - stream NULL: each request goes down its state's own stream, thip_synchronize waits for it, and states of different devices
+ *     may share a call; a non-NULL stream (a hipStream_t) takes every request and all states must be on its device (as in
+ *     thip_decode_frames);
+ *   - all or nothing: every request is checked before anything is queued.  THIP_EFAULT: reqs, a state or a destination the
+ *     format uses is NULL.  THIP_EINVAL: n < 0, a bad format or chroma, a rectangle outside the frame, a pitch smaller than the
+ *     row, a state with no decoded frame, bufi outside -1..2.  n == 0 does nothing and returns THIP_OK;
+ *   - hand-over faults: a picture made from a frame whose tile hand-over failed (thip_synchronize) is as wrong as the frame;
+ *     thip_state_check_fault / thip_synchronize report it as ever, and a new call after the repair gives the right picture.
+ * Destinations may have any alignment and pitch; rows that start on 16 bytes are written with 16-byte stores.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_PIC_YCBCR 0
+#define THIP_PIC_RGB24 1
+#define THIP_PIC_RGBA32 2
+#define THIP_PIC_RGB_PLANAR 3
+#define THIP_CHROMA_NEAREST 0
+#define THIP_CHROMA_LINEAR 1
+typedef struct thip_picture_req {
+  thip_state *state;
+  int32_t bufi;            /* -1: the newest frame's picture (the post-processed one if thip_state_postprocess made it) = what
+                              thip_state_ycbcr_map would hand out; 0..2: that ring buffer as decoded */
+  int32_t format, chroma;  /* THIP_PIC_*, THIP_CHROMA_* (ignored for THIP_PIC_YCBCR) */
+  int32_t x, y, width, height;   /* display coordinates of the coded frame (row 0 at the top); width == 0 && height == 0: the
+                                    whole frame (x and y are then ignored) */
+  void *dst[3];            /* device memory on the state's device */
+  int64_t dst_pitch[3];    /* bytes per row */
+} thip_picture_req;
+int thip_picture_out(const thip_picture_req *reqs, int n, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Work tiles.  The device walks a frame in the reference's CODED ORDER (state.c:123-190):
  * a tile is 4 consecutive super blocks of one super-block row of one plane -- 16x4
  * fragments, 128x32 pixels, one wavefront -- and lane = 16*(super block within the tile) + (position of the

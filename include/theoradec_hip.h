@@ -166,6 +166,27 @@ typedef struct {
 /* Which GPU the context's device state lives on (th_decode_alloc_on, option "device" / THIP_DEVICE): buf = int, receives the
    device index (thip_state_device); TH_EINVAL for a context without device state (slot-trace mode). */
 #define TH_DECCTL_THIP_GET_DEVICE (0x7106)
+/* Extension: buf = int.  0: decoded frames are no longer copied to the host image one by one as they are decoded (the copy the
+   library makes for th_decode_ycbcr_out by default); th_decode_ycbcr_out still works and then copies the picture it is asked for
+   on demand.  1 (the default): every frame is copied as it is decoded (unless post-processing replaces the picture, which is
+   copied when asked for).  For callers that take their pictures on the device (TH_DECCTL_THIP_PICTURE_OUT). */
+#define TH_DECCTL_THIP_SET_HOST_OUTPUT (0x7107)
+/* Extension: buf = thip_picture_out_args.  Writes the picture of the frame th_decode_packetin last returned (TH_DUPFRAME: the
+   repeated one) to device memory, cropped and converted as thip_picture_out does (include/theora_hip.h: formats THIP_PIC_*,
+   chroma THIP_CHROMA_*, the integer colour conversion, alignment, and its ordering and lifetime guarantees): crop 1 = th_info's
+   picture region (pic_x, pic_y, pic_width, pic_height), 0 = the whole coded frame; stream = a hipStream_t (NULL: the context's
+   own stream, which thip_synchronize waits for); dst on the context's device (TH_DECCTL_THIP_GET_DEVICE).  It is the same
+   picture th_decode_ycbcr_out would hand out, also when that call has already decoded the next announced packet ahead (option
+   fe_pipeline).  The request itself never decodes ahead and never waits on the host.  Returns 0, what thip_picture_out returns
+   for bad arguments, TH_EINVAL before the first frame, TH_EIMPL in slot-trace mode (no device state). */
+#define TH_DECCTL_THIP_PICTURE_OUT (0x7108)
+typedef struct thip_picture_out_args {
+  int32_t format, chroma;  /* THIP_PIC_*, THIP_CHROMA_* */
+  int32_t crop;            /* 1: th_info's picture region; 0: the whole coded frame */
+  void *dst[3];            /* device memory */
+  int64_t dst_pitch[3];    /* bytes per row */
+  void *stream;            /* hipStream_t, or NULL */
+} thip_picture_out_args;
 typedef struct thip_slot_trace {
   int64_t ncoded;           /* state_frag_recon calls, in call (= coded) order */
   const int32_t *fragi;     /* _fragi */

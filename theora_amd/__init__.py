@@ -203,6 +203,21 @@ class State:
             outs.append(np.frombuffer(buf, np.uint8).reshape(g["height"], strides[pli])[:, :g["width"]])
         return outs
 
+    def picture(self, fmt="rgb", chroma="linear", rect=None, bufi=-1, stream=None):
+        """The state's newest picture (or ring buffer `bufi` as decoded) as a new uint8 device tensor: (H, W, 3), (H, W, 4),
+        (3, H, W), or a tuple of three planes for "ycbcr".  rect = (x, y, width, height) in display coordinates, None = the whole
+        coded frame.  Asynchronous on `stream` (default: torch's current stream), like picture_out."""
+        import torch
+        x, y, w, h = rect if rect is not None else (0, 0, self.frame_width, self.frame_height)
+        shapes = picture_shapes(fmt, w, h, x, self.pixel_fmt, y)
+        dev = torch.device("cuda", self.device)
+        if fmt == "ycbcr":
+            out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+        else:
+            out = torch.empty(shapes, dtype=torch.uint8, device=dev)
+        picture_out([self], [out], fmt, chroma, [rect], [bufi], stream)
+        return out
+
     def set_eager_output(self, on):
         _lib.check(self._L.thip_state_set_eager_output(self._h, int(bool(on))), "set_eager_output")
 
@@ -237,6 +252,112 @@ class State:
 
     def frame_flush(self):
         return _lib.check(self._L.thip_frame_flush(self._h), "frame_flush")
+
+
+# ---------------------------------------------------------------------------------------
+# pictures that stay on the device (thip_picture_out)
+# ---------------------------------------------------------------------------------------
+PIC_FORMATS = {"ycbcr": _lib.PIC_YCBCR, "rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
+CHROMA_MODES = {"nearest": _lib.CHROMA_NEAREST, "linear": _lib.CHROMA_LINEAR}
+
+
+def picture_shapes(fmt, width, height, x=0, pixel_fmt=PF_420, y=0):
+    """The output shapes of a width x height picture at (x, y): one (H, W, 3) / (H, W, 4) / (3, H, W) shape, or three plane
+    shapes for "ycbcr" (the chroma rectangle by the raw rule of include/theora_hip.h)."""
+    if fmt == "rgb":
+        return (height, width, 3)
+    if fmt == "rgba":
+        return (height, width, 4)
+    if fmt == "rgb_planar":
+        return (3, height, width)
+    if fmt != "ycbcr":
+        raise ValueError("unknown picture format %r" % (fmt,))
+    hdec, vdec = int(not (pixel_fmt & 1)), int(not (pixel_fmt & 2))
+    cw = ((x + width + hdec) >> hdec) - (x >> hdec)
+    ch = ((y + height + vdec) >> vdec) - (y >> vdec)
+    return [(height, width), (ch, cw), (ch, cw)]
+
+
+def _pic_dst(fmt, out, shapes):
+    """Destination pointers and row pitches of `out` after checking it against the request's shapes (the library writes
+    exactly that many rows of that many bytes: a tensor too small for them is refused here)."""
+    import torch
+    if fmt in ("ycbcr", "rgb_planar"):
+        planes = list(out) if isinstance(out, (list, tuple)) else [out[0], out[1], out[2]]
+        pshapes = shapes if fmt == "ycbcr" else [shapes[1:]] * 3
+        if len(planes) != 3:
+            raise ValueError("%s wants three planes" % fmt)
+    else:
+        planes, pshapes = [out], [shapes]
+    ptrs, pitches = [], []
+    for t, shp in zip(planes, pshapes):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+            raise TypeError("picture destinations are uint8 device tensors")
+        if tuple(t.shape) != tuple(shp):
+            raise ValueError("destination of shape %s for a picture of %s" % (tuple(t.shape), tuple(shp)))
+        if t.stride(-1) != 1 or (t.dim() == 3 and t.stride(1) != t.shape[2]) or t.stride(0) < t.shape[1] * (t.shape[2] if t.dim() == 3 else 1):
+            raise ValueError("picture destinations need contiguous rows (a row pitch of their own is fine)")
+        ptrs.append(t.data_ptr())
+        pitches.append(t.stride(0))
+    while len(ptrs) < 3:
+        ptrs.append(None)
+        pitches.append(0)
+    return ptrs, pitches
+
+
+_side_streams = {}
+
+
+def _on_stream(device, stream, call):
+    """call(handle) with a hipStream_t that orders like `stream` (default: torch's current stream of `device`).  torch's null
+    stream has handle 0, which the library reads as "the state's own stream": such a call goes down a side stream that waits for
+    the null stream's work, and the null stream waits for the call's."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
+    if h:
+        return call(h)
+    side = _side_streams.get(device)
+    if side is None:
+        side = _side_streams[device] = torch.cuda.Stream(device)
+    side.wait_stream(s)
+    rc = call(side.cuda_stream)
+    s.wait_stream(side)
+    return rc
+
+
+def picture_out(states, outs, fmt="rgb", chroma="linear", rects=None, bufis=None, stream=None):
+    """thip_picture_out: the pictures of `states` into `outs` (uint8 device tensors: (H, W, 3) for "rgb", (H, W, 4) for "rgba",
+    (3, H, W) or three (H, W) planes for "rgb_planar", three planes for "ycbcr"); fmt and chroma may be lists, one per state.  rects: per state (x, y, width, height) in
+    display coordinates, or None for the whole coded frame; bufis: per state -1 (the newest picture, post-processed if it was)
+    or a ring buffer 0..2.  Asynchronous on `stream` (default torch.cuda.current_stream of the states' device)."""
+    L = _lib.load()
+    n = len(states)
+    if len(outs) != n:
+        raise ValueError("one destination per state")
+    fmts = [fmt] * n if isinstance(fmt, str) else list(fmt)
+    chromas = [chroma] * n if isinstance(chroma, str) else list(chroma)
+    for f, c in zip(fmts, chromas):
+        if f not in PIC_FORMATS or c not in CHROMA_MODES:
+            raise ValueError("format %r / chroma %r" % (f, c))
+    reqs = (_lib.PictureReq * max(n, 1))()
+    for i, st in enumerate(states):
+        fmt, chroma = fmts[i], chromas[i]
+        x, y, w, h = rects[i] if rects is not None and rects[i] is not None else (0, 0, 0, 0)
+        sw, sh = (w, h) if (w or h) else (st.frame_width, st.frame_height)
+        ptrs, pitches = _pic_dst(fmt, outs[i], picture_shapes(fmt, sw, sh, x, st.pixel_fmt, y))
+        r = reqs[i]
+        r.state = st.handle
+        r.bufi = -1 if bufis is None else int(bufis[i])
+        r.format, r.chroma = PIC_FORMATS[fmt], CHROMA_MODES[chroma]
+        r.x, r.y, r.width, r.height = x, y, w, h
+        for p in range(3):
+            r.dst[p] = ptrs[p]
+            r.dst_pitch[p] = pitches[p]
+    if n == 0:
+        return
+    device = states[0].device
+    _lib.check(_on_stream(device, stream, lambda h: L.thip_picture_out(reqs, n, h)), "thip_picture_out")
 
 
 def decode_frames(states, descs, stream=None):

@@ -41,6 +41,17 @@ class TileGeom(C.Structure):
                 ("ntiles", C.c_int32)]
 
 
+PIC_YCBCR, PIC_RGB24, PIC_RGBA32, PIC_RGB_PLANAR = 0, 1, 2, 3
+CHROMA_NEAREST, CHROMA_LINEAR = 0, 1
+
+
+class PictureReq(C.Structure):
+    """thip_picture_req (include/theora_hip.h)."""
+    _fields_ = [("state", C.c_void_p), ("bufi", C.c_int32), ("format", C.c_int32), ("chroma", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3)]
+
+
 class TheoraHipError(RuntimeError):
     pass
 
@@ -79,6 +90,7 @@ SYMBOLS = [
     ("thip_state_token_lists_abort", _I, [_P]),
     ("thip_state_token_lists_staging", _I, [_P, _P]),
     ("thip_state_read_pp_plane", _I, [_P, _I, _P]),
+    ("thip_picture_out", _I, [C.POINTER(PictureReq), _I, _P]),
     ("thip_decode_frames", _I, [C.POINTER(_P), C.POINTER(FrameDesc), _I, _P, C.POINTER(C.c_int32)]),
     ("thip_synchronize", _I, []),
     ("thip_frame_begin", _I, [_P, _I]),

@@ -180,6 +180,7 @@ extern "C" const char *thip_option_name(int index, const char **help) {
 #include "thip_dc.h"
 #include "thip_postproc.h"
 #include "thip_tokens.h"
+#include "thip_picture.h"
 
 // ---------------------------------------------------------------------------------------
 // host side
@@ -1701,6 +1702,144 @@ int thip_state_read_pp_plane(thip_state *st, int pli, uint8_t *host_out) {
   HIP_TRY(hipDeviceSynchronize());
   const uint8_t *src = (st->pp_active[pli] ? st->pp_frame : st->frames[st->last_decoded]) + g.plane_off;
   HIP_TRY(hipMemcpy2D(host_out, g.width, src, g.stride, g.width, g.height, hipMemcpyDeviceToHost));
+  return THIP_OK;
+}
+
+// ---- device-resident pictures (thip_picture_out, k_picture_out in thip_picture.h) ------------------------------------------
+// The rectangle of a request in display coordinates of the coded frame: false if it does not lie inside the frame.
+static bool picture_rect(const thip_picture_req &q, const thip_state *st, int &x, int &y, int &w, int &h) {
+  if (q.width == 0 && q.height == 0) {
+    x = y = 0;
+    w = st->frame_width;
+    h = st->frame_height;
+    return true;
+  }
+  x = q.x;
+  y = q.y;
+  w = q.width;
+  h = q.height;
+  return x >= 0 && y >= 0 && w > 0 && h > 0 && (int64_t)x + w <= st->frame_width && (int64_t)y + h <= st->frame_height;
+}
+
+static int picture_check(const thip_picture_req &q) {
+  const thip_state *st = q.state;
+  if (!st) return THIP_EFAULT;
+  if (q.format < THIP_PIC_YCBCR || q.format > THIP_PIC_RGB_PLANAR) return THIP_EINVAL;
+  if (q.format != THIP_PIC_YCBCR && q.chroma != THIP_CHROMA_NEAREST && q.chroma != THIP_CHROMA_LINEAR) return THIP_EINVAL;
+  const int nd = q.format == THIP_PIC_RGB24 || q.format == THIP_PIC_RGBA32 ? 1 : 3;
+  for (int p = 0; p < nd; p++)
+    if (!q.dst[p]) return THIP_EFAULT;
+  if (q.bufi < -1 || q.bufi > 2 || st->last_decoded < 0) return THIP_EINVAL;
+  int x, y, w, h;
+  if (!picture_rect(q, st, x, y, w, h)) return THIP_EINVAL;
+  for (int p = 0; p < nd; p++) {
+    int64_t need = w;
+    if (q.format == THIP_PIC_RGB24) need = 3 * (int64_t)w;
+    else if (q.format == THIP_PIC_RGBA32) need = 4 * (int64_t)w;
+    else if (q.format == THIP_PIC_YCBCR && p > 0) need = ((x + w + st->hdec) >> st->hdec) - (x >> st->hdec);   // dump_video's raw rule
+    if (q.dst_pitch[p] < need) return THIP_EINVAL;
+  }
+  return THIP_OK;
+}
+
+static void picture_fill(PicReqK &K, const thip_picture_req &q) {
+  const thip_state *st = q.state;
+  memset(&K, 0, sizeof(K));
+  // bufi -1: what thip_state_ycbcr_map would hand out (launch_frame_out's choice); 0..2: that buffer as decoded
+  const bool pp = q.bufi < 0 && st->pp_serial == st->frame_serial;
+  const uint8_t *frame = st->frames[q.bufi < 0 ? st->last_decoded : q.bufi];
+  int x, y, w, h;
+  (void)picture_rect(q, st, x, y, w, h);
+  K.format = q.format;
+  K.linear = q.chroma == THIP_CHROMA_LINEAR;
+  K.hdec = st->hdec;
+  K.vdec = st->vdec;
+  int units = 0;
+  for (int p = 0; p < 3; p++) {
+    const thip_plane_geom &g = st->geom[p];
+    K.src[p] = (pp && st->pp_active[p] ? st->pp_frame : frame) + g.plane_off;
+    K.dst[p] = (uint8_t *)q.dst[p];
+    K.dpitch[p] = q.dst_pitch[p];
+    K.spitch[p] = g.stride;
+    K.pw[p] = g.width;
+    K.ph[p] = g.height;
+    const int hd = p ? st->hdec : 0, vd = p ? st->vdec : 0;
+    K.rx[p] = x >> hd;
+    K.ry[p] = y >> vd;
+    K.rw[p] = ((x + w + hd) >> hd) - K.rx[p];
+    K.rh[p] = ((y + h + vd) >> vd) - K.ry[p];
+    K.cpr[p] = (K.rw[p] + 15) >> 4;
+    if (p == 0 || q.format == THIP_PIC_YCBCR) units += K.cpr[p] * K.rh[p];
+    K.unit_end[p] = units;
+  }
+}
+
+// One launch for up to THIP_MAX_BATCH requests on stream s (their states' device current): behind each state's newest work,
+// and each state's next work behind it (order_mark, as after a decoding launch).
+static int picture_launch(const thip_picture_req *const *reqs, int n, hipStream_t s) {
+  PicBatchK B;
+  int max_units = 0;
+  for (int i = 0; i < n; i++) {
+    const int rc = order_behind_previous(reqs[i]->state, s);
+    if (rc < 0) return rc;
+    picture_fill(B.r[i], *reqs[i]);
+    max_units = std::max(max_units, B.r[i].unit_end[2]);
+  }
+  hipLaunchKernelGGL(k_picture_out, dim3((unsigned)((max_units + 255) / 256), (unsigned)n), dim3(256), 0, s, B);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < n; i++) {
+    const int rc = order_mark(reqs[i]->state, s);
+    if (rc < 0) return rc;
+  }
+  return THIP_OK;
+}
+
+int thip_picture_out(const thip_picture_req *reqs, int n, void *stream) {
+  if (n < 0) return THIP_EINVAL;
+  if (n == 0) return THIP_OK;
+  if (!reqs) return THIP_EFAULT;
+  for (int i = 0; i < n; i++) {   // all or nothing: every request is checked before anything is queued
+    const int rc = picture_check(reqs[i]);
+    if (rc < 0) return rc;
+  }
+  std::vector<const thip_picture_req *> ptrs(n);
+  for (int i = 0; i < n; i++) ptrs[i] = &reqs[i];
+  if (stream) {   // caller-owned stream: all states on its device, in submission order
+    for (int i = 1; i < n; i++)
+      if (reqs[i].state->device != reqs[0].state->device) return THIP_EINVAL;
+    DeviceGuard dg(reqs[0].state->device);
+    for (int i = 0; i < n; i += THIP_MAX_BATCH) {
+      const int rc = picture_launch(ptrs.data() + i, std::min(THIP_MAX_BATCH, n - i), (hipStream_t)stream);
+      if (rc < 0) return rc;
+    }
+    return THIP_OK;
+  }
+  // NULL: each request goes down its state's own stream (followup_stream); requests that share a stream share launches
+  std::vector<hipStream_t> sv(n);
+  std::vector<char> done(n, 0);
+  uint32_t devmask = 0;
+  for (int i = 0; i < n; i++) devmask |= 1u << reqs[i].state->device;
+  for (int dev = 0; dev < kMaxDevices; dev++) {
+    if (!(devmask >> dev & 1u)) continue;
+    DeviceGuard dg(dev);
+    for (int i = 0; i < n; i++) {
+      if (reqs[i].state->device != dev) continue;
+      const int rc = followup_stream(reqs[i].state, &sv[i]);
+      if (rc < 0) return rc;
+    }
+    for (int i = 0; i < n; i++) {
+      if (done[i] || reqs[i].state->device != dev) continue;
+      const thip_picture_req *grp[THIP_MAX_BATCH];
+      int m = 0;
+      for (int k = i; k < n && m < THIP_MAX_BATCH; k++)
+        if (!done[k] && reqs[k].state->device == dev && sv[k] == sv[i]) {
+          grp[m++] = &reqs[k];
+          done[k] = 1;
+        }
+      const int rc = picture_launch(grp, m, sv[i]);
+      if (rc < 0) return rc;
+    }
+  }
   return THIP_OK;
 }
 

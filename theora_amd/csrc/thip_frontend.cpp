@@ -28,6 +28,10 @@
 
 #include "../../include/theora_hip.h"
 #include "../../include/theoradec_hip.h"
+// The one backend entry point the front end reaches only on request (TH_DECCTL_THIP_PICTURE_OUT): referenced weakly, so that this
+// translation unit still links on its own against a backend that provides just the decoding slots (the front end's native test
+// drivers stub those); inside libtheora_hip.so the definition in thip_decode.hip is always there.
+#pragma weak thip_picture_out
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -274,6 +278,7 @@ struct th_dec_ctx {
   bool device_dc;   // DC un-prediction left to the backend (THIP_FE_DEVICE_DC=1, or TH_DECCTL_THIP_SET_DEVICE_DC)
   // out-of-loop post-processing (TH_DECCTL_SET_PPLEVEL; decode.c:1203-1325)
   int pp_level;
+  bool host_output;   // frames copied to the host image as they are decoded (TH_DECCTL_THIP_SET_HOST_OUTPUT; default on)
   bool dc_qis_tracked;
   std::vector<uint8_t> dc_qis, frag_qi;
   int32_t pp_dc_scale[64], pp_sharp_mod[64];
@@ -1487,6 +1492,7 @@ th_dec_ctx *th_decode_alloc_on(const th_info *info, const th_setup_info *setup, 
     delete d;
     return nullptr;
   }
+  d->host_output = true;
   if (d->hip) thip_state_set_eager_output(d->hip, 1);   // every frame is wanted on the host (th_decode_ycbcr_out)
   d->device_dc = false;
   if (d->hip && thip_option("fe_device_dc") != 0)
@@ -1589,8 +1595,43 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
       d->pp_level = lvl;
       // every frame is sent to its host image by the decoding launch itself -- unless a post-processed one
       // is going to replace it: then the image is made when th_decode_ycbcr_out asks
-      if (d->hip) thip_state_set_eager_output(d->hip, lvl < 2);
+      if (d->hip) thip_state_set_eager_output(d->hip, d->host_output && lvl < 2);
       return 0;
+    }
+    case TH_DECCTL_THIP_SET_HOST_OUTPUT: {
+      if (!d || !buf) return TH_EFAULT;
+      if (buf_sz != sizeof(int)) return TH_EINVAL;
+      if (d->trace || !d->hip) return TH_EINVAL;
+      d->host_output = *(int *)buf != 0;
+      thip_state_set_eager_output(d->hip, d->host_output && d->pp_level < 2);
+      return 0;
+    }
+    case TH_DECCTL_THIP_PICTURE_OUT: {
+      if (!d || !buf) return TH_EFAULT;
+      if (buf_sz != sizeof(thip_picture_out_args)) return TH_EINVAL;
+      if (d->trace || !d->hip || !thip_picture_out) return TH_EIMPL;
+      if (!d->have_frame) return TH_EINVAL;
+      const thip_picture_out_args *a = (const thip_picture_out_args *)buf;
+      thip_picture_req q;
+      memset(&q, 0, sizeof(q));
+      q.state = d->hip;
+      // th_decode_ycbcr_out may have handed the next announced packet's frame over already (option fe_pipeline, never with
+      // post-processing): the picture is then the held frame's buffer, not the state's newest
+      q.bufi = d->early.valid ? (int32_t)d->early.mark[3] : -1;
+      q.format = a->format;
+      q.chroma = a->chroma;
+      if (a->crop) {
+        q.x = (int32_t)d->info.pic_x;
+        q.y = (int32_t)d->info.pic_y;
+        q.width = (int32_t)d->info.pic_width;
+        q.height = (int32_t)d->info.pic_height;
+      }
+      for (int p = 0; p < 3; p++) {
+        q.dst[p] = a->dst[p];
+        q.dst_pitch[p] = a->dst_pitch[p];
+      }
+      const int rc = thip_picture_out(&q, 1, a->stream);
+      return rc < 0 ? rc : 0;
     }
     case TH_DECCTL_SET_GRANPOS: {
       if (!d || !buf) return TH_EFAULT;

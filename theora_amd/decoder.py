@@ -10,6 +10,15 @@ from ._lib import OggPacket, ThComment, ThImgPlane, ThInfo, TheoraHipError
 TH_DUPFRAME = 1
 TH_DECCTL_THIP_GET_SLOT_TRACE = 0x7101
 TH_DECCTL_THIP_PREFETCH_PACKET = 0x7105
+TH_DECCTL_THIP_GET_DEVICE = 0x7106
+TH_DECCTL_THIP_SET_HOST_OUTPUT = 0x7107
+TH_DECCTL_THIP_PICTURE_OUT = 0x7108
+
+
+class PictureOutArgs(C.Structure):
+    """thip_picture_out_args (include/theoradec_hip.h)."""
+    _fields_ = [("format", C.c_int32), ("chroma", C.c_int32), ("crop", C.c_int32), ("dst", C.c_void_p * 3),
+                ("dst_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
 
 
 class SlotTrace(C.Structure):
@@ -78,6 +87,51 @@ class Decoder:
         for p in buf:
             a = np.ctypeslib.as_array(p.data, (p.height, p.stride))[:, :p.width]
             out.append(a.copy())
+        return out
+
+    def device(self):
+        """TH_DECCTL_THIP_GET_DEVICE: the GPU the context decodes on."""
+        v = C.c_int(-1)
+        rc = self._L.th_decode_ctl(self._dec, TH_DECCTL_THIP_GET_DEVICE, C.byref(v), C.sizeof(v))
+        if rc < 0:
+            raise TheoraHipError("TH_DECCTL_THIP_GET_DEVICE returned %d" % rc)
+        return v.value
+
+    def set_host_output(self, on):
+        """TH_DECCTL_THIP_SET_HOST_OUTPUT: False stops the copy of every decoded frame to the host image (ycbcr_out() then copies
+        on demand)."""
+        v = C.c_int(int(bool(on)))
+        rc = self._L.th_decode_ctl(self._dec, TH_DECCTL_THIP_SET_HOST_OUTPUT, C.byref(v), C.sizeof(v))
+        if rc < 0:
+            raise TheoraHipError("TH_DECCTL_THIP_SET_HOST_OUTPUT returned %d" % rc)
+
+    def picture(self, fmt="rgb", chroma="linear", crop=True, stream=None, out=None):
+        """TH_DECCTL_THIP_PICTURE_OUT: the picture of the frame packetin() last returned as a uint8 device tensor ((H, W, 3),
+        (H, W, 4), (3, H, W), or three planes for "ycbcr"); crop: th_info's picture region, else the whole coded frame.
+        Asynchronous on `stream` (default: torch's current stream).  `out`: destination(s) of those shapes to write instead."""
+        import torch
+        from . import CHROMA_MODES, PIC_FORMATS, _on_stream, _pic_dst, picture_shapes
+        i = self.info
+        x, y, w, h = (i.pic_x, i.pic_y, i.pic_width, i.pic_height) if crop else (0, 0, i.frame_width, i.frame_height)
+        shapes = picture_shapes(fmt, w, h, x, i.pixel_fmt, y)
+        dev = self.device()
+        if out is None:
+            td = torch.device("cuda", dev)
+            out = (tuple(torch.empty(s, dtype=torch.uint8, device=td) for s in shapes) if fmt == "ycbcr"
+                   else torch.empty(shapes, dtype=torch.uint8, device=td))
+        ptrs, pitches = _pic_dst(fmt, out, shapes)
+        a = PictureOutArgs()
+        a.format, a.chroma, a.crop = PIC_FORMATS[fmt], CHROMA_MODES[chroma], int(bool(crop))
+        for p in range(3):
+            a.dst[p] = ptrs[p]
+            a.dst_pitch[p] = pitches[p]
+
+        def call(hs):
+            a.stream = hs
+            return self._L.th_decode_ctl(self._dec, TH_DECCTL_THIP_PICTURE_OUT, C.byref(a), C.sizeof(a))
+        rc = _on_stream(dev, stream, call)
+        if rc < 0:
+            raise TheoraHipError("TH_DECCTL_THIP_PICTURE_OUT returned %d" % rc)
         return out
 
     def slot_trace(self):
