@@ -1,0 +1,166 @@
+/* encoder_example_hip.c -- YUV4MPEG2 in, Ogg/Theora out, through this library's intra-only th_encode_* (include/theoraenc_hip.h)
+ * and its Ogg writer (include/thip_ogg.h).
+ *
+ *   encoder_example_hip [-q quality] [-o out.ogv] in.y4m
+ *
+ * Input: C420jpeg, C420, C420paldv, C420mpeg2 (4:2:0), C422 or C444, any size; no C tag means 4:2:0.  The frame is the picture
+ * padded to multiples of 16, the picture region at (0, 0); the picture-size planes go to th_encode_ycbcr_in as they are.  Every
+ * frame is a key frame at qi = quality (default 48).  Output on stdout without -o.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "theoraenc_hip.h"
+#include "thip_ogg.h"
+
+static int write_pages(thip_ogg_writer *w, FILE *out) {
+  size_t n = 0;
+  const unsigned char *p = thip_ogg_writer_pages(w, &n);
+  return n && fwrite(p, 1, n, out) != n ? -1 : 0;
+}
+
+/* the header line's tags: W, H, F, A, C; 0 on success */
+static int parse_header(FILE *in, int *w, int *h, int *fn, int *fd, int *an, int *ad, int *fmt) {
+  char line[1024];
+  if (!fgets(line, sizeof(line), in) || strncmp(line, "YUV4MPEG2", 9) != 0) return -1;
+  *w = *h = 0;
+  *fn = 30, *fd = 1, *an = 1, *ad = 1, *fmt = TH_PF_420;
+  for (char *t = strtok(line + 9, " \n"); t; t = strtok(NULL, " \n")) {
+    switch (t[0]) {
+      case 'W': *w = atoi(t + 1); break;
+      case 'H': *h = atoi(t + 1); break;
+      case 'F': sscanf(t + 1, "%d:%d", fn, fd); break;
+      case 'A': sscanf(t + 1, "%d:%d", an, ad); break;
+      case 'C':
+        if (strncmp(t + 1, "420", 3) == 0) *fmt = TH_PF_420;
+        else if (strcmp(t + 1, "422") == 0) *fmt = TH_PF_422;
+        else if (strcmp(t + 1, "444") == 0) *fmt = TH_PF_444;
+        else return -1;
+        break;
+      default: break;
+    }
+  }
+  if (*w <= 0 || *h <= 0 || *fn <= 0 || *fd <= 0) return -1;
+  if (*an <= 0 || *ad <= 0) *an = *ad = 1;
+  return 0;
+}
+
+/* one FRAME: 1 read, 0 at the end, -1 on a broken file */
+static int read_frame(FILE *in, unsigned char *buf, size_t bytes) {
+  char line[256];
+  if (!fgets(line, sizeof(line), in)) return 0;
+  if (strncmp(line, "FRAME", 5) != 0) return -1;
+  return fread(buf, 1, bytes, in) == bytes ? 1 : -1;
+}
+
+int main(int argc, char **argv) {
+  int quality = 48;
+  const char *in_path = NULL, *out_path = NULL;
+  for (int i = 1; i < argc; i++) {
+    if (strcmp(argv[i], "-q") == 0 && i + 1 < argc) quality = atoi(argv[++i]);
+    else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) out_path = argv[++i];
+    else in_path = argv[i];
+  }
+  if (!in_path) {
+    fprintf(stderr, "usage: %s [-q quality] [-o out.ogv] in.y4m\n", argv[0]);
+    return 1;
+  }
+  FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
+  if (!in) {
+    fprintf(stderr, "cannot open %s\n", in_path);
+    return 1;
+  }
+  int w, h, fn, fd, an, ad, fmt;
+  if (parse_header(in, &w, &h, &fn, &fd, &an, &ad, &fmt)) {
+    fprintf(stderr, "not a YUV4MPEG2 file this example reads\n");
+    return 1;
+  }
+  const int hdec = !(fmt & 1), vdec = !(fmt & 2);
+  const int cw = (w + hdec) >> hdec, ch = (h + vdec) >> vdec;
+  const size_t ysz = (size_t)w * h, csz = (size_t)cw * ch, fsz = ysz + 2 * csz;
+
+  th_info ti;
+  th_info_init(&ti);
+  ti.frame_width = (unsigned)(w + 15) & ~15u;
+  ti.frame_height = (unsigned)(h + 15) & ~15u;
+  ti.pic_width = (unsigned)w;
+  ti.pic_height = (unsigned)h;
+  ti.pic_x = ti.pic_y = 0;
+  ti.fps_numerator = (unsigned)fn;
+  ti.fps_denominator = (unsigned)fd;
+  ti.aspect_numerator = (unsigned)an;
+  ti.aspect_denominator = (unsigned)ad;
+  ti.colorspace = TH_CS_UNSPECIFIED;
+  ti.pixel_fmt = (th_pixel_fmt)fmt;
+  ti.target_bitrate = 0;
+  ti.quality = quality;
+  ti.keyframe_granule_shift = 6;
+  th_enc_ctx *enc = th_encode_alloc(&ti);
+  if (!enc) {
+    fprintf(stderr, "th_encode_alloc refused the parameters\n");
+    return 1;
+  }
+  FILE *out = out_path ? fopen(out_path, "wb") : stdout;
+  if (!out) {
+    fprintf(stderr, "cannot open %s\n", out_path);
+    return 1;
+  }
+  thip_ogg_writer *ow = thip_ogg_writer_new(0x7E0u);
+  th_comment tc;
+  th_comment_init(&tc);
+  ogg_packet op;
+  int rc = 0;
+  while ((rc = th_encode_flushheader(enc, &tc, &op)) > 0)
+    if (thip_ogg_writer_packetin(ow, &op)) rc = -1;
+  th_comment_clear(&tc);
+  thip_ogg_writer_flush(ow);   /* the headers end a page: data starts on a fresh one */
+  if (rc < 0 || write_pages(ow, out)) {
+    fprintf(stderr, "header error\n");
+    return 1;
+  }
+  unsigned char *buf[2] = {malloc(fsz), malloc(fsz)};
+  int cur = 0, have = read_frame(in, buf[0], fsz), nframes = 0;
+  while (have == 1) {
+    const int next = read_frame(in, buf[cur ^ 1], fsz);   /* one frame ahead: the last packet carries e_o_s */
+    if (next < 0) {
+      fprintf(stderr, "truncated frame\n");
+      return 1;
+    }
+    th_ycbcr_buffer yb;
+    yb[0].width = w, yb[0].height = h, yb[0].stride = w, yb[0].data = buf[cur];
+    yb[1].width = cw, yb[1].height = ch, yb[1].stride = cw, yb[1].data = buf[cur] + ysz;
+    yb[2].width = cw, yb[2].height = ch, yb[2].stride = cw, yb[2].data = buf[cur] + ysz + csz;
+    if (th_encode_ycbcr_in(enc, yb)) {
+      fprintf(stderr, "th_encode_ycbcr_in failed\n");
+      return 1;
+    }
+    while ((rc = th_encode_packetout(enc, next == 0, &op)) > 0) {
+      if (thip_ogg_writer_packetin(ow, &op) || write_pages(ow, out)) {
+        fprintf(stderr, "write error\n");
+        return 1;
+      }
+    }
+    if (rc < 0) {
+      fprintf(stderr, "th_encode_packetout failed (%d)\n", rc);
+      return 1;
+    }
+    nframes++;
+    cur ^= 1;
+    have = next;
+  }
+  if (have < 0) {
+    fprintf(stderr, "broken YUV4MPEG2 input\n");
+    return 1;
+  }
+  thip_ogg_writer_flush(ow);
+  if (write_pages(ow, out)) return 1;
+  fprintf(stderr, "%d frames\n", nframes);
+  thip_ogg_writer_free(ow);
+  th_encode_free(enc);
+  free(buf[0]);
+  free(buf[1]);
+  if (out != stdout) fclose(out);
+  if (in != stdin) fclose(in);
+  return 0;
+}

@@ -12,7 +12,7 @@
  * oc_state_loop_filter_frag_rows.
  *
  * Not provided (out of scope): the telemetry requests, the legacy theora_* API,
- * th_granule_* helpers beyond th_granule_frame and th_granule_time, the encoder.
+ * th_granule_* helpers beyond th_granule_frame and th_granule_time.  The encoder (intra only) is theoraenc_hip.h.
  */
 #ifndef THEORADEC_HIP_H
 #define THEORADEC_HIP_H

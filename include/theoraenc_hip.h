@@ -1,0 +1,114 @@
+/* theoraenc_hip.h -- libtheora's encoder API (include/theora/theoraenc.h) for an INTRA-ONLY encoder whose block work runs on the
+ * MI355X: the same function names, signatures, TH_ENCCTL_* numbers and TH_E* return codes, so a program written against
+ * libtheoraenc that asks for nothing beyond a constant quality relinks against libtheora_hip.so.  The shared types (th_info,
+ * th_comment, th_ycbcr_buffer, ogg_packet) come from theoradec_hip.h.
+ *
+ * What it is not: every data packet is a key frame.  There is no mode decision, motion search or rate control, so bitrate
+ * mode (th_info.target_bitrate != 0: th_encode_alloc returns NULL), 2-pass, the rate flags and buffer, custom Huffman codes or
+ * quantisation parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every
+ * decoder plays it.
+ *
+ * The bitstream, stated so that a restatement reproduces the packets byte for byte (tests/enc_ref.py does):
+ *   - Setup header.  Loop-filter limits lflim[qi] = (31 * (63 - qi) + 31) / 63.  AC and DC scales fall geometrically,
+ *     acscale[qi] = round(400 * (10/400)^(qi/63)), dcscale[qi] = round(200 * (10/200)^(qi/63)).  Three base matrices, by
+ *     natural position (row r, column c): luma 16 + 3 (r + c) + (r c) / 4, chroma 18 + 5 (r + c), inter 16 + 2 (r + c) (the
+ *     inter set is written because the header needs one; it is never used).  Each (qti, pli) has ONE quant range of size 63
+ *     whose two ends are the same base matrix, so every quantiser step of spec 6.4.3 is max(qmin, min(scale[qi] bm / 100 * 4,
+ *     4096)): non-increasing in qi.  80 Huffman trees: for Huffman group hg (0..4) and table t (0..15), t = 4 a + b, the
+ *     Huffman code of 32 token weights with a sparsity s = {0.1, 0.3, 0.55, 0.8}[b] and a magnitude ratio q = {0.15, 0.35,
+ *     0.55, 0.75}[a] (thip_encode.hip, enc_token_weights); every token has a code, none longer than 31 bits.
+ *   - Frame.  An intra frame with one qi, qi = quality (TH_ENCCTL_SET_QUALITY changes it from the next frame); no block qi.
+ *   - Blocks.  In coded order, each 8x8 block is pixel - 128, oc_enc_fdct8x8, oc_enc_quantize with the intra table of (plane,
+ *     qi).  Pixels outside the picture region take the value of the nearest picture pixel (clamped coordinates) in every plane;
+ *     the chroma picture region is the one of spec 4.4.
+ *   - DC.  The value coded is the quantised DC minus the spec 7.8 predictor of the quantised DCs of the left, upper-left,
+ *     upper and upper-right neighbours, with its +-128 rule; a plane's first fragment predicts from 0.
+ *   - Tokens of a block, for each non-zero coefficient after g >= 0 zeros: a combined token if one fits (RUN_CAT1A/B/C for +-1
+ *     with 1 <= g <= 17, RUN_CAT2A/B for +-2, +-3 with 1 <= g <= 3); else, if g > 0, one zero-run token (SHORT_ZRL for g <= 8,
+ *     else ZRL) and then the smallest value token.  An EOB ends a block whose last non-zero coefficient lies before index 63.
+ *   - Token order is the decoder's (spec 7.7.3): index, then plane (Y, Cb, Cr), then coded order.  Maximal runs of consecutive
+ *     EOBs in that order become EOB-run tokens, across lists and planes, in pieces of at most 4095, each with the smallest token
+ *     that fits and placed in the list of its first EOB.
+ *   - Huffman tables.  The four table indices (DC luma, DC chroma, AC luma, AC chroma) are those that minimise the frame's bits;
+ *     on a tie the lower index.
+ *   - A value the largest value token cannot carry (|v| > 580) counts as an overflow and th_encode_packetout returns TH_EFAULT.
+ *     The minimum quantisers of spec 6.4.3 make this unreachable.
+ *   - Granule positions are those th_decode_packetin reports for the same packets (bitstream 3.2.1 numbering): key frame n,
+ *     counted from 0 with the duplicates, gets (n + 1) << shift, and the k-th duplicate after it ((n + 1) << shift) + k.
+ *
+ * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / TH_ENCCTL_THIP_GET_DEVICE):
+ * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
+ * extensions, YCBCR_IN_DEVICE and GET_DEVICE do.
+ */
+#ifndef THEORAENC_HIP_H
+#define THEORAENC_HIP_H
+#include "theoradec_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* theoraenc.h control codes (same numbers).  Honoured: */
+#define TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (4) /* buf = ogg_uint32_t (4 bytes): accepted, 1 written back */
+#define TH_ENCCTL_GET_SPLEVEL_MAX (12)             /* buf = int: 0 */
+#define TH_ENCCTL_SET_SPLEVEL (14)                 /* buf = int: 0 only, else TH_EINVAL */
+#define TH_ENCCTL_SET_DUP_COUNT (18)               /* buf = int: the next N packets after the next frame are duplicates;
+                                                      N < 1 << keyframe_granule_shift when the shift is not 0, else TH_EINVAL
+                                                      (a duplicate's granule counts it in the shift's bits) */
+#define TH_ENCCTL_SET_QUALITY (28)                 /* buf = int 0..63: from the next frame on */
+/* Known, and answered TH_EIMPL: */
+#define TH_ENCCTL_SET_HUFFMAN_CODES (0)
+#define TH_ENCCTL_SET_QUANT_PARAMS (2)
+#define TH_ENCCTL_SET_VP3_COMPATIBLE (10)
+#define TH_ENCCTL_GET_SPLEVEL (16)
+#define TH_ENCCTL_SET_RATE_FLAGS (20)
+#define TH_ENCCTL_SET_RATE_BUFFER (22)
+#define TH_ENCCTL_2PASS_OUT (24)
+#define TH_ENCCTL_2PASS_IN (26)
+#define TH_ENCCTL_SET_BITRATE (30)
+#define TH_ENCCTL_SET_COMPAT_CONFIG (32)
+
+/* Extension: buf = thip_enc_device_in.  What th_encode_ycbcr_in does, with plane pointers in device memory on the context's GPU
+   (TH_ENCCTL_THIP_GET_DEVICE) and of the same sizes (frame or picture).  `stream` is a hipStream_t (NULL: the null stream): the
+   encoder reads the planes only after the work queued on that stream so far, and the work queued on it afterwards runs only after
+   the encoder has read them -- so the caller may write the buffers again from that stream at once (thip_picture_out's
+   ordering, in the other direction).  The call does not wait on the host. */
+#define TH_ENCCTL_THIP_YCBCR_IN_DEVICE (0x7201)
+typedef struct thip_enc_device_in {
+  th_img_plane planes[3];
+  void *stream;
+} thip_enc_device_in;
+/* Extension: buf = int, receives the context's device index. */
+#define TH_ENCCTL_THIP_GET_DEVICE (0x7202)
+/* Extension: buf = thip_enc_frame_stats, describing the last packet th_encode_packetout returned. */
+#define TH_ENCCTL_THIP_GET_FRAME_STATS (0x7203)
+typedef struct thip_enc_frame_stats {
+  int64_t tokens;          /* tokens in stream order, every block's EOB on its own */
+  int64_t tokens_merged;   /* after the EOB runs are merged: what the packet holds */
+  int64_t bytes;           /* packet bytes (0 for a duplicate) */
+  int32_t huff[4];         /* table indices: DC luma, DC chroma, AC luma, AC chroma */
+  int32_t overflow;        /* coefficients no value token can carry (0 with valid tables) */
+  int32_t qi;
+} thip_enc_frame_stats;
+
+/* Extension: buf = double[2], receives for the last frame packet the device stage in milliseconds (HIP events around its work,
+   the launches' gaps included) and the host's part of th_encode_packetout (EOB runs, tables, bits). */
+#define TH_ENCCTL_THIP_GET_TIMES (0x7204)
+
+typedef struct th_enc_ctx th_enc_ctx;
+
+/* theoraenc.h:456-537 */
+th_enc_ctx *th_encode_alloc(const th_info *info);
+/* Extension: the same with the GPU chosen, as th_decode_alloc_on: device 0 .. thip_device_count()-1, or -1 for what
+   th_encode_alloc does (option "device", else the calling thread's current device at the first frame). */
+th_enc_ctx *th_encode_alloc_on(const th_info *info, int device);
+int th_encode_ctl(th_enc_ctx *enc, int req, void *buf, size_t buf_sz);
+int th_encode_flushheader(th_enc_ctx *enc, th_comment *comments, ogg_packet *op);
+int th_encode_ycbcr_in(th_enc_ctx *enc, th_ycbcr_buffer ycbcr);
+int th_encode_packetout(th_enc_ctx *enc, int last, ogg_packet *op);
+void th_encode_free(th_enc_ctx *enc);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -202,6 +202,17 @@ DEC_SYMBOLS = [
     ("th_comment_query_count", _I, [C.POINTER(ThComment), C.c_char_p]),
 ]
 
+# include/theoraenc_hip.h
+ENC_SYMBOLS = [
+    ("th_encode_alloc", _P, [C.POINTER(ThInfo)]),
+    ("th_encode_alloc_on", _P, [C.POINTER(ThInfo), _I]),
+    ("th_encode_ctl", _I, [_P, _I, _P, C.c_size_t]),
+    ("th_encode_flushheader", _I, [_P, C.POINTER(ThComment), C.POINTER(OggPacket)]),
+    ("th_encode_ycbcr_in", _I, [_P, C.POINTER(ThImgPlane)]),
+    ("th_encode_packetout", _I, [_P, _I, C.POINTER(OggPacket)]),
+    ("th_encode_free", None, [_P]),
+]
+
 # include/thip_ogg.h
 OGG_SYMBOLS = [
     ("thip_ogg_open_memory", _P, [_P, C.c_size_t]),
@@ -209,6 +220,11 @@ OGG_SYMBOLS = [
     ("thip_ogg_next_packet", _I, [_P, C.POINTER(OggPacket), C.POINTER(C.c_uint32)]),
     ("thip_ogg_stats", None, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     ("thip_ogg_close", None, [_P]),
+    ("thip_ogg_writer_new", _P, [C.c_uint32]),
+    ("thip_ogg_writer_packetin", _I, [_P, C.POINTER(OggPacket)]),
+    ("thip_ogg_writer_flush", _I, [_P]),
+    ("thip_ogg_writer_pages", _P, [_P, C.POINTER(C.c_size_t)]),
+    ("thip_ogg_writer_free", None, [_P]),
 ]
 
 _lib = None
@@ -229,7 +245,7 @@ def load():
             "%s not found: build it with `python -m theora_amd.build` (hipcc, gfx950). "
             "theora_amd has no CPU fallback." % SO_PATH)
     L = C.CDLL(SO_PATH)
-    for name, restype, argtypes in SYMBOLS + DEC_SYMBOLS + OGG_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + DEC_SYMBOLS + ENC_SYMBOLS + OGG_SYMBOLS:
         fn = getattr(L, name)   # AttributeError if the library does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libtheora_hip.so")
-SOURCES = ["thip_decode.hip", "thip_slots.hip", "thip_frontend.cpp", "thip_ogg.cpp"]
+SOURCES = ["thip_decode.hip", "thip_slots.hip", "thip_encode.hip", "thip_frontend.cpp", "thip_ogg.cpp"]
 # every header under csrc/ and include/ is a dependency (a list kept by hand went stale once: thip_fused.h was edited and the
 # library was not rebuilt)
 def _headers():

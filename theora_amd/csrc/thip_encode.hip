@@ -1,0 +1,747 @@
+// thip_encode.hip -- th_encode_* (include/theoraenc_hip.h): an intra-only Theora encoder.  The block work -- transform, quantiser,
+// DC prediction, tokens and their stream order -- is the device stage of thip_encode.h; the host merges the EOB runs, chooses the
+// Huffman tables and writes the bits.  The bitstream is stated in the header comment of theoraenc_hip.h.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+#include "../../include/theora_hip.h"
+#include "../../include/theoraenc_hip.h"
+#include "thip_device.h"
+#include "thip_encode.h"
+#include "thip_ctx.h"
+
+using namespace thip;
+
+namespace {
+
+#define ENC_TRY(expr)                                                                                                  \
+  do {                                                                                                                 \
+    hipError_t e_ = (expr);                                                                                            \
+    if (e_ != hipSuccess) {                                                                                            \
+      fprintf(stderr, "theora_hip: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__);        \
+      return TH_EFAULT;                                                                                                \
+    }                                                                                                                  \
+  } while (0)
+
+struct EncDeviceGuard {   // the context's device current for the calling thread while the object lives
+  int prev = -1, want;
+  explicit EncDeviceGuard(int device) : want(device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != want) (void)hipSetDevice(want);
+  }
+  ~EncDeviceGuard() {
+    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
+  }
+};
+
+// natural position of zig-zag index z
+const int kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// extra bits after each DCT token (spec Tables 7.33 / 7.38)
+const uint8_t kExtraBits[32] = {0, 0, 0, 2, 3, 4, 12, 3, 6, 0, 0, 0, 0, 1, 1, 1, 1, 2, 3, 4, 5, 6, 10, 1, 1, 1, 1, 1, 3, 4, 2, 3};
+
+int ilog(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+// MSB-first bit writer with a 64-bit accumulator
+struct BitW {
+  std::vector<uint8_t> *out;
+  uint64_t acc = 0;
+  int n = 0;   // bits in acc (< 8 after every put)
+  void put(uint32_t v, int nb) {
+    if (!nb) return;
+    acc = acc << nb | (v & (nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1)));
+    n += nb;
+    while (n >= 8) {
+      n -= 8;
+      out->push_back((uint8_t)(acc >> n));
+    }
+  }
+  void flush() {
+    if (n) out->push_back((uint8_t)(acc << (8 - n)));
+    n = 0;
+    acc = 0;
+  }
+};
+
+// ---- the setup header's contents (theoraenc_hip.h) -------------------------------------------------------------------
+struct EncSetup {
+  uint8_t lflims[64];
+  uint16_t acscale[64], dcscale[64];
+  uint8_t bms[3][64];           // luma intra, chroma intra, inter (natural order)
+  uint32_t code[80][32];        // Huffman codes (MSB first), lengths
+  uint8_t len[80][32];
+  std::vector<uint8_t> trees;   // the 80 trees as written (spec 6.4.4), a bit string packed MSB first ...
+  int64_t tree_bits;            // ... of this many bits
+};
+
+// the token weights of Huffman group hg, table t (theoraenc_hip.h): sparsity s, magnitude ratio q
+void enc_token_weights(int hg, int t, double w[32]) {
+  static const double kS[4] = {0.1, 0.3, 0.55, 0.8}, kQ[4] = {0.15, 0.35, 0.55, 0.75};
+  const double s = kS[t & 3], q = kQ[t >> 2], e = 0.3 + 0.6 * s;
+  for (int k = 0; k < 6; k++) w[k] = s * pow(e, k);                       // EOB runs 1, 2, 3, 4-7, 8-15, 16-31
+  w[6] = s * pow(e, hg == 0 ? 3 : 5);                                      // 32-4095
+  w[7] = (1 - s) * s * 0.5;                                                // SHORT_ZRL
+  w[8] = (1 - s) * s * s * 0.3;                                            // ZRL
+  w[9] = w[10] = (1 - s) * 0.5;                                            // +-1
+  w[11] = w[12] = (1 - s) * 0.5 * q;                                       // +-2
+  for (int k = 13; k <= 16; k++) w[k] = (1 - s) * pow(q, 2 + 0.5 * (k - 13));   // +-3 .. +-6
+  for (int k = 17; k <= 22; k++) w[k] = (1 - s) * pow(q, k - 13);          // 7-8, 9-12, 13-20, 21-36, 37-68, 69-580
+  for (int g = 1; g <= 5; g++) w[22 + g] = (1 - s) * 0.5 * pow(s, g);      // RUN_CAT1A
+  w[28] = (1 - s) * pow(s, 6) * 2;                                         // RUN_CAT1B
+  w[29] = (1 - s) * pow(s, 10) * 4;                                        // RUN_CAT1C
+  w[30] = (1 - s) * s * q;                                                 // RUN_CAT2A
+  w[31] = (1 - s) * s * s * q;                                             // RUN_CAT2B
+}
+
+// Huffman code of 32 weights: always merge the two lightest (ties: the lower node id); child 0 = the lighter
+void huffman(const double w[32], uint32_t code[32], uint8_t len[32], BitW &tree) {
+  struct Node { uint64_t w; int c0, c1; };
+  std::vector<Node> nodes;
+  std::vector<int> live;
+  for (int k = 0; k < 32; k++) {
+    nodes.push_back({1 + (uint64_t)(w[k] * (double)(1ull << 40)), -1, k});
+    live.push_back(k);
+  }
+  while (live.size() > 1) {
+    int a = -1, b = -1;
+    for (size_t i = 0; i < live.size(); i++) {
+      const int x = live[i];
+      if (a < 0 || nodes[x].w < nodes[a].w || (nodes[x].w == nodes[a].w && x < a)) { b = a; a = x; }
+      else if (b < 0 || nodes[x].w < nodes[b].w || (nodes[x].w == nodes[b].w && x < b)) b = x;
+    }
+    nodes.push_back({nodes[a].w + nodes[b].w, a, b});
+    std::vector<int> nl;
+    for (int x : live)
+      if (x != a && x != b) nl.push_back(x);
+    nl.push_back((int)nodes.size() - 1);
+    live.swap(nl);
+  }
+  // pre-order walk: 0 = internal node, 1 + token = leaf
+  struct Walk { static void go(const std::vector<Node> &nd, int x, uint32_t c, int l, uint32_t *code, uint8_t *len, BitW &t) {
+    if (nd[x].c0 < 0) {
+      t.put(1, 1);
+      t.put((uint32_t)nd[x].c1, 5);
+      code[nd[x].c1] = c;
+      len[nd[x].c1] = (uint8_t)l;
+      return;
+    }
+    t.put(0, 1);
+    go(nd, nd[x].c0, c << 1, l + 1, code, len, t);
+    go(nd, nd[x].c1, c << 1 | 1, l + 1, code, len, t);
+  } };
+  Walk::go(nodes, live[0], 0, 0, code, len, tree);
+}
+
+void enc_setup_init(EncSetup &s) {
+  for (int qi = 0; qi < 64; qi++) {
+    s.lflims[qi] = (uint8_t)((31 * (63 - qi) + 31) / 63);
+    s.acscale[qi] = (uint16_t)lround(400.0 * pow(10.0 / 400.0, qi / 63.0));
+    s.dcscale[qi] = (uint16_t)lround(200.0 * pow(10.0 / 200.0, qi / 63.0));
+  }
+  for (int r = 0; r < 8; r++)
+    for (int c = 0; c < 8; c++) {
+      s.bms[0][r * 8 + c] = (uint8_t)(16 + 3 * (r + c) + (r * c) / 4);
+      s.bms[1][r * 8 + c] = (uint8_t)(18 + 5 * (r + c));
+      s.bms[2][r * 8 + c] = (uint8_t)(16 + 2 * (r + c));
+    }
+  s.trees.clear();
+  BitW t{&s.trees};
+  for (int h = 0; h < 80; h++) {
+    double w[32];
+    enc_token_weights(h >> 4, h & 15, w);
+    huffman(w, s.code[h], s.len[h], t);
+  }
+  s.tree_bits = (int64_t)s.trees.size() * 8 + t.n;
+  t.flush();
+}
+
+// spec 6.4.3 for one quant range whose two ends are base matrix bm: the intra step of (pli, qi) at zig-zag index z
+uint16_t enc_qstep(const EncSetup &s, int pli, int qi, int z) {
+  const int ci = kZigZag[z], bm = s.bms[pli == 0 ? 0 : 1][ci];
+  const int qmin = ci == 0 ? 16 : 8, scale = ci == 0 ? s.dcscale[qi] : s.acscale[qi];
+  return (uint16_t)std::max(qmin, std::min((scale * bm / 100) * 4, 4096));
+}
+
+}  // namespace
+
+struct th_enc_ctx : thip_ctx_head {
+  int device_req, device = -1;
+  bool dev_ready = false;
+  int hdec, vdec;
+  int nh[3], nv[3], froff[3], nfrags;
+  int cx0[3], cy0[3], cw[3], ch[3];   // the picture region per plane (spec 4.4), rows from the top
+  std::vector<int32_t> coded_order;
+  EncSetup setup;
+  int qi;
+  int nheaders_out = 0;
+  std::vector<uint8_t> hdr;
+  int64_t packetno = 0;
+  // frames: the one queued on the device, duplicates to follow it, frame counters (3.2.1 granule numbering)
+  bool frame_pending = false, done = false;
+  int dup_next = 0, dups_left = 0;
+  int64_t cur = -1, key = -1;
+  int frame_qi = 0;
+  // device state
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_in = nullptr, ev_read = nullptr, ev_t0 = nullptr, ev_done = nullptr;
+  uint8_t *d_pix = nullptr, *h_pix = nullptr;   // host input: the three picture planes, packed
+  size_t pix_off[3], pix_bytes = 0;
+  int32_t *d_order = nullptr;
+  uint16_t *d_dequant = nullptr;                // [64 qi][3][64]
+  int16_t *d_levels = nullptr, *d_dcq = nullptr;
+  uint32_t *d_tok = nullptr, *d_cnt = nullptr, *d_base = nullptr, *d_small = nullptr, *d_out = nullptr;
+  uint64_t *d_mask = nullptr;
+  uint32_t *h_small = nullptr;                  // list lengths [3][64], overflow
+  uint32_t *h_tok = nullptr;
+  size_t h_tok_cap = 0;
+  int nchunks = 0;
+  // output
+  std::vector<uint8_t> pkt;
+  std::vector<uint32_t> merged;
+  thip_enc_frame_stats stats;
+  double device_ms = 0, host_ms = 0;
+};
+
+extern "C" {
+
+th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
+  if (!info) return nullptr;
+  const th_info &i = *info;
+  if (!i.frame_width || !i.frame_height || (i.frame_width & 15) || (i.frame_height & 15) || i.frame_width >= (1u << 20) ||
+      i.frame_height >= (1u << 20))
+    return nullptr;
+  if (!i.pic_width || !i.pic_height || i.pic_width > i.frame_width || i.pic_height > i.frame_height ||
+      i.pic_x > i.frame_width - i.pic_width || i.pic_y > i.frame_height - i.pic_height || i.pic_x > 255 ||
+      i.frame_height - i.pic_height - i.pic_y > 255)
+    return nullptr;
+  if ((int)i.pixel_fmt < 0 || (int)i.pixel_fmt >= TH_PF_NFORMATS || i.pixel_fmt == TH_PF_RSVD) return nullptr;
+  if (i.quality < 0 || i.quality > 63 || i.keyframe_granule_shift < 0 || i.keyframe_granule_shift > 31) return nullptr;
+  if (i.target_bitrate != 0) return nullptr;   // bitrate mode needs rate control
+  if (!i.fps_numerator || !i.fps_denominator || i.aspect_numerator >= (1u << 24) || i.aspect_denominator >= (1u << 24) ||
+      (int)i.colorspace < 0 || (int)i.colorspace >= TH_CS_NSPACES)
+    return nullptr;
+  th_enc_ctx *e = new (std::nothrow) th_enc_ctx();
+  if (!e) return nullptr;
+  e->info = i;
+  e->info.version_major = 3;
+  e->info.version_minor = 2;
+  e->info.version_subminor = 1;
+  e->granpos_bias = 1;
+  e->device_req = device;
+  e->qi = i.quality;
+  e->hdec = !(i.pixel_fmt & 1);
+  e->vdec = !(i.pixel_fmt & 2);
+  const int yh = (int)i.frame_width >> 3, yv = (int)i.frame_height >> 3;
+  int off = 0;
+  for (int p = 0; p < 3; p++) {
+    e->nh[p] = p ? (yh + e->hdec) >> e->hdec : yh;
+    e->nv[p] = p ? (yv + e->vdec) >> e->vdec : yv;
+    e->froff[p] = off;
+    off += e->nh[p] * e->nv[p];
+    const int hd = p ? e->hdec : 0, vd = p ? e->vdec : 0;
+    e->cx0[p] = (int)i.pic_x >> hd;
+    e->cy0[p] = (int)i.pic_y >> vd;
+    e->cw[p] = (((int)(i.pic_x + i.pic_width) + hd) >> hd) - e->cx0[p];
+    e->ch[p] = (((int)(i.pic_y + i.pic_height) + vd) >> vd) - e->cy0[p];
+  }
+  e->nfrags = off;
+  // coded order: super blocks of 4x4 fragments in raster order, the fragments of each along the Hilbert curve (spec 2.4)
+  static const int kHil[16][2] = {{0, 0}, {0, 1}, {1, 1}, {1, 0}, {2, 0}, {3, 0}, {3, 1}, {2, 1},
+                                  {2, 2}, {3, 2}, {3, 3}, {2, 3}, {1, 3}, {1, 2}, {0, 2}, {0, 3}};   // (row, column)
+  e->coded_order.reserve(e->nfrags);
+  for (int p = 0; p < 3; p++)
+    for (int sy = 0; sy < e->nv[p]; sy += 4)
+      for (int sx = 0; sx < e->nh[p]; sx += 4)
+        for (int k = 0; k < 16; k++) {
+          const int fy = sy + kHil[k][0], fx = sx + kHil[k][1];
+          if (fy < e->nv[p] && fx < e->nh[p]) e->coded_order.push_back(e->froff[p] + fy * e->nh[p] + fx);
+        }
+  e->nchunks = (e->nfrags + kEncChunk - 1) / kEncChunk;
+  enc_setup_init(e->setup);
+  memset(&e->stats, 0, sizeof(e->stats));
+  return e;
+}
+
+th_enc_ctx *th_encode_alloc(const th_info *info) { return th_encode_alloc_on(info, -1); }
+
+// frees whatever device state exists (also a partial one, after a failed enc_ensure_device) and forgets it
+static void enc_free_device(th_enc_ctx *e) {
+  if (e->device < 0) return;
+  EncDeviceGuard g(e->device);
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  void **dev[] = {(void **)&e->d_pix, (void **)&e->d_order, (void **)&e->d_dequant, (void **)&e->d_levels, (void **)&e->d_dcq,
+                  (void **)&e->d_tok, (void **)&e->d_cnt, (void **)&e->d_base, (void **)&e->d_small, (void **)&e->d_out,
+                  (void **)&e->d_mask};
+  for (void **p : dev) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok};
+  for (void **p : host) {
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+  }
+  e->h_tok_cap = 0;
+  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done}) {
+    if (*ev) (void)hipEventDestroy(*ev);
+    *ev = nullptr;
+  }
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  e->stream = nullptr;
+  e->dev_ready = false;
+}
+
+void th_encode_free(th_enc_ctx *e) {
+  if (!e) return;
+  enc_free_device(e);
+  delete e;
+}
+
+static int enc_alloc_device(th_enc_ctx *e);
+
+// everything on the device, at the first frame: worst-case buffers (kEncTokWords words a block)
+static int enc_ensure_device(th_enc_ctx *e) {
+  if (e->dev_ready) return 0;
+  int dev = e->device_req;
+  if (dev < 0) {
+    const int opt = thip_option("device");
+    if (opt == -2) {
+      static std::atomic<unsigned> next{0};
+      const int n = thip_device_count();
+      dev = n > 0 ? (int)(next.fetch_add(1) % (unsigned)n) : -1;
+    } else if (opt >= 0) {
+      dev = opt;
+    }
+    if (dev < 0) ENC_TRY(hipGetDevice(&dev));
+  }
+  e->device = dev;
+  const int rc = enc_alloc_device(e);
+  if (rc) {
+    enc_free_device(e);   // (a later frame tries again from nothing; nothing runs on a half-made context)
+    return rc;
+  }
+  e->dev_ready = true;
+  return 0;
+}
+
+// the allocations and uploads of enc_ensure_device, on e->device
+static int enc_alloc_device(th_enc_ctx *e) {
+  EncDeviceGuard g(e->device);
+  ENC_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  ENC_TRY(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
+  ENC_TRY(hipEventCreateWithFlags(&e->ev_read, hipEventDisableTiming));
+  ENC_TRY(hipEventCreate(&e->ev_t0));
+  ENC_TRY(hipEventCreate(&e->ev_done));
+  const size_t n = (size_t)e->nfrags;
+  size_t pb = 0;
+  for (int p = 0; p < 3; p++) {
+    e->pix_off[p] = pb;
+    pb += (size_t)e->cw[p] * e->ch[p];
+  }
+  e->pix_bytes = pb;
+  ENC_TRY(hipMalloc((void **)&e->d_pix, pb));
+  ENC_TRY(hipHostMalloc((void **)&e->h_pix, pb, hipHostMallocDefault));
+  ENC_TRY(hipMalloc((void **)&e->d_order, n * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_dequant, 64 * 3 * 64 * 2));
+  ENC_TRY(hipMalloc((void **)&e->d_levels, n * 64 * 2));
+  ENC_TRY(hipMalloc((void **)&e->d_dcq, n * 2));
+  ENC_TRY(hipMalloc((void **)&e->d_tok, n * kEncTokWords * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_out, n * kEncTokWords * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_mask, n * 8));
+  ENC_TRY(hipMalloc((void **)&e->d_cnt, (size_t)e->nchunks * 192 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_base, (size_t)e->nchunks * 64 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_small, 256 * 4));
+  ENC_TRY(hipHostMalloc((void **)&e->h_small, 256 * 4, hipHostMallocDefault));
+  std::vector<uint16_t> dq(64 * 3 * 64);
+  for (int qi = 0; qi < 64; qi++)
+    for (int p = 0; p < 3; p++)
+      for (int z = 0; z < 64; z++) dq[(qi * 3 + p) * 64 + z] = enc_qstep(e->setup, p, qi, z);
+  ENC_TRY(hipMemcpy(e->d_order, e->coded_order.data(), n * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(e->d_dequant, dq.data(), dq.size() * 2, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// the plane sizes a ycbcr buffer may have: the frame's (0) or the picture's (1); -1 neither
+static int enc_buffer_kind(const th_enc_ctx *e, const th_img_plane *y) {
+  for (int kind = 0; kind < 2; kind++) {
+    bool ok = true;
+    for (int p = 0; p < 3 && ok; p++) {
+      const int w = kind ? e->cw[p] : e->nh[p] * 8, h = kind ? e->ch[p] : e->nv[p] * 8;
+      ok = y[p].width == w && y[p].height == h && y[p].data != nullptr;
+    }
+    if (ok) return kind;
+  }
+  return -1;
+}
+
+// the four launches of a frame, reading the picture through `src` / `stride` (top-left pixel of the picture of each plane)
+static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int64_t stride[3]) {
+  EncPlanes g;
+  for (int p = 0; p < 3; p++) {
+    g.src[p] = src[p];
+    g.stride[p] = stride[p];
+    g.px0[p] = e->cx0[p];
+    g.py0[p] = e->cy0[p];
+    g.pw[p] = e->cw[p];
+    g.ph[p] = e->ch[p];
+    g.nh[p] = e->nh[p];
+    g.nv[p] = e->nv[p];
+    g.froff[p] = e->froff[p];
+  }
+  const int64_t n = e->nfrags;
+  e->frame_qi = e->qi;
+  ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
+  hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                     e->d_small + 192, e->d_order, g, e->d_dequant + (size_t)e->frame_qi * 192, n);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+  hipLaunchKernelGGL(k_enc_intra_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
+                     e->d_small + 192, e->d_levels, e->d_dcq, e->d_order, g, n);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_intra_scan, dim3(64), dim3(256), 0, e->stream, e->d_base, e->d_small, e->d_cnt, e->nchunks);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_intra_scatter, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_out, e->d_tok, e->d_mask,
+                     e->d_base, e->d_small, n);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_done, e->stream));
+  e->frame_pending = true;
+  e->dups_left = e->dup_next;
+  e->dup_next = 0;
+  return 0;
+}
+
+int th_encode_ycbcr_in(th_enc_ctx *e, th_ycbcr_buffer ycbcr) {
+  if (!e || !ycbcr) return TH_EFAULT;
+  if (e->done || e->frame_pending || e->dups_left) return TH_EINVAL;
+  const int kind = enc_buffer_kind(e, ycbcr);
+  if (kind < 0) return TH_EINVAL;
+  if (enc_ensure_device(e)) return TH_EFAULT;
+  EncDeviceGuard g(e->device);
+  // the previous frame's upload is complete (its packet is out), so the staging buffer is free
+  const uint8_t *src[3];
+  int64_t stride[3];
+  for (int p = 0; p < 3; p++) {
+    const uint8_t *in = ycbcr[p].data;
+    if (kind == 0) in += (int64_t)e->cy0[p] * ycbcr[p].stride + e->cx0[p];
+    uint8_t *dst = e->h_pix + e->pix_off[p];
+    for (int y = 0; y < e->ch[p]; y++) memcpy(dst + (size_t)y * e->cw[p], in + (int64_t)y * ycbcr[p].stride, (size_t)e->cw[p]);
+    src[p] = e->d_pix + e->pix_off[p];
+    stride[p] = e->cw[p];
+  }
+  ENC_TRY(hipMemcpyAsync(e->d_pix, e->h_pix, e->pix_bytes, hipMemcpyHostToDevice, e->stream));
+  return enc_queue_frame(e, src, stride);
+}
+
+static int enc_ycbcr_in_device(th_enc_ctx *e, const thip_enc_device_in *a) {
+  if (e->done || e->frame_pending || e->dups_left) return TH_EINVAL;
+  const int kind = enc_buffer_kind(e, a->planes);
+  if (kind < 0) return TH_EINVAL;
+  if (enc_ensure_device(e)) return TH_EFAULT;
+  EncDeviceGuard g(e->device);
+  const uint8_t *src[3];
+  int64_t stride[3];
+  for (int p = 0; p < 3; p++) {
+    src[p] = a->planes[p].data + (kind == 0 ? (int64_t)e->cy0[p] * a->planes[p].stride + e->cx0[p] : 0);
+    stride[p] = a->planes[p].stride;
+  }
+  hipStream_t cs = (hipStream_t)a->stream;
+  ENC_TRY(hipEventRecord(e->ev_in, cs));
+  ENC_TRY(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+  const int rc = enc_queue_frame(e, src, stride);
+  if (rc) return rc;
+  ENC_TRY(hipStreamWaitEvent(cs, e->ev_read, 0));
+  return 0;
+}
+
+static void enc_put_eob_run(std::vector<uint32_t> &m, uint32_t run) {   // token | extra << 5 (a 12-bit run is never 0 here)
+  uint32_t t, x;
+  if (run <= 3) { t = run - 1; x = 0; }
+  else if (run <= 7) { t = 3; x = run - 4; }
+  else if (run <= 15) { t = 4; x = run - 8; }
+  else if (run <= 31) { t = 5; x = run - 16; }
+  else { t = 6; x = run; }
+  m.push_back(t | x << 5);
+}
+
+static double enc_now() {
+  timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+// the packet of the frame queued on the device: EOB runs merged, tables chosen, bits written
+static int enc_finish_frame(th_enc_ctx *e) {
+  EncDeviceGuard g(e->device);
+  ENC_TRY(hipEventSynchronize(e->ev_done));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, e->ev_t0, e->ev_done) == hipSuccess) e->device_ms = ms;
+  const uint32_t *len = e->h_small;   // [3][64]
+  size_t total = 0;
+  for (int k = 0; k < 192; k++) total += len[k];
+  const uint32_t overflow = e->h_small[192];
+  if (total > (size_t)e->nfrags * kEncTokWords) return TH_EFAULT;
+  if (total > e->h_tok_cap) {
+    if (e->h_tok) (void)hipHostFree(e->h_tok);
+    e->h_tok = nullptr;
+    e->h_tok_cap = 0;
+    const size_t cap = std::max(total + total / 4, (size_t)4096);
+    ENC_TRY(hipHostMalloc((void **)&e->h_tok, cap * 4, hipHostMallocDefault));
+    e->h_tok_cap = cap;
+  }
+  if (total) {
+    ENC_TRY(hipMemcpyAsync(e->h_tok, e->d_out, total * 4, hipMemcpyDeviceToHost, e->stream));
+    ENC_TRY(hipStreamSynchronize(e->stream));
+  }
+  const double t0 = enc_now();
+  // stream order: index z, then plane p; merged lists in the same order, counted per (z, p)
+  std::vector<uint32_t> &m = e->merged;
+  m.clear();
+  m.reserve(total);
+  uint32_t mlen[64][3] = {};
+  uint32_t run = 0;
+  int rz = 0, rp = 0;
+  size_t at = 0;
+  for (int z = 0; z < 64; z++)
+    for (int p = 0; p < 3; p++) {
+      const uint32_t nl = len[p * 64 + z];
+      for (uint32_t k = 0; k < nl; k++) {
+        const uint32_t w = e->h_tok[at++];
+        if ((w & 31) == 0) {   // a block's EOB
+          if (!run) { rz = z; rp = p; }
+          if (++run == 4095) {
+            enc_put_eob_run(m, run);
+            mlen[rz][rp]++;
+            run = 0;
+          }
+          continue;
+        }
+        if (run) {
+          enc_put_eob_run(m, run);
+          mlen[rz][rp]++;
+          run = 0;
+        }
+        m.push_back(w & 0xFFFFu);
+        mlen[z][p]++;
+      }
+    }
+  if (run) {
+    enc_put_eob_run(m, run);
+    mlen[rz][rp]++;
+  }
+  // per Huffman group and luma / chroma: token counts; the table of least bits for each of the four choices
+  uint32_t hist[5][2][32] = {};
+  at = 0;
+  for (int z = 0; z < 64; z++) {
+    const int hg = z == 0 ? 0 : z <= 5 ? 1 : z <= 14 ? 2 : z <= 27 ? 3 : 4;
+    for (int p = 0; p < 3; p++)
+      for (uint32_t k = 0; k < mlen[z][p]; k++) hist[hg][p > 0][m[at++] & 31]++;
+  }
+  int hti[4];   // DC luma, DC chroma, AC luma, AC chroma
+  for (int c = 0; c < 4; c++) {
+    const int ac = c >> 1, ch = c & 1;
+    uint64_t best = ~0ull;
+    for (int t = 0; t < 16; t++) {
+      uint64_t bits = 0;
+      for (int hg = ac ? 1 : 0; hg < (ac ? 5 : 1); hg++)
+        for (int tok = 0; tok < 32; tok++) bits += (uint64_t)hist[hg][ch][tok] * e->setup.len[16 * hg + t][tok];
+      if (bits < best) {
+        best = bits;
+        hti[c] = t;
+      }
+    }
+  }
+  e->pkt.clear();
+  e->pkt.reserve(total * 2 + 16);
+  BitW bw{&e->pkt};
+  bw.put(0, 1);                          // data packet
+  bw.put(0, 1);                          // intra frame
+  bw.put((uint32_t)e->frame_qi, 6);      // one qi
+  bw.put(0, 1);
+  bw.put(0, 3);                          // reserved
+  at = 0;
+  for (int z = 0; z < 64; z++) {
+    if (z < 2) {
+      bw.put((uint32_t)hti[2 * z], 4);
+      bw.put((uint32_t)hti[2 * z + 1], 4);
+    }
+    const int hg = z == 0 ? 0 : z <= 5 ? 1 : z <= 14 ? 2 : z <= 27 ? 3 : 4;
+    for (int p = 0; p < 3; p++) {
+      const int h = 16 * hg + hti[(z ? 2 : 0) + (p > 0)];
+      for (uint32_t k = 0; k < mlen[z][p]; k++) {
+        const uint32_t w = m[at++], tok = w & 31;
+        bw.put(e->setup.code[h][tok], e->setup.len[h][tok]);
+        bw.put(w >> 5, kExtraBits[tok]);
+      }
+    }
+  }
+  bw.flush();
+  e->host_ms = (enc_now() - t0) * 1e3;
+  e->stats.tokens = (int64_t)total;
+  e->stats.tokens_merged = (int64_t)m.size();
+  e->stats.bytes = (int64_t)e->pkt.size();
+  for (int c = 0; c < 4; c++) e->stats.huff[c] = hti[c];
+  e->stats.overflow = (int32_t)overflow;
+  e->stats.qi = e->frame_qi;
+  return overflow ? TH_EFAULT : 0;
+}
+
+int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
+  if (!e || !op) return TH_EFAULT;
+  if (e->done) return 0;
+  const int shift = e->info.keyframe_granule_shift;
+  if (e->frame_pending) {
+    e->frame_pending = false;
+    const int rc = enc_finish_frame(e);
+    if (rc) return rc;
+    e->key = ++e->cur;
+    op->packet = e->pkt.data();
+    op->bytes = (long)e->pkt.size();
+  } else if (e->dups_left > 0) {
+    e->dups_left--;
+    ++e->cur;
+    e->pkt.clear();
+    op->packet = e->pkt.data();
+    op->bytes = 0;
+    memset(&e->stats, 0, sizeof(e->stats));
+    e->stats.qi = e->frame_qi;
+    e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
+  } else {
+    return 0;
+  }
+  op->b_o_s = 0;
+  op->e_o_s = last && e->dups_left == 0 ? 1 : 0;
+  op->granulepos = ((e->key + e->granpos_bias) << shift) + (e->cur - e->key);
+  op->packetno = e->packetno++;
+  if (op->e_o_s) e->done = true;
+  return 1;
+}
+
+int th_encode_flushheader(th_enc_ctx *e, th_comment *tc, ogg_packet *op) {
+  if (!e || !tc || !op) return TH_EFAULT;
+  if (e->nheaders_out >= 3) return 0;
+  const th_info &i = e->info;
+  e->hdr.clear();
+  BitW bw{&e->hdr};
+  bw.put(0x80u + (uint32_t)e->nheaders_out, 8);
+  for (const char *c = "theora"; *c; c++) bw.put((uint8_t)*c, 8);
+  if (e->nheaders_out == 0) {   // spec 6.2
+    const uint32_t f[][2] = {{3, 8}, {2, 8}, {1, 8}, {i.frame_width >> 4, 16}, {i.frame_height >> 4, 16}, {i.pic_width, 24},
+                             {i.pic_height, 24}, {i.pic_x, 8}, {i.frame_height - i.pic_height - i.pic_y, 8},
+                             {i.fps_numerator, 32}, {i.fps_denominator, 32}, {i.aspect_numerator, 24},
+                             {i.aspect_denominator, 24}, {(uint32_t)i.colorspace, 8}, {0, 24}, {(uint32_t)i.quality, 6},
+                             {(uint32_t)i.keyframe_granule_shift, 5}, {(uint32_t)i.pixel_fmt, 2}, {0, 3}};
+    for (const auto &x : f) bw.put(x[0], (int)x[1]);
+  } else if (e->nheaders_out == 1) {   // spec 6.3
+    auto le32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) bw.put((v >> (8 * k)) & 0xFF, 8); };
+    auto bytes = [&](const char *s, uint32_t n) { for (uint32_t k = 0; k < n; k++) bw.put((uint8_t)s[k], 8); };
+    const char *vendor = th_version_string();
+    le32((uint32_t)strlen(vendor));
+    bytes(vendor, (uint32_t)strlen(vendor));
+    const int nc = tc->comments > 0 && tc->user_comments ? tc->comments : 0;
+    le32((uint32_t)nc);
+    for (int k = 0; k < nc; k++) {
+      const char *s = tc->user_comments[k] ? tc->user_comments[k] : "";
+      const uint32_t n = tc->comment_lengths ? (uint32_t)tc->comment_lengths[k] : (uint32_t)strlen(s);
+      le32(n);
+      bytes(s, n);
+    }
+  } else {   // spec 6.4
+    const EncSetup &s = e->setup;
+    int nb = 0;
+    for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(s.lflims[qi]));
+    bw.put((uint32_t)nb, 3);
+    for (int qi = 0; qi < 64; qi++) bw.put(s.lflims[qi], nb);
+    for (const uint16_t *sc : {s.acscale, s.dcscale}) {
+      nb = 1;
+      for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(sc[qi]));
+      bw.put((uint32_t)nb - 1, 4);
+      for (int qi = 0; qi < 64; qi++) bw.put(sc[qi], nb);
+    }
+    bw.put(3 - 1, 9);   // three base matrices
+    for (int b = 0; b < 3; b++)
+      for (int c = 0; c < 64; c++) bw.put(s.bms[b][c], 8);
+    for (int qti = 0; qti < 2; qti++)
+      for (int pli = 0; pli < 3; pli++) {
+        if (qti > 0 || pli > 0) bw.put(1, 1);   // NEWQR
+        const uint32_t bmi = qti ? 2 : pli ? 1 : 0;
+        bw.put(bmi, ilog(3 - 1));
+        bw.put(63 - 1, ilog(62));               // one range of size 63 ...
+        bw.put(bmi, ilog(3 - 1));               // ... ending in the same matrix
+      }
+    for (int64_t k = 0; k < s.tree_bits; k++) bw.put((s.trees[k >> 3] >> (7 - (k & 7))) & 1, 1);
+  }
+  bw.flush();
+  op->packet = e->hdr.data();
+  op->bytes = (long)e->hdr.size();
+  op->b_o_s = e->nheaders_out == 0;
+  op->e_o_s = 0;
+  op->granulepos = 0;
+  op->packetno = e->packetno++;
+  e->nheaders_out++;
+  return 1;
+}
+
+int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
+  if (!e) return TH_EFAULT;
+  switch (req) {
+    case TH_ENCCTL_SET_QUALITY: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      const int q = *(const int *)buf;
+      if (q < 0 || q > 63) return TH_EINVAL;
+      e->qi = q;
+      return 0;
+    }
+    case TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE:
+      if (!buf || buf_sz != sizeof(uint32_t)) return TH_EINVAL;
+      *(uint32_t *)buf = 1;   // every frame is a key frame
+      return 0;
+    case TH_ENCCTL_SET_DUP_COUNT: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      const int n = *(const int *)buf;
+      // the k-th duplicate's granule is ((key + 1) << shift) + k: k must stay below 1 << shift, or it spills into the key frame
+      // field (with shift 0 the sum itself counts the frames)
+      const int shift = e->info.keyframe_granule_shift;
+      if (n < 0 || (shift > 0 && shift < 31 && n >= (1 << shift))) return TH_EINVAL;
+      e->dup_next = n;
+      return 0;
+    }
+    case TH_ENCCTL_GET_SPLEVEL_MAX:
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      *(int *)buf = 0;
+      return 0;
+    case TH_ENCCTL_SET_SPLEVEL:
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      return *(const int *)buf == 0 ? 0 : TH_EINVAL;
+    case TH_ENCCTL_THIP_YCBCR_IN_DEVICE:
+      if (!buf || buf_sz != sizeof(thip_enc_device_in)) return TH_EINVAL;
+      return enc_ycbcr_in_device(e, (const thip_enc_device_in *)buf);
+    case TH_ENCCTL_THIP_GET_DEVICE:
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (!e->dev_ready && enc_ensure_device(e)) return TH_EFAULT;
+      *(int *)buf = e->device;
+      return 0;
+    case TH_ENCCTL_THIP_GET_FRAME_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_frame_stats)) return TH_EINVAL;
+      *(thip_enc_frame_stats *)buf = e->stats;
+      return 0;
+    case TH_ENCCTL_THIP_GET_TIMES:
+      if (!buf || buf_sz != 2 * sizeof(double)) return TH_EINVAL;
+      ((double *)buf)[0] = e->device_ms;
+      ((double *)buf)[1] = e->host_ms;
+      return 0;
+    default: return TH_EIMPL;
+  }
+}
+
+}  // extern "C"

@@ -28,6 +28,7 @@
 
 #include "../../include/theora_hip.h"
 #include "../../include/theoradec_hip.h"
+#include "thip_ctx.h"
 // The one backend entry point the front end reaches only on request (TH_DECCTL_THIP_PICTURE_OUT): referenced weakly, so that this
 // translation unit still links on its own against a backend that provides just the decoding slots (the front end's native test
 // drivers stub those); inside libtheora_hip.so the definition in thip_decode.hip is always there.
@@ -243,8 +244,8 @@ static void fe_lookahead_free(th_dec_ctx *d);
 static int fe_prefetch(th_dec_ctx *d, const ogg_packet *op);
 }
 
-struct th_dec_ctx {
-  th_info info;
+// (thip_ctx_head: th_info and the granule bias first, as in th_enc_ctx, so that th_granule_frame / _time take either)
+struct th_dec_ctx : thip_ctx_head {
   FeProf prof;
   th_setup_info setup;
   thip_state *hip;
@@ -273,7 +274,6 @@ struct th_dec_ctx {
   uint32_t eob_carry[3][64];
   int qis[3], nqis, frame_type;
   int64_t keyframe_num, curframe_num, granpos;
-  int granpos_bias;
   bool have_frame;
   bool device_dc;   // DC un-prediction left to the backend (THIP_FE_DEVICE_DC=1, or TH_DECCTL_THIP_SET_DEVICE_DC)
   // out-of-loop post-processing (TH_DECCTL_SET_PPLEVEL; decode.c:1203-1325)
@@ -1705,8 +1705,8 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
   }
 }
 
-int64_t th_granule_frame(void *encdec, int64_t granpos) {
-  th_dec_ctx *d = (th_dec_ctx *)encdec;
+int64_t th_granule_frame(void *encdec, int64_t granpos) {   // a th_dec_ctx or a th_enc_ctx: both begin with thip_ctx_head
+  const thip_ctx_head *d = (const thip_ctx_head *)encdec;
   if (!d || granpos < 0) return -1;
   const int shift = d->info.keyframe_granule_shift;
   const int64_t iframe = granpos >> shift;
@@ -1715,7 +1715,7 @@ int64_t th_granule_frame(void *encdec, int64_t granpos) {
 }
 
 double th_granule_time(void *encdec, int64_t granpos) {
-  th_dec_ctx *d = (th_dec_ctx *)encdec;
+  const thip_ctx_head *d = (const thip_ctx_head *)encdec;
   if (!d || granpos < 0 || !d->info.fps_numerator) return -1;
   return (double)(th_granule_frame(encdec, granpos) + 1) * ((double)d->info.fps_denominator / (double)d->info.fps_numerator);
 }

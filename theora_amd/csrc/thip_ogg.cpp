@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <map>
+#include <new>
 #include <vector>
 
 #include "../../include/thip_ogg.h"
@@ -211,5 +212,102 @@ void thip_ogg_stats(const thip_ogg_reader *r, int64_t *bad_pages, int64_t *gaps)
 }
 
 void thip_ogg_close(thip_ogg_reader *r) { delete r; }
+
+}  // extern "C"
+
+// ---- writer (RFC 3533 section 6) -----------------------------------------------------------------------------------------------
+struct thip_ogg_writer {
+  uint32_t serial, seq = 0;
+  std::vector<uint8_t> out;    // completed pages
+  size_t taken = 0;            // bytes of `out` handed out by the last thip_ogg_writer_pages
+  std::vector<uint8_t> body, lace;
+  int64_t granule = -1;        // of the last packet that ends on the page being filled
+  bool continued = false;      // the page being filled starts inside a packet
+  bool eos_packet = false;     // it holds the end of the packet that ends the stream
+  bool ended = false;
+};
+
+namespace {
+void put_le(std::vector<uint8_t> &v, uint64_t x, int n) {
+  for (int i = 0; i < n; i++) v.push_back((uint8_t)(x >> (8 * i)));
+}
+// the page being filled goes out (if it has any segment)
+void writer_page(thip_ogg_writer *w) {
+  if (w->lace.empty()) return;
+  const size_t start = w->out.size();
+  std::vector<uint8_t> &o = w->out;
+  o.insert(o.end(), {'O', 'g', 'g', 'S', 0});
+  o.push_back((uint8_t)((w->continued ? 1 : 0) | (w->seq == 0 ? 2 : 0) | (w->eos_packet ? 4 : 0)));
+  put_le(o, (uint64_t)w->granule, 8);
+  put_le(o, w->serial, 4);
+  put_le(o, w->seq++, 4);
+  put_le(o, 0, 4);   // checksum, below
+  o.push_back((uint8_t)w->lace.size());
+  o.insert(o.end(), w->lace.begin(), w->lace.end());
+  o.insert(o.end(), w->body.begin(), w->body.end());
+  const uint32_t crc = crc_update(0, o.data() + start, o.size() - start);
+  for (int i = 0; i < 4; i++) o[start + 22 + i] = (uint8_t)(crc >> (8 * i));
+  w->lace.clear();
+  w->body.clear();
+  w->granule = -1;
+  w->continued = false;
+  w->eos_packet = false;
+}
+}  // namespace
+
+extern "C" {
+
+thip_ogg_writer *thip_ogg_writer_new(uint32_t serialno) {
+  if (!g_crc_ready) crc_init();
+  thip_ogg_writer *w = new (std::nothrow) thip_ogg_writer();
+  if (w) w->serial = serialno;
+  return w;
+}
+
+int thip_ogg_writer_packetin(thip_ogg_writer *w, const ogg_packet *op) {
+  if (!w || !op || op->bytes < 0 || (op->bytes && !op->packet) || w->ended) return -1;
+  if (w->seq == 0 && w->lace.empty() && !op->b_o_s) return -1;   // the first packet opens the stream
+  if (op->b_o_s) writer_page(w);
+  const uint8_t *p = op->packet;
+  const size_t n = (size_t)op->bytes;
+  size_t off = 0;
+  for (;;) {   // lacing: 255-byte segments continue the packet, a shorter one (possibly 0) ends it
+    if (w->lace.size() == 255) {
+      const bool inside = off > 0;
+      writer_page(w);
+      w->continued = inside;
+    }
+    const size_t seg = n - off < 255 ? n - off : 255;
+    w->lace.push_back((uint8_t)seg);
+    w->body.insert(w->body.end(), p + off, p + off + seg);
+    off += seg;
+    if (seg < 255) break;
+  }
+  w->granule = op->granulepos;
+  if (op->e_o_s) {
+    w->eos_packet = true;
+    w->ended = true;
+    writer_page(w);
+  } else if (op->b_o_s || w->body.size() >= 4096) {
+    writer_page(w);
+  }
+  return 0;
+}
+
+int thip_ogg_writer_flush(thip_ogg_writer *w) {
+  if (!w) return -1;
+  writer_page(w);
+  return 0;
+}
+
+const uint8_t *thip_ogg_writer_pages(thip_ogg_writer *w, size_t *size) {
+  if (!w || !size) return nullptr;
+  w->out.erase(w->out.begin(), w->out.begin() + (ptrdiff_t)w->taken);
+  w->taken = w->out.size();
+  *size = w->out.size();
+  return w->out.data();
+}
+
+void thip_ogg_writer_free(thip_ogg_writer *w) { delete w; }
 
 }  // extern "C"

@@ -1,0 +1,189 @@
+"""Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): an intra-only Theora encoder whose
+block work runs on the GPU."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import OggPacket, ThComment, ThImgPlane, ThInfo, TheoraHipError
+
+TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE = 4
+TH_ENCCTL_GET_SPLEVEL_MAX = 12
+TH_ENCCTL_SET_SPLEVEL = 14
+TH_ENCCTL_SET_DUP_COUNT = 18
+TH_ENCCTL_SET_QUALITY = 28
+TH_ENCCTL_THIP_YCBCR_IN_DEVICE = 0x7201
+TH_ENCCTL_THIP_GET_DEVICE = 0x7202
+TH_ENCCTL_THIP_GET_FRAME_STATS = 0x7203
+TH_ENCCTL_THIP_GET_TIMES = 0x7204
+
+
+class DeviceIn(C.Structure):
+    """thip_enc_device_in (include/theoraenc_hip.h)."""
+    _fields_ = [("planes", ThImgPlane * 3), ("stream", C.c_void_p)]
+
+
+class FrameStats(C.Structure):
+    """thip_enc_frame_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("tokens", C.c_int64), ("tokens_merged", C.c_int64), ("bytes", C.c_int64), ("huff", C.c_int32 * 4),
+                ("overflow", C.c_int32), ("qi", C.c_int32)]
+
+
+def make_info(w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, aspect=(1, 1), colorspace=0, bitrate=0):
+    """A th_info for frame w x h (multiples of 16); pic = (x, y, width, height) with y from the top, default the whole frame."""
+    L = _lib.load()
+    info = ThInfo()
+    L.th_info_init(C.byref(info))
+    x, y, pw, ph = pic if pic is not None else (0, 0, w, h)
+    info.frame_width, info.frame_height = w, h
+    info.pic_x, info.pic_y, info.pic_width, info.pic_height = x, y, pw, ph
+    info.fps_numerator, info.fps_denominator = fps
+    info.aspect_numerator, info.aspect_denominator = aspect
+    info.colorspace, info.pixel_fmt = colorspace, fmt
+    info.target_bitrate, info.quality, info.keyframe_granule_shift = bitrate, quality, kfgshift
+    return info
+
+
+def _copy_packet(op):
+    return C.string_at(op.packet, op.bytes) if op.bytes else b""
+
+
+class Encoder:
+    """th_encode_alloc -> th_encode_flushheader x3 -> {th_encode_ycbcr_in, th_encode_packetout}*."""
+
+    def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=()):
+        L = self._L = _lib.load()
+        self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
+        self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
+                     else L.th_encode_alloc_on(C.byref(self.info), int(device)))
+        if not self._enc:
+            raise TheoraHipError("th_encode_alloc failed")
+        self.comments = list(comments)
+        self.hdec, self.vdec = int(not (fmt & 1)), int(not (fmt & 2))
+
+    def ctl(self, req, value=None, ctype=C.c_int):
+        v = ctype(0 if value is None else value)
+        rc = self._L.th_encode_ctl(self._enc, req, C.byref(v), C.sizeof(v))
+        return rc, v.value
+
+    def header_packets(self):
+        """The three header packets (bytes), with this library's vendor string and self.comments."""
+        tc = ThComment()
+        self._L.th_comment_init(C.byref(tc))
+        for c in self.comments:
+            self._L.th_comment_add(C.byref(tc), c.encode() if isinstance(c, str) else c)
+        out, op = [], OggPacket()
+        try:
+            while True:
+                rc = self._L.th_encode_flushheader(self._enc, C.byref(tc), C.byref(op))
+                if rc < 0:
+                    raise TheoraHipError("th_encode_flushheader returned %d" % rc)
+                if rc == 0:
+                    return out
+                out.append(_copy_packet(op))
+        finally:
+            self._L.th_comment_clear(C.byref(tc))
+
+    def encode(self, planes, stream=None):
+        """Queues one frame.  planes: three uint8 numpy arrays, or three uint8 torch CUDA tensors on the encoder's device (read
+        through TH_ENCCTL_THIP_YCBCR_IN_DEVICE, ordered on `stream`, default torch's current stream); each of the frame's size
+        or of the picture's, rows top first."""
+        if not isinstance(planes[0], np.ndarray):
+            return self._encode_device(planes, stream)
+        buf = (ThImgPlane * 3)()
+        keep = []
+        for p in range(3):
+            a = np.ascontiguousarray(planes[p], dtype=np.uint8)
+            keep.append(a)
+            buf[p].width, buf[p].height, buf[p].stride = a.shape[1], a.shape[0], a.strides[0]
+            buf[p].data = a.ctypes.data_as(C.POINTER(C.c_ubyte))
+        rc = self._L.th_encode_ycbcr_in(self._enc, buf)
+        if rc < 0:
+            raise TheoraHipError("th_encode_ycbcr_in returned %d" % rc)
+
+    def _encode_device(self, planes, stream):
+        import torch
+        a = DeviceIn()
+        for p in range(3):
+            t = planes[p]
+            assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1
+            a.planes[p].width, a.planes[p].height, a.planes[p].stride = t.shape[1], t.shape[0], t.stride(0)
+            a.planes[p].data = C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_ubyte))
+        s = stream if stream is not None else torch.cuda.current_stream(planes[0].device)
+        a.stream = s.cuda_stream
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_YCBCR_IN_DEVICE, C.byref(a), C.sizeof(a))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_YCBCR_IN_DEVICE returned %d" % rc)
+
+    def packetout(self, last=False):
+        """The next packet as (bytes, granulepos, packetno, e_o_s), or None when there is none."""
+        op = OggPacket()
+        rc = self._L.th_encode_packetout(self._enc, int(bool(last)), C.byref(op))
+        if rc < 0:
+            raise TheoraHipError("th_encode_packetout returned %d" % rc)
+        if rc == 0:
+            return None
+        return _copy_packet(op), int(op.granulepos), int(op.packetno), int(op.e_o_s)
+
+    def stats(self):
+        """TH_ENCCTL_THIP_GET_FRAME_STATS of the last packet, as a dict."""
+        s = FrameStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_FRAME_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_FRAME_STATS returned %d" % rc)
+        return dict(tokens=s.tokens, tokens_merged=s.tokens_merged, bytes=s.bytes, huff=list(s.huff), overflow=s.overflow,
+                    qi=s.qi)
+
+    def times(self):
+        """TH_ENCCTL_THIP_GET_TIMES: (device stage ms, host packing ms) of the last frame packet."""
+        t = (C.c_double * 2)()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_TIMES, t, C.sizeof(t))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_TIMES returned %d" % rc)
+        return t[0], t[1]
+
+    def device(self):
+        rc, v = self.ctl(TH_ENCCTL_THIP_GET_DEVICE)
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_DEVICE returned %d" % rc)
+        return v
+
+    def close(self):
+        if getattr(self, "_enc", None):
+            self._L.th_encode_free(self._enc)
+            self._enc = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ogg_stream(header_packets, data_packets, serialno=0x7E0):
+    """One Ogg logical stream (bytes) through the library's writer (include/thip_ogg.h): the headers, a flush after the setup
+    header, then data_packets as (payload, granulepos, e_o_s)."""
+    L = _lib.load()
+    w = L.thip_ogg_writer_new(serialno)
+    if not w:
+        raise TheoraHipError("thip_ogg_writer_new failed")
+    out = []
+    try:
+        allp = [(p, 0, 0) for p in header_packets] + list(data_packets)
+        for k, (payload, gp, eos) in enumerate(allp):
+            buf = (C.c_ubyte * max(len(payload), 1)).from_buffer_copy(bytes(payload) if payload else b"\0")
+            op = OggPacket(C.cast(buf, C.c_void_p), len(payload), int(k == 0), int(eos), gp, k)
+            if L.thip_ogg_writer_packetin(w, C.byref(op)) != 0:
+                raise TheoraHipError("thip_ogg_writer_packetin(packet %d) failed" % k)
+            if k == len(header_packets) - 1:
+                L.thip_ogg_writer_flush(w)
+            n = C.c_size_t()
+            p = L.thip_ogg_writer_pages(w, C.byref(n))
+            out.append(C.string_at(p, n.value) if n.value else b"")
+        L.thip_ogg_writer_flush(w)
+        n = C.c_size_t()
+        p = L.thip_ogg_writer_pages(w, C.byref(n))
+        out.append(C.string_at(p, n.value) if n.value else b"")
+    finally:
+        L.thip_ogg_writer_free(w)
+    return b"".join(out)

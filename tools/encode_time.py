@@ -1,0 +1,74 @@
+"""The intra encoder (th_encode_*) per frame: the device stage (HIP events around its four launches and read-backs,
+TH_ENCCTL_THIP_GET_TIMES), the host's part of th_encode_packetout (EOB runs, tables, bits), packet bytes and Y/Cb/Cr PSNR of the
+decoded picture -- 720p, 1080p and 4K at 4:2:0, the seeded natural image of tests/enc_ref.py, quality 16 and 48.  Kernel times
+come from a separate `rocprofv3 --kernel-trace --stats -- python tools/encode_time.py --frames 8` run.
+
+  python tools/encode_time.py [--frames 20] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SIZES = {"720p": (1280, 720, None), "1080p": (1920, 1088, (0, 0, 1920, 1080)), "4k": (3840, 2160, None)}
+
+
+def psnr(a, b):
+    mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
+    return 99.0 if mse == 0 else 10 * np.log10(255.0 ** 2 / mse)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--json")
+    args = ap.parse_args()
+    from tests import enc_ref
+    from theora_amd.decoder import Decoder
+    from theora_amd.encoder import Encoder
+    rows = []
+    for name, (w, h, pic) in SIZES.items():
+        p = pic or (0, 0, w, h)
+        frame = enc_ref.picture("natural", w, h, 0, p, picture_size=True, seed=5)
+        for q in (16, 48):
+            e = Encoder(w, h, 0, q, pic=pic)
+            hdr = e.header_packets()
+            dev, host, wall = [], [], []
+            for f in range(args.frames + 3):
+                t0 = time.perf_counter()
+                e.encode(frame)
+                pkt = e.packetout()[0]
+                t1 = time.perf_counter()
+                d, hm = e.times()
+                if f >= 3:
+                    dev.append(d)
+                    host.append(hm)
+                    wall.append((t1 - t0) * 1e3)
+            st = e.stats()
+            e.close()
+            dec = Decoder(hdr)
+            dec.packetin(pkt)
+            got = dec.ycbcr_out()
+            dec.close()
+            x0, y0, pw, ph = p
+            ps = []
+            for pl in range(3):
+                cx, cy, cw, ch = enc_ref.chroma_region(p, 0, pl)
+                ps.append(round(psnr(got[pl][cy:cy + ch, cx:cx + cw], frame[pl]), 2))
+            r = dict(size=name, quality=q, device_ms=round(float(np.median(dev)), 4), host_ms=round(float(np.median(host)), 4),
+                     call_ms=round(float(np.median(wall)), 4), bytes=len(pkt), tokens=st["tokens"],
+                     tokens_merged=st["tokens_merged"], psnr=ps)
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if args.json:
+        json.dump(rows, open(args.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
