@@ -55,15 +55,16 @@ static int read_frame(FILE *in, unsigned char *buf, size_t bytes) {
 }
 
 int main(int argc, char **argv) {
-  int quality = 48;
+  int quality = 48, kf = 0;
   const char *in_path = NULL, *out_path = NULL;
   for (int i = 1; i < argc; i++) {
     if (strcmp(argv[i], "-q") == 0 && i + 1 < argc) quality = atoi(argv[++i]);
     else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) out_path = argv[++i];
+    else if (strcmp(argv[i], "-k") == 0 && i + 1 < argc) kf = atoi(argv[++i]);
     else in_path = argv[i];
   }
   if (!in_path) {
-    fprintf(stderr, "usage: %s [-q quality] [-o out.ogv] in.y4m\n", argv[0]);
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames] [-o out.ogv] in.y4m\n", argv[0]);
     return 1;
   }
   FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
@@ -100,6 +101,15 @@ int main(int argc, char **argv) {
   if (!enc) {
     fprintf(stderr, "th_encode_alloc refused the parameters\n");
     return 1;
+  }
+  if (kf > 0) {   /* inter frames, a key frame every kf frames (clamped to 1 << keyframe_granule_shift) */
+    int on = 1;
+    uint32_t k = (uint32_t)kf;
+    if (th_encode_ctl(enc, TH_ENCCTL_THIP_SET_INTER_FRAMES, &on, sizeof(on)) ||
+        th_encode_ctl(enc, TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE, &k, sizeof(k))) {
+      fprintf(stderr, "inter frames refused\n");
+      return 1;
+    }
   }
   FILE *out = out_path ? fopen(out_path, "wb") : stdout;
   if (!out) {

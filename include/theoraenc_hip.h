@@ -1,9 +1,9 @@
-/* theoraenc_hip.h -- libtheora's encoder API (include/theora/theoraenc.h) for an INTRA-ONLY encoder whose block work runs on the
- * MI355X: the same function names, signatures, TH_ENCCTL_* numbers and TH_E* return codes, so a program written against
+/* theoraenc_hip.h -- libtheora's encoder API (include/theora/theoraenc.h) for an encoder whose block work runs on the MI355X,
+ * intra-only by default, with motion-compensated inter frames on request (TH_ENCCTL_THIP_SET_INTER_FRAMES, "Inter frames" below): the same function names, signatures, TH_ENCCTL_* numbers and TH_E* return codes, so a program written against
  * libtheoraenc that asks for nothing beyond a constant quality relinks against libtheora_hip.so.  The shared types (th_info,
  * th_comment, th_ycbcr_buffer, ogg_packet) come from theoradec_hip.h.
  *
- * What it is not: every data packet is a key frame.  There is no mode decision, motion search or rate control, so bitrate
+ * What it is not, by default: every data packet is a key frame.  There is no mode decision, motion search or rate control, so bitrate
  * mode (th_info.target_bitrate != 0: th_encode_alloc returns NULL), 2-pass, the rate flags and buffer, custom Huffman codes or
  * quantisation parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every
  * decoder plays it.
@@ -11,12 +11,13 @@
  * The bitstream, stated so that a restatement reproduces the packets byte for byte (tests/enc_ref.py does):
  *   - Setup header.  Loop-filter limits lflim[qi] = (31 * (63 - qi) + 31) / 63.  AC and DC scales fall geometrically,
  *     acscale[qi] = round(400 * (10/400)^(qi/63)), dcscale[qi] = round(200 * (10/200)^(qi/63)).  Three base matrices, by
- *     natural position (row r, column c): luma 16 + 3 (r + c) + (r c) / 4, chroma 18 + 5 (r + c), inter 16 + 2 (r + c) (the
- *     inter set is written because the header needs one; it is never used).  Each (qti, pli) has ONE quant range of size 63
+ *     natural position (row r, column c): luma 16 + 3 (r + c) + (r c) / 4, chroma 18 + 5 (r + c), inter 16 + 2 (r + c) (used by
+ *     inter frames only).  Each (qti, pli) has ONE quant range of size 63
  *     whose two ends are the same base matrix, so every quantiser step of spec 6.4.3 is max(qmin, min(scale[qi] bm / 100 * 4,
  *     4096)): non-increasing in qi.  80 Huffman trees: for Huffman group hg (0..4) and table t (0..15), t = 4 a + b, the
  *     Huffman code of 32 token weights with a sparsity s = {0.1, 0.3, 0.55, 0.8}[b] and a magnitude ratio q = {0.15, 0.35,
- *     0.55, 0.75}[a] (thip_encode.hip, enc_token_weights); every token has a code, none longer than 31 bits.
+ *     0.55, 0.75}[a] (thip_encode.hip, enc_token_weights); every token has a code, none longer than 31 bits.  (The header is the same with
+ *     inter frames on; the inter matrices are then used.)
  *   - Frame.  An intra frame with one qi, qi = quality (TH_ENCCTL_SET_QUALITY changes it from the next frame); no block qi.
  *   - Blocks.  In coded order, each 8x8 block is pixel - 128, oc_enc_fdct8x8, oc_enc_quantize with the intra table of (plane,
  *     qi).  Pixels outside the picture region take the value of the nearest picture pixel (clamped coordinates) in every plane;
@@ -36,6 +37,36 @@
  *   - Granule positions are those th_decode_packetin reports for the same packets (bitstream 3.2.1 numbering): key frame n,
  *     counted from 0 with the duplicates, gets (n + 1) << shift, and the k-th duplicate after it ((n + 1) << shift) + k.
  *
+ * Inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES), stated likewise (tests/enc_inter_ref.py restates them).  Coordinates are the
+ * bitstream's (rows from the bottom), vectors in half pixels of luma.
+ *   - Key frames are the frames above.  Frame n (counted from 0 with the duplicates) is a key frame when it is the first, when its
+ *     offset from the last key frame is >= the interval N (TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE), or when that offset plus its
+ *     own duplicates would reach 1 << keyframe_granule_shift; otherwise an inter frame.  Granules: frame n after key frame m gets
+ *     ((m + 1) << shift) + (n - m).
+ *   - Reference: PREV only, the decoder's picture of the previous frame (loop filter included; the encoder keeps it by decoding its
+ *     own packets).  One qi, = quality; INTRA blocks use the intra tables, all others the inter tables of that qi (spec 6.4.3).
+ *   - Motion search, per macro block on luma (16 x 16), reads of PREV clamped to the plane as the decoder's:
+ *     full pel: every (dx, dy) in [-15, 15]^2 by SAD; the least of the key (SAD, 2 (|dx| + |dy|), (dy + 15) 31 + dx + 15).
+ *     half pel: the eight vectors 2 (dx, dy) + (hx, hy), hx, hy in {-1, 0, 1}, predicted as the decoder predicts (the truncating
+ *     average of the two reads of spec 7.9.4); with the centre, the least of (SAD, |mvx| + |mvy|, 3 (hy + 1) + hx + 1) gives Smv
+ *     and (mvx, mvy).  S0 = the SAD of vector 0, SI = the sum over the four luma blocks of the SAD against the block's mean
+ *     (sum + 32) >> 6.
+ *   - Mode (per macro block, L = the inter luma step at zig-zag index 1): MV if Smv + L < S0, else NOMV with S = S0 (S = Smv for
+ *     MV); then INTRA if SI + 4 L < S.  In coded order over the macro blocks that have a coded luma block, an MV vector equal to
+ *     the last one written or reused becomes INTER_MV_LAST, equal to the one before INTER_MV_LAST2, else INTER_MV (spec 7.5.2's
+ *     bookkeeping).  Chroma uses the macro block's vector as the decoder derives it (4:2:0, 4:2:2: quarter pels on a decimated axis).
+ *   - Blocks: pixel minus prediction (128 for INTRA; PREV through the vector otherwise), clamped source as for key frames,
+ *     oc_enc_fdct8x8, oc_enc_quantize.  Every block of an INTRA or MV macro block is coded; a block of a NOMV macro block is coded
+ *     when a level is not zero, else uncoded (copied from PREV).  A macro block with no coded luma block writes no mode (it is
+ *     INTER_NOMV to the decoder).  A frame with no coded block is a zero-byte packet (the decoder's duplicate).
+ *   - DC: spec 7.8 with reference classes: a neighbour counts when coded and of the same class (intra, or PREV); with none, the
+ *     last coded quantised DC of that class before the block in the plane's raster order (0 if none).
+ *   - Header: 0, 1 (inter), qi, 0.  Coded flags (spec 7.3): partially coded super blocks, then of the others the fully coded
+ *     ones (long runs), then the block flags of the partial ones (short runs; never longer than 30).  Modes (7.4): the scheme of
+ *     fewest bits (scheme 0 costs 24 more; ties: the lower scheme); scheme 0's alphabet by falling frequency, ties to the lower mode.
+ *     Vectors (7.5): scheme 1 (six bits a component) when it costs fewer bits than the VLC, else the VLC.  Tokens as for key frames,
+ *     over the coded blocks only.
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
  * extensions, YCBCR_IN_DEVICE and GET_DEVICE do.
@@ -49,7 +80,8 @@ extern "C" {
 #endif
 
 /* theoraenc.h control codes (same numbers).  Honoured: */
-#define TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (4) /* buf = ogg_uint32_t (4 bytes): accepted, 1 written back */
+#define TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (4) /* buf = ogg_uint32_t (4 bytes): accepted, 1 written back (with inter
+                                                      frames on: TH_ENCCTL_THIP_SET_INTER_FRAMES) */
 #define TH_ENCCTL_GET_SPLEVEL_MAX (12)             /* buf = int: 0 */
 #define TH_ENCCTL_SET_SPLEVEL (14)                 /* buf = int: 0 only, else TH_EINVAL */
 #define TH_ENCCTL_SET_DUP_COUNT (18)               /* buf = int: the next N packets after the next frame are duplicates;
@@ -94,6 +126,24 @@ typedef struct thip_enc_frame_stats {
 /* Extension: buf = double[2], receives for the last frame packet the device stage in milliseconds (HIP events around its work,
    the launches' gaps included) and the host's part of th_encode_packetout (EOB runs, tables, bits). */
 #define TH_ENCCTL_THIP_GET_TIMES (0x7204)
+
+/* Extension: buf = int 0 / 1, before the first frame only (else TH_EINVAL): inter frames ("Inter frames" above).  Off by default.
+   While on, TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE is honoured as libtheoraenc honours it: the interval is clamped to
+   [1, 1 << keyframe_granule_shift] and written back (default 1 << keyframe_granule_shift; with shift 0 every frame is a key frame). */
+#define TH_ENCCTL_THIP_SET_INTER_FRAMES (0x7205)
+/* Extension: buf = thip_enc_inter_stats, describing the last packet th_encode_packetout returned (with inter frames off too). */
+#define TH_ENCCTL_THIP_GET_INTER_STATS (0x7206)
+typedef struct thip_enc_inter_stats {
+  int32_t key;           /* 1 key frame, 0 inter frame or duplicate */
+  int32_t modes[5];      /* macro blocks per mode as the decoder sees them: INTER_NOMV, INTRA, INTER_MV, INTER_MV_LAST,
+                            INTER_MV_LAST2 (a key frame: all INTRA; a duplicate or a frame with no coded block: all 0) */
+  int32_t coded[3];      /* coded blocks per plane */
+  int32_t mode_scheme;   /* 0..7, or -1 when none was written */
+  int32_t mv_scheme;     /* 0 VLC, 1 six bits, or -1 when none was written */
+} thip_enc_inter_stats;
+/* Extension: buf = th_ycbcr_buffer of host planes of the FRAME's size, rows top first: receives the encoder's reconstruction of the
+   last frame -- the next frame's reference.  Waits for the device.  TH_EINVAL with inter frames off or before the first packet. */
+#define TH_ENCCTL_THIP_GET_RECON (0x7207)
 
 typedef struct th_enc_ctx th_enc_ctx;
 

@@ -107,6 +107,86 @@ __device__ __forceinline__ bool enc_value_token(int v, int &tok, int &extra) {
   return true;
 }
 
+// The DC predictor and the tokens of k_enc_intra_tok as functions, for k_enc_inter_tok / k_enc_inter_dc (thip_encode_inter.h).
+// k_enc_intra_tok keeps its inline copy: calling these from it changed its resource line.
+//
+// spec 7.8 (decode.c:1450-1485) from the neighbour mask (1 left, 2 upper-left, 4 upper, 8 upper-right) and the neighbours' quantised
+// DCs; mask 0 gives 0 (the caller's own fallback)
+__device__ __forceinline__ int enc_dc_pred(int msk, int l, int ul, int u, int ur) {
+  int pred = 0;
+  switch (msk) {
+    case 1: case 3: pred = l; break;
+    case 2: pred = ul; break;
+    case 4: case 6: case 12: pred = u; break;
+    case 5: pred = (l + u) / 2; break;
+    case 8: pred = ur; break;
+    case 9: case 11: case 13: pred = (75 * l + 53 * ur) / 128; break;
+    case 10: pred = (ul + ur) / 2; break;
+    case 14: pred = (3 * (ul + ur) + 10 * u) / 16; break;
+    case 7: case 15:
+      pred = (29 * (l + u) - 26 * ul) / 32;
+      if (abs(pred - u) > 128) pred = u;
+      else if (abs(pred - l) > 128) pred = l;
+      else if (abs(pred - ul) > 128) pred = ul;
+      break;
+    default: break;
+  }
+  return pred;
+}
+
+// the tokens of one block (zig-zag levels lv, its DC residual dc, plane p) as words at out, the indices at which they start in m,
+// counted per (plane, index) in s_cnt; returns the number of overflows
+__device__ __forceinline__ int enc_block_tokens(uint32_t *out, uint64_t &mask_out, uint32_t *s_cnt, const int16_t *lv, int dc, int p) {
+  // which levels are non-zero (the DC: its residual), then the tokens walk the non-zero ones in zig-zag order
+  const int4 *src = reinterpret_cast<const int4 *>(lv);
+  uint64_t nzm = 0;
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    const int4 w = src[r];
+    const int w4[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      nzm |= (uint64_t)((w4[q] & 0xFFFF) != 0) << (r * 8 + 2 * q);
+      nzm |= (uint64_t)((w4[q] >> 16) != 0) << (r * 8 + 2 * q + 1);
+    }
+  }
+  nzm = (nzm & ~1ull) | (uint64_t)(dc != 0);
+  const uint32_t plane = (uint32_t)p << 22;
+  uint64_t m = 0;
+  int cnt = 0, ovf = 0, next = 0;   // next: the index after the last non-zero level written
+  auto emit = [&](int t, int extra, int z) {
+    out[cnt++] = (uint32_t)t | (uint32_t)extra << 5 | (uint32_t)z << 16 | plane;
+    m |= 1ull << z;
+    atomicAdd(&s_cnt[p * 64 + z], 1u);
+  };
+  while (nzm) {
+    const int z = __builtin_ctzll(nzm);
+    nzm &= nzm - 1;
+    const int a = z ? (int)lv[z] : dc, gap = z - next;
+    const int aa = abs(a), s = a < 0 ? 1 : 0;
+    if (aa == 1 && gap >= 1 && gap <= 17) {   // RUN_CAT1A / B / C
+      if (gap <= 5) emit(22 + gap, s, next);
+      else if (gap <= 9) emit(28, s << 2 | (gap - 6), next);
+      else emit(29, s << 3 | (gap - 10), next);
+    } else if ((aa == 2 || aa == 3) && gap >= 1 && gap <= 3) {   // RUN_CAT2A / B
+      if (gap == 1) emit(30, s << 1 | (aa - 2), next);
+      else emit(31, s << 2 | (aa - 2) << 1 | (gap - 2), next);
+    } else {
+      if (gap > 0) {
+        if (gap <= 8) emit(7, gap - 1, next);   // SHORT_ZRL
+        else emit(8, gap - 1, next);            // ZRL
+      }
+      int t, extra;
+      ovf += enc_value_token(a, t, extra) ? 0 : 1;
+      emit(t, extra, z);
+    }
+    next = z + 1;
+  }
+  if (next < 64) emit(0, 0, next);   // EOB (a run of one; the host merges them)
+  mask_out = m;
+  return ovf;
+}
+
 // tok [n][kEncTokWords], mask [n], chunk_cnt [gridDim.x][3][64], overflow: one word
 __global__ __launch_bounds__(256) void k_enc_intra_tok(uint32_t *tok, uint64_t *mask, uint32_t *chunk_cnt, uint32_t *overflow,
                                                        const int16_t *levels, const int16_t *dcq, const int32_t *coded_order,

@@ -1,6 +1,12 @@
-// thip_encode.hip -- th_encode_* (include/theoraenc_hip.h): an intra-only Theora encoder.  The block work -- transform, quantiser,
-// DC prediction, tokens and their stream order -- is the device stage of thip_encode.h; the host merges the EOB runs, chooses the
-// Huffman tables and writes the bits.  The bitstream is stated in the header comment of theoraenc_hip.h.
+// thip_encode.hip -- th_encode_* (include/theoraenc_hip.h): a Theora encoder, intra-only by default, with motion-compensated inter
+// frames on request (TH_ENCCTL_THIP_SET_INTER_FRAMES).  The block work -- motion search, transform, quantiser, DC prediction, tokens
+// and their stream order -- is the device stage of thip_encode.h and thip_encode_inter.h; the host merges the EOB runs, chooses the
+// Huffman tables, the mode and vector codes and writes the bits.  The bitstream is stated in the header comment of theoraenc_hip.h.
+//
+// The reference of an inter frame is the encoder's own reconstruction of the previous frame, made by a th_decode_* context of this
+// library fed with every packet the encoder returns (loop filter included): the encoder's reference is then the decoder's picture by
+// construction, bit for bit, and the decoder's kernels do the work (dequantisation, iDCT, prediction, the uncoded copies, the loop
+// filter).  The price is a host round trip between frames: the packet must exist before the next frame's search can start.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -16,7 +22,7 @@
 #include "../../include/theora_hip.h"
 #include "../../include/theoraenc_hip.h"
 #include "thip_device.h"
-#include "thip_encode.h"
+#include "thip_encode_inter.h"
 #include "thip_ctx.h"
 
 using namespace thip;
@@ -171,6 +177,73 @@ uint16_t enc_qstep(const EncSetup &s, int pli, int qi, int z) {
   const int qmin = ci == 0 ? 16 : 8, scale = ci == 0 ? s.dcscale[qi] : s.acscale[qi];
   return (uint16_t)std::max(qmin, std::min((scale * bm / 100) * 4, 4096));
 }
+// ... and the inter step (every plane uses the inter base matrix)
+uint16_t enc_qstep_inter(const EncSetup &s, int qi, int z) {
+  const int ci = kZigZag[z], bm = s.bms[2][ci];
+  const int qmin = ci == 0 ? 32 : 16, scale = ci == 0 ? s.dcscale[qi] : s.acscale[qi];
+  return (uint16_t)std::max(qmin, std::min((scale * bm / 100) * 4, 4096));
+}
+
+// spec 7.2.1 (long: runs up to 4129, a new bit after a run of 4129) and 7.2.2 (short: runs up to 30, the bit always flips; the
+// block flags of partially coded super blocks never hold a longer run, since each such super block has a block of either value)
+void enc_put_runs(BitW &bw, const std::vector<uint8_t> &bits, bool lng) {
+  struct Code { uint32_t code; int len, start, nb; };
+  static const Code kLong[7] = {{0, 1, 1, 0}, {2, 2, 2, 1}, {6, 3, 4, 1}, {14, 4, 6, 2}, {30, 5, 10, 3}, {62, 6, 18, 4},
+                                {63, 6, 34, 12}};
+  static const Code kShort[6] = {{0, 1, 1, 1}, {2, 2, 3, 1}, {6, 3, 5, 1}, {14, 4, 7, 2}, {30, 5, 11, 2}, {31, 5, 15, 4}};
+  const size_t n = bits.size(), maxrun = lng ? 4129 : 30;
+  if (!n) return;
+  int cur = bits[0];
+  bw.put((uint32_t)cur, 1);
+  size_t i = 0;
+  while (i < n) {
+    size_t j = i;
+    while (j < n && bits[j] == cur && j - i < maxrun) j++;
+    const int run = (int)(j - i);
+    for (const Code &c : lng ? std::vector<Code>(kLong, kLong + 7) : std::vector<Code>(kShort, kShort + 6))
+      if (run < c.start + (1 << c.nb)) {
+        bw.put(c.code, c.len);
+        bw.put((uint32_t)(run - c.start), c.nb);
+        break;
+      }
+    i = j;
+    if (i >= n) break;
+    if (lng && run == 4129) {
+      cur = bits[i];
+      bw.put((uint32_t)cur, 1);
+    } else {
+      cur ^= 1;
+    }
+  }
+}
+
+// spec 7.5.1: bits of one vector component in scheme 0 (VLC), and the component written in scheme mvs
+int enc_mv_vlc_bits(int v) {
+  const int a = abs(v);
+  return a <= 1 ? 3 : a <= 3 ? 4 : a <= 7 ? 6 : a <= 15 ? 7 : 8;
+}
+void enc_put_mv(BitW &bw, int v, int mvs) {
+  const int a = abs(v), sg = v < 0;
+  if (mvs) {
+    bw.put((uint32_t)a, 5);
+    bw.put((uint32_t)sg, 1);
+  } else if (a == 0) {
+    bw.put(0, 3);
+  } else if (a == 1) {
+    bw.put(sg ? 2 : 1, 3);
+  } else {
+    if (a <= 3) bw.put(a == 2 ? 3 : 4, 3);
+    else if (a <= 7) { bw.put(5, 3); bw.put((uint32_t)(a - 4), 2); }
+    else if (a <= 15) { bw.put(6, 3); bw.put((uint32_t)(a - 8), 3); }
+    else { bw.put(7, 3); bw.put((uint32_t)(a - 16), 4); }
+    bw.put((uint32_t)sg, 1);
+  }
+}
+
+// spec 7.4: the mode alphabets of schemes 1..6 (code index -> mode)
+const int kModeAlphabets[6][8] = {{3, 4, 2, 0, 1, 5, 6, 7}, {3, 4, 0, 2, 1, 5, 6, 7}, {3, 2, 4, 0, 1, 5, 6, 7},
+                                  {3, 2, 0, 4, 1, 5, 6, 7}, {0, 3, 4, 2, 1, 5, 6, 7}, {0, 5, 3, 4, 2, 1, 6, 7}};
+enum { kModeNomv = 0, kModeIntra = 1, kModeMv = 2, kModeMvLast = 3, kModeMvLast2 = 4 };
 
 }  // namespace
 
@@ -205,6 +278,19 @@ struct th_enc_ctx : thip_ctx_head {
   uint32_t *h_tok = nullptr;
   size_t h_tok_cap = 0;
   int nchunks = 0;
+  // inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES)
+  bool inter = false, frame_key = true;
+  int64_t kf_interval = 1;
+  int nmbx = 0, nmbs = 0;
+  std::vector<int32_t> sb_len;     // fragments of each super block (all planes) in coded order
+  std::vector<int32_t> mb_order;   // macro blocks (raster index, rows from the bottom) in coded order
+  uint32_t *d_mb = nullptr, *d_dclast = nullptr, *h_mb = nullptr;
+  uint8_t *d_cmap = nullptr, *h_cmap = nullptr;
+  int16_t *d_dcr = nullptr;
+  uint16_t *d_dqi = nullptr;       // [64 qi][intra, inter][3][64]
+  th_dec_ctx *dec = nullptr;       // the reconstruction: a decoder of the encoder's own packets
+  bool have_recon = false;
+  thip_enc_inter_stats istats;
   // output
   std::vector<uint8_t> pkt;
   std::vector<uint32_t> merged;
@@ -261,14 +347,28 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   e->coded_order.reserve(e->nfrags);
   for (int p = 0; p < 3; p++)
     for (int sy = 0; sy < e->nv[p]; sy += 4)
-      for (int sx = 0; sx < e->nh[p]; sx += 4)
+      for (int sx = 0; sx < e->nh[p]; sx += 4) {
+        const size_t at = e->coded_order.size();
         for (int k = 0; k < 16; k++) {
           const int fy = sy + kHil[k][0], fx = sx + kHil[k][1];
           if (fy < e->nv[p] && fx < e->nh[p]) e->coded_order.push_back(e->froff[p] + fy * e->nh[p] + fx);
         }
+        e->sb_len.push_back((int32_t)(e->coded_order.size() - at));
+      }
+  // macro blocks in coded order: luma super blocks in raster order, in each the four along the same curve (spec 2.4)
+  e->nmbx = yh >> 1;
+  e->nmbs = e->nmbx * (yv >> 1);
+  for (int sy = 0; sy < yv; sy += 4)
+    for (int sx = 0; sx < yh; sx += 4)
+      for (int k = 0; k < 4; k++) {
+        const int y = sy + 2 * (k == 1 || k == 2), x = sx + 2 * (k >= 2);
+        if (y < yv && x < yh) e->mb_order.push_back((y >> 1) * e->nmbx + (x >> 1));
+      }
   e->nchunks = (e->nfrags + kEncChunk - 1) / kEncChunk;
   enc_setup_init(e->setup);
   memset(&e->stats, 0, sizeof(e->stats));
+  memset(&e->istats, 0, sizeof(e->istats));
+  e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
 }
 
@@ -279,14 +379,18 @@ static void enc_free_device(th_enc_ctx *e) {
   if (e->device < 0) return;
   EncDeviceGuard g(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
+  if (e->dec) th_decode_free(e->dec);
+  e->dec = nullptr;
+  e->have_recon = false;
   void **dev[] = {(void **)&e->d_pix, (void **)&e->d_order, (void **)&e->d_dequant, (void **)&e->d_levels, (void **)&e->d_dcq,
                   (void **)&e->d_tok, (void **)&e->d_cnt, (void **)&e->d_base, (void **)&e->d_small, (void **)&e->d_out,
-                  (void **)&e->d_mask};
+                  (void **)&e->d_mask, (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr,
+                  (void **)&e->d_dqi};
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok};
+  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap};
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -368,6 +472,20 @@ static int enc_alloc_device(th_enc_ctx *e) {
       for (int z = 0; z < 64; z++) dq[(qi * 3 + p) * 64 + z] = enc_qstep(e->setup, p, qi, z);
   ENC_TRY(hipMemcpy(e->d_order, e->coded_order.data(), n * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_dequant, dq.data(), dq.size() * 2, hipMemcpyHostToDevice));
+  if (!e->inter) return 0;   // (nothing more exists with inter frames off)
+  ENC_TRY(hipMalloc((void **)&e->d_mb, (size_t)e->nmbs * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_dclast, (size_t)e->nchunks * 2 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_cmap, n));
+  ENC_TRY(hipMalloc((void **)&e->d_dcr, n * 2));
+  ENC_TRY(hipMalloc((void **)&e->d_dqi, 64 * 6 * 64 * 2));
+  ENC_TRY(hipHostMalloc((void **)&e->h_mb, (size_t)e->nmbs * 4, hipHostMallocDefault));
+  ENC_TRY(hipHostMalloc((void **)&e->h_cmap, n, hipHostMallocDefault));
+  std::vector<uint16_t> dqi(64 * 6 * 64);
+  for (int qi = 0; qi < 64; qi++)
+    for (int t = 0; t < 6; t++)
+      for (int z = 0; z < 64; z++)
+        dqi[(qi * 6 + t) * 64 + z] = t < 3 ? enc_qstep(e->setup, t, qi, z) : enc_qstep_inter(e->setup, qi, z);
+  ENC_TRY(hipMemcpy(e->d_dqi, dqi.data(), dqi.size() * 2, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -382,6 +500,54 @@ static int enc_buffer_kind(const th_enc_ctx *e, const th_img_plane *y) {
     if (ok) return kind;
   }
   return -1;
+}
+
+// the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
+static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
+  thip_state *st = thip_dec_backend(e->dec);
+  const int prev = st ? thip_state_ref_idx(st, THIP_FRAME_PREV) : -1;
+  if (prev < 0) return TH_EFAULT;
+  thip_plane_geom geom[3];
+  if (thip_state_get_geom(st, geom, nullptr, nullptr)) return TH_EFAULT;
+  const uint8_t *base = thip_state_frame_ptr(st, prev);
+  EncRef R;
+  for (int p = 0; p < 3; p++) {
+    R.plane[p] = base + geom[p].plane_off;
+    R.stride[p] = geom[p].stride;
+    R.w[p] = geom[p].width;
+    R.h[p] = geom[p].height;
+  }
+  R.hdec = e->hdec;
+  R.vdec = e->vdec;
+  const int64_t n = e->nfrags;
+  const int lambda = enc_qstep_inter(e->setup, e->frame_qi, 1);
+  ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
+  ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 2 * 4, e->stream));
+  hipLaunchKernelGGL(k_enc_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb, g, R, e->nmbx, lambda);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq, e->d_cmap,
+                     e->d_dclast, e->d_small + 192, e->d_order, g, R, e->d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+  hipLaunchKernelGGL(k_enc_inter_dc, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast,
+                     g, n);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_inter_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
+                     e->d_small + 192, e->d_levels, e->d_dcr, e->d_cmap, e->d_order, g, n);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_intra_scan, dim3(64), dim3(256), 0, e->stream, e->d_base, e->d_small, e->d_cnt, e->nchunks);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_intra_scatter, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_out, e->d_tok, e->d_mask,
+                     e->d_base, e->d_small, n);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_done, e->stream));
+  e->frame_pending = true;
+  e->dups_left = e->dup_next;
+  e->dup_next = 0;
+  return 0;
 }
 
 // the four launches of a frame, reading the picture through `src` / `stride` (top-left pixel of the picture of each plane)
@@ -400,6 +566,10 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   }
   const int64_t n = e->nfrags;
   e->frame_qi = e->qi;
+  // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
+  const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
+  e->frame_key = !e->inter || e->key < 0 || off >= e->kf_interval || off + e->dup_next >= full;
+  if (!e->frame_key) return enc_queue_inter(e, g);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
                      e->d_small + 192, e->d_order, g, e->d_dequant + (size_t)e->frame_qi * 192, n);
@@ -478,6 +648,100 @@ static double enc_now() {
   timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+// spec 7.3-7.5 of an inter frame: coded flags, macro-block modes, vectors (from h_cmap, h_mb)
+static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
+  // 7.3: super blocks partially coded; of the others, fully coded; the block flags of the partial ones
+  std::vector<uint8_t> sbp, sbf, blk;
+  size_t at = 0;
+  for (int32_t len : e->sb_len) {
+    int nc = 0;
+    for (int32_t k = 0; k < len; k++) nc += e->h_cmap[e->coded_order[at + k]] != 0;
+    const bool partial = nc > 0 && nc < len;
+    sbp.push_back(partial);
+    if (!partial) sbf.push_back(nc == len);
+    else
+      for (int32_t k = 0; k < len; k++) blk.push_back(e->h_cmap[e->coded_order[at + k]] != 0);
+    at += (size_t)len;
+  }
+  enc_put_runs(bw, sbp, true);
+  enc_put_runs(bw, sbf, true);
+  enc_put_runs(bw, blk, false);
+  // 7.4: the mode of every macro block with a coded luma block; vectors equal to the last (the one before) become INTER_MV_LAST
+  // (INTER_MV_LAST2), with the bookkeeping of 7.5
+  std::vector<uint8_t> modes;
+  std::vector<int> mvs;   // the vectors written: x, y
+  int lx = 0, ly = 0, l2x = 0, l2y = 0;
+  const int nh = e->nh[0];
+  for (int32_t mb : e->mb_order) {
+    const int mx = mb % e->nmbx, my = mb / e->nmbx, f0 = 2 * my * nh + 2 * mx;
+    if (!e->h_cmap[f0] && !e->h_cmap[f0 + 1] && !e->h_cmap[f0 + nh] && !e->h_cmap[f0 + nh + 1]) {
+      e->istats.modes[kModeNomv]++;
+      continue;
+    }
+    const uint32_t w = e->h_mb[mb];
+    int mode = (w & 0xFF) == kEncPixIntra ? kModeIntra : (w & 0xFF) == kEncPixMv ? kModeMv : kModeNomv;
+    if (mode == kModeMv) {
+      const int vx = (int)(int8_t)(w >> 8), vy = (int)(int8_t)(w >> 16);
+      if (vx == lx && vy == ly) {
+        mode = kModeMvLast;
+      } else if (vx == l2x && vy == l2y) {
+        mode = kModeMvLast2;
+        l2x = lx;
+        l2y = ly;
+        lx = vx;
+        ly = vy;
+      } else {
+        mvs.push_back(vx);
+        mvs.push_back(vy);
+        l2x = lx;
+        l2y = ly;
+        lx = vx;
+        ly = vy;
+      }
+    }
+    modes.push_back((uint8_t)mode);
+    e->istats.modes[mode]++;
+  }
+  // the cheapest scheme; scheme 0's alphabet by falling frequency (ties: the lower mode); ties between schemes: the lower index
+  int64_t freq[8] = {};
+  for (uint8_t m : modes) freq[m]++;
+  int alpha0[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+  std::stable_sort(alpha0, alpha0 + 8, [&](int a, int b) { return freq[a] > freq[b]; });
+  int rank[8][8];   // [scheme][mode] -> code index (scheme 7: none)
+  for (int i = 0; i < 8; i++) rank[0][alpha0[i]] = i;
+  for (int sc = 1; sc < 7; sc++)
+    for (int i = 0; i < 8; i++) rank[sc][kModeAlphabets[sc - 1][i]] = i;
+  int scheme = 0;
+  int64_t best = -1;
+  for (int sc = 0; sc < 8; sc++) {
+    int64_t bits = sc == 0 ? 24 : 0;
+    for (int m = 0; m < 8; m++) bits += freq[m] * (sc == 7 ? 3 : rank[sc][m] < 7 ? rank[sc][m] + 1 : 7);
+    if (best < 0 || bits < best) {
+      best = bits;
+      scheme = sc;
+    }
+  }
+  bw.put((uint32_t)scheme, 3);
+  if (scheme == 0)
+    for (int m = 0; m < 8; m++) bw.put((uint32_t)rank[0][m], 3);
+  for (uint8_t m : modes) {
+    if (scheme == 7) {
+      bw.put(m, 3);
+    } else {
+      const int i = rank[scheme][m];
+      bw.put(i < 7 ? ((1u << i) - 1) << 1 : 0x7Fu, i < 7 ? i + 1 : 7);
+    }
+  }
+  e->istats.mode_scheme = scheme;
+  // 7.5: the cheaper vector scheme (ties: VLC)
+  int64_t vlc = 0;
+  for (int v : mvs) vlc += enc_mv_vlc_bits(v);
+  const int mvsch = vlc > 6 * (int64_t)mvs.size() ? 1 : 0;
+  bw.put((uint32_t)mvsch, 1);
+  for (int v : mvs) enc_put_mv(bw, v, mvsch);
+  e->istats.mv_scheme = mvsch;
 }
 
 // the packet of the frame queued on the device: EOB runs merged, tables chosen, bits written
@@ -564,11 +828,36 @@ static int enc_finish_frame(th_enc_ctx *e) {
   e->pkt.clear();
   e->pkt.reserve(total * 2 + 16);
   BitW bw{&e->pkt};
-  bw.put(0, 1);                          // data packet
-  bw.put(0, 1);                          // intra frame
-  bw.put((uint32_t)e->frame_qi, 6);      // one qi
-  bw.put(0, 1);
-  bw.put(0, 3);                          // reserved
+  memset(&e->istats, 0, sizeof(e->istats));
+  e->istats.mode_scheme = e->istats.mv_scheme = -1;
+  if (e->frame_key) {
+    e->istats.key = 1;
+    e->istats.modes[kModeIntra] = e->nmbs;
+    for (int p = 0; p < 3; p++) e->istats.coded[p] = e->nh[p] * e->nv[p];
+    bw.put(0, 1);                          // data packet
+    bw.put(0, 1);                          // intra frame
+    bw.put((uint32_t)e->frame_qi, 6);      // one qi
+    bw.put(0, 1);
+    bw.put(0, 3);                          // reserved
+  } else {
+    for (int p = 0; p < 3; p++)
+      for (int f = e->froff[p]; f < e->froff[p] + e->nh[p] * e->nv[p]; f++) e->istats.coded[p] += e->h_cmap[f] != 0;
+    if (!e->istats.coded[0] && !e->istats.coded[1] && !e->istats.coded[2]) {
+      // no block coded: the frame is the previous one, a zero-byte packet (what a duplicate is)
+      e->pkt.clear();
+      e->host_ms = (enc_now() - t0) * 1e3;
+      e->stats.tokens = e->stats.tokens_merged = e->stats.bytes = 0;
+      for (int c = 0; c < 4; c++) e->stats.huff[c] = -1;
+      e->stats.overflow = 0;
+      e->stats.qi = e->frame_qi;
+      return 0;
+    }
+    bw.put(0, 1);                          // data packet
+    bw.put(1, 1);                          // inter frame
+    bw.put((uint32_t)e->frame_qi, 6);      // one qi
+    bw.put(0, 1);
+    enc_put_inter_header(e, bw);
+  }
   at = 0;
   for (int z = 0; z < 64; z++) {
     if (z < 2) {
@@ -596,6 +885,68 @@ static int enc_finish_frame(th_enc_ctx *e) {
   return overflow ? TH_EFAULT : 0;
 }
 
+static void enc_header(const th_enc_ctx *e, int which, const th_comment *tc, std::vector<uint8_t> &out);
+
+// the reconstruction: the packet just made goes through the encoder's own decoder (created at the first packet, with the encoder's
+// headers; no host copy of its pictures); its PREV frame is then the next frame's reference
+static int enc_recon(th_enc_ctx *e) {
+  if (!e->dec) {
+    th_info info;
+    th_comment tc;
+    th_setup_info *setup = nullptr;
+    th_info_init(&info);
+    th_comment_init(&tc);
+    std::vector<uint8_t> h;
+    int rc = 0;
+    for (int k = 0; k < 3 && rc >= 0; k++) {
+      enc_header(e, k, &tc, h);
+      ogg_packet op;
+      memset(&op, 0, sizeof(op));
+      op.packet = h.data();
+      op.bytes = (long)h.size();
+      op.b_o_s = k == 0;
+      op.packetno = k;
+      rc = th_decode_headerin(&info, &tc, &setup, &op);
+    }
+    if (rc >= 0) e->dec = th_decode_alloc_on(&info, setup, e->device);
+    th_setup_free(setup);
+    th_comment_clear(&tc);
+    th_info_clear(&info);
+    if (!e->dec) return TH_EFAULT;
+    int off = 0;
+    if (th_decode_ctl(e->dec, TH_DECCTL_THIP_SET_HOST_OUTPUT, &off, sizeof(off)) ||
+        th_decode_ctl(e->dec, TH_DECCTL_THIP_SET_DEVICE_LISTS, &off, sizeof(off)))
+      return TH_EFAULT;
+  }
+  ogg_packet op;
+  memset(&op, 0, sizeof(op));
+  op.packet = e->pkt.data();
+  op.bytes = (long)e->pkt.size();
+  op.granulepos = -1;
+  int64_t gp = 0;
+  if (th_decode_packetin(e->dec, &op, &gp) < 0) return TH_EFAULT;
+  thip_state *st = thip_dec_backend(e->dec);
+  if (!st || thip_state_check_fault(st) < 0) return TH_EFAULT;   // (waits for the decoder's stream)
+  e->have_recon = true;
+  return 0;
+}
+
+static int enc_get_recon(th_enc_ctx *e, th_img_plane *y) {
+  if (!e->inter || !e->have_recon) return TH_EINVAL;
+  for (int p = 0; p < 3; p++)
+    if (y[p].width != e->nh[p] * 8 || y[p].height != e->nv[p] * 8 || !y[p].data || y[p].stride < y[p].width) return TH_EINVAL;
+  thip_state *st = thip_dec_backend(e->dec);
+  const int prev = st ? thip_state_ref_idx(st, THIP_FRAME_PREV) : -1;
+  if (prev < 0) return TH_EFAULT;
+  for (int p = 0; p < 3; p++) {
+    const int w = y[p].width, h = y[p].height;
+    std::vector<uint8_t> tmp((size_t)w * h);
+    if (thip_state_read_plane(st, prev, p, tmp.data())) return TH_EFAULT;
+    for (int r = 0; r < h; r++) memcpy(y[p].data + (int64_t)r * y[p].stride, tmp.data() + (size_t)(h - 1 - r) * w, (size_t)w);
+  }
+  return 0;
+}
+
 int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
   if (!e || !op) return TH_EFAULT;
   if (e->done) return 0;
@@ -604,7 +955,12 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->frame_pending = false;
     const int rc = enc_finish_frame(e);
     if (rc) return rc;
-    e->key = ++e->cur;
+    if (e->frame_key) e->key = e->cur + 1;
+    ++e->cur;
+    if (e->inter && !e->pkt.empty()) {
+      const int drc = enc_recon(e);
+      if (drc) return drc;
+    }
     op->packet = e->pkt.data();
     op->bytes = (long)e->pkt.size();
   } else if (e->dups_left > 0) {
@@ -616,6 +972,8 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->stats, 0, sizeof(e->stats));
     e->stats.qi = e->frame_qi;
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
+    memset(&e->istats, 0, sizeof(e->istats));
+    e->istats.mode_scheme = e->istats.mv_scheme = -1;
   } else {
     return 0;
   }
@@ -627,22 +985,21 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
   return 1;
 }
 
-int th_encode_flushheader(th_enc_ctx *e, th_comment *tc, ogg_packet *op) {
-  if (!e || !tc || !op) return TH_EFAULT;
-  if (e->nheaders_out >= 3) return 0;
+// header packet `which` (0 info, 1 comment, 2 setup) into out
+static void enc_header(const th_enc_ctx *e, int which, const th_comment *tc, std::vector<uint8_t> &out) {
   const th_info &i = e->info;
-  e->hdr.clear();
-  BitW bw{&e->hdr};
-  bw.put(0x80u + (uint32_t)e->nheaders_out, 8);
+  out.clear();
+  BitW bw{&out};
+  bw.put(0x80u + (uint32_t)which, 8);
   for (const char *c = "theora"; *c; c++) bw.put((uint8_t)*c, 8);
-  if (e->nheaders_out == 0) {   // spec 6.2
+  if (which == 0) {   // spec 6.2
     const uint32_t f[][2] = {{3, 8}, {2, 8}, {1, 8}, {i.frame_width >> 4, 16}, {i.frame_height >> 4, 16}, {i.pic_width, 24},
                              {i.pic_height, 24}, {i.pic_x, 8}, {i.frame_height - i.pic_height - i.pic_y, 8},
                              {i.fps_numerator, 32}, {i.fps_denominator, 32}, {i.aspect_numerator, 24},
                              {i.aspect_denominator, 24}, {(uint32_t)i.colorspace, 8}, {0, 24}, {(uint32_t)i.quality, 6},
                              {(uint32_t)i.keyframe_granule_shift, 5}, {(uint32_t)i.pixel_fmt, 2}, {0, 3}};
     for (const auto &x : f) bw.put(x[0], (int)x[1]);
-  } else if (e->nheaders_out == 1) {   // spec 6.3
+  } else if (which == 1) {   // spec 6.3
     auto le32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) bw.put((v >> (8 * k)) & 0xFF, 8); };
     auto bytes = [&](const char *s, uint32_t n) { for (uint32_t k = 0; k < n; k++) bw.put((uint8_t)s[k], 8); };
     const char *vendor = th_version_string();
@@ -682,6 +1039,12 @@ int th_encode_flushheader(th_enc_ctx *e, th_comment *tc, ogg_packet *op) {
     for (int64_t k = 0; k < s.tree_bits; k++) bw.put((s.trees[k >> 3] >> (7 - (k & 7))) & 1, 1);
   }
   bw.flush();
+}
+
+int th_encode_flushheader(th_enc_ctx *e, th_comment *tc, ogg_packet *op) {
+  if (!e || !tc || !op) return TH_EFAULT;
+  if (e->nheaders_out >= 3) return 0;
+  enc_header(e, e->nheaders_out, tc, e->hdr);
   op->packet = e->hdr.data();
   op->bytes = (long)e->hdr.size();
   op->b_o_s = e->nheaders_out == 0;
@@ -702,10 +1065,32 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->qi = q;
       return 0;
     }
-    case TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE:
+    case TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE: {
       if (!buf || buf_sz != sizeof(uint32_t)) return TH_EINVAL;
-      *(uint32_t *)buf = 1;   // every frame is a key frame
+      if (!e->inter) {
+        *(uint32_t *)buf = 1;   // every frame is a key frame
+        return 0;
+      }
+      const int64_t full = (int64_t)1 << e->info.keyframe_granule_shift;
+      e->kf_interval = std::min(std::max((int64_t)*(uint32_t *)buf, (int64_t)1), full);
+      *(uint32_t *)buf = (uint32_t)e->kf_interval;
       return 0;
+    }
+    case TH_ENCCTL_THIP_SET_INTER_FRAMES: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const bool on = *(const int *)buf != 0;
+      if (on != e->inter && e->dev_ready) enc_free_device(e);   // (GET_DEVICE made the buffers of the other kind)
+      e->inter = on;
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_INTER_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_inter_stats)) return TH_EINVAL;
+      *(thip_enc_inter_stats *)buf = e->istats;
+      return 0;
+    case TH_ENCCTL_THIP_GET_RECON:
+      if (!buf || buf_sz != sizeof(th_ycbcr_buffer)) return TH_EINVAL;
+      return enc_get_recon(e, (th_img_plane *)buf);
     case TH_ENCCTL_SET_DUP_COUNT: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       const int n = *(const int *)buf;

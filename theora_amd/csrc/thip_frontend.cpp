@@ -3053,3 +3053,5 @@ int th_decode_ycbcr_out(th_dec_ctx *d, th_ycbcr_buffer ycbcr) {
 }
 
 }  // extern "C"
+
+thip_state *thip_dec_backend(th_dec_ctx *d) { return d && !d->trace ? d->hip : nullptr; }

@@ -1,5 +1,5 @@
-"""Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): an intra-only Theora encoder whose
-block work runs on the GPU."""
+"""Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): a Theora encoder whose block work runs
+on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True)."""
 import ctypes as C
 
 import numpy as np
@@ -16,6 +16,10 @@ TH_ENCCTL_THIP_YCBCR_IN_DEVICE = 0x7201
 TH_ENCCTL_THIP_GET_DEVICE = 0x7202
 TH_ENCCTL_THIP_GET_FRAME_STATS = 0x7203
 TH_ENCCTL_THIP_GET_TIMES = 0x7204
+TH_ENCCTL_THIP_SET_INTER_FRAMES = 0x7205
+TH_ENCCTL_THIP_GET_INTER_STATS = 0x7206
+TH_ENCCTL_THIP_GET_RECON = 0x7207
+MODE_NAMES = ("INTER_NOMV", "INTRA", "INTER_MV", "INTER_MV_LAST", "INTER_MV_LAST2")
 
 
 class DeviceIn(C.Structure):
@@ -27,6 +31,12 @@ class FrameStats(C.Structure):
     """thip_enc_frame_stats (include/theoraenc_hip.h)."""
     _fields_ = [("tokens", C.c_int64), ("tokens_merged", C.c_int64), ("bytes", C.c_int64), ("huff", C.c_int32 * 4),
                 ("overflow", C.c_int32), ("qi", C.c_int32)]
+
+
+class InterStats(C.Structure):
+    """thip_enc_inter_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("key", C.c_int32), ("modes", C.c_int32 * 5), ("coded", C.c_int32 * 3), ("mode_scheme", C.c_int32),
+                ("mv_scheme", C.c_int32)]
 
 
 def make_info(w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, aspect=(1, 1), colorspace=0, bitrate=0):
@@ -51,7 +61,10 @@ def _copy_packet(op):
 class Encoder:
     """th_encode_alloc -> th_encode_flushheader x3 -> {th_encode_ycbcr_in, th_encode_packetout}*."""
 
-    def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=()):
+    def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
+                 keyframe_interval=None):
+        """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
+        TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -60,6 +73,18 @@ class Encoder:
             raise TheoraHipError("th_encode_alloc failed")
         self.comments = list(comments)
         self.hdec, self.vdec = int(not (fmt & 1)), int(not (fmt & 2))
+        self.inter = bool(inter)
+        self.keyframe_interval = None
+        if self.inter:
+            rc, _ = self.ctl(TH_ENCCTL_THIP_SET_INTER_FRAMES, 1)
+            if rc < 0:
+                raise TheoraHipError("TH_ENCCTL_THIP_SET_INTER_FRAMES returned %d" % rc)
+            rc, self.keyframe_interval = self.ctl(TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE,
+                                                  1 << kfgshift if keyframe_interval is None else keyframe_interval, C.c_uint32)
+            if rc < 0:
+                raise TheoraHipError("TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE returned %d" % rc)
+        elif keyframe_interval is not None:
+            raise ValueError("keyframe_interval needs inter=True (an intra-only stream is all key frames)")
 
     def ctl(self, req, value=None, ctype=C.c_int):
         v = ctype(0 if value is None else value)
@@ -141,6 +166,30 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_TIMES returned %d" % rc)
         return t[0], t[1]
+
+    def inter_stats(self):
+        """TH_ENCCTL_THIP_GET_INTER_STATS of the last packet, as a dict (modes: macro blocks per mode name)."""
+        s = InterStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_INTER_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_INTER_STATS returned %d" % rc)
+        return dict(key=bool(s.key), modes=dict(zip(MODE_NAMES, list(s.modes))), coded=list(s.coded), mode_scheme=s.mode_scheme,
+                    mv_scheme=s.mv_scheme)
+
+    def recon(self):
+        """TH_ENCCTL_THIP_GET_RECON: the encoder's reconstruction of the last frame (the next one's reference) as three uint8 numpy
+        planes of the frame's size, rows top first."""
+        w, h = self.info.frame_width, self.info.frame_height
+        shapes = [(h, w)] + [(h >> self.vdec, w >> self.hdec)] * 2
+        out = [np.empty(sh, np.uint8) for sh in shapes]
+        buf = (ThImgPlane * 3)()
+        for p in range(3):
+            buf[p].width, buf[p].height, buf[p].stride = out[p].shape[1], out[p].shape[0], out[p].strides[0]
+            buf[p].data = out[p].ctypes.data_as(C.POINTER(C.c_ubyte))
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_RECON, buf, C.sizeof(buf))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_RECON returned %d" % rc)
+        return out
 
     def device(self):
         rc, v = self.ctl(TH_ENCCTL_THIP_GET_DEVICE)

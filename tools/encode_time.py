@@ -3,7 +3,11 @@ TH_ENCCTL_THIP_GET_TIMES), the host's part of th_encode_packetout (EOB runs, tab
 decoded picture -- 720p, 1080p and 4K at 4:2:0, the seeded natural image of tests/enc_ref.py, quality 16 and 48.  Kernel times
 come from a separate `rocprofv3 --kernel-trace --stats -- python tools/encode_time.py --frames 8` run.
 
-  python tools/encode_time.py [--frames 20] [--json out.json]
+With --inter N: inter frames with a key frame every N frames (TH_ENCCTL_THIP_SET_INTER_FRAMES) on the panning sequence of
+tests/enc_inter_ref.py; device and host times are medians over the inter frames, bytes the mean packet, PSNR the mean of the decoded
+frames.  call_ms includes the reconstruction (the encoder's own decoder) that sits between two frames.
+
+  python tools/encode_time.py [--frames 20] [--inter N] [--json out.json]
 """
 import argparse
 import json
@@ -27,8 +31,11 @@ def psnr(a, b):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--inter", type=int, default=0)
     ap.add_argument("--json")
     args = ap.parse_args()
+    if args.inter:
+        return main_inter(args)
     from tests import enc_ref
     from theora_amd.decoder import Decoder
     from theora_amd.encoder import Encoder
@@ -64,6 +71,50 @@ def main():
             r = dict(size=name, quality=q, device_ms=round(float(np.median(dev)), 4), host_ms=round(float(np.median(host)), 4),
                      call_ms=round(float(np.median(wall)), 4), bytes=len(pkt), tokens=st["tokens"],
                      tokens_merged=st["tokens_merged"], psnr=ps)
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if args.json:
+        json.dump(rows, open(args.json, "w"), indent=1)
+
+
+def main_inter(args):
+    from tests import enc_inter_ref, enc_ref
+    from theora_amd.decoder import Decoder
+    from theora_amd.encoder import Encoder
+    rows = []
+    n = args.frames + 3
+    for name, (w, h, pic) in SIZES.items():
+        p = pic or (0, 0, w, h)
+        frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
+                  for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
+        for q in (16, 48):
+            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter)
+            hdr = e.header_packets()
+            dev, host, wall, pkts, keys = [], [], [], [], 0
+            for f in range(n):
+                t0 = time.perf_counter()
+                e.encode(frames[f])
+                pkt = e.packetout(f == n - 1)[0]
+                t1 = time.perf_counter()
+                d, hm = e.times()
+                key = e.inter_stats()["key"]
+                pkts.append(pkt)
+                if f >= 3 and not key and pkt:
+                    dev.append(d)
+                    host.append(hm)
+                    wall.append((t1 - t0) * 1e3)
+                keys += key
+            e.close()
+            dec = Decoder(hdr)
+            ps = []
+            for f, pkt in enumerate(pkts):
+                dec.packetin(pkt)
+                got = dec.ycbcr_out()
+                ps.append(psnr(got[0][:p[3], :p[2]], frames[f][0]))
+            dec.close()
+            r = dict(size=name, quality=q, inter=args.inter, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
+                     host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
+                     bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
