@@ -5,16 +5,21 @@ A "step" decodes ONE frame of each of the rank's streams (default: 4 concurrent 
 streams per GPU, keyframe interval 64) from fragment command streams already resident in
 HBM: coded-fragment reconstruction (dequantised coefficients -> iDCT -> intra / motion
 compensated predictor -> pixels), uncoded-fragment copy and the in-loop deblocking filter,
-through the C ABI (thip_decode_frames).  Prints ONE JSON line (rank 0), at most 6 KB: the
-contract's keys, `roofline`, `cpu_baseline`, and one {value, ms_per_step, frac} triple per
-keyed entry (every BASELINE.json config); everything else -- notes, spreads, per-section
-wall times, the encoder kernels' full lines -- goes to bench_detail.json (written next to
-gpurun_out/ when that exists, else to the working directory; --detail names it).
+through the C ABI (thip_decode_frames).  Prints ONE JSON line (rank 0).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4k|1080p|720p]
-                  [--content dense|smooth|mixed] [--streams-per-gpu S] [--dump-outputs DIR]
+                  [--content dense|smooth|mixed] [--streams-per-gpu S] [--dump-outputs DIR] [--full]
 The headline times exactly K steps, after W warm-up steps, in one window: ms_per_step is the window over K.
 --dump-outputs writes the pictures the K-th step decoded (seeded inputs: the same arguments, the same pictures).
+
+A plain run does only what the headline needs: it generates the timed streams, decodes the --parity-frames
+frames that precede the warm-up in every run, pauses a second where --full compares them, warms up, times
+the K steps, dumps and prints the line.
+--full adds everything else, at most 6 KB on the line: the oracle comparison of those first frames (and the
+committed frame-39 CRCs), `roofline` (an instrumented pass and rocprofv3 --pmc re-executions), `cpu_baseline`,
+and one {value, ms_per_step, frac} triple per keyed entry (every BASELINE.json config); the rest -- notes,
+spreads, per-section wall times, the encoder kernels' full lines -- goes to a detail file (--detail names it,
+default ./bench_detail.json).  The timed steps are the same steps with and without --full.
 For N>1 launch with  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
 Streams are sharded whole across ranks (no data-path collective); RCCL is used for the
 barriers, the max-over-ranks time and the checksum gather.
@@ -26,7 +31,7 @@ Secondary modes (one GPU, not the headline metric):
 How the run is organised (475 s of wall, 1 % GPU busy): every synthetic command stream is generated, packed and --
 for the streams that are compared -- decoded by the oracle in WORKER PROCESSES (numpy + oracle only) that start before torch is
 imported; they hand their arrays over as .npz files, which the rocprofv3 --pmc re-executions of this script read too instead of
-generating them again.  The CPU baseline is timed behind everything else, on an idle box.
+generating them again.  The CPU baseline is timed behind everything else, on an idle box.  Nothing is kept between runs.
 """
 import argparse
 import json
@@ -51,6 +56,7 @@ FUSED = os.environ.get("THIP_FUSE", "3")
 # option "fuse": 3 = k_recon_lf (reconstruction + loop filter in one pass), anything else = the two passes
 KERNEL_NAMES = ("k_recon_lf", None) if FUSED == "3" else ("k_recon", "k_loopfilter")
 KF_INTERVAL = 64
+SETTLE_S = 1.0                 # a plain run's pause before the warm-up, in place of --full's oracle comparison (main())
 
 
 def _kernel_name(name):
@@ -219,23 +225,9 @@ def _cpu_job(job):
 
 
 def _e2e_prep_job(job):
-    """The packets of the keyed entry e2e_720p and the oracle's pictures of them (CRC32 per frame), in a worker process; cached
-    under tools/_cache (git-ignored; the Python packet generator takes tens of seconds), keyed by the generator's source."""
-    import hashlib
-    import pickle
+    """The packets of the keyed entry e2e_720p and the oracle's pictures of them (CRC32 per frame), in a worker process (the
+    Python packet generator takes about ten seconds, beside the GPU's entries)."""
     size, nframes = job["size"], job["nframes"]
-    src = open(os.path.join(ROOT, "tests", "streamgen.py"), "rb").read()
-    key = hashlib.sha1(src + repr((size, nframes, "dense", 99)).encode()).hexdigest()[:16]
-    cdir = os.path.join(ROOT, "tools", "_cache")
-    cpath = os.path.join(cdir, "bench_e2e_%s_%d_%s.pkl" % (size, nframes, key))
-    if os.path.exists(cpath):
-        try:
-            with open(cpath, "rb") as f:
-                d = pickle.load(f)
-            d["cached"] = True
-            return d
-        except Exception:   # noqa: BLE001 -- a damaged cache file: make the packets again
-            pass
     t0 = time.perf_counter()
     from tests import streamgen
     import oracle
@@ -251,16 +243,7 @@ def _e2e_prep_job(job):
             assert ost.decode_frame(**st.oracle_inputs(truth, ost)) == 0
         want.append(zlib.crc32(b"".join(np.ascontiguousarray(ost.get_plane(oracle.FRAME_PREV, pli)[::-1]).tobytes() for pli in range(3))))
     ost.close()
-    d = {"hdr": [bytes(x) for x in hdr], "pkts": [bytes(m[0]) for m in made], "want": want, "cached": False,
-         "prep_s": round(time.perf_counter() - t0, 1)}
-    try:
-        os.makedirs(cdir, exist_ok=True)
-        with open(cpath + ".tmp", "wb") as f:
-            pickle.dump(d, f)
-        os.replace(cpath + ".tmp", cpath)
-    except OSError:
-        pass
-    return d
+    return {"hdr": [bytes(x) for x in hdr], "pkts": [bytes(m[0]) for m in made], "want": want, "prep_s": round(time.perf_counter() - t0, 1)}
 
 
 # =====================================================================================================================
@@ -481,7 +464,7 @@ def e2e_keyed_entry(prep, size="720p", loops=30, ahead=8):
             return {"error": "pictures differ from the oracle's: %r frames of %d" % (bad, len(seq))}
         return {"metric": "end-to-end decode frames/sec, one %s 4:2:0 stream (packets in host memory -> pictures in host memory)" % size,
                 "unit": "frames/s", **res, "same_pictures": same, "frames_equal_to_the_oracle": "all %d of each leg's second, untimed pass (and the first %d of the timed one)" % (len(seq), len(pkts)),
-                "c_caller": native, "packets_from_cache": bool(prep.get("cached")),
+                "c_caller": native,
                 "avg_packet_bytes": sum(map(len, pkts)) // len(pkts),
                 "data": "synthetic packets (tests/streamgen.py), dense content, matched Huffman trees",
                 "note": "host-bound (Python caller): the plain loop is one entropy-decode thread per stream; announced packets are "
@@ -552,9 +535,14 @@ def parse_args():
                          "vtable slot's int16 products, state.h:365-366)")
     ap.add_argument("--streams-per-gpu", type=int, default=4)
     ap.add_argument("--pool", type=int, default=6, help="distinct inter-frame command streams per stream")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline: the oracle comparison, roofline, cpu_baseline, the keyed entries, "
+                         "the detail file (the --no-* options below leave parts out)")
     ap.add_argument("--cpu-frames", type=int, default=160, help="frames of stream 0 the scalar CPU oracle decodes for cpu_baseline (~6 s at 4K)")
-    ap.add_argument("--parity-frames", type=int, default=40, help="frames every timed stream is decoded and compared with the oracle before timing")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of the timed batch (profiling runs)")
+    ap.add_argument("--parity-frames", type=int, default=40, help="frames every timed stream is decoded before the warm-up (with --full: and "
+                                                                  "compared with the oracle)")
+    ap.add_argument("--no-parity", action="store_true", help="start the warm-up at the first frame: no frames decoded before it, no oracle comparison "
+                                                             "(profiling runs)")
     ap.add_argument("--repeats", type=int, default=15, help="blocks timed for each keyed entry (clamped to 5..15)")
     ap.add_argument("--min-time", type=float, default=0.3, help="(kept for old command lines: the headline times exactly --steps steps now)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -571,7 +559,7 @@ def parse_args():
     ap.add_argument("--no-enc", action="store_true", help="skip the keyed entry enc_1080p_444 (BASELINE.json config 5: the encoder's block kernels)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the keyed entry e2e_720p (th_decode_* end to end, one stream, with and without the look-ahead)")
     ap.add_argument("--no-pmc", action="store_true", help="do not re-execute under rocprofv3 --pmc for roofline.traffic (N = 1 only)")
-    ap.add_argument("--detail", default="", help="where the detail file goes (default: gpurun_out/bench_detail.json if gpurun_out/ exists, else ./bench_detail.json)")
+    ap.add_argument("--detail", default="bench_detail.json", help="where the detail file of a --full run goes")
     ap.add_argument("--all-entries", action="store_true", help="the keyed entries at any --size (they belong to the 4K default line; tests/test_bench_flow.py)")
     ap.add_argument("--pmc-child", default="", help=argparse.SUPPRESS)
     return ap.parse_known_args()
@@ -1042,15 +1030,20 @@ def main():
     from theora_amd import shard       # (torch only: no HIP yet)
 
     S = args.streams_per_gpu
+    # the first nparity frames are decoded in every run (the timed steps follow them); only --full compares them with the oracle
     nparity = 0 if args.no_parity else max(1, args.parity_frames)
-    main_4k = args.size == "4k" or args.all_entries
-    do_second = bool(args.second_content) and args.second_content != args.content
+    full = args.full
+    check = full and nparity > 0
+    main_4k = full and (args.size == "4k" or args.all_entries)
+    do_second = full and bool(args.second_content) and args.second_content != args.content
     do_1080p = main_4k and not args.no_1080p
     do_form16 = main_4k and args.form == "levels" and not args.no_form16
     do_wide = main_4k and args.content == "dense" and args.form == "levels" and not args.no_wide and world == 1
     do_enc = rank == 0 and world == 1 and main_4k and not args.no_enc
     do_e2e = rank == 0 and world == 1 and main_4k and not args.no_e2e
-    do_cpu = rank == 0 and not args.no_cpu_baseline and nparity > 0
+    do_cpu = rank == 0 and not args.no_cpu_baseline and check
+    profiling = full and not args.no_profile
+    do_pmc = rank == 0 and world == 1 and not args.no_pmc and profiling
     # At every world size rank 0's CPU baseline (tens of seconds, one process per core) runs BEHIND the timed regions, so that no
     # rank's clock starts after a long wait in a collective and nothing competes with the generation workers
     cpu_late = True
@@ -1060,7 +1053,7 @@ def main():
     import tempfile
     tmp = tempfile.TemporaryDirectory(prefix="thip_bench_", dir=os.environ.get("TMPDIR", "/tmp"))
     ncores = _usable_cores()
-    nworkers = max(2, min(24, ncores // max(1, world)))
+    nworkers = max(2, min(24 if full else S, ncores // max(1, world)))
     workers = mp.get_context("spawn").Pool(nworkers)
     gids = shard.stream_ids(rank, world, S)
     jobs = {}
@@ -1072,7 +1065,7 @@ def main():
     for s, gid in enumerate(gids):
         forms = (args.form,) + (("dequant16",) if do_form16 else ())
         ask("main%d" % s, size=args.size, content=args.content, seed=shard.stream_seed(12345, gid), forms=forms,
-            parity={"frames": nparity} if nparity else None, host=(do_cpu and s == 0))
+            parity={"frames": nparity} if check else None, host=(do_cpu and s == 0))
     if do_1080p:
         # (1080p: seed base 777, stream gid; the single stream is rank's stream `rank`, the four streams 4 rank .. 4 rank + 3)
         for gid in sorted(set(shard.stream_ids(rank, world, 1) + shard.stream_ids(rank, world, 4))):
@@ -1186,11 +1179,12 @@ def main():
     # Parity of the TIMED batch: the states, plans and launch shape that are timed below first decode the first `parity_frames`
     # frames of the sequence; every plane of every stream is then compared with the oracle's decoding of the same frames (done by
     # the worker that generated the stream; a stream's content depends on its global id only, so streams [0, S) are the same
-    # pictures at every world size).  No number is printed on a mismatch.
+    # pictures at every world size).  No number is printed on a mismatch.  A plain run decodes the same frames unchecked.
     parity, parity_crcs = None, []
     if nparity:
         run(nparity)
         sync()
+    if check:
         ok, bad = True, []
         for s in range(S):
             b, c = planes_equal(states[s], main_res[s]["oracle_planes"])
@@ -1203,6 +1197,11 @@ def main():
         parity = {"frames": nparity, "bit_exact": True,
                   "checked": "the timed batch itself: all %d streams of every rank, decoded %d frames deep by the timed states in the timed launch "
                              "shape (one thip_decode_frames call per step), every plane of every stream against the oracle" % (S, nparity)}
+    elif nparity:
+        # Where --full compares (about half a second), a plain run pauses: a window started straight after these frames read about
+        # 10 % slow over 20 steps on the MI355X (88.5-94.7 k frames/s against 99.8-100.6 k with a one-second pause here, with the
+        # planes read back instead, or with busy host cores), so the headline is timed as it always was, after the comparison.
+        time.sleep(SETTLE_S)
     wall.mark("upload_and_parity")
 
     # ---- timed region ---------------------------------------------------------------------
@@ -1230,11 +1229,11 @@ def main():
                     budget=DUMP_BUDGET_BYTES // world)
     # (diagnostic: what the bracket itself costs -- sync() on an idle device, part of the window's time)
     idle_sync = []
-    for _ in range(20):
+    for _ in range(20 if full else 0):
         t0 = time.perf_counter()
         sync()
         idle_sync.append(time.perf_counter() - t0)
-    idle_sync_us = 1e6 * sorted(idle_sync)[len(idle_sync) // 2]
+    idle_sync_us = 1e6 * sorted(idle_sync)[len(idle_sync) // 2] if idle_sync else None
     submit_us = 1e6 * t_sub
     # Pass B: steps with every kernel bracketed by HIP events on the stream it runs on -> per-kernel durations for the
     # roofline.  Kept out of pass A because four event records per step cost ~15 % of the step.  Two shapes:
@@ -1242,7 +1241,6 @@ def main():
     #       kernel proper (`roofline`), what `rocprofv3 --kernel-trace --stats` of a THIP_LANES=1 run shows;
     #   (2) the TIMED shape: the library's lanes, S/lanes streams per launch, launches of different lanes overlapping
     #       (detail: a launch takes longer there because it shares the chip with the other lane's).
-    profiling = not args.no_profile
     launches, kms, elapsed_b = [0, 0], [0.0, 0.0], 0.0
     launches_t, kms_t = [0, 0], [0.0, 0.0]
     prof_steps = max(args.steps, 256)
@@ -1267,7 +1265,7 @@ def main():
         step0 += prof_steps
     # checksum of each stream's final frame (all planes): gathered over ranks, printed
     crcs = []
-    for st in states:
+    for st in (states if full else []):
         c = 0
         for pli in range(3):
             c = zlib.crc32(st.read_plane(st.ref_idx(theora_amd.FRAME_PREV), pli).tobytes(), c)
@@ -1276,8 +1274,9 @@ def main():
     per_rank_ms = [round(1e3 * v / args.steps, 5) for v in shard.gather_floats(dt, dev)]   # every rank's own
     pg = {"initialized": bool(dist.is_initialized()), "world_size": dist.get_world_size() if dist.is_initialized() else 1,
           "backend": dist.get_backend() if dist.is_initialized() else None}
-    _, crcs = shard.reduce_results(0.0, crcs, dev)
-    if nparity:
+    if full:
+        _, crcs = shard.reduce_results(0.0, crcs, dev)
+    if check:
         _, parity_crcs = shard.reduce_results(0.0, parity_crcs, dev)
     kms = shard.reduce_max(kms, dev)
     kms_t = shard.reduce_max(kms_t, dev)
@@ -1463,7 +1462,7 @@ def main():
     # ---- HBM bytes and vector instructions per launch from the PMC counters of THIS workload: this script again under rocprofv3,
     #      one pass per counter group, reading the command streams the workers wrote ---------------------------------------------------
     pmc = None
-    if rank == 0 and world == 1 and not args.no_pmc and profiling:
+    if do_pmc:
         manifest = {"size": args.size, "steps": 24, "enc": bool(do_enc),
                     "forms": {args.form: [r["files"][args.form] for r in main_res]}}
         if do_form16:
@@ -1548,8 +1547,6 @@ def main():
         rng_steps = range(first_timed, first_timed + args.steps)
         steps_b_alg = sum(alg_of_step(i, 0) for i in rng_steps)
         steps_b_read = sum(alg_of_step(i, 1) for i in rng_steps)
-        prof_b_alg = sum(alg_of_step(i, 0) for i in range(first_prof, first_prof + prof_steps))
-        prof_t_alg = sum(alg_of_step(i, 0) for i in range(first_prof + prof_steps, first_prof + 2 * prof_steps))
         total_frames = args.steps * S * world
         fps = total_frames / elapsed
         kname = KERNEL_NAMES[0] + ("<true>" if args.form == "levels" else "<false>")
@@ -1575,10 +1572,10 @@ def main():
                        if dist.is_initialized() else None},
             "timing": {"statistic": "one window of --steps steps, the slowest rank", "ms_per_step_by_rank": per_rank_ms},
         }
-        detail["timing"] = {"steps": args.steps, "host_submit_us": round(submit_us, 1), "idle_sync_us": round(idle_sync_us, 1)}
-        detail["process_group"] = pg
         td_ = traffic_of(_pmc_flat(pmc), kname) or (traffic_of(_pmc_flat(pmc), KERNEL_NAMES[0]) if pmc else None)
         if profiling and kms[0] > 0:
+            prof_b_alg = sum(alg_of_step(i, 0) for i in range(first_prof, first_prof + prof_steps))
+            prof_t_alg = sum(alg_of_step(i, 0) for i in range(first_prof + prof_steps, first_prof + 2 * prof_steps))
             gbs = prof_b_alg / (kms[0] * 1e-3) / 1e9
             out["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": round(gbs, 1),
                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
@@ -1632,19 +1629,22 @@ def main():
                 if got39 != COMMITTED_CRC_FRAME39:
                     raise SystemExit("bench: frame-39 CRCs of streams 0..3 %s differ from the committed %s" % (got39, COMMITTED_CRC_FRAME39))
                 out["parity"]["matches_committed_crc32"] = True
-        detail["stream_crc32"] = ["%08x" % c for c in crcs]
         wall.mark("assemble")
-        detail["wall_s"] = dict(wall.sections, total=wall.total(), workers=nworkers,
-                                gen_s_by_job={t: j.get()["gen_s"] for t, j in jobs.items() if j.ready() and j.successful()})
         out["wall_s"] = wall.total()
-        dpath = args.detail or (os.path.join(ROOT, "gpurun_out", "bench_detail.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else "bench_detail.json")
-        try:
-            detail["line"] = out
-            with open(dpath, "w") as f:
-                json.dump(detail, f, indent=1)
-            out["detail"] = os.path.relpath(dpath, ROOT) if dpath.startswith(ROOT) else dpath
-        except OSError as e:
-            out["detail"] = "not written: %s" % e
+        if full:
+            detail["timing"] = {"steps": args.steps, "host_submit_us": round(submit_us, 1), "idle_sync_us": round(idle_sync_us, 1)}
+            detail["process_group"] = pg
+            detail["stream_crc32"] = ["%08x" % c for c in crcs]
+            detail["wall_s"] = dict(wall.sections, total=wall.total(), workers=nworkers,
+                                    gen_s_by_job={t: j.get()["gen_s"] for t, j in jobs.items() if j.ready() and j.successful()})
+            dpath = args.detail
+            try:
+                detail["line"] = out
+                with open(dpath, "w") as f:
+                    json.dump(detail, f, indent=1)
+                out["detail"] = os.path.relpath(dpath, ROOT) if dpath.startswith(ROOT) else dpath
+            except OSError as e:
+                out["detail"] = "not written: %s" % e
         line = json.dumps(out)
         if len(line) > 6000:       # the driver keeps an 8 KB tail of the output: the line must fit with room to spare
             for k in ("timing", "pipeline"):

@@ -1,7 +1,8 @@
 """bench.py's control flow without a GPU: the device side replaced by stand-ins that decode nothing (so the oracle comparison is
 switched off with --no-parity and no number means anything) -- what is checked is that every keyed entry is produced, the line is
 valid JSON under the 6 KB the driver's 8 KB tail leaves room for, the detail file is written, and the worker processes deliver.
-The real thing runs on the GPU box (tools/prof_round6.sh)."""
+The real thing runs on the GPU box (tools/prof_round6.sh).
+A plain run (no --full) is checked to submit the headline's steps and nothing else."""
 import json
 import os
 import sys
@@ -29,20 +30,27 @@ class _FakeState:
 
 class _FakePlan:
     submitted = 0
+    frames = []         # the frame (index into a stream's [key, inter_1 .. inter_pool]) of every submitted step, in order
 
     def __init__(self, states, descs):
         assert len(states) == len(descs) and all(d is not None for d in descs)
+        self.frame = descs[0]["frame"]
 
     def submit(self, stream=None):
         _FakePlan.submitted += 1
+        _FakePlan.frames.append(self.frame)
 
 
-def test_default_line_fits_the_drivers_tail(monkeypatch, tmp_path, capsys):
+def _fake_device(monkeypatch):
+    """bench.main() without a GPU: states, plans and uploads are stand-ins; an uploaded frame remembers its index in the pool
+    (the file a worker wrote it to ends in _<index>.npz)."""
     sys.path.insert(0, ROOT)
     import torch
     import theora_amd
     from theora_amd import synth
     import bench
+    load = bench._npz_load
+    monkeypatch.setattr(bench, "_npz_load", lambda p: dict(load(p), _frame=int(p.rsplit("_", 1)[1][:-4])))
     monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
 
@@ -59,9 +67,14 @@ def test_default_line_fits_the_drivers_tail(monkeypatch, tmp_path, capsys):
     monkeypatch.setattr(theora_amd, "profile_reset", lambda: None)
     monkeypatch.setattr(theora_amd, "profile_enable", lambda on: None)
     monkeypatch.setattr(theora_amd, "profile_read", lambda: ([256, 0], [12.5, 0.0]))
-    monkeypatch.setattr(synth, "upload_frame", lambda packed, device="cuda": (dict(nslots=packed["nslots"]), None))
+    monkeypatch.setattr(synth, "upload_frame", lambda packed, device="cuda": (dict(nslots=packed["nslots"], frame=packed["_frame"]), None))
+    return bench
+
+
+def test_default_line_fits_the_drivers_tail(monkeypatch, tmp_path, capsys):
+    bench = _fake_device(monkeypatch)
     detail = tmp_path / "detail.json"
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--size", "qcif", "--all-entries", "--no-parity", "--no-cpu-baseline", "--no-pmc", "--no-enc", "--no-e2e",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--size", "qcif", "--all-entries", "--no-parity", "--no-cpu-baseline", "--no-pmc", "--no-enc", "--no-e2e",
                                       "--steps", "20", "--repeats", "3", "--min-time", "0", "--detail", str(detail),
                                       "--dump-outputs", str(tmp_path / "dump")])
     bench.main()
@@ -95,6 +108,27 @@ def test_default_line_fits_the_drivers_tail(monkeypatch, tmp_path, capsys):
             a = np.load(tmp_path / "dump" / ("stream%d_%s.npy" % (s, p)))
             assert a.dtype == np.float32 and a.shape == shape
 
+
+def test_plain_run_times_the_headline_only(monkeypatch, tmp_path, capsys):
+    """Without --full: the --parity-frames frames (unchecked), the warm-up and the timed steps of the one sequence, nothing else
+    submitted; the line holds the headline and nothing that takes a run of its own; no detail file."""
+    bench = _fake_device(monkeypatch)
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--size", "qcif", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / "dump")])
+    _FakePlan.frames = []
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert _FakePlan.frames == [bench.seq_frame(i, 0, 1, 6) for i in range(40 + 5 + 20)]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "timing", "pipeline", "wall_s"):
+        assert k in line, k
+    assert line["metric"] == "decode frames/sec (qcif 4:2:0, bit-exact)" and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "i16" and line["steps"] == 20 and line["warmup"] == 5
+    assert line["value"] > 0 and line["ms_per_step"] >= 0
+    for k in ("roofline", "entries", "cpu_baseline", "parity", "detail"):
+        assert k not in line, k
+    assert sorted(os.listdir(tmp_path)) == ["dump"]
+    assert sorted(os.listdir(tmp_path / "dump")) == sorted("stream%d_%s.npy" % (s, p) for s in range(4) for p in ("y", "cb", "cr"))
 
 def test_dump_outputs_stay_in_budget_and_repeat(tmp_path):
     """bench.dump_arrays: whole arrays in float32 when they fit; else the same seeded sample of every array in every run, the files

@@ -5,14 +5,14 @@
 export TMPDIR=/tmp
 o=gpurun_out/r04p
 mkdir -p $o
-python bench.py > $o/bench_default.json 2> $o/bench_default.err
-python bench.py --steps 20 --no-cpu-baseline > $o/bench_steps20.json 2>/dev/null
-THIP_FUSE=0 python bench.py --no-cpu-baseline --no-1080p > $o/bench_twopass.json 2>/dev/null
-python bench.py --size 1080p --streams-per-gpu 1 --no-cpu-baseline --no-1080p --second-content "" > $o/bench_1080p_single.json 2>/dev/null
-python bench.py --size 1080p --streams-per-gpu 1 --gop-parallel 16 --no-cpu-baseline --no-1080p --parity-frames 70 > $o/bench_1080p_single_gop16.json 2>/dev/null
-python bench.py --size 1080p --no-cpu-baseline --no-1080p --second-content "" > $o/bench_1080p_4streams.json 2>/dev/null
-python bench.py --size 720p --streams-per-gpu 1 --no-cpu-baseline --no-1080p --second-content "" > $o/bench_720p_single.json 2>/dev/null
-THIP_SB_TILES=0 python bench.py --size 720p --streams-per-gpu 1 --no-cpu-baseline --no-1080p --second-content "" > $o/bench_720p_single_tilekernel.json 2>/dev/null
+python bench.py --full > $o/bench_default.json 2> $o/bench_default.err
+python bench.py --full --steps 20 --no-cpu-baseline > $o/bench_steps20.json 2>/dev/null
+THIP_FUSE=0 python bench.py --full --no-cpu-baseline --no-1080p > $o/bench_twopass.json 2>/dev/null
+python bench.py --full --size 1080p --streams-per-gpu 1 --no-cpu-baseline --no-1080p --second-content "" > $o/bench_1080p_single.json 2>/dev/null
+python bench.py --full --size 1080p --streams-per-gpu 1 --gop-parallel 16 --no-cpu-baseline --no-1080p --parity-frames 70 > $o/bench_1080p_single_gop16.json 2>/dev/null
+python bench.py --full --size 1080p --no-cpu-baseline --no-1080p --second-content "" > $o/bench_1080p_4streams.json 2>/dev/null
+python bench.py --full --size 720p --streams-per-gpu 1 --no-cpu-baseline --no-1080p --second-content "" > $o/bench_720p_single.json 2>/dev/null
+THIP_SB_TILES=0 python bench.py --full --size 720p --streams-per-gpu 1 --no-cpu-baseline --no-1080p --second-content "" > $o/bench_720p_single_tilekernel.json 2>/dev/null
 THIP_LANES=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_lanes1 -- python bench.py --steps 64 --repeats 2 --min-time 0 --no-cpu-baseline --no-parity --no-profile --no-pmc --no-1080p --second-content "" > $o/stats_lanes1.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_default -- python bench.py --steps 64 --repeats 2 --min-time 0 --no-cpu-baseline --no-parity --no-profile --no-pmc --no-1080p --second-content "" > $o/stats_default.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do

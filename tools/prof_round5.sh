@@ -8,7 +8,7 @@
 export TMPDIR=/tmp
 what=${1:-final}
 o=gpurun_out/r05_$what; mkdir -p $o
-B="python bench.py --content dense --second-content '' --no-cpu-baseline --parity-frames 4 --no-1080p --no-e2e --no-pmc --no-wide --no-enc"
+B="python bench.py --full --content dense --second-content '' --no-cpu-baseline --parity-frames 4 --no-1080p --no-e2e --no-pmc --no-wide --no-enc"
 show() { python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); t=d['timing']; print('%-26s' % '$1', d['value'], d['ms_per_step'], d['pipeline']['read_roofline_frac'], 'min', t['ms_per_step_min'], 'max', t['ms_per_step_max'], 'submit_us', t['host_submit_us_per_block'], 'idle_sync_us', t['idle_sync_us'])"; }
 case $what in
@@ -56,9 +56,9 @@ e2e)
   cat $o/native_1stream.jsonl $o/native_4streams.jsonl | cut -c1-250 ;;
 final)
   timeout 2400 python -m pytest tests -m gpu -q > $o/pytest_gpu.txt 2>&1; tail -3 $o/pytest_gpu.txt
-  python bench.py > $o/bench_default.json 2> $o/bench_default.err
-  python bench.py --steps 20 > $o/bench_steps20.json 2>/dev/null
-  THIP_FUSE=0 python bench.py --no-cpu-baseline --no-1080p --no-e2e --no-wide --no-enc > $o/bench_twopass.json 2>/dev/null
+  python bench.py --full > $o/bench_default.json 2> $o/bench_default.err
+  python bench.py --full --steps 20 > $o/bench_steps20.json 2>/dev/null
+  THIP_FUSE=0 python bench.py --full --no-cpu-baseline --no-1080p --no-e2e --no-wide --no-enc > $o/bench_twopass.json 2>/dev/null
   python bench.py --mode enc > $o/bench_enc.jsonl 2>/dev/null
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_enc -- python bench.py --mode enc > $o/bench_enc_under_rocprof.jsonl 2>$o/stats_enc.log
   THIP_LANES=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_lanes1 -- python bench.py --steps 64 --repeats 2 --min-time 0 --no-cpu-baseline --no-parity --no-profile --no-pmc --no-1080p --no-e2e --no-wide --no-enc --second-content "" > $o/stats_lanes1.log 2>&1
@@ -67,6 +67,6 @@ final)
   LANES=2 bash tools/pmc_r4.sh smooth > /dev/null 2>&1; cp gpurun_out/r04/pmc_smooth.txt $o/pmc_counters_smooth_lanes2.txt 2>/dev/null
   python tools/lf_trace.py --content dense 2>&1 | grep -v amdgpu.ids > $o/lf_trace_dense.txt
   python tools/lf_trace.py --content smooth 2>&1 | grep -v amdgpu.ids > $o/lf_trace_smooth.txt
-  MASTER_ADDR=127.0.0.1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 5 --no-1080p --no-e2e --no-wide --no-enc --no-pmc --cpu-frames 32 > $o/torchrun_world1.log 2>&1
+  MASTER_ADDR=127.0.0.1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-1080p --no-e2e --no-wide --no-enc --no-pmc --cpu-frames 32 > $o/torchrun_world1.log 2>&1
   tail -c 400 $o/bench_default.json ;;
 esac

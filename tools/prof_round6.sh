@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 what=${1:-final}
 o=gpurun_out/r06_$what; mkdir -p $o
-Q="--second-content '' --no-cpu-baseline --parity-frames 4 --no-1080p --no-e2e --no-pmc --no-wide --no-enc --no-form16"
+Q="--full --second-content '' --no-cpu-baseline --parity-frames 4 --no-1080p --no-e2e --no-pmc --no-wide --no-enc --no-form16"
 show() { python -c "
 import sys,json
 try:
@@ -15,7 +15,7 @@ except Exception as e:
 case $what in
 ab1)
   timeout 1500 python -m pytest tests/test_gpu_slots.py tests/test_gpu_costmaps.py -m gpu -q > $o/pytest_kernels.txt 2>&1; tail -3 $o/pytest_kernels.txt
-  python bench.py --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; tail -c 600 $o/bench_default.err; wc -c $o/bench_default.json
+  python bench.py --full --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; tail -c 600 $o/bench_default.err; wc -c $o/bench_default.json
   for round in 1 2; do
     for spec in 0 1; do
       THIP_SPEC_COEFFS=$spec bash -c "python bench.py --size 1080p --streams-per-gpu 1 --steps 256 $Q" 2>/dev/null | show "1080p_1stream spec=$spec"
@@ -34,8 +34,8 @@ ab1)
 ab2)
   timeout 1500 python -m pytest tests/test_gpu_frontend.py -m gpu -q -x > $o/pytest_frontend.txt 2>&1; tail -3 $o/pytest_frontend.txt
   python bench.py --mode enc > $o/bench_enc.jsonl 2> $o/bench_enc.err; tail -5 $o/bench_enc.err; cut -c1-200 $o/bench_enc.jsonl
-  python bench.py --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; tail -c 1500 $o/bench_default.err; wc -c $o/bench_default.json
-  python bench.py --steps 20 --detail $o/bench_detail20.json > $o/bench_steps20.json 2> /dev/null; wc -c $o/bench_steps20.json
+  python bench.py --full --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; tail -c 1500 $o/bench_default.err; wc -c $o/bench_default.json
+  python bench.py --full --steps 20 --detail $o/bench_detail20.json > $o/bench_steps20.json 2> /dev/null; wc -c $o/bench_steps20.json
   AB_ROUNDS=2 bash tools/ab.sh base=tools/_build/ab/base.so pitch152=tools/_build/ab/pitch152.so 2>&1 | tee $o/ab_pitch.txt
   AB_ROUNDS=2 AB_STEPS=20 bash tools/ab.sh base=tools/_build/ab/base.so pitch152=tools/_build/ab/pitch152.so 2>&1 | tee $o/ab_pitch20.txt
   E2E_LOOPS=6 python tools/native_lookahead.py 720p,1080p dense 1 0,8 0,1 > $o/native_1stream.jsonl 2>$o/native.err; cut -c1-250 $o/native_1stream.jsonl ;;
@@ -111,13 +111,13 @@ spec2)
 soak)
   timeout 400 python tests/soak_take_back.py 7 150 2>&1 | tail -3 | tee $o/soak_take_back.txt
   timeout 400 python tests/soak_frontend.py 11 120 2>&1 | tail -2 | tee $o/soak_frontend.txt
-  python bench.py --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; tail -c 300 $o/bench_default.json ;;
+  python bench.py --full --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; tail -c 300 $o/bench_default.json ;;
 final)
   Q2="--no-cpu-baseline --no-parity --no-profile --no-pmc --no-1080p --no-e2e --no-wide --no-enc --no-form16 --second-content ''"
   timeout 2400 python -m pytest tests -m gpu -q > $o/pytest_gpu.txt 2>&1; tail -3 $o/pytest_gpu.txt
-  python bench.py --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; wc -c $o/bench_default.json
-  python bench.py --steps 20 --detail $o/bench_detail_steps20.json > $o/bench_steps20.json 2>/dev/null; wc -c $o/bench_steps20.json
-  THIP_FUSE=0 python bench.py --no-cpu-baseline --no-1080p --no-e2e --no-wide --no-enc --no-form16 --detail $o/bench_detail_twopass.json > $o/bench_twopass.json 2>/dev/null
+  python bench.py --full --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.err; wc -c $o/bench_default.json
+  python bench.py --full --steps 20 --detail $o/bench_detail_steps20.json > $o/bench_steps20.json 2>/dev/null; wc -c $o/bench_steps20.json
+  THIP_FUSE=0 python bench.py --full --no-cpu-baseline --no-1080p --no-e2e --no-wide --no-enc --no-form16 --detail $o/bench_detail_twopass.json > $o/bench_twopass.json 2>/dev/null
   python bench.py --mode enc > $o/bench_enc.jsonl 2>$o/bench_enc.err
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_enc -- python bench.py --mode enc > $o/bench_enc_under_rocprof.jsonl 2>$o/stats_enc.log
   THIP_LANES=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_lanes1 -- bash -c "python bench.py --steps 64 --repeats 2 --min-time 0 $Q2" > $o/stats_lanes1.log 2>&1
@@ -126,7 +126,7 @@ final)
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_1080p_single -- bash -c "python bench.py --size 1080p --streams-per-gpu 1 --steps 128 --repeats 2 --min-time 0 $Q2" > $o/stats_1080p_single.log 2>&1
   LANES=2 bash tools/pmc_r4.sh dense > /dev/null 2>&1; cp gpurun_out/r04/pmc_dense.txt $o/pmc_counters_dense_lanes2.txt 2>/dev/null
   LANES=2 bash tools/pmc_r4.sh smooth > /dev/null 2>&1; cp gpurun_out/r04/pmc_smooth.txt $o/pmc_counters_smooth_lanes2.txt 2>/dev/null
-  MASTER_ADDR=127.0.0.1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 5 --no-1080p --no-e2e --no-wide --no-enc --no-form16 --no-pmc --cpu-frames 32 --detail $o/bench_detail_torchrun.json > $o/torchrun_world1.log 2>&1
+  MASTER_ADDR=127.0.0.1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-1080p --no-e2e --no-wide --no-enc --no-form16 --no-pmc --cpu-frames 32 --detail $o/bench_detail_torchrun.json > $o/torchrun_world1.log 2>&1
   E2E_LOOPS=6 python tools/native_lookahead.py 720p,1080p,4k dense 1 0,8,16 0,1 > $o/native_1stream.jsonl 2>$o/native.err
   E2E_LOOPS=6 python tools/native_lookahead.py 720p,4k dense 4 0,8 0,1 > $o/native_4streams.jsonl 2>>$o/native.err
   tail -c 600 $o/bench_default.json ;;
