@@ -3,10 +3,10 @@
  * libtheoraenc that asks for nothing beyond a constant quality relinks against libtheora_hip.so.  The shared types (th_info,
  * th_comment, th_ycbcr_buffer, ogg_packet) come from theoradec_hip.h.
  *
- * What it is not, by default: every data packet is a key frame.  There is no mode decision, motion search or rate control, so bitrate
- * mode (th_info.target_bitrate != 0: th_encode_alloc returns NULL), 2-pass, the rate flags and buffer, custom Huffman codes or
- * quantisation parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every
- * decoder plays it.
+ * What it is not, by default: every data packet is a key frame.  There is no mode decision, motion search or rate control by
+ * default.  Bitrate mode is entered through TH_ENCCTL_SET_BITRATE after th_encode_alloc ("Bitrate mode" below); th_info.target_bitrate
+ * != 0 at th_encode_alloc is refused (NULL).  2-pass, custom Huffman codes or quantisation parameters and VP3 compatibility are not
+ * available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
  *
  * The bitstream, stated so that a restatement reproduces the packets byte for byte (tests/enc_ref.py does):
  *   - Setup header.  Loop-filter limits lflim[qi] = (31 * (63 - qi) + 31) / 63.  AC and DC scales fall geometrically,
@@ -67,6 +67,37 @@
  *     Vectors (7.5): scheme 1 (six bits a component) when it costs fewer bits than the VLC, else the VLC.  Tokens as for key frames,
  *     over the coded blocks only.
  *
+ * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
+ * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
+ *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
+ *     at qi q counted from its tokens with every block's EOB its own token (no EOB runs).  Each token is counted in the list of the
+ *     zig-zag index where it starts, in the Huffman group of that index, for luma or chroma; per choice (DC luma, DC chroma, AC luma,
+ *     AC chroma) the least, over the 16 tables, of sum count x code length (for AC one table over groups 1-4), plus the tokens'
+ *     extra bits, plus the header: 28 bits for a key frame, 25 + nfrags / 8 for an inter frame.  A key frame's blocks are the
+ *     bitstream's at q.  An inter frame's macro-block mode at q follows from the search's S0, Smv, SI and vector with L = the inter
+ *     luma step of q (the mode rule above); each block codes its macro block's residual at q and is coded by the rule above, exact
+ *     except: (1) a DC is predicted from the coded neighbours of its class at q, and with none from 0; (2) instead of the coded
+ *     flags, modes and vectors, 3 M(q) + 12 V(q) bits, M(q) the macro blocks with a coded luma block, V(q) those of them MV.
+ *   - Setup, at the first frame in bitrate mode: T = clamp(bitrate * fps_denominator / fps_numerator, 32, 2^40) bits a frame;
+ *     D = the buffer (TH_ENCCTL_SET_RATE_BUFFER), else clamp(K, 12, 256) with K the key-frame interval in force (1 with inter frames
+ *     off); R = T D, F* = R / 2, fullness F = F*.  Per frame type t (key, inter) a correction c_t = 65536 (Q16) and the type's last
+ *     probe L_t (none yet).
+ *   - Each frame n (not a duplicate): L_t = E; Cur(q) = E[q] c_t >> 16.  Of frames n + 1 .. n + D - 1, n_k are key frames and
+ *     n_i inter frames by the interval rule from the current key position (all key frames with inter frames off);
+ *     Future(q) = n_k (L_key[q] c_key >> 16) + n_i (L_inter[q] c_inter >> 16), where a missing inter term is the key term / 4 and a
+ *     missing key term 4 x the inter term.  S = F + D T - F*.  qi = the largest q with Cur(q) + Future(q) <= S, else 0.
+ *   - Drop: with TH_RATECTL_DROP_FRAMES, when the frame is not the first, F + T - Cur(0) < 0 and a duplicate's granule fits there
+ *     (frame offset from the key frame plus the frame's own duplicates < 1 << keyframe_granule_shift), the frame becomes a zero-byte
+ *     packet with a duplicate's granule: F += T, the reference is unchanged, and it counts as a frame for the key-frame rule.
+ *   - After a coded frame of A bits (8 x its bytes): F += T - A; c_t = clamp((c_t + (A << 16) / max(E[qi], 1)) / 2, 4096, 2^20).
+ *     A duplicate (TH_ENCCTL_SET_DUP_COUNT) adds F += T.  After every change of F: with TH_RATECTL_CAP_OVERFLOW F = min(F, R), with
+ *     TH_RATECTL_CAP_UNDERFLOW F = max(F, 0).
+ *   - A later TH_ENCCTL_SET_BITRATE recomputes T, R and F*, keeps D, and sets F = min(F, R); TH_ENCCTL_SET_RATE_BUFFER likewise
+ *     with the new D.
+ *   - The wait: in bitrate mode th_encode_ycbcr_in and TH_ENCCTL_THIP_YCBCR_IN_DEVICE queue the probe, wait on the host for its
+ *     512 bytes, choose, and then queue the frame's launches at the chosen qi exactly as quality mode does at that qi (with inter
+ *     frames, its own motion search with that qi's lambda).  Quality mode never waits.
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
  * extensions, YCBCR_IN_DEVICE and GET_DEVICE do.
@@ -87,24 +118,32 @@ extern "C" {
 #define TH_ENCCTL_SET_DUP_COUNT (18)               /* buf = int: the next N packets after the next frame are duplicates;
                                                       N < 1 << keyframe_granule_shift when the shift is not 0, else TH_EINVAL
                                                       (a duplicate's granule counts it in the shift's bits) */
-#define TH_ENCCTL_SET_QUALITY (28)                 /* buf = int 0..63: from the next frame on */
+#define TH_ENCCTL_SET_QUALITY (28)                 /* buf = int 0..63: from the next frame on; TH_EINVAL in bitrate mode */
+#define TH_ENCCTL_SET_BITRATE (30)                 /* buf = long (or int when buf_sz == sizeof(int)): > 0 enters bitrate mode
+                                                      or changes its target, from the next frame on; before th_encode_flushheader
+                                                      the info header's NOMBR field carries it (clamped to 2^24 - 1); 0 (leave
+                                                      bitrate mode) TH_EIMPL; < 0 TH_EINVAL */
+#define TH_ENCCTL_SET_RATE_FLAGS (20)              /* buf = int, TH_RATECTL_*: in bitrate mode (default DROP_FRAMES | CAP_OVERFLOW),
+                                                      else TH_EIMPL */
+#define TH_ENCCTL_SET_RATE_BUFFER (22)             /* buf = int, frames: clamped to [12, 256] and written back; in bitrate mode,
+                                                      else TH_EIMPL */
+#define TH_RATECTL_DROP_FRAMES (0x1)
+#define TH_RATECTL_CAP_OVERFLOW (0x2)
+#define TH_RATECTL_CAP_UNDERFLOW (0x4)
 /* Known, and answered TH_EIMPL: */
 #define TH_ENCCTL_SET_HUFFMAN_CODES (0)
 #define TH_ENCCTL_SET_QUANT_PARAMS (2)
 #define TH_ENCCTL_SET_VP3_COMPATIBLE (10)
 #define TH_ENCCTL_GET_SPLEVEL (16)
-#define TH_ENCCTL_SET_RATE_FLAGS (20)
-#define TH_ENCCTL_SET_RATE_BUFFER (22)
 #define TH_ENCCTL_2PASS_OUT (24)
 #define TH_ENCCTL_2PASS_IN (26)
-#define TH_ENCCTL_SET_BITRATE (30)
 #define TH_ENCCTL_SET_COMPAT_CONFIG (32)
 
 /* Extension: buf = thip_enc_device_in.  What th_encode_ycbcr_in does, with plane pointers in device memory on the context's GPU
    (TH_ENCCTL_THIP_GET_DEVICE) and of the same sizes (frame or picture).  `stream` is a hipStream_t (NULL: the null stream): the
    encoder reads the planes only after the work queued on that stream so far, and the work queued on it afterwards runs only after
    the encoder has read them -- so the caller may write the buffers again from that stream at once (thip_picture_out's
-   ordering, in the other direction).  The call does not wait on the host. */
+   ordering, in the other direction).  The call does not wait on the host (in bitrate mode it waits for the rate probe). */
 #define TH_ENCCTL_THIP_YCBCR_IN_DEVICE (0x7201)
 typedef struct thip_enc_device_in {
   th_img_plane planes[3];
@@ -144,6 +183,25 @@ typedef struct thip_enc_inter_stats {
 /* Extension: buf = th_ycbcr_buffer of host planes of the FRAME's size, rows top first: receives the encoder's reconstruction of the
    last frame -- the next frame's reference.  Waits for the device.  TH_EINVAL with inter frames off or before the first packet. */
 #define TH_ENCCTL_THIP_GET_RECON (0x7207)
+
+/* Extension: buf = thip_enc_rate_stats, describing the last packet th_encode_packetout returned; TH_EINVAL outside bitrate mode. */
+#define TH_ENCCTL_THIP_GET_RATE_STATS (0x7208)
+typedef struct thip_enc_rate_stats {
+  int32_t qi;              /* the qi chosen (a dropped frame or a duplicate: the last frame's) */
+  int32_t dropped;         /* 1: the controller dropped the frame (a zero-byte packet) */
+  int32_t key;             /* 1: coded as a key frame */
+  int32_t duplicate;       /* 1: a TH_ENCCTL_SET_DUP_COUNT duplicate (nothing probed; the probe fields are 0) */
+  int64_t target;          /* T, bits a frame */
+  int64_t fullness_before; /* F before the packet ... */
+  int64_t fullness_after;  /* ... and after it */
+  int64_t spend;           /* S */
+  int64_t estimate;        /* Cur(qi) */
+  int64_t actual;          /* A, the packet's bits */
+  int64_t probe[64];       /* E[q] as the device measured it */
+  int64_t corr[2];         /* c_key, c_inter (Q16) after the packet */
+  double probe_ms;         /* the probe's device time (HIP events, from its first launch to its 512 bytes on the host) */
+  double control_ms;       /* the host controller's time */
+} thip_enc_rate_stats;
 
 typedef struct th_enc_ctx th_enc_ctx;
 

@@ -22,7 +22,7 @@
 #include "../../include/theora_hip.h"
 #include "../../include/theoraenc_hip.h"
 #include "thip_device.h"
-#include "thip_encode_inter.h"
+#include "thip_rate.h"
 #include "thip_ctx.h"
 
 using namespace thip;
@@ -291,6 +291,25 @@ struct th_enc_ctx : thip_ctx_head {
   th_dec_ctx *dec = nullptr;       // the reconstruction: a decoder of the encoder's own packets
   bool have_recon = false;
   thip_enc_inter_stats istats;
+  // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
+  bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
+  int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
+  int64_t bitrate = 0, rT = 0, rD = 0, rR = 0, rFstar = 0, rF = 0;
+  int64_t rc_corr[2] = {65536, 65536};   // c_key, c_inter (Q16)
+  int64_t rL[2][64];                     // the last probe of each frame type
+  bool rL_have[2] = {false, false};
+  int64_t rE[64];                        // the probe of the frame queued
+  int rate_nwg = 0;
+  int16_t *d_coef = nullptr, *d_qdc = nullptr;
+  uint64_t *d_rcoded = nullptr, *d_rcls = nullptr;
+  uint4 *d_rmbs = nullptr;
+  uint2 *d_rtab = nullptr;
+  int *d_rlam = nullptr;
+  uint8_t *d_rlens = nullptr;
+  uint32_t *d_rpart = nullptr;
+  int64_t *d_rest = nullptr, *h_rest = nullptr;
+  hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+  thip_enc_rate_stats rstats;
   // output
   std::vector<uint8_t> pkt;
   std::vector<uint32_t> merged;
@@ -368,6 +387,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   enc_setup_init(e->setup);
   memset(&e->stats, 0, sizeof(e->stats));
   memset(&e->istats, 0, sizeof(e->istats));
+  memset(&e->rstats, 0, sizeof(e->rstats));
   e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
 }
@@ -385,18 +405,22 @@ static void enc_free_device(th_enc_ctx *e) {
   void **dev[] = {(void **)&e->d_pix, (void **)&e->d_order, (void **)&e->d_dequant, (void **)&e->d_levels, (void **)&e->d_dcq,
                   (void **)&e->d_tok, (void **)&e->d_cnt, (void **)&e->d_base, (void **)&e->d_small, (void **)&e->d_out,
                   (void **)&e->d_mask, (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr,
-                  (void **)&e->d_dqi};
+                  (void **)&e->d_dqi, (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls,
+                  (void **)&e->d_rmbs, (void **)&e->d_rtab, (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart,
+                  (void **)&e->d_rest};
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap};
+  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap,
+                    (void **)&e->h_rest};
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
   }
   e->h_tok_cap = 0;
-  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done}) {
+  e->rate_dev = false;
+  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -502,15 +526,14 @@ static int enc_buffer_kind(const th_enc_ctx *e, const th_img_plane *y) {
   return -1;
 }
 
-// the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
-static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
+// the reconstruction of the previous frame (the decoder's PREV) as the device stage reads it
+static int enc_prev_ref(th_enc_ctx *e, EncRef &R) {
   thip_state *st = thip_dec_backend(e->dec);
   const int prev = st ? thip_state_ref_idx(st, THIP_FRAME_PREV) : -1;
   if (prev < 0) return TH_EFAULT;
   thip_plane_geom geom[3];
   if (thip_state_get_geom(st, geom, nullptr, nullptr)) return TH_EFAULT;
   const uint8_t *base = thip_state_frame_ptr(st, prev);
-  EncRef R;
   for (int p = 0; p < 3; p++) {
     R.plane[p] = base + geom[p].plane_off;
     R.stride[p] = geom[p].stride;
@@ -519,6 +542,13 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
   }
   R.hdec = e->hdec;
   R.vdec = e->vdec;
+  return 0;
+}
+
+// the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
+static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
+  EncRef R;
+  if (enc_prev_ref(e, R)) return TH_EFAULT;
   const int64_t n = e->nfrags;
   const int lambda = enc_qstep_inter(e->setup, e->frame_qi, 1);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
@@ -550,6 +580,201 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
   return 0;
 }
 
+static double enc_now();
+
+// ---- bitrate mode -----------------------------------------------------------------------------------------------------------
+// the probe's buffers, at the first frame in bitrate mode
+static int enc_rate_alloc(th_enc_ctx *e) {
+  if (e->rate_dev) return 0;
+  const int64_t n = e->nfrags;
+  ENC_TRY(hipEventCreate(&e->ev_p0));
+  ENC_TRY(hipEventCreate(&e->ev_p1));
+  // (a group then takes at most n / nwg + kRateTokWaves blocks)
+  e->rate_nwg = (int)std::max(std::min((int64_t)256, (n + kRateTokWaves - 1) / kRateTokWaves),
+                              (n + kRateMaxBlocksPerGroup - 1) / kRateMaxBlocksPerGroup);
+  ENC_TRY(hipMalloc((void **)&e->d_coef, (size_t)(e->inter ? 3 : 1) * n * 64 * 2));
+  ENC_TRY(hipMalloc((void **)&e->d_qdc, (size_t)n * 64 * 2));
+  ENC_TRY(hipMalloc((void **)&e->d_rcoded, (size_t)n * 8));
+  ENC_TRY(hipMalloc((void **)&e->d_rcls, (size_t)n * 8));
+  ENC_TRY(hipMalloc((void **)&e->d_rmbs, (size_t)std::max(e->nmbs, 1) * sizeof(uint4)));
+  ENC_TRY(hipMalloc((void **)&e->d_rtab, 6 * 64 * 64 * sizeof(uint2)));
+  ENC_TRY(hipMalloc((void **)&e->d_rlam, 64 * sizeof(int)));
+  ENC_TRY(hipMalloc((void **)&e->d_rlens, 80 * 32));
+  ENC_TRY(hipMalloc((void **)&e->d_rpart, (size_t)e->rate_nwg * 64 * kRatePartial * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_rest, 64 * 8));
+  ENC_TRY(hipHostMalloc((void **)&e->h_rest, 64 * 8, hipHostMallocDefault));
+  // oc_enc_quantize's table entries of every (table, z, q), as k_enc_intra_fq forms them: (step | m << 16, l)
+  std::vector<uint2> tab(6 * 64 * 64);
+  for (int t = 0; t < 6; t++)
+    for (int z = 0; z < 64; z++)
+      for (int q = 0; q < 64; q++) {
+        const uint32_t dq = t < 3 ? enc_qstep(e->setup, t, q, z) : enc_qstep_inter(e->setup, q, z);
+        const uint32_t d = dq << 1;
+        const int l = 31 - __builtin_clz(d);
+        const uint32_t tt = 1u + ((1u << (16 + l)) / d);
+        const int m = (int)(int16_t)(tt - 0x10000u);
+        tab[(t * 64 + z) * 64 + q] = make_uint2(dq | (uint32_t)(uint16_t)m << 16, (uint32_t)l);
+      }
+  int lam[64];
+  for (int q = 0; q < 64; q++) lam[q] = enc_qstep_inter(e->setup, q, 1);
+  ENC_TRY(hipMemcpy(e->d_rtab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(e->d_rlam, lam, sizeof(lam), hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(e->d_rlens, e->setup.len, 80 * 32, hipMemcpyHostToDevice));
+  e->rate_dev = true;
+  return 0;
+}
+
+// E[0..63] of the frame about to be coded (thip_rate.h) into e->rE: queued on the encoder's stream behind its input, waited for
+static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key) {
+  const int64_t n = e->nfrags;
+  RateArgs a;
+  a.coef = e->d_coef;
+  a.tab = e->d_rtab;
+  a.mbs = e->d_rmbs;
+  a.lam = e->d_rlam;
+  a.nmbx = e->nmbx;
+  a.hdec = e->hdec;
+  a.vdec = e->vdec;
+  const unsigned g4 = (unsigned)((4 * n + 255) / 256), gw = (unsigned)((n + 3) / 4);
+  ENC_TRY(hipEventRecord(e->ev_p0, e->stream));
+  if (key) {
+    hipLaunchKernelGGL(k_rate_fdct_key, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, n);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_rate_dc<false>, dim3(gw), dim3(256), 0, e->stream, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_rate_tok<false>, dim3((unsigned)e->rate_nwg), dim3(64 * kRateTokWaves), 0, e->stream, e->d_rpart, e->d_qdc, e->d_rcoded,
+                       e->d_rcls, a, g, n);
+    ENC_TRY(hipGetLastError());
+  } else {
+    EncRef R;
+    if (enc_prev_ref(e, R)) return TH_EFAULT;
+    hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_rate_fdct_inter, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, R, (const uint4 *)e->d_rmbs, e->nmbx, n);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_rate_dc<true>, dim3(gw), dim3(256), 0, e->stream, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_rate_tok<true>, dim3((unsigned)e->rate_nwg), dim3(64 * kRateTokWaves), 0, e->stream, e->d_rpart, e->d_qdc, e->d_rcoded,
+                       e->d_rcls, a, g, n);
+    ENC_TRY(hipGetLastError());
+  }
+  // header bits: 0, frame type, qi, 0 (+ 3 reserved bits in a key frame) and the four table indices; an inter frame adds nfrags / 8
+  const int fixed = key ? 12 + 16 : 9 + 16 + (int)(n / 8);
+  hipLaunchKernelGGL(k_rate_bits, dim3(64), dim3(1024), 0, e->stream, e->d_rest, (const uint32_t *)e->d_rpart, e->rate_nwg,
+                     (const uint8_t *)e->d_rlens, fixed);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(e->h_rest, e->d_rest, 64 * 8, hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_p1, e->stream));
+  ENC_TRY(hipEventSynchronize(e->ev_p1));
+  float ms = 0;
+  e->rstats.probe_ms = hipEventElapsedTime(&ms, e->ev_p0, e->ev_p1) == hipSuccess ? ms : 0.0;
+  memcpy(e->rE, e->h_rest, sizeof(e->rE));
+  return 0;
+}
+
+static int64_t rate_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// T, R, F* of the bitrate in force (D kept)
+static void enc_rate_targets(th_enc_ctx *e) {
+  const th_info &i = e->info;
+  e->rT = rate_clamp((int64_t)((__int128)e->bitrate * i.fps_denominator / i.fps_numerator), 32, (int64_t)1 << 40);
+  e->rR = e->rT * e->rD;
+  e->rFstar = e->rR / 2;
+}
+
+static void enc_rate_caps(th_enc_ctx *e) {
+  if (e->rate_flags & TH_RATECTL_CAP_OVERFLOW) e->rF = std::min(e->rF, e->rR);
+  if (e->rate_flags & TH_RATECTL_CAP_UNDERFLOW) e->rF = std::max(e->rF, (int64_t)0);
+}
+
+// the controller's choice for frame f (theoraenc_hip.h, "Bitrate mode"): returns the qi, or -1 to drop the frame
+static int enc_rate_choose(th_enc_ctx *e, bool key, int64_t f, int64_t keypos) {
+  const double t0 = enc_now();
+  if (!e->rate_started) {
+    e->rD = e->rate_buf ? e->rate_buf : rate_clamp(e->inter ? e->kf_interval : 1, 12, 256);
+    enc_rate_targets(e);
+    e->rF = e->rFstar;
+    e->rate_started = true;
+  }
+  const int t = key ? 0 : 1;
+  memcpy(e->rL[t], e->rE, sizeof(e->rE));
+  e->rL_have[t] = true;
+  // the next D - 1 frames: key or inter by the interval rule from the current key position
+  int64_t nk = 0, ni = 0;
+  for (int64_t m = f + 1; m < f + e->rD; m++) {
+    if (!e->inter || (m - keypos) % e->kf_interval == 0) nk++;
+    else ni++;
+  }
+  int64_t cur[64], fut[64];
+  for (int q = 0; q < 64; q++) {
+    cur[q] = e->rE[q] * e->rc_corr[t] >> 16;
+    int64_t kt = e->rL_have[0] ? e->rL[0][q] * e->rc_corr[0] >> 16 : -1;
+    int64_t it = e->rL_have[1] ? e->rL[1][q] * e->rc_corr[1] >> 16 : -1;
+    if (it < 0) it = kt / 4;
+    if (kt < 0) kt = 4 * it;
+    fut[q] = nk * kt + ni * it;
+  }
+  const int64_t S = e->rF + e->rD * e->rT - e->rFstar;
+  int qi = 0;
+  for (int q = 63; q >= 0; q--)
+    if (cur[q] + fut[q] <= S) {
+      qi = q;
+      break;
+    }
+  const int64_t full = (int64_t)1 << e->info.keyframe_granule_shift;
+  const bool drop = (e->rate_flags & TH_RATECTL_DROP_FRAMES) && e->cur >= 0 && e->rF + e->rT - cur[0] < 0 && e->key >= 0 &&
+                    f - e->key + e->dup_next < full;
+  thip_enc_rate_stats &r = e->rstats;
+  r.qi = drop ? e->frame_qi : qi;
+  r.dropped = drop;
+  r.key = key && !drop;
+  r.duplicate = 0;
+  r.target = e->rT;
+  r.fullness_before = e->rF;
+  r.spend = S;
+  r.estimate = cur[qi];
+  r.actual = 0;
+  memcpy(r.probe, e->rE, sizeof(r.probe));
+  if (drop) {
+    e->rF += e->rT;
+    enc_rate_caps(e);
+  }
+  r.fullness_after = e->rF;
+  r.corr[0] = e->rc_corr[0];
+  r.corr[1] = e->rc_corr[1];
+  r.control_ms = (enc_now() - t0) * 1e3;
+  return drop ? -1 : qi;
+}
+
+// after a coded frame of A bits
+static void enc_rate_update(th_enc_ctx *e, bool key, int64_t A) {
+  const int t = key ? 0 : 1;
+  e->rF += e->rT - A;
+  enc_rate_caps(e);
+  const int64_t est = std::max(e->rE[e->frame_qi], (int64_t)1);
+  e->rc_corr[t] = rate_clamp((e->rc_corr[t] + (A << 16) / est) / 2, 4096, (int64_t)1 << 20);
+  e->rstats.actual = A;
+  e->rstats.fullness_after = e->rF;
+  e->rstats.corr[0] = e->rc_corr[0];
+  e->rstats.corr[1] = e->rc_corr[1];
+}
+
+// a duplicate (TH_ENCCTL_SET_DUP_COUNT) in bitrate mode
+static void enc_rate_dup(th_enc_ctx *e) {
+  if (!e->rate_started) return;
+  thip_enc_rate_stats &r = e->rstats;
+  r.dropped = r.key = 0;
+  r.duplicate = 1;
+  r.qi = e->frame_qi;
+  r.fullness_before = e->rF;
+  e->rF += e->rT;
+  enc_rate_caps(e);
+  r.fullness_after = e->rF;
+  r.spend = r.estimate = r.actual = 0;
+  memset(r.probe, 0, sizeof(r.probe));
+  r.probe_ms = r.control_ms = 0;
+}
+
 // the four launches of a frame, reading the picture through `src` / `stride` (top-left pixel of the picture of each plane)
 static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int64_t stride[3]) {
   EncPlanes g;
@@ -565,10 +790,27 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     g.froff[p] = e->froff[p];
   }
   const int64_t n = e->nfrags;
-  e->frame_qi = e->qi;
+  if (!e->rate) e->frame_qi = e->qi;   // (bitrate mode: the controller's choice, below)
   // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
   const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
   e->frame_key = !e->inter || e->key < 0 || off >= e->kf_interval || off + e->dup_next >= full;
+  if (e->rate) {
+    // bitrate mode: the probe, then the controller's qi -- or a dropped frame, a zero-byte packet with nothing more queued
+    if (enc_rate_alloc(e)) return TH_EFAULT;
+    const int prc = enc_rate_probe(e, g, e->frame_key);
+    if (prc) return prc;
+    ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the launches below record it again)
+    const int qi = enc_rate_choose(e, e->frame_key, f, e->frame_key ? f : e->key);
+    if (qi < 0) {
+      e->frame_key = false;
+      e->rate_dropped = true;
+      e->frame_pending = true;
+      e->dups_left = e->dup_next;
+      e->dup_next = 0;
+      return 0;
+    }
+    e->frame_qi = qi;
+  }
   if (!e->frame_key) return enc_queue_inter(e, g);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
@@ -951,7 +1193,18 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
   if (!e || !op) return TH_EFAULT;
   if (e->done) return 0;
   const int shift = e->info.keyframe_granule_shift;
-  if (e->frame_pending) {
+  if (e->frame_pending && e->rate_dropped) {   // a frame the rate controller dropped: the previous frame again
+    e->frame_pending = e->rate_dropped = false;
+    ++e->cur;
+    e->pkt.clear();
+    op->packet = e->pkt.data();
+    op->bytes = 0;
+    memset(&e->stats, 0, sizeof(e->stats));
+    e->stats.qi = e->frame_qi;
+    e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
+    memset(&e->istats, 0, sizeof(e->istats));
+    e->istats.mode_scheme = e->istats.mv_scheme = -1;
+  } else if (e->frame_pending) {
     e->frame_pending = false;
     const int rc = enc_finish_frame(e);
     if (rc) return rc;
@@ -961,11 +1214,13 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
       const int drc = enc_recon(e);
       if (drc) return drc;
     }
+    if (e->rate) enc_rate_update(e, e->frame_key, (int64_t)e->pkt.size() * 8);
     op->packet = e->pkt.data();
     op->bytes = (long)e->pkt.size();
   } else if (e->dups_left > 0) {
     e->dups_left--;
     ++e->cur;
+    if (e->rate) enc_rate_dup(e);
     e->pkt.clear();
     op->packet = e->pkt.data();
     op->bytes = 0;
@@ -996,7 +1251,7 @@ static void enc_header(const th_enc_ctx *e, int which, const th_comment *tc, std
     const uint32_t f[][2] = {{3, 8}, {2, 8}, {1, 8}, {i.frame_width >> 4, 16}, {i.frame_height >> 4, 16}, {i.pic_width, 24},
                              {i.pic_height, 24}, {i.pic_x, 8}, {i.frame_height - i.pic_height - i.pic_y, 8},
                              {i.fps_numerator, 32}, {i.fps_denominator, 32}, {i.aspect_numerator, 24},
-                             {i.aspect_denominator, 24}, {(uint32_t)i.colorspace, 8}, {0, 24}, {(uint32_t)i.quality, 6},
+                             {i.aspect_denominator, 24}, {(uint32_t)i.colorspace, 8}, {(uint32_t)i.target_bitrate, 24}, {(uint32_t)i.quality, 6},
                              {(uint32_t)i.keyframe_granule_shift, 5}, {(uint32_t)i.pixel_fmt, 2}, {0, 3}};
     for (const auto &x : f) bw.put(x[0], (int)x[1]);
   } else if (which == 1) {   // spec 6.3
@@ -1060,6 +1315,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
   switch (req) {
     case TH_ENCCTL_SET_QUALITY: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->rate) return TH_EINVAL;   // (bitrate mode chooses the qi)
       const int q = *(const int *)buf;
       if (q < 0 || q > 63) return TH_EINVAL;
       e->qi = q;
@@ -1084,6 +1340,46 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->inter = on;
       return 0;
     }
+    case TH_ENCCTL_SET_BITRATE: {
+      if (!buf) return TH_EINVAL;
+      long v;
+      if (buf_sz == sizeof(long)) v = *(const long *)buf;
+      else if (buf_sz == sizeof(int)) v = *(const int *)buf;
+      else return TH_EINVAL;
+      if (v < 0) return TH_EINVAL;
+      if (v == 0) return TH_EIMPL;   // (leaving bitrate mode)
+      e->bitrate = (int64_t)v;
+      e->rate = true;
+      if (e->nheaders_out == 0) e->info.target_bitrate = (int)std::min(v, (long)((1 << 24) - 1));
+      if (e->rate_started) {
+        enc_rate_targets(e);
+        e->rF = std::min(e->rF, e->rR);
+      }
+      return 0;
+    }
+    case TH_ENCCTL_SET_RATE_FLAGS:
+      if (!e->rate) return TH_EIMPL;
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      e->rate_flags = *(const int *)buf & (TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW | TH_RATECTL_CAP_UNDERFLOW);
+      return 0;
+    case TH_ENCCTL_SET_RATE_BUFFER: {
+      if (!e->rate) return TH_EIMPL;
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      const int d = (int)rate_clamp(*(const int *)buf, 12, 256);
+      *(int *)buf = d;
+      e->rate_buf = d;
+      if (e->rate_started) {
+        e->rD = d;
+        enc_rate_targets(e);
+        e->rF = std::min(e->rF, e->rR);
+      }
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_RATE_STATS:
+      if (!e->rate) return TH_EINVAL;
+      if (!buf || buf_sz != sizeof(thip_enc_rate_stats)) return TH_EINVAL;
+      *(thip_enc_rate_stats *)buf = e->rstats;
+      return 0;
     case TH_ENCCTL_THIP_GET_INTER_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_inter_stats)) return TH_EINVAL;
       *(thip_enc_inter_stats *)buf = e->istats;

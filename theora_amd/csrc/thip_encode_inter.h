@@ -66,7 +66,8 @@ __device__ __forceinline__ uint64_t enc_min64_wave(uint64_t v) {
   return v;
 }
 
-// grid: one work group per macro block (raster, rows from the bottom).  lambda: the frame's inter luma step at zig-zag index 1
+// grid: one work group per macro block (raster, rows from the bottom).  lambda: the frame's inter luma step at zig-zag index 1.
+// k_rate_me (thip_rate.h) copies the search and writes its statistics instead of the decision: a fix here belongs there too.
 __global__ __launch_bounds__(256) void k_enc_me(uint32_t *mb_out, EncPlanes g, EncRef R, int nmbx, int lambda) {
   __shared__ uint32_t s_win[kMeWin * kMeWin / 4];
   __shared__ uint32_t s_src[16 * 4];

@@ -54,7 +54,8 @@ __device__ constexpr int kFZigZag[64] = {
 // line an SGPR.  On entry the wave's 2 KB `lds` holds the sixteen blocks' int16 input, piece pc (row pc, natural order) of block bb at
 // lds[bb * 8 + ((pc + bb) & 7)], and s_t the block's 64 table entries by natural position (step | reciprocal m << 16, shift l |
 // zig-zag index << 8); a barrier lies behind both.  On return the same 2 KB hold the block's quantised levels in zig-zag order, in the
-// same layout, every LDS operation of the wave complete.
+// same layout, every LDS operation of the wave complete.  rate_fdct4_lds (thip_rate.h) copies the transform half: a fix here belongs
+// there too.
 __device__ __forceinline__ void fdct_quantize4_lds(int4 *lds, const uint2 *s_t, int b, int j) {
   const int *ldw = reinterpret_cast<const int *>(lds);
   int c0[8], c1[8];   // columns 2j and 2j + 1

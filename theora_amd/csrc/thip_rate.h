@@ -1,0 +1,472 @@
+// thip_rate.h -- the rate probe of th_encode_*'s bitrate mode (thip_encode.hip; the controller and E[q] are stated in
+// theoraenc_hip.h, "Bitrate mode").  Before a frame is coded, the probe measures its token bits E[q] at every qi q = 0..63 at once:
+// the 64 lanes of a wave are the 64 qi, a wave takes one block.  The quality-mode kernels are not touched; the probe has its own.
+//
+//   k_rate_me          (inter frames) k_enc_me's search, writing the qi-independent statistics of each macro block instead of a mode:
+//                      S0, Smv, SI and the half-pel vector.  The mode at q then follows from them and q's lambda (rate_mode).
+//   k_rate_fdct_key    the unquantised fDCT of every block (raster order, natural order in the block): fdct_quantize4_lds's transform.
+//   k_rate_fdct_inter  the same for the three residuals an inter block may code: INTRA (pixel - 128), NOMV (PREV, vector 0) and MV
+//                      (PREV through the macro block's vector) -- [3][nfrags][64].
+//   k_rate_dc          one wave a block, lane q: the block's quantised DC at q, and (inter) whether the block is coded at q and in
+//                      which class (ballots into one 64-bit word each).
+//   k_rate_tok         a persistent grid, one wave a block, lane q: DC prediction at q, the AC levels at q and the block's tokens,
+//                      counted into the work group's LDS histogram [q][luma / chroma][Huffman group][token] (u16 pairs).  The
+//                      levels are walked over the indices that are non-zero at ANY q (a ballot at qi 63, whose steps are the least),
+//                      so a sparse block costs a few iterations.  The quantiser tables of the frame type sit in LDS beside the
+//                      histogram (48 KB key, 96 KB inter).  Each work group writes its histogram once, as a partial.
+//   k_rate_bits        one work group per q (one group alone reads the partials too slowly): the partials summed, the least bits of
+//                      each of the four table choices (the setup's code lengths), the extra bits and the frame header -> E[q] (int64;
+//                      the host reads back 512 bytes).
+#pragma once
+#include "thip_encode_inter.h"
+
+namespace thip {
+
+constexpr int kRateBins = 2 * 5 * 32;        // luma / chroma, Huffman group, token
+constexpr int kRateHistStride = 161;         // u16-pair words a qi in LDS: 160 + 1, so the 64 lanes spread over the 64 banks
+constexpr int kRatePartial = kRateBins + 1;  // a partial's row per qi: the bins and the side count (M, V of the inter estimate)
+constexpr int kRateTokWaves = 16;             // waves a work group of k_rate_tok (four a SIMD: the histogram allows one group a CU)
+constexpr int kRateMaxBlocksPerGroup = 960;  // a bin grows by at most 64 a block: k_rate_tok's grid keeps a group's blocks below 1020
+
+// the transform of fdct_quantize4_lds without its quantiser: on return o[h * 8 + c] holds natural position (2j + h) * 8 + c of
+// block b; the same LDS layout and contract on entry
+__device__ __forceinline__ void rate_fdct4_lds(int4 *lds, int b, int j, int o[16]) {
+  const int *ldw = reinterpret_cast<const int *>(lds);
+  int c0[8], c1[8];
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    const int w = ldw[(b * 8 + ((r + b) & 7)) * 4 + j];
+    c0[r] = sx16(sx16(w) << 2);
+    c1[r] = sx16((w >> 16) << 2);
+  }
+  if (j == 0) {
+    c0[0] = sx16(c0[0] + (c0[0] != 0) + 1);
+    c1[0] = sx16(c1[0] + 1);
+    c0[1] = sx16(c0[1] - 1);
+  }
+  fdct8(c0[0], c0[1], c0[2], c0[3], c0[4], c0[5], c0[6], c0[7]);
+  fdct8(c1[0], c1[1], c1[2], c1[3], c1[4], c1[5], c1[6], c1[7]);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  int *ldww = reinterpret_cast<int *>(lds);
+#pragma unroll
+  for (int k = 0; k < 8; k++) ldww[(b * 8 + ((k + b) & 7)) * 4 + j] = (c0[k] & 0xFFFF) | (c1[k] << 16);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int r = 2 * j + h;
+    const int4 w = lds[b * 8 + ((r + b) & 7)];
+    int v[8] = {sx16(w.x), w.x >> 16, sx16(w.y), w.y >> 16, sx16(w.z), w.z >> 16, sx16(w.w), w.w >> 16};
+    fdct8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+#pragma unroll
+    for (int c = 0; c < 8; c++) o[h * 8 + c] = sx16((v[c] + 2) >> 2);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// one coefficient through oc_enc_quantize (enquant.c:228-245), table entry (d | m << 16, l) as fdct_quantize4_lds uses it
+__device__ __forceinline__ int rate_quant(int coef, uint2 e) {
+  const int d = (int)(e.x & 0xFFFFu), m = (int)e.x >> 16, l = (int)e.y;
+  int val = coef << 1;
+  if (abs(val) < d) return 0;
+  const int sg = val >> 31;
+  val += (d + sg) ^ sg;
+  return sx16(((((m * val) >> 16) + val) >> l) - sg);
+}
+
+// the table entry of rate_quant from its first word: l = the bit length of 2 d, less one (oc_iquant_init, as the host forms it)
+__device__ __forceinline__ uint2 rate_entry(uint32_t x) {
+  return make_uint2(x, (uint32_t)(31 - __builtin_clz((x & 0xFFFFu) << 1)));
+}
+
+// the four lanes of a block store its 64 coefficients (natural order) at out[0..63]
+__device__ __forceinline__ void rate_store16(int16_t *out, int j, const int o[16]) {
+  int4 *d = reinterpret_cast<int4 *>(out + 16 * j);
+  d[0] = make_int4((o[0] & 0xFFFF) | (o[1] << 16), (o[2] & 0xFFFF) | (o[3] << 16), (o[4] & 0xFFFF) | (o[5] << 16),
+                   (o[6] & 0xFFFF) | (o[7] << 16));
+  d[1] = make_int4((o[8] & 0xFFFF) | (o[9] << 16), (o[10] & 0xFFFF) | (o[11] << 16), (o[12] & 0xFFFF) | (o[13] << 16),
+                   (o[14] & 0xFFFF) | (o[15] << 16));
+}
+
+// the raster fragment fi's plane, column, row (rows from the bottom)
+__device__ __forceinline__ void rate_frag_xy(const EncPlanes &g, int fi, int &p, int &fx, int &fy) {
+  p = enc_plane_of(g, fi);
+  const int loc = fi - g.froff[p];
+  fy = loc / g.nh[p];
+  fx = loc - fy * g.nh[p];
+}
+
+// grid: ceil(4 nfrags / 256).  coef [nfrags][64] int16, natural order, raster fragment order
+__global__ __launch_bounds__(256) void k_rate_fdct_key(int16_t *coef, EncPlanes g, int64_t nfrags) {
+  __shared__ int4 s_x[4 * 128];
+  int4 *lds = s_x + (threadIdx.x >> 6) * 128;
+  const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
+  const int64_t fi = (((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2) + b;
+  if (fi < nfrags) {
+    int p, fx, fy;
+    rate_frag_xy(g, (int)fi, p, fx, fy);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int r = 2 * j + h;
+      int v[8];
+#pragma unroll
+      for (int c = 0; c < 8; c++) v[c] = enc_src_px(g, p, fx * 8 + c, fy * 8 + r) - 128;
+      lds[b * 8 + ((r + b) & 7)] = make_int4((v[0] & 0xFFFF) | (v[1] << 16), (v[2] & 0xFFFF) | (v[3] << 16),
+                                             (v[4] & 0xFFFF) | (v[5] << 16), (v[6] & 0xFFFF) | (v[7] << 16));
+    }
+  } else {
+    lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
+    lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
+  }
+  __syncthreads();
+  int o[16];
+  rate_fdct4_lds(lds, b, j, o);
+  if (fi < nfrags) rate_store16(coef + fi * 64, j, o);
+}
+
+// the macro block's word of k_rate_me: x = S0, y = Smv, z = SI, w = mvx & 0xFF | (mvy & 0xFF) << 8 (the half-pel vector)
+__device__ __forceinline__ int rate_mode(uint4 s, int lambda) {
+  int mode = (int)s.y + lambda < (int)s.x ? kEncPixMv : kEncPixNomv;
+  const int sinter = mode == kEncPixMv ? (int)s.y : (int)s.x;
+  if ((int)s.z + 4 * lambda < sinter) mode = kEncPixIntra;
+  return mode;
+}
+
+// the macro block (raster) of fragment (p, fx, fy)
+__device__ __forceinline__ int rate_mb_of(int p, int fx, int fy, int hdec, int vdec, int nmbx) {
+  const int mbx = p ? fx >> (1 - hdec) : fx >> 1, mby = p ? fy >> (1 - vdec) : fy >> 1;
+  return mby * nmbx + mbx;
+}
+
+// k_enc_me (thip_encode_inter.h) with the decision left out: the same full-pel search, half-pel refinement, S0 and SI, written as
+// rate_mode's statistics.  (A copy, so that k_enc_me and its resource line stay as they are.)
+__global__ __launch_bounds__(256) void k_rate_me(uint4 *mb_out, EncPlanes g, EncRef R, int nmbx) {
+  __shared__ uint32_t s_win[kMeWin * kMeWin / 4];
+  __shared__ uint32_t s_src[16 * 4];
+  __shared__ uint64_t s_best[4];
+  __shared__ uint32_t s_hp[8], s_s0, s_si;
+  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int mb = (int)blockIdx.x, mbx = mb % nmbx, mby = mb / nmbx, x0 = mbx * 16, y0 = mby * 16;
+  {
+    const uint8_t *pl = R.plane[0];
+    const int W = R.w[0], H = R.h[0];
+    for (int i = tid; i < kMeWin * kMeWin / 4; i += 256) {
+      const int r = i / (kMeWin / 4), c = (i - r * (kMeWin / 4)) * 4;
+      const uint8_t *row = pl + (int64_t)min(max(y0 - 16 + r, 0), H - 1) * R.stride[0];
+      uint32_t v = 0;
+#pragma unroll
+      for (int b = 0; b < 4; b++) v |= (uint32_t)row[min(max(x0 - 16 + c + b, 0), W - 1)] << (8 * b);
+      s_win[i] = v;
+    }
+  }
+  if (tid < 64) {
+    const int r = tid >> 2, c = (tid & 3) * 4;
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) v |= (uint32_t)enc_src_px(g, 0, x0 + c + b, y0 + r) << (8 * b);
+    s_src[tid] = v;
+  }
+  if (tid < 8) s_hp[tid] = 0;
+  if (tid == 8) s_si = 0;
+  __syncthreads();
+  uint64_t best = ~0ull;
+  for (int ci = tid; ci < kMeSide * kMeSide; ci += 256) {
+    const int dy = ci / kMeSide - kMeRange, dx = ci % kMeSide - kMeRange;
+    const int cc = dx + 16, q = cc >> 2, sh = cc & 3;
+    uint32_t sad = 0;
+#pragma unroll 4
+    for (int r = 0; r < 16; r++) {
+      const uint32_t *row = s_win + (r + dy + 16) * (kMeWin / 4) + q;
+      uint32_t a[5];
+#pragma unroll
+      for (int k = 0; k < 5; k++) a[k] = row[k];
+#pragma unroll
+      for (int k = 0; k < 4; k++) sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(a[k + 1], a[k], (uint32_t)sh), s_src[r * 4 + k], sad);
+    }
+    if (dx == 0 && dy == 0) s_s0 = sad;
+    const uint64_t key = (uint64_t)sad << 32 | (uint64_t)(2 * (abs(dx) + abs(dy))) << 16 | (uint64_t)ci;
+    best = key < best ? key : best;
+  }
+  best = enc_min64_wave(best);
+  if (lane == 0) s_best[w] = best;
+  if (tid >= 64 && tid < 68) {
+    const int bq = tid - 64, bx = (bq & 1) * 2, by = (bq >> 1) * 8;
+    uint32_t sum = 0;
+    for (int r = 0; r < 8; r++) sum = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], 0u, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], 0u, sum));
+    const uint32_t m = ((sum + 32) >> 6) * 0x01010101u;
+    uint32_t v = 0;
+    for (int r = 0; r < 8; r++) v = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], m, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], m, v));
+    atomicAdd(&s_si, v);
+  }
+  __syncthreads();
+  best = s_best[0];
+#pragma unroll
+  for (int k = 1; k < 4; k++) best = s_best[k] < best ? s_best[k] : best;
+  const int bci = (int)(best & 0xFFFF);
+  const int bdx = bci % kMeSide - kMeRange, bdy = bci / kMeSide - kMeRange;
+  if (tid < 128) {
+    const int hk = tid >> 4, k9 = hk < 4 ? hk : hk + 1, r = tid & 15;
+    const int mvx = 2 * bdx + k9 % 3 - 1, mvy = 2 * bdy + k9 / 3 - 1;
+    int mx, mx2, my, my2;
+    mv_axis(mvx, false, mx, mx2);
+    mv_axis(mvy, false, my, my2);
+    const uint8_t *win = reinterpret_cast<const uint8_t *>(s_win);
+    const uint8_t *ra = win + (r + my + 16) * kMeWin + mx + 16, *rb = win + (r + my + my2 + 16) * kMeWin + mx + mx2 + 16;
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(s_src) + r * 16;
+    uint32_t sad = 0;
+#pragma unroll
+    for (int c = 0; c < 16; c++) sad += (uint32_t)abs((int)src[c] - (((int)ra[c] + (int)rb[c]) >> 1));
+    atomicAdd(&s_hp[hk], sad);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t cb = (best >> 16 << 16) | 4u;
+    int bk = 4;
+    for (int hk = 0; hk < 8; hk++) {
+      const int k9 = hk < 4 ? hk : hk + 1;
+      const int mvx = 2 * bdx + k9 % 3 - 1, mvy = 2 * bdy + k9 / 3 - 1;
+      const uint64_t key = (uint64_t)s_hp[hk] << 32 | (uint64_t)(abs(mvx) + abs(mvy)) << 16 | (uint64_t)k9;
+      if (key < cb) {
+        cb = key;
+        bk = k9;
+      }
+    }
+    const int mvx = 2 * bdx + bk % 3 - 1, mvy = 2 * bdy + bk / 3 - 1;
+    mb_out[mb] = make_uint4(s_s0, (uint32_t)(cb >> 32), s_si, ((uint32_t)mvx & 0xFFu) | ((uint32_t)mvy & 0xFFu) << 8);
+  }
+}
+
+// grid: ceil(4 nfrags / 256).  coef [3][nfrags][64]: the INTRA, NOMV and MV residuals' coefficients (natural order, raster)
+__global__ __launch_bounds__(256) void k_rate_fdct_inter(int16_t *coef, EncPlanes g, EncRef R, const uint4 *mbs, int nmbx,
+                                                         int64_t nfrags) {
+  __shared__ int4 s_x[4 * 128];
+  int4 *lds = s_x + (threadIdx.x >> 6) * 128;
+  const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
+  const int64_t fi = (((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2) + b;
+  int p = 0, fx = 0, fy = 0, mvx = 0, mvy = 0;
+  if (fi < nfrags) {
+    rate_frag_xy(g, (int)fi, p, fx, fy);
+    const uint32_t w = mbs[rate_mb_of(p, fx, fy, R.hdec, R.vdec, nmbx)].w;
+    mvx = (int)(int8_t)(w & 0xFF);
+    mvy = (int)(int8_t)(w >> 8);
+  }
+  for (int v = 0; v < 3; v++) {
+    if (fi < nfrags) {
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int r = 2 * j + h, y = fy * 8 + r;
+        int px[8];
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+          const int x = fx * 8 + c;
+          px[c] = enc_src_px(g, p, x, y) - (v == 0 ? 128 : v == 1 ? enc_pred_px(R, p, x, y, 0, 0) : enc_pred_px(R, p, x, y, mvx, mvy));
+        }
+        lds[b * 8 + ((r + b) & 7)] = make_int4((px[0] & 0xFFFF) | (px[1] << 16), (px[2] & 0xFFFF) | (px[3] << 16),
+                                               (px[4] & 0xFFFF) | (px[5] << 16), (px[6] & 0xFFFF) | (px[7] << 16));
+      }
+    } else {
+      lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
+      lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    int o[16];
+    rate_fdct4_lds(lds, b, j, o);
+    if (fi < nfrags) rate_store16(coef + ((int64_t)v * nfrags + fi) * 64, j, o);
+    __syncthreads();   // (the next residual reuses the LDS)
+  }
+}
+
+// What lane q of a wave knows about block fi at q: which residual it codes (0 INTRA, 1 NOMV, 2 MV) and with which table (0..2
+// intra of the plane, 3..5 inter); key frames: always (0, plane).
+struct RateSel {
+  int var, tab, mode;
+};
+template <bool kInter>
+__device__ __forceinline__ RateSel rate_select(const uint4 *mbs, const int *lam, int p, int fx, int fy, int hdec, int vdec, int nmbx,
+                                               int q) {
+  if (!kInter) return {0, p, kEncPixIntra};
+  const int mode = rate_mode(mbs[rate_mb_of(p, fx, fy, hdec, vdec, nmbx)], lam[q]);
+  return {mode == kEncPixIntra ? 0 : mode == kEncPixNomv ? 1 : 2, (mode == kEncPixIntra ? 0 : 3) + p, mode};
+}
+
+struct RateArgs {
+  const int16_t *coef;   // [1 or 3][nfrags][64] natural order
+  const uint2 *tab;      // [6 tables][64 z][64 q]: (d | m << 16, l) of oc_enc_quantize
+  const uint4 *mbs;      // k_rate_me's words (inter)
+  const int *lam;        // [64]: the inter luma step at zig-zag index 1 of each qi
+  int nmbx, hdec, vdec;
+};
+
+// grid: ceil(nfrags / 4), one wave a block.  qdc [nfrags][64]: the quantised DC at each q; (inter) coded, cls [nfrags]: bit q =
+// coded at q, of class PREV at q
+template <bool kInter>
+__global__ __launch_bounds__(256) void k_rate_dc(int16_t *qdc, uint64_t *coded, uint64_t *cls, RateArgs a, EncPlanes g,
+                                                 int64_t nfrags) {
+  const int q = (int)threadIdx.x & 63;
+  const int64_t fi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (fi >= nfrags) return;   // (wave-uniform)
+  int p, fx, fy;
+  rate_frag_xy(g, (int)fi, p, fx, fy);
+  const RateSel s = rate_select<kInter>(a.mbs, a.lam, p, fx, fy, a.hdec, a.vdec, a.nmbx, q);
+  const int16_t *cb = a.coef + ((int64_t)s.var * nfrags + fi) * 64;
+  qdc[fi * 64 + q] = (int16_t)rate_quant(cb[0], a.tab[(s.tab * 64 + 0) * 64 + q]);
+  if (!kInter) return;
+  // a NOMV block is coded when a level is not zero: test the indices that are non-zero at qi 63 (a superset at every q)
+  const int16_t *cn = a.coef + (nfrags + fi) * 64;
+  const int cz = cn[kFZigZag[q]];   // lane z holds zig-zag index z of the NOMV residual
+  const uint2 e63 = a.tab[((3 + p) * 64 + q) * 64 + 63];
+  uint64_t m = __ballot(abs(cz << 1) >= (int)(e63.x & 0xFFFFu));
+  bool nz = false;
+  while (m) {
+    const int z = __builtin_ctzll(m);
+    m &= m - 1;
+    const int c = __shfl(cz, z);
+    nz |= rate_quant(c, a.tab[((3 + p) * 64 + z) * 64 + q]) != 0;
+  }
+  const bool isc = s.mode != kEncPixNomv || nz;
+  const uint64_t bc = __ballot(isc), bp = __ballot(s.mode != kEncPixIntra);
+  if (q == 0) {
+    coded[fi] = bc;
+    cls[fi] = bp;
+  }
+}
+
+// token t (spec 7.7) counted for lane q: bin (chroma, Huffman group of its start index z, t) of the u16-pair histogram
+__device__ __forceinline__ void rate_count(uint32_t *h, int cc, int z, int t) {
+  const int hg = z == 0 ? 0 : z <= 5 ? 1 : z <= 14 ? 2 : z <= 27 ? 3 : 4;
+  const int i = (cc * 5 + hg) * 32 + t;
+  atomicAdd(&h[i >> 1], 1u << (16 * (i & 1)));
+}
+
+// grid: nwg persistent work groups of kRateTokWaves waves; wave w of work group wg takes the blocks wg * 16 + w + k * 16 nwg (with
+// nwg >= nfrags / kRateMaxBlocksPerGroup, fewer than 1020 of them a group).  partial [nwg][64][kRatePartial] u32: the work group's
+// token histogram per q, then (inter) its side count 3 M + 12 V
+template <bool kInter>
+__global__ __launch_bounds__(64 * kRateTokWaves) void k_rate_tok(uint32_t *partial, const int16_t *qdc, const uint64_t *coded, const uint64_t *cls,
+                                                  RateArgs a, EncPlanes g, int64_t nfrags) {
+  constexpr int kTabs = kInter ? 6 : 3;
+  __shared__ uint32_t s_h[64 * kRateHistStride];
+  __shared__ uint32_t s_side[64];
+  // the quantiser entries (d | m << 16) of the tables this frame type uses, [table][z][q]: lane q reads a word of its own bank.
+  // (Read from global memory, every index a lane quantises cost a dependent round trip.)  l follows from d (rate_entry).  s_d63:
+  // the qi-63 step of each (table, z), for the ballot of the indices any q may find non-zero.
+  __shared__ uint32_t s_tab[kTabs * 64 * 64];
+  __shared__ uint32_t s_d63[kTabs * 64];
+  for (int i = (int)threadIdx.x; i < 64 * kRateHistStride; i += 64 * kRateTokWaves) s_h[i] = 0;
+  for (int i = (int)threadIdx.x; i < kTabs * 64 * 64; i += 64 * kRateTokWaves) s_tab[i] = a.tab[i].x;
+  for (int i = (int)threadIdx.x; i < kTabs * 64; i += 64 * kRateTokWaves) s_d63[i] = a.tab[i * 64 + 63].x & 0xFFFFu;
+  if (threadIdx.x < 64) s_side[threadIdx.x] = 0;
+  __syncthreads();
+  const int q = (int)threadIdx.x & 63;
+  uint32_t *h = s_h + q * kRateHistStride;
+  const int64_t step = (int64_t)gridDim.x * kRateTokWaves;
+  for (int64_t fi = (int64_t)blockIdx.x * kRateTokWaves + (threadIdx.x >> 6); fi < nfrags; fi += step) {
+    int p, fx, fy;
+    rate_frag_xy(g, (int)fi, p, fx, fy);
+    const int nh = g.nh[p];
+    const RateSel s = rate_select<kInter>(a.mbs, a.lam, p, fx, fy, a.hdec, a.vdec, a.nmbx, q);
+    const bool isc = kInter ? ((coded[fi] >> q) & 1ull) != 0 : true;
+    // DC: spec 7.8 from the neighbours coded at q in the block's class (inter: no "last DC" fallback, the predictor is then 0)
+    const uint64_t bit = 1ull << q;
+    const uint64_t mycls = kInter ? cls[fi] & bit : 0;
+    auto same = [&](int64_t f) { return !kInter || ((coded[f] & bit) && (cls[f] & bit) == mycls); };
+    int l = 0, ul = 0, u = 0, ur = 0, msk = 0;
+    if (fx > 0 && same(fi - 1)) { l = qdc[(fi - 1) * 64 + q]; msk |= 1; }
+    if (fy > 0) {
+      if (fx > 0 && same(fi - nh - 1)) { ul = qdc[(fi - nh - 1) * 64 + q]; msk |= 2; }
+      if (same(fi - nh)) { u = qdc[(fi - nh) * 64 + q]; msk |= 4; }
+      if (fx + 1 < nh && same(fi - nh + 1)) { ur = qdc[(fi - nh + 1) * 64 + q]; msk |= 8; }
+    }
+    const int dc = (int)qdc[fi * 64 + q] - enc_dc_pred(msk, l, ul, u, ur);
+    // lane z holds zig-zag index z of each residual the block may code; the indices any q may find non-zero
+    const int nvar = kInter ? 3 : 1;
+    int cz[3] = {0, 0, 0};
+    uint64_t any = 0;
+    for (int v = 0; v < nvar; v++) {
+      cz[v] = a.coef[((int64_t)v * nfrags + fi) * 64 + kFZigZag[q]];
+      const int t = v == 0 ? p : 3 + p;
+      any |= __ballot(abs(cz[v] << 1) >= (int)s_d63[t * 64 + q]);
+    }
+    any &= ~1ull;
+    const int cc = p > 0;
+    int next = 0;
+    auto emit_value = [&](int v, int z) {   // v != 0 after `next`: the tokens of enc_block_tokens
+      const int gap = z - next, av = abs(v);
+      if (av == 1 && gap >= 1 && gap <= 17) {
+        rate_count(h, cc, next, gap <= 5 ? 22 + gap : gap <= 9 ? 28 : 29);
+      } else if ((av == 2 || av == 3) && gap >= 1 && gap <= 3) {
+        rate_count(h, cc, next, gap == 1 ? 30 : 31);
+      } else {
+        if (gap > 0) rate_count(h, cc, next, gap <= 8 ? 7 : 8);
+        int t, x;
+        enc_value_token(v, t, x);
+        rate_count(h, cc, z, t);
+      }
+      next = z + 1;
+    };
+    if (isc && dc) emit_value(dc, 0);
+    while (any) {
+      const int z = __builtin_ctzll(any);
+      any &= any - 1;
+      const int c0 = __shfl(cz[0], z);
+      const int c1 = kInter ? __shfl(cz[1], z) : 0, c2 = kInter ? __shfl(cz[2], z) : 0;
+      const int lv = rate_quant(s.var == 0 ? c0 : s.var == 1 ? c1 : c2, rate_entry(s_tab[(s.tab * 64 + z) * 64 + q]));
+      if (isc && lv) emit_value(lv, z);
+    }
+    if (isc && next < 64) rate_count(h, cc, next, 0);   // the block's own EOB
+    if (kInter && p == 0 && !(fx & 1) && !(fy & 1)) {
+      // the macro block's side bits: 3 for its mode, 12 more for a vector, when one of its four luma blocks is coded
+      const uint64_t mc = coded[fi] | coded[fi + 1] | coded[fi + nh] | coded[fi + nh + 1];
+      if ((mc >> q) & 1ull) atomicAdd(&s_side[q], s.mode == kEncPixMv ? 15u : 3u);
+    }
+  }
+  __syncthreads();
+  uint32_t *out = partial + (int64_t)blockIdx.x * 64 * kRatePartial;
+  for (int i = (int)threadIdx.x; i < 64 * kRateBins; i += 64 * kRateTokWaves) {
+    const int qq = i / kRateBins, bin = i - qq * kRateBins;
+    out[qq * kRatePartial + bin] = (s_h[qq * kRateHistStride + (bin >> 1)] >> (16 * (bin & 1))) & 0xFFFFu;
+  }
+  if (threadIdx.x < 64) out[threadIdx.x * kRatePartial + kRateBins] = s_side[threadIdx.x];
+}
+
+// extra bits after each DCT token (spec Tables 7.33 / 7.38)
+__device__ constexpr uint8_t kRateExtraBits[32] = {0, 0, 0, 2, 3, 4, 12, 3, 6, 0, 0, 0, 0, 1, 1, 1,
+                                                   1, 2, 3, 4, 5, 6, 10, 1, 1, 1, 1, 1, 3, 4, 2, 3};
+
+// grid: 64 work groups of 1024 threads, one per q.  lens [80][32]: the setup's code lengths.  est [64] int64: E[q].  fixed: header bits (and, inter,
+// nfrags / 8)
+__global__ __launch_bounds__(1024) void k_rate_bits(int64_t *est, const uint32_t *partial, int nwg, const uint8_t *lens, int fixed) {
+  __shared__ uint32_t s_h[kRatePartial];
+  __shared__ uint64_t s_cost[64];
+  const int q = (int)blockIdx.x;
+  for (int i = (int)threadIdx.x; i < kRatePartial; i += 1024) s_h[i] = 0;
+  __syncthreads();
+  // the partials' rows of q, flattened: every thread's loads are independent of each other (no chain of nwg loads)
+  const int total = nwg * kRatePartial;
+#pragma unroll 4
+  for (int k = (int)threadIdx.x; k < total; k += 1024) {
+    const int w = k / kRatePartial, i = k - w * kRatePartial;
+    const uint32_t v = partial[((int64_t)w * 64 + q) * kRatePartial + i];
+    if (v) atomicAdd(&s_h[i], v);
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {   // choice c (DC luma, DC chroma, AC luma, AC chroma), table t
+    const int c = (int)threadIdx.x >> 4, t = (int)threadIdx.x & 15, ac = c >> 1, cc = c & 1;
+    uint64_t bits = 0;
+    for (int hg = ac ? 1 : 0; hg < (ac ? 5 : 1); hg++)
+      for (int tok = 0; tok < 32; tok++) bits += (uint64_t)s_h[(cc * 5 + hg) * 32 + tok] * lens[(16 * hg + t) * 32 + tok];
+    s_cost[threadIdx.x] = bits;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t e = (uint64_t)fixed + s_h[kRateBins];
+    for (int c = 0; c < 4; c++) {
+      uint64_t best = s_cost[c * 16];
+      for (int t = 1; t < 16; t++) best = s_cost[c * 16 + t] < best ? s_cost[c * 16 + t] : best;
+      e += best;
+    }
+    for (int i = 0; i < kRateBins; i++) e += (uint64_t)s_h[i] * kRateExtraBits[i & 31];
+    est[q] = (int64_t)e;
+  }
+}
+
+}  // namespace thip

@@ -1,5 +1,6 @@
 """Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): a Theora encoder whose block work runs
-on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True)."""
+on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True), at a constant quality or in bitrate
+mode (bitrate=...)."""
 import ctypes as C
 
 import numpy as np
@@ -19,6 +20,13 @@ TH_ENCCTL_THIP_GET_TIMES = 0x7204
 TH_ENCCTL_THIP_SET_INTER_FRAMES = 0x7205
 TH_ENCCTL_THIP_GET_INTER_STATS = 0x7206
 TH_ENCCTL_THIP_GET_RECON = 0x7207
+TH_ENCCTL_THIP_GET_RATE_STATS = 0x7208
+TH_ENCCTL_SET_RATE_FLAGS = 20
+TH_ENCCTL_SET_RATE_BUFFER = 22
+TH_ENCCTL_SET_BITRATE = 30
+TH_RATECTL_DROP_FRAMES = 1
+TH_RATECTL_CAP_OVERFLOW = 2
+TH_RATECTL_CAP_UNDERFLOW = 4
 MODE_NAMES = ("INTER_NOMV", "INTRA", "INTER_MV", "INTER_MV_LAST", "INTER_MV_LAST2")
 
 
@@ -37,6 +45,14 @@ class InterStats(C.Structure):
     """thip_enc_inter_stats (include/theoraenc_hip.h)."""
     _fields_ = [("key", C.c_int32), ("modes", C.c_int32 * 5), ("coded", C.c_int32 * 3), ("mode_scheme", C.c_int32),
                 ("mv_scheme", C.c_int32)]
+
+
+class RateStats(C.Structure):
+    """thip_enc_rate_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("qi", C.c_int32), ("dropped", C.c_int32), ("key", C.c_int32), ("duplicate", C.c_int32), ("target", C.c_int64),
+                ("fullness_before", C.c_int64), ("fullness_after", C.c_int64), ("spend", C.c_int64), ("estimate", C.c_int64),
+                ("actual", C.c_int64), ("probe", C.c_int64 * 64), ("corr", C.c_int64 * 2), ("probe_ms", C.c_double),
+                ("control_ms", C.c_double)]
 
 
 def make_info(w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, aspect=(1, 1), colorspace=0, bitrate=0):
@@ -62,9 +78,11 @@ class Encoder:
     """th_encode_alloc -> th_encode_flushheader x3 -> {th_encode_ycbcr_in, th_encode_packetout}*."""
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
-                 keyframe_interval=None):
+                 keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
-        TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval)."""
+        TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
+        bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
+        rate_buffer (frames, clamped to [12, 256]; the value in force is self.rate_buffer)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -85,6 +103,26 @@ class Encoder:
                 raise TheoraHipError("TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE returned %d" % rc)
         elif keyframe_interval is not None:
             raise ValueError("keyframe_interval needs inter=True (an intra-only stream is all key frames)")
+        self.rate_buffer = self.bitrate = None
+        if bitrate is not None:
+            self.set_bitrate(bitrate)
+            if rate_flags is not None:
+                rc, _ = self.ctl(TH_ENCCTL_SET_RATE_FLAGS, rate_flags)
+                if rc < 0:
+                    raise TheoraHipError("TH_ENCCTL_SET_RATE_FLAGS returned %d" % rc)
+            if rate_buffer is not None:
+                rc, self.rate_buffer = self.ctl(TH_ENCCTL_SET_RATE_BUFFER, rate_buffer)
+                if rc < 0:
+                    raise TheoraHipError("TH_ENCCTL_SET_RATE_BUFFER returned %d" % rc)
+        elif rate_flags is not None or rate_buffer is not None:
+            raise ValueError("rate_flags and rate_buffer need a bitrate")
+
+    def set_bitrate(self, bitrate):
+        """TH_ENCCTL_SET_BITRATE (a long): enters bitrate mode, or changes its target from the next frame on."""
+        rc, _ = self.ctl(TH_ENCCTL_SET_BITRATE, bitrate, C.c_long)
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_SET_BITRATE returned %d" % rc)
+        self.bitrate = bitrate
 
     def ctl(self, req, value=None, ctype=C.c_int):
         v = ctype(0 if value is None else value)
@@ -190,6 +228,16 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_RECON returned %d" % rc)
         return out
+
+    def rate_stats(self):
+        """TH_ENCCTL_THIP_GET_RATE_STATS of the last packet, as a dict (probe: E[0..63], corr: [c_key, c_inter])."""
+        s = RateStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_RATE_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_RATE_STATS returned %d" % rc)
+        d = {k: getattr(s, k) for k, _ in RateStats._fields_}
+        d["probe"], d["corr"] = list(s.probe), list(s.corr)
+        return d
 
     def device(self):
         rc, v = self.ctl(TH_ENCCTL_THIP_GET_DEVICE)

@@ -7,7 +7,11 @@ With --inter N: inter frames with a key frame every N frames (TH_ENCCTL_THIP_SET
 tests/enc_inter_ref.py; device and host times are medians over the inter frames, bytes the mean packet, PSNR the mean of the decoded
 frames.  call_ms includes the reconstruction (the encoder's own decoder) that sits between two frames.
 
-  python tools/encode_time.py [--frames 20] [--inter N] [--json out.json]
+With --bitrate B: bitrate mode at B bits a second (30 fps), key frames (intra-only) and inter frames (a key frame every --inter N,
+default 12) of the panning sequence: per frame type the medians of the probe's device time (probe_ms), the controller (control_ms),
+the frame's device stage after it (device_ms) and the whole call (call_ms), next to quality mode at the median qi chosen (q_*).
+
+  python tools/encode_time.py [--frames 20] [--inter N] [--bitrate B] [--json out.json]
 """
 import argparse
 import json
@@ -32,8 +36,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--inter", type=int, default=0)
+    ap.add_argument("--bitrate", type=int, default=0)
     ap.add_argument("--json")
     args = ap.parse_args()
+    if args.bitrate:
+        return main_bitrate(args)
     if args.inter:
         return main_inter(args)
     from tests import enc_ref
@@ -115,6 +122,55 @@ def main_inter(args):
             r = dict(size=name, quality=q, inter=args.inter, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if args.json:
+        json.dump(rows, open(args.json, "w"), indent=1)
+
+
+def _timed(e, frames, keep):
+    """Encodes frames; per frame kept by keep(stats dict): (call ms, device ms, rate stats or None)."""
+    out = []
+    for f, fr in enumerate(frames):
+        t0 = time.perf_counter()
+        e.encode(fr)
+        e.packetout(f == len(frames) - 1)
+        t1 = time.perf_counter()
+        st = e.rate_stats() if e.bitrate else None
+        if f >= 3 and keep(e, st):
+            out.append(((t1 - t0) * 1e3, e.times()[0], st))
+    return out
+
+
+def main_bitrate(args):
+    from tests import enc_inter_ref, enc_ref
+    from theora_amd.encoder import Encoder
+    rows = []
+    n = args.frames + 3
+    kf = args.inter or 12
+    for name, (w, h, pic) in SIZES.items():
+        p = pic or (0, 0, w, h)
+        frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
+                  for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
+        for kind in ("key", "inter"):
+            inter = kind == "inter"
+            want_key = not inter
+
+            def keep(e, st):
+                return not st["dropped"] and not st["duplicate"] and bool(st["key"]) == want_key
+            e = Encoder(w, h, 0, 32, pic=pic, inter=inter, keyframe_interval=kf if inter else None, bitrate=args.bitrate)
+            e.header_packets()
+            rr = _timed(e, frames, keep)
+            e.close()
+            qi = int(np.median([r[2]["qi"] for r in rr]))
+            e = Encoder(w, h, 0, qi, pic=pic, inter=inter, keyframe_interval=kf if inter else None)
+            e.header_packets()
+            qq = _timed(e, frames, lambda e, st: e.inter_stats()["key"] == want_key)
+            e.close()
+            med = lambda xs: round(float(np.median(xs)), 4)
+            r = dict(size=name, frames=kind, bitrate=args.bitrate, qi=qi, n=len(rr), call_ms=med([x[0] for x in rr]),
+                     probe_ms=med([x[2]["probe_ms"] for x in rr]), control_ms=med([x[2]["control_ms"] for x in rr]),
+                     device_ms=med([x[1] for x in rr]), q_call_ms=med([x[0] for x in qq]), q_device_ms=med([x[1] for x in qq]))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
