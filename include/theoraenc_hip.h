@@ -67,6 +67,26 @@
  *     Vectors (7.5): scheme 1 (six bits a component) when it costs fewer bits than the VLC, else the VLC.  Tokens as for key frames,
  *     over the coded blocks only.
  *
+ * All eight modes (TH_ENCCTL_THIP_SET_INTER_MODES with inter frames on), stated likewise (tests/enc_modes_ref.py restates them).  The
+ * inter frames above with these differences; with GOLD and the per-block terms left out the rule is the one above.
+ *   - References: PREV, and GOLD, the decoder's picture of the last key frame (the encoder's own decoder's THIP_FRAME_GOLD).
+ *   - Search, per macro block on luma: S0, Smv, (mvx, mvy) and SI as above.  Per luma block b (the decoder's order: bottom left,
+ *     bottom right, top left, top right), the same two stages on the 8 x 8 block against PREV: full pel over [-15, 15]^2 with the key
+ *     (SAD, 2 (|dx| + |dy|), raster index), then the eight half-pel neighbours with (SAD, |mvx| + |mvy|, 3 (hy + 1) + hx + 1), giving
+ *     Sb and (bx_b, by_b); S4 = the sum of the four Sb.  Against GOLD: G0 (vector 0), and Gmv, (gx, gy) by the macro block's two
+ *     stages.
+ *   - Mode (L as above): (1) the PREV choice above: NOMV with C = S = S0, or MV with C = Smv + L, S = Smv; (2) INTER_MV_FOUR if
+ *     S4 + 4 L < C, then C = S4 + 4 L, S = S4; (3) CG = G0 + L (GOLDEN_NOMV), or GOLDEN_MV with CG = Gmv + 2 L if Gmv + 2 L < G0 + L;
+ *     that golden mode if CG < C, with S = G0 or Gmv; (4) INTRA if SI + 4 L < S.  Ties keep the earlier choice, so no golden mode
+ *     wins while GOLD is PREV (the frame after a key frame).
+ *   - Blocks: GOLDEN_NOMV and GOLDEN_MV predict from GOLD through 0 or (gx, gy); INTER_MV_FOUR luma blocks through their own vectors,
+ *     its chroma through the vector the decoder derives (spec 7.5.2: 4:2:0 the rounded average of the four, 4:2:2 of the row's two,
+ *     4:4:4 the block's own).  Every block of an INTRA, MV, MV_FOUR, GOLDEN_NOMV or GOLDEN_MV macro block is coded; NOMV as above.
+ *   - DC: three reference classes (intra, PREV, GOLD), each with its own last coded DC.
+ *   - Modes and vectors: INTER_MV becomes INTER_MV_LAST / LAST2 as above; INTER_MV_FOUR writes its four vectors (block order) and
+ *     then last2 = last1, last1 = the fourth; GOLDEN_MV writes its vector and leaves last1 and last2 alone.  The scheme choice is the
+ *     one above over all eight modes.
+ *
  * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
  * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
  *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
@@ -97,6 +117,8 @@
  *   - The wait: in bitrate mode th_encode_ycbcr_in and TH_ENCCTL_THIP_YCBCR_IN_DEVICE queue the probe, wait on the host for its
  *     512 bytes, choose, and then queue the frame's launches at the chosen qi exactly as quality mode does at that qi (with inter
  *     frames, its own motion search with that qi's lambda).  Quality mode never waits.
+ *   - With all eight modes on, the probe is unchanged (E[q] models the five modes above); the frame is coded with the eight-mode
+ *     search at the chosen qi, and c_inter absorbs the difference.
  *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
@@ -183,6 +205,17 @@ typedef struct thip_enc_inter_stats {
 /* Extension: buf = th_ycbcr_buffer of host planes of the FRAME's size, rows top first: receives the encoder's reconstruction of the
    last frame -- the next frame's reference.  Waits for the device.  TH_EINVAL with inter frames off or before the first packet. */
 #define TH_ENCCTL_THIP_GET_RECON (0x7207)
+
+/* Extension: buf = int 0 / 1, before the first frame only (else TH_EINVAL; the call never touches the GPU): all eight macro-block
+   modes in inter frames ("All eight modes" above).  Off by default; no effect with inter frames off. */
+#define TH_ENCCTL_THIP_SET_INTER_MODES (0x7209)
+/* Extension: buf = thip_enc_mode_stats, describing the last packet th_encode_packetout returned (with the modes off too). */
+#define TH_ENCCTL_THIP_GET_MODE_STATS (0x720A)
+typedef struct thip_enc_mode_stats {
+  int32_t modes[8];      /* macro blocks per mode, the spec's numbering: INTER_NOMV, INTRA, INTER_MV, INTER_MV_LAST, INTER_MV_LAST2,
+                            GOLDEN_NOMV, GOLDEN_MV, INTER_MV_FOUR (counted as thip_enc_inter_stats counts its five) */
+  int32_t vectors;       /* motion vectors written to the packet */
+} thip_enc_mode_stats;
 
 /* Extension: buf = thip_enc_rate_stats, describing the last packet th_encode_packetout returned; TH_EINVAL outside bitrate mode. */
 #define TH_ENCCTL_THIP_GET_RATE_STATS (0x7208)

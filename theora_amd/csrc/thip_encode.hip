@@ -23,6 +23,7 @@
 #include "../../include/theoraenc_hip.h"
 #include "thip_device.h"
 #include "thip_rate.h"
+#include "thip_encode_modes.h"
 #include "thip_ctx.h"
 
 using namespace thip;
@@ -243,7 +244,8 @@ void enc_put_mv(BitW &bw, int v, int mvs) {
 // spec 7.4: the mode alphabets of schemes 1..6 (code index -> mode)
 const int kModeAlphabets[6][8] = {{3, 4, 2, 0, 1, 5, 6, 7}, {3, 4, 0, 2, 1, 5, 6, 7}, {3, 2, 4, 0, 1, 5, 6, 7},
                                   {3, 2, 0, 4, 1, 5, 6, 7}, {0, 3, 4, 2, 1, 5, 6, 7}, {0, 5, 3, 4, 2, 1, 6, 7}};
-enum { kModeNomv = 0, kModeIntra = 1, kModeMv = 2, kModeMvLast = 3, kModeMvLast2 = 4 };
+enum { kModeNomv = 0, kModeIntra = 1, kModeMv = 2, kModeMvLast = 3, kModeMvLast2 = 4, kModeGoldNomv = 5, kModeGoldMv = 6,
+       kModeMvFour = 7 };
 
 }  // namespace
 
@@ -291,6 +293,10 @@ struct th_enc_ctx : thip_ctx_head {
   th_dec_ctx *dec = nullptr;       // the reconstruction: a decoder of the encoder's own packets
   bool have_recon = false;
   thip_enc_inter_stats istats;
+  // all eight modes (TH_ENCCTL_THIP_SET_INTER_MODES): k_enc_me_all's words a macro block
+  bool modes = false;
+  uint4 *d_mb4 = nullptr, *h_mb4 = nullptr;
+  thip_enc_mode_stats mstats;
   // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
   bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
   int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
@@ -387,6 +393,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   enc_setup_init(e->setup);
   memset(&e->stats, 0, sizeof(e->stats));
   memset(&e->istats, 0, sizeof(e->istats));
+  memset(&e->mstats, 0, sizeof(e->mstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
   e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
@@ -407,13 +414,13 @@ static void enc_free_device(th_enc_ctx *e) {
                   (void **)&e->d_mask, (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr,
                   (void **)&e->d_dqi, (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls,
                   (void **)&e->d_rmbs, (void **)&e->d_rtab, (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart,
-                  (void **)&e->d_rest};
+                  (void **)&e->d_rest, (void **)&e->d_mb4};
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap,
-                    (void **)&e->h_rest};
+                    (void **)&e->h_rest, (void **)&e->h_mb4};
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -498,7 +505,7 @@ static int enc_alloc_device(th_enc_ctx *e) {
   ENC_TRY(hipMemcpy(e->d_dequant, dq.data(), dq.size() * 2, hipMemcpyHostToDevice));
   if (!e->inter) return 0;   // (nothing more exists with inter frames off)
   ENC_TRY(hipMalloc((void **)&e->d_mb, (size_t)e->nmbs * 4));
-  ENC_TRY(hipMalloc((void **)&e->d_dclast, (size_t)e->nchunks * 2 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_dclast, (size_t)e->nchunks * 3 * 4));   // (two classes, or three with all eight modes)
   ENC_TRY(hipMalloc((void **)&e->d_cmap, n));
   ENC_TRY(hipMalloc((void **)&e->d_dcr, n * 2));
   ENC_TRY(hipMalloc((void **)&e->d_dqi, 64 * 6 * 64 * 2));
@@ -526,10 +533,10 @@ static int enc_buffer_kind(const th_enc_ctx *e, const th_img_plane *y) {
   return -1;
 }
 
-// the reconstruction of the previous frame (the decoder's PREV) as the device stage reads it
-static int enc_prev_ref(th_enc_ctx *e, EncRef &R) {
+// a reference of the encoder's own decoder (PREV: the previous frame; GOLD: the last key frame) as the device stage reads it
+static int enc_ref_frame(th_enc_ctx *e, EncRef &R, int which = THIP_FRAME_PREV) {
   thip_state *st = thip_dec_backend(e->dec);
-  const int prev = st ? thip_state_ref_idx(st, THIP_FRAME_PREV) : -1;
+  const int prev = st ? thip_state_ref_idx(st, which) : -1;
   if (prev < 0) return TH_EFAULT;
   thip_plane_geom geom[3];
   if (thip_state_get_geom(st, geom, nullptr, nullptr)) return TH_EFAULT;
@@ -548,20 +555,43 @@ static int enc_prev_ref(th_enc_ctx *e, EncRef &R) {
 // the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
 static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
   EncRef R;
-  if (enc_prev_ref(e, R)) return TH_EFAULT;
+  if (enc_ref_frame(e, R)) return TH_EFAULT;
   const int64_t n = e->nfrags;
   const int lambda = enc_qstep_inter(e->setup, e->frame_qi, 1);
+  EncRef G;
+  if (e->modes) {
+    if (enc_ref_frame(e, G, THIP_FRAME_GOLD)) return TH_EFAULT;
+    if (!e->d_mb4) {   // (at the first inter frame: TH_ENCCTL_THIP_SET_INTER_MODES never touches the GPU)
+      ENC_TRY(hipMalloc((void **)&e->d_mb4, (size_t)e->nmbs * sizeof(uint4)));
+      ENC_TRY(hipHostMalloc((void **)&e->h_mb4, (size_t)e->nmbs * sizeof(uint4), hipHostMallocDefault));
+    }
+  }
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
-  ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 2 * 4, e->stream));
-  hipLaunchKernelGGL(k_enc_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb, g, R, e->nmbx, lambda);
-  ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq, e->d_cmap,
-                     e->d_dclast, e->d_small + 192, e->d_order, g, R, e->d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n);
-  ENC_TRY(hipGetLastError());
-  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
-  hipLaunchKernelGGL(k_enc_inter_dc, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast,
-                     g, n);
-  ENC_TRY(hipGetLastError());
+  if (e->modes) {   // all eight modes (thip_encode_modes.h)
+    ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 3 * 4, e->stream));
+    hipLaunchKernelGGL(k_enc_me_all, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb4, g, R, G, e->nmbx, lambda);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_enc_inter_fq_all, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                       e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, G, (const uint4 *)e->d_mb4, e->nmbx,
+                       e->d_dqi + (size_t)e->frame_qi * 384, n);
+    ENC_TRY(hipGetLastError());
+    ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+    hipLaunchKernelGGL(k_enc_inter_dc3, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap,
+                       e->d_dclast, g, n);
+    ENC_TRY(hipGetLastError());
+  } else {
+    ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 2 * 4, e->stream));
+    hipLaunchKernelGGL(k_enc_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb, g, R, e->nmbx, lambda);
+    ENC_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                       e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, e->d_mb, e->nmbx,
+                       e->d_dqi + (size_t)e->frame_qi * 384, n);
+    ENC_TRY(hipGetLastError());
+    ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+    hipLaunchKernelGGL(k_enc_inter_dc, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap,
+                       e->d_dclast, g, n);
+    ENC_TRY(hipGetLastError());
+  }
   hipLaunchKernelGGL(k_enc_inter_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
                      e->d_small + 192, e->d_levels, e->d_dcr, e->d_cmap, e->d_order, g, n);
   ENC_TRY(hipGetLastError());
@@ -571,7 +601,8 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
                      e->d_base, e->d_small, n);
   ENC_TRY(hipGetLastError());
   ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
-  ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
+  if (e->modes) ENC_TRY(hipMemcpyAsync(e->h_mb4, e->d_mb4, (size_t)e->nmbs * sizeof(uint4), hipMemcpyDeviceToHost, e->stream));
+  else ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
   e->frame_pending = true;
@@ -647,7 +678,7 @@ static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key) {
     ENC_TRY(hipGetLastError());
   } else {
     EncRef R;
-    if (enc_prev_ref(e, R)) return TH_EFAULT;
+    if (enc_ref_frame(e, R)) return TH_EFAULT;
     hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
     ENC_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_rate_fdct_inter, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, R, (const uint4 *)e->d_rmbs, e->nmbx, n);
@@ -911,7 +942,8 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
   enc_put_runs(bw, sbf, true);
   enc_put_runs(bw, blk, false);
   // 7.4: the mode of every macro block with a coded luma block; vectors equal to the last (the one before) become INTER_MV_LAST
-  // (INTER_MV_LAST2), with the bookkeeping of 7.5
+  // (INTER_MV_LAST2), with the bookkeeping of 7.5; INTER_MV_FOUR writes its four vectors and makes the last one the last,
+  // GOLDEN_MV writes its vector and leaves the bookkeeping alone
   std::vector<uint8_t> modes;
   std::vector<int> mvs;   // the vectors written: x, y
   int lx = 0, ly = 0, l2x = 0, l2y = 0;
@@ -920,11 +952,28 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
     const int mx = mb % e->nmbx, my = mb / e->nmbx, f0 = 2 * my * nh + 2 * mx;
     if (!e->h_cmap[f0] && !e->h_cmap[f0 + 1] && !e->h_cmap[f0 + nh] && !e->h_cmap[f0 + nh + 1]) {
       e->istats.modes[kModeNomv]++;
+      e->mstats.modes[kModeNomv]++;
       continue;
     }
-    const uint32_t w = e->h_mb[mb];
-    int mode = (w & 0xFF) == kEncPixIntra ? kModeIntra : (w & 0xFF) == kEncPixMv ? kModeMv : kModeNomv;
-    if (mode == kModeMv) {
+    const uint32_t w = e->modes ? e->h_mb4[mb].x : e->h_mb[mb];
+    const int pix = (int)(w & 0xFF);
+    int mode = pix == kEncPixIntra ? kModeIntra : pix == kEncPixMv ? kModeMv : pix == kEncPixGoldNomv ? kModeGoldNomv
+             : pix == kEncPixGoldMv ? kModeGoldMv : pix == kEncPixFour ? kModeMvFour : kModeNomv;
+    if (mode == kModeMvFour) {
+      const uint32_t bw4[2] = {e->h_mb4[mb].y, e->h_mb4[mb].z};
+      for (int k = 0; k < 4; k++) {
+        const uint32_t v = bw4[k >> 1] >> (16 * (k & 1));
+        mvs.push_back((int)(int8_t)v);
+        mvs.push_back((int)(int8_t)(v >> 8));
+      }
+      l2x = lx;
+      l2y = ly;
+      lx = mvs[mvs.size() - 2];
+      ly = mvs[mvs.size() - 1];
+    } else if (mode == kModeGoldMv) {
+      mvs.push_back((int)(int8_t)(w >> 8));
+      mvs.push_back((int)(int8_t)(w >> 16));
+    } else if (mode == kModeMv) {
       const int vx = (int)(int8_t)(w >> 8), vy = (int)(int8_t)(w >> 16);
       if (vx == lx && vy == ly) {
         mode = kModeMvLast;
@@ -944,8 +993,10 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
       }
     }
     modes.push_back((uint8_t)mode);
-    e->istats.modes[mode]++;
+    if (mode < 5) e->istats.modes[mode]++;   // (GET_INTER_STATS counts the five modes of the PREV-only coder)
+    e->mstats.modes[mode]++;
   }
+  e->mstats.vectors = (int32_t)(mvs.size() / 2);
   // the cheapest scheme; scheme 0's alphabet by falling frequency (ties: the lower mode); ties between schemes: the lower index
   int64_t freq[8] = {};
   for (uint8_t m : modes) freq[m]++;
@@ -1071,10 +1122,12 @@ static int enc_finish_frame(th_enc_ctx *e) {
   e->pkt.reserve(total * 2 + 16);
   BitW bw{&e->pkt};
   memset(&e->istats, 0, sizeof(e->istats));
+  memset(&e->mstats, 0, sizeof(e->mstats));
   e->istats.mode_scheme = e->istats.mv_scheme = -1;
   if (e->frame_key) {
     e->istats.key = 1;
     e->istats.modes[kModeIntra] = e->nmbs;
+    e->mstats.modes[kModeIntra] = e->nmbs;
     for (int p = 0; p < 3; p++) e->istats.coded[p] = e->nh[p] * e->nv[p];
     bw.put(0, 1);                          // data packet
     bw.put(0, 1);                          // intra frame
@@ -1203,6 +1256,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->stats.qi = e->frame_qi;
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
     memset(&e->istats, 0, sizeof(e->istats));
+    memset(&e->mstats, 0, sizeof(e->mstats));
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
   } else if (e->frame_pending) {
     e->frame_pending = false;
@@ -1228,6 +1282,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->stats.qi = e->frame_qi;
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
     memset(&e->istats, 0, sizeof(e->istats));
+    memset(&e->mstats, 0, sizeof(e->mstats));
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
   } else {
     return 0;
@@ -1340,6 +1395,16 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->inter = on;
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_INTER_MODES: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      e->modes = *(const int *)buf != 0;   // (its buffers are made at the first inter frame)
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_MODE_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_mode_stats)) return TH_EINVAL;
+      *(thip_enc_mode_stats *)buf = e->mstats;
+      return 0;
     case TH_ENCCTL_SET_BITRATE: {
       if (!buf) return TH_EINVAL;
       long v;

@@ -1,6 +1,6 @@
 """Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): a Theora encoder whose block work runs
-on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True), at a constant quality or in bitrate
-mode (bitrate=...)."""
+on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True; all eight macro-block modes with
+all_modes=True), at a constant quality or in bitrate mode (bitrate=...)."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +21,8 @@ TH_ENCCTL_THIP_SET_INTER_FRAMES = 0x7205
 TH_ENCCTL_THIP_GET_INTER_STATS = 0x7206
 TH_ENCCTL_THIP_GET_RECON = 0x7207
 TH_ENCCTL_THIP_GET_RATE_STATS = 0x7208
+TH_ENCCTL_THIP_SET_INTER_MODES = 0x7209
+TH_ENCCTL_THIP_GET_MODE_STATS = 0x720A
 TH_ENCCTL_SET_RATE_FLAGS = 20
 TH_ENCCTL_SET_RATE_BUFFER = 22
 TH_ENCCTL_SET_BITRATE = 30
@@ -28,6 +30,7 @@ TH_RATECTL_DROP_FRAMES = 1
 TH_RATECTL_CAP_OVERFLOW = 2
 TH_RATECTL_CAP_UNDERFLOW = 4
 MODE_NAMES = ("INTER_NOMV", "INTRA", "INTER_MV", "INTER_MV_LAST", "INTER_MV_LAST2")
+ALL_MODE_NAMES = MODE_NAMES + ("GOLDEN_NOMV", "GOLDEN_MV", "INTER_MV_FOUR")
 
 
 class DeviceIn(C.Structure):
@@ -45,6 +48,11 @@ class InterStats(C.Structure):
     """thip_enc_inter_stats (include/theoraenc_hip.h)."""
     _fields_ = [("key", C.c_int32), ("modes", C.c_int32 * 5), ("coded", C.c_int32 * 3), ("mode_scheme", C.c_int32),
                 ("mv_scheme", C.c_int32)]
+
+
+class ModeStats(C.Structure):
+    """thip_enc_mode_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("modes", C.c_int32 * 8), ("vectors", C.c_int32)]
 
 
 class RateStats(C.Structure):
@@ -78,11 +86,13 @@ class Encoder:
     """th_encode_alloc -> th_encode_flushheader x3 -> {th_encode_ycbcr_in, th_encode_packetout}*."""
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
-                 keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None):
+                 keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
-        rate_buffer (frames, clamped to [12, 256]; the value in force is self.rate_buffer)."""
+        rate_buffer (frames, clamped to [12, 256]; the value in force is self.rate_buffer).  all_modes: inter frames with all eight
+        macro-block modes, golden-frame prediction and four vectors a macro block among them (TH_ENCCTL_THIP_SET_INTER_MODES; needs
+        inter=True)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -103,6 +113,13 @@ class Encoder:
                 raise TheoraHipError("TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE returned %d" % rc)
         elif keyframe_interval is not None:
             raise ValueError("keyframe_interval needs inter=True (an intra-only stream is all key frames)")
+        self.all_modes = bool(all_modes)
+        if self.all_modes:
+            if not self.inter:
+                raise ValueError("all_modes needs inter=True (an intra-only stream has no inter modes)")
+            rc, _ = self.ctl(TH_ENCCTL_THIP_SET_INTER_MODES, 1)
+            if rc < 0:
+                raise TheoraHipError("TH_ENCCTL_THIP_SET_INTER_MODES returned %d" % rc)
         self.rate_buffer = self.bitrate = None
         if bitrate is not None:
             self.set_bitrate(bitrate)
@@ -213,6 +230,14 @@ class Encoder:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_INTER_STATS returned %d" % rc)
         return dict(key=bool(s.key), modes=dict(zip(MODE_NAMES, list(s.modes))), coded=list(s.coded), mode_scheme=s.mode_scheme,
                     mv_scheme=s.mv_scheme)
+
+    def mode_stats(self):
+        """TH_ENCCTL_THIP_GET_MODE_STATS of the last packet, as a dict (modes: macro blocks per name of ALL_MODE_NAMES; vectors)."""
+        s = ModeStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_MODE_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_MODE_STATS returned %d" % rc)
+        return dict(modes=dict(zip(ALL_MODE_NAMES, list(s.modes))), vectors=s.vectors)
 
     def recon(self):
         """TH_ENCCTL_THIP_GET_RECON: the encoder's reconstruction of the last frame (the next one's reference) as three uint8 numpy

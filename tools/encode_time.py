@@ -5,13 +5,14 @@ come from a separate `rocprofv3 --kernel-trace --stats -- python tools/encode_ti
 
 With --inter N: inter frames with a key frame every N frames (TH_ENCCTL_THIP_SET_INTER_FRAMES) on the panning sequence of
 tests/enc_inter_ref.py; device and host times are medians over the inter frames, bytes the mean packet, PSNR the mean of the decoded
-frames.  call_ms includes the reconstruction (the encoder's own decoder) that sits between two frames.
+frames.  call_ms includes the reconstruction (the encoder's own decoder) that sits between two frames.  With --all-modes as well,
+each case runs with all eight macro-block modes off and then on (TH_ENCCTL_THIP_SET_INTER_MODES), in the same process.
 
 With --bitrate B: bitrate mode at B bits a second (30 fps), key frames (intra-only) and inter frames (a key frame every --inter N,
 default 12) of the panning sequence: per frame type the medians of the probe's device time (probe_ms), the controller (control_ms),
 the frame's device stage after it (device_ms) and the whole call (call_ms), next to quality mode at the median qi chosen (q_*).
 
-  python tools/encode_time.py [--frames 20] [--inter N] [--bitrate B] [--json out.json]
+  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--json out.json]
 """
 import argparse
 import json
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--inter", type=int, default=0)
     ap.add_argument("--bitrate", type=int, default=0)
+    ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
     ap.add_argument("--json")
     args = ap.parse_args()
     if args.bitrate:
@@ -94,8 +96,8 @@ def main_inter(args):
         p = pic or (0, 0, w, h)
         frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
                   for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
-        for q in (16, 48):
-            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter)
+        for q, am in [(q, am) for q in (16, 48) for am in ((False, True) if args.all_modes else (False,))]:
+            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am)
             hdr = e.header_packets()
             dev, host, wall, pkts, keys = [], [], [], [], 0
             for f in range(n):
@@ -119,7 +121,7 @@ def main_inter(args):
                 got = dec.ycbcr_out()
                 ps.append(psnr(got[0][:p[3], :p[2]], frames[f][0]))
             dec.close()
-            r = dict(size=name, quality=q, inter=args.inter, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
+            r = dict(size=name, quality=q, inter=args.inter, all_modes=am, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
             print(json.dumps(r), flush=True)
