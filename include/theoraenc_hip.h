@@ -87,6 +87,32 @@
  *     then last2 = last1, last1 = the fourth; GOLDEN_MV writes its vector and leaves last1 and last2 alone.  The scheme choice is the
  *     one above over all eight modes.
  *
+ * Block-level qi (TH_ENCCTL_THIP_SET_BLOCK_QI with a delta D in 1..31), stated likewise (tests/enc_bqi_ref.py restates it).  It applies to
+ * key frames and to inter frames with five or eight modes, in quality and in bitrate mode; everything not named here is as above.
+ *   - The frame's qi list: qis[0] = the frame's qi (the quality, or the controller's choice), then max(qis[0] - D, 0) (coarser) and
+ *     min(qis[0] + D, 63) (finer); a value equal to one already in the list is left out, so nqis is 2 or 3.
+ *   - Header (spec 7.1): after qis[0] a 1 and qis[1], then a 1 and qis[2] when nqis = 3, else a 0 (a key frame's 3 reserved bits follow).
+ *   - The qii flags (spec 7.6), after the vectors of an inter frame or straight after the header of a key frame, before the tokens,
+ *     over the coded blocks in coded order: one flag qii > 0 a block as long runs (7.2.1); then, when nqis = 3 and a block has
+ *     qii > 0, one flag qii > 1 for each block with qii > 0, as long runs.
+ *   - Dequantisation: the DC always at qis[0] (its quantiser, its prediction and the loop-filter limit are those above); the AC
+ *     coefficients at qis[qii], through the intra or inter table of the block's plane.
+ *   - The choice, per block: c = the fDCT of the block's residual under its mode (before the quantiser); for each k < nqis, with
+ *     levels l_z = oc_enc_quantize(c_z) and steps s_z of the block's table at qis[k]:
+ *       D_k = sum over z >= 1 of (c_z - l_z s_z)^2;
+ *       R_k = the bits of the block's AC tokens: the tokens of the levels at z >= 1 as if the DC were not zero (the walk starts at
+ *             index 1), and the block's own EOB when its last non-zero level lies before index 63 (or at index 1 when all are zero);
+ *             each token costs its code length in the AC table of its start index's Huffman group for the block's plane (luma,
+ *             chroma) plus its extra bits.  The AC table indices are those the previous packet of the same frame type (key, inter)
+ *             chose; before there is one, 5;
+ *       lambda = (s * s * 40) >> 7, s = the step at zig-zag index 1 of the block's table at qis[0] (about 0.31 s^2;
+ *             high-rate theory's 0.115 s^2 let the real cost rise at quality 16);
+ *       J_k = D_k + lambda R_k, plus lambda for k != 0 (a bit's worth against the flags), in 64-bit integers (no term overflows).
+ *     The block takes the least J_k; on a tie the lower k.  Its DC is quantised at qis[0] whatever it takes.
+ *   - Coded blocks in inter frames: a block of a NOMV macro block is coded when a level is not zero (the DC at qis[0], the AC at its
+ *     chosen qi).
+ *   - Bitrate mode: the probe is unchanged (it models one qi) and the controller chooses qis[0]; c_key and c_inter absorb the rest.
+ *
  * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
  * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
  *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
@@ -216,6 +242,19 @@ typedef struct thip_enc_mode_stats {
                             GOLDEN_NOMV, GOLDEN_MV, INTER_MV_FOUR (counted as thip_enc_inter_stats counts its five) */
   int32_t vectors;       /* motion vectors written to the packet */
 } thip_enc_mode_stats;
+
+/* Extension: buf = int D: 0 off (the default: every packet as without the call), 1..31 block-level qi with that delta ("Block-level
+   qi" above); any other value TH_EINVAL.  Before the first frame only (else TH_EINVAL); the call never touches the GPU. */
+#define TH_ENCCTL_THIP_SET_BLOCK_QI (0x720B)
+/* Extension: buf = thip_enc_block_qi_stats, describing the last packet th_encode_packetout returned (with block qi off too: nqis 1;
+   a zero-byte packet: all 0). */
+#define TH_ENCCTL_THIP_GET_BLOCK_QI_STATS (0x720C)
+typedef struct thip_enc_block_qi_stats {
+  int32_t nqis;            /* qi values in the frame header */
+  int32_t qis[3];          /* the list (unused entries 0) */
+  int32_t blocks[3][3];    /* coded blocks by qii (row) and plane (column) */
+  int32_t flag_bits;       /* bits the qii flags took */
+} thip_enc_block_qi_stats;
 
 /* Extension: buf = thip_enc_rate_stats, describing the last packet th_encode_packetout returned; TH_EINVAL outside bitrate mode. */
 #define TH_ENCCTL_THIP_GET_RATE_STATS (0x7208)

@@ -134,6 +134,33 @@ __device__ __forceinline__ int enc_dc_pred(int msk, int l, int ul, int u, int ur
   return pred;
 }
 
+// the tokens of the non-zero value a at zig-zag index z when the block's previous token ended before index `next` (spec 7.7.1): a
+// combined token if one fits, else a zero run (when z > next) and the smallest value token.  emit(token, extra, start index) for
+// each; returns the number of overflows (0 or 1).  The block-qi choice (thip_encode_bqi.h) counts with it.  enc_block_tokens below
+// keeps its inline form of the same rule: calling this function from it cost k_enc_inter_tok's resource line a VGPR.
+template <class Emit>
+__device__ __forceinline__ int enc_value_tokens(int a, int z, int next, Emit &&emit) {
+  const int gap = z - next, aa = abs(a), s = a < 0 ? 1 : 0;
+  if (aa == 1 && gap >= 1 && gap <= 17) {   // RUN_CAT1A / B / C
+    if (gap <= 5) emit(22 + gap, s, next);
+    else if (gap <= 9) emit(28, s << 2 | (gap - 6), next);
+    else emit(29, s << 3 | (gap - 10), next);
+  } else if ((aa == 2 || aa == 3) && gap >= 1 && gap <= 3) {   // RUN_CAT2A / B
+    if (gap == 1) emit(30, s << 1 | (aa - 2), next);
+    else emit(31, s << 2 | (aa - 2) << 1 | (gap - 2), next);
+  } else {
+    if (gap > 0) {
+      if (gap <= 8) emit(7, gap - 1, next);   // SHORT_ZRL
+      else emit(8, gap - 1, next);            // ZRL
+    }
+    int t, extra;
+    const int ovf = enc_value_token(a, t, extra) ? 0 : 1;
+    emit(t, extra, z);
+    return ovf;
+  }
+  return 0;
+}
+
 // the tokens of one block (zig-zag levels lv, its DC residual dc, plane p) as words at out, the indices at which they start in m,
 // counted per (plane, index) in s_cnt; returns the number of overflows
 __device__ __forceinline__ int enc_block_tokens(uint32_t *out, uint64_t &mask_out, uint32_t *s_cnt, const int16_t *lv, int dc, int p) {

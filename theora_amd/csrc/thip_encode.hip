@@ -24,6 +24,7 @@
 #include "thip_device.h"
 #include "thip_rate.h"
 #include "thip_encode_modes.h"
+#include "thip_encode_bqi.h"
 #include "thip_ctx.h"
 
 using namespace thip;
@@ -297,6 +298,11 @@ struct th_enc_ctx : thip_ctx_head {
   bool modes = false;
   uint4 *d_mb4 = nullptr, *h_mb4 = nullptr;
   thip_enc_mode_stats mstats;
+  // block-level qi (TH_ENCCTL_THIP_SET_BLOCK_QI): the delta (0 off), the frame's qi list, one qii a block (coded order)
+  int bqi = 0, fnqis = 1, fqis[3] = {0, 0, 0};
+  int bqi_hti[2][2] = {{5, 5}, {5, 5}};   // AC luma, AC chroma tables of the last packet of each type (key, inter)
+  uint8_t *d_qii = nullptr, *h_qii = nullptr, *d_bqbits = nullptr;
+  thip_enc_block_qi_stats bstats;
   // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
   bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
   int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
@@ -394,6 +400,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->stats, 0, sizeof(e->stats));
   memset(&e->istats, 0, sizeof(e->istats));
   memset(&e->mstats, 0, sizeof(e->mstats));
+  memset(&e->bstats, 0, sizeof(e->bstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
   e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
@@ -414,13 +421,13 @@ static void enc_free_device(th_enc_ctx *e) {
                   (void **)&e->d_mask, (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr,
                   (void **)&e->d_dqi, (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls,
                   (void **)&e->d_rmbs, (void **)&e->d_rtab, (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart,
-                  (void **)&e->d_rest, (void **)&e->d_mb4};
+                  (void **)&e->d_rest, (void **)&e->d_mb4, (void **)&e->d_qii, (void **)&e->d_bqbits};
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap,
-                    (void **)&e->h_rest, (void **)&e->h_mb4};
+                    (void **)&e->h_rest, (void **)&e->h_mb4, (void **)&e->h_qii};
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -552,8 +559,34 @@ static int enc_ref_frame(th_enc_ctx *e, EncRef &R, int which = THIP_FRAME_PREV) 
   return 0;
 }
 
+// the frame's qi list (theoraenc_hip.h, "Block-level qi"; one qi with block qi off) and, with block qi on, the selection of the
+// block-qi kernels (thip_encode_bqi.h); their buffers at the first such frame (TH_ENCCTL_THIP_SET_BLOCK_QI never touches the GPU)
+static int enc_bqi_prepare(th_enc_ctx *e, BqiSel &sel) {
+  const int q0 = e->frame_qi;
+  e->fnqis = 1;
+  e->fqis[0] = q0;
+  e->fqis[1] = e->fqis[2] = 0;
+  if (!e->bqi) return 0;
+  const int coarse = std::max(q0 - e->bqi, 0), fine = std::min(q0 + e->bqi, 63);
+  if (coarse != q0) e->fqis[e->fnqis++] = coarse;
+  if (fine != q0 && fine != coarse) e->fqis[e->fnqis++] = fine;
+  if (!e->d_qii) {
+    ENC_TRY(hipMalloc((void **)&e->d_qii, (size_t)e->nfrags));
+    ENC_TRY(hipHostMalloc((void **)&e->h_qii, (size_t)e->nfrags, hipHostMallocDefault));
+    ENC_TRY(hipMalloc((void **)&e->d_bqbits, 16 * 4 * 32));
+    std::vector<uint8_t> bits(16 * 4 * 32);   // [table][Huffman group - 1][token]: code length + extra bits
+    for (int t = 0; t < 16; t++)
+      for (int hg = 1; hg < 5; hg++)
+        for (int tok = 0; tok < 32; tok++) bits[(t * 4 + hg - 1) * 32 + tok] = (uint8_t)(e->setup.len[16 * hg + t][tok] + kExtraBits[tok]);
+    ENC_TRY(hipMemcpy(e->d_bqbits, bits.data(), bits.size(), hipMemcpyHostToDevice));
+  }
+  const int ft = e->frame_key ? 0 : 1;
+  sel = BqiSel{e->fnqis, e->fqis[0], e->fqis[1], e->fqis[2], e->bqi_hti[ft][0], e->bqi_hti[ft][1]};
+  return 0;
+}
+
 // the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
-static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
+static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel) {
   EncRef R;
   if (enc_ref_frame(e, R)) return TH_EFAULT;
   const int64_t n = e->nfrags;
@@ -571,9 +604,14 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
     ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 3 * 4, e->stream));
     hipLaunchKernelGGL(k_enc_me_all, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb4, g, R, G, e->nmbx, lambda);
     ENC_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_enc_inter_fq_all, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                       e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, G, (const uint4 *)e->d_mb4, e->nmbx,
-                       e->d_dqi + (size_t)e->frame_qi * 384, n);
+    if (e->bqi)
+      hipLaunchKernelGGL(k_enc_inter_fq_all_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels,
+                         e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, G, (const uint4 *)e->d_mb4,
+                         e->nmbx, e->d_dqi, e->d_bqbits, sel, n);
+    else
+      hipLaunchKernelGGL(k_enc_inter_fq_all, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                         e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, G, (const uint4 *)e->d_mb4, e->nmbx,
+                         e->d_dqi + (size_t)e->frame_qi * 384, n);
     ENC_TRY(hipGetLastError());
     ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
     hipLaunchKernelGGL(k_enc_inter_dc3, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap,
@@ -583,9 +621,14 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
     ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 2 * 4, e->stream));
     hipLaunchKernelGGL(k_enc_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb, g, R, e->nmbx, lambda);
     ENC_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                       e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, e->d_mb, e->nmbx,
-                       e->d_dqi + (size_t)e->frame_qi * 384, n);
+    if (e->bqi)
+      hipLaunchKernelGGL(k_enc_inter_fq_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                         e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, (const uint32_t *)e->d_mb, e->nmbx,
+                         e->d_dqi, e->d_bqbits, sel, n);
+    else
+      hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                         e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, e->d_mb, e->nmbx,
+                         e->d_dqi + (size_t)e->frame_qi * 384, n);
     ENC_TRY(hipGetLastError());
     ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
     hipLaunchKernelGGL(k_enc_inter_dc, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap,
@@ -604,6 +647,7 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g) {
   if (e->modes) ENC_TRY(hipMemcpyAsync(e->h_mb4, e->d_mb4, (size_t)e->nmbs * sizeof(uint4), hipMemcpyDeviceToHost, e->stream));
   else ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
   e->frame_pending = true;
   e->dups_left = e->dup_next;
@@ -842,10 +886,16 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     }
     e->frame_qi = qi;
   }
-  if (!e->frame_key) return enc_queue_inter(e, g);
+  BqiSel sel{};
+  if (enc_bqi_prepare(e, sel)) return TH_EFAULT;
+  if (!e->frame_key) return enc_queue_inter(e, g, sel);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
-  hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                     e->d_small + 192, e->d_order, g, e->d_dequant + (size_t)e->frame_qi * 192, n);
+  if (e->bqi)
+    hipLaunchKernelGGL(k_enc_intra_fq_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                       e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, sel, n);
+  else
+    hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                       e->d_small + 192, e->d_order, g, e->d_dequant + (size_t)e->frame_qi * 192, n);
   ENC_TRY(hipGetLastError());
   ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
   hipLaunchKernelGGL(k_enc_intra_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
@@ -857,6 +907,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
                      e->d_base, e->d_small, n);
   ENC_TRY(hipGetLastError());
   ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
+  if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
   e->frame_pending = true;
   e->dups_left = e->dup_next;
@@ -1037,6 +1088,39 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
   e->istats.mv_scheme = mvsch;
 }
 
+// spec 7.1: the frame's qi list, qis[0] first, each further one behind a 1, a 0 after the last when there are fewer than three
+static void enc_put_qis(const th_enc_ctx *e, BitW &bw) {
+  bw.put((uint32_t)e->fqis[0], 6);
+  for (int k = 1; k < e->fnqis; k++) {
+    bw.put(1, 1);
+    bw.put((uint32_t)e->fqis[k], 6);
+  }
+  if (e->fnqis < 3) bw.put(0, 1);
+}
+
+// spec 7.6: the qii flags of the coded blocks in coded order (h_qii; every block of a key frame, h_cmap's of an inter frame), as long
+// runs: qii > 0 for each, then, with three qis, qii > 1 for those with qii > 0.  Fills e->bstats.
+static void enc_put_qiis(th_enc_ctx *e, BitW &bw) {
+  thip_enc_block_qi_stats &s = e->bstats;
+  memset(&s, 0, sizeof(s));
+  s.nqis = e->fnqis;
+  for (int k = 0; k < 3; k++) s.qis[k] = k < e->fnqis ? e->fqis[k] : 0;
+  std::vector<uint8_t> f1, f2;
+  for (int k = 0; k < e->nfrags; k++) {
+    const int fi = e->coded_order[k];
+    if (!e->frame_key && !e->h_cmap[fi]) continue;
+    const int q = e->fnqis > 1 ? e->h_qii[k] : 0, p = fi >= e->froff[2] ? 2 : fi >= e->froff[1] ? 1 : 0;
+    s.blocks[q][p]++;
+    f1.push_back(q > 0);
+    if (q > 0) f2.push_back(q > 1);
+  }
+  if (e->fnqis < 2) return;
+  const int64_t b0 = (int64_t)bw.out->size() * 8 + bw.n;
+  enc_put_runs(bw, f1, true);
+  if (e->fnqis == 3) enc_put_runs(bw, f2, true);
+  s.flag_bits = (int32_t)((int64_t)bw.out->size() * 8 + bw.n - b0);
+}
+
 // the packet of the frame queued on the device: EOB runs merged, tables chosen, bits written
 static int enc_finish_frame(th_enc_ctx *e) {
   EncDeviceGuard g(e->device);
@@ -1131,9 +1215,9 @@ static int enc_finish_frame(th_enc_ctx *e) {
     for (int p = 0; p < 3; p++) e->istats.coded[p] = e->nh[p] * e->nv[p];
     bw.put(0, 1);                          // data packet
     bw.put(0, 1);                          // intra frame
-    bw.put((uint32_t)e->frame_qi, 6);      // one qi
-    bw.put(0, 1);
+    enc_put_qis(e, bw);
     bw.put(0, 3);                          // reserved
+    enc_put_qiis(e, bw);
   } else {
     for (int p = 0; p < 3; p++)
       for (int f = e->froff[p]; f < e->froff[p] + e->nh[p] * e->nv[p]; f++) e->istats.coded[p] += e->h_cmap[f] != 0;
@@ -1145,14 +1229,17 @@ static int enc_finish_frame(th_enc_ctx *e) {
       for (int c = 0; c < 4; c++) e->stats.huff[c] = -1;
       e->stats.overflow = 0;
       e->stats.qi = e->frame_qi;
+      memset(&e->bstats, 0, sizeof(e->bstats));
       return 0;
     }
     bw.put(0, 1);                          // data packet
     bw.put(1, 1);                          // inter frame
-    bw.put((uint32_t)e->frame_qi, 6);      // one qi
-    bw.put(0, 1);
+    enc_put_qis(e, bw);
     enc_put_inter_header(e, bw);
+    enc_put_qiis(e, bw);
   }
+  e->bqi_hti[e->frame_key ? 0 : 1][0] = hti[2];   // (the next block-qi choice of this frame type counts with them)
+  e->bqi_hti[e->frame_key ? 0 : 1][1] = hti[3];
   at = 0;
   for (int z = 0; z < 64; z++) {
     if (z < 2) {
@@ -1257,6 +1344,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
     memset(&e->istats, 0, sizeof(e->istats));
     memset(&e->mstats, 0, sizeof(e->mstats));
+    memset(&e->bstats, 0, sizeof(e->bstats));
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
   } else if (e->frame_pending) {
     e->frame_pending = false;
@@ -1283,6 +1371,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
     memset(&e->istats, 0, sizeof(e->istats));
     memset(&e->mstats, 0, sizeof(e->mstats));
+    memset(&e->bstats, 0, sizeof(e->bstats));
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
   } else {
     return 0;
@@ -1401,6 +1490,18 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->modes = *(const int *)buf != 0;   // (its buffers are made at the first inter frame)
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_BLOCK_QI: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int d = *(const int *)buf;
+      if (d < 0 || d > 31) return TH_EINVAL;
+      e->bqi = d;   // (its buffers are made at the first frame that uses it)
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_BLOCK_QI_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_block_qi_stats)) return TH_EINVAL;
+      *(thip_enc_block_qi_stats *)buf = e->bstats;
+      return 0;
     case TH_ENCCTL_THIP_GET_MODE_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_mode_stats)) return TH_EINVAL;
       *(thip_enc_mode_stats *)buf = e->mstats;

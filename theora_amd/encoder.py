@@ -1,6 +1,6 @@
 """Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): a Theora encoder whose block work runs
 on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True; all eight macro-block modes with
-all_modes=True), at a constant quality or in bitrate mode (bitrate=...)."""
+all_modes=True), at a constant quality or in bitrate mode (bitrate=...), with block-level qi on request (block_qi=delta)."""
 import ctypes as C
 
 import numpy as np
@@ -23,6 +23,8 @@ TH_ENCCTL_THIP_GET_RECON = 0x7207
 TH_ENCCTL_THIP_GET_RATE_STATS = 0x7208
 TH_ENCCTL_THIP_SET_INTER_MODES = 0x7209
 TH_ENCCTL_THIP_GET_MODE_STATS = 0x720A
+TH_ENCCTL_THIP_SET_BLOCK_QI = 0x720B
+TH_ENCCTL_THIP_GET_BLOCK_QI_STATS = 0x720C
 TH_ENCCTL_SET_RATE_FLAGS = 20
 TH_ENCCTL_SET_RATE_BUFFER = 22
 TH_ENCCTL_SET_BITRATE = 30
@@ -53,6 +55,11 @@ class InterStats(C.Structure):
 class ModeStats(C.Structure):
     """thip_enc_mode_stats (include/theoraenc_hip.h)."""
     _fields_ = [("modes", C.c_int32 * 8), ("vectors", C.c_int32)]
+
+
+class BlockQiStats(C.Structure):
+    """thip_enc_block_qi_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("nqis", C.c_int32), ("qis", C.c_int32 * 3), ("blocks", (C.c_int32 * 3) * 3), ("flag_bits", C.c_int32)]
 
 
 class RateStats(C.Structure):
@@ -86,13 +93,14 @@ class Encoder:
     """th_encode_alloc -> th_encode_flushheader x3 -> {th_encode_ycbcr_in, th_encode_packetout}*."""
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
-                 keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False):
+                 keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
+                 block_qi=0):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
         rate_buffer (frames, clamped to [12, 256]; the value in force is self.rate_buffer).  all_modes: inter frames with all eight
         macro-block modes, golden-frame prediction and four vectors a macro block among them (TH_ENCCTL_THIP_SET_INTER_MODES; needs
-        inter=True)."""
+        inter=True).  block_qi: block-level qi with that delta, 1..31 (TH_ENCCTL_THIP_SET_BLOCK_QI; 0 off)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -120,6 +128,11 @@ class Encoder:
             rc, _ = self.ctl(TH_ENCCTL_THIP_SET_INTER_MODES, 1)
             if rc < 0:
                 raise TheoraHipError("TH_ENCCTL_THIP_SET_INTER_MODES returned %d" % rc)
+        self.block_qi = int(block_qi)
+        if self.block_qi:
+            rc, _ = self.ctl(TH_ENCCTL_THIP_SET_BLOCK_QI, self.block_qi)
+            if rc < 0:
+                raise ValueError("block_qi must be 0..31 (TH_ENCCTL_THIP_SET_BLOCK_QI returned %d)" % rc)
         self.rate_buffer = self.bitrate = None
         if bitrate is not None:
             self.set_bitrate(bitrate)
@@ -238,6 +251,14 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_MODE_STATS returned %d" % rc)
         return dict(modes=dict(zip(ALL_MODE_NAMES, list(s.modes))), vectors=s.vectors)
+
+    def block_qi_stats(self):
+        """TH_ENCCTL_THIP_GET_BLOCK_QI_STATS of the last packet, as a dict (blocks: coded blocks [qii][plane])."""
+        s = BlockQiStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_BLOCK_QI_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_BLOCK_QI_STATS returned %d" % rc)
+        return dict(nqis=s.nqis, qis=list(s.qis), blocks=[list(r) for r in s.blocks], flag_bits=s.flag_bits)
 
     def recon(self):
         """TH_ENCCTL_THIP_GET_RECON: the encoder's reconstruction of the last frame (the next one's reference) as three uint8 numpy

@@ -12,7 +12,7 @@ With --bitrate B: bitrate mode at B bits a second (30 fps), key frames (intra-on
 default 12) of the panning sequence: per frame type the medians of the probe's device time (probe_ms), the controller (control_ms),
 the frame's device stage after it (device_ms) and the whole call (call_ms), next to quality mode at the median qi chosen (q_*).
 
-  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--json out.json]
+  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D] [--json out.json]
 """
 import argparse
 import json
@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--inter", type=int, default=0)
     ap.add_argument("--bitrate", type=int, default=0)
     ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
+    ap.add_argument("--block-qi", type=int, default=0, help="block-level qi with this delta (TH_ENCCTL_THIP_SET_BLOCK_QI)")
     ap.add_argument("--json")
     args = ap.parse_args()
     if args.bitrate:
@@ -53,7 +54,7 @@ def main():
         p = pic or (0, 0, w, h)
         frame = enc_ref.picture("natural", w, h, 0, p, picture_size=True, seed=5)
         for q in (16, 48):
-            e = Encoder(w, h, 0, q, pic=pic)
+            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi)
             hdr = e.header_packets()
             dev, host, wall = [], [], []
             for f in range(args.frames + 3):
@@ -97,7 +98,7 @@ def main_inter(args):
         frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
                   for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
         for q, am in [(q, am) for q in (16, 48) for am in ((False, True) if args.all_modes else (False,))]:
-            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am)
+            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi)
             hdr = e.header_packets()
             dev, host, wall, pkts, keys = [], [], [], [], 0
             for f in range(n):
