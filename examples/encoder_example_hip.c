@@ -7,7 +7,8 @@
  * padded to multiples of 16, the picture region at (0, 0); the picture-size planes go to th_encode_ycbcr_in as they are.  Every
  * frame is a key frame at qi = quality (default 48).  -k: inter frames; -m with it: all eight macro-block modes
  * (TH_ENCCTL_THIP_SET_INTER_MODES: golden-frame prediction, four vectors a macro block).  -b: block-level qi with that delta, 1..31
- * (TH_ENCCTL_THIP_SET_BLOCK_QI).  -V: bitrate mode at kbps * 1000 bits a second
+ * (TH_ENCCTL_THIP_SET_BLOCK_QI).  --device-pack: the packets' token bits are made on the GPU (TH_ENCCTL_THIP_SET_DEVICE_PACK; the
+ * same bytes).  -V: bitrate mode at kbps * 1000 bits a second
  * (TH_ENCCTL_SET_BITRATE), as libtheora's encoder_example -V.  Output on stdout without -o.
  */
 #include <stdio.h>
@@ -58,7 +59,7 @@ static int read_frame(FILE *in, unsigned char *buf, size_t bytes) {
 }
 
 int main(int argc, char **argv) {
-  int quality = 48, kf = 0, all_modes = 0, bqi = 0;
+  int quality = 48, kf = 0, all_modes = 0, bqi = 0, device_pack = 0;
   long kbps = 0;
   const char *in_path = NULL, *out_path = NULL;
   for (int i = 1; i < argc; i++) {
@@ -68,10 +69,11 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[i], "-V") == 0 && i + 1 < argc) kbps = atol(argv[++i]);
     else if (strcmp(argv[i], "-m") == 0) all_modes = 1;
     else if (strcmp(argv[i], "-b") == 0 && i + 1 < argc) bqi = atoi(argv[++i]);
+    else if (strcmp(argv[i], "--device-pack") == 0) device_pack = 1;
     else in_path = argv[i];
   }
   if (!in_path || (all_modes && kf <= 0)) {
-    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes]] [-b delta: block qi] [-V kbps] [-o out.ogv] in.y4m\n", argv[0]);
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes]] [-b delta: block qi] [--device-pack] [-V kbps] [-o out.ogv] in.y4m\n", argv[0]);
     return 1;
   }
   FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
@@ -124,6 +126,10 @@ int main(int argc, char **argv) {
   }
   if (bqi && th_encode_ctl(enc, TH_ENCCTL_THIP_SET_BLOCK_QI, &bqi, sizeof(bqi))) {
     fprintf(stderr, "block qi refused (delta 1..31)\n");
+    return 1;
+  }
+  if (device_pack && th_encode_ctl(enc, TH_ENCCTL_THIP_SET_DEVICE_PACK, &device_pack, sizeof(device_pack))) {
+    fprintf(stderr, "device packetiser refused\n");
     return 1;
   }
   if (kbps > 0) {   /* bitrate mode, before the headers so that the info header carries the bitrate */

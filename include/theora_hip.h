@@ -658,6 +658,10 @@ const char *thip_version_string(void);
  *   enc_fdct_lanes thip_enc_fdct8x8_batch: 4 (default) four lanes per block, 1 one block per lane
  *   enc_fq_lanes   thip_enc_fdct_quantize_batch: 4 (default) four lanes per block, 1 one block per lane
  *   enc_halfpel_lanes  thip_enc_frag_metric_halfpel_batch: 2 (default) a lane per side with four sites each, 3 a lane per dx
+ *   enc_device_pack  th_encode_alloc*: the initial setting of TH_ENCCTL_THIP_SET_DEVICE_PACK (theoraenc_hip.h): 0 (default) the host
+ *                packs the tokens, 1 the device packetiser; the packets are the same byte for byte (environment THIP_ENC_DEVICE_PACK)
+ *   enc_pack_cap   device packetiser: bytes of the device's packet buffer a frame may use before it falls back to the host packer;
+ *                0 (default) all of it, 128 bytes a block (tests lower it to see the fall-back)
  *   redo_descs   thip_decode_frames on the caller's descriptors: 1 = the caller promises that the buffers a descriptor points to stay
  *                as they are until the state's next synchronising call, so a frame whose hand-over failed is decoded again (default 0:
  *                THIP_EFAULT, see thip_synchronize)

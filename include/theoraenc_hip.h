@@ -146,6 +146,16 @@
  *   - With all eight modes on, the probe is unchanged (E[q] models the five modes above); the frame is coded with the eight-mode
  *     search at the chosen qi, and c_inter absorbs the difference.
  *
+ * Device packetiser (TH_ENCCTL_THIP_SET_DEVICE_PACK).  By default the host makes the token part of a packet: it reads the frame's
+ * tokens back, merges the EOB runs, chooses the four Huffman tables and writes the bits.  With the packetiser on, the device does
+ * those three steps by the same rules (runs cut into pieces of 4095 from their start and counted in the list of their first token;
+ * per choice the table 0..15 of least sum count x code length, a tie to the lower index; MSB-first bits, the last byte padded with
+ * zeros) and the host writes only the frame header, coded flags, modes, vectors and qii flags in front.  It changes no bit of any
+ * packet, and nothing that follows from one (statistics, the rate controller's A, the block-qi tables, the reconstruction).  A frame
+ * whose bits exceed the device's packet buffer (128 bytes a block) is packed by the host as by default and counted in
+ * thip_enc_pack_stats.fallbacks.  The packet th_encode_packetout returns then lies in pinned host memory owned by the context, valid
+ * as always until the next call on it.
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
  * extensions, YCBCR_IN_DEVICE and GET_DEVICE do.
@@ -256,6 +266,23 @@ typedef struct thip_enc_block_qi_stats {
   int32_t flag_bits;       /* bits the qii flags took */
 } thip_enc_block_qi_stats;
 
+/* Extension: buf = int 0 / 1, from the next frame on: the device packetiser ("Device packetiser" above).  Any other value, and a
+   call between th_encode_ycbcr_in and th_encode_packetout, TH_EINVAL.  The call never touches the GPU (the packetiser's buffers are
+   made at the first frame that uses it).  Initially what option "enc_device_pack" says (theora_hip.h; default 0). */
+#define TH_ENCCTL_THIP_SET_DEVICE_PACK (0x720D)
+/* Extension: buf = thip_enc_pack_stats, describing the last packet th_encode_packetout returned (a zero-byte packet: all 0 but
+   fallbacks). */
+#define TH_ENCCTL_THIP_GET_PACK_STATS (0x720E)
+typedef struct thip_enc_pack_stats {
+  int32_t device;          /* 1: the token bits were packed on the GPU; 0: by the host (the fall-back included) */
+  int32_t phase;           /* header_bits mod 8: the bit of the device's first byte at which the token bits start */
+  int64_t header_bits;     /* the host-written bits in front of the tokens: frame header, coded flags, modes, vectors, qii flags */
+  int64_t token_bits;      /* the four table indices (16 bits) and the merged tokens; header_bits + token_bits, rounded up to a
+                              byte, is the packet */
+  double pack_ms;          /* the packetiser's device time: HIP events around its launches and its read-backs (0 on the host) */
+  int32_t fallbacks;       /* frames of this context whose bits exceeded the device buffer and were packed by the host */
+  int32_t reserved;
+} thip_enc_pack_stats;
 /* Extension: buf = thip_enc_rate_stats, describing the last packet th_encode_packetout returned; TH_EINVAL outside bitrate mode. */
 #define TH_ENCCTL_THIP_GET_RATE_STATS (0x7208)
 typedef struct thip_enc_rate_stats {

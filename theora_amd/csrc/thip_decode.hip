@@ -118,6 +118,8 @@ Option g_options[] = {
     {"enc_sites_lds", 1, "thip_enc_frag_metric_sites_batch, SATD: 1 (default, round 6): k_enc_sites_satd, the source block shared by a block's three lanes through LDS; 0: k_enc_sites<SATD> (rounds 4-5)"},
     {"enc_fdct_lanes", 4, "thip_enc_fdct8x8_batch: 4 (default): four lanes per block (k_enc_fdct4); 1: one block per lane (k_enc_fdct, rounds 1-5)"},
     {"enc_fq_lanes", 4, "thip_enc_fdct_quantize_batch: 4 (default): four lanes per block (k_enc_fdct_quantize4); 1: one block per lane (round 4's kernel)"},
+    {"enc_device_pack", 0, "th_encode_alloc*: the initial setting of TH_ENCCTL_THIP_SET_DEVICE_PACK: 0 (default): the host packs the tokens; 1: the device packetiser (the same packets, byte for byte)"},
+    {"enc_pack_cap", 0, "th_encode_*, device packetiser: bytes of the device's packet buffer a frame may use before it falls back to the host packer; 0 (default): all of it, 128 bytes a block (tests lower it)"},
     {"redo_descs", 0, "thip_decode_frames on the caller's descriptors: 1: the caller promises that the buffers a descriptor points to stay as they are until the state's next synchronising call, so a frame whose hand-over failed can be decoded again like a th_decode_* frame; 0 (default): such a frame gets THIP_EFAULT"},
     {"faults_recovered", 0, "(counter) frames decoded a second time with the two passes because a bounded wait of k_recon_lf had run out"},
 };

@@ -1,7 +1,9 @@
 // thip_encode.hip -- th_encode_* (include/theoraenc_hip.h): a Theora encoder, intra-only by default, with motion-compensated inter
 // frames on request (TH_ENCCTL_THIP_SET_INTER_FRAMES).  The block work -- motion search, transform, quantiser, DC prediction, tokens
 // and their stream order -- is the device stage of thip_encode.h and thip_encode_inter.h; the host merges the EOB runs, chooses the
-// Huffman tables, the mode and vector codes and writes the bits.  The bitstream is stated in the header comment of theoraenc_hip.h.
+// Huffman tables, the mode and vector codes and writes the bits.  With TH_ENCCTL_THIP_SET_DEVICE_PACK the token part of the packet
+// (EOB runs, tables, bits) is made on the device too (thip_encode_pack.h) and the host writes the frame header only.  The bitstream
+// is stated in the header comment of theoraenc_hip.h.
 //
 // The reference of an inter frame is the encoder's own reconstruction of the previous frame, made by a th_decode_* context of this
 // library fed with every packet the encoder returns (loop filter included): the encoder's reference is then the decoder's picture by
@@ -25,6 +27,7 @@
 #include "thip_rate.h"
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
+#include "thip_encode_pack.h"
 #include "thip_ctx.h"
 
 using namespace thip;
@@ -322,7 +325,19 @@ struct th_enc_ctx : thip_ctx_head {
   int64_t *d_rest = nullptr, *h_rest = nullptr;
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
   thip_enc_rate_stats rstats;
-  // output
+  // the device packetiser (TH_ENCCTL_THIP_SET_DEVICE_PACK; thip_encode_pack.h): on from the next frame; queued for the frame pending
+  bool dpack = false, frame_dpack = false;
+  int pack_groups = 0, pack_fallbacks = 0;
+  size_t pack_cap = 0, h_pk_cap = 0;   // bytes of d_pk, h_pk
+  uint8_t *d_pk = nullptr, *h_pk = nullptr;
+  uint32_t *d_pglast = nullptr, *d_phist = nullptr, *d_pcodes = nullptr, *d_pcl = nullptr;
+  PackSum *d_pgsum = nullptr, *d_pgbase = nullptr;
+  PackRec *d_prec = nullptr, *h_prec = nullptr;
+  hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_q0 = nullptr, ev_q1 = nullptr;
+  thip_enc_pack_stats pstats;
+  // output: pkt_data is pkt's (the host packer, empty packets) or h_pk (the device packetiser)
+  const uint8_t *pkt_data = nullptr;
+  size_t pkt_size = 0;
   std::vector<uint8_t> pkt;
   std::vector<uint32_t> merged;
   thip_enc_frame_stats stats;
@@ -402,6 +417,8 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->mstats, 0, sizeof(e->mstats));
   memset(&e->bstats, 0, sizeof(e->bstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
+  memset(&e->pstats, 0, sizeof(e->pstats));
+  e->dpack = thip_option("enc_device_pack") != 0;
   e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
 }
@@ -421,20 +438,24 @@ static void enc_free_device(th_enc_ctx *e) {
                   (void **)&e->d_mask, (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr,
                   (void **)&e->d_dqi, (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls,
                   (void **)&e->d_rmbs, (void **)&e->d_rtab, (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart,
-                  (void **)&e->d_rest, (void **)&e->d_mb4, (void **)&e->d_qii, (void **)&e->d_bqbits};
+                  (void **)&e->d_rest, (void **)&e->d_mb4, (void **)&e->d_qii, (void **)&e->d_bqbits, (void **)&e->d_pk,
+                  (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
+                  (void **)&e->d_pgbase, (void **)&e->d_prec};
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap,
-                    (void **)&e->h_rest, (void **)&e->h_mb4, (void **)&e->h_qii};
+                    (void **)&e->h_rest, (void **)&e->h_mb4, (void **)&e->h_qii, (void **)&e->h_pk, (void **)&e->h_prec};
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
   }
-  e->h_tok_cap = 0;
+  e->h_tok_cap = e->h_pk_cap = e->pack_cap = 0;
+  e->pkt_data = nullptr;   // (it may have been h_pk)
+  e->pkt_size = 0;
   e->rate_dev = false;
-  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1}) {
+  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -585,6 +606,60 @@ static int enc_bqi_prepare(th_enc_ctx *e, BqiSel &sel) {
   return 0;
 }
 
+// ---- the device packetiser (thip_encode_pack.h) ----------------------------------------------------------------------------------
+// its buffers and tables, at the first frame that needs them.  The packet buffer holds 128 bytes a block -- 16 bits a coefficient,
+// twice the raw picture; the natural image of tools/encode_time.py takes 9.5 bytes a block at quality 48 -- where the worst case, 65
+// tokens of 43 bits a block, would be 350.  A frame beyond it is packed by the host.
+static int enc_pack_alloc(th_enc_ctx *e) {
+  if (e->d_pk) return 0;
+  const size_t n = (size_t)e->nfrags;
+  e->pack_groups = (int)std::min(std::max(n / 64, (size_t)1), (size_t)kPackMaxGroups);
+  const size_t cap = n * 128 + 64;
+  for (hipEvent_t *ev : {&e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1})
+    if (!*ev) ENC_TRY(hipEventCreate(ev));
+  ENC_TRY(hipMalloc((void **)&e->d_pglast, (size_t)e->pack_groups * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_phist, 320 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_pcodes, 80 * 32 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_pcl, 80 * 32 * 4));
+  ENC_TRY(hipMalloc((void **)&e->d_pgsum, (size_t)e->pack_groups * sizeof(PackSum)));
+  ENC_TRY(hipMalloc((void **)&e->d_pgbase, (size_t)e->pack_groups * sizeof(PackSum)));
+  ENC_TRY(hipMalloc((void **)&e->d_prec, sizeof(PackRec)));
+  ENC_TRY(hipHostMalloc((void **)&e->h_prec, sizeof(PackRec), hipHostMallocDefault));
+  std::vector<uint32_t> cl(80 * 32);   // code length | extra bits << 8
+  for (int h = 0; h < 80; h++)
+    for (int tok = 0; tok < 32; tok++) cl[h * 32 + tok] = (uint32_t)e->setup.len[h][tok] | (uint32_t)kExtraBits[tok] << 8;
+  ENC_TRY(hipMemcpy(e->d_pcodes, e->setup.code, 80 * 32 * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(e->d_pcl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMalloc((void **)&e->d_pk, cap));
+  e->pack_cap = cap;
+  return 0;
+}
+
+// everything that does not need the header's length, queued behind k_enc_intra_scatter with no host wait: the merge, the tables,
+// the scan, and the record's copy.  The merged words go where the tokens were before the scatter (d_tok is dead by then).
+static int enc_pack_queue(th_enc_ctx *e) {
+  e->frame_dpack = false;
+  if (!e->dpack || (uint64_t)e->nfrags * kEncTokWords >= (1ull << 31)) return 0;   // (token indices are 32-bit with room for i + 1)
+  if (enc_pack_alloc(e)) return TH_EFAULT;
+  const dim3 grid((unsigned)e->pack_groups), wg(256);
+  ENC_TRY(hipEventRecord(e->ev_k0, e->stream));
+  hipLaunchKernelGGL(k_enc_pack_edges, grid, wg, 0, e->stream, e->d_pglast, e->d_phist, (const uint32_t *)e->d_out,
+                     (const uint32_t *)e->d_small);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_pack_merge, grid, wg, 0, e->stream, e->d_tok, e->d_phist, (const uint32_t *)e->d_pglast,
+                     (const uint32_t *)e->d_out, (const uint32_t *)e->d_small);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_pack_bits, grid, wg, 0, e->stream, e->d_pgsum, e->d_prec, (const uint32_t *)e->d_tok,
+                     (const uint32_t *)e->d_phist, (const uint32_t *)e->d_pcl, (const uint32_t *)e->d_small);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_pack_scan, dim3(1), wg, 0, e->stream, e->d_pgbase, e->d_prec, (const PackSum *)e->d_pgsum, e->pack_groups);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(e->h_prec, e->d_prec, sizeof(PackRec), hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_k1, e->stream));
+  e->frame_dpack = true;
+  return 0;
+}
+
 // the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
 static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel) {
   EncRef R;
@@ -649,6 +724,7 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel)
   ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
+  if (enc_pack_queue(e)) return TH_EFAULT;
   e->frame_pending = true;
   e->dups_left = e->dup_next;
   e->dup_next = 0;
@@ -878,6 +954,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     const int qi = enc_rate_choose(e, e->frame_key, f, e->frame_key ? f : e->key);
     if (qi < 0) {
       e->frame_key = false;
+      e->frame_dpack = false;
       e->rate_dropped = true;
       e->frame_pending = true;
       e->dups_left = e->dup_next;
@@ -909,6 +986,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
   if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
+  if (enc_pack_queue(e)) return TH_EFAULT;
   e->frame_pending = true;
   e->dups_left = e->dup_next;
   e->dup_next = 0;
@@ -1121,17 +1199,62 @@ static void enc_put_qiis(th_enc_ctx *e, BitW &bw) {
   s.flag_bits = (int32_t)((int64_t)bw.out->size() * 8 + bw.n - b0);
 }
 
-// the packet of the frame queued on the device: EOB runs merged, tables chosen, bits written
-static int enc_finish_frame(th_enc_ctx *e) {
-  EncDeviceGuard g(e->device);
-  ENC_TRY(hipEventSynchronize(e->ev_done));
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, e->ev_t0, e->ev_done) == hipSuccess) e->device_ms = ms;
+// the frame header in front of the tokens (spec 7.1-7.6) and the statistics that come with it; false: an inter frame with no coded
+// block, whose packet is empty
+static bool enc_put_frame_header(th_enc_ctx *e, BitW &bw) {
+  memset(&e->istats, 0, sizeof(e->istats));
+  memset(&e->mstats, 0, sizeof(e->mstats));
+  e->istats.mode_scheme = e->istats.mv_scheme = -1;
+  if (e->frame_key) {
+    e->istats.key = 1;
+    e->istats.modes[kModeIntra] = e->nmbs;
+    e->mstats.modes[kModeIntra] = e->nmbs;
+    for (int p = 0; p < 3; p++) e->istats.coded[p] = e->nh[p] * e->nv[p];
+    bw.put(0, 1);                          // data packet
+    bw.put(0, 1);                          // intra frame
+    enc_put_qis(e, bw);
+    bw.put(0, 3);                          // reserved
+    enc_put_qiis(e, bw);
+    return true;
+  }
+  for (int p = 0; p < 3; p++)
+    for (int f = e->froff[p]; f < e->froff[p] + e->nh[p] * e->nv[p]; f++) e->istats.coded[p] += e->h_cmap[f] != 0;
+  if (!e->istats.coded[0] && !e->istats.coded[1] && !e->istats.coded[2]) return false;
+  bw.put(0, 1);                          // data packet
+  bw.put(1, 1);                          // inter frame
+  enc_put_qis(e, bw);
+  enc_put_inter_header(e, bw);
+  enc_put_qiis(e, bw);
+  return true;
+}
+
+// no block coded: the frame is the previous one, a zero-byte packet (what a duplicate is)
+static void enc_empty_packet(th_enc_ctx *e) {
+  e->pkt.clear();
+  e->pkt_data = e->pkt.data();
+  e->pkt_size = 0;
+  e->stats.tokens = e->stats.tokens_merged = e->stats.bytes = 0;
+  for (int c = 0; c < 4; c++) e->stats.huff[c] = -1;
+  e->stats.overflow = 0;
+  e->stats.qi = e->frame_qi;
+  memset(&e->bstats, 0, sizeof(e->bstats));
+}
+
+// what both packers leave behind: the frame's statistics, and the AC tables the next block-qi choice of this frame type counts with
+static void enc_packet_done(th_enc_ctx *e, size_t total, size_t merged, const int hti[4], uint32_t overflow) {
+  e->bqi_hti[e->frame_key ? 0 : 1][0] = hti[2];
+  e->bqi_hti[e->frame_key ? 0 : 1][1] = hti[3];
+  e->stats.tokens = (int64_t)total;
+  e->stats.tokens_merged = (int64_t)merged;
+  e->stats.bytes = (int64_t)e->pkt_size;
+  for (int c = 0; c < 4; c++) e->stats.huff[c] = hti[c];
+  e->stats.overflow = (int32_t)overflow;
+  e->stats.qi = e->frame_qi;
+}
+
+// the host packer: the tokens come to the host, which merges the EOB runs, chooses the tables and writes the bits
+static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
   const uint32_t *len = e->h_small;   // [3][64]
-  size_t total = 0;
-  for (int k = 0; k < 192; k++) total += len[k];
-  const uint32_t overflow = e->h_small[192];
-  if (total > (size_t)e->nfrags * kEncTokWords) return TH_EFAULT;
   if (total > e->h_tok_cap) {
     if (e->h_tok) (void)hipHostFree(e->h_tok);
     e->h_tok = nullptr;
@@ -1205,41 +1328,12 @@ static int enc_finish_frame(th_enc_ctx *e) {
   e->pkt.clear();
   e->pkt.reserve(total * 2 + 16);
   BitW bw{&e->pkt};
-  memset(&e->istats, 0, sizeof(e->istats));
-  memset(&e->mstats, 0, sizeof(e->mstats));
-  e->istats.mode_scheme = e->istats.mv_scheme = -1;
-  if (e->frame_key) {
-    e->istats.key = 1;
-    e->istats.modes[kModeIntra] = e->nmbs;
-    e->mstats.modes[kModeIntra] = e->nmbs;
-    for (int p = 0; p < 3; p++) e->istats.coded[p] = e->nh[p] * e->nv[p];
-    bw.put(0, 1);                          // data packet
-    bw.put(0, 1);                          // intra frame
-    enc_put_qis(e, bw);
-    bw.put(0, 3);                          // reserved
-    enc_put_qiis(e, bw);
-  } else {
-    for (int p = 0; p < 3; p++)
-      for (int f = e->froff[p]; f < e->froff[p] + e->nh[p] * e->nv[p]; f++) e->istats.coded[p] += e->h_cmap[f] != 0;
-    if (!e->istats.coded[0] && !e->istats.coded[1] && !e->istats.coded[2]) {
-      // no block coded: the frame is the previous one, a zero-byte packet (what a duplicate is)
-      e->pkt.clear();
-      e->host_ms = (enc_now() - t0) * 1e3;
-      e->stats.tokens = e->stats.tokens_merged = e->stats.bytes = 0;
-      for (int c = 0; c < 4; c++) e->stats.huff[c] = -1;
-      e->stats.overflow = 0;
-      e->stats.qi = e->frame_qi;
-      memset(&e->bstats, 0, sizeof(e->bstats));
-      return 0;
-    }
-    bw.put(0, 1);                          // data packet
-    bw.put(1, 1);                          // inter frame
-    enc_put_qis(e, bw);
-    enc_put_inter_header(e, bw);
-    enc_put_qiis(e, bw);
+  if (!enc_put_frame_header(e, bw)) {
+    enc_empty_packet(e);
+    e->host_ms = (enc_now() - t0) * 1e3;
+    return 0;
   }
-  e->bqi_hti[e->frame_key ? 0 : 1][0] = hti[2];   // (the next block-qi choice of this frame type counts with them)
-  e->bqi_hti[e->frame_key ? 0 : 1][1] = hti[3];
+  const int64_t hbits = (int64_t)e->pkt.size() * 8 + bw.n;
   at = 0;
   for (int z = 0; z < 64; z++) {
     if (z < 2) {
@@ -1256,15 +1350,98 @@ static int enc_finish_frame(th_enc_ctx *e) {
       }
     }
   }
+  e->pstats.header_bits = hbits;
+  e->pstats.token_bits = (int64_t)e->pkt.size() * 8 + bw.n - hbits;
+  e->pstats.phase = (int32_t)(hbits & 7);
   bw.flush();
   e->host_ms = (enc_now() - t0) * 1e3;
-  e->stats.tokens = (int64_t)total;
-  e->stats.tokens_merged = (int64_t)m.size();
-  e->stats.bytes = (int64_t)e->pkt.size();
-  for (int c = 0; c < 4; c++) e->stats.huff[c] = hti[c];
-  e->stats.overflow = (int32_t)overflow;
-  e->stats.qi = e->frame_qi;
+  e->pkt_data = e->pkt.data();
+  e->pkt_size = e->pkt.size();
+  enc_packet_done(e, total, m.size(), hti, overflow);
   return overflow ? TH_EFAULT : 0;
+}
+
+// the device packetiser's second half (enc_pack_queue queued the first): the host writes the frame header while the device merges,
+// chooses and scans; then the bits are placed from bit `phase` = header bits mod 8 of the device's byte 0 and come back behind the
+// header's whole bytes in the pinned packet buffer; the header's last partial byte is ORed into the first of them.  The host touches
+// the header's bytes only.  A frame whose bits exceed the device buffer goes to the host packer.
+static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
+  const double t0 = enc_now();
+  double waited = 0;
+  e->pkt.clear();
+  BitW bw{&e->pkt};
+  if (!enc_put_frame_header(e, bw)) {
+    enc_empty_packet(e);
+    e->host_ms = (enc_now() - t0) * 1e3;
+    return 0;
+  }
+  const size_t hb = e->pkt.size();
+  const int phase = bw.n;
+  double tw = enc_now();
+  ENC_TRY(hipEventSynchronize(e->ev_k1));
+  waited += enc_now() - tw;
+  float ms = 0;
+  const double pack1 = hipEventElapsedTime(&ms, e->ev_k0, e->ev_k1) == hipSuccess ? ms : 0.0;
+  const PackRec rec = *e->h_prec;
+  const uint64_t need = ((uint64_t)phase + 16 + rec.bits + 7) >> 3;
+  const int capopt = thip_option("enc_pack_cap");
+  const uint64_t cap = capopt > 0 ? std::min((uint64_t)capopt, (uint64_t)e->pack_cap) : (uint64_t)e->pack_cap;
+  if (rec.total != total) return TH_EFAULT;
+  if (need + 4 > cap) {   // (the memset below rounds up to a word)
+    e->pack_fallbacks++;
+    const int rc = enc_pack_host(e, total, overflow);
+    e->pstats.pack_ms = pack1;
+    return rc;
+  }
+  if (hb + need > e->h_pk_cap) {
+    if (e->h_pk) (void)hipHostFree(e->h_pk);
+    e->h_pk = nullptr;
+    e->h_pk_cap = 0;
+    const size_t hcap = std::max((size_t)(hb + need) + (size_t)(hb + need) / 4, (size_t)65536);
+    ENC_TRY(hipHostMalloc((void **)&e->h_pk, hcap, hipHostMallocDefault));
+    e->h_pk_cap = hcap;
+  }
+  const size_t nwords = (size_t)((need + 3) >> 2);
+  ENC_TRY(hipEventRecord(e->ev_q0, e->stream));
+  ENC_TRY(hipMemsetAsync(e->d_pk, 0, nwords * 4, e->stream));
+  hipLaunchKernelGGL(k_enc_pack_place, dim3((unsigned)e->pack_groups), dim3(256), 0, e->stream, (uint32_t *)e->d_pk, (uint32_t)nwords,
+                     (const PackSum *)e->d_pgbase, (const PackRec *)e->d_prec, (const uint32_t *)e->d_tok,
+                     (const uint32_t *)e->d_pcodes, (const uint32_t *)e->d_pcl, (const uint32_t *)e->d_small, phase);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(e->h_pk + hb, e->d_pk, (size_t)need, hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_q1, e->stream));
+  memcpy(e->h_pk, e->pkt.data(), hb);
+  tw = enc_now();
+  ENC_TRY(hipEventSynchronize(e->ev_q1));
+  waited += enc_now() - tw;
+  if (phase) e->h_pk[hb] |= (uint8_t)(bw.acc << (8 - phase));
+  const double pack2 = hipEventElapsedTime(&ms, e->ev_q0, e->ev_q1) == hipSuccess ? ms : 0.0;
+  e->pkt_data = e->h_pk;
+  e->pkt_size = hb + (size_t)need;
+  e->pstats.device = 1;
+  e->pstats.header_bits = (int64_t)hb * 8 + phase;
+  e->pstats.token_bits = (int64_t)rec.bits + 16;
+  e->pstats.phase = phase;
+  e->pstats.pack_ms = pack1 + pack2;
+  enc_packet_done(e, total, rec.merged, rec.hti, overflow);
+  e->host_ms = (enc_now() - t0 - waited) * 1e3;   // (the host's own work: the waits for the packetiser are in pack_ms)
+  return overflow ? TH_EFAULT : 0;
+}
+
+// the packet of the frame queued on the device: the wait for its list lengths, then one of the two packers
+static int enc_finish_frame(th_enc_ctx *e) {
+  EncDeviceGuard g(e->device);
+  ENC_TRY(hipEventSynchronize(e->ev_done));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, e->ev_t0, e->ev_done) == hipSuccess) e->device_ms = ms;
+  size_t total = 0;
+  for (int k = 0; k < 192; k++) total += e->h_small[k];
+  const uint32_t overflow = e->h_small[192];
+  if (total > (size_t)e->nfrags * kEncTokWords) return TH_EFAULT;
+  memset(&e->pstats, 0, sizeof(e->pstats));
+  const int rc = e->frame_dpack ? enc_pack_device(e, total, overflow) : enc_pack_host(e, total, overflow);
+  e->pstats.fallbacks = e->pack_fallbacks;
+  return rc;
 }
 
 static void enc_header(const th_enc_ctx *e, int which, const th_comment *tc, std::vector<uint8_t> &out);
@@ -1302,8 +1479,8 @@ static int enc_recon(th_enc_ctx *e) {
   }
   ogg_packet op;
   memset(&op, 0, sizeof(op));
-  op.packet = e->pkt.data();
-  op.bytes = (long)e->pkt.size();
+  op.packet = const_cast<uint8_t *>(e->pkt_data);
+  op.bytes = (long)e->pkt_size;
   op.granulepos = -1;
   int64_t gp = 0;
   if (th_decode_packetin(e->dec, &op, &gp) < 0) return TH_EFAULT;
@@ -1337,8 +1514,12 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->frame_pending = e->rate_dropped = false;
     ++e->cur;
     e->pkt.clear();
+    e->pkt_data = e->pkt.data();
+    e->pkt_size = 0;
     op->packet = e->pkt.data();
     op->bytes = 0;
+    memset(&e->pstats, 0, sizeof(e->pstats));
+    e->pstats.fallbacks = e->pack_fallbacks;
     memset(&e->stats, 0, sizeof(e->stats));
     e->stats.qi = e->frame_qi;
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
@@ -1352,20 +1533,24 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     if (rc) return rc;
     if (e->frame_key) e->key = e->cur + 1;
     ++e->cur;
-    if (e->inter && !e->pkt.empty()) {
+    if (e->inter && e->pkt_size) {
       const int drc = enc_recon(e);
       if (drc) return drc;
     }
-    if (e->rate) enc_rate_update(e, e->frame_key, (int64_t)e->pkt.size() * 8);
-    op->packet = e->pkt.data();
-    op->bytes = (long)e->pkt.size();
+    if (e->rate) enc_rate_update(e, e->frame_key, (int64_t)e->pkt_size * 8);
+    op->packet = const_cast<uint8_t *>(e->pkt_data);
+    op->bytes = (long)e->pkt_size;
   } else if (e->dups_left > 0) {
     e->dups_left--;
     ++e->cur;
     if (e->rate) enc_rate_dup(e);
     e->pkt.clear();
+    e->pkt_data = e->pkt.data();
+    e->pkt_size = 0;
     op->packet = e->pkt.data();
     op->bytes = 0;
+    memset(&e->pstats, 0, sizeof(e->pstats));
+    e->pstats.fallbacks = e->pack_fallbacks;
     memset(&e->stats, 0, sizeof(e->stats));
     e->stats.qi = e->frame_qi;
     e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
@@ -1498,6 +1683,17 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->bqi = d;   // (its buffers are made at the first frame that uses it)
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_DEVICE_PACK: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      const int v = *(const int *)buf;
+      if ((v != 0 && v != 1) || e->frame_pending) return TH_EINVAL;
+      e->dpack = v != 0;   // (from the next frame on; its buffers are made at the first frame that uses it)
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_PACK_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_pack_stats)) return TH_EINVAL;
+      *(thip_enc_pack_stats *)buf = e->pstats;
+      return 0;
     case TH_ENCCTL_THIP_GET_BLOCK_QI_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_block_qi_stats)) return TH_EINVAL;
       *(thip_enc_block_qi_stats *)buf = e->bstats;

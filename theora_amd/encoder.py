@@ -1,6 +1,7 @@
 """Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): a Theora encoder whose block work runs
 on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True; all eight macro-block modes with
-all_modes=True), at a constant quality or in bitrate mode (bitrate=...), with block-level qi on request (block_qi=delta)."""
+all_modes=True), at a constant quality or in bitrate mode (bitrate=...), with block-level qi on request (block_qi=delta) and the
+packets' token bits made on the GPU on request (device_pack=True)."""
 import ctypes as C
 
 import numpy as np
@@ -25,6 +26,8 @@ TH_ENCCTL_THIP_SET_INTER_MODES = 0x7209
 TH_ENCCTL_THIP_GET_MODE_STATS = 0x720A
 TH_ENCCTL_THIP_SET_BLOCK_QI = 0x720B
 TH_ENCCTL_THIP_GET_BLOCK_QI_STATS = 0x720C
+TH_ENCCTL_THIP_SET_DEVICE_PACK = 0x720D
+TH_ENCCTL_THIP_GET_PACK_STATS = 0x720E
 TH_ENCCTL_SET_RATE_FLAGS = 20
 TH_ENCCTL_SET_RATE_BUFFER = 22
 TH_ENCCTL_SET_BITRATE = 30
@@ -62,6 +65,12 @@ class BlockQiStats(C.Structure):
     _fields_ = [("nqis", C.c_int32), ("qis", C.c_int32 * 3), ("blocks", (C.c_int32 * 3) * 3), ("flag_bits", C.c_int32)]
 
 
+class PackStats(C.Structure):
+    """thip_enc_pack_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("device", C.c_int32), ("phase", C.c_int32), ("header_bits", C.c_int64), ("token_bits", C.c_int64),
+                ("pack_ms", C.c_double), ("fallbacks", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RateStats(C.Structure):
     """thip_enc_rate_stats (include/theoraenc_hip.h)."""
     _fields_ = [("qi", C.c_int32), ("dropped", C.c_int32), ("key", C.c_int32), ("duplicate", C.c_int32), ("target", C.c_int64),
@@ -94,13 +103,15 @@ class Encoder:
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
-                 block_qi=0):
+                 block_qi=0, device_pack=None):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
         rate_buffer (frames, clamped to [12, 256]; the value in force is self.rate_buffer).  all_modes: inter frames with all eight
         macro-block modes, golden-frame prediction and four vectors a macro block among them (TH_ENCCTL_THIP_SET_INTER_MODES; needs
-        inter=True).  block_qi: block-level qi with that delta, 1..31 (TH_ENCCTL_THIP_SET_BLOCK_QI; 0 off)."""
+        inter=True).  block_qi: block-level qi with that delta, 1..31 (TH_ENCCTL_THIP_SET_BLOCK_QI; 0 off).  device_pack: the device
+        packetiser on (True) or off (False) through TH_ENCCTL_THIP_SET_DEVICE_PACK -- the packets are the same either way; None (the
+        default) leaves the context as option "enc_device_pack" made it, which is off unless THIP_ENC_DEVICE_PACK says otherwise."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -133,6 +144,8 @@ class Encoder:
             rc, _ = self.ctl(TH_ENCCTL_THIP_SET_BLOCK_QI, self.block_qi)
             if rc < 0:
                 raise ValueError("block_qi must be 0..31 (TH_ENCCTL_THIP_SET_BLOCK_QI returned %d)" % rc)
+        if device_pack is not None:
+            self.set_device_pack(device_pack)
         self.rate_buffer = self.bitrate = None
         if bitrate is not None:
             self.set_bitrate(bitrate)
@@ -153,6 +166,21 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_SET_BITRATE returned %d" % rc)
         self.bitrate = bitrate
+
+    def set_device_pack(self, on):
+        """TH_ENCCTL_THIP_SET_DEVICE_PACK: from the next frame on (not between encode() and packetout())."""
+        rc, _ = self.ctl(TH_ENCCTL_THIP_SET_DEVICE_PACK, int(bool(on)))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_SET_DEVICE_PACK returned %d" % rc)
+
+    def pack_stats(self):
+        """TH_ENCCTL_THIP_GET_PACK_STATS of the last packet, as a dict."""
+        s = PackStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_PACK_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_PACK_STATS returned %d" % rc)
+        return dict(device=s.device, phase=s.phase, header_bits=s.header_bits, token_bits=s.token_bits, pack_ms=s.pack_ms,
+                    fallbacks=s.fallbacks)
 
     def ctl(self, req, value=None, ctype=C.c_int):
         v = ctype(0 if value is None else value)

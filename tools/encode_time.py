@@ -12,7 +12,10 @@ With --bitrate B: bitrate mode at B bits a second (30 fps), key frames (intra-on
 default 12) of the panning sequence: per frame type the medians of the probe's device time (probe_ms), the controller (control_ms),
 the frame's device stage after it (device_ms) and the whole call (call_ms), next to quality mode at the median qi chosen (q_*).
 
-  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D] [--json out.json]
+With --device-pack each case runs with the device packetiser off and then on (TH_ENCCTL_THIP_SET_DEVICE_PACK), in the same process;
+pack_ms is the packetiser's own device time (TH_ENCCTL_THIP_GET_PACK_STATS), call_spread the (min, max) of the call times.
+
+  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D] [--device-pack] [--json out.json]
 """
 import argparse
 import json
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--bitrate", type=int, default=0)
     ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
     ap.add_argument("--block-qi", type=int, default=0, help="block-level qi with this delta (TH_ENCCTL_THIP_SET_BLOCK_QI)")
+    ap.add_argument("--device-pack", action="store_true", help="each case with the device packetiser off, then on")
     ap.add_argument("--json")
     args = ap.parse_args()
     if args.bitrate:
@@ -53,10 +57,10 @@ def main():
     for name, (w, h, pic) in SIZES.items():
         p = pic or (0, 0, w, h)
         frame = enc_ref.picture("natural", w, h, 0, p, picture_size=True, seed=5)
-        for q in (16, 48):
-            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi)
+        for q, dp in [(q, dp) for q in (16, 48) for dp in ((False, True) if args.device_pack else (False,))]:
+            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp)
             hdr = e.header_packets()
-            dev, host, wall = [], [], []
+            dev, host, wall, pack = [], [], [], []
             for f in range(args.frames + 3):
                 t0 = time.perf_counter()
                 e.encode(frame)
@@ -67,6 +71,7 @@ def main():
                     dev.append(d)
                     host.append(hm)
                     wall.append((t1 - t0) * 1e3)
+                    pack.append(e.pack_stats()["pack_ms"])
             st = e.stats()
             e.close()
             dec = Decoder(hdr)
@@ -81,6 +86,9 @@ def main():
             r = dict(size=name, quality=q, device_ms=round(float(np.median(dev)), 4), host_ms=round(float(np.median(host)), 4),
                      call_ms=round(float(np.median(wall)), 4), bytes=len(pkt), tokens=st["tokens"],
                      tokens_merged=st["tokens_merged"], psnr=ps)
+            if args.device_pack:
+                r.update(device_pack=dp, pack_ms=round(float(np.median(pack)), 4),
+                         call_spread=[round(float(min(wall)), 4), round(float(max(wall)), 4)])
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
@@ -97,10 +105,12 @@ def main_inter(args):
         p = pic or (0, 0, w, h)
         frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
                   for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
-        for q, am in [(q, am) for q in (16, 48) for am in ((False, True) if args.all_modes else (False,))]:
-            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi)
+        for q, am, dp in [(q, am, dp) for q in (16, 48) for am in ((False, True) if args.all_modes else (False,))
+                          for dp in ((False, True) if args.device_pack else (False,))]:
+            e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi,
+                        device_pack=dp)
             hdr = e.header_packets()
-            dev, host, wall, pkts, keys = [], [], [], [], 0
+            dev, host, wall, pkts, keys, pack = [], [], [], [], 0, []
             for f in range(n):
                 t0 = time.perf_counter()
                 e.encode(frames[f])
@@ -113,6 +123,7 @@ def main_inter(args):
                     dev.append(d)
                     host.append(hm)
                     wall.append((t1 - t0) * 1e3)
+                    pack.append(e.pack_stats()["pack_ms"])
                 keys += key
             e.close()
             dec = Decoder(hdr)
@@ -125,6 +136,9 @@ def main_inter(args):
             r = dict(size=name, quality=q, inter=args.inter, all_modes=am, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
+            if args.device_pack:
+                r.update(device_pack=dp, pack_ms=round(float(np.median(pack)), 4),
+                         call_spread=[round(float(min(wall)), 4), round(float(max(wall)), 4)])
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
