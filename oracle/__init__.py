@@ -1,7 +1,8 @@
 """ctypes binding of the CPU oracle -- TEST INFRASTRUCTURE ONLY.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this
-package.  The product (theora_amd/) never does.  PARITY UNPINNED: see theora_oracle.h.
+package.  The product (theora_amd/) never does.  Pinned to the reference codec (oracle/ref.py) by
+tests/test_reference_cpu.py: see theora_oracle.h.
 """
 import ctypes as C
 import os

@@ -4,7 +4,8 @@ An independent restatement of the NORMATIVE SPECIFICATION text of the Theora for
 (/root/reference/doc/spec/spec.tex), written from the spec's enumerated procedures and
 NOT from libtheora's C.  It exists to cross-check oracle/theora_oracle.c (which follows the
 C line by line): two restatements made from two different descriptions agreeing bit for bit
-is the strongest pin available while the reference cannot be built here (no libogg).
+is a pin that holds on every machine; where the reference itself is built (oracle/ref.py),
+tests/test_reference_cpu.py compares the oracle with it directly.
 
 Covered: the 1D/2D inverse DCT (spec.tex:6255-6593, "The Inverse DCT"), the DC-only rule
 and the per-pixel reconstruction (spec.tex:6751-7120, "The Complete Reconstruction

@@ -1,9 +1,10 @@
 /* theora_oracle.c -- TEST INFRASTRUCTURE ONLY (see theora_oracle.h).
  *
  * Plain-C restatement of the reference's per-fragment reconstruction path.
- * PARITY UNPINNED: not validated against a reference binary (the reference does not
- * build in this image: <ogg/ogg.h> is missing) and the reference ships no golden
- * vectors for this path.  Each function cites the reference lines it restates.
+ * PINNED TO THE REFERENCE: tests/test_reference_cpu.py compares every block kernel here
+ * with the reference's function of the same name and whole decoded streams with the
+ * reference decoder (oracle/ref.py builds it from the reference's sources), exactly.
+ * Each function cites the reference lines it restates.
  * The inverse DCT, reconstruction, motion-vector, loop-filter and encoder parts are restructured
  * restatements; the out-of-loop post-processing part (orc_pp_*, near the end) follows
  * decode.c:1610-1957 statement by statement on purpose -- that filter is non-normative, has no
@@ -161,7 +162,7 @@ static void idct8x8_zz10(int16_t y[64], int16_t x[64]) {
    The SSE2 legs of this file (built only into _build/libtheora_oracle_simd.so, -DORC_SIMD): own intrinsics code for the three
    hot loops -- the full 8x8 inverse transform, the three reconstruction loops and the loop filter's two edge filters -- so
    that bench.py's cpu_baseline has a figure from a VECTORISED CPU path measured on the box, beside the scalar one (BASELINE.md
-   section 4.2; the reference's own x86 path cannot be built here).  tests/test_oracle.py proves them equal to the scalar
+   section 4.2; the reference's own x86 path is not built here: oracle/ref.py builds its C path).  tests/test_oracle.py proves them equal to the scalar
    functions above and below, value for value; nothing else differs between the two libraries.
    ------------------------------------------------------------------------------------------------------------------ */
 #include <emmintrin.h>

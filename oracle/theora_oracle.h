@@ -6,16 +6,17 @@
  * (theora_amd/ + include/).  Only tests/, __graft_entry__.smoke() and the
  * cpu_baseline leg of bench.py may use it.
  *
- * PARITY UNPINNED: the reference (/root/reference, libtheora 1.2.0) cannot be
- * built in this image -- every translation unit includes <ogg/ogg.h> through
- * include/theora/codec.h:66 and libogg is not installed -- and the reference's
- * tests/ hold no golden vectors for this path.  This
- * restatement therefore follows the reference source line by line (citations
- * below are file:line into /root/reference) and is cross-checked against an
+ * PINNED TO THE REFERENCE (libtheora 1.2.0): oracle/ref.py builds the reference's
+ * own C sources into oracle/_ref/libtheora_ref.so (oracle/ref_shim/ stands in for
+ * <ogg/ogg.h>, which every translation unit includes through
+ * include/theora/codec.h:66), and tests/test_reference_cpu.py compares every block
+ * kernel below with the reference function of the same name, and whole decoded
+ * streams and the post-processing with the reference decoder, exactly.  This
+ * restatement follows the reference source line by line (citations below are
+ * file:line into the reference tree) and is also cross-checked against an
  * independent restatement of the normative specification text
  * (oracle/spec_model.py, doc/spec/spec.tex) and against a third-party decoder
- * (FFmpeg's, inside the Chromium of the kaleido package: tests/test_thirdparty_decoder.py),
- * but it has not been run against the reference binary.
+ * (FFmpeg's, inside the Chromium of the kaleido package: tests/test_thirdparty_decoder.py).
  */
 #ifndef THEORA_ORACLE_H
 #define THEORA_ORACLE_H

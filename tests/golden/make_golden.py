@@ -1,10 +1,11 @@
-"""Generates tests/golden/kernels.npz and qcif_sequence.json.
+"""Generates tests/golden/kernels.npz, qcif_sequence.json and ref_qcif_q32.npz.
 
-Provenance: these vectors come from the in-repo CPU oracle (oracle/theora_oracle.c), NOT
-from a run of the reference library -- the reference cannot be built in this image (no
-libogg headers).  They pin the oracle against accidental change and travel to the GPU box
-as fixed inputs/outputs for the HIP path.  Re-run from the repo root:
-    python tests/golden/make_golden.py
+Provenance: kernels.npz and qcif_sequence.json come from the in-repo CPU oracle (oracle/theora_oracle.c); kernels.npz is
+checked equal to the reference by tests/test_reference_cpu.py (the reference's own functions on the same inputs), and
+ref_qcif_q32.npz is made by the reference encoder and decoder themselves (reference_fixture() below; needs oracle/_ref/).
+They travel to the GPU box as fixed inputs/outputs for the HIP path.  Re-run from the repo root:
+    python tests/golden/make_golden.py                        (kernels.npz, qcif_sequence.json)
+    python tests/golden/make_golden.py --reference-fixture    (ref_qcif_q32.npz)
 """
 import json
 import os
@@ -76,5 +77,32 @@ def main():
     print("wrote", os.path.join(HERE, "kernels.npz"), os.path.getsize(os.path.join(HERE, "kernels.npz")))
 
 
+def reference_fixture():
+    """tests/golden/ref_qcif_q32.npz: SURVEY.md's config 1 (QCIF 4:2:0, 30 frames of the section 8(d) generator, quality 32, key-frame
+    interval 64) encoded by the REFERENCE encoder (oracle/ref.py; needs oracle/_ref/), the three header packets and the thirty
+    data packets end to end, their lengths and granule positions, and the reference decoder's SHA-256 of every decoded frame
+    (Y, Cb, Cr, rows top first).  Data only."""
+    from oracle import ref
+    from tests import refcmp
+    hdr, pk = refcmp.ref_encode(refcmp.lcg_frames(176, 144, 0, 30), 176, 144, 0, quality=32, kf_interval=64)
+    rd = ref.RefDecoder(hdr)
+    digests = []
+    for p, gp in pk:
+        assert rd.packetin(p) == (0, gp)
+        digests.append(refcmp.digest(rd.ycbcr_out()))
+    rd.close()
+    allp = hdr + [p for p, _ in pk]
+    path = os.path.join(HERE, "ref_qcif_q32.npz")
+    np.savez_compressed(path, data=np.frombuffer(b"".join(allp), np.uint8), lengths=np.array([len(p) for p in allp], np.int64),
+                        granulepos=np.array([g for _, g in pk], np.int64), digests=np.array(digests))
+    print("wrote", path, os.path.getsize(path))
+
+
 if __name__ == "__main__":
-    main()
+    from oracle import ref as _ref
+    if "--reference-fixture" in sys.argv[1:]:       # alone: needs oracle/_ref/ or the reference tree, leaves kernels.npz as it is
+        if not _ref.available():
+            sys.exit("no oracle/_ref/libtheora_ref.so and no reference tree: ref_qcif_q32.npz is left as it is")
+        reference_fixture()
+    else:
+        main()

@@ -3,8 +3,9 @@ packets (three header packets + data packets) together with the ground truth of 
 they mean (coded flags, modes, vectors, qi indices, coefficients, last_zzi).
 
 It is NOT an encoder: coefficients are random, not the transform of any picture.  It
-exists because the reference encoder cannot be built here and the repository holds no
-sample streams; written from the bitstream specification (doc/spec/spec.tex section 6-7)
+exists because it can ask for what no encoder produces (every syntax element, at any
+density, with ground truth); streams with an encoder's statistics come from the reference encoder
+in tests/test_reference_cpu.py and tests/test_gpu_reference.py.  Written from the bitstream specification (doc/spec/spec.tex section 6-7)
 independently of the C++ front end it tests (theora_amd/csrc/thip_frontend.cpp).  Every
 syntax element the decoder knows is exercised: all eight mode schemes, both vector
 codings, 4MV with uncoded luma blocks, 1-3 qi values, every DCT token, EOB runs crossing

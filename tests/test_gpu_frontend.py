@@ -1,8 +1,8 @@
 """End to end through the th_decode_* API: Theora packets -> the library's own front end
 (bit reader, Huffman, modes, vectors, tokens, DC un-prediction, dequantisation) -> HIP
 reconstruction -> th_decode_ycbcr_out, against the oracle fed with the generator's ground
-truth.  The packets come from tests/streamgen.py (the reference encoder cannot be built
-here and no sample streams exist)."""
+truth.  The packets come from tests/streamgen.py (reference-encoded streams against the reference
+decoder: tests/test_gpu_reference.py)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """The CPU oracle against itself, against closed forms, and against the committed golden
 vectors (tests/golden/, produced by tests/golden/make_golden.py from the oracle + the
-spec model).  PARITY UNPINNED: none of this has been compared with a reference binary."""
+spec model).  The comparison with the reference codec itself is tests/test_reference_cpu.py."""
 import os
 
 import numpy as np

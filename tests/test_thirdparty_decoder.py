@@ -4,8 +4,8 @@ an implementation independent of libtheora and of this repository) plays Ogg/The
 from tests/streamgen.py are wrapped with tests/oggmux.py, played in that browser, read back
 from a canvas, and compared with the oracle's pictures converted to RGB.
 
-What this pins, and what it does not.  It is NOT the reference decoder, so the oracle stays
-"parity unpinned" in the sense of the build contract.  But it is a decoder neither derived from
+What this pins, and what it does not.  It is NOT the reference decoder (the oracle is pinned to
+that one by tests/test_reference_cpu.py, which builds the reference itself).  But it is a decoder neither derived from
 this repository's reading of the specification nor sharing code with it, and it agrees with the
 oracle (and so with the HIP path, which equals the oracle bit for bit) to within RGB rounding on
 every frame of multi-frame sequences that use all eight coding modes, both vector codings, 4MV,

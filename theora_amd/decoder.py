@@ -9,6 +9,9 @@ from ._lib import OggPacket, ThComment, ThImgPlane, ThInfo, TheoraHipError
 
 TH_DUPFRAME = 1
 TH_DECCTL_THIP_GET_SLOT_TRACE = 0x7101
+TH_DECCTL_THIP_SET_DEVICE_DC = 0x7102
+TH_DECCTL_THIP_SET_DEVICE_TOKENS = 0x7103
+TH_DECCTL_THIP_SET_DEVICE_LISTS = 0x7104
 TH_DECCTL_THIP_PREFETCH_PACKET = 0x7105
 TH_DECCTL_THIP_GET_DEVICE = 0x7106
 TH_DECCTL_THIP_SET_HOST_OUTPUT = 0x7107
