@@ -1,6 +1,10 @@
 // thip_encode.h -- the device stage of the intra-only th_encode_* encoder (thip_encode.hip): four launches a frame, none of which
 // waits for another on the host.
 //
+// The pieces of k_enc_intra_fq -- the quantiser table entry (enc_quant_entry), a lane's two rows into LDS (enc_stage_rows), what
+// follows the quantiser (enc_fq_tail) -- are functions here: the inter, all-modes, block-qi and rate-probe kernels
+// (thip_encode_inter.h, thip_encode_modes.h, thip_encode_bqi.h, thip_rate.h) are made of the same ones.
+//
 //   k_enc_intra_fq       transform and quantise.  Four lanes a block (the layout of k_enc_fdct_quantize4, through
 //                        fdct_quantize4_lds of thip_fdct.h): each lane loads two rows of its block straight from the caller's planes (any stride or
 //                        alignment; coordinates clamped to the picture region), subtracts 128, and the block goes through the fDCT
@@ -36,43 +40,69 @@ struct EncPlanes {
 
 __device__ __forceinline__ int enc_plane_of(const EncPlanes &g, int fi) { return fi >= g.froff[2] ? 2 : fi >= g.froff[1] ? 1 : 0; }
 
-// levels [n][64] int16 (zig-zag), dcq [nfrags] int16 (raster), overflow: zeroed for k_enc_intra_tok, dequant [3][64] (zig-zag, the intra tables of the frame's qi)
-__global__ __launch_bounds__(256) void k_enc_intra_fq(int16_t *levels, int16_t *dcq, uint32_t *overflow, const int32_t *coded_order,
-                                                      EncPlanes g, const uint16_t *dequant, int64_t n) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0;   // (k_enc_intra_tok counts into it)
-  __shared__ __attribute__((aligned(16))) uint2 s_t[3 * 64];   // per plane, by natural position (see fdct_quantize4_lds)
-  if (threadIdx.x < 192) {
-    const int p = (int)threadIdx.x >> 6, z = (int)threadIdx.x & 63, pos = kFZigZag[z];
-    const uint32_t dq = dequant[p * 64 + z];
-    const uint32_t d = dq << 1;   // oc_iquant_init (enquant.c:183-191)
-    const int l = 31 - __builtin_clz(d);
-    const uint32_t t = 1u + ((1u << (16 + l)) / d);
-    const int m = (int)(int16_t)(t - 0x10000u);
-    s_t[p * 64 + pos] = make_uint2(dq | (uint32_t)(uint16_t)m << 16, (uint32_t)(l & 0xFF) | (uint32_t)z << 8);
+// the raster fragment fi's plane, column, row (rows from the bottom)
+__device__ __forceinline__ void enc_frag_xy(const EncPlanes &g, int fi, int &p, int &fx, int &fy) {
+  p = enc_plane_of(g, fi);
+  const int loc = fi - g.froff[p];
+  fy = loc / g.nh[p];
+  fx = loc - fy * g.nh[p];
+}
+
+// ---- the pieces every transform-and-quantise kernel is made of (k_enc_intra_fq here, enc_inter_fq of thip_encode_inter.h,
+// enc_fq_bqi of thip_encode_bqi.h, the probe's transforms of thip_rate.h).  Four lanes a block, sixteen blocks a wave: lane
+// 4 b + j holds rows 2j, 2j + 1 of block b; the wave's 128 int4 of LDS hold row r of block b at b * 8 + ((r + b) & 7).
+
+// oc_iquant_init (enquant.c:183-191) for the step dq: l, the bit length of 2 dq less one ...
+__host__ __device__ __forceinline__ int enc_quant_shift(uint32_t dq) { return 31 - __builtin_clz(dq << 1); }
+// ... and the whole table entry of fdct_quantize4_lds for zig-zag index z: (dq | m << 16, l | z << 8)
+__host__ __device__ __forceinline__ uint2 enc_quant_entry(uint32_t dq, int z) {
+  const int l = enc_quant_shift(dq);
+  const uint32_t t = 1u + ((1u << (16 + l)) / (dq << 1));
+  const int m = (int)(int16_t)(t - 0x10000u);
+  return make_uint2(dq | (uint32_t)(uint16_t)m << 16, (uint32_t)(l & 0xFF) | (uint32_t)z << 8);
+}
+
+// `ntabs` tables of `dequant` ([ntabs][64], zig-zag) as entries by natural position in s_t, by the whole work group
+__device__ __forceinline__ void enc_quant_tables(uint2 *s_t, const uint16_t *dequant, int ntabs) {
+  for (int i = (int)threadIdx.x; i < ntabs * 64; i += 256) {
+    const int z = i & 63;
+    s_t[(i & ~63) + kFZigZag[z]] = enc_quant_entry(dequant[i], z);
   }
-  __shared__ int4 s_x[4 * 128];
-  int4 *lds = s_x + (threadIdx.x >> 6) * 128;
-  const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
-  const int64_t b0 = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2;
-  const int64_t k = b0 + b;
-  int p = 0, fi = 0;
-  if (k < n) {
-    fi = coded_order[k];
-    p = enc_plane_of(g, fi);
-    const int loc = fi - g.froff[p], fy = loc / g.nh[p], fx = loc - fy * g.nh[p];
-    const uint8_t *src = g.src[p];
-    const int64_t stride = g.stride[p];
-    int cx[8];
+}
+
+// The source pixels of block (p, fx, fy), the picture clamped outward: the plane's scalars by value and the clamped columns, once
+// for all the block's rows (chosen a pixel at a time, the plane's members and the clamps are recomputed a pixel at a time)
+struct EncSrcBlock {
+  const uint8_t *src;
+  int64_t stride;
+  int top, ph1;   // block row r (from the BOTTOM, spec 2.2) is picture row top - r, clamped to [0, ph1]
+  int cx[8];
+};
+__device__ __forceinline__ EncSrcBlock enc_src_block(const EncPlanes &g, int p, int fx, int fy) {
+  EncSrcBlock s;
+  s.src = g.src[p];
+  s.stride = g.stride[p];
+  s.top = g.nv[p] * 8 - 1 - fy * 8 - g.py0[p];
+  s.ph1 = g.ph[p] - 1;
+  const int x0 = fx * 8 - g.px0[p], pw1 = g.pw[p] - 1;
 #pragma unroll
-    for (int c = 0; c < 8; c++) cx[c] = min(max(fx * 8 + c - g.px0[p], 0), g.pw[p] - 1);
+  for (int c = 0; c < 8; c++) s.cx[c] = min(max(x0 + c, 0), pw1);
+  return s;
+}
+__device__ __forceinline__ const uint8_t *enc_src_row(const EncSrcBlock &s, int r) {
+  return s.src + (int64_t)min(max(s.top - r, 0), s.ph1) * s.stride;
+}
+
+// a lane's two rows of its block into the wave's LDS as packed int16; row(r, v) fills v[0..7] with row r of the residual (rows from
+// the bottom).  A lane past the last block (!live) stores zeros.
+template <class Row>
+__device__ __forceinline__ void enc_stage_rows(int4 *lds, int b, int j, bool live, Row &&row) {
+  if (live) {
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-      const int r = 2 * j + h;   // block row r is plane row 8 fy + r counted from the BOTTOM (spec 2.2)
-      const int top = g.nv[p] * 8 - 1 - (fy * 8 + r);
-      const uint8_t *row = src + (int64_t)min(max(top - g.py0[p], 0), g.ph[p] - 1) * stride;
+      const int r = 2 * j + h;
       int v[8];
-#pragma unroll
-      for (int c = 0; c < 8; c++) v[c] = (int)row[cx[c]] - 128;
+      row(r, v);
       lds[b * 8 + ((r + b) & 7)] = make_int4((v[0] & 0xFFFF) | (v[1] << 16), (v[2] & 0xFFFF) | (v[3] << 16),
                                              (v[4] & 0xFFFF) | (v[5] << 16), (v[6] & 0xFFFF) | (v[7] << 16));
     }
@@ -80,15 +110,68 @@ __global__ __launch_bounds__(256) void k_enc_intra_fq(int16_t *levels, int16_t *
     lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
     lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
   }
-  __syncthreads();   // (the tables too)
-  fdct_quantize4_lds(lds, s_t + 64 * p, b, j);
+}
+
+enum { kEncPixNomv = 0, kEncPixIntra = 1, kEncPixMv = 2, kEncPixGoldNomv = 5, kEncPixGoldMv = 6, kEncPixFour = 7 };   // (the spec's mode numbers)
+__device__ __forceinline__ bool enc_pix_gold(int pix) { return pix == kEncPixGoldNomv || pix == kEncPixGoldMv; }
+
+// What follows the quantiser.  The wave's levels go out (block b0 + bb from src(bb), the lane's own block's are `own`: the wave's
+// LDS, or the block's chosen qi), the
+// quantised DC of the lane's block (zig-zag index 0 in `lds`) to dcq[fi], and with kClasses reference classes (2: intra, PREV; 3:
+// GOLD too; 0: a key frame, nothing more) the block's coded flag and class to cmap[fi] -- an INTRA or MV block is always coded, a
+// NOMV one when a level is not zero -- and the last coded fragment (+1) of its 256 raster fragments and class to dclast.
+template <int kClasses, class Src>
+__device__ __forceinline__ void enc_fq_tail(int16_t *levels, int16_t *dcq, uint8_t *cmap, uint32_t *dclast, const int4 *lds,
+                                            Src &&src, const int4 *own, int64_t b0, int64_t n, int fi, int pix) {
+  const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
   int4 *o = reinterpret_cast<int4 *>(levels) + b0 * 8;
 #pragma unroll
   for (int q = 0; q < 2; q++) {
     const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-    if (b0 + bb < n) o[idx] = lds[bb * 8 + ((pc + bb) & 7)];
+    const int4 *s = src(bb);
+    if (b0 + bb < n) o[idx] = s[bb * 8 + ((pc + bb) & 7)];
   }
-  if (j == 0 && k < n) dcq[fi] = (int16_t)lds[b * 8 + (b & 7)].x;   // zig-zag index 0 of the block
+  const bool first = j == 0 && b0 + b < n;   // the lane that writes for its block
+  if constexpr (kClasses == 0) {
+    if (first) dcq[fi] = (int16_t)lds[b * 8 + (b & 7)].x;
+  } else {
+    // any level of the block not zero: lane j looks at rows 2j, 2j + 1 of its (rotated) zig-zag pieces
+    const int4 r0 = own[b * 8 + ((2 * j + b) & 7)], r1 = own[b * 8 + ((2 * j + 1 + b) & 7)];
+    int nz = (r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w) != 0;
+    nz |= __shfl_xor(nz, 1);
+    nz |= __shfl_xor(nz, 2);
+    if (!first) return;
+    dcq[fi] = (int16_t)lds[b * 8 + (b & 7)].x;
+    const int cls = pix == kEncPixIntra ? 1 : kClasses == 3 && enc_pix_gold(pix) ? 3 : 2;
+    const bool coded = pix != kEncPixNomv || nz;
+    cmap[fi] = coded ? (uint8_t)cls : (uint8_t)0;
+    if (coded) atomicMax(&dclast[(fi >> 8) * kClasses + cls - 1], (uint32_t)fi + 1u);
+  }
+}
+
+// levels [n][64] int16 (zig-zag), dcq [nfrags] int16 (raster), overflow: zeroed for k_enc_intra_tok, dequant [3][64] (zig-zag, the intra tables of the frame's qi)
+__global__ __launch_bounds__(256) void k_enc_intra_fq(int16_t *levels, int16_t *dcq, uint32_t *overflow, const int32_t *coded_order,
+                                                      EncPlanes g, const uint16_t *dequant, int64_t n) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0;   // (k_enc_intra_tok counts into it)
+  __shared__ __attribute__((aligned(16))) uint2 s_t[3 * 64];   // per plane, by natural position (see fdct_quantize4_lds)
+  enc_quant_tables(s_t, dequant, 3);
+  __shared__ int4 s_x[4 * 128];
+  int4 *lds = s_x + (threadIdx.x >> 6) * 128;
+  const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
+  const int64_t b0 = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2;
+  const int64_t k = b0 + b;
+  const int fi = coded_order[min(k, n - 1)];   // (a lane past the last block: any block's, it stores nothing)
+  int p, fx, fy;
+  enc_frag_xy(g, fi, p, fx, fy);
+  const EncSrcBlock sb = enc_src_block(g, p, fx, fy);
+  enc_stage_rows(lds, b, j, k < n, [&](int r, int v[8]) {
+    const uint8_t *row = enc_src_row(sb, r);
+#pragma unroll
+    for (int c = 0; c < 8; c++) v[c] = (int)row[sb.cx[c]] - 128;
+  });
+  __syncthreads();   // (the tables too)
+  fdct_quantize4_lds(lds, s_t + 64 * p, b, j);
+  enc_fq_tail<0>(levels, dcq, nullptr, nullptr, lds, [=](int) { return lds; }, lds, b0, n, fi, kEncPixIntra);
 }
 
 // the smallest value token of a coefficient (spec Table 7.38); false when |v| > 580

@@ -433,20 +433,28 @@ static void enc_free_device(th_enc_ctx *e) {
   if (e->dec) th_decode_free(e->dec);
   e->dec = nullptr;
   e->have_recon = false;
-  void **dev[] = {(void **)&e->d_pix, (void **)&e->d_order, (void **)&e->d_dequant, (void **)&e->d_levels, (void **)&e->d_dcq,
-                  (void **)&e->d_tok, (void **)&e->d_cnt, (void **)&e->d_base, (void **)&e->d_small, (void **)&e->d_out,
-                  (void **)&e->d_mask, (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr,
-                  (void **)&e->d_dqi, (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls,
-                  (void **)&e->d_rmbs, (void **)&e->d_rtab, (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart,
-                  (void **)&e->d_rest, (void **)&e->d_mb4, (void **)&e->d_qii, (void **)&e->d_bqbits, (void **)&e->d_pk,
-                  (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
-                  (void **)&e->d_pgbase, (void **)&e->d_prec};
+  // one line a feature, in the order of th_enc_ctx, with the function that allocates it: a new buffer goes into that function and
+  // its line here
+  void **dev[] = {
+      (void **)&e->d_pix, (void **)&e->d_order, (void **)&e->d_dequant, (void **)&e->d_levels, (void **)&e->d_dcq, (void **)&e->d_tok,
+      (void **)&e->d_cnt, (void **)&e->d_base, (void **)&e->d_small, (void **)&e->d_out, (void **)&e->d_mask,   // enc_alloc_device
+      (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr, (void **)&e->d_dqi,       // ... inter frames
+      (void **)&e->d_mb4,                                                                                            // enc_modes_alloc
+      (void **)&e->d_qii, (void **)&e->d_bqbits,                                                                     // enc_bqi_prepare
+      (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
+      (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
+      (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
+      (void **)&e->d_pgbase, (void **)&e->d_prec};                                                                   // enc_pack_alloc
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok, (void **)&e->h_mb, (void **)&e->h_cmap,
-                    (void **)&e->h_rest, (void **)&e->h_mb4, (void **)&e->h_qii, (void **)&e->h_pk, (void **)&e->h_prec};
+  void **host[] = {(void **)&e->h_pix, (void **)&e->h_small, (void **)&e->h_tok,   // enc_alloc_device
+                   (void **)&e->h_mb, (void **)&e->h_cmap,                        // ... inter frames
+                   (void **)&e->h_mb4,                                            // enc_modes_alloc
+                   (void **)&e->h_qii,                                            // enc_bqi_prepare
+                   (void **)&e->h_rest,                                           // enc_rate_alloc
+                   (void **)&e->h_pk, (void **)&e->h_prec};                       // enc_pack_alloc
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -660,75 +668,80 @@ static int enc_pack_queue(th_enc_ctx *e) {
   return 0;
 }
 
-// the launches of an inter frame (thip_encode_inter.h) against the reconstruction of the previous frame
-static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel) {
-  EncRef R;
-  if (enc_ref_frame(e, R)) return TH_EFAULT;
+// the frame queued (or dropped) is pending for th_encode_packetout, with the duplicates asked for it
+static void enc_frame_queued(th_enc_ctx *e) {
+  e->frame_pending = true;
+  e->dups_left = e->dup_next;
+  e->dup_next = 0;
+}
+
+// everything behind the token kernel, for both frame types: the scan, the scatter, the read-backs, the device packetiser
+static int enc_queue_tail(th_enc_ctx *e) {
   const int64_t n = e->nfrags;
-  const int lambda = enc_qstep_inter(e->setup, e->frame_qi, 1);
-  EncRef G;
-  if (e->modes) {
-    if (enc_ref_frame(e, G, THIP_FRAME_GOLD)) return TH_EFAULT;
-    if (!e->d_mb4) {   // (at the first inter frame: TH_ENCCTL_THIP_SET_INTER_MODES never touches the GPU)
-      ENC_TRY(hipMalloc((void **)&e->d_mb4, (size_t)e->nmbs * sizeof(uint4)));
-      ENC_TRY(hipHostMalloc((void **)&e->h_mb4, (size_t)e->nmbs * sizeof(uint4), hipHostMallocDefault));
-    }
-  }
-  ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
-  if (e->modes) {   // all eight modes (thip_encode_modes.h)
-    ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 3 * 4, e->stream));
-    hipLaunchKernelGGL(k_enc_me_all, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb4, g, R, G, e->nmbx, lambda);
-    ENC_TRY(hipGetLastError());
-    if (e->bqi)
-      hipLaunchKernelGGL(k_enc_inter_fq_all_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels,
-                         e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, G, (const uint4 *)e->d_mb4,
-                         e->nmbx, e->d_dqi, e->d_bqbits, sel, n);
-    else
-      hipLaunchKernelGGL(k_enc_inter_fq_all, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                         e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, G, (const uint4 *)e->d_mb4, e->nmbx,
-                         e->d_dqi + (size_t)e->frame_qi * 384, n);
-    ENC_TRY(hipGetLastError());
-    ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
-    hipLaunchKernelGGL(k_enc_inter_dc3, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap,
-                       e->d_dclast, g, n);
-    ENC_TRY(hipGetLastError());
-  } else {
-    ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * 2 * 4, e->stream));
-    hipLaunchKernelGGL(k_enc_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_mb, g, R, e->nmbx, lambda);
-    ENC_TRY(hipGetLastError());
-    if (e->bqi)
-      hipLaunchKernelGGL(k_enc_inter_fq_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                         e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, (const uint32_t *)e->d_mb, e->nmbx,
-                         e->d_dqi, e->d_bqbits, sel, n);
-    else
-      hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                         e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R, e->d_mb, e->nmbx,
-                         e->d_dqi + (size_t)e->frame_qi * 384, n);
-    ENC_TRY(hipGetLastError());
-    ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
-    hipLaunchKernelGGL(k_enc_inter_dc, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap,
-                       e->d_dclast, g, n);
-    ENC_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_enc_inter_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
-                     e->d_small + 192, e->d_levels, e->d_dcr, e->d_cmap, e->d_order, g, n);
-  ENC_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_enc_intra_scan, dim3(64), dim3(256), 0, e->stream, e->d_base, e->d_small, e->d_cnt, e->nchunks);
   ENC_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_enc_intra_scatter, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_out, e->d_tok, e->d_mask,
                      e->d_base, e->d_small, n);
   ENC_TRY(hipGetLastError());
   ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
-  if (e->modes) ENC_TRY(hipMemcpyAsync(e->h_mb4, e->d_mb4, (size_t)e->nmbs * sizeof(uint4), hipMemcpyDeviceToHost, e->stream));
-  else ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
-  ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (!e->frame_key) {
+    if (e->modes) ENC_TRY(hipMemcpyAsync(e->h_mb4, e->d_mb4, (size_t)e->nmbs * sizeof(uint4), hipMemcpyDeviceToHost, e->stream));
+    else ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
+    ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  }
   if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
   if (enc_pack_queue(e)) return TH_EFAULT;
-  e->frame_pending = true;
-  e->dups_left = e->dup_next;
-  e->dup_next = 0;
+  enc_frame_queued(e);
   return 0;
+}
+
+// the buffers of all eight modes (k_enc_me_all's words), at the first inter frame with them: TH_ENCCTL_THIP_SET_INTER_MODES never
+// touches the GPU
+static int enc_modes_alloc(th_enc_ctx *e) {
+  if (e->d_mb4) return 0;
+  ENC_TRY(hipMalloc((void **)&e->d_mb4, (size_t)e->nmbs * sizeof(uint4)));
+  ENC_TRY(hipHostMalloc((void **)&e->h_mb4, (size_t)e->nmbs * sizeof(uint4), hipHostMallocDefault));
+  return 0;
+}
+
+// The launches of an inter frame, written once for its two sets of kernels: the search, the two quantising kernels and the DC
+// kernel of one macro-block word (d_mb), with `classes` reference classes; gold: GOLD for the kernels that read it, else nothing
+extern "C++" template <class Me, class Fq, class FqBqi, class Dc, class Word, class... Gold>
+static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, Me k_me, Fq k_fq, FqBqi k_fq_bqi, Dc k_dc,
+                            int classes, Word *d_mb, const EncRef &R, const Gold &...gold) {
+  const int64_t n = e->nfrags;
+  const int lambda = enc_qstep_inter(e->setup, e->frame_qi, 1);
+  const dim3 gfq((unsigned)((4 * n + 255) / 256)), gch((unsigned)e->nchunks), wg(256);
+  ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
+  ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
+  hipLaunchKernelGGL(k_me, dim3((unsigned)e->nmbs), wg, 0, e->stream, d_mb, g, R, gold..., e->nmbx, lambda);
+  ENC_TRY(hipGetLastError());
+  if (e->bqi)
+    hipLaunchKernelGGL(k_fq_bqi, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
+                       e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, n);
+  else
+    hipLaunchKernelGGL(k_fq, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R,
+                       gold..., (const Word *)d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+  hipLaunchKernelGGL(k_dc, gch, wg, 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_inter_tok, gch, wg, 0, e->stream, e->d_tok, e->d_mask, e->d_cnt, e->d_small + 192, e->d_levels, e->d_dcr,
+                     e->d_cmap, e->d_order, g, n);
+  ENC_TRY(hipGetLastError());
+  return enc_queue_tail(e);
+}
+
+// an inter frame against the reconstruction of the previous frame (thip_encode_inter.h), with all eight modes against the last
+// key frame's too (thip_encode_modes.h)
+static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel) {
+  EncRef R, G;
+  if (enc_ref_frame(e, R)) return TH_EFAULT;
+  if (!e->modes)
+    return enc_launch_inter(e, g, sel, k_enc_me, k_enc_inter_fq, k_enc_inter_fq_bqi, k_enc_inter_dc, 2, e->d_mb, R);
+  if (enc_ref_frame(e, G, THIP_FRAME_GOLD) || enc_modes_alloc(e)) return TH_EFAULT;
+  return enc_launch_inter(e, g, sel, k_enc_me_all, k_enc_inter_fq_all, k_enc_inter_fq_all_bqi, k_enc_inter_dc3, 3, e->d_mb4, R, G);
 }
 
 static double enc_now();
@@ -759,12 +772,8 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   for (int t = 0; t < 6; t++)
     for (int z = 0; z < 64; z++)
       for (int q = 0; q < 64; q++) {
-        const uint32_t dq = t < 3 ? enc_qstep(e->setup, t, q, z) : enc_qstep_inter(e->setup, q, z);
-        const uint32_t d = dq << 1;
-        const int l = 31 - __builtin_clz(d);
-        const uint32_t tt = 1u + ((1u << (16 + l)) / d);
-        const int m = (int)(int16_t)(tt - 0x10000u);
-        tab[(t * 64 + z) * 64 + q] = make_uint2(dq | (uint32_t)(uint16_t)m << 16, (uint32_t)l);
+        // (rate_quant reads the second word as l alone: no zig-zag index in it)
+        tab[(t * 64 + z) * 64 + q] = enc_quant_entry(t < 3 ? enc_qstep(e->setup, t, q, z) : enc_qstep_inter(e->setup, q, z), 0);
       }
   int lam[64];
   for (int q = 0; q < 64; q++) lam[q] = enc_qstep_inter(e->setup, q, 1);
@@ -956,9 +965,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
       e->frame_key = false;
       e->frame_dpack = false;
       e->rate_dropped = true;
-      e->frame_pending = true;
-      e->dups_left = e->dup_next;
-      e->dup_next = 0;
+      enc_frame_queued(e);
       return 0;
     }
     e->frame_qi = qi;
@@ -978,19 +985,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   hipLaunchKernelGGL(k_enc_intra_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
                      e->d_small + 192, e->d_levels, e->d_dcq, e->d_order, g, n);
   ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_intra_scan, dim3(64), dim3(256), 0, e->stream, e->d_base, e->d_small, e->d_cnt, e->nchunks);
-  ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_intra_scatter, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_out, e->d_tok, e->d_mask,
-                     e->d_base, e->d_small, n);
-  ENC_TRY(hipGetLastError());
-  ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
-  if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
-  ENC_TRY(hipEventRecord(e->ev_done, e->stream));
-  if (enc_pack_queue(e)) return TH_EFAULT;
-  e->frame_pending = true;
-  e->dups_left = e->dup_next;
-  e->dup_next = 0;
-  return 0;
+  return enc_queue_tail(e);
 }
 
 int th_encode_ycbcr_in(th_enc_ctx *e, th_ycbcr_buffer ycbcr) {

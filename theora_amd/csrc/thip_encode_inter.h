@@ -1,22 +1,27 @@
 // thip_encode_inter.h -- the device stage of an inter frame of th_encode_* (thip_encode.hip; the bitstream is stated in
 // theoraenc_hip.h).  Everything is in bitstream coordinates: rows counted from the BOTTOM of the coded frame (spec 2.2), vectors
 // in half pixels with y pointing up.  The reference is PREV, a frame of the encoder's own decoder: three planes, bitstream row order,
-// no border (reads clamp their coordinates, as the decoder's motion-compensated reads do).
+// no border (reads clamp their coordinates, as the decoder's motion-compensated reads do).  With all eight modes
+// (thip_encode_modes.h) there is a second reference, GOLD; the bodies here are written once for both and the kernels are their
+// named instances.
 //
-//   k_enc_me        one work group a macro block: the 48 x 48 reference window around it (the search range plus one pixel for
-//                   the half-pel reads, coordinates clamped) and the 16 x 16 source go through LDS; a lane takes one full-pel
-//                   candidate in four (961 of them: every (dx, dy) in [-15, 15]^2), a row costs four v_sad_u8 on alignbyte-shifted
-//                   words.  The best full-pel vector is refined over its eight half-pel neighbours with the decoder's own
-//                   prediction (mv_axis, a truncating average of two reads).  Out: one word a macro block (raster order, rows from
-//                   the bottom): the pixel mode (NOMV / INTRA / MV) | mvx << 8 | mvy << 16 (bytes, zero unless MV).
-//   k_enc_inter_fq  k_enc_intra_fq for an inter frame: the prediction (128 for INTRA, PREV through the macro block's vector, with
-//                   the chroma vector of spec 7.9.4 for 4:2:0 and 4:2:2) is subtracted, the block is transformed and quantised
-//                   with the intra or inter table of its plane, and its coded flag is set: always for INTRA and MV macro blocks,
-//                   for NOMV ones when a level is not zero.  cmap[fi] (raster): 0 uncoded, 1 coded intra, 2 coded from PREV.  For
-//                   the DC predictor it records, per 256 raster fragments and class, the last coded fragment (+1, atomicMax).
-//   k_enc_inter_dc  the DC residuals of spec 7.8 with reference classes: a neighbour counts when it is coded and of the same
-//                   class; a block with none predicts from the last coded DC of its class before it in the plane's raster order --
-//                   a segmented "last value" scan (a max-scan of fragment indices, cut at the plane's first fragment).
+//   enc_me_search   the motion search of a macro block, one work group: the 48 x 48 reference window around it (the search range
+//                   plus one pixel for the half-pel reads, coordinates clamped) and the 16 x 16 source go through LDS; a lane
+//                   takes one full-pel candidate in four (961 of them: every (dx, dy) in [-15, 15]^2), a row costs four v_sad_u8
+//                   on alignbyte-shifted words.  The best full-pel vector is refined over its eight half-pel neighbours with the
+//                   decoder's own prediction (mv_axis, a truncating average of two reads).  Thread 0 gets S0, Smv, SI and the vector.
+//   k_enc_me        enc_me_search, then the decision.  Out: one word a macro block (raster order, rows from the bottom): the pixel
+//                   mode (NOMV / INTRA / MV) | mvx << 8 | mvy << 16 (bytes, zero unless MV).  (k_rate_me of thip_rate.h writes the
+//                   statistics instead.)
+//   enc_block_pred  a block's prediction from its macro block's word (k_enc_me's or k_enc_me_all's): pixel mode, vector (with the
+//                   chroma vector of spec 7.9.4 for 4:2:0 and 4:2:2), reference plane.  enc_pred_block turns it into the block's read
+//                   offsets and clamped columns once; enc_residual_row subtracts it from the source row by row (128 for INTRA).
+//   k_enc_inter_fq  (enc_inter_fq over k_enc_me's words) k_enc_intra_fq for an inter frame: the prediction is subtracted, the block
+//                   is transformed and quantised with the intra or inter table of its plane, and its coded flag is set
+//                   (enc_fq_tail).  cmap[fi] (raster): 0 uncoded, 1 coded intra, 2 coded from PREV.
+//   k_enc_inter_dc  (enc_inter_dc<2>) the DC residuals of spec 7.8 with reference classes: a neighbour counts when it is coded and
+//                   of the same class; a block with none predicts from the last coded DC of its class before it in the plane's
+//                   raster order -- a segmented "last value" scan (a max-scan of fragment indices, cut at the plane's first fragment).
 //   k_enc_inter_tok k_enc_intra_tok over the coded blocks only (an uncoded block has no tokens and an empty mask), with the DC
 //                   residual of k_enc_inter_dc.  k_enc_intra_scan and k_enc_intra_scatter then serve both frame types.
 #pragma once
@@ -27,9 +32,8 @@ namespace thip {
 constexpr int kMeRange = 15;              // full-pel search: dx, dy in [-15, 15]
 constexpr int kMeSide = 31;               // candidates a side
 constexpr int kMeWin = 48;                // window side: 16 + 2 * (15 + 1)
-enum { kEncPixNomv = 0, kEncPixIntra = 1, kEncPixMv = 2 };
 
-struct EncRef {            // PREV, bitstream row order
+struct EncRef {            // PREV or GOLD, bitstream row order
   const uint8_t *plane[3];
   int stride[3];
   int w[3], h[3];
@@ -43,19 +47,6 @@ __device__ __forceinline__ int enc_src_px(const EncPlanes &g, int p, int x, int 
   return (int)g.src[p][(int64_t)r * g.stride[p] + c];
 }
 
-// the predictor pixel at (x, y) of plane p for vector (mvx, mvy) (half pixels of luma): the decoder's offsets (mv_axis, quarter
-// pixels on a decimated chroma axis) and its truncating average of the two reads, coordinates clamped
-__device__ __forceinline__ int enc_pred_px(const EncRef &R, int p, int x, int y, int mvx, int mvy) {
-  int mx, mx2, my, my2;
-  mv_axis(mvx, p != 0 && R.hdec, mx, mx2);
-  mv_axis(mvy, p != 0 && R.vdec, my, my2);
-  const uint8_t *pl = R.plane[p];
-  const int W = R.w[p], H = R.h[p];
-  const int a = pl[(int64_t)min(max(y + my, 0), H - 1) * R.stride[p] + min(max(x + mx, 0), W - 1)];
-  const int b = pl[(int64_t)min(max(y + my + my2, 0), H - 1) * R.stride[p] + min(max(x + mx + mx2, 0), W - 1)];
-  return (a + b) >> 1;
-}
-
 __device__ __forceinline__ uint64_t enc_min64_wave(uint64_t v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
@@ -66,9 +57,68 @@ __device__ __forceinline__ uint64_t enc_min64_wave(uint64_t v) {
   return v;
 }
 
-// grid: one work group per macro block (raster, rows from the bottom).  lambda: the frame's inter luma step at zig-zag index 1.
-// k_rate_me (thip_rate.h) copies the search and writes its statistics instead of the decision: a fix here belongs there too.
-__global__ __launch_bounds__(256) void k_enc_me(uint32_t *mb_out, EncPlanes g, EncRef R, int nmbx, int lambda) {
+// ---- motion search ---------------------------------------------------------------------------------------------------------------
+// the 16 x 16 source of the macro block at (x0, y0) into s_src (rows of four words), by threads 0..63
+__device__ __forceinline__ void enc_me_load_src(uint32_t *s_src, const EncPlanes &g, int x0, int y0) {
+  const int tid = (int)threadIdx.x;
+  if (tid < 64) {
+    const int r = tid >> 2, c = (tid & 3) * 4;
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) v |= (uint32_t)enc_src_px(g, 0, x0 + c + b, y0 + r) << (8 * b);
+    s_src[tid] = v;
+  }
+}
+
+// the intra SAD of luma block bq (0..3) of s_src against its rounded mean
+__device__ __forceinline__ uint32_t enc_me_intra_sad(const uint32_t *s_src, int bq) {
+  const int bx = (bq & 1) * 2, by = (bq >> 1) * 8;
+  uint32_t sum = 0;
+  for (int r = 0; r < 8; r++) sum = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], 0u, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], 0u, sum));
+  const uint32_t m = ((sum + 32) >> 6) * 0x01010101u;
+  uint32_t v = 0;
+  for (int r = 0; r < 8; r++) v = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], m, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], m, v));
+  return v;
+}
+
+// the full-pel vector of a search key (its low 16 bits: the candidate's raster index)
+__device__ __forceinline__ void enc_me_key_vec(uint64_t best, int &bdx, int &bdy) {
+  const int bci = (int)(best & 0xFFFF);
+  bdx = bci % kMeSide - kMeRange;
+  bdy = bci / kMeSide - kMeRange;
+}
+
+// the half-pel refinement's choice around the full-pel vector (bdx, bdy) of key `best`: the centre keeps its full-pel key with
+// raster index 4 of the 3 x 3 neighbourhood; hp: the eight neighbours' SADs.  Returns the SAD of the vector chosen
+__device__ __forceinline__ int enc_hp_choose(uint64_t best, int bdx, int bdy, const uint32_t *hp, int &mvx, int &mvy) {
+  uint64_t cb = (best >> 16 << 16) | 4u;
+  int bk = 4;
+  for (int hk = 0; hk < 8; hk++) {
+    const int k9 = hk < 4 ? hk : hk + 1;
+    const int x = 2 * bdx + k9 % 3 - 1, y = 2 * bdy + k9 / 3 - 1;
+    const uint64_t key = (uint64_t)hp[hk] << 32 | (uint64_t)(abs(x) + abs(y)) << 16 | (uint64_t)k9;
+    if (key < cb) {
+      cb = key;
+      bk = k9;
+    }
+  }
+  mvx = 2 * bdx + bk % 3 - 1;
+  mvy = 2 * bdy + bk / 3 - 1;
+  return (int)(cb >> 32);
+}
+__device__ __forceinline__ int enc_hp_choose(uint64_t best, const uint32_t *hp, int &mvx, int &mvy) {
+  int bdx, bdy;
+  enc_me_key_vec(best, bdx, bdy);
+  return enc_hp_choose(best, bdx, bdy, hp, mvx, mvy);
+}
+
+struct EncMe {   // what the search finds: the SADs of vector 0, of the vector chosen and of INTRA, and the vector (half pixels)
+  int s0, smv, si, mvx, mvy;
+};
+
+// The search of macro block blockIdx.x (raster, rows from the bottom) against R, by the whole work group of 256.  True in thread
+// 0, which holds the result.
+__device__ __forceinline__ bool enc_me_search(EncMe &out, const EncPlanes &g, const EncRef &R, int nmbx) {
   __shared__ uint32_t s_win[kMeWin * kMeWin / 4];
   __shared__ uint32_t s_src[16 * 4];
   __shared__ uint64_t s_best[4];
@@ -87,13 +137,7 @@ __global__ __launch_bounds__(256) void k_enc_me(uint32_t *mb_out, EncPlanes g, E
       s_win[i] = v;
     }
   }
-  if (tid < 64) {
-    const int r = tid >> 2, c = (tid & 3) * 4;
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) v |= (uint32_t)enc_src_px(g, 0, x0 + c + b, y0 + r) << (8 * b);
-    s_src[tid] = v;
-  }
+  enc_me_load_src(s_src, g, x0, y0);
   if (tid < 8) s_hp[tid] = 0;
   if (tid == 8) s_si = 0;
   __syncthreads();
@@ -118,21 +162,13 @@ __global__ __launch_bounds__(256) void k_enc_me(uint32_t *mb_out, EncPlanes g, E
   }
   best = enc_min64_wave(best);
   if (lane == 0) s_best[w] = best;
-  if (tid >= 64 && tid < 68) {   // intra SAD of the four luma blocks against their rounded means
-    const int bq = tid - 64, bx = (bq & 1) * 2, by = (bq >> 1) * 8;
-    uint32_t sum = 0;
-    for (int r = 0; r < 8; r++) sum = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], 0u, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], 0u, sum));
-    const uint32_t m = ((sum + 32) >> 6) * 0x01010101u;
-    uint32_t v = 0;
-    for (int r = 0; r < 8; r++) v = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], m, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], m, v));
-    atomicAdd(&s_si, v);
-  }
+  if (tid >= 64 && tid < 68) atomicAdd(&s_si, enc_me_intra_sad(s_src, tid - 64));   // the four luma blocks
   __syncthreads();
   best = s_best[0];
 #pragma unroll
   for (int k = 1; k < 4; k++) best = s_best[k] < best ? s_best[k] : best;
-  const int bci = (int)(best & 0xFFFF);
-  const int bdx = bci % kMeSide - kMeRange, bdy = bci / kMeSide - kMeRange;
+  int bdx, bdy;
+  enc_me_key_vec(best, bdx, bdy);
   // half pel: the eight neighbours of 2 (bdx, bdy); 16 lanes a candidate, one row each
   if (tid < 128) {
     const int hk = tid >> 4, k9 = hk < 4 ? hk : hk + 1, r = tid & 15;
@@ -149,94 +185,147 @@ __global__ __launch_bounds__(256) void k_enc_me(uint32_t *mb_out, EncPlanes g, E
     atomicAdd(&s_hp[hk], sad);
   }
   __syncthreads();
-  if (tid == 0) {
-    uint64_t cb = (best >> 16 << 16) | 4u;   // the centre keeps its full-pel key, with raster index 4 of the 3 x 3 neighbourhood
-    int bk = 4;
-    for (int hk = 0; hk < 8; hk++) {
-      const int k9 = hk < 4 ? hk : hk + 1;
-      const int mvx = 2 * bdx + k9 % 3 - 1, mvy = 2 * bdy + k9 / 3 - 1;
-      const uint64_t key = (uint64_t)s_hp[hk] << 32 | (uint64_t)(abs(mvx) + abs(mvy)) << 16 | (uint64_t)k9;
-      if (key < cb) {
-        cb = key;
-        bk = k9;
+  if (tid != 0) return false;
+  out.smv = enc_hp_choose(best, bdx, bdy, s_hp, out.mvx, out.mvy);
+  out.s0 = (int)s_s0;
+  out.si = (int)s_si;
+  return true;
+}
+
+// grid: one work group per macro block (raster, rows from the bottom).  lambda: the frame's inter luma step at zig-zag index 1.
+__global__ __launch_bounds__(256) void k_enc_me(uint32_t *mb_out, EncPlanes g, EncRef R, int nmbx, int lambda) {
+  EncMe m;
+  if (!enc_me_search(m, g, R, nmbx)) return;
+  int mode = m.smv + lambda < m.s0 ? kEncPixMv : kEncPixNomv;
+  const int sinter = mode == kEncPixMv ? m.smv : m.s0;
+  if (m.si + 4 * lambda < sinter) mode = kEncPixIntra;
+  mb_out[blockIdx.x] = mode == kEncPixMv ? (uint32_t)mode | ((uint32_t)m.mvx & 0xFFu) << 8 | ((uint32_t)m.mvy & 0xFFu) << 16 : (uint32_t)mode;
+}
+
+// ---- block prediction ------------------------------------------------------------------------------------------------------------
+// the macro block (raster) of fragment (p, fx, fy)
+__device__ __forceinline__ int enc_mb_of(int p, int fx, int fy, int hdec, int vdec, int nmbx) {
+  const int mbx = p ? fx >> (1 - hdec) : fx >> 1, mby = p ? fy >> (1 - vdec) : fy >> 1;
+  return mby * nmbx + mbx;
+}
+
+__device__ __forceinline__ int enc_round_div(int v, int shift) {   // the decoder's round_div: ties away from zero
+  const int half = 1 << (shift - 1);
+  return v >= 0 ? (v + half) >> shift : -((-v + half) >> shift);
+}
+
+struct EncPred {   // how a block is predicted: the pixel mode, the vector of its plane, the reference's plane
+  int pix, mvx, mvy;
+  const uint8_t *pl;
+};
+
+// the prediction of block (p, fx, fy) from its macro block's word.  Word: uint32_t (k_enc_me's: mode | mvx << 8 | mvy << 16, PREV
+// only; G is not read) or uint4 (k_enc_me_all's, thip_encode_modes.h: GOLD modes, and MV_FOUR with the block's own vector in luma
+// and the vector the decoder derives in chroma -- thip_frontend.cpp, spec 7.5)
+template <class Word>
+__device__ __forceinline__ EncPred enc_block_pred(const Word *mbw, int nmbx, const EncRef &R, const EncRef &G, int p, int fx, int fy) {
+  const Word mw = mbw[enc_mb_of(p, fx, fy, R.hdec, R.vdec, nmbx)];
+  if constexpr (sizeof(Word) == sizeof(uint32_t)) {
+    return {(int)(mw & 0xFF), (int)(int8_t)(mw >> 8), (int)(int8_t)(mw >> 16), R.plane[p]};
+  } else {
+    const int pix = (int)(mw.x & 0xFF);
+    int mvx = (int)(int8_t)(mw.x >> 8), mvy = (int)(int8_t)(mw.x >> 16);
+    if (pix == kEncPixFour) {
+      // the block vectors A, B (bottom), C, D (top)
+      const int row = fy & 1;
+      const uint32_t rw = row ? mw.z : mw.y;   // the two vectors of the block's row
+      const int ax = (int)(int8_t)rw, ay = (int)(int8_t)(rw >> 8), bx = (int)(int8_t)(rw >> 16), by = (int)(int8_t)(rw >> 24);
+      if (p == 0 || (!R.hdec && !R.vdec)) {
+        mvx = fx & 1 ? bx : ax;
+        mvy = fx & 1 ? by : ay;
+      } else if (R.hdec && R.vdec) {
+        const uint32_t o = row ? mw.y : mw.z;   // (the other row)
+        mvx = enc_round_div(ax + bx + (int)(int8_t)o + (int)(int8_t)(o >> 16), 2);
+        mvy = enc_round_div(ay + by + (int)(int8_t)(o >> 8) + (int)(int8_t)(o >> 24), 2);
+      } else {   // 4:2:2: the row's two
+        mvx = enc_round_div(ax + bx, 1);
+        mvy = enc_round_div(ay + by, 1);
       }
     }
-    const int mvx = 2 * bdx + bk % 3 - 1, mvy = 2 * bdy + bk / 3 - 1;
-    const int smv = (int)(cb >> 32), s0 = (int)s_s0, si = (int)s_si;
-    int mode = smv + lambda < s0 ? kEncPixMv : kEncPixNomv;
-    const int sinter = mode == kEncPixMv ? smv : s0;
-    if (si + 4 * lambda < sinter) mode = kEncPixIntra;
-    mb_out[mb] = mode == kEncPixMv ? (uint32_t)mode | ((uint32_t)mvx & 0xFFu) << 8 | ((uint32_t)mvy & 0xFFu) << 16 : (uint32_t)mode;
+    const uint8_t *pr = R.plane[p], *pg = G.plane[p];   // (both loaded, then the value chosen: choosing the struct copied both to scratch)
+    return {pix, mvx, mvy, enc_pix_gold(pix) ? pg : pr};
   }
 }
 
-// levels [n][64], dcq [nfrags], cmap [nfrags], dclast [ceil(nfrags / 256)][2] (zeroed before), overflow: zeroed for the tokens.
-// dequant: [2][3][64] zig-zag, the intra then the inter tables of the frame's qi
-__global__ __launch_bounds__(256) void k_enc_inter_fq(int16_t *levels, int16_t *dcq, uint8_t *cmap, uint32_t *dclast,
-                                                      uint32_t *overflow, const int32_t *coded_order, EncPlanes g, EncRef R,
-                                                      const uint32_t *mb_mode, int nmbx, const uint16_t *dequant, int64_t n) {
+// The predictor pixels of block (p, fx, fy) under `pr`, as EncSrcBlock holds the source's: the decoder's offsets (mv_axis, quarter
+// pixels on a decimated chroma axis) and the clamped columns of its two reads, once for all the block's rows
+struct EncPredBlock {
+  bool intra;
+  const uint8_t *pl;
+  int stride, h1, ya, yb;   // row r reads plane rows ya + r and yb + r, clamped to [0, h1]
+  int ca[8], cb[8];
+};
+__device__ __forceinline__ EncPredBlock enc_pred_block(const EncRef &R, const EncPred &pr, int p, int fx, int fy) {
+  int mx, mx2, my, my2;
+  mv_axis(pr.mvx, p != 0 && R.hdec, mx, mx2);
+  mv_axis(pr.mvy, p != 0 && R.vdec, my, my2);
+  EncPredBlock b;
+  b.intra = pr.pix == kEncPixIntra;
+  b.pl = pr.pl;
+  b.stride = R.stride[p];
+  b.h1 = R.h[p] - 1;
+  b.ya = fy * 8 + my;
+  b.yb = b.ya + my2;
+  const int xa = fx * 8 + mx, xb = xa + mx2, w1 = R.w[p] - 1;
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    b.ca[c] = min(max(xa + c, 0), w1);
+    b.cb[c] = min(max(xb + c, 0), w1);
+  }
+  return b;
+}
+
+// row r of a block's residual: the source less its prediction (the decoder's truncating average of the two reads), 128 for an
+// INTRA block (enc_stage_rows' row)
+__device__ __forceinline__ void enc_residual_row(int v[8], const EncSrcBlock &s, const EncPredBlock &b, int r) {
+  const uint8_t *row = enc_src_row(s, r);
+  if (b.intra) {
+#pragma unroll
+    for (int c = 0; c < 8; c++) v[c] = (int)row[s.cx[c]] - 128;
+  } else {
+    const uint8_t *ra = b.pl + (int64_t)min(max(b.ya + r, 0), b.h1) * b.stride;
+    const uint8_t *rb = b.pl + (int64_t)min(max(b.yb + r, 0), b.h1) * b.stride;
+#pragma unroll
+    for (int c = 0; c < 8; c++) v[c] = (int)row[s.cx[c]] - (((int)ra[b.ca[c]] + (int)rb[b.cb[c]]) >> 1);
+  }
+}
+
+// The body of k_enc_inter_fq (two classes, k_enc_me's words) and k_enc_inter_fq_all (three, k_enc_me_all's).  levels [n][64], dcq
+// [nfrags], cmap [nfrags], dclast [ceil(nfrags / 256)][kClasses] (zeroed before), overflow: zeroed for the tokens.  dequant:
+// [2][3][64] zig-zag, the intra then the inter tables of the frame's qi
+template <int kClasses, class Word>
+__device__ __forceinline__ void enc_inter_fq(int16_t *levels, int16_t *dcq, uint8_t *cmap, uint32_t *dclast, uint32_t *overflow,
+                                             const int32_t *coded_order, const EncPlanes &g, const EncRef &R, const EncRef &G,
+                                             const Word *mbw, int nmbx, const uint16_t *dequant, int64_t n) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0;
   __shared__ __attribute__((aligned(16))) uint2 s_t[6 * 64];   // per (intra / inter, plane), by natural position
-  for (int i = (int)threadIdx.x; i < 6 * 64; i += 256) {
-    const int t = i >> 6, z = i & 63, pos = kFZigZag[z];
-    const uint32_t dq = dequant[t * 64 + z];
-    const uint32_t d = dq << 1;   // as k_enc_intra_fq
-    const int l = 31 - __builtin_clz(d);
-    const uint32_t tt = 1u + ((1u << (16 + l)) / d);
-    const int m = (int)(int16_t)(tt - 0x10000u);
-    s_t[t * 64 + pos] = make_uint2(dq | (uint32_t)(uint16_t)m << 16, (uint32_t)(l & 0xFF) | (uint32_t)z << 8);
-  }
+  enc_quant_tables(s_t, dequant, 6);
   __shared__ int4 s_x[4 * 128];
   int4 *lds = s_x + (threadIdx.x >> 6) * 128;
   const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
   const int64_t b0 = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2;
   const int64_t k = b0 + b;
-  int p = 0, fi = 0, tab = 0, pix = kEncPixIntra;
-  if (k < n) {
-    fi = coded_order[k];
-    p = enc_plane_of(g, fi);
-    const int loc = fi - g.froff[p], fy = loc / g.nh[p], fx = loc - fy * g.nh[p];
-    const int mbx = p ? fx >> (1 - R.hdec) : fx >> 1, mby = p ? fy >> (1 - R.vdec) : fy >> 1;
-    const uint32_t mw = mb_mode[mby * nmbx + mbx];
-    pix = (int)(mw & 0xFF);
-    const int mvx = (int)(int8_t)(mw >> 8), mvy = (int)(int8_t)(mw >> 16);
-    tab = (pix == kEncPixIntra ? 0 : 3) + p;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int r = 2 * j + h, y = fy * 8 + r;
-      int v[8];
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        const int x = fx * 8 + c;
-        v[c] = enc_src_px(g, p, x, y) - (pix == kEncPixIntra ? 128 : enc_pred_px(R, p, x, y, mvx, mvy));
-      }
-      lds[b * 8 + ((r + b) & 7)] = make_int4((v[0] & 0xFFFF) | (v[1] << 16), (v[2] & 0xFFFF) | (v[3] << 16),
-                                             (v[4] & 0xFFFF) | (v[5] << 16), (v[6] & 0xFFFF) | (v[7] << 16));
-    }
-  } else {
-    lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
-    lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
-  }
+  const int fi = coded_order[min(k, n - 1)];   // (a lane past the last block: any block's, it stores nothing)
+  int p, fx, fy;
+  enc_frag_xy(g, fi, p, fx, fy);
+  const EncPred pr = enc_block_pred(mbw, nmbx, R, G, p, fx, fy);
+  const EncSrcBlock sb = enc_src_block(g, p, fx, fy);
+  const EncPredBlock pb = enc_pred_block(R, pr, p, fx, fy);
+  enc_stage_rows(lds, b, j, k < n, [&](int r, int v[8]) { enc_residual_row(v, sb, pb, r); });
   __syncthreads();   // (the tables too)
-  fdct_quantize4_lds(lds, s_t + 64 * tab, b, j);
-  int4 *o = reinterpret_cast<int4 *>(levels) + b0 * 8;
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-    if (b0 + bb < n) o[idx] = lds[bb * 8 + ((pc + bb) & 7)];
-  }
-  // any level of the block not zero: lane j looks at rows 2j, 2j + 1 of its (rotated) zig-zag pieces
-  const int4 r0 = lds[b * 8 + ((2 * j + b) & 7)], r1 = lds[b * 8 + ((2 * j + 1 + b) & 7)];
-  int nz = (r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w) != 0;
-  nz |= __shfl_xor(nz, 1);
-  nz |= __shfl_xor(nz, 2);
-  if (j == 0 && k < n) {
-    dcq[fi] = (int16_t)lds[b * 8 + (b & 7)].x;
-    const int cls = pix == kEncPixIntra ? 1 : 2;
-    const bool coded = pix != kEncPixNomv || nz;
-    cmap[fi] = coded ? (uint8_t)cls : (uint8_t)0;
-    if (coded) atomicMax(&dclast[(fi >> 8) * 2 + cls - 1], (uint32_t)fi + 1u);
-  }
+  fdct_quantize4_lds(lds, s_t + 64 * ((pr.pix == kEncPixIntra ? 0 : 3) + p), b, j);
+  enc_fq_tail<kClasses>(levels, dcq, cmap, dclast, lds, [=](int) { return lds; }, lds, b0, n, fi, pr.pix);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_enc_inter_fq(int16_t *levels, int16_t *dcq, uint8_t *cmap, uint32_t *dclast,
+                                                      uint32_t *overflow, const int32_t *coded_order, EncPlanes g, EncRef R,
+                                                      const uint32_t *mb_mode, int nmbx, const uint16_t *dequant, int64_t n) {
+  enc_inter_fq<2>(levels, dcq, cmap, dclast, overflow, coded_order, g, R, R, mb_mode, nmbx, dequant, n);
 }
 
 // inclusive max-scan over the 256 threads of a work group (s_w: 4 words of LDS)
@@ -255,32 +344,40 @@ __device__ __forceinline__ uint32_t enc_block_max_scan(uint32_t v, uint32_t *s_w
   return v;
 }
 
-// grid: ceil(nfrags / 256) work groups over the RASTER fragment index.  dcr [nfrags]: the DC residual of every coded fragment
-__global__ __launch_bounds__(256) void k_enc_inter_dc(int16_t *dcr, const int16_t *dcq, const uint8_t *cmap, const uint32_t *dclast,
-                                                      EncPlanes g, int64_t nfrags) {
-  __shared__ uint32_t s_w[4], s_pre[2], s_own[2][256];
+// The body of k_enc_inter_dc (two reference classes) and k_enc_inter_dc3 (three, thip_encode_modes.h).  grid: ceil(nfrags / 256)
+// work groups over the RASTER fragment index.  dcr [nfrags]: the DC residual of every coded fragment; dclast [chunks][kClasses]
+template <int kClasses>
+__device__ __forceinline__ void enc_inter_dc(int16_t *dcr, const int16_t *dcq, const uint8_t *cmap, const uint32_t *dclast,
+                                             const EncPlanes &g, int64_t nfrags) {
+  __shared__ uint32_t s_w[4], s_pre[kClasses], s_own[kClasses][256];
   const int tid = (int)threadIdx.x;
-  if (tid < 2) s_pre[tid] = 0;
+  if (tid < kClasses) s_pre[tid] = 0;
   const int64_t fi64 = (int64_t)blockIdx.x * 256 + tid;
   const int fi = (int)fi64;
   const int cl = fi64 < nfrags ? (int)cmap[fi] : 0;
-  s_own[0][tid] = cl == 1 ? (uint32_t)fi + 1u : 0u;
-  s_own[1][tid] = cl == 2 ? (uint32_t)fi + 1u : 0u;
+#pragma unroll
+  for (int c = 0; c < kClasses; c++) s_own[c][tid] = cl == c + 1 ? (uint32_t)fi + 1u : 0u;
   __syncthreads();
   // the last coded fragment (+1) of each class in the earlier chunks ...
-  uint32_t pm0 = 0, pm1 = 0;
+  uint32_t pm[kClasses] = {};
   for (int c = tid; c < (int)blockIdx.x; c += 256) {
-    pm0 = max(pm0, dclast[2 * c]);
-    pm1 = max(pm1, dclast[2 * c + 1]);
+#pragma unroll
+    for (int q = 0; q < kClasses; q++) pm[q] = max(pm[q], dclast[kClasses * c + q]);
   }
-  if (pm0) atomicMax(&s_pre[0], pm0);
-  if (pm1) atomicMax(&s_pre[1], pm1);
+#pragma unroll
+  for (int q = 0; q < kClasses; q++)
+    if (pm[q]) atomicMax(&s_pre[q], pm[q]);
   // ... and in this chunk before the thread's own: the inclusive max-scan of the values shifted by one
-  const uint32_t x0 = enc_block_max_scan(tid ? s_own[0][tid - 1] : 0u, s_w);   // (its barriers also publish s_pre)
-  const uint32_t x1 = enc_block_max_scan(tid ? s_own[1][tid - 1] : 0u, s_w);
+  uint32_t xl = 0;
+#pragma unroll
+  for (int q = 0; q < kClasses; q++) {
+    const uint32_t x = enc_block_max_scan(tid ? s_own[q][tid - 1] : 0u, s_w);   // (its barriers also publish s_pre)
+    if (cl == q + 1) xl = x;
+  }
   if (!cl) return;
-  const int p = enc_plane_of(g, fi), nh = g.nh[p];
-  const int loc = fi - g.froff[p], fy = loc / nh, fx = loc - fy * nh;
+  int p, fx, fy;
+  enc_frag_xy(g, fi, p, fx, fy);
+  const int nh = g.nh[p];
   int l = 0, ul = 0, u = 0, ur = 0, msk = 0;
   if (fx > 0 && cmap[fi - 1] == cl) { l = dcq[fi - 1]; msk |= 1; }
   if (fy > 0) {
@@ -292,10 +389,15 @@ __global__ __launch_bounds__(256) void k_enc_inter_dc(int16_t *dcr, const int16_
   if (msk) {
     pred = enc_dc_pred(msk, l, ul, u, ur);
   } else {
-    const uint32_t last = max(cl == 1 ? x0 : x1, s_pre[cl - 1]);   // (0: none)
+    const uint32_t last = max(xl, s_pre[cl - 1]);   // (0: none)
     pred = last > (uint32_t)g.froff[p] ? (int)dcq[last - 1] : 0;
   }
   dcr[fi] = (int16_t)((int)dcq[fi] - pred);
+}
+
+__global__ __launch_bounds__(256) void k_enc_inter_dc(int16_t *dcr, const int16_t *dcq, const uint8_t *cmap, const uint32_t *dclast,
+                                                      EncPlanes g, int64_t nfrags) {
+  enc_inter_dc<2>(dcr, dcq, cmap, dclast, g, nfrags);
 }
 
 // tok [n][kEncTokWords], mask [n], chunk_cnt [gridDim.x][3][64], overflow: as k_enc_intra_tok, over the coded blocks

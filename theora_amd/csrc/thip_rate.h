@@ -2,11 +2,13 @@
 // theoraenc_hip.h, "Bitrate mode").  Before a frame is coded, the probe measures its token bits E[q] at every qi q = 0..63 at once:
 // the 64 lanes of a wave are the 64 qi, a wave takes one block.  The quality-mode kernels are not touched; the probe has its own.
 //
-//   k_rate_me          (inter frames) k_enc_me's search, writing the qi-independent statistics of each macro block instead of a mode:
-//                      S0, Smv, SI and the half-pel vector.  The mode at q then follows from them and q's lambda (rate_mode).
+//   k_rate_me          (inter frames) k_enc_me's search (enc_me_search, thip_encode_inter.h), writing the qi-independent statistics
+//                      of each macro block instead of a mode: S0, Smv, SI and the half-pel vector.  The mode at q then follows
+//                      from them and q's lambda (rate_mode).
 //   k_rate_fdct_key    the unquantised fDCT of every block (raster order, natural order in the block): fdct_quantize4_lds's transform.
 //   k_rate_fdct_inter  the same for the three residuals an inter block may code: INTRA (pixel - 128), NOMV (PREV, vector 0) and MV
-//                      (PREV through the macro block's vector) -- [3][nfrags][64].
+//                      (PREV through the macro block's vector) -- [3][nfrags][64].  Both stage their residuals as the frame's
+//                      kernels do (enc_stage_rows, enc_residual_row).
 //   k_rate_dc          one wave a block, lane q: the block's quantised DC at q, and (inter) whether the block is coded at q and in
 //                      which class (ballots into one 64-bit word each).
 //   k_rate_tok         a persistent grid, one wave a block, lane q: DC prediction at q, the AC levels at q and the block's tokens,
@@ -73,10 +75,8 @@ __device__ __forceinline__ int rate_quant(int coef, uint2 e) {
   return sx16(((((m * val) >> 16) + val) >> l) - sg);
 }
 
-// the table entry of rate_quant from its first word: l = the bit length of 2 d, less one (oc_iquant_init, as the host forms it)
-__device__ __forceinline__ uint2 rate_entry(uint32_t x) {
-  return make_uint2(x, (uint32_t)(31 - __builtin_clz((x & 0xFFFFu) << 1)));
-}
+// the table entry of rate_quant from its first word (enc_quant_entry's, without the zig-zag index)
+__device__ __forceinline__ uint2 rate_entry(uint32_t x) { return make_uint2(x, (uint32_t)enc_quant_shift(x & 0xFFFFu)); }
 
 // the four lanes of a block store its 64 coefficients (natural order) at out[0..63]
 __device__ __forceinline__ void rate_store16(int16_t *out, int j, const int o[16]) {
@@ -87,36 +87,18 @@ __device__ __forceinline__ void rate_store16(int16_t *out, int j, const int o[16
                    (o[14] & 0xFFFF) | (o[15] << 16));
 }
 
-// the raster fragment fi's plane, column, row (rows from the bottom)
-__device__ __forceinline__ void rate_frag_xy(const EncPlanes &g, int fi, int &p, int &fx, int &fy) {
-  p = enc_plane_of(g, fi);
-  const int loc = fi - g.froff[p];
-  fy = loc / g.nh[p];
-  fx = loc - fy * g.nh[p];
-}
-
 // grid: ceil(4 nfrags / 256).  coef [nfrags][64] int16, natural order, raster fragment order
 __global__ __launch_bounds__(256) void k_rate_fdct_key(int16_t *coef, EncPlanes g, int64_t nfrags) {
   __shared__ int4 s_x[4 * 128];
   int4 *lds = s_x + (threadIdx.x >> 6) * 128;
   const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
   const int64_t fi = (((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2) + b;
-  if (fi < nfrags) {
-    int p, fx, fy;
-    rate_frag_xy(g, (int)fi, p, fx, fy);
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int r = 2 * j + h;
-      int v[8];
-#pragma unroll
-      for (int c = 0; c < 8; c++) v[c] = enc_src_px(g, p, fx * 8 + c, fy * 8 + r) - 128;
-      lds[b * 8 + ((r + b) & 7)] = make_int4((v[0] & 0xFFFF) | (v[1] << 16), (v[2] & 0xFFFF) | (v[3] << 16),
-                                             (v[4] & 0xFFFF) | (v[5] << 16), (v[6] & 0xFFFF) | (v[7] << 16));
-    }
-  } else {
-    lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
-    lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
-  }
+  int p = 0, fx = 0, fy = 0;
+  if (fi < nfrags) enc_frag_xy(g, (int)fi, p, fx, fy);
+  const EncSrcBlock sb = enc_src_block(g, p, fx, fy);
+  EncPredBlock pb = {};
+  pb.intra = true;   // pixel - 128
+  enc_stage_rows(lds, b, j, fi < nfrags, [&](int r, int v[8]) { enc_residual_row(v, sb, pb, r); });
   __syncthreads();
   int o[16];
   rate_fdct4_lds(lds, b, j, o);
@@ -131,108 +113,11 @@ __device__ __forceinline__ int rate_mode(uint4 s, int lambda) {
   return mode;
 }
 
-// the macro block (raster) of fragment (p, fx, fy)
-__device__ __forceinline__ int rate_mb_of(int p, int fx, int fy, int hdec, int vdec, int nmbx) {
-  const int mbx = p ? fx >> (1 - hdec) : fx >> 1, mby = p ? fy >> (1 - vdec) : fy >> 1;
-  return mby * nmbx + mbx;
-}
-
-// k_enc_me (thip_encode_inter.h) with the decision left out: the same full-pel search, half-pel refinement, S0 and SI, written as
-// rate_mode's statistics.  (A copy, so that k_enc_me and its resource line stay as they are.)
+// enc_me_search (thip_encode_inter.h) with the decision left out: S0, Smv, SI and the vector, written as rate_mode's statistics
 __global__ __launch_bounds__(256) void k_rate_me(uint4 *mb_out, EncPlanes g, EncRef R, int nmbx) {
-  __shared__ uint32_t s_win[kMeWin * kMeWin / 4];
-  __shared__ uint32_t s_src[16 * 4];
-  __shared__ uint64_t s_best[4];
-  __shared__ uint32_t s_hp[8], s_s0, s_si;
-  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int mb = (int)blockIdx.x, mbx = mb % nmbx, mby = mb / nmbx, x0 = mbx * 16, y0 = mby * 16;
-  {
-    const uint8_t *pl = R.plane[0];
-    const int W = R.w[0], H = R.h[0];
-    for (int i = tid; i < kMeWin * kMeWin / 4; i += 256) {
-      const int r = i / (kMeWin / 4), c = (i - r * (kMeWin / 4)) * 4;
-      const uint8_t *row = pl + (int64_t)min(max(y0 - 16 + r, 0), H - 1) * R.stride[0];
-      uint32_t v = 0;
-#pragma unroll
-      for (int b = 0; b < 4; b++) v |= (uint32_t)row[min(max(x0 - 16 + c + b, 0), W - 1)] << (8 * b);
-      s_win[i] = v;
-    }
-  }
-  if (tid < 64) {
-    const int r = tid >> 2, c = (tid & 3) * 4;
-    uint32_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) v |= (uint32_t)enc_src_px(g, 0, x0 + c + b, y0 + r) << (8 * b);
-    s_src[tid] = v;
-  }
-  if (tid < 8) s_hp[tid] = 0;
-  if (tid == 8) s_si = 0;
-  __syncthreads();
-  uint64_t best = ~0ull;
-  for (int ci = tid; ci < kMeSide * kMeSide; ci += 256) {
-    const int dy = ci / kMeSide - kMeRange, dx = ci % kMeSide - kMeRange;
-    const int cc = dx + 16, q = cc >> 2, sh = cc & 3;
-    uint32_t sad = 0;
-#pragma unroll 4
-    for (int r = 0; r < 16; r++) {
-      const uint32_t *row = s_win + (r + dy + 16) * (kMeWin / 4) + q;
-      uint32_t a[5];
-#pragma unroll
-      for (int k = 0; k < 5; k++) a[k] = row[k];
-#pragma unroll
-      for (int k = 0; k < 4; k++) sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(a[k + 1], a[k], (uint32_t)sh), s_src[r * 4 + k], sad);
-    }
-    if (dx == 0 && dy == 0) s_s0 = sad;
-    const uint64_t key = (uint64_t)sad << 32 | (uint64_t)(2 * (abs(dx) + abs(dy))) << 16 | (uint64_t)ci;
-    best = key < best ? key : best;
-  }
-  best = enc_min64_wave(best);
-  if (lane == 0) s_best[w] = best;
-  if (tid >= 64 && tid < 68) {
-    const int bq = tid - 64, bx = (bq & 1) * 2, by = (bq >> 1) * 8;
-    uint32_t sum = 0;
-    for (int r = 0; r < 8; r++) sum = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], 0u, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], 0u, sum));
-    const uint32_t m = ((sum + 32) >> 6) * 0x01010101u;
-    uint32_t v = 0;
-    for (int r = 0; r < 8; r++) v = __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx + 1], m, __builtin_amdgcn_sad_u8(s_src[(by + r) * 4 + bx], m, v));
-    atomicAdd(&s_si, v);
-  }
-  __syncthreads();
-  best = s_best[0];
-#pragma unroll
-  for (int k = 1; k < 4; k++) best = s_best[k] < best ? s_best[k] : best;
-  const int bci = (int)(best & 0xFFFF);
-  const int bdx = bci % kMeSide - kMeRange, bdy = bci / kMeSide - kMeRange;
-  if (tid < 128) {
-    const int hk = tid >> 4, k9 = hk < 4 ? hk : hk + 1, r = tid & 15;
-    const int mvx = 2 * bdx + k9 % 3 - 1, mvy = 2 * bdy + k9 / 3 - 1;
-    int mx, mx2, my, my2;
-    mv_axis(mvx, false, mx, mx2);
-    mv_axis(mvy, false, my, my2);
-    const uint8_t *win = reinterpret_cast<const uint8_t *>(s_win);
-    const uint8_t *ra = win + (r + my + 16) * kMeWin + mx + 16, *rb = win + (r + my + my2 + 16) * kMeWin + mx + mx2 + 16;
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(s_src) + r * 16;
-    uint32_t sad = 0;
-#pragma unroll
-    for (int c = 0; c < 16; c++) sad += (uint32_t)abs((int)src[c] - (((int)ra[c] + (int)rb[c]) >> 1));
-    atomicAdd(&s_hp[hk], sad);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    uint64_t cb = (best >> 16 << 16) | 4u;
-    int bk = 4;
-    for (int hk = 0; hk < 8; hk++) {
-      const int k9 = hk < 4 ? hk : hk + 1;
-      const int mvx = 2 * bdx + k9 % 3 - 1, mvy = 2 * bdy + k9 / 3 - 1;
-      const uint64_t key = (uint64_t)s_hp[hk] << 32 | (uint64_t)(abs(mvx) + abs(mvy)) << 16 | (uint64_t)k9;
-      if (key < cb) {
-        cb = key;
-        bk = k9;
-      }
-    }
-    const int mvx = 2 * bdx + bk % 3 - 1, mvy = 2 * bdy + bk / 3 - 1;
-    mb_out[mb] = make_uint4(s_s0, (uint32_t)(cb >> 32), s_si, ((uint32_t)mvx & 0xFFu) | ((uint32_t)mvy & 0xFFu) << 8);
-  }
+  EncMe m;
+  if (enc_me_search(m, g, R, nmbx))
+    mb_out[blockIdx.x] = make_uint4((uint32_t)m.s0, (uint32_t)m.smv, (uint32_t)m.si, ((uint32_t)m.mvx & 0xFFu) | ((uint32_t)m.mvy & 0xFFu) << 8);
 }
 
 // grid: ceil(4 nfrags / 256).  coef [3][nfrags][64]: the INTRA, NOMV and MV residuals' coefficients (natural order, raster)
@@ -244,29 +129,16 @@ __global__ __launch_bounds__(256) void k_rate_fdct_inter(int16_t *coef, EncPlane
   const int64_t fi = (((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2) + b;
   int p = 0, fx = 0, fy = 0, mvx = 0, mvy = 0;
   if (fi < nfrags) {
-    rate_frag_xy(g, (int)fi, p, fx, fy);
-    const uint32_t w = mbs[rate_mb_of(p, fx, fy, R.hdec, R.vdec, nmbx)].w;
+    enc_frag_xy(g, (int)fi, p, fx, fy);
+    const uint32_t w = mbs[enc_mb_of(p, fx, fy, R.hdec, R.vdec, nmbx)].w;
     mvx = (int)(int8_t)(w & 0xFF);
     mvy = (int)(int8_t)(w >> 8);
   }
-  for (int v = 0; v < 3; v++) {
-    if (fi < nfrags) {
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int r = 2 * j + h, y = fy * 8 + r;
-        int px[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-          const int x = fx * 8 + c;
-          px[c] = enc_src_px(g, p, x, y) - (v == 0 ? 128 : v == 1 ? enc_pred_px(R, p, x, y, 0, 0) : enc_pred_px(R, p, x, y, mvx, mvy));
-        }
-        lds[b * 8 + ((r + b) & 7)] = make_int4((px[0] & 0xFFFF) | (px[1] << 16), (px[2] & 0xFFFF) | (px[3] << 16),
-                                               (px[4] & 0xFFFF) | (px[5] << 16), (px[6] & 0xFFFF) | (px[7] << 16));
-      }
-    } else {
-      lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
-      lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
-    }
+  const EncSrcBlock sb = enc_src_block(g, p, fx, fy);
+  for (int v = 0; v < 3; v++) {   // INTRA, NOMV, MV
+    const EncPred pr = {v == 0 ? kEncPixIntra : kEncPixMv, v == 2 ? mvx : 0, v == 2 ? mvy : 0, R.plane[p]};
+    const EncPredBlock pb = enc_pred_block(R, pr, p, fx, fy);
+    enc_stage_rows(lds, b, j, fi < nfrags, [&](int r, int px[8]) { enc_residual_row(px, sb, pb, r); });
     __syncthreads();
     int o[16];
     rate_fdct4_lds(lds, b, j, o);
@@ -284,7 +156,7 @@ template <bool kInter>
 __device__ __forceinline__ RateSel rate_select(const uint4 *mbs, const int *lam, int p, int fx, int fy, int hdec, int vdec, int nmbx,
                                                int q) {
   if (!kInter) return {0, p, kEncPixIntra};
-  const int mode = rate_mode(mbs[rate_mb_of(p, fx, fy, hdec, vdec, nmbx)], lam[q]);
+  const int mode = rate_mode(mbs[enc_mb_of(p, fx, fy, hdec, vdec, nmbx)], lam[q]);
   return {mode == kEncPixIntra ? 0 : mode == kEncPixNomv ? 1 : 2, (mode == kEncPixIntra ? 0 : 3) + p, mode};
 }
 
@@ -305,7 +177,7 @@ __global__ __launch_bounds__(256) void k_rate_dc(int16_t *qdc, uint64_t *coded, 
   const int64_t fi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (fi >= nfrags) return;   // (wave-uniform)
   int p, fx, fy;
-  rate_frag_xy(g, (int)fi, p, fx, fy);
+  enc_frag_xy(g, (int)fi, p, fx, fy);
   const RateSel s = rate_select<kInter>(a.mbs, a.lam, p, fx, fy, a.hdec, a.vdec, a.nmbx, q);
   const int16_t *cb = a.coef + ((int64_t)s.var * nfrags + fi) * 64;
   qdc[fi * 64 + q] = (int16_t)rate_quant(cb[0], a.tab[(s.tab * 64 + 0) * 64 + q]);
@@ -361,7 +233,7 @@ __global__ __launch_bounds__(64 * kRateTokWaves) void k_rate_tok(uint32_t *parti
   const int64_t step = (int64_t)gridDim.x * kRateTokWaves;
   for (int64_t fi = (int64_t)blockIdx.x * kRateTokWaves + (threadIdx.x >> 6); fi < nfrags; fi += step) {
     int p, fx, fy;
-    rate_frag_xy(g, (int)fi, p, fx, fy);
+    enc_frag_xy(g, (int)fi, p, fx, fy);
     const int nh = g.nh[p];
     const RateSel s = rate_select<kInter>(a.mbs, a.lam, p, fx, fy, a.hdec, a.vdec, a.nmbx, q);
     const bool isc = kInter ? ((coded[fi] >> q) & 1ull) != 0 : true;
