@@ -656,3 +656,89 @@ def _fdct_quantize_trials(hip, L, rng, n):
         nz3 = torch.empty(n, dtype=torch.int32, device="cuda")
         assert L.thip_enc_fdct_quantize_batch(q3.data_ptr(), nz3.data_ptr(), None, dev(x).data_ptr(), dev(dq).data_ptr(), dev(enq).data_ptr(), n) == 0
         assert torch.equal(q3.reshape(-1), q.reshape(-1)) and torch.equal(nz3, nz)
+
+
+# ---- the block counts at which the wave's coalesced block move ends inside a wave's sixteen blocks, inside a wave of 64 and one
+#      block into the next work group's wave, for every quantising slot (test_enc_fdct has them for the transform alone)
+_SMALL_COUNTS = (1, 15, 17, 63, 65)
+_SMALL_PAD = 16          # blocks of sentinel behind each output: nothing may be written past the last block
+_SMALL = {}
+
+
+def _small_case():
+    """65 residual blocks and 65 coefficient blocks with the oracle's results, computed once and left unchanged."""
+    if not _SMALL:
+        rng = np.random.default_rng(77)
+        n = max(_SMALL_COUNTS)
+        x = rng.integers(-255, 256, (n, 64)).astype(np.int16)
+        x[3] = 255
+        x[16] = -255
+        x[40:48] = rng.integers(-8160, 8161, (8, 64))
+        dq = rng.integers(8, 4097, 64).astype(np.uint16)
+        dq[0], dq[1] = 8, 4096
+        enq = np.zeros(128, np.int16)
+        oracle.lib().orc_enc_enquant_table_init(enq.ctypes.data, dq.ctypes.data)
+        coef = random_blocks(rng, n)
+        _SMALL["x"], _SMALL["dq"], _SMALL["enq"], _SMALL["coef"] = x, dq, enq, coef
+        _SMALL["dct"] = oracle.fdct8x8_batch(x)
+        _SMALL["q"], _SMALL["nz"] = oracle.quantize_batch(_SMALL["dct"], dq)
+        _SMALL["coef_q"], _SMALL["coef_nz"] = oracle.quantize_batch(coef, dq)
+        for v in _SMALL.values():
+            v.setflags(write=False)
+    return _SMALL
+
+
+def _guarded(m, cols, dtype):
+    """A device output of m rows with _SMALL_PAD rows of sentinel behind them."""
+    import torch
+    return torch.full((m + _SMALL_PAD, cols) if cols else (m + _SMALL_PAD,), 0x5A5A, dtype=dtype, device="cuda")
+
+
+def _check_guarded(t, m, want):
+    got = t.cpu().numpy()
+    assert np.array_equal(got[:m], want[:m])
+    assert (got[m:] == 0x5A5A).all()
+
+
+@pytest.mark.parametrize("m", _SMALL_COUNTS)
+@pytest.mark.parametrize("table", [False, True])
+def test_enc_quantize_small_block_counts(hip, table, m):
+    """thip_enc_quantize_batch / thip_enc_quantize_tab_batch on a few blocks: bit-exact with oc_enc_quantize, nothing written
+    behind the last block."""
+    import torch
+    from theora_amd import _lib
+    L, c = _lib.load(), _small_case()
+    q, nz = _guarded(m, 64, torch.int16), _guarded(m, 0, torch.int32)
+    coef, dq = dev(c["coef"][:m].copy()), dev(c["dq"].copy())
+    if table:
+        rc = L.thip_enc_quantize_tab_batch(q.data_ptr(), nz.data_ptr(), coef.data_ptr(), dq.data_ptr(), dev(c["enq"].copy()).data_ptr(), m)
+    else:
+        rc = L.thip_enc_quantize_batch(q.data_ptr(), nz.data_ptr(), coef.data_ptr(), dq.data_ptr(), m)
+    assert rc == 0
+    _check_guarded(q, m, c["coef_q"])
+    _check_guarded(nz, m, c["coef_nz"])
+
+
+@pytest.mark.parametrize("m", _SMALL_COUNTS)
+@pytest.mark.parametrize("lanes", [4, 1])
+def test_enc_fdct_quantize_small_block_counts(hip, lanes, m):
+    """thip_enc_fdct_quantize_batch on a few blocks, both kernels, with and without the coefficients handed back (a null dct_out
+    is not written to) and with and without an enquant table: bit-exact with oc_enc_fdct8x8 + oc_enc_quantize, nothing written
+    behind the last block."""
+    import torch
+    from theora_amd import _lib
+    L, c = _lib.load(), _small_case()
+    x, dq, enq = dev(c["x"][:m].copy()), dev(c["dq"].copy()), dev(c["enq"].copy())
+    with util.options(L, enc_fq_lanes=lanes):
+        for want_dct in (True, False):
+            for table in (False, True):
+                q, nz = _guarded(m, 64, torch.int16), _guarded(m, 0, torch.int32)
+                dct = _guarded(m, 64, torch.int16) if want_dct else None
+                rc = L.thip_enc_fdct_quantize_batch(q.data_ptr(), nz.data_ptr(), dct.data_ptr() if want_dct else None, x.data_ptr(),
+                                                    dq.data_ptr(), enq.data_ptr() if table else None, m)
+                assert rc == 0, (want_dct, table)
+                torch.cuda.synchronize()
+                _check_guarded(q, m, c["q"])
+                _check_guarded(nz, m, c["nz"])
+                if want_dct:
+                    _check_guarded(dct, m, c["dct"])

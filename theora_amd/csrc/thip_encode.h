@@ -1,12 +1,13 @@
 // thip_encode.h -- the device stage of the intra-only th_encode_* encoder (thip_encode.hip): four launches a frame, none of which
 // waits for another on the host.
 //
-// The pieces of k_enc_intra_fq -- the quantiser table entry (enc_quant_entry), a lane's two rows into LDS (enc_stage_rows), what
+// The pieces of k_enc_intra_fq -- the quantiser tables (enc_quant_tables), a lane's two rows into LDS (enc_stage_rows), what
 // follows the quantiser (enc_fq_tail) -- are functions here: the inter, all-modes, block-qi and rate-probe kernels
-// (thip_encode_inter.h, thip_encode_modes.h, thip_encode_bqi.h, thip_rate.h) are made of the same ones.
+// (thip_encode_inter.h, thip_encode_modes.h, thip_encode_bqi.h, thip_rate.h) are made of the same ones.  The transform, the
+// quantiser and the LDS layout between them are thip_fdct.h's, the same code as the batched slots run.
 //
-//   k_enc_intra_fq       transform and quantise.  Four lanes a block (the layout of k_enc_fdct_quantize4, through
-//                        fdct_quantize4_lds of thip_fdct.h): each lane loads two rows of its block straight from the caller's planes (any stride or
+//   k_enc_intra_fq       transform and quantise.  Four lanes a block (fdct_quantize4_lds of thip_fdct.h): each lane loads two
+//                        rows of its block straight from the caller's planes (any stride or
 //                        alignment; coordinates clamped to the picture region), subtracts 128, and the block goes through the fDCT
 //                        and the quantiser of its plane.  Out: the zig-zag levels of block k (coded order) at levels[64 k], the
 //                        quantised DC by raster fragment index at dcq[fi].
@@ -50,16 +51,13 @@ __device__ __forceinline__ void enc_frag_xy(const EncPlanes &g, int fi, int &p, 
 
 // ---- the pieces every transform-and-quantise kernel is made of (k_enc_intra_fq here, enc_inter_fq of thip_encode_inter.h,
 // enc_fq_bqi of thip_encode_bqi.h, the probe's transforms of thip_rate.h).  Four lanes a block, sixteen blocks a wave: lane
-// 4 b + j holds rows 2j, 2j + 1 of block b; the wave's 128 int4 of LDS hold row r of block b at b * 8 + ((r + b) & 7).
+// 4 b + j holds rows 2j, 2j + 1 of block b; the wave's 128 int4 of LDS hold row r of block b at lds_block_piece(b, r).
 
-// oc_iquant_init (enquant.c:183-191) for the step dq: l, the bit length of 2 dq less one ...
-__host__ __device__ __forceinline__ int enc_quant_shift(uint32_t dq) { return 31 - __builtin_clz(dq << 1); }
-// ... and the whole table entry of fdct_quantize4_lds for zig-zag index z: (dq | m << 16, l | z << 8)
+// the table entry (quant_entry of thip_fdct.h) of the step dq at zig-zag index z, its reciprocal derived (quant_recip)
 __host__ __device__ __forceinline__ uint2 enc_quant_entry(uint32_t dq, int z) {
-  const int l = enc_quant_shift(dq);
-  const uint32_t t = 1u + ((1u << (16 + l)) / (dq << 1));
-  const int m = (int)(int16_t)(t - 0x10000u);
-  return make_uint2(dq | (uint32_t)(uint16_t)m << 16, (uint32_t)(l & 0xFF) | (uint32_t)z << 8);
+  int m, l;
+  quant_recip(dq << 1, m, l);
+  return quant_entry(dq, m, l, z);
 }
 
 // `ntabs` tables of `dequant` ([ntabs][64], zig-zag) as entries by natural position in s_t, by the whole work group
@@ -103,12 +101,12 @@ __device__ __forceinline__ void enc_stage_rows(int4 *lds, int b, int j, bool liv
       const int r = 2 * j + h;
       int v[8];
       row(r, v);
-      lds[b * 8 + ((r + b) & 7)] = make_int4((v[0] & 0xFFFF) | (v[1] << 16), (v[2] & 0xFFFF) | (v[3] << 16),
+      lds[lds_block_piece(b, r)] = make_int4((v[0] & 0xFFFF) | (v[1] << 16), (v[2] & 0xFFFF) | (v[3] << 16),
                                              (v[4] & 0xFFFF) | (v[5] << 16), (v[6] & 0xFFFF) | (v[7] << 16));
     }
   } else {
-    lds[b * 8 + ((2 * j + b) & 7)] = make_int4(0, 0, 0, 0);
-    lds[b * 8 + ((2 * j + 1 + b) & 7)] = make_int4(0, 0, 0, 0);
+    lds[lds_block_piece(b, 2 * j)] = make_int4(0, 0, 0, 0);
+    lds[lds_block_piece(b, 2 * j + 1)] = make_int4(0, 0, 0, 0);
   }
 }
 
@@ -124,24 +122,18 @@ template <int kClasses, class Src>
 __device__ __forceinline__ void enc_fq_tail(int16_t *levels, int16_t *dcq, uint8_t *cmap, uint32_t *dclast, const int4 *lds,
                                             Src &&src, const int4 *own, int64_t b0, int64_t n, int fi, int pix) {
   const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
-  int4 *o = reinterpret_cast<int4 *>(levels) + b0 * 8;
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-    const int4 *s = src(bb);
-    if (b0 + bb < n) o[idx] = s[bb * 8 + ((pc + bb) & 7)];
-  }
+  wave_blocks_out_of(levels, src, b0, n);
   const bool first = j == 0 && b0 + b < n;   // the lane that writes for its block
   if constexpr (kClasses == 0) {
-    if (first) dcq[fi] = (int16_t)lds[b * 8 + (b & 7)].x;
+    if (first) dcq[fi] = (int16_t)lds[lds_block_piece(b, 0)].x;
   } else {
     // any level of the block not zero: lane j looks at rows 2j, 2j + 1 of its (rotated) zig-zag pieces
-    const int4 r0 = own[b * 8 + ((2 * j + b) & 7)], r1 = own[b * 8 + ((2 * j + 1 + b) & 7)];
+    const int4 r0 = own[lds_block_piece(b, 2 * j)], r1 = own[lds_block_piece(b, 2 * j + 1)];
     int nz = (r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w) != 0;
     nz |= __shfl_xor(nz, 1);
     nz |= __shfl_xor(nz, 2);
     if (!first) return;
-    dcq[fi] = (int16_t)lds[b * 8 + (b & 7)].x;
+    dcq[fi] = (int16_t)lds[lds_block_piece(b, 0)].x;
     const int cls = pix == kEncPixIntra ? 1 : kClasses == 3 && enc_pix_gold(pix) ? 3 : 2;
     const bool coded = pix != kEncPixNomv || nz;
     cmap[fi] = coded ? (uint8_t)cls : (uint8_t)0;

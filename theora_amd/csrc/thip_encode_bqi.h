@@ -1,7 +1,8 @@
 // thip_encode_bqi.h -- block-level qi (TH_ENCCTL_THIP_SET_BLOCK_QI; the rule is stated in theoraenc_hip.h, "Block-level qi"): the
 // block-qi forms of the three quantising kernels, one body (enc_fq_bqi) over the pieces of the plain ones: enc_quant_entry,
-// enc_block_pred, enc_stage_rows with enc_residual_row, enc_fq_tail.  It stages the block's residual, transforms it once (rate_fdct4_lds: fdct_quantize4_lds's transform), quantises the
-// coefficients at every qi of the frame's list into LDS, and chooses per block:
+// enc_block_pred, enc_stage_rows with enc_residual_row, enc_fq_tail.  It stages the block's residual, transforms it once (fdct4_lds
+// of thip_fdct.h), quantises the coefficients at every qi of the frame's list into LDS (quantize4_lds, whose hook sums the squared
+// error), and chooses per block:
 //   D_k  each of the block's four lanes sums the squared error of its 16 coefficients (z >= 1) at qi k; two shuffles add them;
 //   R_k  lane k of the block walks the AC levels at qi k with enc_value_tokens (enc_block_tokens's classification) and adds the
 //        token bits of the previous packet's AC tables (a 256-byte table in LDS);
@@ -22,11 +23,11 @@ struct BqiSel {      // the frame's qi list and the AC table indices (luma, chro
 // EOB included; bits [4][32]: code length + extra bits by (Huffman group - 1, token)
 __device__ __forceinline__ int bqi_ac_bits(const int4 *lv, int b, const uint8_t *bits) {
   const int16_t *l16 = reinterpret_cast<const int16_t *>(lv);
-  auto level = [&](int z) { return (int)l16[(b * 8 + (((z >> 3) + b) & 7)) * 8 + (z & 7)]; };
+  auto level = [&](int z) { return (int)l16[lds_block_at(b, z)]; };
   uint64_t nzm = 0;
 #pragma unroll
   for (int pc = 0; pc < 8; pc++) {
-    const int4 w = lv[b * 8 + ((pc + b) & 7)];
+    const int4 w = lv[lds_block_piece(b, pc)];
     const int w4[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -95,39 +96,21 @@ __device__ __forceinline__ void enc_fq_bqi(int16_t *levels, int16_t *dcq, uint8_
   enc_stage_rows(lds, b, j, k < n, [&](int r, int v[8]) { enc_residual_row(v, sb, pb, r); });
   __syncthreads();   // (the tables too)
   int o[16];
-  rate_fdct4_lds(lds, b, j, o);
-  // the levels at each qi of the list (fdct_quantize4_lds's quantiser) and the block's squared error at z >= 1
-  auto at = [&](int z) { return (b * 8 + (((z >> 3) + b) & 7)) * 8 + (z & 7); };
+  fdct4_lds(lds, b, j, o);
+  // the levels at each qi of the list and the block's squared error at z >= 1
   int64_t dist0 = 0, dist1 = 0, dist2 = 0;
 #pragma unroll 1
   for (int kq = 0; kq < sel.nqis; kq++) {
-    int16_t *d16 = reinterpret_cast<int16_t *>(lds + kq * kLv);
-    const uint2 *st = s_t + (kq * kTabs + tab) * 64;
     int64_t dist = 0;
-#pragma unroll
-    for (int q = 0; q < 16; q += 2) {
-      const uint4 e = *reinterpret_cast<const uint4 *>(&st[(2 * j + (q >> 3)) * 8 + (q & 7)]);
-#pragma unroll
-      for (int h2 = 0; h2 < 2; h2++) {
-        const uint32_t ex = h2 ? e.z : e.x, ey = h2 ? e.w : e.y;
-        const int z = (int)(ey >> 8), d = (int)(ex & 0xFFFFu), m = (int)ex >> 16, l = (int)(ey & 0xFFu);
-        const int c = o[q + h2];
-        int val = c << 1, lv = 0;
-        if (abs(val) >= d) {
-          const int sg = val >> 31;
-          val += (d + sg) ^ sg;
-          lv = sx16(((((m * val) >> 16) + val) >> l) - sg);
-        }
-        d16[at(z)] = (int16_t)lv;
-        const int64_t err = (int64_t)c - (int64_t)lv * d;
-        dist += z ? err * err : 0;
-      }
-    }
+    quantize4_lds(lds + kq * kLv, s_t + (kq * kTabs + tab) * 64, b, j, o, [&](int z, int c, int lv, int d) {
+      const int64_t err = (int64_t)c - (int64_t)lv * d;
+      dist += z ? err * err : 0;
+    });
     if (kq == 0) dist0 = dist;
     else if (kq == 1) dist1 = dist;
     else dist2 = dist;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every level of the wave is in LDS
+  wave_lds_handover();   // every level of the wave is in LDS
   int rbits = 0;
   if (j < sel.nqis) rbits = bqi_ac_bits(lds + j * kLv, b, s_bits + (p > 0 ? 128 : 0));
   const int lb = lane & ~3;
@@ -144,8 +127,8 @@ __device__ __forceinline__ void enc_fq_bqi(int16_t *levels, int16_t *dcq, uint8_
   if (sel.nqis > 2 && d2 + lam * (r2 + 1) < best) kb = 2;
   int4 *chosen = lds + kb * kLv;
   // the DC stays at qis[0]
-  if (kb && j == 0) reinterpret_cast<int16_t *>(chosen)[at(0)] = reinterpret_cast<const int16_t *>(lds)[at(0)];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if (kb && j == 0) reinterpret_cast<int16_t *>(chosen)[lds_block_at(b, 0)] = reinterpret_cast<const int16_t *>(lds)[lds_block_at(b, 0)];
+  wave_lds_handover();
   enc_fq_tail<kClasses>(levels, dcq, cmap, dclast, lds, [=](int bb) {
     return lds + __shfl(kb, bb * 4) * kLv;   // (the choice of block bb of the wave)
   }, chosen, b0, n, fi, pr.pix);

@@ -5,7 +5,8 @@
 //   k_rate_me          (inter frames) k_enc_me's search (enc_me_search, thip_encode_inter.h), writing the qi-independent statistics
 //                      of each macro block instead of a mode: S0, Smv, SI and the half-pel vector.  The mode at q then follows
 //                      from them and q's lambda (rate_mode).
-//   k_rate_fdct_key    the unquantised fDCT of every block (raster order, natural order in the block): fdct_quantize4_lds's transform.
+//   k_rate_fdct_key    the unquantised fDCT of every block (raster order, natural order in the block): fdct4_lds of
+//                      thip_fdct.h, the transform of every four-lane kernel.
 //   k_rate_fdct_inter  the same for the three residuals an inter block may code: INTRA (pixel - 128), NOMV (PREV, vector 0) and MV
 //                      (PREV through the macro block's vector) -- [3][nfrags][64].  Both stage their residuals as the frame's
 //                      kernels do (enc_stage_rows, enc_residual_row).
@@ -30,53 +31,18 @@ constexpr int kRatePartial = kRateBins + 1;  // a partial's row per qi: the bins
 constexpr int kRateTokWaves = 16;             // waves a work group of k_rate_tok (four a SIMD: the histogram allows one group a CU)
 constexpr int kRateMaxBlocksPerGroup = 960;  // a bin grows by at most 64 a block: k_rate_tok's grid keeps a group's blocks below 1020
 
-// the transform of fdct_quantize4_lds without its quantiser: on return o[h * 8 + c] holds natural position (2j + h) * 8 + c of
-// block b; the same LDS layout and contract on entry
-__device__ __forceinline__ void rate_fdct4_lds(int4 *lds, int b, int j, int o[16]) {
-  const int *ldw = reinterpret_cast<const int *>(lds);
-  int c0[8], c1[8];
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    const int w = ldw[(b * 8 + ((r + b) & 7)) * 4 + j];
-    c0[r] = sx16(sx16(w) << 2);
-    c1[r] = sx16((w >> 16) << 2);
-  }
-  if (j == 0) {
-    c0[0] = sx16(c0[0] + (c0[0] != 0) + 1);
-    c1[0] = sx16(c1[0] + 1);
-    c0[1] = sx16(c0[1] - 1);
-  }
-  fdct8(c0[0], c0[1], c0[2], c0[3], c0[4], c0[5], c0[6], c0[7]);
-  fdct8(c1[0], c1[1], c1[2], c1[3], c1[4], c1[5], c1[6], c1[7]);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  int *ldww = reinterpret_cast<int *>(lds);
-#pragma unroll
-  for (int k = 0; k < 8; k++) ldww[(b * 8 + ((k + b) & 7)) * 4 + j] = (c0[k] & 0xFFFF) | (c1[k] << 16);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const int r = 2 * j + h;
-    const int4 w = lds[b * 8 + ((r + b) & 7)];
-    int v[8] = {sx16(w.x), w.x >> 16, sx16(w.y), w.y >> 16, sx16(w.z), w.z >> 16, sx16(w.w), w.w >> 16};
-    fdct8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-#pragma unroll
-    for (int c = 0; c < 8; c++) o[h * 8 + c] = sx16((v[c] + 2) >> 2);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-// one coefficient through oc_enc_quantize (enquant.c:228-245), table entry (d | m << 16, l) as fdct_quantize4_lds uses it
+// one coefficient through the quantiser, table entry (d | m << 16, l): enc_quant_entry's with zig-zag index 0
 __device__ __forceinline__ int rate_quant(int coef, uint2 e) {
-  const int d = (int)(e.x & 0xFFFFu), m = (int)e.x >> 16, l = (int)e.y;
-  int val = coef << 1;
-  if (abs(val) < d) return 0;
-  const int sg = val >> 31;
-  val += (d + sg) ^ sg;
-  return sx16(((((m * val) >> 16) + val) >> l) - sg);
+  const QuantEntry f = quant_entry_fields(e.x, e.y);
+  return quant_level(coef, f.d, f.m, f.l, [] {});
 }
 
-// the table entry of rate_quant from its first word (enc_quant_entry's, without the zig-zag index)
-__device__ __forceinline__ uint2 rate_entry(uint32_t x) { return make_uint2(x, (uint32_t)enc_quant_shift(x & 0xFFFFu)); }
+// the table entry of rate_quant from its first word: l follows from the step
+__device__ __forceinline__ uint2 rate_entry(uint32_t x) {
+  int m, l;
+  quant_recip((x & 0xFFFFu) << 1, m, l);
+  return make_uint2(x, (uint32_t)l);
+}
 
 // the four lanes of a block store its 64 coefficients (natural order) at out[0..63]
 __device__ __forceinline__ void rate_store16(int16_t *out, int j, const int o[16]) {
@@ -101,7 +67,7 @@ __global__ __launch_bounds__(256) void k_rate_fdct_key(int16_t *coef, EncPlanes 
   enc_stage_rows(lds, b, j, fi < nfrags, [&](int r, int v[8]) { enc_residual_row(v, sb, pb, r); });
   __syncthreads();
   int o[16];
-  rate_fdct4_lds(lds, b, j, o);
+  fdct4_lds(lds, b, j, o);
   if (fi < nfrags) rate_store16(coef + fi * 64, j, o);
 }
 
@@ -141,7 +107,7 @@ __global__ __launch_bounds__(256) void k_rate_fdct_inter(int16_t *coef, EncPlane
     enc_stage_rows(lds, b, j, fi < nfrags, [&](int r, int px[8]) { enc_residual_row(px, sb, pb, r); });
     __syncthreads();
     int o[16];
-    rate_fdct4_lds(lds, b, j, o);
+    fdct4_lds(lds, b, j, o);
     if (fi < nfrags) rate_store16(coef + ((int64_t)v * nfrags + fi) * 64, j, o);
     __syncthreads();   // (the next residual reuses the LDS)
   }

@@ -226,28 +226,9 @@ __global__ __launch_bounds__(256) void k_enc_fdct(int16_t *y, const int16_t *x, 
   __shared__ int4 s_x[4 * 512];
   int4 *lds = s_x + (threadIdx.x >> 6) * 512;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int w[64];
+  int w[64], o[64];
   load_block16_wave(w, x, i, n, lds);
-#pragma unroll
-  for (int k = 0; k < 64; k++) w[k] = sx16(w[k] << 2);        // fdct.c:136
-  w[0] = sx16(w[0] + (w[0] != 0) + 1);                        // fdct.c:139-141
-  w[1] = sx16(w[1] + 1);
-  w[8] = sx16(w[8] - 1);
-  // columns of w -> rows of z (fdct.c:143), then columns of z -> rows of w (fdct.c:145).
-  // In registers: transform each column in place (result element k of column c sits at
-  // [k][c], i.e. z transposed), then each row in place; the final element (r,c) holds
-  // what the reference leaves at w[r*8+c] transposed twice == natural position.
-#pragma unroll
-  for (int c = 0; c < 8; c++)
-    fdct8(w[0 * 8 + c], w[1 * 8 + c], w[2 * 8 + c], w[3 * 8 + c], w[4 * 8 + c], w[5 * 8 + c], w[6 * 8 + c],
-          w[7 * 8 + c]);
-#pragma unroll
-  for (int r = 0; r < 8; r++)
-    fdct8(w[r * 8 + 0], w[r * 8 + 1], w[r * 8 + 2], w[r * 8 + 3], w[r * 8 + 4], w[r * 8 + 5], w[r * 8 + 6],
-          w[r * 8 + 7]);
-  int o[64];
-#pragma unroll
-  for (int k = 0; k < 64; k++) o[k] = sx16((w[kFZigZag[k]] + 2) >> 2);   // fdct.c:149
+  fdct8x8_lane(w, o);
   store_block16_wave(y, i, n, o, lds);
 }
 
@@ -256,118 +237,57 @@ __device__ __attribute__((aligned(8), unused)) constexpr uint8_t kIZigZag8[64] =
     0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
     10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
 
-// oc_enc_fdct8x8 with FOUR lanes per block (round 6; the layout of k_enc_fdct_quantize4 below, without its second half): one block per
-// lane is 700 dependent instructions a wave on 1.5 waves per SIMD behind one exposed round trip, 105 registers and 32 KB of LDS a
-// work group -- 10.4 us for the 25 MB of a 1080p 4:4:4 frame.  Lane 4b + j takes columns 2j, 2j + 1 of block b for the first pass
-// (fdct.c:143), the block is transposed through the wave's 2 KB of LDS as int16 pairs, the lane takes rows 2j, 2j + 1 for the
-// second (fdct.c:145); the zig-zag order (fdct.c:149) happens on the way out through the same 2 KB, so that loads and stores are
-// whole 16-byte pieces.
-
+// oc_enc_fdct8x8 with FOUR lanes per block (round 6; fdct4_lds of thip_fdct.h, the layout of k_enc_fdct_quantize4 below): one block
+// per lane is 700 dependent instructions a wave on 1.5 waves per SIMD behind one exposed round trip, 105 registers and 32 KB of LDS
+// a work group -- 10.4 us for the 25 MB of a 1080p 4:4:4 frame.  The zig-zag order (fdct.c:149) happens on the way out through the
+// wave's 2 KB, so that loads and stores are whole 16-byte pieces.
 __global__ __launch_bounds__(256) void k_enc_fdct4(int16_t *y, const int16_t *x, int64_t n) {
-  __shared__ int4 s_x[4 * 128];                          // 2 KB a wave: 16 blocks of eight 16-byte pieces (piece r = row r)
+  __shared__ int4 s_x[4 * 128];                          // 2 KB a wave: 16 blocks of eight 16-byte pieces
   int4 *lds = s_x + (threadIdx.x >> 6) * 128;
   const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
   const int64_t b0 = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2;   // the wave's first block
-  // piece pc of block bb lives at lds[bb * 8 + ((pc + bb) & 7)]: rotated, so that sixteen blocks' equal rows spread over the banks
-  {
-    const int4 *g = reinterpret_cast<const int4 *>(x) + b0 * 8;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-      if (b0 + bb < n) lds[bb * 8 + ((pc + bb) & 7)] = g[idx];
-    }
-  }
-  // (the wave's own 2 KB: no other wave reads them, the wave's LDS operations are issued in order -- no barrier; the zig-zag
-  //  indices of the lane's two rows come out of a 64-byte table in memory, asked for now)
-  const uint2 zz0 = reinterpret_cast<const uint2 *>(kIZigZag8)[2 * j], zz1 = reinterpret_cast<const uint2 *>(kIZigZag8)[2 * j + 1];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const int *ldw = reinterpret_cast<const int *>(lds);
-  int c0[8], c1[8];   // columns 2j and 2j + 1
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    const int w = ldw[(b * 8 + ((r + b) & 7)) * 4 + j];
-    c0[r] = sx16(sx16(w) << 2);                          // fdct.c:136
-    c1[r] = sx16((w >> 16) << 2);
-  }
-  if (j == 0) {                                          // fdct.c:139-141: positions 0, 1 and 8
-    c0[0] = sx16(c0[0] + (c0[0] != 0) + 1);
-    c1[0] = sx16(c1[0] + 1);
-    c0[1] = sx16(c0[1] - 1);
-  }
-  fdct8(c0[0], c0[1], c0[2], c0[3], c0[4], c0[5], c0[6], c0[7]);
-  fdct8(c1[0], c1[1], c1[2], c1[3], c1[4], c1[5], c1[6], c1[7]);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every lane of the wave has read the input
-  int *ldww = reinterpret_cast<int *>(lds);
-#pragma unroll
-  for (int k = 0; k < 8; k++) ldww[(b * 8 + ((k + b) & 7)) * 4 + j] = (c0[k] & 0xFFFF) | (c1[k] << 16);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  int o[16];           // rows 2j and 2j + 1, natural position (2j + h) * 8 + c at o[h * 8 + c]
-  uint2 zz[2];         // ... and their zig-zag indices, a byte each
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const int r = 2 * j + h;
-    const int4 w = lds[b * 8 + ((r + b) & 7)];
-    zz[h] = h ? zz1 : zz0;
-    int v[8] = {sx16(w.x), w.x >> 16, sx16(w.y), w.y >> 16, sx16(w.z), w.z >> 16, sx16(w.w), w.w >> 16};
-    fdct8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-#pragma unroll
-    for (int c = 0; c < 8; c++) o[h * 8 + c] = sx16((v[c] + 2) >> 2);   // fdct.c:149
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wave_blocks_in(lds, x, b0, n);
+  // (the zig-zag indices of the lane's two rows come out of a 64-byte table in memory, asked for now)
+  const uint2 zz[2] = {reinterpret_cast<const uint2 *>(kIZigZag8)[2 * j], reinterpret_cast<const uint2 *>(kIZigZag8)[2 * j + 1]};
+  wave_lds_handover();   // (the wave's own 2 KB: no work-group barrier)
+  int o[16];
+  fdct4_lds(lds, b, j, o);
   int16_t *lds16 = reinterpret_cast<int16_t *>(lds);
-  // where zig-zag index z of block b lies in the wave's area (the same rotation of 16-byte pieces)
-  auto at = [&](int z) { return (b * 8 + (((z >> 3) + b) & 7)) * 8 + (z & 7); };
 #pragma unroll
   for (int h = 0; h < 2; h++)
 #pragma unroll
     for (int c = 0; c < 8; c++) {
       const uint32_t word = c < 4 ? zz[h].x : zz[h].y;
-      lds16[at((int)((word >> (8 * (c & 3))) & 0xFFu))] = (int16_t)o[h * 8 + c];
+      lds16[lds_block_at(b, (int)((word >> (8 * (c & 3))) & 0xFFu))] = (int16_t)o[h * 8 + c];
     }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  int4 *g = reinterpret_cast<int4 *>(y) + b0 * 8;
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-    if (b0 + bb < n) g[idx] = lds[bb * 8 + ((pc + bb) & 7)];
-  }
+  wave_lds_handover();
+  wave_blocks_out(y, lds, b0, n);
 }
 
-// oc_enc_quantize_c (enquant.c:219-248); the {m,l} reciprocal of each step is derived in
-// place exactly as oc_iquant_init does (enquant.c:183-191).
-__global__ __launch_bounds__(256) void k_enc_quantize(int16_t *qdct, int32_t *nonzero, const int16_t *dct,
-                                                     const uint16_t *dequant, int64_t n) {
+// oc_enc_quantize_c (enquant.c:219-248), one block a lane.  enquant: the 64-entry {m, l} table thip_enc_enquant_table_init built
+// once (oc_enc_enquant_table_init, enquant.c:194), as the reference's quantize slot receives it (encint.h:319-320); null: the
+// reciprocal of each step is derived in place (quant_recip).
+__device__ __forceinline__ void enc_quantize_body(int16_t *qdct, int32_t *nonzero, const int16_t *dct, const uint16_t *dequant,
+                                                  const int16_t *enquant, int64_t n) {
   __shared__ int s_d[64], s_m[64], s_l[64];
-  if (threadIdx.x < 64) {
-    const uint32_t d = (uint32_t)dequant[threadIdx.x] << 1;
-    const int l = 31 - __builtin_clz(d);                       // OC_ILOGNZ_32(d)-1
-    const uint32_t t = 1u + ((1u << (16 + l)) / d);
-    s_d[threadIdx.x] = (int)dequant[threadIdx.x];
-    s_m[threadIdx.x] = (int)(int16_t)(t - 0x10000u);
-    s_l[threadIdx.x] = l;
-  }
+  quant_tables(s_d, s_m, s_l, dequant, enquant);
   __syncthreads();
   __shared__ int4 s_x[4 * 512];
   int4 *lds = s_x + (threadIdx.x >> 6) * 512;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int v[64];
   load_block16_wave(v, dct, i, n, lds);
-  int nz = 0;
-#pragma unroll
-  for (int z = 0; z < 64; z++) {
-    int val = v[z] << 1;
-    const int d = s_d[z];
-    int q = 0;
-    if (abs(val) >= d) {
-      const int s = val >> 31;
-      val += (d + s) ^ s;
-      q = sx16(((((s_m[z] * val) >> 16) + val) >> s_l[z]) - s);
-      nz = z;
-    }
-    v[z] = q;
-  }
+  const int nz = quantize_lane(v, s_d, s_m, s_l);
   store_block16_wave(qdct, i, n, v, lds);
   if (i < n) nonzero[i] = nz;
+}
+__global__ __launch_bounds__(256) void k_enc_quantize(int16_t *qdct, int32_t *nonzero, const int16_t *dct,
+                                                     const uint16_t *dequant, int64_t n) {
+  enc_quantize_body(qdct, nonzero, dct, dequant, nullptr, n);
+}
+__global__ __launch_bounds__(256) void k_enc_quantize_tab(int16_t *qdct, int32_t *nonzero, const int16_t *dct,
+                                                         const uint16_t *dequant, const int16_t *enquant, int64_t n) {
+  enc_quantize_body(qdct, nonzero, dct, dequant, enquant, n);
 }
 
 // oc_enc_fdct8x8 followed by oc_enc_quantize on the same block (what oc_enc_block_transform_quantize does with every residual,
@@ -376,54 +296,16 @@ __global__ __launch_bounds__(256) void k_enc_quantize(int16_t *qdct, int32_t *no
 __global__ __launch_bounds__(256) void k_enc_fdct_quantize(int16_t *qdct, int32_t *nonzero, int16_t *dct_out, const int16_t *x,
                                                           const uint16_t *dequant, const int16_t *enquant, int64_t n) {
   __shared__ int s_d[64], s_m[64], s_l[64];
-  if (threadIdx.x < 64) {
-    s_d[threadIdx.x] = (int)dequant[threadIdx.x];
-    if (enquant) {
-      s_m[threadIdx.x] = (int)enquant[2 * threadIdx.x];
-      s_l[threadIdx.x] = (int)enquant[2 * threadIdx.x + 1];
-    } else {   // oc_iquant_init (enquant.c:183-191)
-      const uint32_t d = (uint32_t)dequant[threadIdx.x] << 1;
-      const int l = 31 - __builtin_clz(d);
-      const uint32_t t = 1u + ((1u << (16 + l)) / d);
-      s_m[threadIdx.x] = (int)(int16_t)(t - 0x10000u);
-      s_l[threadIdx.x] = l;
-    }
-  }
+  quant_tables(s_d, s_m, s_l, dequant, enquant);
   __shared__ int4 s_x[4 * 512];
   int4 *lds = s_x + (threadIdx.x >> 6) * 512;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int w[64];
+  int w[64], o[64];
   load_block16_wave(w, x, i, n, lds);
-#pragma unroll
-  for (int k = 0; k < 64; k++) w[k] = sx16(w[k] << 2);        // fdct.c:136
-  w[0] = sx16(w[0] + (w[0] != 0) + 1);                        // fdct.c:139-141
-  w[1] = sx16(w[1] + 1);
-  w[8] = sx16(w[8] - 1);
-#pragma unroll
-  for (int c = 0; c < 8; c++)
-    fdct8(w[0 * 8 + c], w[1 * 8 + c], w[2 * 8 + c], w[3 * 8 + c], w[4 * 8 + c], w[5 * 8 + c], w[6 * 8 + c], w[7 * 8 + c]);
-#pragma unroll
-  for (int r = 0; r < 8; r++)
-    fdct8(w[r * 8 + 0], w[r * 8 + 1], w[r * 8 + 2], w[r * 8 + 3], w[r * 8 + 4], w[r * 8 + 5], w[r * 8 + 6], w[r * 8 + 7]);
-  int o[64];
-#pragma unroll
-  for (int k = 0; k < 64; k++) o[k] = sx16((w[kFZigZag[k]] + 2) >> 2);   // fdct.c:149
+  fdct8x8_lane(w, o);
   if (dct_out) store_block16_wave(dct_out, i, n, o, lds);
   __syncthreads();   // the tables; and every wave is done with its LDS area's first use
-  int nz = 0;
-#pragma unroll
-  for (int z = 0; z < 64; z++) {   // enquant.c:228-245
-    int val = o[z] << 1;
-    const int d = s_d[z];
-    int q = 0;
-    if (abs(val) >= d) {
-      const int sg = val >> 31;
-      val += (d + sg) ^ sg;
-      q = sx16(((((s_m[z] * val) >> 16) + val) >> s_l[z]) - sg);
-      nz = z;
-    }
-    o[z] = q;
-  }
+  const int nz = quantize_lane(o, s_d, s_m, s_l);
   store_block16_wave(qdct, i, n, o, lds);
   if (i < n) nonzero[i] = nz;
 }
@@ -431,162 +313,44 @@ __global__ __launch_bounds__(256) void k_enc_fdct_quantize(int16_t *qdct, int32_
 // The same pass with FOUR lanes per block (the default of thip_enc_fdct_quantize_batch).  One block per lane is 1 500 dependent
 // vector instructions a wave, and a 1080p 4:4:4 frame is 1 530 such waves -- one and a half per SIMD, issuing at the single-wave
 // rate (8.3 clocks an instruction, profiles/r04_valu_rate2.txt) behind one exposed round trip: 17.3 us, slower per block than
-// either half alone.  Here lane 4b + j takes columns 2j, 2j + 1 of block b for the first pass (fdct.c:143), the block is
-// transposed through the wave's 2 KB of LDS as int16 pairs, the lane takes rows 2j, 2j + 1 for the second (fdct.c:145), and it
-// quantises its sixteen coefficients with the tables kept by NATURAL position; the zig-zag order (fdct.c:149) happens on the way
-// out, through the same 2 KB, so that the stores are whole 16-byte pieces.  Four times the waves, a quarter of the chain each.
+// either half alone.  Here four lanes transform a block (fdct4_lds) and each quantises its sixteen coefficients with the tables
+// kept by NATURAL position (quantize4_lds); the zig-zag order (fdct.c:149) happens on the way out, through the wave's 2 KB, so that
+// the stores are whole 16-byte pieces.  Four times the waves, a quarter of the chain each.
 __global__ __launch_bounds__(256) void k_enc_fdct_quantize4(int16_t *qdct, int32_t *nonzero, int16_t *dct_out, const int16_t *x,
                                                            const uint16_t *dequant, const int16_t *enquant, int64_t n) {
-  // by natural position, ONE 8-byte entry: step | reciprocal m << 16, shift l | zig-zag index << 8 -- a lane's sixteen positions are
-  // two runs of eight entries, eight 16-byte LDS reads instead of the 64 four-byte ones of four separate tables (the LDS pipe is
-  // one per compute unit: with four lanes a block it is as busy as the vector units)
+  // by natural position, ONE 8-byte entry (quant_entry) -- a lane's sixteen positions are two runs of eight entries, eight 16-byte
+  // LDS reads instead of the 64 four-byte ones of four separate tables (the LDS pipe is one per compute unit: with four lanes a
+  // block it is as busy as the vector units)
   __shared__ __attribute__((aligned(16))) uint2 s_t[64];
   if (threadIdx.x < 64) {
-    const int z = (int)threadIdx.x, pos = kFZigZag[z];
+    const int z = (int)threadIdx.x;
     int m, l;
-    if (enquant) {
-      m = (int)enquant[2 * z];
-      l = (int)enquant[2 * z + 1];
-    } else {   // oc_iquant_init (enquant.c:183-191)
-      const uint32_t d = (uint32_t)dequant[z] << 1;
-      l = 31 - __builtin_clz(d);
-      const uint32_t t = 1u + ((1u << (16 + l)) / d);
-      m = (int)(int16_t)(t - 0x10000u);
-    }
-    s_t[pos] = make_uint2((uint32_t)dequant[z] | (uint32_t)(uint16_t)m << 16, (uint32_t)(l & 0xFF) | (uint32_t)z << 8);
+    quant_recip_at(dequant, enquant, z, m, l);
+    s_t[kFZigZag[z]] = quant_entry(dequant[z], m, l, z);
   }
-  __shared__ int4 s_x[4 * 128];                          // 2 KB a wave: 16 blocks of eight 16-byte pieces (piece r = row r)
+  __shared__ int4 s_x[4 * 128];                          // 2 KB a wave: 16 blocks of eight 16-byte pieces
   int4 *lds = s_x + (threadIdx.x >> 6) * 128;
   const int lane = (int)threadIdx.x & 63, b = lane >> 2, j = lane & 3;
   const int64_t b0 = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u)) >> 2;   // the wave's first block
   const int64_t i = b0 + b;
-  // piece pc of block bb lives at lds[bb * 8 + ((pc + bb) & 7)]: rotated, so that sixteen blocks' equal rows spread over the banks
-  {
-    const int4 *g = reinterpret_cast<const int4 *>(x) + b0 * 8;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-      if (b0 + bb < n) lds[bb * 8 + ((pc + bb) & 7)] = g[idx];
-    }
-  }
+  wave_blocks_in(lds, x, b0, n);
   __syncthreads();   // (the tables too)
-  const int *ldw = reinterpret_cast<const int *>(lds);
-  int c0[8], c1[8];   // columns 2j and 2j + 1
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    const int w = ldw[(b * 8 + ((r + b) & 7)) * 4 + j];
-    c0[r] = sx16(sx16(w) << 2);                          // fdct.c:136
-    c1[r] = sx16((w >> 16) << 2);
-  }
-  if (j == 0) {                                          // fdct.c:139-141: positions 0, 1 and 8
-    c0[0] = sx16(c0[0] + (c0[0] != 0) + 1);
-    c1[0] = sx16(c1[0] + 1);
-    c0[1] = sx16(c0[1] - 1);
-  }
-  fdct8(c0[0], c0[1], c0[2], c0[3], c0[4], c0[5], c0[6], c0[7]);
-  fdct8(c1[0], c1[1], c1[2], c1[3], c1[4], c1[5], c1[6], c1[7]);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every lane of the wave has read the input
-  int *ldww = reinterpret_cast<int *>(lds);
-#pragma unroll
-  for (int k = 0; k < 8; k++) ldww[(b * 8 + ((k + b) & 7)) * 4 + j] = (c0[k] & 0xFFFF) | (c1[k] << 16);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  int o[16];           // rows 2j and 2j + 1, natural position (2j + h) * 8 + c at o[h * 8 + c]
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const int r = 2 * j + h;
-    const int4 w = lds[b * 8 + ((r + b) & 7)];
-    int v[8] = {sx16(w.x), w.x >> 16, sx16(w.y), w.y >> 16, sx16(w.z), w.z >> 16, sx16(w.w), w.w >> 16};
-    fdct8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-#pragma unroll
-    for (int c = 0; c < 8; c++) o[h * 8 + c] = sx16((v[c] + 2) >> 2);   // fdct.c:149
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  int16_t *lds16 = reinterpret_cast<int16_t *>(lds);
-  // where zig-zag index z of block b lies in the wave's area (the same rotation of 16-byte pieces)
-  auto at = [&](int z) { return (b * 8 + (((z >> 3) + b) & 7)) * 8 + (z & 7); };
-  // (the table entries of positions k, k + 1: one 16-byte read)
-  auto entries = [&](int k) { return *reinterpret_cast<const uint4 *>(&s_t[(2 * j + (k >> 3)) * 8 + (k & 7)]); };
+  int o[16];
+  fdct4_lds(lds, b, j, o);
   if (dct_out) {
-#pragma unroll
-    for (int k = 0; k < 16; k += 2) {
-      const uint4 e = entries(k);
-      lds16[at((int)(e.y >> 8))] = (int16_t)o[k];
-      lds16[at((int)(e.w >> 8))] = (int16_t)o[k + 1];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    int4 *g = reinterpret_cast<int4 *>(dct_out) + b0 * 8;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-      if (b0 + bb < n) g[idx] = lds[bb * 8 + ((pc + bb) & 7)];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    int16_t *lds16 = reinterpret_cast<int16_t *>(lds);
+    lane_entries4(s_t, j, [&](int k, const QuantEntry &e) { lds16[lds_block_at(b, e.z)] = (int16_t)o[k]; });
+    wave_lds_handover();
+    wave_blocks_out(dct_out, lds, b0, n);
+    wave_lds_handover();
   }
-  int nz = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k += 2) {   // enquant.c:228-245
-    const uint4 e = entries(k);
-#pragma unroll
-    for (int h2 = 0; h2 < 2; h2++) {
-      const uint32_t ex = h2 ? e.z : e.x, ey = h2 ? e.w : e.y;
-      const int z = (int)(ey >> 8), d = (int)(ex & 0xFFFFu), m = (int)ex >> 16, l = (int)(ey & 0xFFu);
-      int val = o[k + h2] << 1, q = 0;
-      if (abs(val) >= d) {
-        const int sg = val >> 31;
-        val += (d + sg) ^ sg;
-        q = sx16(((((m * val) >> 16) + val) >> l) - sg);
-        nz = max(nz, z);            // (the reference's loop runs up the zig-zag order: the last index that passes is the largest)
-      }
-      lds16[at(z)] = (int16_t)q;
-    }
-  }
+  // (the reference's loop runs up the zig-zag order: the last index that passes is the largest)
+  int nz = quantize4_lds(lds, s_t, b, j, o, [](int, int, int, int) {});
   nz = max(nz, __shfl_xor(nz, 1));
   nz = max(nz, __shfl_xor(nz, 2));
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  {
-    int4 *g = reinterpret_cast<int4 *>(qdct) + b0 * 8;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const int idx = q * 64 + lane, bb = idx >> 3, pc = idx & 7;
-      if (b0 + bb < n) g[idx] = lds[bb * 8 + ((pc + bb) & 7)];
-    }
-  }
+  wave_lds_handover();
+  wave_blocks_out(qdct, lds, b0, n);
   if (j == 0 && i < n) nonzero[i] = nz;
-}
-
-// The same with the reciprocals handed in: `enquant` is the 64-entry {m, l} table
-// thip_enc_enquant_table_init built once (oc_enc_enquant_table_init, enquant.c:194), as the
-// reference's quantize slot receives it (encint.h:319-320), instead of being re-derived per launch.
-__global__ __launch_bounds__(256) void k_enc_quantize_tab(int16_t *qdct, int32_t *nonzero, const int16_t *dct,
-                                                         const uint16_t *dequant, const int16_t *enquant, int64_t n) {
-  __shared__ int s_d[64], s_m[64], s_l[64];
-  if (threadIdx.x < 64) {
-    s_d[threadIdx.x] = (int)dequant[threadIdx.x];
-    s_m[threadIdx.x] = (int)enquant[2 * threadIdx.x];
-    s_l[threadIdx.x] = (int)enquant[2 * threadIdx.x + 1];
-  }
-  __syncthreads();
-  __shared__ int4 s_x[4 * 512];
-  int4 *lds = s_x + (threadIdx.x >> 6) * 512;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int v[64];
-  load_block16_wave(v, dct, i, n, lds);
-  int nz = 0;
-#pragma unroll
-  for (int z = 0; z < 64; z++) {
-    int val = v[z] << 1;
-    const int d = s_d[z];
-    int q = 0;
-    if (abs(val) >= d) {
-      const int s = val >> 31;
-      val += (d + s) ^ s;
-      q = sx16(((((s_m[z] * val) >> 16) + val) >> s_l[z]) - s);
-      nz = z;
-    }
-    v[z] = q;
-  }
-  store_block16_wave(qdct, i, n, v, lds);
-  if (i < n) nonzero[i] = nz;
 }
 
 // Stream and completion policy of the batched entry points below (thip_set_batch_stream).
@@ -620,11 +384,11 @@ int thip_enc_quantize_batch(int16_t *qdct, int32_t *nonzero, const int16_t *dct,
 void thip_enc_enquant_table_init(void *enquant, const uint16_t dequant[64]) {
   int16_t *t = (int16_t *)enquant;   // oc_iquant {ogg_int16_t m, l} (enquant.h), 64 entries
   for (int zzi = 0; zzi < 64; zzi++) {
-    // oc_iquant_init, enquant.c:183-191
+    // (a zero step is not legal; it gets the reciprocal of d = 1 and no division by zero)
     const uint32_t d = (uint32_t)dequant[zzi] << 1;
-    const int l = 31 - __builtin_clz(d | 1u);
-    const uint32_t tt = 1u + ((1u << (16 + l)) / (d ? d : 1u));
-    t[2 * zzi] = (int16_t)(tt - 0x10000u);
+    int m, l;
+    quant_recip(d ? d : 1u, m, l);
+    t[2 * zzi] = (int16_t)m;
     t[2 * zzi + 1] = (int16_t)l;
   }
 }
