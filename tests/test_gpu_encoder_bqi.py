@@ -49,7 +49,15 @@ CASES = [   # (w, h, fmt, pic, quality, delta, content, inter, eight modes, devi
     (96, 64, 2, (1, 2, 93, 61), 24, 5, "cut", True, False, True, 5),
     (96, 64, 0, None, 40, 8, "shear", True, True, False, 5),
     (96, 64, 3, None, 28, 31, "uncover", True, True, True, 5),
+    # the smallest frames at which the geometry can go wrong, in every pixel format, a key frame and two inter frames with all
+    # eight modes: one macro block (every super block partial; a 1x1 chroma plane at 4:2:0), and 6x10 luma fragments over 3x5
+    # chroma fragments at 4:2:0 (super blocks partial in both directions, odd chroma counts)
     (16, 16, 0, None, 48, 3, "pan", True, True, False, 3),
+    (16, 16, 2, None, 40, 5, "shear", True, True, False, 3),
+    (16, 16, 3, None, 32, 6, "uncover", True, True, True, 3),
+    (48, 80, 0, None, 36, 8, "uncover", True, True, False, 3),
+    (48, 80, 2, None, 28, 6, "shear", True, True, True, 3),
+    (48, 80, 3, None, 44, 10, "pan", True, True, False, 3),
 ]
 
 

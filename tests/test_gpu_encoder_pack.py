@@ -126,6 +126,9 @@ def test_bqi_packets_equal_the_restatement(hip, w, h, fmt, pic, quality, delta, 
             want = ref.frame(fr, quality)
             assert out[f]["bqi"] == want["bqi"], (f, out[f]["bqi"], want["bqi"])
             assert out[f]["packet"] == want["packet"], (f, len(out[f]["packet"]), len(want["packet"]), out[f]["pack"])
+            if inter:   # th_decode_*'s picture of the packets is the oracle's
+                for p in range(3):
+                    assert np.array_equal(out[f]["recon"][p], ref.recon[p]), (f, p)
     finally:
         ref.close()
     _packed_on_device(out)

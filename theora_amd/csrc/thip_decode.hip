@@ -41,6 +41,8 @@
 
 #include "../../include/theora_hip.h"
 #include "thip_device.h"
+#include "thip_ctx.h"
+#include "thip_device_guard.h"
 
 using namespace thip;
 
@@ -57,16 +59,6 @@ using namespace thip;
 // ---------------------------------------------------------------------------------------
 // run-time options: one table, one parser (include/theora_hip.h: thip_set_option)
 // ---------------------------------------------------------------------------------------
-// a spinning thread's pause: the x86 hint where there is one (the unguarded builtin kept other hosts from compiling)
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#elif defined(__aarch64__)
-  asm volatile("yield" ::: "memory");
-#else
-  std::this_thread::yield();
-#endif
-}
 namespace {
 struct Option {
   const char *name;
@@ -339,19 +331,6 @@ int g_ctx_ready[kMaxDevices], g_next_ctx[kMaxDevices];
 // tens of microseconds of host time, which a caller that brackets 0.8 ms of work with it (bench.py's blocks) would book as GPU time.
 std::atomic<uint8_t> g_lane_dirty[kMaxDevices][kMaxLanes], g_ctx_dirty[kMaxDevices][kCtxLanes];
 
-// Makes `device` current for the calling host thread for the lifetime of the object (HIP's current
-// device is per thread) and puts the previous one back: a state may live on any GPU of the node
-// whatever the caller's current device is.
-struct DeviceGuard {
-  int prev = -1, want;
-  explicit DeviceGuard(int device) : want(device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want) (void)hipSetDevice(want);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
-  }
-};
 int g_profile = 0;
 // Every state has a pinned host word that kernels set when a bounded wait ran out (k_recon_lf's hand-over: bit 0; the
 // de-ringing's: bit 1).  The calls that synchronise with a state look at it (check_fault, below launch_chunk): a frame whose
@@ -870,8 +849,7 @@ static int wait_event(hipEvent_t ev) {
   // Look continuously for the first 60 microseconds -- what is left of a frame's kernels when the host gets here is usually
   // shorter than the shortest sleep the kernel grants (a 20-us nanosleep returns after 70) --, then in short sleeps: a context
   // that waits longer must not hold a core other contexts' entropy decoders want.
-  timespec t0;
-  clock_gettime(CLOCK_MONOTONIC, &t0);
+  const double t0 = thip_now();
   for (int polls = 0;; polls++) {
     const hipError_t e = hipEventQuery(ev);
     if (e == hipSuccess) return THIP_OK;
@@ -880,10 +858,7 @@ static int wait_event(hipEvent_t ev) {
       return THIP_EFAULT;
     }
     if (polls >= 8) {
-      timespec t1;
-      clock_gettime(CLOCK_MONOTONIC, &t1);
-      const long long ns = (long long)(t1.tv_sec - t0.tv_sec) * 1000000000ll + (t1.tv_nsec - t0.tv_nsec);
-      if (ns > 60000) {
+      if (thip_now() - t0 > 60e-6) {
         timespec ts = {0, 20000};
         nanosleep(&ts, nullptr);
       } else {

@@ -5,6 +5,10 @@
 // (EOB runs, tables, bits) is made on the device too (thip_encode_pack.h) and the host writes the frame header only.  The bitstream
 // is stated in the header comment of theoraenc_hip.h.
 //
+// What the bitstream fixes for encoder and decoder alike -- the tables, the frame's geometry (th_enc_ctx is a FrameGeometry), the
+// quantisation matrix (the setup is a QuantParams: compute_qmat gives every step, and the setup header is written from it), the
+// run-length and vector codes -- is thip_bitstream.h's, shared with the decoder's front end.
+//
 // The reference of an inter frame is the encoder's own reconstruction of the previous frame, made by a th_decode_* context of this
 // library fed with every packet the encoder returns (loop filter included): the encoder's reference is then the decoder's picture by
 // construction, bit for bit, and the decoder's kernels do the work (dequantisation, iDCT, prediction, the uncoded copies, the loop
@@ -15,7 +19,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <atomic>
@@ -28,7 +31,9 @@
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_pack.h"
+#include "thip_bitstream.h"
 #include "thip_ctx.h"
+#include "thip_device_guard.h"
 
 using namespace thip;
 
@@ -42,26 +47,6 @@ namespace {
       return TH_EFAULT;                                                                                                \
     }                                                                                                                  \
   } while (0)
-
-struct EncDeviceGuard {   // the context's device current for the calling thread while the object lives
-  int prev = -1, want;
-  explicit EncDeviceGuard(int device) : want(device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want) (void)hipSetDevice(want);
-  }
-  ~EncDeviceGuard() {
-    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
-  }
-};
-
-// natural position of zig-zag index z
-const int kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-// extra bits after each DCT token (spec Tables 7.33 / 7.38)
-const uint8_t kExtraBits[32] = {0, 0, 0, 2, 3, 4, 12, 3, 6, 0, 0, 0, 0, 1, 1, 1, 1, 2, 3, 4, 5, 6, 10, 1, 1, 1, 1, 1, 3, 4, 2, 3};
-
-int ilog(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
 
 // MSB-first bit writer with a 64-bit accumulator
 struct BitW {
@@ -86,9 +71,7 @@ struct BitW {
 
 // ---- the setup header's contents (theoraenc_hip.h) -------------------------------------------------------------------
 struct EncSetup {
-  uint8_t lflims[64];
-  uint16_t acscale[64], dcscale[64];
-  uint8_t bms[3][64];           // luma intra, chroma intra, inter (natural order)
+  QuantParams qp;               // three base matrices (luma intra, chroma intra, inter); one range of 63 a (qti, pli), both ends alike
   uint32_t code[80][32];        // Huffman codes (MSB first), lengths
   uint8_t len[80][32];
   std::vector<uint8_t> trees;   // the 80 trees as written (spec 6.4.4), a bit string packed MSB first ...
@@ -154,16 +137,25 @@ void huffman(const double w[32], uint32_t code[32], uint8_t len[32], BitW &tree)
 }
 
 void enc_setup_init(EncSetup &s) {
+  QuantParams &q = s.qp;
   for (int qi = 0; qi < 64; qi++) {
-    s.lflims[qi] = (uint8_t)((31 * (63 - qi) + 31) / 63);
-    s.acscale[qi] = (uint16_t)lround(400.0 * pow(10.0 / 400.0, qi / 63.0));
-    s.dcscale[qi] = (uint16_t)lround(200.0 * pow(10.0 / 200.0, qi / 63.0));
+    q.lflims[qi] = (uint8_t)((31 * (63 - qi) + 31) / 63);
+    q.acscale[qi] = (uint16_t)lround(400.0 * pow(10.0 / 400.0, qi / 63.0));
+    q.dcscale[qi] = (uint16_t)lround(200.0 * pow(10.0 / 200.0, qi / 63.0));
   }
+  q.nbms = 3;
+  q.bms.resize(3 * 64);
   for (int r = 0; r < 8; r++)
     for (int c = 0; c < 8; c++) {
-      s.bms[0][r * 8 + c] = (uint8_t)(16 + 3 * (r + c) + (r * c) / 4);
-      s.bms[1][r * 8 + c] = (uint8_t)(18 + 5 * (r + c));
-      s.bms[2][r * 8 + c] = (uint8_t)(16 + 2 * (r + c));
+      q.bms[0 * 64 + r * 8 + c] = (uint8_t)(16 + 3 * (r + c) + (r * c) / 4);
+      q.bms[1 * 64 + r * 8 + c] = (uint8_t)(18 + 5 * (r + c));
+      q.bms[2 * 64 + r * 8 + c] = (uint8_t)(16 + 2 * (r + c));
+    }
+  for (int qti = 0; qti < 2; qti++)
+    for (int pli = 0; pli < 3; pli++) {
+      q.nqrs[qti][pli] = 1;
+      q.qrsizes[qti][pli][0] = 63;
+      q.qrbmis[qti][pli][0] = q.qrbmis[qti][pli][1] = qti ? 2 : pli ? 1 : 0;
     }
   s.trees.clear();
   BitW t{&s.trees};
@@ -176,27 +168,11 @@ void enc_setup_init(EncSetup &s) {
   t.flush();
 }
 
-// spec 6.4.3 for one quant range whose two ends are base matrix bm: the intra step of (pli, qi) at zig-zag index z
-uint16_t enc_qstep(const EncSetup &s, int pli, int qi, int z) {
-  const int ci = kZigZag[z], bm = s.bms[pli == 0 ? 0 : 1][ci];
-  const int qmin = ci == 0 ? 16 : 8, scale = ci == 0 ? s.dcscale[qi] : s.acscale[qi];
-  return (uint16_t)std::max(qmin, std::min((scale * bm / 100) * 4, 4096));
-}
-// ... and the inter step (every plane uses the inter base matrix)
-uint16_t enc_qstep_inter(const EncSetup &s, int qi, int z) {
-  const int ci = kZigZag[z], bm = s.bms[2][ci];
-  const int qmin = ci == 0 ? 32 : 16, scale = ci == 0 ? s.dcscale[qi] : s.acscale[qi];
-  return (uint16_t)std::max(qmin, std::min((scale * bm / 100) * 4, 4096));
-}
-
 // spec 7.2.1 (long: runs up to 4129, a new bit after a run of 4129) and 7.2.2 (short: runs up to 30, the bit always flips; the
 // block flags of partially coded super blocks never hold a longer run, since each such super block has a block of either value)
 void enc_put_runs(BitW &bw, const std::vector<uint8_t> &bits, bool lng) {
-  struct Code { uint32_t code; int len, start, nb; };
-  static const Code kLong[7] = {{0, 1, 1, 0}, {2, 2, 2, 1}, {6, 3, 4, 1}, {14, 4, 6, 2}, {30, 5, 10, 3}, {62, 6, 18, 4},
-                                {63, 6, 34, 12}};
-  static const Code kShort[6] = {{0, 1, 1, 1}, {2, 2, 3, 1}, {6, 3, 5, 1}, {14, 4, 7, 2}, {30, 5, 11, 2}, {31, 5, 15, 4}};
-  const size_t n = bits.size(), maxrun = lng ? 4129 : 30;
+  const RunCode &rc = lng ? kLongRuns : kShortRuns;
+  const size_t n = bits.size(), maxrun = (size_t)rc.longest();
   if (!n) return;
   int cur = bits[0];
   bw.put((uint32_t)cur, 1);
@@ -205,15 +181,14 @@ void enc_put_runs(BitW &bw, const std::vector<uint8_t> &bits, bool lng) {
     size_t j = i;
     while (j < n && bits[j] == cur && j - i < maxrun) j++;
     const int run = (int)(j - i);
-    for (const Code &c : lng ? std::vector<Code>(kLong, kLong + 7) : std::vector<Code>(kShort, kShort + 6))
-      if (run < c.start + (1 << c.nb)) {
-        bw.put(c.code, c.len);
-        bw.put((uint32_t)(run - c.start), c.nb);
-        break;
-      }
+    int k = 0;
+    while (run >= rc.cls[k].start + (1 << rc.cls[k].bits)) k++;
+    if (k < rc.last) bw.put((2u << k) - 2, k + 1);   // k ones and a zero
+    else bw.put((1u << k) - 1, k);                   // the last class: all ones
+    bw.put((uint32_t)(run - rc.cls[k].start), rc.cls[k].bits);
     i = j;
     if (i >= n) break;
-    if (lng && run == 4129) {
+    if (lng && (size_t)run == maxrun) {
       cur = bits[i];
       bw.put((uint32_t)cur, 1);
     } else {
@@ -222,44 +197,22 @@ void enc_put_runs(BitW &bw, const std::vector<uint8_t> &bits, bool lng) {
   }
 }
 
-// spec 7.5.1: bits of one vector component in scheme 0 (VLC), and the component written in scheme mvs
-int enc_mv_vlc_bits(int v) {
-  const int a = abs(v);
-  return a <= 1 ? 3 : a <= 3 ? 4 : a <= 7 ? 6 : a <= 15 ? 7 : 8;
-}
+// spec 7.5.1: one vector component written in scheme mvs (0: the VLC of Table 7.23)
 void enc_put_mv(BitW &bw, int v, int mvs) {
-  const int a = abs(v), sg = v < 0;
   if (mvs) {
-    bw.put((uint32_t)a, 5);
-    bw.put((uint32_t)sg, 1);
-  } else if (a == 0) {
-    bw.put(0, 3);
-  } else if (a == 1) {
-    bw.put(sg ? 2 : 1, 3);
+    bw.put((uint32_t)abs(v), 5);
+    bw.put(v < 0, 1);
   } else {
-    if (a <= 3) bw.put(a == 2 ? 3 : 4, 3);
-    else if (a <= 7) { bw.put(5, 3); bw.put((uint32_t)(a - 4), 2); }
-    else if (a <= 15) { bw.put(6, 3); bw.put((uint32_t)(a - 8), 3); }
-    else { bw.put(7, 3); bw.put((uint32_t)(a - 16), 4); }
-    bw.put((uint32_t)sg, 1);
+    bw.put(kMvVlc.code[v + 31], kMvVlc.nbits[v + 31]);
   }
 }
 
-// spec 7.4: the mode alphabets of schemes 1..6 (code index -> mode)
-const int kModeAlphabets[6][8] = {{3, 4, 2, 0, 1, 5, 6, 7}, {3, 4, 0, 2, 1, 5, 6, 7}, {3, 2, 4, 0, 1, 5, 6, 7},
-                                  {3, 2, 0, 4, 1, 5, 6, 7}, {0, 3, 4, 2, 1, 5, 6, 7}, {0, 5, 3, 4, 2, 1, 6, 7}};
-enum { kModeNomv = 0, kModeIntra = 1, kModeMv = 2, kModeMvLast = 3, kModeMvLast2 = 4, kModeGoldNomv = 5, kModeGoldMv = 6,
-       kModeMvFour = 7 };
-
 }  // namespace
 
-struct th_enc_ctx : thip_ctx_head {
+struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bitstream.h)
   int device_req, device = -1;
   bool dev_ready = false;
-  int hdec, vdec;
-  int nh[3], nv[3], froff[3], nfrags;
   int cx0[3], cy0[3], cw[3], ch[3];   // the picture region per plane (spec 4.4), rows from the top
-  std::vector<int32_t> coded_order;
   EncSetup setup;
   int qi;
   int nheaders_out = 0;
@@ -288,8 +241,7 @@ struct th_enc_ctx : thip_ctx_head {
   bool inter = false, frame_key = true;
   int64_t kf_interval = 1;
   int nmbx = 0, nmbs = 0;
-  std::vector<int32_t> sb_len;     // fragments of each super block (all planes) in coded order
-  std::vector<int32_t> mb_order;   // macro blocks (raster index, rows from the bottom) in coded order
+  int lambda[64];                  // the search's weight at each qi: the inter step of zig-zag index 1
   uint32_t *d_mb = nullptr, *d_dclast = nullptr, *h_mb = nullptr;
   uint8_t *d_cmap = nullptr, *h_cmap = nullptr;
   int16_t *d_dcr = nullptr;
@@ -371,47 +323,23 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   e->granpos_bias = 1;
   e->device_req = device;
   e->qi = i.quality;
-  e->hdec = !(i.pixel_fmt & 1);
-  e->vdec = !(i.pixel_fmt & 2);
-  const int yh = (int)i.frame_width >> 3, yv = (int)i.frame_height >> 3;
-  int off = 0;
+  build_geometry(*e, (int)i.frame_width, (int)i.frame_height, (int)i.pixel_fmt);
   for (int p = 0; p < 3; p++) {
-    e->nh[p] = p ? (yh + e->hdec) >> e->hdec : yh;
-    e->nv[p] = p ? (yv + e->vdec) >> e->vdec : yv;
-    e->froff[p] = off;
-    off += e->nh[p] * e->nv[p];
     const int hd = p ? e->hdec : 0, vd = p ? e->vdec : 0;
     e->cx0[p] = (int)i.pic_x >> hd;
     e->cy0[p] = (int)i.pic_y >> vd;
     e->cw[p] = (((int)(i.pic_x + i.pic_width) + hd) >> hd) - e->cx0[p];
     e->ch[p] = (((int)(i.pic_y + i.pic_height) + vd) >> vd) - e->cy0[p];
   }
-  e->nfrags = off;
-  // coded order: super blocks of 4x4 fragments in raster order, the fragments of each along the Hilbert curve (spec 2.4)
-  static const int kHil[16][2] = {{0, 0}, {0, 1}, {1, 1}, {1, 0}, {2, 0}, {3, 0}, {3, 1}, {2, 1},
-                                  {2, 2}, {3, 2}, {3, 3}, {2, 3}, {1, 3}, {1, 2}, {0, 2}, {0, 3}};   // (row, column)
-  e->coded_order.reserve(e->nfrags);
-  for (int p = 0; p < 3; p++)
-    for (int sy = 0; sy < e->nv[p]; sy += 4)
-      for (int sx = 0; sx < e->nh[p]; sx += 4) {
-        const size_t at = e->coded_order.size();
-        for (int k = 0; k < 16; k++) {
-          const int fy = sy + kHil[k][0], fx = sx + kHil[k][1];
-          if (fy < e->nv[p] && fx < e->nh[p]) e->coded_order.push_back(e->froff[p] + fy * e->nh[p] + fx);
-        }
-        e->sb_len.push_back((int32_t)(e->coded_order.size() - at));
-      }
-  // macro blocks in coded order: luma super blocks in raster order, in each the four along the same curve (spec 2.4)
-  e->nmbx = yh >> 1;
-  e->nmbs = e->nmbx * (yv >> 1);
-  for (int sy = 0; sy < yv; sy += 4)
-    for (int sx = 0; sx < yh; sx += 4)
-      for (int k = 0; k < 4; k++) {
-        const int y = sy + 2 * (k == 1 || k == 2), x = sx + 2 * (k >= 2);
-        if (y < yv && x < yh) e->mb_order.push_back((y >> 1) * e->nmbx + (x >> 1));
-      }
+  e->nmbx = e->nh[0] >> 1;
+  e->nmbs = (int)e->mbs.size();
   e->nchunks = (e->nfrags + kEncChunk - 1) / kEncChunk;
   enc_setup_init(e->setup);
+  for (int qi = 0; qi < 64; qi++) {
+    uint16_t step[64];
+    compute_qmat(e->setup.qp, 1, 0, qi, step);
+    e->lambda[qi] = step[1];
+  }
   memset(&e->stats, 0, sizeof(e->stats));
   memset(&e->istats, 0, sizeof(e->istats));
   memset(&e->mstats, 0, sizeof(e->mstats));
@@ -428,7 +356,7 @@ th_enc_ctx *th_encode_alloc(const th_info *info) { return th_encode_alloc_on(inf
 // frees whatever device state exists (also a partial one, after a failed enc_ensure_device) and forgets it
 static void enc_free_device(th_enc_ctx *e) {
   if (e->device < 0) return;
-  EncDeviceGuard g(e->device);
+  DeviceGuard g(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->dec) th_decode_free(e->dec);
   e->dec = nullptr;
@@ -507,7 +435,7 @@ static int enc_ensure_device(th_enc_ctx *e) {
 
 // the allocations and uploads of enc_ensure_device, on e->device
 static int enc_alloc_device(th_enc_ctx *e) {
-  EncDeviceGuard g(e->device);
+  DeviceGuard g(e->device);
   ENC_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   ENC_TRY(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
   ENC_TRY(hipEventCreateWithFlags(&e->ev_read, hipEventDisableTiming));
@@ -536,7 +464,7 @@ static int enc_alloc_device(th_enc_ctx *e) {
   std::vector<uint16_t> dq(64 * 3 * 64);
   for (int qi = 0; qi < 64; qi++)
     for (int p = 0; p < 3; p++)
-      for (int z = 0; z < 64; z++) dq[(qi * 3 + p) * 64 + z] = enc_qstep(e->setup, p, qi, z);
+      compute_qmat(e->setup.qp, 0, p, qi, &dq[(qi * 3 + p) * 64]);
   ENC_TRY(hipMemcpy(e->d_order, e->coded_order.data(), n * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_dequant, dq.data(), dq.size() * 2, hipMemcpyHostToDevice));
   if (!e->inter) return 0;   // (nothing more exists with inter frames off)
@@ -549,9 +477,7 @@ static int enc_alloc_device(th_enc_ctx *e) {
   ENC_TRY(hipHostMalloc((void **)&e->h_cmap, n, hipHostMallocDefault));
   std::vector<uint16_t> dqi(64 * 6 * 64);
   for (int qi = 0; qi < 64; qi++)
-    for (int t = 0; t < 6; t++)
-      for (int z = 0; z < 64; z++)
-        dqi[(qi * 6 + t) * 64 + z] = t < 3 ? enc_qstep(e->setup, t, qi, z) : enc_qstep_inter(e->setup, qi, z);
+    for (int t = 0; t < 6; t++) compute_qmat(e->setup.qp, t / 3, t % 3, qi, &dqi[(qi * 6 + t) * 64]);   // intra, inter of each plane
   ENC_TRY(hipMemcpy(e->d_dqi, dqi.data(), dqi.size() * 2, hipMemcpyHostToDevice));
   return 0;
 }
@@ -606,7 +532,7 @@ static int enc_bqi_prepare(th_enc_ctx *e, BqiSel &sel) {
     std::vector<uint8_t> bits(16 * 4 * 32);   // [table][Huffman group - 1][token]: code length + extra bits
     for (int t = 0; t < 16; t++)
       for (int hg = 1; hg < 5; hg++)
-        for (int tok = 0; tok < 32; tok++) bits[(t * 4 + hg - 1) * 32 + tok] = (uint8_t)(e->setup.len[16 * hg + t][tok] + kExtraBits[tok]);
+        for (int tok = 0; tok < 32; tok++) bits[(t * 4 + hg - 1) * 32 + tok] = (uint8_t)(e->setup.len[16 * hg + t][tok] + kTokExtraBits[tok]);
     ENC_TRY(hipMemcpy(e->d_bqbits, bits.data(), bits.size(), hipMemcpyHostToDevice));
   }
   const int ft = e->frame_key ? 0 : 1;
@@ -635,7 +561,7 @@ static int enc_pack_alloc(th_enc_ctx *e) {
   ENC_TRY(hipHostMalloc((void **)&e->h_prec, sizeof(PackRec), hipHostMallocDefault));
   std::vector<uint32_t> cl(80 * 32);   // code length | extra bits << 8
   for (int h = 0; h < 80; h++)
-    for (int tok = 0; tok < 32; tok++) cl[h * 32 + tok] = (uint32_t)e->setup.len[h][tok] | (uint32_t)kExtraBits[tok] << 8;
+    for (int tok = 0; tok < 32; tok++) cl[h * 32 + tok] = (uint32_t)e->setup.len[h][tok] | (uint32_t)kTokExtraBits[tok] << 8;
   ENC_TRY(hipMemcpy(e->d_pcodes, e->setup.code, 80 * 32 * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_pcl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMalloc((void **)&e->d_pk, cap));
@@ -711,7 +637,7 @@ extern "C++" template <class Me, class Fq, class FqBqi, class Dc, class Word, cl
 static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, Me k_me, Fq k_fq, FqBqi k_fq_bqi, Dc k_dc,
                             int classes, Word *d_mb, const EncRef &R, const Gold &...gold) {
   const int64_t n = e->nfrags;
-  const int lambda = enc_qstep_inter(e->setup, e->frame_qi, 1);
+  const int lambda = e->lambda[e->frame_qi];
   const dim3 gfq((unsigned)((4 * n + 255) / 256)), gch((unsigned)e->nchunks), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
@@ -744,8 +670,6 @@ static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel)
   return enc_launch_inter(e, g, sel, k_enc_me_all, k_enc_inter_fq_all, k_enc_inter_fq_all_bqi, k_enc_inter_dc3, 3, e->d_mb4, R, G);
 }
 
-static double enc_now();
-
 // ---- bitrate mode -----------------------------------------------------------------------------------------------------------
 // the probe's buffers, at the first frame in bitrate mode
 static int enc_rate_alloc(th_enc_ctx *e) {
@@ -770,15 +694,14 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   // oc_enc_quantize's table entries of every (table, z, q), as k_enc_intra_fq forms them: (step | m << 16, l)
   std::vector<uint2> tab(6 * 64 * 64);
   for (int t = 0; t < 6; t++)
-    for (int z = 0; z < 64; z++)
-      for (int q = 0; q < 64; q++) {
-        // (rate_quant reads the second word as l alone: no zig-zag index in it)
-        tab[(t * 64 + z) * 64 + q] = enc_quant_entry(t < 3 ? enc_qstep(e->setup, t, q, z) : enc_qstep_inter(e->setup, q, z), 0);
-      }
-  int lam[64];
-  for (int q = 0; q < 64; q++) lam[q] = enc_qstep_inter(e->setup, q, 1);
+    for (int q = 0; q < 64; q++) {
+      uint16_t step[64];
+      compute_qmat(e->setup.qp, t / 3, t % 3, q, step);
+      // (rate_quant reads the second word as l alone: no zig-zag index in it)
+      for (int z = 0; z < 64; z++) tab[(t * 64 + z) * 64 + q] = enc_quant_entry(step[z], 0);
+    }
   ENC_TRY(hipMemcpy(e->d_rtab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
-  ENC_TRY(hipMemcpy(e->d_rlam, lam, sizeof(lam), hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(e->d_rlam, e->lambda, sizeof(e->lambda), hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_rlens, e->setup.len, 80 * 32, hipMemcpyHostToDevice));
   e->rate_dev = true;
   return 0;
@@ -849,7 +772,7 @@ static void enc_rate_caps(th_enc_ctx *e) {
 
 // the controller's choice for frame f (theoraenc_hip.h, "Bitrate mode"): returns the qi, or -1 to drop the frame
 static int enc_rate_choose(th_enc_ctx *e, bool key, int64_t f, int64_t keypos) {
-  const double t0 = enc_now();
+  const double t0 = thip_now();
   if (!e->rate_started) {
     e->rD = e->rate_buf ? e->rate_buf : rate_clamp(e->inter ? e->kf_interval : 1, 12, 256);
     enc_rate_targets(e);
@@ -902,7 +825,7 @@ static int enc_rate_choose(th_enc_ctx *e, bool key, int64_t f, int64_t keypos) {
   r.fullness_after = e->rF;
   r.corr[0] = e->rc_corr[0];
   r.corr[1] = e->rc_corr[1];
-  r.control_ms = (enc_now() - t0) * 1e3;
+  r.control_ms = (thip_now() - t0) * 1e3;
   return drop ? -1 : qi;
 }
 
@@ -947,7 +870,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     g.ph[p] = e->ch[p];
     g.nh[p] = e->nh[p];
     g.nv[p] = e->nv[p];
-    g.froff[p] = e->froff[p];
+    g.froff[p] = e->fro[p];
   }
   const int64_t n = e->nfrags;
   if (!e->rate) e->frame_qi = e->qi;   // (bitrate mode: the controller's choice, below)
@@ -994,7 +917,7 @@ int th_encode_ycbcr_in(th_enc_ctx *e, th_ycbcr_buffer ycbcr) {
   const int kind = enc_buffer_kind(e, ycbcr);
   if (kind < 0) return TH_EINVAL;
   if (enc_ensure_device(e)) return TH_EFAULT;
-  EncDeviceGuard g(e->device);
+  DeviceGuard g(e->device);
   // the previous frame's upload is complete (its packet is out), so the staging buffer is free
   const uint8_t *src[3];
   int64_t stride[3];
@@ -1015,7 +938,7 @@ static int enc_ycbcr_in_device(th_enc_ctx *e, const thip_enc_device_in *a) {
   const int kind = enc_buffer_kind(e, a->planes);
   if (kind < 0) return TH_EINVAL;
   if (enc_ensure_device(e)) return TH_EFAULT;
-  EncDeviceGuard g(e->device);
+  DeviceGuard g(e->device);
   const uint8_t *src[3];
   int64_t stride[3];
   for (int p = 0; p < 3; p++) {
@@ -1041,18 +964,12 @@ static void enc_put_eob_run(std::vector<uint32_t> &m, uint32_t run) {   // token
   m.push_back(t | x << 5);
 }
 
-static double enc_now() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
 // spec 7.3-7.5 of an inter frame: coded flags, macro-block modes, vectors (from h_cmap, h_mb)
 static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
   // 7.3: super blocks partially coded; of the others, fully coded; the block flags of the partial ones
   std::vector<uint8_t> sbp, sbf, blk;
-  size_t at = 0;
-  for (int32_t len : e->sb_len) {
+  for (int sb = 0; sb < e->nsbs; sb++) {
+    const int32_t at = e->sb_start[sb], len = e->sb_start[sb + 1] - at;
     int nc = 0;
     for (int32_t k = 0; k < len; k++) nc += e->h_cmap[e->coded_order[at + k]] != 0;
     const bool partial = nc > 0 && nc < len;
@@ -1060,7 +977,6 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
     if (!partial) sbf.push_back(nc == len);
     else
       for (int32_t k = 0; k < len; k++) blk.push_back(e->h_cmap[e->coded_order[at + k]] != 0);
-    at += (size_t)len;
   }
   enc_put_runs(bw, sbp, true);
   enc_put_runs(bw, sbf, true);
@@ -1071,19 +987,18 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
   std::vector<uint8_t> modes;
   std::vector<int> mvs;   // the vectors written: x, y
   int lx = 0, ly = 0, l2x = 0, l2y = 0;
-  const int nh = e->nh[0];
-  for (int32_t mb : e->mb_order) {
-    const int mx = mb % e->nmbx, my = mb / e->nmbx, f0 = 2 * my * nh + 2 * mx;
-    if (!e->h_cmap[f0] && !e->h_cmap[f0 + 1] && !e->h_cmap[f0 + nh] && !e->h_cmap[f0 + nh + 1]) {
-      e->istats.modes[kModeNomv]++;
-      e->mstats.modes[kModeNomv]++;
+  for (const MacroBlock &m : e->mbs) {
+    const int32_t mb = m.raster;
+    if (!e->h_cmap[m.luma[0]] && !e->h_cmap[m.luma[1]] && !e->h_cmap[m.luma[2]] && !e->h_cmap[m.luma[3]]) {
+      e->istats.modes[MODE_INTER_NOMV]++;
+      e->mstats.modes[MODE_INTER_NOMV]++;
       continue;
     }
     const uint32_t w = e->modes ? e->h_mb4[mb].x : e->h_mb[mb];
     const int pix = (int)(w & 0xFF);
-    int mode = pix == kEncPixIntra ? kModeIntra : pix == kEncPixMv ? kModeMv : pix == kEncPixGoldNomv ? kModeGoldNomv
-             : pix == kEncPixGoldMv ? kModeGoldMv : pix == kEncPixFour ? kModeMvFour : kModeNomv;
-    if (mode == kModeMvFour) {
+    int mode = pix == kEncPixIntra ? MODE_INTRA : pix == kEncPixMv ? MODE_INTER_MV : pix == kEncPixGoldNomv ? MODE_GOLDEN_NOMV
+             : pix == kEncPixGoldMv ? MODE_GOLDEN_MV : pix == kEncPixFour ? MODE_INTER_MV_FOUR : MODE_INTER_NOMV;
+    if (mode == MODE_INTER_MV_FOUR) {
       const uint32_t bw4[2] = {e->h_mb4[mb].y, e->h_mb4[mb].z};
       for (int k = 0; k < 4; k++) {
         const uint32_t v = bw4[k >> 1] >> (16 * (k & 1));
@@ -1094,15 +1009,15 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
       l2y = ly;
       lx = mvs[mvs.size() - 2];
       ly = mvs[mvs.size() - 1];
-    } else if (mode == kModeGoldMv) {
+    } else if (mode == MODE_GOLDEN_MV) {
       mvs.push_back((int)(int8_t)(w >> 8));
       mvs.push_back((int)(int8_t)(w >> 16));
-    } else if (mode == kModeMv) {
+    } else if (mode == MODE_INTER_MV) {
       const int vx = (int)(int8_t)(w >> 8), vy = (int)(int8_t)(w >> 16);
       if (vx == lx && vy == ly) {
-        mode = kModeMvLast;
+        mode = MODE_INTER_MV_LAST;
       } else if (vx == l2x && vy == l2y) {
-        mode = kModeMvLast2;
+        mode = MODE_INTER_MV_LAST2;
         l2x = lx;
         l2y = ly;
         lx = vx;
@@ -1154,7 +1069,7 @@ static void enc_put_inter_header(th_enc_ctx *e, BitW &bw) {
   e->istats.mode_scheme = scheme;
   // 7.5: the cheaper vector scheme (ties: VLC)
   int64_t vlc = 0;
-  for (int v : mvs) vlc += enc_mv_vlc_bits(v);
+  for (int v : mvs) vlc += kMvVlc.nbits[v + 31];
   const int mvsch = vlc > 6 * (int64_t)mvs.size() ? 1 : 0;
   bw.put((uint32_t)mvsch, 1);
   for (int v : mvs) enc_put_mv(bw, v, mvsch);
@@ -1182,7 +1097,7 @@ static void enc_put_qiis(th_enc_ctx *e, BitW &bw) {
   for (int k = 0; k < e->nfrags; k++) {
     const int fi = e->coded_order[k];
     if (!e->frame_key && !e->h_cmap[fi]) continue;
-    const int q = e->fnqis > 1 ? e->h_qii[k] : 0, p = fi >= e->froff[2] ? 2 : fi >= e->froff[1] ? 1 : 0;
+    const int q = e->fnqis > 1 ? e->h_qii[k] : 0, p = fi >= e->fro[2] ? 2 : fi >= e->fro[1] ? 1 : 0;
     s.blocks[q][p]++;
     f1.push_back(q > 0);
     if (q > 0) f2.push_back(q > 1);
@@ -1202,8 +1117,8 @@ static bool enc_put_frame_header(th_enc_ctx *e, BitW &bw) {
   e->istats.mode_scheme = e->istats.mv_scheme = -1;
   if (e->frame_key) {
     e->istats.key = 1;
-    e->istats.modes[kModeIntra] = e->nmbs;
-    e->mstats.modes[kModeIntra] = e->nmbs;
+    e->istats.modes[MODE_INTRA] = e->nmbs;
+    e->mstats.modes[MODE_INTRA] = e->nmbs;
     for (int p = 0; p < 3; p++) e->istats.coded[p] = e->nh[p] * e->nv[p];
     bw.put(0, 1);                          // data packet
     bw.put(0, 1);                          // intra frame
@@ -1213,7 +1128,7 @@ static bool enc_put_frame_header(th_enc_ctx *e, BitW &bw) {
     return true;
   }
   for (int p = 0; p < 3; p++)
-    for (int f = e->froff[p]; f < e->froff[p] + e->nh[p] * e->nv[p]; f++) e->istats.coded[p] += e->h_cmap[f] != 0;
+    for (int f = e->fro[p]; f < e->fro[p] + e->nh[p] * e->nv[p]; f++) e->istats.coded[p] += e->h_cmap[f] != 0;
   if (!e->istats.coded[0] && !e->istats.coded[1] && !e->istats.coded[2]) return false;
   bw.put(0, 1);                          // data packet
   bw.put(1, 1);                          // inter frame
@@ -1262,7 +1177,7 @@ static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
     ENC_TRY(hipMemcpyAsync(e->h_tok, e->d_out, total * 4, hipMemcpyDeviceToHost, e->stream));
     ENC_TRY(hipStreamSynchronize(e->stream));
   }
-  const double t0 = enc_now();
+  const double t0 = thip_now();
   // stream order: index z, then plane p; merged lists in the same order, counted per (z, p)
   std::vector<uint32_t> &m = e->merged;
   m.clear();
@@ -1325,7 +1240,7 @@ static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
   BitW bw{&e->pkt};
   if (!enc_put_frame_header(e, bw)) {
     enc_empty_packet(e);
-    e->host_ms = (enc_now() - t0) * 1e3;
+    e->host_ms = (thip_now() - t0) * 1e3;
     return 0;
   }
   const int64_t hbits = (int64_t)e->pkt.size() * 8 + bw.n;
@@ -1341,7 +1256,7 @@ static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
       for (uint32_t k = 0; k < mlen[z][p]; k++) {
         const uint32_t w = m[at++], tok = w & 31;
         bw.put(e->setup.code[h][tok], e->setup.len[h][tok]);
-        bw.put(w >> 5, kExtraBits[tok]);
+        bw.put(w >> 5, kTokExtraBits[tok]);
       }
     }
   }
@@ -1349,7 +1264,7 @@ static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
   e->pstats.token_bits = (int64_t)e->pkt.size() * 8 + bw.n - hbits;
   e->pstats.phase = (int32_t)(hbits & 7);
   bw.flush();
-  e->host_ms = (enc_now() - t0) * 1e3;
+  e->host_ms = (thip_now() - t0) * 1e3;
   e->pkt_data = e->pkt.data();
   e->pkt_size = e->pkt.size();
   enc_packet_done(e, total, m.size(), hti, overflow);
@@ -1361,20 +1276,20 @@ static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
 // header's whole bytes in the pinned packet buffer; the header's last partial byte is ORed into the first of them.  The host touches
 // the header's bytes only.  A frame whose bits exceed the device buffer goes to the host packer.
 static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
-  const double t0 = enc_now();
+  const double t0 = thip_now();
   double waited = 0;
   e->pkt.clear();
   BitW bw{&e->pkt};
   if (!enc_put_frame_header(e, bw)) {
     enc_empty_packet(e);
-    e->host_ms = (enc_now() - t0) * 1e3;
+    e->host_ms = (thip_now() - t0) * 1e3;
     return 0;
   }
   const size_t hb = e->pkt.size();
   const int phase = bw.n;
-  double tw = enc_now();
+  double tw = thip_now();
   ENC_TRY(hipEventSynchronize(e->ev_k1));
-  waited += enc_now() - tw;
+  waited += thip_now() - tw;
   float ms = 0;
   const double pack1 = hipEventElapsedTime(&ms, e->ev_k0, e->ev_k1) == hipSuccess ? ms : 0.0;
   const PackRec rec = *e->h_prec;
@@ -1406,9 +1321,9 @@ static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
   ENC_TRY(hipMemcpyAsync(e->h_pk + hb, e->d_pk, (size_t)need, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_q1, e->stream));
   memcpy(e->h_pk, e->pkt.data(), hb);
-  tw = enc_now();
+  tw = thip_now();
   ENC_TRY(hipEventSynchronize(e->ev_q1));
-  waited += enc_now() - tw;
+  waited += thip_now() - tw;
   if (phase) e->h_pk[hb] |= (uint8_t)(bw.acc << (8 - phase));
   const double pack2 = hipEventElapsedTime(&ms, e->ev_q0, e->ev_q1) == hipSuccess ? ms : 0.0;
   e->pkt_data = e->h_pk;
@@ -1419,13 +1334,13 @@ static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
   e->pstats.phase = phase;
   e->pstats.pack_ms = pack1 + pack2;
   enc_packet_done(e, total, rec.merged, rec.hti, overflow);
-  e->host_ms = (enc_now() - t0 - waited) * 1e3;   // (the host's own work: the waits for the packetiser are in pack_ms)
+  e->host_ms = (thip_now() - t0 - waited) * 1e3;   // (the host's own work: the waits for the packetiser are in pack_ms)
   return overflow ? TH_EFAULT : 0;
 }
 
 // the packet of the frame queued on the device: the wait for its list lengths, then one of the two packers
 static int enc_finish_frame(th_enc_ctx *e) {
-  EncDeviceGuard g(e->device);
+  DeviceGuard g(e->device);
   ENC_TRY(hipEventSynchronize(e->ev_done));
   float ms = 0;
   if (hipEventElapsedTime(&ms, e->ev_t0, e->ev_done) == hipSuccess) e->device_ms = ms;
@@ -1594,26 +1509,29 @@ static void enc_header(const th_enc_ctx *e, int which, const th_comment *tc, std
     }
   } else {   // spec 6.4
     const EncSetup &s = e->setup;
+    const QuantParams &q = s.qp;
     int nb = 0;
-    for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(s.lflims[qi]));
+    for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(q.lflims[qi]));
     bw.put((uint32_t)nb, 3);
-    for (int qi = 0; qi < 64; qi++) bw.put(s.lflims[qi], nb);
-    for (const uint16_t *sc : {s.acscale, s.dcscale}) {
+    for (int qi = 0; qi < 64; qi++) bw.put(q.lflims[qi], nb);
+    for (const uint16_t *sc : {q.acscale, q.dcscale}) {
       nb = 1;
       for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(sc[qi]));
       bw.put((uint32_t)nb - 1, 4);
       for (int qi = 0; qi < 64; qi++) bw.put(sc[qi], nb);
     }
-    bw.put(3 - 1, 9);   // three base matrices
-    for (int b = 0; b < 3; b++)
-      for (int c = 0; c < 64; c++) bw.put(s.bms[b][c], 8);
+    bw.put((uint32_t)q.nbms - 1, 9);
+    for (uint8_t b : q.bms) bw.put(b, 8);
+    const int bmbits = ilog((uint32_t)q.nbms - 1);
     for (int qti = 0; qti < 2; qti++)
       for (int pli = 0; pli < 3; pli++) {
-        if (qti > 0 || pli > 0) bw.put(1, 1);   // NEWQR
-        const uint32_t bmi = qti ? 2 : pli ? 1 : 0;
-        bw.put(bmi, ilog(3 - 1));
-        bw.put(63 - 1, ilog(62));               // one range of size 63 ...
-        bw.put(bmi, ilog(3 - 1));               // ... ending in the same matrix
+        if (qti > 0 || pli > 0) bw.put(1, 1);   // NEWQR: every (qti, pli) states its ranges
+        bw.put((uint32_t)q.qrbmis[qti][pli][0], bmbits);
+        for (int qri = 0, qi = 0; qri < q.nqrs[qti][pli]; qri++) {
+          bw.put((uint32_t)q.qrsizes[qti][pli][qri] - 1, ilog((uint32_t)(62 - qi)));
+          qi += q.qrsizes[qti][pli][qri];
+          bw.put((uint32_t)q.qrbmis[qti][pli][qri + 1], bmbits);
+        }
       }
     for (int64_t k = 0; k < s.tree_bits; k++) bw.put((s.trees[k >> 3] >> (7 - (k & 7))) & 1, 1);
   }

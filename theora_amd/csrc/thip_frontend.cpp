@@ -10,6 +10,10 @@
 // (plane, zig-zag index) list before expanding per fragment (decode.c:993-1201), because
 // it is what makes a single pass over the packet possible.
 //
+// The tables of the specification, the frame's geometry (th_dec_ctx is a FrameGeometry), QuantParams / compute_qmat and the
+// run-length and vector codes are thip_bitstream.h's, shared with the encoder (thip_encode.hip); the readers of them, and the
+// token tables built for the token loop (kZigZagDump, TokFast, TokTable), are here.
+//
 // Exports the th_decode_* API declared in include/theoradec_hip.h.
 #include <stdint.h>
 #include <stdio.h>
@@ -28,6 +32,7 @@
 
 #include "../../include/theora_hip.h"
 #include "../../include/theoradec_hip.h"
+#include "thip_bitstream.h"
 #include "thip_ctx.h"
 // The one backend entry point the front end reaches only on request (TH_DECCTL_THIP_PICTURE_OUT): referenced weakly, so that this
 // translation unit still links on its own against a backend that provides just the decoding slots (the front end's native test
@@ -36,6 +41,8 @@
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
+
+using namespace thip;
 
 namespace {
 
@@ -86,21 +93,7 @@ struct BitReader {
   bool overrun() const { return pos > nbits; }
 };
 
-inline int ilog(uint32_t v) {   // number of bits needed to store v (spec 1.4 ilog)
-  int n = 0;
-  while (v) {
-    n++;
-    v >>= 1;
-  }
-  return n;
-}
-
-// zig-zag index -> natural position (spec Figure "zig-zag order")
-const uint8_t kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// the same for positions 0..127: everything past 63 goes to entry 64 (a dump slot)
+// kZigZag for positions 0..127: everything past 63 goes to entry 64 (a dump slot)
 struct ZigZagDump {
   uint8_t t[128];
   ZigZagDump() {
@@ -110,21 +103,9 @@ struct ZigZagDump {
 };
 const ZigZagDump kZigZagDump;
 
-// (row, col) of the k-th block of a super block in coded (Hilbert) order (spec Figure 2.4)
-const uint8_t kHilbert[16][2] = {{0, 0}, {0, 1}, {1, 1}, {1, 0}, {2, 0}, {3, 0}, {3, 1}, {2, 1},
-                                 {2, 2}, {3, 2}, {3, 3}, {2, 3}, {1, 3}, {1, 2}, {0, 2}, {0, 3}};
-// macro blocks of a super block in coded order: (row, col) in units of macro blocks (spec Figure 2.5)
-const uint8_t kMbOrder[4][2] = {{0, 0}, {1, 0}, {1, 1}, {0, 1}};
-
-// Table 7.19: mode alphabets of schemes 1..6
-const uint8_t kModeAlphabets[6][8] = {{3, 4, 2, 0, 1, 5, 6, 7}, {3, 4, 0, 2, 1, 5, 6, 7}, {3, 2, 4, 0, 1, 5, 6, 7},
-                                      {3, 2, 0, 4, 1, 5, 6, 7}, {0, 3, 4, 2, 1, 5, 6, 7}, {0, 5, 3, 4, 2, 1, 6, 7}};
 // reference frame of each coding mode (Table 7.46): 0 intra/self, 1 previous, 2 golden -> THIP_FRAME_*
 const uint8_t kModeRefi[8] = {THIP_FRAME_PREV, THIP_FRAME_SELF, THIP_FRAME_PREV, THIP_FRAME_PREV,
                               THIP_FRAME_PREV, THIP_FRAME_GOLD, THIP_FRAME_GOLD, THIP_FRAME_PREV};
-enum { MODE_INTER_NOMV = 0, MODE_INTRA = 1, MODE_INTER_MV = 2, MODE_INTER_MV_LAST = 3, MODE_INTER_MV_LAST2 = 4,
-       MODE_GOLDEN_NOMV = 5, MODE_GOLDEN_MV = 6, MODE_INTER_MV_FOUR = 7 };
-
 constexpr int kHuffLutBits = 9;
 struct HuffTree {
   // node i: child[i][b] >= 0 is another node, < 0 is the leaf -(token+1)
@@ -133,16 +114,6 @@ struct HuffTree {
   int root_leaf;   // a single-leaf tree: token+1, else 0
   // next kHuffLutBits bits -> (code length << 8 | token), or 0x8000 | node to continue from
   uint64_t lut[1 << kHuffLutBits];
-};
-
-struct QuantParams {
-  uint8_t lflims[64];
-  uint16_t acscale[64], dcscale[64];
-  int nbms;
-  std::vector<uint8_t> bms;   // nbms*64
-  int nqrs[2][3];
-  int qrsizes[2][3][64];
-  int qrbmis[2][3][65];
 };
 
 struct Tok {
@@ -159,32 +130,12 @@ struct th_setup_info {
   QuantParams qp;
 };
 
-struct MacroBlock {
-  int32_t luma[4];     // fragment indices in raster order (A,B,C,D), -1 outside the frame
-  int32_t chroma[2][4];
-  int nchroma;         // chroma blocks per plane in this macro block
-};
-
 // THIP_FE_PROF=1: wall time per section of th_decode_packetin, printed by th_decode_free
 enum { FE_FLAGS, FE_MODES, FE_QI, FE_TOKENS, FE_DC, FE_EXPAND, FE_FLUSH, FE_OUT, FE_LPACK, FE_LMETA, FE_LBEGIN, FE_LFINISH, FE_NSEC };
 static const char *const kFeNames[FE_NSEC] = {"header+coded flags", "modes+MVs", "block qi", "DCT tokens", "DC unpredict",
                                               "expand+dequant+stage", "flush (H2D, launch, sync)", "ycbcr_out (D2H)",
                                               "lists: tokens packed", "lists: fragment words", "lists: begin (stage, launch)",
                                               "lists: finish (launch)"};
-static inline void cpu_relax() {   // a spinning thread's pause (the x86 hint where there is one)
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#elif defined(__aarch64__)
-  asm volatile("yield" ::: "memory");
-#else
-  std::this_thread::yield();
-#endif
-}
-static inline double fe_now() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
 // decoder contexts alive in the process (the token-list path is chosen by default while there are few)
 static std::atomic<int> g_fe_contexts{0};
 constexpr int kFeListsAutoContexts = 4;
@@ -192,10 +143,10 @@ struct FeProf {
   bool on, warmed;   // (the first frames carry one-time costs -- streams, allocations -- and are dropped from the sums)
   double acc[FE_NSEC], t;
   long frames, tokens;
-  void start() { if (on) t = fe_now(); }
+  void start() { if (on) t = thip_now(); }
   void lap(int s) {
     if (!on) return;
-    const double n = fe_now();
+    const double n = thip_now();
     acc[s] += n - t;
     t = n;
   }
@@ -245,17 +196,10 @@ static int fe_prefetch(th_dec_ctx *d, const ogg_packet *op);
 }
 
 // (thip_ctx_head: th_info and the granule bias first, as in th_enc_ctx, so that th_granule_frame / _time take either)
-struct th_dec_ctx : thip_ctx_head {
+struct th_dec_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bitstream.h)
   FeProf prof;
   th_setup_info setup;
   thip_state *hip;
-  int nh[3], nv[3], fro[3], nfrags_pl[3];
-  int nfrags;
-  int hdec, vdec;
-  std::vector<int32_t> coded_order;      // all fragments, coded order, planes concatenated
-  std::vector<int32_t> sb_start;         // per super block (all planes): first index in coded_order, +1 sentinel
-  int nsbs;
-  std::vector<MacroBlock> mbs;           // macro blocks in coded order (only those inside the frame)
   std::vector<uint16_t> dequant;         // [qi][pli][qti][zzi]
   // per frame
   std::vector<uint8_t> coded, refi, qii, mbmode_of_frag;
@@ -443,9 +387,6 @@ int parse_huff_tree(BitReader &br, HuffTree &t, int depth, int *nleaves) {   // 
   return me;
 }
 
-// extra bits that follow each DCT token (Tables 7.33 / 7.38; kTokDef below has the rest)
-const uint8_t kTokExtraBits[32] = {0, 0, 0, 2, 3, 4, 12, 3, 6, 0, 0, 0, 0, 1, 1, 1,
-                                   1, 2, 3, 4, 5, 6, 10, 1, 1, 1, 1, 1, 3, 4, 2, 3};
 constexpr uint64_t kLutMore = 1ull << 63;
 // lut entry: (code length + extra bits) | extra bits << 8 | code length << 16 | token << 24 | first entry of the token in the
 // expansion table (TokTable::tab) << 32, so that how far the bit window moves is known one load after the window -- in the entry's
@@ -541,45 +482,24 @@ int parse_setup(BitReader &br, th_setup_info *s) {   // spec 6.4
   return br.overrun() ? TH_EBADHEADER : 0;
 }
 
-// spec 6.4.3 "Computing a Quantization Matrix"; output in ZIG-ZAG order
-void compute_qmat(const QuantParams &q, int qti, int pli, int qi, uint16_t out_zz[64]) {
-  int qri = 0, qistart = 0;
-  while (qri < q.nqrs[qti][pli] - 1 && qi > qistart + q.qrsizes[qti][pli][qri]) {
-    qistart += q.qrsizes[qti][pli][qri];
-    qri++;
-  }
-  const int size = q.qrsizes[qti][pli][qri];
-  const int qiend = qistart + size;
-  const uint8_t *bmi = &q.bms[(size_t)q.qrbmis[qti][pli][qri] * 64];
-  const uint8_t *bmj = &q.bms[(size_t)q.qrbmis[qti][pli][qri + 1] * 64];
-  for (int zzi = 0; zzi < 64; zzi++) {
-    const int ci = kZigZag[zzi];
-    const int bm = (2 * (qiend - qi) * bmi[ci] + 2 * (qi - qistart) * bmj[ci] + size) / (2 * size);
-    const int qmin = ci == 0 ? (qti == 0 ? 16 : 32) : (qti == 0 ? 8 : 16);
-    const int qscale = ci == 0 ? q.dcscale[qi] : q.acscale[qi];
-    int v = (qscale * bm / 100) * 4;
-    if (v > 4096) v = 4096;
-    if (v < qmin) v = qmin;
-    out_zz[zzi] = (uint16_t)v;
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // run-length coded bit strings (spec 7.2)
 // ---------------------------------------------------------------------------------------
-void read_long_run_bits(BitReader &br, size_t nbits, std::vector<uint8_t> &out) {   // 7.2.1
+// 7.2.1 (LNG: Table 7.7, a new bit after a run of the longest length) and 7.2.2 (Table 7.11, the bit always flips)
+template <bool LNG>
+void read_run_bits(BitReader &br, size_t nbits, std::vector<uint8_t> &out) {
+  constexpr const RunCode &rc = LNG ? kLongRuns : kShortRuns;
   out.assign(nbits, 0);
   size_t len = 0;
   if (!nbits) return;
   uint32_t bit = br.bit();
   for (;;) {
-    // Table 7.7: the run-length class is the number of leading ones (0..6) of the next six bits
-    static const uint8_t kStart[7] = {1, 2, 4, 6, 10, 18, 34}, kBits[7] = {0, 1, 1, 2, 3, 4, 12};
-    int ones = __builtin_clz(~(br.peek(6) << 26));
-    if (ones > 6) ones = 6;
-    br.skip(ones < 6 ? ones + 1 : 6);
-    size_t rlen = (size_t)kStart[ones] + br.read(kBits[ones]);
-    const bool full = rlen == 4129;
+    // the run-length class is the number of leading ones (0..last) of the next `last` bits
+    int ones = __builtin_clz(~(br.peek(rc.last) << (32 - rc.last)));
+    if (ones > rc.last) ones = rc.last;
+    br.skip(ones < rc.last ? ones + 1 : rc.last);
+    size_t rlen = (size_t)rc.cls[ones].start + br.read(rc.cls[ones].bits);
+    const bool full = LNG && rlen == (size_t)rc.longest();
     if (rlen > nbits - len) rlen = nbits - len;   // invalid stream: clip
     memset(&out[len], (int)bit, rlen);
     len += rlen;
@@ -588,58 +508,9 @@ void read_long_run_bits(BitReader &br, size_t nbits, std::vector<uint8_t> &out) 
   }
 }
 
-void read_short_run_bits(BitReader &br, size_t nbits, std::vector<uint8_t> &out) {   // 7.2.2
-  out.assign(nbits, 0);
-  size_t len = 0;
-  if (!nbits) return;
-  uint32_t bit = br.bit();
-  for (;;) {
-    // Table 7.11: leading ones (0..5) of the next five bits
-    static const uint8_t kStart[6] = {1, 3, 5, 7, 11, 15}, kBits[6] = {1, 1, 1, 2, 2, 4};
-    int ones = __builtin_clz(~(br.peek(5) << 27));
-    if (ones > 5) ones = 5;
-    br.skip(ones < 5 ? ones + 1 : 5);
-    size_t rlen = (size_t)kStart[ones] + br.read(kBits[ones]);
-    if (rlen > nbits - len) rlen = nbits - len;
-    memset(&out[len], (int)bit, rlen);
-    len += rlen;
-    if (len >= nbits || br.overrun()) return;
-    bit = 1 - bit;
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // motion vectors (spec 7.5.1)
 // ---------------------------------------------------------------------------------------
-// Table 7.23 is a 3-bit prefix + magnitude bits + sign, eight bits at most: tabulated by the next eight bits (value, length)
-struct MvTable {
-  int8_t value[256];
-  uint8_t len[256];
-  MvTable() {
-    for (int w = 0; w < 256; w++) {
-      const int p = w >> 5;
-      int mag = 0, nb = 3, v;
-      switch (p) {
-        case 0: v = 0; break;
-        case 1: v = 1; break;
-        case 2: v = -1; break;
-        case 3: mag = 2; nb = 3; v = 2; break;
-        case 4: mag = 3; nb = 3; v = 2; break;
-        case 5: nb = 5; mag = 4 + ((w >> 3) & 3); v = 2; break;
-        case 6: nb = 6; mag = 8 + ((w >> 2) & 7); v = 2; break;
-        default: nb = 7; mag = 16 + ((w >> 1) & 15); v = 2; break;
-      }
-      if (p >= 3) {   // the sign follows the magnitude bits
-        const int sign = (w >> (7 - nb)) & 1;
-        v = sign ? -mag : mag;
-        nb++;
-      }
-      value[w] = (int8_t)v;
-      len[w] = (uint8_t)nb;
-    }
-  }
-};
-const MvTable kMvTab;
 inline int read_mv_component(BitReader &br, int mvmode) {
   if (mvmode) {   // five bits of magnitude, one of sign
     const uint32_t v = br.read(6);
@@ -647,8 +518,8 @@ inline int read_mv_component(BitReader &br, int mvmode) {
     return (v & 1u) ? -mag : mag;
   }
   const uint32_t w = br.peek(8);   // (bits past the packet's end read as zeros)
-  br.skip(kMvTab.len[w]);
-  return kMvTab.value[w];
+  br.skip(kMvVlc.len[w]);
+  return kMvVlc.value[w];
 }
 
 inline int round_div(int v, int shift) {   // round(v / 2^shift), ties away from zero (spec 7.5.2)
@@ -696,26 +567,25 @@ inline int read_token(BitReader &br, const HuffTree &t) {
 //   values (9-31):      |value| = vbase + ((rest >> vshift) & vmask), skip = sbase + (rest & smask),
 //                       adv = skip + 1, rest = the bits after the sign
 struct TokDef {
-  uint8_t ebits;     // extra bits in total
   uint8_t kind;      // 0 EOB run, 1 zero run, 2 value
   uint8_t sign;      // 0 positive, 1 negative, 2 read from the stream
   uint8_t vshift, sbase, smask;
   uint16_t vmask;
   int16_t vbase;
 };
-#define TD(eb, kind, sign, vshift, vmask, sbase, smask, vbase) {eb, kind, sign, vshift, sbase, smask, vmask, vbase}
+#define TD(kind, sign, vshift, vmask, sbase, smask, vbase) {kind, sign, vshift, sbase, smask, vmask, vbase}
 const TokDef kTokDef[32] = {
-    TD(0, 0, 0, 0, 0, 0, 0, 1),      TD(0, 0, 0, 0, 0, 0, 0, 2),      TD(0, 0, 0, 0, 0, 0, 0, 3),
-    TD(2, 0, 0, 0, 0x3, 0, 0, 4),    TD(3, 0, 0, 0, 0x7, 0, 0, 8),    TD(4, 0, 0, 0, 0xF, 0, 0, 16),
-    TD(12, 0, 0, 0, 0xFFF, 0, 0, 0), TD(3, 1, 0, 0, 0, 1, 0x07, 0),   TD(6, 1, 0, 0, 0, 1, 0x3F, 0),
-    TD(0, 2, 0, 0, 0, 0, 0, 1),      TD(0, 2, 1, 0, 0, 0, 0, 1),      TD(0, 2, 0, 0, 0, 0, 0, 2),
-    TD(0, 2, 1, 0, 0, 0, 0, 2),      TD(1, 2, 2, 0, 0, 0, 0, 3),      TD(1, 2, 2, 0, 0, 0, 0, 4),
-    TD(1, 2, 2, 0, 0, 0, 0, 5),      TD(1, 2, 2, 0, 0, 0, 0, 6),      TD(2, 2, 2, 0, 0x01, 0, 0, 7),
-    TD(3, 2, 2, 0, 0x03, 0, 0, 9),   TD(4, 2, 2, 0, 0x07, 0, 0, 13),  TD(5, 2, 2, 0, 0x0F, 0, 0, 21),
-    TD(6, 2, 2, 0, 0x1F, 0, 0, 37),  TD(10, 2, 2, 0, 0x1FF, 0, 0, 69), TD(1, 2, 2, 0, 0, 1, 0, 1),
-    TD(1, 2, 2, 0, 0, 2, 0, 1),      TD(1, 2, 2, 0, 0, 3, 0, 1),      TD(1, 2, 2, 0, 0, 4, 0, 1),
-    TD(1, 2, 2, 0, 0, 5, 0, 1),      TD(3, 2, 2, 0, 0, 6, 0x03, 1),   TD(4, 2, 2, 0, 0, 10, 0x07, 1),
-    TD(2, 2, 2, 0, 0x01, 1, 0, 2),   TD(3, 2, 2, 1, 0x01, 2, 0x01, 2)};
+    TD(0, 0, 0, 0, 0, 0, 1),      TD(0, 0, 0, 0, 0, 0, 2),      TD(0, 0, 0, 0, 0, 0, 3),
+    TD(0, 0, 0, 0x3, 0, 0, 4),    TD(0, 0, 0, 0x7, 0, 0, 8),    TD(0, 0, 0, 0xF, 0, 0, 16),
+    TD(0, 0, 0, 0xFFF, 0, 0, 0), TD(1, 0, 0, 0, 1, 0x07, 0),   TD(1, 0, 0, 0, 1, 0x3F, 0),
+    TD(2, 0, 0, 0, 0, 0, 1),      TD(2, 1, 0, 0, 0, 0, 1),      TD(2, 0, 0, 0, 0, 0, 2),
+    TD(2, 1, 0, 0, 0, 0, 2),      TD(2, 2, 0, 0, 0, 0, 3),      TD(2, 2, 0, 0, 0, 0, 4),
+    TD(2, 2, 0, 0, 0, 0, 5),      TD(2, 2, 0, 0, 0, 0, 6),      TD(2, 2, 0, 0x01, 0, 0, 7),
+    TD(2, 2, 0, 0x03, 0, 0, 9),   TD(2, 2, 0, 0x07, 0, 0, 13),  TD(2, 2, 0, 0x0F, 0, 0, 21),
+    TD(2, 2, 0, 0x1F, 0, 0, 37),  TD(2, 2, 0, 0x1FF, 0, 0, 69), TD(2, 2, 0, 0, 1, 0, 1),
+    TD(2, 2, 0, 0, 2, 0, 1),      TD(2, 2, 0, 0, 3, 0, 1),      TD(2, 2, 0, 0, 4, 0, 1),
+    TD(2, 2, 0, 0, 5, 0, 1),      TD(2, 2, 0, 0, 6, 0x03, 1),   TD(2, 2, 0, 0, 10, 0x07, 1),
+    TD(2, 2, 0, 0x01, 1, 0, 2),   TD(2, 2, 1, 0x01, 2, 0x01, 2)};
 #undef TD
 
 // kTokDef with every selection turned into a mask.  Straight-line on purpose: which of the 32
@@ -738,9 +608,9 @@ struct TokFastTable {
       const TokDef &d = kTokDef[i];
       TokFast &f = t[i];
       const bool rd = d.sign == 2;
-      if (kTokExtraBits[i] != d.ebits) abort();   // the two tables state the same thing
-      f.ebits = d.ebits;
-      f.sign_shift = (uint8_t)(rd ? d.ebits - 1 : 0);
+      const uint8_t eb = kTokExtraBits[i];
+      f.ebits = eb;
+      f.sign_shift = (uint8_t)(rd ? eb - 1 : 0);
       f.sign_and = rd ? 1 : 0;
       f.sign_const = (uint8_t)(rd ? 0 : d.sign);
       f.vshift = d.vshift;
@@ -748,7 +618,7 @@ struct TokFastTable {
       f.smask = d.smask;
       f.isval = d.kind == 2;
       f.vmask = d.vmask;
-      f.rest_mask = (uint16_t)((1u << (rd ? d.ebits - 1 : d.ebits)) - 1u);
+      f.rest_mask = (uint16_t)((1u << (rd ? eb - 1 : eb)) - 1u);
       f.vbase = d.vbase;
       f.val_mask = d.kind == 2 ? -1 : 0;
       f.eob_mask = d.kind == 0 ? 0xFFFFFFFFu : 0u;
@@ -988,62 +858,6 @@ inline Tok *decode_token_list(BitReader &br, const HuffTree &tree, size_t n, Tok
   if (kHaveBmi2) return decode_token_list_bmi2<PAIR>(br, tree, n, out, left, p, z, eobs, pa);
 #endif
   return decode_token_list_plain<PAIR>(br, tree, n, out, left, p, z, eobs, pa);
-}
-
-// ---------------------------------------------------------------------------------------
-// geometry (spec 2.3 - 2.4): coded order, super blocks, macro blocks
-// ---------------------------------------------------------------------------------------
-void build_geometry(th_dec_ctx *d) {
-  const int fmt = (int)d->info.pixel_fmt;
-  d->hdec = !(fmt & 1);
-  d->vdec = !(fmt & 2);
-  const int yh = (int)d->info.frame_width >> 3, yv = (int)d->info.frame_height >> 3;
-  int fro = 0;
-  for (int p = 0; p < 3; p++) {
-    d->nh[p] = p ? (yh + d->hdec) >> d->hdec : yh;
-    d->nv[p] = p ? (yv + d->vdec) >> d->vdec : yv;
-    d->fro[p] = fro;
-    d->nfrags_pl[p] = d->nh[p] * d->nv[p];
-    fro += d->nfrags_pl[p];
-  }
-  d->nfrags = fro;
-  d->coded_order.clear();
-  d->sb_start.clear();
-  for (int p = 0; p < 3; p++)
-    for (int sby = 0; sby < d->nv[p]; sby += 4)
-      for (int sbx = 0; sbx < d->nh[p]; sbx += 4) {
-        d->sb_start.push_back((int32_t)d->coded_order.size());
-        for (int k = 0; k < 16; k++) {
-          const int by = sby + kHilbert[k][0], bx = sbx + kHilbert[k][1];
-          if (by < d->nv[p] && bx < d->nh[p]) d->coded_order.push_back(d->fro[p] + by * d->nh[p] + bx);
-        }
-      }
-  d->nsbs = (int)d->sb_start.size();
-  d->sb_start.push_back((int32_t)d->coded_order.size());
-  // macro blocks: luma super blocks in raster order, four macro blocks each in coded order
-  d->mbs.clear();
-  for (int sby = 0; sby < yv; sby += 4)
-    for (int sbx = 0; sbx < yh; sbx += 4)
-      for (int k = 0; k < 4; k++) {
-        const int my = sby + 2 * kMbOrder[k][0], mx = sbx + 2 * kMbOrder[k][1];
-        if (my >= yv || mx >= yh) continue;   // frame sizes are multiples of 16: whole MBs only
-        MacroBlock mb;
-        for (int i = 0; i < 2; i++)
-          for (int j = 0; j < 2; j++) mb.luma[i * 2 + j] = (my + i) * yh + mx + j;
-        for (int c = 0; c < 2; c++)
-          for (int i = 0; i < 4; i++) mb.chroma[c][i] = -1;
-        const int cx = mx >> d->hdec, cy = my >> d->vdec;
-        const int ncx = d->hdec ? 1 : 2, ncy = d->vdec ? 1 : 2;
-        mb.nchroma = ncx * ncy;
-        for (int c = 0; c < 2; c++) {
-          // raster order inside the macro block; slot = i*2+j so that 4:4:4 lines up with
-          // luma A,B,C,D and 4:2:2 uses slots 0 (bottom) and 2 (top)
-          for (int i = 0; i < ncy; i++)
-            for (int j = 0; j < ncx; j++)
-              mb.chroma[c][i * 2 + j] = d->fro[1 + c] + (cy + i) * d->nh[1] + cx + j;
-        }
-        d->mbs.push_back(mb);
-      }
 }
 
 }  // namespace
@@ -1500,7 +1314,7 @@ th_dec_ctx *th_decode_alloc_on(const th_info *info, const th_setup_info *setup, 
   d->device_tokens = d->hip && thip_option("fe_device_tokens") != 0;
   d->device_lists = d->hip ? thip_option("fe_device_lists") : 0;
   g_fe_contexts.fetch_add(1, std::memory_order_relaxed);
-  build_geometry(d);
+  build_geometry(*d, (int)d->info.frame_width, (int)d->info.frame_height, (int)d->info.pixel_fmt);
   d->dequant.resize((size_t)64 * 3 * 2 * 64);
   for (int qi = 0; qi < 64; qi++)
     for (int p = 0; p < 3; p++)
@@ -1807,11 +1621,11 @@ static int fe_front(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos, FeRun
       ncoded_total = N;
     } else {
       // ---- 7.3 coded block flags ---------------------------------------------------------------
-      read_long_run_bits(br, (size_t)d->nsbs, d->sbp);
+      read_run_bits<true>(br, (size_t)d->nsbs, d->sbp);
       size_t nfull = 0;
       for (int s = 0; s < d->nsbs; s++) nfull += !d->sbp[s];
       std::vector<uint8_t> fbits;
-      read_long_run_bits(br, nfull, fbits);
+      read_run_bits<true>(br, nfull, fbits);
       d->sbf.assign((size_t)d->nsbs, 0);
       size_t fi = 0, nblk = 0;
       for (int s = 0; s < d->nsbs; s++) {
@@ -1819,7 +1633,7 @@ static int fe_front(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos, FeRun
         else nblk += (size_t)(d->sb_start[s + 1] - d->sb_start[s]);
       }
       std::vector<uint8_t> bbits;
-      read_short_run_bits(br, nblk, bbits);
+      read_run_bits<false>(br, nblk, bbits);
       size_t bi = 0;
       for (int s = 0; s < d->nsbs; s++)
         for (int k = d->sb_start[s]; k < d->sb_start[s + 1]; k++) {
@@ -1983,7 +1797,7 @@ static int fe_front(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos, FeRun
     for (int q = 0; q + 1 < d->nqis; q++) {
       size_t nb = 0;
       for (size_t i = 0; i < nc; i++) nb += d->qii[cl[i]] == q;
-      read_long_run_bits(br, nb, bits);
+      read_run_bits<true>(br, nb, bits);
       bits.push_back(0);   // the entry a block that takes no bit looks at
       size_t bi = 0;
       for (size_t i = 0; i < nc; i++) {
@@ -2608,7 +2422,7 @@ static th_dec_ctx *fe_new_parser(const th_dec_ctx *m) {
   s->stripe_cb.ctx = nullptr;
   s->stripe_cb.stripe_decoded = nullptr;
   memset(&s->prof, 0, sizeof(s->prof));
-  build_geometry(s);
+  build_geometry(*s, (int)s->info.frame_width, (int)s->info.frame_height, (int)s->info.pixel_fmt);
   fe_init_frame_arrays(s);
   return s;
 }
@@ -2623,21 +2437,21 @@ static void fe_parse_job(FeSlot &sl) {
   FeRun r;
   s->qii_dirty = true;   // (the coded blocks' entries are always written: the owner takes exactly those)
   double t[5] = {0, 0, 0, 0, 0};
-  if (sl.timed) t[0] = fe_now();
+  if (sl.timed) t[0] = thip_now();
   s->pair_on = sl.want_assign;
   int rc = fe_front(s, &op, nullptr, r);
-  if (sl.timed) t[1] = fe_now();
+  if (sl.timed) t[1] = thip_now();
   if (rc == kFeContinue) {
     fe_undo_dc(s);
     const size_t nc = s->cl_start[3];
     s->tl_dc.resize(nc + 1);
     for (size_t ci = 0; ci < nc; ci++) s->tl_dc[ci] = s->dc[s->clist[ci]];
-    if (sl.timed) t[2] = fe_now();
+    if (sl.timed) t[2] = thip_now();
     s->tl_packed = false;
     if (sl.want_lists) {
       fe_pack_lists(s);
       s->tl_packed = true;
-      if (sl.timed) t[3] = t[4] = fe_now();
+      if (sl.timed) t[3] = t[4] = thip_now();
     }
     if (sl.timed && t[4] > 0) {
       for (int k = 0; k < 4; k++) sl.acc[k] += t[k + 1] - t[k];
@@ -2968,7 +2782,7 @@ int th_decode_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos) {
   if (d->la && !d->la->count) d->la->pair_last = 0;
   if (d->la && d->la->count) {
     d->prof.start();
-    const double now = fe_now();
+    const double now = thip_now();
     FeSlot *const sl = fe_lookahead_take(d, op);
     fe_pair_rule(d->la, now, sl != nullptr);
     if (sl) {
@@ -2980,7 +2794,7 @@ int th_decode_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos) {
       return fe_back(d, granpos, r);
     }
   }
-  if (d->device_lists < 0) fe_lists_rule(d, fe_now(), op->bytes > 0);
+  if (d->device_lists < 0) fe_lists_rule(d, thip_now(), op->bytes > 0);
   const int rc = fe_front(d, op, granpos, r);
   if (rc != kFeContinue) return rc;
   return fe_back(d, granpos, r);
@@ -3017,7 +2831,7 @@ int th_decode_ycbcr_out(th_dec_ctx *d, th_ycbcr_buffer ycbcr) {
         la->adopted++;
         thip_option_add("fe_lookahead_adopted", 1);
         thip_option_add("fe_pipelined", 1);
-        const double now = fe_now();
+        const double now = thip_now();
         fe_pair_rule(la, now, true);
         fe_lists_rule(d, now, false);
         d->early.pkt.assign(sl.pkt.begin(), sl.pkt.begin() + sl.bytes);
