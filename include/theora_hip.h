@@ -105,7 +105,15 @@ int thip_state_ycbcr_map_end(thip_state *st, const uint8_t *planes[3], int32_t s
    valid).  What the discarded frame left in its buffer, its half of the coded map and the host image it went to is treated as
    unknown (the next frame takes no static-block shortcut).  Work already queued is not cancelled: it runs, in order, ahead of
    whatever is queued next.  th_decode_packetin uses this when, with option fe_pipeline, another packet arrives than the one
-   th_decode_ycbcr_out decoded ahead.  mark: eight words owned by the caller. */
+   th_decode_ycbcr_out decoded ahead, and th_decode_ctl for the requests that change what such a frame would have been
+   (include/theoradec_hip.h).  mark: eight words owned by the caller.
+   ONE frame can be taken back, not two: the first frame behind a mark goes to the buffer that is neither marked reference, the
+   second to the marked PREV buffer (or, behind a key frame, the marked GOLD one), and those pixels are gone.  _rewind returns
+   THIP_EINVAL and changes nothing if more than one frame was decoded since the mark, or if a marked GOLD or PREV buffer was
+   written since.  A thip_state_write_plane or thip_state_set_ref_idx since the mark counts as a frame: it changes pixels or
+   labels the mark knows nothing about (so one plane write into a buffer that is no marked reference can be rewound over, one
+   into a marked reference cannot, and neither can a plane write and a frame).  A frame that decodes nothing (THIP_DUPFRAME)
+   does not count. */
 int thip_state_ring_mark(thip_state *st, int64_t mark[8]);
 int thip_state_ring_rewind(thip_state *st, const int64_t mark[8]);
 /* on != 0: every decoded frame of this state is sent to its pinned host image by the launch that

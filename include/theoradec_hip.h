@@ -161,7 +161,20 @@ typedef struct {
    th_decode_packetin as ever.  A th_decode_packetin whose packet is not the oldest announced one drops everything announced and
    parses the ordinary way: announcing is a hint, never a requirement, and the pictures are the same either way.
    (That holds under option fe_pipeline too, include/theora_hip.h -- there th_decode_ycbcr_out hands the oldest announced packet's
-   frame to the device before it waits for its own picture: a th_decode_packetin that brings another packet takes that frame back.) */
+   frame to the device before it waits for its own picture: a th_decode_packetin that brings another packet takes that frame back.)
+
+   While a frame is held.  From the th_decode_ycbcr_out(N) that decoded the announced frame N + 1 ahead until the next
+   th_decode_packetin, the context holds a frame the caller has not handed in.  Every th_decode_ctl in that interval behaves as if
+   frame N were the newest, as it is for the caller and in the reference: a request that changes what the held frame would have
+   been TAKES IT BACK first -- reference ring, frame counters, frame type, qi tables, the blocks' qi indices as they were after
+   frame N -- once its arguments have been checked, so that a refused request changes nothing; the next th_decode_packetin then
+   decodes its packet on the caller's thread like any packet nobody announced (slower for that one frame, always right).  These
+   take back: TH_DECCTL_SET_GRANPOS (the counters it sets are frame N's), TH_DECCTL_SET_PPLEVEL with a level above 0 (the held
+   frame was decoded unfiltered and untracked), TH_DECCTL_SET_STRIPE_CB (the callback is made inside a frame's
+   th_decode_packetin), TH_DECCTL_THIP_SET_DEVICE_DC and _SET_DEVICE_TOKENS.  These leave the held frame alone: every
+   TH_DECCTL_GET_*, TH_DECCTL_SET_PPLEVEL 0, TH_DECCTL_THIP_PREFETCH_PACKET, _PICTURE_OUT, _SET_HOST_OUTPUT, _SET_DEVICE_LISTS.
+   The picture th_decode_ycbcr_out handed out for frame N stays valid and unchanged either way.  One frame is held at most: the
+   backend can take back one (thip_state_ring_rewind, include/theora_hip.h). */
 #define TH_DECCTL_THIP_PREFETCH_PACKET (0x7105)
 /* Which GPU the context's device state lives on (th_decode_alloc_on, option "device" / THIP_DEVICE): buf = int, receives the
    device index (thip_state_device); TH_EINVAL for a context without device state (slot-trace mode). */

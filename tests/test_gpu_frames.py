@@ -841,6 +841,65 @@ def test_a_frame_decoded_ahead_is_taken_back_at_the_c_abi(hip, content, skip_sta
     ost.close()
 
 
+@pytest.mark.parametrize("second_is_key", [False, True])
+@pytest.mark.parametrize("first_is_key", [False, True])
+def test_two_frames_behind_a_mark_are_not_taken_back(hip, first_is_key, second_is_key):
+    """thip_state_ring_rewind undoes ONE frame (include/theora_hip.h): the first frame behind a mark goes to the buffer that is
+    neither marked reference, the second to a marked one -- the ring put back would name pixels that are gone.  Mark, two frames,
+    rewind: THIP_EINVAL and nothing changed -- ring, picture, and the frames decoded next equal an oracle that decoded both.  One
+    frame behind the mark is still taken back (the test above); so is one plane written into a buffer that is no marked reference,
+    while a plane written into a marked reference is not (a plane write counts as a frame: it changes pixels the mark knows
+    nothing about)."""
+    import ctypes as C
+    from theora_amd import _lib
+    L = _lib.load()
+    w, h = 80, 48                    # partial super blocks in every plane, more than one tile
+    geom = synth.Geometry(w, h)
+    rng = np.random.default_rng(815)
+    ost, gst = oracle.State(w, h), hip.State(w, h)
+    keep = []
+
+    def both(ftype):
+        fr = synth.gen_frame(geom, rng, ftype, "mixed", flimit=3)
+        assert util.oracle_apply(ost, fr) == 0
+        d, ka = synth.upload_frame(synth.pack_frame(geom, fr))
+        keep.append(ka)
+        assert hip.decode_frames([gst], [d])[0] == 0
+    both(hip.INTRA_FRAME)
+    both(hip.INTER_FRAME)
+    both(hip.INTER_FRAME)
+    mark = (C.c_int64 * 8)()
+    assert L.thip_state_ring_mark(gst.handle, mark) == 0
+    both(hip.INTRA_FRAME if first_is_key else hip.INTER_FRAME)
+    both(hip.INTRA_FRAME if second_is_key else hip.INTER_FRAME)
+    ring = [gst.ref_idx(k) for k in range(3)]
+    assert L.thip_state_ring_rewind(gst.handle, mark) == _lib.EINVAL
+    assert [gst.ref_idx(k) for k in range(3)] == ring == ost.ref_frame_idx
+    assert not util.planes_equal(ost, gst)
+    got = gst.ycbcr_out()
+    for pli in range(3):
+        assert np.array_equal(got[pli], ost.get_plane(oracle.FRAME_PREV, pli)[::-1]), pli
+    for _ in range(3):
+        both(hip.INTER_FRAME)
+        assert not util.planes_equal(ost, gst)
+        assert ost.ref_frame_idx == [gst.ref_idx(k) for k in range(3)]
+    # a plane write is a frame as far as a mark goes
+    g = gst.planes[0]
+    img = rng.integers(0, 256, (g["height"], g["width"])).astype(np.uint8)
+    free = next(b for b in range(3) if b not in (gst.ref_idx(hip.FRAME_GOLD), gst.ref_idx(hip.FRAME_PREV)))
+    assert L.thip_state_ring_mark(gst.handle, mark) == 0
+    gst.write_plane(free, 0, img)
+    assert L.thip_state_ring_rewind(gst.handle, mark) == 0
+    assert L.thip_state_ring_mark(gst.handle, mark) == 0
+    gst.write_plane(gst.ref_idx(hip.FRAME_PREV), 0, gst.read_plane(gst.ref_idx(hip.FRAME_PREV), 0))    # (the same pixels: still refused)
+    assert L.thip_state_ring_rewind(gst.handle, mark) == _lib.EINVAL
+    assert not util.planes_equal(ost, gst)
+    both(hip.INTER_FRAME)
+    assert not util.planes_equal(ost, gst)
+    gst.close()
+    ost.close()
+
+
 def test_check_fault_repairs_for_a_caller_that_only_synchronises(hip, capfd):
     """thip_state_check_fault: a caller that keeps its frames on the device and brackets its work with thip_synchronize
     only never reaches the calls that repair a failed hand-over -- thip_synchronize REPORTS (THIP_EFAULT while a state's word is

@@ -191,6 +191,9 @@ struct thip_state {
   // Which decoded frame (counted by frame_serial) each buffer holds, -1 if unknown, and which frame's
   // flags sit in each half of coded_map: what makes leaving static blocks in place safe (launch_chunk).
   int64_t buf_serial[3], map_serial[2];
+  // frame_serial of whatever last wrote each buffer or re-labelled it -- a decoded frame, thip_state_write_plane, thip_state_set_ref_idx,
+  // the mid-grey fill: what thip_state_ring_rewind asks before it promises that a marked reference still holds the marked pixels
+  int64_t buf_touched[3];
   int ref_idx[3];       // THIP_FRAME_* -> buffer index
   int last_decoded;     // buffer index of the most recently completed frame, -1 if none
   int lane;             // library-owned HIP stream this state is bound to, -1 until first use
@@ -667,6 +670,7 @@ int thip_state_create_on(thip_state **out, int device, int frame_width, int fram
   st->held_img = -1;
   st->out_serial = -1;
   st->buf_serial[0] = st->buf_serial[1] = st->buf_serial[2] = -1;
+  st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = -1;
   st->map_serial[0] = st->map_serial[1] = -1;
   st->pp_serial = -1;
   {
@@ -783,6 +787,7 @@ int thip_state_set_ref_idx(thip_state *st, int gold, int prev, int self) {
   if (self >= 0) st->last_decoded = self;
   st->frame_serial++;
   st->buf_serial[0] = st->buf_serial[1] = st->buf_serial[2] = -1;   // the caller re-labelled the buffers
+  st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = st->frame_serial;
   return THIP_OK;
 }
 
@@ -814,6 +819,7 @@ int thip_state_write_plane(thip_state *st, int bufi, int pli, const uint8_t *hos
                       hipMemcpyHostToDevice));
   st->frame_serial++;
   st->buf_serial[bufi] = -1;
+  st->buf_touched[bufi] = st->frame_serial;
   return THIP_OK;
 }
 
@@ -999,6 +1005,14 @@ int thip_state_ring_rewind(thip_state *st, const int64_t mark[8]) {
     if (mark[k] < -1 || mark[k] > 2) return THIP_EINVAL;
   if (mark[3] < -1 || mark[3] > 2) return THIP_EINVAL;
   if (mark[4] == st->frame_serial) return THIP_OK;   // nothing was decoded since
+  // ONE frame can be undone: it went to the buffer that was neither marked reference.  A second one has gone to the marked PREV
+  // buffer (or, behind a key frame, to the marked GOLD one), and the ring put back would name pixels that are gone.  Everything
+  // that moves frame_serial counts as a frame here -- thip_state_write_plane and thip_state_set_ref_idx too: they change pixels or
+  // labels the mark knows nothing about -- and whatever the one step was, it must not have touched a marked reference.  Refused
+  // before anything is changed.
+  if (st->frame_serial - mark[4] > 1) return THIP_EINVAL;
+  for (int k = THIP_FRAME_GOLD; k <= THIP_FRAME_PREV; k++)
+    if (mark[k] >= 0 && st->buf_touched[mark[k]] > mark[4]) return THIP_EINVAL;
   for (int k = 0; k < 3; k++) st->ref_idx[k] = (int)mark[k];
   st->last_decoded = (int)mark[3];
   // every buffer that is not one of the marked references may have been written by a discarded frame; so may either half of the
@@ -1146,6 +1160,7 @@ static int launch_chunk(thip_state *const *states, const thip_frame_desc *descs,
       st->order_recorded = 0;
       st->frame_serial++;
       st->buf_serial[0] = st->buf_serial[1] = st->buf_serial[2] = -1;
+      st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = st->frame_serial;
     }
     if (d.ncoded == 0) {  // decode.c:2764-2772
       if (results) results[i] = THIP_DUPFRAME;
@@ -1196,6 +1211,7 @@ static int launch_chunk(thip_state *const *states, const thip_frame_desc *descs,
                 st->ref_idx[THIP_FRAME_PREV] >= 0 && st->buf_serial[st->ref_idx[THIP_FRAME_PREV]] == serial - 1;
     st->map_serial[cm] = serial;
     st->buf_serial[bufi] = serial;
+    st->buf_touched[bufi] = serial;
     K.flimit2 = 2 * d.flimit;
     K.debug = THIP_OPT("debug");
     // a unit for every block of the frame: the first unit of a tile in the whole tile rows of a plane is the plane's first +

@@ -193,6 +193,7 @@ struct FeLookahead;
 extern "C" {
 static void fe_lookahead_free(th_dec_ctx *d);
 static int fe_prefetch(th_dec_ctx *d, const ogg_packet *op);
+static int fe_take_back(th_dec_ctx *d);
 }
 
 // (thip_ctx_head: th_info and the granule bias first, as in th_enc_ctx, so that th_granule_frame / _time take either)
@@ -256,6 +257,7 @@ struct th_dec_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
     int64_t mark[8] = {0};
     int frame_type0 = 0, nqis0 = 0, qis0[3] = {0, 0, 0};
     bool qii_dirty0 = false, qii_saved = false;
+    bool dc_qis_tracked0 = false;      // (the frame ahead is decoded without post-processing and so stops the tracking, decode.c:1209-1219)
     std::vector<uint8_t> qii0;         // the blocks' qi indices (they outlive a frame, decode.c:913-917), when the frame ahead writes them
   } early;
   FeWorker *worker;                  // (created with the first frame that takes the token-list path with option fe_worker on)
@@ -1406,6 +1408,9 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
       if (buf_sz != sizeof(int)) return TH_EINVAL;
       const int lvl = *(int *)buf;
       if (lvl < 0 || lvl > 7) return TH_EINVAL;   // decode.c:1994
+      // a frame th_decode_ycbcr_out decoded ahead was decoded at level 0: at any other level it would have been tracked, and from
+      // level 2 up shown filtered (the rule for every request: include/theoradec_hip.h, "While a frame is held")
+      if (lvl > 0 && fe_take_back(d) < 0) return TH_EFAULT;
       d->pp_level = lvl;
       // every frame is sent to its host image by the decoding launch itself -- unless a post-processed one
       // is going to replace it: then the image is made when th_decode_ycbcr_out asks
@@ -1452,6 +1457,7 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
       if (buf_sz != sizeof(int64_t)) return TH_EINVAL;
       const int64_t g = *(int64_t *)buf;
       if (g < 0) return TH_EINVAL;
+      if (fe_take_back(d) < 0) return TH_EFAULT;   // (the counters below are frame N's: a frame decoded ahead has moved them on)
       d->granpos = g;
       d->keyframe_num = (g >> d->info.keyframe_granule_shift) - d->granpos_bias;
       d->curframe_num = d->keyframe_num + (g & (((int64_t)1 << d->info.keyframe_granule_shift) - 1));
@@ -1460,6 +1466,7 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
     case TH_DECCTL_SET_STRIPE_CB:
       if (!d || !buf) return TH_EFAULT;
       if (buf_sz != sizeof(th_stripe_callback)) return TH_EINVAL;
+      if (fe_take_back(d) < 0) return TH_EFAULT;   // (the callback is made inside a frame's th_decode_packetin: a frame decoded ahead made none)
       d->stripe_cb = *(const th_stripe_callback *)buf;
       return 0;
     case TH_DECCTL_THIP_SET_DEVICE_DC: {
@@ -1467,6 +1474,7 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
       if (buf_sz != sizeof(int)) return TH_EINVAL;
       if (d->trace || !d->hip) return TH_EINVAL;
       const int on = *(int *)buf != 0;
+      if (fe_take_back(d) < 0) return TH_EFAULT;
       if (thip_state_set_device_dc(d->hip, on) < 0) return TH_EIMPL;
       d->device_dc = on != 0;
       return 0;
@@ -1475,6 +1483,7 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
       if (!d || !buf) return TH_EFAULT;
       if (buf_sz != sizeof(int)) return TH_EINVAL;
       if (d->trace || !d->hip) return TH_EINVAL;
+      if (fe_take_back(d) < 0) return TH_EFAULT;
       d->device_tokens = *(int *)buf != 0;
       return 0;
     }
@@ -2733,6 +2742,30 @@ static void fe_pair_rule(FeLookahead *la, double now, bool adopted) {
   la->pair_last = now;
 }
 
+// The frame th_decode_ycbcr_out decoded ahead of its th_decode_packetin (option fe_pipeline) never happened: the backend's reference
+// ring goes back to where it stood (thip_state_ring_rewind: the discarded frame's kernels still run, ahead of whatever comes next
+// on the state's stream; what they wrote counts as unknown), the context's counters, frame type, qi tables, the blocks' qi indices
+// and the post-processing's tracking likewise.  The picture th_decode_ycbcr_out handed out stays where it is.  Called by the
+// th_decode_packetin that brings another packet, and by every th_decode_ctl request that changes what the held frame would have
+// been -- after the request's arguments have been checked, so that a refused request changes nothing.  0 with no frame held.
+static int fe_take_back(th_dec_ctx *d) {
+  if (!d->early.valid) return 0;
+  if (thip_state_ring_rewind(d->hip, d->early.mark) < 0) return TH_EFAULT;
+  d->early.valid = false;
+  d->keyframe_num = d->early.key0;
+  d->curframe_num = d->early.cur0;
+  d->granpos = ((d->early.key0 + d->granpos_bias) << d->info.keyframe_granule_shift) + (d->early.cur0 - 1 - d->early.key0);
+  d->frame_type = d->early.frame_type0;
+  d->nqis = d->early.nqis0;
+  memcpy(d->qis, d->early.qis0, sizeof(d->qis));
+  d->qii_dirty = d->early.qii_dirty0;
+  if (d->early.qii_saved && d->early.qii0.size() == d->qii.size()) d->qii.swap(d->early.qii0);
+  d->early.qii_saved = false;
+  d->dc_qis_tracked = d->early.dc_qis_tracked0;
+  thip_option_add("fe_pipeline_taken_back", 1);
+  return 0;
+}
+
 int th_decode_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos) {
   if (!d || !op) return TH_EFAULT;
   if (d->parse_only) return TH_EINVAL;
@@ -2755,27 +2788,15 @@ int th_decode_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos) {
       d->curframe_num = c0 + 2;
       return TH_DUPFRAME;
     }
-    d->early.valid = false;
     if ((size_t)op->bytes == d->early.pkt.size() && op->packet && !memcmp(op->packet, d->early.pkt.data(), d->early.pkt.size())) {
+      d->early.valid = false;
       if (granpos) *granpos = d->early.granpos;
       return d->early.rc;
     }
     // Another packet than the one th_decode_ycbcr_out decoded ahead (a seek, a caller that changed its mind): the frame is TAKEN
-    // BACK.  The backend's reference ring goes back to where it stood (thip_state_ring_rewind: the discarded frame's kernels still
-    // run, ahead of whatever comes next on the state's stream; what they wrote counts as unknown), the context's counters and the
-    // blocks' qi indices likewise, and this packet is decoded as if nothing had happened (it may itself be the next
-    // announced one).  (Round 5 returned TH_EINVAL here -- an announcement was a promise.)
-    if (thip_state_ring_rewind(d->hip, d->early.mark) < 0) return TH_EFAULT;
-    d->keyframe_num = d->early.key0;
-    d->curframe_num = d->early.cur0;
-    d->granpos = G(d->early.key0, d->early.cur0 - 1);
-    d->frame_type = d->early.frame_type0;
-    d->nqis = d->early.nqis0;
-    memcpy(d->qis, d->early.qis0, sizeof(d->qis));
-    d->qii_dirty = d->early.qii_dirty0;
-    if (d->early.qii_saved && d->early.qii0.size() == d->qii.size()) d->qii.swap(d->early.qii0);
-    d->early.qii_saved = false;
-    thip_option_add("fe_pipeline_taken_back", 1);
+    // BACK (fe_take_back), and this packet is decoded as if nothing had happened (it may itself be the next announced one).
+    // (Round 5 returned TH_EINVAL here -- an announcement was a promise.)
+    if (fe_take_back(d) < 0) return TH_EFAULT;
     // (what else was announced is looked at below like any announcement: adopted if this packet is the oldest of them, dropped if not)
   }
   FeRun r;
@@ -2843,6 +2864,7 @@ int th_decode_ycbcr_out(th_dec_ctx *d, th_ycbcr_buffer ycbcr) {
         d->early.nqis0 = d->nqis;
         memcpy(d->early.qis0, d->qis, sizeof(d->qis));
         d->early.qii_dirty0 = d->qii_dirty;
+        d->early.dc_qis_tracked0 = d->dc_qis_tracked;
         d->early.qii_saved = sl.ctx->nqis > 1 || d->qii_dirty;   // (fe_adopt writes the coded blocks' entries then)
         if (d->early.qii_saved) d->early.qii0.assign(d->qii.begin(), d->qii.end());
         fe_adopt(d, sl.ctx);

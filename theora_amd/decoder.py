@@ -8,6 +8,7 @@ from . import _lib
 from ._lib import OggPacket, ThComment, ThImgPlane, ThInfo, TheoraHipError
 
 TH_DUPFRAME = 1
+TH_DECCTL_GET_PPLEVEL_MAX, TH_DECCTL_SET_PPLEVEL, TH_DECCTL_SET_GRANPOS, TH_DECCTL_SET_STRIPE_CB = 1, 3, 5, 7
 TH_DECCTL_THIP_GET_SLOT_TRACE = 0x7101
 TH_DECCTL_THIP_SET_DEVICE_DC = 0x7102
 TH_DECCTL_THIP_SET_DEVICE_TOKENS = 0x7103
@@ -22,6 +23,14 @@ class PictureOutArgs(C.Structure):
     """thip_picture_out_args (include/theoradec_hip.h)."""
     _fields_ = [("format", C.c_int32), ("chroma", C.c_int32), ("crop", C.c_int32), ("dst", C.c_void_p * 3),
                 ("dst_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
+
+
+STRIPE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ThImgPlane), C.c_int, C.c_int)
+
+
+class StripeCallback(C.Structure):
+    """th_stripe_callback (theoradec.h:79-92)."""
+    _fields_ = [("ctx", C.c_void_p), ("stripe_decoded", STRIPE_FN)]
 
 
 class SlotTrace(C.Structure):
@@ -61,15 +70,50 @@ class Decoder:
             raise TheoraHipError("th_decode_alloc failed")
         self._npackets = len(header_packets)
 
-    def packetin(self, data):
-        """Returns (rc, granulepos); rc 0 = new frame, TH_DUPFRAME = repeat of the last one."""
+    def packetin_raw(self, data):
+        """th_decode_packetin as it is: (rc, granulepos), a negative rc included; nothing is raised."""
         op, keep = _packet(data, packetno=self._npackets)
         self._npackets += 1
         gp = C.c_int64(-1)
         rc = self._L.th_decode_packetin(self._dec, C.byref(op), C.byref(gp))
+        return rc, gp.value
+
+    def packetin(self, data):
+        """Returns (rc, granulepos); rc 0 = new frame, TH_DUPFRAME = repeat of the last one."""
+        rc, gp = self.packetin_raw(data)
         if rc < 0:
             raise TheoraHipError("th_decode_packetin returned %d" % rc)
-        return rc, gp.value
+        return rc, gp
+
+    def ctl(self, req, buf, size):
+        """th_decode_ctl as it is: buf a ctypes object (or None), size in bytes; the return code, nothing is raised."""
+        return self._L.th_decode_ctl(self._dec, int(req), None if buf is None else C.byref(buf), int(size))
+
+    def set_granpos(self, granpos, size=None):
+        """TH_DECCTL_SET_GRANPOS (a seek: the next frame counts on from here); the return code.  size: buf_sz, if not the value's."""
+        v = C.c_int64(granpos)
+        return self.ctl(TH_DECCTL_SET_GRANPOS, v, C.sizeof(v) if size is None else size)
+
+    def set_pp_level(self, level):
+        """TH_DECCTL_SET_PPLEVEL, 0 .. 7; the return code."""
+        v = C.c_int(level)
+        return self.ctl(TH_DECCTL_SET_PPLEVEL, v, C.sizeof(v))
+
+    def pp_level_max(self):
+        """TH_DECCTL_GET_PPLEVEL_MAX: (return code, value)."""
+        v = C.c_int(-1)
+        rc = self.ctl(TH_DECCTL_GET_PPLEVEL_MAX, v, C.sizeof(v))
+        return rc, v.value
+
+    def set_stripe_cb(self, fn, ctx=None):
+        """TH_DECCTL_SET_STRIPE_CB: fn(ctx, th_ycbcr_buffer, first fragment row, end fragment row) is called from inside
+        packetin() for every decoded frame; None switches it off.  The return code."""
+        cb = STRIPE_FN(fn) if fn is not None else STRIPE_FN()
+        s = StripeCallback(ctx, cb)
+        rc = self.ctl(TH_DECCTL_SET_STRIPE_CB, s, C.sizeof(s))
+        if rc == 0:
+            self._stripe_keep = cb          # (the library calls it until it is replaced)
+        return rc
 
     def prefetch(self, data):
         """TH_DECCTL_THIP_PREFETCH_PACKET: announce a packet that a later packetin() will bring (decode order).  True when
