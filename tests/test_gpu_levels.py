@@ -179,3 +179,109 @@ def test_one_form_per_frame_for_slot_owning_blocks(hip):
     assert buf[1] == 5                                   # a refused call leaves the block alone
     assert L.thip_state_frag_recon(gst.handle, 1, 0, buf.ctypes.data, 1, 20, hip.FRAME_SELF, 0) == 0     # DC-only: no slot, either entry
     assert L.thip_state_frag_recon_levels(gst.handle, 2, 0, buf.ctypes.data, 3, 20, 3, hip.FRAME_SELF, 0) == hip._lib.EINVAL   # qii 0..2
+
+
+@pytest.mark.parametrize("form", ["dense", "levels", "tokens"])
+def test_refused_slot_calls_leave_the_frame_as_it_was(hip, form):
+    """One intra frame through thip_state_frag_recon / _levels / _tokens in coded order, with every kind of refused call between
+    the good ones: the fragment just enqueued again, a slot-owning block at a lower lane of the tile being filled, one back in a
+    tile that has been left, one in another form than the frame's, arguments out of range.  Each answers THIP_EINVAL, leaves the
+    caller's block alone and leaves the frame as it was: the picture is the oracle's.  144 x 16 is the smallest 4:2:0 picture whose
+    luma plane has two tiles (one tile cannot show the contiguity rule).  Two blocks of tile 0 are DC-only (they own no slot, so
+    they may come late): they are what the refused out-of-order calls present as slot-owning blocks.  A level beyond eight bits
+    comes after narrow blocks of its tile: in the levels form the tile's units are rewritten, with refusals before and after."""
+    w, h = 144, 16
+    geom = synth.Geometry(w, h, PF_420)
+    ost, gst = oracle.State(w, h, PF_420), hip.State(w, h, PF_420)
+    assert gst.tiles_x[0] * gst.tiles_y[0] == 2
+    L = hip._lib.load()
+    fr = synth.gen_frame(geom, np.random.default_rng(77), hip.INTRA_FRAME, "dense", flimit=4)
+    cf = fr["coded_fragis"]
+    tile, lane = geom.frag_pos[cf] >> 6, geom.frag_pos[cf] & 63
+    k0, k1 = np.nonzero(tile == 0)[0], np.nonzero(tile == 1)[0]
+    rest = np.nonzero(tile > 1)[0]
+    assert np.all(np.diff(lane[k0]) > 0) and np.all(np.diff(lane[k1]) > 0) and k0[-1] < k1[0] < rest[0]
+    late_a, late_b, big = int(k0[5]), int(k0[-1]), int(k0[20])
+    for k in (late_a, late_b):
+        fr["last_zzi"][k] = 1
+        fr["levels"][k, 1:] = 0
+    fr["levels"][big, synth.FZIG_ZAG[1]] = 300
+    fr["coeffs"] = synth.dequantise(geom, fr)
+    util.oracle_apply(ost, fr)
+    buf = np.zeros(128, np.int16)
+
+    def call(entry, k, last_zzi=None, refi=hip.FRAME_SELF, qii=None, ntoks=None, dqsel=None):
+        """Block k through `entry`: the return code, and whether the caller's block is as it was."""
+        k = int(k)
+        fi = int(cf[k])
+        pli = int(geom.plane_of[fi])
+        lz = int(fr["last_zzi"][k]) if last_zzi is None else last_zzi
+        dcq = int(fr["dc_quant"][k])
+        if entry == "tokens":
+            lv = fr["levels"][k, synth.FZIG_ZAG[1:]].astype(np.int64)
+            nz = np.nonzero(lv)[0]
+            toks = np.zeros(64, np.uint32)
+            toks[:nz.size] = (nz + 1) << 16 | (lv[nz] & 0xFFFF)
+            before = toks.copy()
+            rc = L.thip_state_frag_recon_tokens(gst.handle, fi, pli, toks.ctypes.data, int(nz.size) if ntoks is None else ntoks,
+                                                int(fr["levels"][k, 0]), lz, dcq,
+                                                (pli * 3 + int(fr["qii"][k])) * 2 if dqsel is None else dqsel, refi, 0)
+            return rc, np.array_equal(toks, before)
+        buf[:64] = fr["coeffs" if entry == "dense" else "levels"][k]
+        before = buf.copy()
+        if entry == "dense":
+            rc = L.thip_state_frag_recon(gst.handle, fi, pli, buf.ctypes.data, lz, dcq, refi, 0)
+        else:
+            rc = L.thip_state_frag_recon_levels(gst.handle, fi, pli, buf.ctypes.data, lz, dcq, int(fr["qii"][k]) if qii is None else qii,
+                                                refi, 0)
+        return rc, np.array_equal(buf, before)
+
+    def good(k):
+        rc, _ = call(form, k)
+        assert rc == 0, (k, rc)
+        assert form == "tokens" or not buf[:64].any()       # zeroed on success
+
+    def refused(entry, k, **kw):
+        rc, same = call(entry, k, **kw)
+        assert rc == hip._lib.EINVAL, (entry, k, kw, rc)
+        assert same, (entry, k, kw)
+
+    def refused_arguments(k):
+        refused(form, k, last_zzi=65)
+        refused(form, k, refi=3)
+        if form == "levels":
+            refused(form, k, qii=3)
+        if form == "tokens":
+            refused(form, k, ntoks=64)
+            refused(form, k, dqsel=18)
+
+    others = [e for e in ("dense", "levels", "tokens") if e != form]
+    gst.frame_begin(hip.INTRA_FRAME)
+    for sel in range(18):
+        gst.frame_dequant_table(sel, fr["dequant"][sel // 6, sel // 2 % 3, sel % 2])
+    for k in k0[:11]:
+        if k != late_a:
+            good(k)
+    refused(form, k0[10])                       # the fragment just enqueued, again
+    refused(form, late_a, last_zzi=3)           # a slot-owning block at a lower lane than the tile's last
+    for e in others:
+        refused(e, k0[11])                      # a slot-owning block in another form
+    refused_arguments(k0[11])
+    good(late_a)                                # (DC-only: no slot, no order)
+    for k in k0[11:-1]:
+        good(k)
+        if k == big:                            # (levels: the tile has just turned wide)
+            refused(form, k)
+    for e in others:                            # the same before the first block of a tile
+        refused(e, k1[0])
+    refused_arguments(k1[0])
+    good(k1[0])
+    refused(form, late_b, last_zzi=3)           # tile 0 has been left: a higher lane than its last, but its slots are contiguous
+    refused(form, k0[-2])
+    good(late_b)
+    for k in list(k1[1:]) + list(rest):
+        good(k)
+    for pli in range(3):
+        gst.loop_filter_frag_rows(fr["flimit"], hip.FRAME_SELF, pli, 0, geom.nv[pli])
+    gst.frame_flush()
+    assert not util.planes_equal(ost, gst)

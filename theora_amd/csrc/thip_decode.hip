@@ -104,7 +104,6 @@ Option g_options[] = {
     {"fe_trace_backend", 0, "th_decode_*: record the slot calls instead of running them (tests)"},
     {"fe_prof", 0, "th_decode_*: per-stage host timing"},
     {"device", -1, "th_decode_alloc: -1 the current device, n that device, -2 round robin over the node's devices (THIP_DEVICE=rr)"},
-    {"half_tiles", 0, "k_recon_lf_h (two super blocks per wave, two lanes per block) for launches of at least sb_tiles and fewer tiles than this (0: never)"},
     {"sb_tiles", 600, "k_recon_lf_sb (one super block per wave, four lanes per block) instead of k_recon_lf for launches of fewer tiles than this (0: never)"},
     {"enc_halfpel_lanes", 2, "thip_enc_frag_metric_halfpel_batch: 2 (default): a lane per side (dx = -1 / +1), four sites each; 3: a lane per dx (two or three sites)"},
     {"enc_sites_lds", 1, "thip_enc_frag_metric_sites_batch, SATD: 1 (default, round 6): k_enc_sites_satd, the source block shared by a block's three lanes through LDS; 0: k_enc_sites<SATD> (rounds 4-5)"},
@@ -179,6 +178,11 @@ extern "C" const char *thip_option_name(int index, const char **help) {
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
+// What a frame of the enqueue path takes along besides its descriptor; kept with the frame that may be decoded again (redo).
+struct FrameExtras {
+  int lf_rows_custom, lf_y0[3], lf_y1[3];   // the loop filter's rows as thip_state_loop_filter_frag_rows recorded them (else: every row)
+  int flush_flags;                          // d_flags describes the frame (device DC un-prediction)
+};
 struct thip_state {
   int device;             // HIP device the frames, the staging buffers and the launches of this state live on
   int frame_width, frame_height, pixel_fmt, hdec, vdec;
@@ -223,7 +227,7 @@ struct thip_state {
   int32_t *enq_last_lane;   // per tile: last lane that received a slot (arrival-order check)
   int enq_ncoded, enq_nuncoded, enq_nslots, enq_frame_type, enq_flimit, enq_active, enq_last_tile;
   int enq_lf_y0[3], enq_lf_y1[3], enq_lf_any;
-  int lf_y0[3], lf_y1[3], lf_rows_custom;
+  FrameExtras extras;   // of the frame being launched (thip_frame_flush sets them around its thip_decode_frames call)
   // DC un-prediction on the device (thip_frame_desc.dc_tokens / thip_state_set_device_dc)
   int16_t *d_dc;        // device, nfrags: un-predicted DC values of the frame being decoded
   uint4 *d_dc_ent;      // device, nfrags: k_dc_prepare's per-fragment entries
@@ -236,23 +240,19 @@ struct thip_state {
     int valid;
     thip_frame_desc d;
     int ring[3];            // ref_idx before the frame
-    int lf_custom, lf_y0[3], lf_y1[3];
-    int flush_flags;
+    FrameExtras extras;
     int64_t serial;         // frame_serial after the frame
     uint32_t launch_id;     // what its fused launch writes behind the fault flag (0: the frame took the two passes)
   } redo;
   int redo_owned;       // set by the callers whose descriptors point into the state's own buffers, around their thip_decode_frames call
   uint8_t *d_edge;      // device, k_recon_lf: kTfRec bytes per tile (the tiles' edges for their neighbours)
   uint32_t edge_epoch;  // serial number of the last k_recon_lf launch for this state (0 = never: the records are zero); 12 bits
-  uint8_t *d_edge_h;    // ... k_recon_lf_h's (a record per half tile; 12-bit serial numbers of its own like the other two)
-  uint32_t edge_epoch_h;
   uint8_t *d_edge_sb;   // ... and k_recon_lf_sb's: a record per super block (a buffer and a serial number of its own: a tag vouches for
   uint32_t edge_epoch_sb;   //  the bytes in front of it only while every launch that uses the buffer rewrites every unit of it)
   int device_dc, enq_device_dc;
   int16_t *h_dc, *d_dc_in;   // enqueue path: token DC values staged per fragment (pinned) and their device copy
   uint8_t *h_flags, *d_flags;   // ... and the fragments' coded | refi << 1 in fragment-index order (the staged command
                                 // words stay in host memory: the wavefront kernel must not poll them across PCIe)
-  int flush_flags;              // set while thip_frame_flush runs: d_flags describes the frame being launched
   // token form of the slot (thip_state_frag_recon_tokens): tokens, per-slot {first token, count | table << 8}, tables
   uint32_t *h_tok, *d_tok;
   uint32_t *h_slot_tok, *d_slot_tok;
@@ -717,7 +717,6 @@ void thip_state_free(thip_state *st) {
   if (st->ev_order) (void)hipEventDestroy(st->ev_order);
   if (st->d_edge) (void)hipFree(st->d_edge);
   if (st->d_edge_sb) (void)hipFree(st->d_edge_sb);
-  if (st->d_edge_h) (void)hipFree(st->d_edge_h);
   for (int k = 0; k < 2; k++)
     if (st->h_tl_buf[k]) (void)hipHostFree(st->h_tl_buf[k]);
   if (st->d_tl) (void)hipFree(st->d_tl);
@@ -1123,261 +1122,261 @@ static hipError_t set_dynamic_lds(const void *kernel, int bytes, int which) {
   return e;
 }
 
-// Launch one chunk of <= THIP_MAX_BATCH streams.
-static int launch_chunk(thip_state *const *states, const thip_frame_desc *descs, int n, hipStream_t s,
-                        int32_t *results, bool two_passes = false) {
-  BatchK B;
-  memset(&B, 0, sizeof(B));
-  int max_wg = 0, max_seam_wg = 0, any_lf = 0, nlive = 0;
-  int any_skip = 0;
-  int live_state[THIP_MAX_BATCH];
-  const bool levels = n > 0 && descs[0].coeff_format == THIP_COEFFS_LEVELS;   // (the callers cut chunks where the form changes)
+// What is wrong with one frame for one state (nothing is launched, no state advanced).
+static int check_frame(const thip_state *st, const thip_frame_desc &d) {
+  if (!st) return THIP_EFAULT;
+  if (d.coeff_format != THIP_COEFFS_DEQUANT16 && d.coeff_format != THIP_COEFFS_LEVELS) return THIP_EINVAL;
+  // (nslots counts slots, or units in the levels form: at most two per coded fragment)
+  if (d.ncoded < 0 || d.nslots < 0 || d.nslots > (d.coeff_format == THIP_COEFFS_LEVELS ? 2 : 1) * (int64_t)d.ncoded || d.ncoded > st->nfrags) return THIP_EINVAL;
+  if (d.ncoded && (!d.frag_info || !d.tile_slot0 || (d.nslots && !d.coeffs))) return THIP_EFAULT;
+  if (d.ncoded && d.coeff_format == THIP_COEFFS_LEVELS && !d.dequant) return THIP_EFAULT;
+  if (d.flimit < 0 || d.flimit > 127) return THIP_EINVAL;
+  if (d.frame_type != THIP_INTRA_FRAME && d.frame_type != THIP_INTER_FRAME) return THIP_EINVAL;
+  if (d.frame_type == THIP_INTRA_FRAME && d.ncoded != st->nfrags) return THIP_EINVAL;
+  return THIP_OK;
+}
+// ... and with a whole call, checked before anything is launched or any state is advanced: a bad descriptor in stream 11 must
+// not leave streams 0..7 one frame ahead.  launch_chunk checks no descriptor again (the frame check_fault launches a second
+// time was checked when it was first launched).
+static int validate_frames(thip_state *const *states, const thip_frame_desc *descs, int n) {
   for (int i = 0; i < n; i++) {
-    thip_state *st = states[i];
-    const thip_frame_desc &d = descs[i];
-    if (!st) return THIP_EFAULT;
-    if (d.coeff_format != THIP_COEFFS_DEQUANT16 && d.coeff_format != THIP_COEFFS_LEVELS) return THIP_EINVAL;
-    if ((d.coeff_format == THIP_COEFFS_LEVELS) != levels) return THIP_EINVAL;
-    // (nslots counts slots, or units in the levels form: at most two per coded fragment)
-    if (d.ncoded < 0 || d.nslots < 0 || d.nslots > (d.coeff_format == THIP_COEFFS_LEVELS ? 2 : 1) * (int64_t)d.ncoded || d.ncoded > st->nfrags) return THIP_EINVAL;
-    if (d.ncoded && (!d.frag_info || !d.tile_slot0 || (d.nslots && !d.coeffs))) return THIP_EFAULT;
-    if (d.ncoded && d.coeff_format == THIP_COEFFS_LEVELS && !d.dequant) return THIP_EFAULT;
-    if (d.flimit < 0 || d.flimit > 127) return THIP_EINVAL;
-    if (d.frame_type != THIP_INTRA_FRAME && d.frame_type != THIP_INTER_FRAME) return THIP_EINVAL;
-    if (d.frame_type == THIP_INTRA_FRAME && d.ncoded != st->nfrags) return THIP_EINVAL;
-    // a state whose previous frame went down another stream (frame calls and enqueue calls mixed): this one waits for it
-    {
-      const int orc = order_behind_previous(st, s);
-      if (orc < 0) return orc;
-    }
-    // decode.c:2757-2762: an inter frame without references decodes against mid-grey
-    if (d.frame_type != THIP_INTRA_FRAME &&
-        (st->ref_idx[THIP_FRAME_GOLD] < 0 || st->ref_idx[THIP_FRAME_PREV] < 0)) {
-      HIP_TRY(hipMemsetAsync(st->frames[0], 0x80, st->frame_bytes, s));
-      st->ref_idx[0] = st->ref_idx[1] = st->ref_idx[2] = 0;
-      st->last_decoded = 0;
-      st->last_stream = s;
-      st->order_recorded = 0;
-      st->frame_serial++;
-      st->buf_serial[0] = st->buf_serial[1] = st->buf_serial[2] = -1;
-      st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = st->frame_serial;
-    }
-    if (d.ncoded == 0) {  // decode.c:2764-2772
-      if (results) results[i] = THIP_DUPFRAME;
-      continue;
-    }
-    if (results) results[i] = THIP_OK;
-    st->redo.valid = 0;
-    if (st->redo_owned || THIP_OPT("redo_descs")) {   // (the descriptor points into the state's own buffers, or into buffers the caller keeps still: the frame can be decoded again, check_fault)
-      st->redo.d = d;
-      for (int k = 0; k < 3; k++) st->redo.ring[k] = st->ref_idx[k];
-      st->redo.lf_custom = st->lf_rows_custom;
-      for (int k = 0; k < 3; k++) {
-        st->redo.lf_y0[k] = st->lf_y0[k];
-        st->redo.lf_y1[k] = st->lf_y1[k];
-      }
-      st->redo.flush_flags = st->flush_flags;
-      st->redo.serial = st->frame_serial + 1;
-      st->redo.launch_id = 0;
-      st->redo.valid = 1;
-    }
-    int bufi = 0;  // decode.c:2790-2794
-    while (bufi == st->ref_idx[THIP_FRAME_GOLD] || bufi == st->ref_idx[THIP_FRAME_PREV]) bufi++;
-    st->ref_idx[THIP_FRAME_SELF] = bufi;
-    StreamK &K = B.s[nlive];
-    K.fault = st->fault;
-    K.info = reinterpret_cast<const uint2 *>(d.frag_info);
-    K.coeffs = reinterpret_cast<const int4 *>(d.coeffs);
-    K.tile_slot0 = d.tile_slot0;
-    K.dequant = d.coeff_format == THIP_COEFFS_LEVELS ? reinterpret_cast<const uint4 *>(d.dequant) : nullptr;
-    K.self = st->frames[bufi];
-    K.prev = st->ref_idx[THIP_FRAME_PREV] >= 0 ? st->frames[st->ref_idx[THIP_FRAME_PREV]] : st->frames[bufi];
-    K.gold = st->ref_idx[THIP_FRAME_GOLD] >= 0 ? st->frames[st->ref_idx[THIP_FRAME_GOLD]] : st->frames[bufi];
-    // The flags of this frame go to the half of coded_map that does not hold the previous frame's.
-    // A block that is uncoded now can stay where it is if the destination already holds it: the
-    // buffer was last written two frames ago (the usual rotation between two key frames), the
-    // previous frame is the PREV reference, and the previous frame's flags are at hand to tell that
-    // it did not touch the block (k_recon).  THIP_SKIP_STATIC=0 switches the elision off, 2 applies it to
-    // every frame with an uncoded block (tests).
-    const int skip_static = THIP_OPT("skip_static");
-    const int64_t serial = st->frame_serial + 1;   // of the frame being decoded
-    const int pm = st->map_serial[0] == serial - 1 ? 0 : (st->map_serial[1] == serial - 1 ? 1 : -1);
-    const int cm = pm == 0 ? 1 : 0;
-    K.coded_map = st->coded_map + (size_t)cm * st->nfrags;
-    K.coded_prev = st->coded_map + (size_t)(pm < 0 ? cm : pm) * st->nfrags;
-    // (only when most of the frame is uncoded: the test costs every tile five byte loads per block, and
-    //  with scattered uncoded blocks -- the smooth class, 34 % -- hardly a 64-byte line is saved)
-    K.skip_ok = skip_static && pm >= 0 && ((int64_t)d.ncoded * 2 < st->nfrags || (skip_static == 2 && d.ncoded < st->nfrags)) && serial >= 2 && st->buf_serial[bufi] == serial - 2 &&
-                st->ref_idx[THIP_FRAME_PREV] >= 0 && st->buf_serial[st->ref_idx[THIP_FRAME_PREV]] == serial - 1;
-    st->map_serial[cm] = serial;
-    st->buf_serial[bufi] = serial;
-    st->buf_touched[bufi] = serial;
-    K.flimit2 = 2 * d.flimit;
-    K.debug = THIP_OPT("debug");
-    // a unit for every block of the frame: the first unit of a tile in the whole tile rows of a plane is the plane's first +
-    // 4 nhfrags * its tile row + 64 * its place in the row (StreamK::spec_*)
-    K.spec_on = d.coeff_format == THIP_COEFFS_LEVELS && d.nslots == st->nfrags && d.ncoded == st->nfrags && THIP_OPT("spec_coeffs") != 0;
-    K.spec_last = d.nslots > 0 ? (uint32_t)d.nslots - 1u : 0u;
-    {
-      uint32_t base = 0;
-      for (int pli = 0; pli < 3; pli++) {
-        K.spec_base[pli] = base;
-        K.spec_rows[pli] = st->geom[pli].nvfrags / 4;
-        K.spec_rowunits[pli] = 4 * st->geom[pli].nhfrags;
-        K.spec_tx[pli] = st->tiles.tiles_x[pli];
-        base += (uint32_t)st->geom[pli].nhfrags * (uint32_t)st->geom[pli].nvfrags;
-      }
-    }
-    // flags-first loop filter when at least a tenth of the frame is uncoded (THIP_LF_SPARSE=0/1 forces)
-    const int lf_sparse_env = THIP_OPT("lf_sparse");
-    K.lf_sparse = lf_sparse_env >= 0 ? lf_sparse_env : (int64_t)d.ncoded * 10 < (int64_t)st->nfrags * 9;
-    K.qpx = st->hdec;
-    K.qpy = st->vdec;
-    fill_stream_geom(K, st);
-    for (int pli = 0; pli < 3; pli++) {
-      K.lf_y0[pli] = st->lf_rows_custom ? st->lf_y0[pli] : 0;
-      K.lf_y1[pli] = st->lf_rows_custom ? st->lf_y1[pli] : st->geom[pli].nvfrags;
-    }
-    const int wgs = ((K.tile_end[2] + THIP_RECON_WG_WAVES - 1) / THIP_RECON_WG_WAVES + 7) & ~7;   // 8 XCD bands
-    if (wgs > max_wg) max_wg = wgs;
-    if (d.flimit) {
-      any_lf = 1;
-      const int swg = ((K.cell_end[2] + THIP_LF_WG - 1) / THIP_LF_WG + 7) & ~7;   // 8 XCD bands
-      if (swg > max_seam_wg) max_seam_wg = swg;
-    }
-    if (K.skip_ok) any_skip = 1;
-    live_state[nlive++] = i;
+    const thip_state *st = states[i];
+    const int rc = check_frame(st, descs[i]);
+    if (rc < 0) return rc;
+    if (descs[i].dc_tokens)
+      for (int pli = 0; pli < 3; pli++)
+        if (st->geom[pli].nvfrags > kDcMaxRows) return THIP_EIMPL;
+    for (int j = 0; j < i; j++)
+      if (states[j] == st) return THIP_EINVAL;   // one frame per stream per call
   }
-  if (!nlive) return THIP_OK;
-  // ---- DC un-prediction on the device for the streams that ask for it (decode.c:1392-1500) ----------
+  return THIP_OK;
+}
+
+// One chunk of <= THIP_MAX_BATCH streams on its way through launch_chunk's steps: the streams with something coded are B.s[0 .. nlive),
+// live[j] their place in the caller's arrays.
+struct Chunk {
+  BatchK B;
+  int nlive, live[THIP_MAX_BATCH];
+  int max_wg, max_seam_wg, any_lf, any_skip;
+};
+
+// Step 1, per stream: the grey start, the record for decoding the frame again, the ring slot, the halves of the coded map, skip_ok and
+// the stream's StreamK.  Returns THIP_OK, THIP_DUPFRAME (nothing coded: the stream takes no part in the launch) or an error.
+static int prepare_stream(Chunk &C, thip_state *st, const thip_frame_desc &d, int i, hipStream_t s) {
+  // a state whose previous frame went down another stream (frame calls and enqueue calls mixed): this one waits for it
   {
-    DcBatchK D;
-    memset(&D, 0, sizeof(D));
-    int ndc = 0, max_rows = 0, max_nh = 0;
-    for (int j = 0; j < nlive; j++) {
-      thip_state *st = states[live_state[j]];
-      const thip_frame_desc &d = descs[live_state[j]];
-      if (!d.dc_tokens) continue;
-      if (!st->d_dc) HIP_TRY(hipMalloc((void **)&st->d_dc, sizeof(int16_t) * (size_t)st->nfrags));
-      if (!st->d_dc_ent) HIP_TRY(hipMalloc((void **)&st->d_dc_ent, sizeof(uint4) * (size_t)st->nfrags));
-      const int rows_total = st->geom[0].nvfrags + st->geom[1].nvfrags + st->geom[2].nvfrags;
-      if (!st->d_dc_rowhas) HIP_TRY(hipMalloc((void **)&st->d_dc_rowhas, (size_t)rows_total + 16));
-      B.s[j].dc = st->d_dc;          // k_recon / k_recon_lf take every block's DC from here
-      int row0 = 0;
-      for (int pli = 0; pli < 3; pli++) {
-        const thip_plane_geom &g = st->geom[pli];
-        DcPlaneK &p = D.p[ndc][pli];
-        p.ent = st->d_dc_ent + g.froffset;
-        p.rowhas = st->d_dc_rowhas + row0;
-        row0 += g.nvfrags;
-        max_nh = std::max(max_nh, g.nhfrags);
-        p.in = d.dc_tokens + g.froffset;
-        p.out = st->d_dc + g.froffset;
-        p.flags = st->flush_flags ? st->d_flags + g.froffset : nullptr;
-        p.info = d.frag_info;
-        p.nh = g.nhfrags;
-        p.nv = g.nvfrags;
-        p.tiles_x = st->tiles.tiles_x[pli];
-        p.tile_base = st->tiles.tile_off[pli];
-        if (g.nvfrags > max_rows) max_rows = g.nvfrags;
-      }
-      ndc++;
-    }
-    if (ndc) {
-      // one wave per plane with the rows in flight in LDS (thip_dc.h); planes too large for that -- beyond 4K -- keep the
-      // work-group version that goes through memory
-      int lds = 0;
-      bool fits = true;
-      for (int j = 0; j < ndc && fits; j++)
-        for (int pli = 0; pli < 3 && fits; pli++) {
-          fits = dcw_fits(D.p[j][pli].nh, D.p[j][pli].nv);
-          if (fits) lds = std::max(lds, dcw_layout(D.p[j][pli].nh, D.p[j][pli].nv).bytes);
-        }
-      const int dc_global = THIP_OPT("dc_global");
-      if (fits && !dc_global) {
-        HIP_TRY(set_dynamic_lds(reinterpret_cast<const void *>(k_dc_wave), kDcwLdsMax, 3));
-        hipLaunchKernelGGL(k_dc_prepare, dim3(max_rows, 3, ndc), dim3((max_nh + 63) & ~63), 0, s, D);
-        hipLaunchKernelGGL(k_dc_wave, dim3(3, ndc), dim3(64), (size_t)lds, s, D);
-      } else {
-        hipLaunchKernelGGL(k_dc_unpredict, dim3(3, ndc), dim3((max_rows + 63) & ~63), 0, s, D);
-      }
-      HIP_TRY(hipGetLastError());
+    const int orc = order_behind_previous(st, s);
+    if (orc < 0) return orc;
+  }
+  // decode.c:2757-2762: an inter frame without references decodes against mid-grey
+  if (d.frame_type != THIP_INTRA_FRAME &&
+      (st->ref_idx[THIP_FRAME_GOLD] < 0 || st->ref_idx[THIP_FRAME_PREV] < 0)) {
+    HIP_TRY(hipMemsetAsync(st->frames[0], 0x80, st->frame_bytes, s));
+    st->ref_idx[0] = st->ref_idx[1] = st->ref_idx[2] = 0;
+    st->last_decoded = 0;
+    st->last_stream = s;
+    st->order_recorded = 0;
+    st->frame_serial++;
+    st->buf_serial[0] = st->buf_serial[1] = st->buf_serial[2] = -1;
+    st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = st->frame_serial;
+  }
+  if (d.ncoded == 0) return THIP_DUPFRAME;  // decode.c:2764-2772
+  st->redo.valid = 0;
+  if (st->redo_owned || THIP_OPT("redo_descs")) {   // (the descriptor points into the state's own buffers, or into buffers the caller keeps still: the frame can be decoded again, check_fault)
+    st->redo.d = d;
+    for (int k = 0; k < 3; k++) st->redo.ring[k] = st->ref_idx[k];
+    st->redo.extras = st->extras;
+    st->redo.serial = st->frame_serial + 1;
+    st->redo.launch_id = 0;
+    st->redo.valid = 1;
+  }
+  int bufi = 0;  // decode.c:2790-2794
+  while (bufi == st->ref_idx[THIP_FRAME_GOLD] || bufi == st->ref_idx[THIP_FRAME_PREV]) bufi++;
+  st->ref_idx[THIP_FRAME_SELF] = bufi;
+  StreamK &K = C.B.s[C.nlive];
+  K.fault = st->fault;
+  K.info = reinterpret_cast<const uint2 *>(d.frag_info);
+  K.coeffs = reinterpret_cast<const int4 *>(d.coeffs);
+  K.tile_slot0 = d.tile_slot0;
+  K.dequant = d.coeff_format == THIP_COEFFS_LEVELS ? reinterpret_cast<const uint4 *>(d.dequant) : nullptr;
+  K.self = st->frames[bufi];
+  K.prev = st->ref_idx[THIP_FRAME_PREV] >= 0 ? st->frames[st->ref_idx[THIP_FRAME_PREV]] : st->frames[bufi];
+  K.gold = st->ref_idx[THIP_FRAME_GOLD] >= 0 ? st->frames[st->ref_idx[THIP_FRAME_GOLD]] : st->frames[bufi];
+  // The flags of this frame go to the half of coded_map that does not hold the previous frame's.
+  // A block that is uncoded now can stay where it is if the destination already holds it: the
+  // buffer was last written two frames ago (the usual rotation between two key frames), the
+  // previous frame is the PREV reference, and the previous frame's flags are at hand to tell that
+  // it did not touch the block (k_recon).  THIP_SKIP_STATIC=0 switches the elision off, 2 applies it to
+  // every frame with an uncoded block (tests).
+  const int skip_static = THIP_OPT("skip_static");
+  const int64_t serial = st->frame_serial + 1;   // of the frame being decoded
+  const int pm = st->map_serial[0] == serial - 1 ? 0 : (st->map_serial[1] == serial - 1 ? 1 : -1);
+  const int cm = pm == 0 ? 1 : 0;
+  K.coded_map = st->coded_map + (size_t)cm * st->nfrags;
+  K.coded_prev = st->coded_map + (size_t)(pm < 0 ? cm : pm) * st->nfrags;
+  // (only when most of the frame is uncoded: the test costs every tile five byte loads per block, and
+  //  with scattered uncoded blocks -- the smooth class, 34 % -- hardly a 64-byte line is saved)
+  K.skip_ok = skip_static && pm >= 0 && ((int64_t)d.ncoded * 2 < st->nfrags || (skip_static == 2 && d.ncoded < st->nfrags)) && serial >= 2 && st->buf_serial[bufi] == serial - 2 &&
+              st->ref_idx[THIP_FRAME_PREV] >= 0 && st->buf_serial[st->ref_idx[THIP_FRAME_PREV]] == serial - 1;
+  st->map_serial[cm] = serial;
+  st->buf_serial[bufi] = serial;
+  st->buf_touched[bufi] = serial;
+  K.flimit2 = 2 * d.flimit;
+  K.debug = THIP_OPT("debug");
+  // a unit for every block of the frame: the first unit of a tile in the whole tile rows of a plane is the plane's first +
+  // 4 nhfrags * its tile row + 64 * its place in the row (StreamK::spec_*)
+  K.spec_on = d.coeff_format == THIP_COEFFS_LEVELS && d.nslots == st->nfrags && d.ncoded == st->nfrags && THIP_OPT("spec_coeffs") != 0;
+  K.spec_last = d.nslots > 0 ? (uint32_t)d.nslots - 1u : 0u;
+  {
+    uint32_t base = 0;
+    for (int pli = 0; pli < 3; pli++) {
+      K.spec_base[pli] = base;
+      K.spec_rows[pli] = st->geom[pli].nvfrags / 4;
+      K.spec_rowunits[pli] = 4 * st->geom[pli].nhfrags;
+      K.spec_tx[pli] = st->tiles.tiles_x[pli];
+      base += (uint32_t)st->geom[pli].nhfrags * (uint32_t)st->geom[pli].nvfrags;
     }
   }
-  // Default (option "fuse" = 3): k_recon_lf, reconstruction and the whole loop filter in one pass (thip_fused.h); 0: the two
-  // passes k_recon + k_loopfilter.  Frames that leave static blocks in place (skip_ok) and frames without a loop filter
-  // always take the two passes, whose first kernel knows how to skip whole tiles.
+  // flags-first loop filter when at least a tenth of the frame is uncoded (THIP_LF_SPARSE=0/1 forces)
+  const int lf_sparse_env = THIP_OPT("lf_sparse");
+  K.lf_sparse = lf_sparse_env >= 0 ? lf_sparse_env : (int64_t)d.ncoded * 10 < (int64_t)st->nfrags * 9;
+  K.qpx = st->hdec;
+  K.qpy = st->vdec;
+  fill_stream_geom(K, st);
+  for (int pli = 0; pli < 3; pli++) {
+    K.lf_y0[pli] = st->extras.lf_rows_custom ? st->extras.lf_y0[pli] : 0;
+    K.lf_y1[pli] = st->extras.lf_rows_custom ? st->extras.lf_y1[pli] : st->geom[pli].nvfrags;
+  }
+  C.max_wg = std::max(C.max_wg, ((K.tile_end[2] + THIP_RECON_WG_WAVES - 1) / THIP_RECON_WG_WAVES + 7) & ~7);   // 8 XCD bands
+  if (d.flimit) {
+    C.any_lf = 1;
+    C.max_seam_wg = std::max(C.max_seam_wg, ((K.cell_end[2] + THIP_LF_WG - 1) / THIP_LF_WG + 7) & ~7);   // 8 XCD bands
+  }
+  if (K.skip_ok) C.any_skip = 1;
+  C.live[C.nlive++] = i;
+  return THIP_OK;
+}
+
+// Step 2: DC un-prediction on the device for the streams that ask for it (decode.c:1392-1500).
+static int unpredict_dc(Chunk &C, thip_state *const *states, const thip_frame_desc *descs, hipStream_t s) {
+  DcBatchK D;
+  memset(&D, 0, sizeof(D));
+  int ndc = 0, max_rows = 0, max_nh = 0;
+  for (int j = 0; j < C.nlive; j++) {
+    thip_state *st = states[C.live[j]];
+    const thip_frame_desc &d = descs[C.live[j]];
+    if (!d.dc_tokens) continue;
+    if (!st->d_dc) HIP_TRY(hipMalloc((void **)&st->d_dc, sizeof(int16_t) * (size_t)st->nfrags));
+    if (!st->d_dc_ent) HIP_TRY(hipMalloc((void **)&st->d_dc_ent, sizeof(uint4) * (size_t)st->nfrags));
+    const int rows_total = st->geom[0].nvfrags + st->geom[1].nvfrags + st->geom[2].nvfrags;
+    if (!st->d_dc_rowhas) HIP_TRY(hipMalloc((void **)&st->d_dc_rowhas, (size_t)rows_total + 16));
+    C.B.s[j].dc = st->d_dc;          // k_recon / k_recon_lf take every block's DC from here
+    int row0 = 0;
+    for (int pli = 0; pli < 3; pli++) {
+      const thip_plane_geom &g = st->geom[pli];
+      DcPlaneK &p = D.p[ndc][pli];
+      p.ent = st->d_dc_ent + g.froffset;
+      p.rowhas = st->d_dc_rowhas + row0;
+      row0 += g.nvfrags;
+      max_nh = std::max(max_nh, g.nhfrags);
+      p.in = d.dc_tokens + g.froffset;
+      p.out = st->d_dc + g.froffset;
+      p.flags = st->extras.flush_flags ? st->d_flags + g.froffset : nullptr;
+      p.info = d.frag_info;
+      p.nh = g.nhfrags;
+      p.nv = g.nvfrags;
+      p.tiles_x = st->tiles.tiles_x[pli];
+      p.tile_base = st->tiles.tile_off[pli];
+      if (g.nvfrags > max_rows) max_rows = g.nvfrags;
+    }
+    ndc++;
+  }
+  if (!ndc) return THIP_OK;
+  // one wave per plane with the rows in flight in LDS (thip_dc.h); planes too large for that -- beyond 4K -- keep the
+  // work-group version that goes through memory
+  int lds = 0;
+  bool fits = true;
+  for (int j = 0; j < ndc && fits; j++)
+    for (int pli = 0; pli < 3 && fits; pli++) {
+      fits = dcw_fits(D.p[j][pli].nh, D.p[j][pli].nv);
+      if (fits) lds = std::max(lds, dcw_layout(D.p[j][pli].nh, D.p[j][pli].nv).bytes);
+    }
+  const int dc_global = THIP_OPT("dc_global");
+  if (fits && !dc_global) {
+    HIP_TRY(set_dynamic_lds(reinterpret_cast<const void *>(k_dc_wave), kDcwLdsMax, 3));
+    hipLaunchKernelGGL(k_dc_prepare, dim3(max_rows, 3, ndc), dim3((max_nh + 63) & ~63), 0, s, D);
+    hipLaunchKernelGGL(k_dc_wave, dim3(3, ndc), dim3(64), (size_t)lds, s, D);
+  } else {
+    hipLaunchKernelGGL(k_dc_unpredict, dim3(3, ndc), dim3((max_rows + 63) & ~63), 0, s, D);
+  }
+  HIP_TRY(hipGetLastError());
+  return THIP_OK;
+}
+
+// The edge records of a fused kernel for one stream: the buffer, allocated and zero-filled with its first use, and the launch's
+// serial number in it (12 bits in a record's flag word, never 0), which with the kernel's tag is the id a failed wait reports.
+static int take_edge_records(thip_state *st, StreamK &K, uint8_t **buf, uint32_t *epoch, size_t bytes, uint32_t tag, hipStream_t s) {
+  if (!*buf) {
+    HIP_TRY(hipMalloc((void **)buf, bytes));
+    HIP_TRY(hipMemsetAsync(*buf, 0, bytes, s));
+  }
+  K.edge = *buf;
+  *epoch = *epoch % 4095u + 1u;
+  K.epoch = *epoch;
+  st->redo.launch_id = K.epoch | tag;
+  return THIP_OK;
+}
+
+// Step 3: the kernels.  Default (option "fuse" = 3): reconstruction and the whole loop filter in one pass (thip_fused.h); 0: the two
+// passes k_recon + k_loopfilter.  Frames that leave static blocks in place (skip_ok) and frames without a loop filter
+// always take the two passes, whose first kernel knows how to skip whole tiles.
+static int launch_recon(Chunk &C, thip_state *const *states, bool levels, bool two_passes, hipStream_t s) {
+  const BatchK &B = C.B;
+  const int nlive = C.nlive;
   const int fuse = two_passes ? 0 : THIP_OPT("fuse");
-  if (fuse == 3 && any_lf && !any_skip && xcd_round_robin(states[live_state[0]]->device)) {
-    // one wave per tile, reconstruction and every filter cell in one pass (thip_fused.h) -- or, for a launch that would leave
-    // the chip empty, one wave per super block (thip_fused_sb.h)
+  if (fuse == 3 && C.any_lf && !C.any_skip && xcd_round_robin(states[C.live[0]]->device)) {
+    // one wave per tile (k_recon_lf) -- or, for a launch that would leave the chip empty, one wave per super block (k_recon_lf_sb,
+    // thip_fused_sb.h)
     int longest = 1, total_tiles = 0;
     for (int j = 0; j < nlive; j++) total_tiles += B.s[j].tile_end[2];
-    const int sb_tiles = THIP_OPT("sb_tiles"), half_tiles = THIP_OPT("half_tiles");
+    const int sb_tiles = THIP_OPT("sb_tiles");
     const bool small = sb_tiles > 0 && total_tiles < sb_tiles;
-    const bool half = !small && half_tiles > 0 && total_tiles < half_tiles;   // two super blocks a wave, two lanes a block (k_recon_lf_h)
     for (int j = 0; j < nlive; j++) {
-      thip_state *st = states[live_state[j]];
-      StreamK &K = B.s[j];
+      thip_state *st = states[C.live[j]];
+      StreamK &K = C.B.s[j];
       if (st->tiles.tiles_y[0] > 4096) return THIP_EIMPL;
       longest = std::max(longest, fill_bands(K, st));
-      if (small) {
-        if (!st->d_edge_sb) {
-          HIP_TRY(hipMalloc((void **)&st->d_edge_sb, (size_t)4 * K.tile_end[2] * Tf4::kRec));
-          HIP_TRY(hipMemsetAsync(st->d_edge_sb, 0, (size_t)4 * K.tile_end[2] * Tf4::kRec, s));
-        }
-        K.edge = st->d_edge_sb;
-        st->edge_epoch_sb = st->edge_epoch_sb % 4095u + 1u;
-        K.epoch = st->edge_epoch_sb;
-        st->redo.launch_id = K.epoch | 0x1000u;
-        continue;
-      }
-      if (half) {
-        if (!st->d_edge_h) {
-          HIP_TRY(hipMalloc((void **)&st->d_edge_h, (size_t)2 * K.tile_end[2] * Tf8::kRec));
-          HIP_TRY(hipMemsetAsync(st->d_edge_h, 0, (size_t)2 * K.tile_end[2] * Tf8::kRec, s));
-        }
-        K.edge = st->d_edge_h;
-        st->edge_epoch_h = st->edge_epoch_h % 4095u + 1u;
-        K.epoch = st->edge_epoch_h;
-        st->redo.launch_id = K.epoch | 0x2000u;
-        continue;
-      }
-      if (!st->d_edge) {
-        HIP_TRY(hipMalloc((void **)&st->d_edge, (size_t)K.tile_end[2] * kTfRec));
-        HIP_TRY(hipMemsetAsync(st->d_edge, 0, (size_t)K.tile_end[2] * kTfRec, s));
-      }
-      K.edge = st->d_edge;
-      st->edge_epoch = st->edge_epoch % 4095u + 1u;   // 12 bits in a record's flag word, never 0
-      K.epoch = st->edge_epoch;
-      st->redo.launch_id = K.epoch;
+      const int rc = small ? take_edge_records(st, K, &st->d_edge_sb, &st->edge_epoch_sb, (size_t)4 * K.tile_end[2] * Tf4::kRec, 0x1000u, s)
+                           : take_edge_records(st, K, &st->d_edge, &st->edge_epoch, (size_t)K.tile_end[2] * kTfRec, 0u, s);
+      if (rc < 0) return rc;
     }
     ScopedTimer t(s, THIP_KERNEL_RECON);
     if (small) {
       if (levels) hipLaunchKernelGGL(k_recon_lf_sb<true>, dim3(8 * longest, nlive), dim3(256), 0, s, B);
       else hipLaunchKernelGGL(k_recon_lf_sb<false>, dim3(8 * longest, nlive), dim3(256), 0, s, B);
-    } else if (half) {
-      if (levels) hipLaunchKernelGGL(k_recon_lf_h<true>, dim3(8 * longest, nlive), dim3(128), 0, s, B);
-      else hipLaunchKernelGGL(k_recon_lf_h<false>, dim3(8 * longest, nlive), dim3(128), 0, s, B);
     } else if (levels) hipLaunchKernelGGL(k_recon_lf<true>, dim3(8 * longest, nlive), dim3(64), 0, s, B);
     else hipLaunchKernelGGL(k_recon_lf<false>, dim3(8 * longest, nlive), dim3(64), 0, s, B);
   } else {
     {
       ScopedTimer t(s, THIP_KERNEL_RECON);
-      if (levels) hipLaunchKernelGGL(k_recon<true>, dim3(max_wg, nlive), dim3(64 * THIP_RECON_WG_WAVES), 0, s, B);
-      else hipLaunchKernelGGL(k_recon<false>, dim3(max_wg, nlive), dim3(64 * THIP_RECON_WG_WAVES), 0, s, B);
+      if (levels) hipLaunchKernelGGL(k_recon<true>, dim3(C.max_wg, nlive), dim3(64 * THIP_RECON_WG_WAVES), 0, s, B);
+      else hipLaunchKernelGGL(k_recon<false>, dim3(C.max_wg, nlive), dim3(64 * THIP_RECON_WG_WAVES), 0, s, B);
     }
-    if (any_lf) {
+    if (C.any_lf) {
       ScopedTimer t(s, THIP_KERNEL_LOOPFILTER);
-      hipLaunchKernelGGL(k_loopfilter, dim3(max_seam_wg, nlive), dim3(THIP_LF_WG), 0, s, B);
+      hipLaunchKernelGGL(k_loopfilter, dim3(C.max_seam_wg, nlive), dim3(THIP_LF_WG), 0, s, B);
     }
   }
   HIP_TRY(hipGetLastError());
-  // decode.c:2947-2962
-  for (int j = 0; j < nlive; j++) {
-    thip_state *st = states[live_state[j]];
+  return THIP_OK;
+}
+
+// Step 4: the reference rings go round (decode.c:2947-2962), the eager output copy, and what follows on another stream waits.
+static int advance_rings(const Chunk &C, thip_state *const *states, const thip_frame_desc *descs, hipStream_t s) {
+  for (int j = 0; j < C.nlive; j++) {
+    thip_state *st = states[C.live[j]];
     const int self = st->ref_idx[THIP_FRAME_SELF];
-    if (descs[live_state[j]].frame_type == THIP_INTRA_FRAME) st->ref_idx[THIP_FRAME_GOLD] = self;
+    if (descs[C.live[j]].frame_type == THIP_INTRA_FRAME) st->ref_idx[THIP_FRAME_GOLD] = self;
     st->ref_idx[THIP_FRAME_PREV] = self;
     st->last_decoded = self;
     st->frame_serial++;
@@ -1389,6 +1388,25 @@ static int launch_chunk(thip_state *const *states, const thip_frame_desc *descs,
     if (orc < 0) return orc;
   }
   return THIP_OK;
+}
+
+// Launch one chunk of <= THIP_MAX_BATCH streams whose descriptors validate_frames has passed.
+static int launch_chunk(thip_state *const *states, const thip_frame_desc *descs, int n, hipStream_t s,
+                        int32_t *results, bool two_passes = false) {
+  Chunk C;
+  memset(&C, 0, sizeof(C));
+  const bool levels = n > 0 && descs[0].coeff_format == THIP_COEFFS_LEVELS;
+  for (int i = 0; i < n; i++) {
+    if ((descs[i].coeff_format == THIP_COEFFS_LEVELS) != levels) return THIP_EINVAL;   // k_recon / k_recon_lf exist once per form: the callers cut chunks where it changes
+    const int rc = prepare_stream(C, states[i], descs[i], i, s);
+    if (rc < 0) return rc;
+    if (results) results[i] = rc;
+  }
+  if (!C.nlive) return THIP_OK;
+  int rc = unpredict_dc(C, states, descs, s);
+  if (rc >= 0) rc = launch_recon(C, states, levels, two_passes, s);
+  if (rc >= 0) rc = advance_rings(C, states, descs, s);
+  return rc;
 }
 
 static int check_fault(thip_state *st) {
@@ -1416,12 +1434,7 @@ static int check_fault(thip_state *st) {
                     "the two passes\n", st->device);
     const thip_frame_desc d = st->redo.d;
     for (int k = 0; k < 3; k++) st->ref_idx[k] = st->redo.ring[k];
-    st->lf_rows_custom = st->redo.lf_custom;
-    for (int k = 0; k < 3; k++) {
-      st->lf_y0[k] = st->redo.lf_y0[k];
-      st->lf_y1[k] = st->redo.lf_y1[k];
-    }
-    st->flush_flags = st->redo.flush_flags;
+    st->extras = st->redo.extras;
     if (st->out_cur >= 0 && st->out_serial == st->frame_serial) st->out_cur ^= 1;   // the wrong picture's host image is the one to overwrite
     hipStream_t s;
     int rc = followup_stream(st, &s);
@@ -1431,8 +1444,7 @@ static int check_fault(thip_state *st) {
     st->redo_owned = 1;
     rc = launch_chunk(&sp, &d, 1, s, &res, true);
     st->redo_owned = 0;
-    st->lf_rows_custom = 0;
-    st->flush_flags = 0;
+    st->extras = FrameExtras();
     if (rc < 0) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if (!(fw[0] | fw[9])) {
@@ -1453,30 +1465,6 @@ extern "C" int thip_state_check_fault(thip_state *st) {
   DeviceGuard dg(st->device);
   if (st->last_stream && is_library_stream(st->device, st->last_stream)) HIP_TRY(hipStreamSynchronize(st->last_stream));
   return check_fault(st);
-}
-
-// What launch_chunk would refuse, checked for the whole call before anything is launched or any
-// state is advanced: a bad descriptor in stream 11 must not leave streams 0..7 one frame ahead.
-static int validate_frames(thip_state *const *states, const thip_frame_desc *descs, int n) {
-  for (int i = 0; i < n; i++) {
-    const thip_state *st = states[i];
-    const thip_frame_desc &d = descs[i];
-    if (!st) return THIP_EFAULT;
-    if (d.coeff_format != THIP_COEFFS_DEQUANT16 && d.coeff_format != THIP_COEFFS_LEVELS) return THIP_EINVAL;
-    // (nslots counts slots, or units in the levels form: at most two per coded fragment)
-    if (d.ncoded < 0 || d.nslots < 0 || d.nslots > (d.coeff_format == THIP_COEFFS_LEVELS ? 2 : 1) * (int64_t)d.ncoded || d.ncoded > st->nfrags) return THIP_EINVAL;
-    if (d.ncoded && (!d.frag_info || !d.tile_slot0 || (d.nslots && !d.coeffs))) return THIP_EFAULT;
-    if (d.ncoded && d.coeff_format == THIP_COEFFS_LEVELS && !d.dequant) return THIP_EFAULT;
-    if (d.flimit < 0 || d.flimit > 127) return THIP_EINVAL;
-    if (d.frame_type != THIP_INTRA_FRAME && d.frame_type != THIP_INTER_FRAME) return THIP_EINVAL;
-    if (d.frame_type == THIP_INTRA_FRAME && d.ncoded != st->nfrags) return THIP_EINVAL;
-    if (d.dc_tokens)
-      for (int pli = 0; pli < 3; pli++)
-        if (st->geom[pli].nvfrags > kDcMaxRows) return THIP_EIMPL;
-    for (int j = 0; j < i; j++)
-      if (states[j] == st) return THIP_EINVAL;   // one frame per stream per call
-  }
-  return THIP_OK;
 }
 
 int thip_decode_frames(thip_state *const *states, const thip_frame_desc *descs, int nstreams,
@@ -1925,64 +1913,6 @@ int thip_frame_begin(thip_state *st, int frame_type) {
   return THIP_OK;
 }
 
-int thip_state_frag_recon(thip_state *st, ptrdiff_t fragi, int pli, int16_t dct_coeffs[128],
-                          int last_zzi, uint16_t dc_quant, int refi, int16_t mv) {
-  if (!st || !dct_coeffs) return THIP_EFAULT;
-  if (!st->enq_active || fragi < 0 || fragi >= st->nfrags || pli < 0 || pli > 2 || refi < 0 || refi > 2 ||
-      last_zzi < 0 || last_zzi > 64 || (int64_t)st->enq_ncoded + st->enq_nuncoded >= st->nfrags)
-    return THIP_EINVAL;
-  const int32_t pos = st->frag_pos[fragi];
-  if (st->h_info[2 * (size_t)pos] & THIP_INFO_CODED) return THIP_EINVAL;   // fragment enqueued twice
-  uint32_t flags = THIP_INFO_CODED | ((uint32_t)refi << THIP_INFO_REFI_SHIFT) |
-                   ((uint32_t)last_zzi << THIP_INFO_LAST_ZZI_SHIFT) |
-                   ((uint32_t)(uint8_t)(mv & 0xFF) << THIP_INFO_MVX_SHIFT) |
-                   ((uint32_t)(uint8_t)((mv >> 8) & 0xFF) << THIP_INFO_MVY_SHIFT);
-  // The DC coefficient travels raw; k_recon applies state.c:967-979 (the rounded DC-only form or the
-  // 16-bit product) with the dc_quant carried in the upper half of command word 1.
-  uint32_t word1 = (uint32_t)dc_quant << 16;
-  if (last_zzi < 2) {
-    flags |= THIP_INFO_DC_ONLY;   // no coefficient slot
-    word1 |= (uint32_t)(uint16_t)dct_coeffs[0];
-  } else {
-    // Slots are handed out in arrival order, which for the reference's caller is coded
-    // order == tile/lane order (decode.c:1530-1586); the kernel re-derives a lane's slot
-    // from the tile's first slot and a prefix count, so arrival must not jump backwards
-    // inside a tile.
-    const int tile = pos / THIP_TILE_FRAGS, lane = pos % THIP_TILE_FRAGS;
-    if (st->enq_tok_slots || st->enq_level_slots) return THIP_EINVAL;   // the frame's coefficient slots come in another form (tokens, levels)
-    if (lane <= st->enq_last_lane[tile]) return THIP_EINVAL;
-    if (st->enq_last_lane[tile] >= 0 && st->enq_last_tile != tile) return THIP_EINVAL;   // a tile's slots must be contiguous
-    // (every refusal is above this line: a refused call leaves the tile bookkeeping as it was)
-    if (st->enq_last_lane[tile] < 0) st->h_slot0[tile] = (uint32_t)st->enq_nslots;
-    st->enq_last_lane[tile] = lane;
-    st->enq_last_tile = tile;
-    st->enq_dense_slots++;
-    const int slot = st->enq_nslots++;
-    // piece q = 2*j+h of the block: columns c = 4h..4h+3 as pairs { x[2j][c], x[2j+1][c] }, i.e. the
-    // low (h = 0) and high (h = 1) halves of rows 2j and 2j+1 interleaved: two shuffles per row pair
-    typedef int16_t v8s __attribute__((vector_size(16)));
-    int16_t *blk = st->h_coeffs + (size_t)(slot >> 6) * (THIP_SLOT_GROUP_BYTES / 2) + (size_t)(slot & 63) * 8;
-    for (int j = 0; j < 4; j++) {
-      v8s a, b;
-      memcpy(&a, dct_coeffs + (2 * j) * 8, 16);
-      memcpy(&b, dct_coeffs + (2 * j + 1) * 8, 16);
-      const v8s lo = __builtin_shufflevector(a, b, 0, 8, 1, 9, 2, 10, 3, 11);
-      const v8s hi = __builtin_shufflevector(a, b, 4, 12, 5, 13, 6, 14, 7, 15);
-      memcpy(blk + (size_t)(2 * j) * 512, &lo, 16);
-      memcpy(blk + (size_t)(2 * j + 1) * 512, &hi, 16);
-    }
-  }
-  if (st->enq_device_dc) {   // the token value: un-predicted on the device at flush
-    st->h_dc[fragi] = dct_coeffs[0];
-    st->h_flags[fragi] = (uint8_t)(1u | (uint32_t)refi << 1);
-  }
-  memset(dct_coeffs, 0, 64 * sizeof(int16_t));   // idct.c:245,276,295
-  st->h_info[2 * (size_t)pos] = flags;
-  st->h_info[2 * (size_t)pos + 1] = word1;
-  st->enq_ncoded++;
-  return THIP_OK;
-}
-
 // the frame's AC dequantisation tables (thip_frame_dequant_table): zig-zag order for k_expand_tokens, slot order for the levels form
 static int ensure_dq_staging(thip_state *st) {
   if (!st->h_dq) {
@@ -2038,25 +1968,31 @@ int thip_frame_dequant_table(thip_state *st, int sel, const uint16_t dequant[64]
   return THIP_OK;
 }
 
-// The levels form of the oc_state_frag_recon slot: dct_coeffs holds the quantised LEVELS as the tokens carry them (natural order,
-// [0] the raw DC as ever), qii = frags[fragi].qii; the frame's tables come through thip_frame_dequant_table and
-// `(ogg_int16_t)(coeff*ac_quant[zzi])` (decode.c:1573) happens in the reconstruction kernel.  64 bytes of staging per block
-// instead of 128 (the kernels read the staging across PCIe); a tile turns wide -- int16 units -- with its first level beyond
-// eight bits, and the units it has been given so far are rewritten in place (tiles arrive contiguously, so nothing lies behind them).
+// A block in natural order -> the eight 16-byte pieces the kernels read.  Piece q = 2*j+h: columns c = 4h..4h+3 as pairs
+// { x[2j][c], x[2j+1][c] }, i.e. the low (h = 0) and high (h = 1) halves of rows 2j and 2j+1 interleaved: two shuffles per row
+// pair.  piece(q): where piece q goes.  (Templates have C++ linkage, also between the C ABI's functions.)
+extern "C++" template <typename Piece>
+static inline void shuffle_block(const int16_t x[64], Piece piece) {
+  typedef int16_t v8s __attribute__((vector_size(16)));
+  for (int j = 0; j < 4; j++) {
+    v8s a, b;
+    memcpy(&a, x + (2 * j) * 8, 16);
+    memcpy(&b, x + (2 * j + 1) * 8, 16);
+    const v8s lo = __builtin_shufflevector(a, b, 0, 8, 1, 9, 2, 10, 3, 11);
+    const v8s hi = __builtin_shufflevector(a, b, 4, 12, 5, 13, 6, 14, 7, 15);
+    memcpy(piece(2 * j), &lo, 16);
+    memcpy(piece(2 * j + 1), &hi, 16);
+  }
+}
+
+// The units of the levels form (thip_state_frag_recon_levels): 64 bytes of staging per block instead of 128 (the kernels read the
+// staging across PCIe); a tile turns wide -- int16 units -- with its first level beyond eight bits, and the units it has been given
+// so far are rewritten in place (tiles arrive contiguously, so nothing lies behind them).
 static inline uint8_t *unit_piece_host(int16_t *base, uint32_t unit, int q) {
   return reinterpret_cast<uint8_t *>(base) + (size_t)(unit >> 6) * THIP_UNIT_GROUP_BYTES + (size_t)q * 1024 + (size_t)(unit & 63) * 16;
 }
 static void pack_wide_block(int16_t *base, uint32_t unit, const int16_t lv[64]) {
-  typedef int16_t v8s __attribute__((vector_size(16)));
-  for (int j = 0; j < 4; j++) {
-    v8s a, b;
-    memcpy(&a, lv + (2 * j) * 8, 16);
-    memcpy(&b, lv + (2 * j + 1) * 8, 16);
-    const v8s lo = __builtin_shufflevector(a, b, 0, 8, 1, 9, 2, 10, 3, 11);
-    const v8s hi = __builtin_shufflevector(a, b, 4, 12, 5, 13, 6, 14, 7, 15);
-    memcpy(unit_piece_host(base, unit + (uint32_t)((2 * j) >> 2), (2 * j) & 3), &lo, 16);
-    memcpy(unit_piece_host(base, unit + (uint32_t)((2 * j + 1) >> 2), (2 * j + 1) & 3), &hi, 16);
-  }
+  shuffle_block(lv, [=](int q) { return unit_piece_host(base, unit + (uint32_t)(q >> 2), q & 3); });
 }
 static void pack_narrow_block(int16_t *base, uint32_t unit, const int16_t lv[64]) {
   typedef int16_t v8s __attribute__((vector_size(16)));
@@ -2083,37 +2019,94 @@ static void unpack_narrow_block(const int16_t *base, uint32_t unit, int16_t lv[6
   }
 }
 
+// The oc_state_frag_recon slot.  Its three entry points differ in the form a slot-owning block's coefficients arrive in and in
+// nothing else: what they share is enqueue_slot.
+enum SlotForm { kSlotDense, kSlotLevels, kSlotTokens };
+struct SlotCall {
+  SlotForm form;
+  ptrdiff_t fragi;
+  int pli, last_zzi;
+  uint16_t dc_quant;
+  int refi;
+  int16_t mv, dc;        // dc: the raw DC, dct_coeffs[0]
+  uint32_t form_flags;   // the form's own field of command word 0 (levels: qii)
+};
+// refuse(): the form's own reasons to refuse a slot-owning block (THIP_OK or the error); stage(tile, tile_first): stages the
+// block's coefficients and takes its slots from enq_nslots.  Every refusal comes before the first write: a refused call leaves the
+// frame as it was (tests/test_gpu_levels.py, test_refused_slot_calls_leave_the_frame_as_it_was).
+extern "C++" template <typename Refuse, typename Stage>
+static inline int enqueue_slot(thip_state *st, const SlotCall &c, Refuse refuse, Stage stage) {
+  if (!st->enq_active || c.fragi < 0 || c.fragi >= st->nfrags || c.pli < 0 || c.pli > 2 || c.refi < 0 || c.refi > 2 ||
+      c.last_zzi < 0 || c.last_zzi > 64 || (int64_t)st->enq_ncoded + st->enq_nuncoded >= st->nfrags)
+    return THIP_EINVAL;
+  const int32_t pos = st->frag_pos[c.fragi];
+  if (st->h_info[2 * (size_t)pos] & THIP_INFO_CODED) return THIP_EINVAL;   // fragment enqueued twice
+  uint32_t flags = THIP_INFO_CODED | ((uint32_t)c.refi << THIP_INFO_REFI_SHIFT) | c.form_flags |
+                   ((uint32_t)c.last_zzi << THIP_INFO_LAST_ZZI_SHIFT) |
+                   ((uint32_t)(uint8_t)(c.mv & 0xFF) << THIP_INFO_MVX_SHIFT) |
+                   ((uint32_t)(uint8_t)((c.mv >> 8) & 0xFF) << THIP_INFO_MVY_SHIFT);
+  // The DC coefficient travels raw; k_recon applies state.c:967-979 (the rounded DC-only form or the
+  // 16-bit product) with the dc_quant carried in the upper half of command word 1.  Its lower half carries the DC of a block
+  // without a slot, and of every block of the levels form.
+  uint32_t word1 = (uint32_t)c.dc_quant << 16;
+  if (c.last_zzi < 2 || c.form == kSlotLevels) word1 |= (uint32_t)(uint16_t)c.dc;
+  if (c.last_zzi < 2) {
+    flags |= THIP_INFO_DC_ONLY;   // no coefficient slot
+  } else {
+    // Slots are handed out in arrival order, which for the reference's caller is coded
+    // order == tile/lane order (decode.c:1530-1586); the kernel re-derives a lane's slot
+    // from the tile's first slot and a prefix count, so arrival must not jump backwards
+    // inside a tile.
+    int *const nform[3] = {&st->enq_dense_slots, &st->enq_level_slots, &st->enq_tok_slots};   // (by SlotForm)
+    const int tile = pos / THIP_TILE_FRAGS, lane = pos % THIP_TILE_FRAGS;
+    const int rc = refuse();
+    if (rc) return rc;
+    for (int f = 0; f < 3; f++)
+      if (f != c.form && *nform[f]) return THIP_EINVAL;   // one form per frame for the blocks that own a coefficient slot
+    if (lane <= st->enq_last_lane[tile]) return THIP_EINVAL;
+    if (st->enq_last_lane[tile] >= 0 && st->enq_last_tile != tile) return THIP_EINVAL;   // a tile's slots must be contiguous
+    // (every refusal is above this line: a refused call leaves the tile bookkeeping as it was)
+    const bool tile_first = st->enq_last_lane[tile] < 0;
+    if (tile_first) st->h_slot0[tile] = (uint32_t)st->enq_nslots;
+    st->enq_last_lane[tile] = lane;
+    st->enq_last_tile = tile;
+    (*nform[c.form])++;
+    stage(tile, tile_first);
+  }
+  if (st->enq_device_dc) {   // the token value: un-predicted on the device at flush
+    st->h_dc[c.fragi] = c.dc;
+    st->h_flags[c.fragi] = (uint8_t)(1u | (uint32_t)c.refi << 1);
+  }
+  st->h_info[2 * (size_t)pos] = flags;
+  st->h_info[2 * (size_t)pos + 1] = word1;
+  st->enq_ncoded++;
+  return THIP_OK;
+}
+
+int thip_state_frag_recon(thip_state *st, ptrdiff_t fragi, int pli, int16_t dct_coeffs[128],
+                          int last_zzi, uint16_t dc_quant, int refi, int16_t mv) {
+  if (!st || !dct_coeffs) return THIP_EFAULT;
+  const SlotCall c = {kSlotDense, fragi, pli, last_zzi, dc_quant, refi, mv, dct_coeffs[0], 0u};
+  const int rc = enqueue_slot(st, c, [] { return THIP_OK; }, [&](int, bool) {
+    const int slot = st->enq_nslots++;
+    int16_t *const blk = st->h_coeffs + (size_t)(slot >> 6) * (THIP_SLOT_GROUP_BYTES / 2) + (size_t)(slot & 63) * 8;
+    shuffle_block(dct_coeffs, [=](int q) { return blk + (size_t)q * 512; });
+  });
+  if (rc == THIP_OK) memset(dct_coeffs, 0, 64 * sizeof(int16_t));   // idct.c:245,276,295
+  return rc;
+}
+
+// The levels form of the slot: dct_coeffs holds the quantised LEVELS as the tokens carry them (natural order, [0] the raw DC as
+// ever), qii = frags[fragi].qii; the frame's tables come through thip_frame_dequant_table and
+// `(ogg_int16_t)(coeff*ac_quant[zzi])` (decode.c:1573) happens in the reconstruction kernel.
 int thip_state_frag_recon_levels(thip_state *st, ptrdiff_t fragi, int pli, int16_t dct_coeffs[128], int last_zzi, uint16_t dc_quant,
                                  int qii, int refi, int16_t mv) {
   if (!st || !dct_coeffs) return THIP_EFAULT;
-  if (!st->enq_active || fragi < 0 || fragi >= st->nfrags || pli < 0 || pli > 2 || refi < 0 || refi > 2 || qii < 0 || qii > 2 ||
-      last_zzi < 0 || last_zzi > 64 || (int64_t)st->enq_ncoded + st->enq_nuncoded >= st->nfrags)
-    return THIP_EINVAL;
-  const int32_t pos = st->frag_pos[fragi];
-  if (st->h_info[2 * (size_t)pos] & THIP_INFO_CODED) return THIP_EINVAL;   // fragment enqueued twice
-  uint32_t flags = THIP_INFO_CODED | ((uint32_t)refi << THIP_INFO_REFI_SHIFT) | ((uint32_t)qii << THIP_INFO_QII_SHIFT) |
-                   ((uint32_t)last_zzi << THIP_INFO_LAST_ZZI_SHIFT) |
-                   ((uint32_t)(uint8_t)(mv & 0xFF) << THIP_INFO_MVX_SHIFT) |
-                   ((uint32_t)(uint8_t)((mv >> 8) & 0xFF) << THIP_INFO_MVY_SHIFT);
-  const uint32_t word1 = (uint32_t)dc_quant << 16 | (uint32_t)(uint16_t)dct_coeffs[0];   // the raw DC of every block rides here
-  if (last_zzi < 2) {
-    flags |= THIP_INFO_DC_ONLY;   // no unit
-    st->enq_levels_hint = 1;
-  } else {
-    if (st->enq_dense_slots || st->enq_tok_slots) return THIP_EINVAL;   // one form per frame for the blocks that own a slot
-    const int tile = pos / THIP_TILE_FRAGS, lane = pos % THIP_TILE_FRAGS;
-    if (lane <= st->enq_last_lane[tile]) return THIP_EINVAL;
-    if (st->enq_last_lane[tile] >= 0 && st->enq_last_tile != tile) return THIP_EINVAL;   // a tile's units must be contiguous
-    // (every refusal is above this line)
-    if (st->enq_last_lane[tile] < 0) {
-      st->h_slot0[tile] = (uint32_t)st->enq_nslots;
-      st->enq_tile_blocks = 0;
-    }
-    st->enq_last_lane[tile] = lane;
-    st->enq_last_tile = tile;
-    st->enq_level_slots++;
-    int16_t keep0 = dct_coeffs[0];
-    dct_coeffs[0] = 0;
+  if (qii < 0 || qii > 2) return THIP_EINVAL;
+  const SlotCall c = {kSlotLevels, fragi, pli, last_zzi, dc_quant, refi, mv, dct_coeffs[0], (uint32_t)qii << THIP_INFO_QII_SHIFT};
+  const int rc = enqueue_slot(st, c, [] { return THIP_OK; }, [&](int tile, bool tile_first) {
+    if (tile_first) st->enq_tile_blocks = 0;
+    dct_coeffs[0] = 0;   // (the DC rides in the command word)
     bool big;
     {
       typedef int16_t v8s __attribute__((vector_size(16)));
@@ -2151,67 +2144,34 @@ int thip_state_frag_recon_levels(thip_state *st, ptrdiff_t fragi, int pli, int16
       st->enq_nslots += 1;
     }
     st->enq_tile_blocks++;
-    dct_coeffs[0] = keep0;
-  }
-  if (st->enq_device_dc) {
-    st->h_dc[fragi] = dct_coeffs[0];
-    st->h_flags[fragi] = (uint8_t)(1u | (uint32_t)refi << 1);
-  }
+  });
+  if (rc != THIP_OK) return rc;
+  if (last_zzi < 2) st->enq_levels_hint = 1;   // (no unit: a frame of such blocks alone is in the levels form too)
   memset(dct_coeffs, 0, 64 * sizeof(int16_t));   // idct.c:245,276,295
-  st->h_info[2 * (size_t)pos] = flags;
-  st->h_info[2 * (size_t)pos + 1] = word1;
-  st->enq_ncoded++;
   return THIP_OK;
 }
 
 int thip_state_frag_recon_tokens(thip_state *st, ptrdiff_t fragi, int pli, const uint32_t *toks, int ntoks, int16_t dc,
                                  int last_zzi, uint16_t dc_quant, int dqsel, int refi, int16_t mv) {
   if (!st || (!toks && ntoks)) return THIP_EFAULT;
-  if (!st->enq_active || fragi < 0 || fragi >= st->nfrags || pli < 0 || pli > 2 || refi < 0 || refi > 2 ||
-      last_zzi < 0 || last_zzi > 64 || ntoks < 0 || ntoks > 63 || dqsel < 0 || dqsel >= 18 ||
-      (int64_t)st->enq_ncoded + st->enq_nuncoded >= st->nfrags)
-    return THIP_EINVAL;
-  const int32_t pos = st->frag_pos[fragi];
-  if (st->h_info[2 * (size_t)pos] & THIP_INFO_CODED) return THIP_EINVAL;   // fragment enqueued twice
-  uint32_t flags = THIP_INFO_CODED | ((uint32_t)refi << THIP_INFO_REFI_SHIFT) |
-                   ((uint32_t)last_zzi << THIP_INFO_LAST_ZZI_SHIFT) |
-                   ((uint32_t)(uint8_t)(mv & 0xFF) << THIP_INFO_MVX_SHIFT) |
-                   ((uint32_t)(uint8_t)((mv >> 8) & 0xFF) << THIP_INFO_MVY_SHIFT);
-  uint32_t word1 = (uint32_t)dc_quant << 16;
-  if (last_zzi < 2) {
-    flags |= THIP_INFO_DC_ONLY;
-    word1 |= (uint32_t)(uint16_t)dc;
-  } else {
+  if (ntoks < 0 || ntoks > 63 || dqsel < 0 || dqsel >= 18) return THIP_EINVAL;
+  const SlotCall c = {kSlotTokens, fragi, pli, last_zzi, dc_quant, refi, mv, dc, 0u};
+  return enqueue_slot(st, c, [&]() -> int {
     if (!st->tok_ready) {
       DeviceGuard dg(st->device);
       const int rc = ensure_token_staging(st);
       if (rc) return rc;
     }
-    if (st->enq_dense_slots || st->enq_level_slots) return THIP_EINVAL;   // (see thip_state_frag_recon: one form per frame for the blocks that own a coefficient slot)
-    if ((size_t)st->enq_ntok + (size_t)ntoks + 1 > st->tok_cap) return THIP_EINVAL;   // more tokens than the frame has coefficients
-    const int tile = pos / THIP_TILE_FRAGS, lane = pos % THIP_TILE_FRAGS;
-    if (lane <= st->enq_last_lane[tile]) return THIP_EINVAL;
-    if (st->enq_last_lane[tile] >= 0 && st->enq_last_tile != tile) return THIP_EINVAL;   // a tile's slots must be contiguous
-    if (st->enq_last_lane[tile] < 0) st->h_slot0[tile] = (uint32_t)st->enq_nslots;
-    st->enq_last_lane[tile] = lane;
-    st->enq_last_tile = tile;
+    return (size_t)st->enq_ntok + (size_t)ntoks + 1 > st->tok_cap ? THIP_EINVAL : THIP_OK;   // more tokens than the frame has coefficients
+  }, [&](int, bool) {
     const int slot = st->enq_nslots++;
-    st->enq_tok_slots++;
     uint32_t *t = st->h_tok + st->enq_ntok;
     t[0] = (uint32_t)(uint16_t)dc;                       // position 0: the raw DC
     for (int k = 0; k < ntoks; k++) t[1 + k] = toks[k];
     st->h_slot_tok[2 * (size_t)slot] = (uint32_t)st->enq_ntok;
     st->h_slot_tok[2 * (size_t)slot + 1] = (uint32_t)(ntoks + 1) | (uint32_t)dqsel << 8;
     st->enq_ntok += ntoks + 1;
-  }
-  if (st->enq_device_dc) {
-    st->h_dc[fragi] = dc;
-    st->h_flags[fragi] = (uint8_t)(1u | (uint32_t)refi << 1);
-  }
-  st->h_info[2 * (size_t)pos] = flags;
-  st->h_info[2 * (size_t)pos + 1] = word1;
-  st->enq_ncoded++;
-  return THIP_OK;
+  });
 }
 
 int thip_frag_copy_list(thip_state *st, const ptrdiff_t *fragis, ptrdiff_t nfragis) {
@@ -2315,20 +2275,19 @@ int thip_frame_flush(thip_state *st) {
     HIP_TRY(hipMemcpyAsync(st->d_dc_in, st->h_dc, sizeof(int16_t) * (size_t)st->nfrags, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(st->d_flags, st->h_flags, (size_t)st->nfrags, hipMemcpyHostToDevice, s));
     d.dc_tokens = st->d_dc_in;
-    st->flush_flags = 1;
+    st->extras.flush_flags = 1;
   }
-  st->lf_rows_custom = st->enq_lf_any;
+  st->extras.lf_rows_custom = st->enq_lf_any;
   for (int p = 0; p < 3; p++) {
-    st->lf_y0[p] = st->enq_lf_y1[p] < 0 ? 0 : st->enq_lf_y0[p];
-    st->lf_y1[p] = st->enq_lf_y1[p] < 0 ? 0 : st->enq_lf_y1[p];
+    st->extras.lf_y0[p] = st->enq_lf_y1[p] < 0 ? 0 : st->enq_lf_y0[p];
+    st->extras.lf_y1[p] = st->enq_lf_y1[p] < 0 ? 0 : st->enq_lf_y1[p];
   }
   int32_t res = 0;
   thip_state *sp = st;
   st->redo_owned = 1;   // (the descriptor points into this state's staging buffers, intact until the next thip_frame_begin)
   rc = thip_decode_frames(&sp, &d, 1, (void *)s, &res);
   st->redo_owned = 0;
-  st->lf_rows_custom = 0;
-  st->flush_flags = 0;
+  st->extras = FrameExtras();
   if (rc < 0) return rc;
   if (!st->ev_staging) HIP_TRY(hipEventCreateWithFlags(&st->ev_staging, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(st->ev_staging, s));

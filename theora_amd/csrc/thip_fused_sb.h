@@ -17,22 +17,12 @@
 // chip executes about 1.7 times the instructions of k_recon_lf -- which is why the launch takes this kernel only while its
 // tiles are fewer than two per SIMD (option sb_tiles) -- but three or four waves per SIMD now overlap each other's round trips.
 // LDS: 5 KB per wave (exchange 2 KB | results 2 KB | owner words | the plane's tables), the image over the exchange afterwards.
-//
-// Round 6: the same kernel with TWO super blocks a wave and two lanes a block (k_recon_lf_h; NSB = 2 below: a half tile of 8 x 4
-// blocks, lane 2 b + p owns rows 4p .. 4p + 3 of block b) for launches between the two -- one 1080p stream is 782 tiles on 1 024
-// SIMDs: with a wave per tile every wave runs alone at the single-wave issue rate, with a wave per super block (3 128 waves) the
-// cells' idle lanes and three waves a SIMD eat what the shorter chain gains (DESIGN_HISTORY.md section 5h).  1 564 waves with half
-// the transforms, predictor rows and image rows each, and the cells of 9 x 5 corners on 45 lanes (sb: 25).  Same records, tags,
-// bands and recovery with TfGeom<8>, a buffer and a serial number of its own.  LDS: exchange 4 KB with the results over it
-// (residual_shared's COMPACT form) | owner words | tables: the same 5 KB.
 #pragma once
 
 typedef TfGeom<4> Tf4;
-typedef TfGeom<8> Tf8;
 constexpr int kSbLds = 5120;
 constexpr int kSbTab16 = 4352 / 16;     // the tables: behind the exchange, the results and the 64 owner words
 static_assert(Tf4::kFlagOff + 6 * Tf4::kFlagPitch <= 2048, "the image lives over the exchange area");
-static_assert(Tf8::kFlagOff + 6 * Tf8::kFlagPitch <= 4096, "the image lives over the exchange area");
 
 // Predictor of the NR rows a lane owns (pred_issue / pred_finish of thip_kernels.h for rows y0 .. y0 + NR - 1 of a block)
 template <int NR>
@@ -101,15 +91,13 @@ __device__ __forceinline__ void predn_finish(const PredWinN<NR> &Q, int W, uint2
 // A work group is the four super blocks of a tile, one wave each: the waves never synchronise with each other (the left
 // neighbour's units travel through memory like everybody else's), they only arrive together -- the dispatcher starts some 700
 // work groups a microsecond, and 3 128 single-wave groups for a 1080p frame would spend a third of the frame's time being started.
-// NSB: super blocks a wave takes (1: k_recon_lf_sb, four lanes a block; 2: k_recon_lf_h, two lanes a block).  The work group is the
-// tile: 4 / NSB waves.
-template <bool LEVELS, int NSB>
+template <bool LEVELS>
 __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_sb, const int wave) {
-  constexpr int LPB = 4 / NSB;             // lanes a block
+  constexpr int LPB = 4;                   // lanes a block
   constexpr int NR = 8 / LPB;              // pixel rows a lane
-  constexpr int BW = 4 * NSB;              // blocks across
-  constexpr int RPT = 4 / NSB;             // waves (and records) a tile
-  typedef TfGeom<BW> Tf;
+  constexpr int BW = 4;                    // blocks across
+  constexpr int RPT = 4;                   // waves (and records) a tile
+  typedef Tf4 Tf;
   const StreamK &S = B.s[blockIdx.y];
   const int lane = (int)threadIdx.x & 63;
   const int band = (int)blockIdx.x & 7;
@@ -142,7 +130,7 @@ __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_s
   const int nh = G.nh, nv = G.nv, tiles_x = G.tiles_x;
   const int rel = u - (pli == 0 ? 0 : (pli == 1 ? te0 : te1));
   const int sby = rel / tiles_x, t = rel - sby * tiles_x;
-  const int sbx = 4 * t + NSB * sub;                  // the wave's first super block
+  const int sbx = 4 * t + sub;                        // the wave's super block
   const int tw = RPT * t + sub;                       // ... its number across the plane in units of BW blocks
   const int nsbw = (nh + 3) >> 2;
   if (sbx >= nsbw) return;                            // super blocks past the plane's right edge: nobody waits for them
@@ -158,7 +146,7 @@ __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_s
 #endif
   THIP_TR(tr, 0);
   if (levels) tables_to_lds(dq_p, pli, lane, s_sb, kSbTab16);   // (first: whoever has its command word has the tables)
-  const bool has_left = sbx > 0, row_end = sbx + NSB - 1 >= nsbw - 1;
+  const bool has_left = sbx > 0, row_end = sbx >= nsbw - 1;
   const bool has_up = sby > 0, has_dn = sby < G.tiles_y - 1;
   const bool up_in = has_up && u - tiles_x >= bu0, dn_in = has_dn && u + tiles_x < bu1;
   const bool xb_up = has_up && !up_in;
@@ -177,9 +165,9 @@ __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_s
   }
   THIP_TR(tr, 1);
   const uint64_t mask = __ballot((flags_t & THIP_INFO_CODED) != 0 && (flags_t & THIP_INFO_DC_ONLY) == 0);
-  // ... and this lane's block: b on the Hilbert curves of the wave's super blocks, part p
+  // ... and this lane's block: b on the Hilbert curve of the wave's super block, part p
   const int b = lane / LPB, part = lane % LPB;
-  const int src = 16 * NSB * sub + b;
+  const int src = 16 * sub + b;
   const uint32_t flags = (uint32_t)__shfl((int)flags_t, src), w1 = (uint32_t)__shfl((int)info.y, src);
   uint32_t dcv = (uint32_t)__shfl((int)dcv_t, src);
   if (levels && !dc_p) dcv = 0x10000u | (w1 & 0xFFFFu);
@@ -196,11 +184,11 @@ __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_s
   L.has_coeff = L.coded && !L.dc_only;
   L.x0 = bx * 8;
   L.y0 = by * 8;
-  const uint64_t mask_w = (mask >> (16 * NSB * sub)) & ((1ull << (16 * NSB)) - 1ull);   // the owners among the wave's blocks
+  const uint64_t mask_w = (mask >> (16 * sub)) & 0xFFFFull;   // the owners among the wave's blocks
   const int nown = __popcll(mask_w);
   const uint32_t prefix = (uint32_t)__popcll(mask_w & ((1ull << b) - 1ull));
   CoefForm F = coef_form(slot0w, levels);
-  F.slot0 += (uint32_t)__popcll(mask & ((1ull << (16 * NSB * sub)) - 1ull)) * (F.wide ? 2u : 1u);
+  F.slot0 += (uint32_t)__popcll(mask & ((1ull << (16 * sub)) - 1ull)) * (F.wide ? 2u : 1u);
   uint8_t *const lds = reinterpret_cast<uint8_t *>(s_sb);
   uint32_t *const lds_dw = reinterpret_cast<uint32_t *>(s_sb);
   uint32_t *const meta = lds_dw + 1024;
@@ -220,8 +208,7 @@ __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_s
     predn_issue<NR>(Q, (refi == THIP_FRAME_PREV ? prev : gold) + G.off, G.stride, W, H, L.x0, L.y0 + NR * part, L.coded ? L.flags : 0u, pli != 0 && sqpx,
                     pli != 0 && sqpy);
   if (valid && part == 0) coded_map[G.fro + by * nh + bx] = L.coded ? 1 : 0;
-  // (two lanes a block: the results go where the exchange was -- 4 KB for 32 owners --, the owner words and the tables behind it)
-  if (nown) residual_shared<LPB, NSB == 2, 4 * NR>(Wc, F, lds_dw, meta, lane, L, prefix, Y, kSbTab16);
+  if (nown) residual_shared<LPB, false, 4 * NR>(Wc, F, lds_dw, meta, lane, L, prefix, Y, kSbTab16);
   if (!L.has_coeff) {
     const uint32_t fill = L.dc_only ? L.dcp : 0u;
 #pragma unroll
@@ -282,7 +269,7 @@ __device__ __forceinline__ void recon_lf_small(const BatchK &B, uint4 *const s_s
   //         columns 28..31, 17 the upper-left one's corner ----------------------------------------------------------------------
   {
     constexpr int kB = Tf::kBotUnits, kR = Tf::kRightUnits;
-    constexpr uint32_t kFaultTag = NSB == 1 ? 0x1000u : 0x2000u;   // (which kernel's serial number a failed wait reports)
+    constexpr uint32_t kFaultTag = 0x1000u;   // (which kernel's serial number a failed wait reports: launch_recon's tag)
     const uint8_t *usrc = nullptr;
     if (lane < kB) {
       if (up_in) usrc = rec_up + Tf::kBot + lane * kTfUnit;
@@ -371,11 +358,5 @@ template <bool LEVELS>
 __global__ __launch_bounds__(256) void k_recon_lf_sb(const BatchK B) {
   __shared__ uint4 s_sb4[4 * (kSbLds / 16)];
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  recon_lf_small<LEVELS, 1>(B, s_sb4 + wave * (kSbLds / 16), wave);
-}
-template <bool LEVELS>
-__global__ __launch_bounds__(128) void k_recon_lf_h(const BatchK B) {
-  __shared__ uint4 s_sb2[2 * (kSbLds / 16)];
-  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  recon_lf_small<LEVELS, 2>(B, s_sb2 + wave * (kSbLds / 16), wave);
+  recon_lf_small<LEVELS>(B, s_sb4 + wave * (kSbLds / 16), wave);
 }
