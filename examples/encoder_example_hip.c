@@ -1,12 +1,13 @@
 /* encoder_example_hip.c -- YUV4MPEG2 in, Ogg/Theora out, through this library's intra-only th_encode_* (include/theoraenc_hip.h)
  * and its Ogg writer (include/thip_ogg.h).
  *
- *   encoder_example_hip [-q quality] [-k keyframe_interval [-m]] [-b delta] [-V kbps] [-o out.ogv] in.y4m
+ *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta] [-V kbps] [-o out.ogv] in.y4m
  *
  * Input: C420jpeg, C420, C420paldv, C420mpeg2 (4:2:0), C422 or C444, any size; no C tag means 4:2:0.  The frame is the picture
  * padded to multiples of 16, the picture region at (0, 0); the picture-size planes go to th_encode_ycbcr_in as they are.  Every
  * frame is a key frame at qi = quality (default 48).  -k: inter frames; -m with it: all eight macro-block modes
- * (TH_ENCCTL_THIP_SET_INTER_MODES: golden-frame prediction, four vectors a macro block).  -b: block-level qi with that delta, 1..31
+ * (TH_ENCCTL_THIP_SET_INTER_MODES: golden-frame prediction, four vectors a macro block); -a with it: a key frame at every scene
+ * cut as well, the interval becoming a maximum (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES with the ratio t, 1..4096; 230 without one).  -b: block-level qi with that delta, 1..31
  * (TH_ENCCTL_THIP_SET_BLOCK_QI).  --device-pack: the packets' token bits are made on the GPU (TH_ENCCTL_THIP_SET_DEVICE_PACK; the
  * same bytes).  -V: bitrate mode at kbps * 1000 bits a second
  * (TH_ENCCTL_SET_BITRATE), as libtheora's encoder_example -V.  Output on stdout without -o.
@@ -59,7 +60,7 @@ static int read_frame(FILE *in, unsigned char *buf, size_t bytes) {
 }
 
 int main(int argc, char **argv) {
-  int quality = 48, kf = 0, all_modes = 0, bqi = 0, device_pack = 0;
+  int quality = 48, kf = 0, all_modes = 0, bqi = 0, device_pack = 0, auto_kf = 0;
   long kbps = 0;
   const char *in_path = NULL, *out_path = NULL;
   for (int i = 1; i < argc; i++) {
@@ -68,12 +69,13 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[i], "-k") == 0 && i + 1 < argc) kf = atoi(argv[++i]);
     else if (strcmp(argv[i], "-V") == 0 && i + 1 < argc) kbps = atol(argv[++i]);
     else if (strcmp(argv[i], "-m") == 0) all_modes = 1;
+    else if (strcmp(argv[i], "-a") == 0) auto_kf = i + 2 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' ? atoi(argv[++i]) : 230;
     else if (strcmp(argv[i], "-b") == 0 && i + 1 < argc) bqi = atoi(argv[++i]);
     else if (strcmp(argv[i], "--device-pack") == 0) device_pack = 1;
     else in_path = argv[i];
   }
-  if (!in_path || (all_modes && kf <= 0)) {
-    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes]] [-b delta: block qi] [--device-pack] [-V kbps] [-o out.ogv] in.y4m\n", argv[0]);
+  if (!in_path || ((all_modes || auto_kf) && kf <= 0)) {
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi] [--device-pack] [-V kbps] [-o out.ogv] in.y4m\n", argv[0]);
     return 1;
   }
   FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
@@ -121,6 +123,10 @@ int main(int argc, char **argv) {
     }
     if (all_modes && th_encode_ctl(enc, TH_ENCCTL_THIP_SET_INTER_MODES, &all_modes, sizeof(all_modes))) {
       fprintf(stderr, "all modes refused\n");
+      return 1;
+    }
+    if (auto_kf && th_encode_ctl(enc, TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES, &auto_kf, sizeof(auto_kf))) {
+      fprintf(stderr, "automatic key frames refused (ratio 1..4096)\n");
       return 1;
     }
   }

@@ -142,9 +142,32 @@
  *     with the new D.
  *   - The wait: in bitrate mode th_encode_ycbcr_in and TH_ENCCTL_THIP_YCBCR_IN_DEVICE queue the probe, wait on the host for its
  *     512 bytes, choose, and then queue the frame's launches at the chosen qi exactly as quality mode does at that qi (with inter
- *     frames, its own motion search with that qi's lambda).  Quality mode never waits.
+ *     frames, its own motion search with that qi's lambda).  Quality mode never waits, except for a frame measured for an automatic key frame
+ *     ("Automatic key frames" below).
  *   - With all eight modes on, the probe is unchanged (E[q] models the five modes above); the frame is coded with the eight-mode
  *     search at the chosen qi, and c_inter absorbs the difference.
+ *
+ * Automatic key frames (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES with a ratio t in 1..4096), stated so that a restatement reproduces every
+ * choice (tests/enc_cut_ref.py does).  The interval N of "Inter frames" becomes a maximum: a frame that prediction no longer serves
+ * starts a new key frame.  Off (t = 0, the default), every packet is as without the call.  The headers do not change.
+ *   - When a frame is measured: when it is not a duplicate and the interval rule of "Inter frames" makes it an inter frame.  A frame
+ *     that rule makes a key frame is not measured; with inter frames off no frame is.
+ *   - What is measured: per macro block, against PREV, S0, Smv and SI of the five-mode search of "Inter frames" (this search also
+ *     with all eight modes on).  Over all nmbs macro blocks of the frame, in 64-bit integers: P = sum min(S0, Smv), I = sum SI,
+ *     N = the macro blocks with SI < min(S0, Smv).  N is reported only.
+ *   - Decision: the frame is a key frame when 256 P >= t I and P >= 4 * 256 nmbs.  The second condition is a mean absolute
+ *     prediction error of at least 4 levels a luma pixel: it keeps flat, noisy pictures (P about I, both small) from turning into
+ *     all-key streams.  Neither depends on qi, so quality mode and bitrate mode decide alike.  Recommended t: 230 (P / I >= 0.9).
+ *   - A cut key frame is a key frame in every respect: its granule, GOLD, the interval (it restarts from the frame),
+ *     thip_enc_inter_stats.key, thip_enc_rate_stats.key.
+ *   - Bitrate mode: the decision precedes the probe, which is then the key or the inter probe accordingly; the controller's key
+ *     position for Future(q) is the frame itself, as for an interval key frame.  The drop rule is unchanged, and a dropped frame is
+ *     not a key frame whatever was measured (thip_enc_cut_stats.cut is 0 for it).
+ *   - The wait: a measured frame waits on the host for 32 bytes (P, I, N) before its launches are queued, in th_encode_ycbcr_in or
+ *     TH_ENCCTL_THIP_YCBCR_IN_DEVICE.  A measured frame that stays an inter frame is coded from the statistics already on the
+ *     device where they determine it: with five modes its macro-block words follow from them and the frame's lambda (one search
+ *     a frame, in bitrate mode too, whose inter probe also reads them); with all eight modes the eight-mode search runs as
+ *     always and the measurement is an extra search.
  *
  * Device packetiser (TH_ENCCTL_THIP_SET_DEVICE_PACK).  By default the host makes the token part of a packet: it reads the frame's
  * tokens back, merges the EOB runs, chooses the four Huffman tables and writes the bits.  With the packetiser on, the device does
@@ -201,7 +224,8 @@ extern "C" {
    (TH_ENCCTL_THIP_GET_DEVICE) and of the same sizes (frame or picture).  `stream` is a hipStream_t (NULL: the null stream): the
    encoder reads the planes only after the work queued on that stream so far, and the work queued on it afterwards runs only after
    the encoder has read them -- so the caller may write the buffers again from that stream at once (thip_picture_out's
-   ordering, in the other direction).  The call does not wait on the host (in bitrate mode it waits for the rate probe). */
+   ordering, in the other direction).  The call does not wait on the host (in bitrate mode it waits for the rate probe, with automatic
+   key frames on for a measured frame's 32 bytes). */
 #define TH_ENCCTL_THIP_YCBCR_IN_DEVICE (0x7201)
 typedef struct thip_enc_device_in {
   th_img_plane planes[3];
@@ -283,6 +307,23 @@ typedef struct thip_enc_pack_stats {
   int32_t fallbacks;       /* frames of this context whose bits exceeded the device buffer and were packed by the host */
   int32_t reserved;
 } thip_enc_pack_stats;
+/* Extension: buf = int t: 0 off (the default: every packet as without the call), 1..4096 automatic key frames with the ratio t / 256
+   ("Automatic key frames" above; recommended 230); any other value TH_EINVAL.  Before the first frame only (else TH_EINVAL); the
+   call never touches the GPU.  Accepted with inter frames off, where it has no effect. */
+#define TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES (0x720F)
+/* Extension: buf = thip_enc_cut_stats, describing the last packet th_encode_packetout returned (with the switch off too).  For a frame
+   that was not measured -- a key frame by the interval rule, a duplicate, any frame with the switch off -- every field is 0 except
+   ratio. */
+#define TH_ENCCTL_THIP_GET_CUT_STATS (0x7210)
+typedef struct thip_enc_cut_stats {
+  int32_t measured;   /* 1: the frame was measured */
+  int32_t cut;        /* 1: the measurement made it a key frame */
+  int32_t intra_mbs;  /* N */
+  int32_t ratio;      /* t in force (0: off) */
+  int64_t pred;       /* P */
+  int64_t intra;      /* I */
+  double measure_ms;  /* HIP events, from the search's launch to the 32 bytes on the host */
+} thip_enc_cut_stats;
 /* Extension: buf = thip_enc_rate_stats, describing the last packet th_encode_packetout returned; TH_EINVAL outside bitrate mode. */
 #define TH_ENCCTL_THIP_GET_RATE_STATS (0x7208)
 typedef struct thip_enc_rate_stats {

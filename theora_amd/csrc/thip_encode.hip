@@ -31,6 +31,7 @@
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_pack.h"
+#include "thip_encode_cut.h"
 #include "thip_bitstream.h"
 #include "thip_ctx.h"
 #include "thip_device_guard.h"
@@ -287,6 +288,12 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   PackRec *d_prec = nullptr, *h_prec = nullptr;
   hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_q0 = nullptr, ev_q1 = nullptr;
   thip_enc_pack_stats pstats;
+  // automatic key frames (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES; thip_encode_cut.h): the ratio t (0 off); the measurement of the frame
+  // queued (cnext) becomes the last packet's (cstats) in th_encode_packetout
+  int auto_kf = 0;
+  CutSums *d_cut = nullptr, *h_cut = nullptr;
+  hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
+  thip_enc_cut_stats cnext, cstats;
   // output: pkt_data is pkt's (the host packer, empty packets) or h_pk (the device packetiser)
   const uint8_t *pkt_data = nullptr;
   size_t pkt_size = 0;
@@ -346,6 +353,8 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->bstats, 0, sizeof(e->bstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
   memset(&e->pstats, 0, sizeof(e->pstats));
+  memset(&e->cnext, 0, sizeof(e->cnext));
+  memset(&e->cstats, 0, sizeof(e->cstats));
   e->dpack = thip_option("enc_device_pack") != 0;
   e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
@@ -372,7 +381,8 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
-      (void **)&e->d_pgbase, (void **)&e->d_prec};                                                                   // enc_pack_alloc
+      (void **)&e->d_pgbase, (void **)&e->d_prec,                                                                    // enc_pack_alloc
+      (void **)&e->d_cut};                                                                                           // enc_cut_alloc
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
@@ -382,7 +392,8 @@ static void enc_free_device(th_enc_ctx *e) {
                    (void **)&e->h_mb4,                                            // enc_modes_alloc
                    (void **)&e->h_qii,                                            // enc_bqi_prepare
                    (void **)&e->h_rest,                                           // enc_rate_alloc
-                   (void **)&e->h_pk, (void **)&e->h_prec};                       // enc_pack_alloc
+                   (void **)&e->h_pk, (void **)&e->h_prec,                        // enc_pack_alloc
+                   (void **)&e->h_cut};                                           // enc_cut_alloc
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -391,7 +402,8 @@ static void enc_free_device(th_enc_ctx *e) {
   e->pkt_data = nullptr;   // (it may have been h_pk)
   e->pkt_size = 0;
   e->rate_dev = false;
-  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1}) {
+  for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
+                          &e->ev_c0, &e->ev_c1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -632,16 +644,23 @@ static int enc_modes_alloc(th_enc_ctx *e) {
 }
 
 // The launches of an inter frame, written once for its two sets of kernels: the search, the two quantising kernels and the DC
-// kernel of one macro-block word (d_mb), with `classes` reference classes; gold: GOLD for the kernels that read it, else nothing
+// kernel of one macro-block word (d_mb), with `classes` reference classes; gold: GOLD for the kernels that read it, else nothing.
+// stats: k_rate_me's words of this frame where the measurement of thip_encode_cut.h left them and d_mb follows from them (five
+// modes) -- k_enc_mb_modes then stands in for the search --, else nullptr
 extern "C++" template <class Me, class Fq, class FqBqi, class Dc, class Word, class... Gold>
 static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, Me k_me, Fq k_fq, FqBqi k_fq_bqi, Dc k_dc,
-                            int classes, Word *d_mb, const EncRef &R, const Gold &...gold) {
+                            int classes, Word *d_mb, const uint4 *stats, const EncRef &R, const Gold &...gold) {
   const int64_t n = e->nfrags;
   const int lambda = e->lambda[e->frame_qi];
   const dim3 gfq((unsigned)((4 * n + 255) / 256)), gch((unsigned)e->nchunks), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
-  hipLaunchKernelGGL(k_me, dim3((unsigned)e->nmbs), wg, 0, e->stream, d_mb, g, R, gold..., e->nmbx, lambda);
+  if constexpr (sizeof(Word) == sizeof(uint32_t)) {
+    if (stats) hipLaunchKernelGGL(k_enc_mb_modes, dim3((unsigned)((e->nmbs + 255) / 256)), wg, 0, e->stream, d_mb, stats, e->nmbs, lambda);
+    else hipLaunchKernelGGL(k_me, dim3((unsigned)e->nmbs), wg, 0, e->stream, d_mb, g, R, gold..., e->nmbx, lambda);
+  } else {
+    hipLaunchKernelGGL(k_me, dim3((unsigned)e->nmbs), wg, 0, e->stream, d_mb, g, R, gold..., e->nmbx, lambda);
+  }
   ENC_TRY(hipGetLastError());
   if (e->bqi)
     hipLaunchKernelGGL(k_fq_bqi, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
@@ -661,13 +680,13 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
 
 // an inter frame against the reconstruction of the previous frame (thip_encode_inter.h), with all eight modes against the last
 // key frame's too (thip_encode_modes.h)
-static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel) {
+static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, const uint4 *stats) {
   EncRef R, G;
   if (enc_ref_frame(e, R)) return TH_EFAULT;
   if (!e->modes)
-    return enc_launch_inter(e, g, sel, k_enc_me, k_enc_inter_fq, k_enc_inter_fq_bqi, k_enc_inter_dc, 2, e->d_mb, R);
+    return enc_launch_inter(e, g, sel, k_enc_me, k_enc_inter_fq, k_enc_inter_fq_bqi, k_enc_inter_dc, 2, e->d_mb, stats, R);
   if (enc_ref_frame(e, G, THIP_FRAME_GOLD) || enc_modes_alloc(e)) return TH_EFAULT;
-  return enc_launch_inter(e, g, sel, k_enc_me_all, k_enc_inter_fq_all, k_enc_inter_fq_all_bqi, k_enc_inter_dc3, 3, e->d_mb4, R, G);
+  return enc_launch_inter(e, g, sel, k_enc_me_all, k_enc_inter_fq_all, k_enc_inter_fq_all_bqi, k_enc_inter_dc3, 3, e->d_mb4, nullptr, R, G);
 }
 
 // ---- bitrate mode -----------------------------------------------------------------------------------------------------------
@@ -684,7 +703,7 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   ENC_TRY(hipMalloc((void **)&e->d_qdc, (size_t)n * 64 * 2));
   ENC_TRY(hipMalloc((void **)&e->d_rcoded, (size_t)n * 8));
   ENC_TRY(hipMalloc((void **)&e->d_rcls, (size_t)n * 8));
-  ENC_TRY(hipMalloc((void **)&e->d_rmbs, (size_t)std::max(e->nmbs, 1) * sizeof(uint4)));
+  if (!e->d_rmbs) ENC_TRY(hipMalloc((void **)&e->d_rmbs, (size_t)std::max(e->nmbs, 1) * sizeof(uint4)));   // (enc_cut_alloc's, else)
   ENC_TRY(hipMalloc((void **)&e->d_rtab, 6 * 64 * 64 * sizeof(uint2)));
   ENC_TRY(hipMalloc((void **)&e->d_rlam, 64 * sizeof(int)));
   ENC_TRY(hipMalloc((void **)&e->d_rlens, 80 * 32));
@@ -707,8 +726,9 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   return 0;
 }
 
-// E[0..63] of the frame about to be coded (thip_rate.h) into e->rE: queued on the encoder's stream behind its input, waited for
-static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key) {
+// E[0..63] of the frame about to be coded (thip_rate.h) into e->rE: queued on the encoder's stream behind its input, waited for.
+// searched: d_rmbs holds k_rate_me's words of this frame already (enc_cut_measure)
+static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key, bool searched) {
   const int64_t n = e->nfrags;
   RateArgs a;
   a.coef = e->d_coef;
@@ -731,8 +751,10 @@ static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key) {
   } else {
     EncRef R;
     if (enc_ref_frame(e, R)) return TH_EFAULT;
-    hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
-    ENC_TRY(hipGetLastError());
+    if (!searched) {
+      hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
+      ENC_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_rate_fdct_inter, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, R, (const uint4 *)e->d_rmbs, e->nmbx, n);
     ENC_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_rate_dc<true>, dim3(gw), dim3(256), 0, e->stream, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n);
@@ -858,6 +880,45 @@ static void enc_rate_dup(th_enc_ctx *e) {
   r.probe_ms = r.control_ms = 0;
 }
 
+// ---- automatic key frames (thip_encode_cut.h) ---------------------------------------------------------------------------------------
+// the measurement's buffers, at the first frame measured: TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES never touches the GPU
+static int enc_cut_alloc(th_enc_ctx *e) {
+  if (e->d_cut) return 0;
+  for (hipEvent_t *ev : {&e->ev_c0, &e->ev_c1})
+    if (!*ev) ENC_TRY(hipEventCreate(ev));
+  if (!e->d_rmbs) ENC_TRY(hipMalloc((void **)&e->d_rmbs, (size_t)std::max(e->nmbs, 1) * sizeof(uint4)));   // (enc_rate_alloc's, else)
+  if (!e->h_cut) ENC_TRY(hipHostMalloc((void **)&e->h_cut, sizeof(CutSums), hipHostMallocDefault));
+  ENC_TRY(hipMalloc((void **)&e->d_cut, sizeof(CutSums)));
+  return 0;
+}
+
+// P, I and N of the frame about to be coded against PREV into e->cnext, and the decision: queued on the encoder's stream behind its
+// input, waited for.  k_rate_me's words stay in d_rmbs for the frame's own launches and for the probe.
+static int enc_cut_measure(th_enc_ctx *e, const EncPlanes &g) {
+  if (enc_cut_alloc(e)) return TH_EFAULT;
+  EncRef R;
+  if (enc_ref_frame(e, R)) return TH_EFAULT;
+  ENC_TRY(hipEventRecord(e->ev_c0, e->stream));
+  ENC_TRY(hipMemsetAsync(e->d_cut, 0, sizeof(CutSums), e->stream));
+  hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
+  ENC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_enc_cut_sums, dim3((unsigned)((e->nmbs + 255) / 256)), dim3(256), 0, e->stream, e->d_cut, (const uint4 *)e->d_rmbs,
+                     e->nmbs);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(e->h_cut, e->d_cut, sizeof(CutSums), hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_c1, e->stream));
+  ENC_TRY(hipEventSynchronize(e->ev_c1));
+  float ms = 0;
+  thip_enc_cut_stats &c = e->cnext;
+  c.measured = 1;
+  c.pred = (int64_t)e->h_cut->pred;
+  c.intra = (int64_t)e->h_cut->intra;
+  c.intra_mbs = (int32_t)e->h_cut->nintra;
+  c.cut = 256 * c.pred >= (int64_t)e->auto_kf * c.intra && c.pred >= (int64_t)4 * 256 * e->nmbs;
+  c.measure_ms = hipEventElapsedTime(&ms, e->ev_c0, e->ev_c1) == hipSuccess ? ms : 0.0;
+  return 0;
+}
+
 // the four launches of a frame, reading the picture through `src` / `stride` (top-left pixel of the picture of each plane)
 static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int64_t stride[3]) {
   EncPlanes g;
@@ -877,15 +938,26 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
   const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
   e->frame_key = !e->inter || e->key < 0 || off >= e->kf_interval || off + e->dup_next >= full;
+  // automatic key frames: an inter frame by that rule is measured first, and a cut makes it a key frame in every respect
+  memset(&e->cnext, 0, sizeof(e->cnext));
+  e->cnext.ratio = e->auto_kf;
+  bool searched = false;   // d_rmbs holds this frame's search
+  if (e->auto_kf && !e->frame_key) {
+    const int mrc = enc_cut_measure(e, g);
+    if (mrc) return mrc;
+    e->frame_key = e->cnext.cut != 0;
+    searched = !e->frame_key;
+  }
   if (e->rate) {
     // bitrate mode: the probe, then the controller's qi -- or a dropped frame, a zero-byte packet with nothing more queued
     if (enc_rate_alloc(e)) return TH_EFAULT;
-    const int prc = enc_rate_probe(e, g, e->frame_key);
+    const int prc = enc_rate_probe(e, g, e->frame_key, searched);
     if (prc) return prc;
     ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the launches below record it again)
     const int qi = enc_rate_choose(e, e->frame_key, f, e->frame_key ? f : e->key);
     if (qi < 0) {
       e->frame_key = false;
+      e->cnext.cut = 0;   // (a dropped frame is not a key frame, whatever was measured)
       e->frame_dpack = false;
       e->rate_dropped = true;
       enc_frame_queued(e);
@@ -895,7 +967,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   }
   BqiSel sel{};
   if (enc_bqi_prepare(e, sel)) return TH_EFAULT;
-  if (!e->frame_key) return enc_queue_inter(e, g, sel);
+  if (!e->frame_key) return enc_queue_inter(e, g, sel, searched ? (const uint4 *)e->d_rmbs : nullptr);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   if (e->bqi)
     hipLaunchKernelGGL(k_enc_intra_fq_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
@@ -1423,6 +1495,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
   if (e->frame_pending && e->rate_dropped) {   // a frame the rate controller dropped: the previous frame again
     e->frame_pending = e->rate_dropped = false;
     ++e->cur;
+    e->cstats = e->cnext;
     e->pkt.clear();
     e->pkt_data = e->pkt.data();
     e->pkt_size = 0;
@@ -1441,6 +1514,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->frame_pending = false;
     const int rc = enc_finish_frame(e);
     if (rc) return rc;
+    e->cstats = e->cnext;
     if (e->frame_key) e->key = e->cur + 1;
     ++e->cur;
     if (e->inter && e->pkt_size) {
@@ -1454,6 +1528,8 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->dups_left--;
     ++e->cur;
     if (e->rate) enc_rate_dup(e);
+    memset(&e->cstats, 0, sizeof(e->cstats));
+    e->cstats.ratio = e->auto_kf;
     e->pkt.clear();
     e->pkt_data = e->pkt.data();
     e->pkt_size = 0;
@@ -1603,6 +1679,19 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->dpack = v != 0;   // (from the next frame on; its buffers are made at the first frame that uses it)
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int t = *(const int *)buf;
+      if (t < 0 || t > 4096) return TH_EINVAL;
+      e->auto_kf = t;   // (its buffers are made at the first frame measured)
+      e->cstats.ratio = t;
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_CUT_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_cut_stats)) return TH_EINVAL;
+      *(thip_enc_cut_stats *)buf = e->cstats;
+      return 0;
     case TH_ENCCTL_THIP_GET_PACK_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_pack_stats)) return TH_EINVAL;
       *(thip_enc_pack_stats *)buf = e->pstats;

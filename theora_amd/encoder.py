@@ -1,7 +1,8 @@
 """Python face of the th_encode_* API exported by libtheora_hip.so (include/theoraenc_hip.h): a Theora encoder whose block work runs
 on the GPU, intra-only by default, with motion-compensated inter frames on request (inter=True; all eight macro-block modes with
 all_modes=True), at a constant quality or in bitrate mode (bitrate=...), with block-level qi on request (block_qi=delta) and the
-packets' token bits made on the GPU on request (device_pack=True)."""
+packets' token bits made on the GPU on request (device_pack=True), and with key frames at scene cuts on request
+(auto_keyframes=True)."""
 import ctypes as C
 
 import numpy as np
@@ -28,6 +29,9 @@ TH_ENCCTL_THIP_SET_BLOCK_QI = 0x720B
 TH_ENCCTL_THIP_GET_BLOCK_QI_STATS = 0x720C
 TH_ENCCTL_THIP_SET_DEVICE_PACK = 0x720D
 TH_ENCCTL_THIP_GET_PACK_STATS = 0x720E
+TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES = 0x720F
+TH_ENCCTL_THIP_GET_CUT_STATS = 0x7210
+AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
 TH_ENCCTL_SET_RATE_FLAGS = 20
 TH_ENCCTL_SET_RATE_BUFFER = 22
 TH_ENCCTL_SET_BITRATE = 30
@@ -71,6 +75,12 @@ class PackStats(C.Structure):
                 ("pack_ms", C.c_double), ("fallbacks", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CutStats(C.Structure):
+    """thip_enc_cut_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("measured", C.c_int32), ("cut", C.c_int32), ("intra_mbs", C.c_int32), ("ratio", C.c_int32), ("pred", C.c_int64),
+                ("intra", C.c_int64), ("measure_ms", C.c_double)]
+
+
 class RateStats(C.Structure):
     """thip_enc_rate_stats (include/theoraenc_hip.h)."""
     _fields_ = [("qi", C.c_int32), ("dropped", C.c_int32), ("key", C.c_int32), ("duplicate", C.c_int32), ("target", C.c_int64),
@@ -103,7 +113,7 @@ class Encoder:
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
-                 block_qi=0, device_pack=None):
+                 block_qi=0, device_pack=None, auto_keyframes=None):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -111,7 +121,10 @@ class Encoder:
         macro-block modes, golden-frame prediction and four vectors a macro block among them (TH_ENCCTL_THIP_SET_INTER_MODES; needs
         inter=True).  block_qi: block-level qi with that delta, 1..31 (TH_ENCCTL_THIP_SET_BLOCK_QI; 0 off).  device_pack: the device
         packetiser on (True) or off (False) through TH_ENCCTL_THIP_SET_DEVICE_PACK -- the packets are the same either way; None (the
-        default) leaves the context as option "enc_device_pack" made it, which is off unless THIP_ENC_DEVICE_PACK says otherwise."""
+        default) leaves the context as option "enc_device_pack" made it, which is off unless THIP_ENC_DEVICE_PACK says otherwise.
+        auto_keyframes: a key frame wherever prediction stops paying, the interval becoming a maximum
+        (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES): True for the recommended ratio AUTO_KEYFRAMES_DEFAULT, or the ratio t itself, 1..4096;
+        None, False or 0 leave it off.  No effect without inter=True."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -146,6 +159,11 @@ class Encoder:
                 raise ValueError("block_qi must be 0..31 (TH_ENCCTL_THIP_SET_BLOCK_QI returned %d)" % rc)
         if device_pack is not None:
             self.set_device_pack(device_pack)
+        self.auto_keyframes = AUTO_KEYFRAMES_DEFAULT if auto_keyframes is True else int(auto_keyframes or 0)
+        if self.auto_keyframes:
+            rc, _ = self.ctl(TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES, self.auto_keyframes)
+            if rc < 0:
+                raise ValueError("auto_keyframes must be True or 1..4096 (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES returned %d)" % rc)
         self.rate_buffer = self.bitrate = None
         if bitrate is not None:
             self.set_bitrate(bitrate)
@@ -287,6 +305,14 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_BLOCK_QI_STATS returned %d" % rc)
         return dict(nqis=s.nqis, qis=list(s.qis), blocks=[list(r) for r in s.blocks], flag_bits=s.flag_bits)
+
+    def cut_stats(self):
+        """TH_ENCCTL_THIP_GET_CUT_STATS of the last packet, as a dict."""
+        s = CutStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_CUT_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_CUT_STATS returned %d" % rc)
+        return {k: getattr(s, k) for k, _ in CutStats._fields_}
 
     def recon(self):
         """TH_ENCCTL_THIP_GET_RECON: the encoder's reconstruction of the last frame (the next one's reference) as three uint8 numpy

@@ -15,7 +15,13 @@ the frame's device stage after it (device_ms) and the whole call (call_ms), next
 With --device-pack each case runs with the device packetiser off and then on (TH_ENCCTL_THIP_SET_DEVICE_PACK), in the same process;
 pack_ms is the packetiser's own device time (TH_ENCCTL_THIP_GET_PACK_STATS), call_spread the (min, max) of the call times.
 
-  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D] [--device-pack] [--json out.json]
+With --auto-keyframes [T] (with --inter or --bitrate) each case runs with automatic key frames off and then on at the ratio T
+(TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES; default 230), in the same process; measure_ms is the measurement's own device time
+(TH_ENCCTL_THIP_GET_CUT_STATS: the search, the sums and the 32 bytes on the host), which device_ms does not include, and cut_frames
+counts the key frames it made (none on the panning sequence).
+
+  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D] [--device-pack]
+                              [--auto-keyframes [T]] [--json out.json]
 """
 import argparse
 import json
@@ -44,6 +50,8 @@ def main():
     ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
     ap.add_argument("--block-qi", type=int, default=0, help="block-level qi with this delta (TH_ENCCTL_THIP_SET_BLOCK_QI)")
     ap.add_argument("--device-pack", action="store_true", help="each case with the device packetiser off, then on")
+    ap.add_argument("--auto-keyframes", type=int, nargs="?", const=230, default=0, metavar="T",
+                    help="with --inter or --bitrate: each case with automatic key frames off, then on at ratio T (default 230)")
     ap.add_argument("--json")
     args = ap.parse_args()
     if args.bitrate:
@@ -105,12 +113,13 @@ def main_inter(args):
         p = pic or (0, 0, w, h)
         frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
                   for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
-        for q, am, dp in [(q, am, dp) for q in (16, 48) for am in ((False, True) if args.all_modes else (False,))
-                          for dp in ((False, True) if args.device_pack else (False,))]:
+        for q, am, dp, ak in [(q, am, dp, ak) for q in (16, 48) for am in ((False, True) if args.all_modes else (False,))
+                              for dp in ((False, True) if args.device_pack else (False,))
+                              for ak in ((0, args.auto_keyframes) if args.auto_keyframes else (0,))]:
             e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi,
-                        device_pack=dp)
+                        device_pack=dp, auto_keyframes=ak)
             hdr = e.header_packets()
-            dev, host, wall, pkts, keys, pack = [], [], [], [], 0, []
+            dev, host, wall, pkts, keys, pack, meas, cuts = [], [], [], [], 0, [], [], 0
             for f in range(n):
                 t0 = time.perf_counter()
                 e.encode(frames[f])
@@ -124,7 +133,9 @@ def main_inter(args):
                     host.append(hm)
                     wall.append((t1 - t0) * 1e3)
                     pack.append(e.pack_stats()["pack_ms"])
+                    meas.append(e.cut_stats()["measure_ms"])
                 keys += key
+                cuts += e.cut_stats()["cut"]
             e.close()
             dec = Decoder(hdr)
             ps = []
@@ -139,6 +150,8 @@ def main_inter(args):
             if args.device_pack:
                 r.update(device_pack=dp, pack_ms=round(float(np.median(pack)), 4),
                          call_spread=[round(float(min(wall)), 4), round(float(max(wall)), 4)])
+            if args.auto_keyframes:
+                r.update(auto_keyframes=ak, measure_ms=round(float(np.median(meas)), 4), cut_frames=cuts)
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
@@ -146,7 +159,7 @@ def main_inter(args):
 
 
 def _timed(e, frames, keep):
-    """Encodes frames; per frame kept by keep(stats dict): (call ms, device ms, rate stats or None)."""
+    """Encodes frames; per frame kept by keep(stats dict): (call ms, device ms, rate stats or None, measure ms)."""
     out = []
     for f, fr in enumerate(frames):
         t0 = time.perf_counter()
@@ -155,7 +168,7 @@ def _timed(e, frames, keep):
         t1 = time.perf_counter()
         st = e.rate_stats() if e.bitrate else None
         if f >= 3 and keep(e, st):
-            out.append(((t1 - t0) * 1e3, e.times()[0], st))
+            out.append(((t1 - t0) * 1e3, e.times()[0], st, e.cut_stats()["measure_ms"]))
     return out
 
 
@@ -169,18 +182,19 @@ def main_bitrate(args):
         p = pic or (0, 0, w, h)
         frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
                   for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
-        for kind in ("key", "inter"):
+        for kind, ak in [("key", 0), ("inter", 0)] + ([("inter", args.auto_keyframes)] if args.auto_keyframes else []):
             inter = kind == "inter"
             want_key = not inter
 
             def keep(e, st):
                 return not st["dropped"] and not st["duplicate"] and bool(st["key"]) == want_key
-            e = Encoder(w, h, 0, 32, pic=pic, inter=inter, keyframe_interval=kf if inter else None, bitrate=args.bitrate)
+            e = Encoder(w, h, 0, 32, pic=pic, inter=inter, keyframe_interval=kf if inter else None, bitrate=args.bitrate,
+                        auto_keyframes=ak)
             e.header_packets()
             rr = _timed(e, frames, keep)
             e.close()
             qi = int(np.median([r[2]["qi"] for r in rr]))
-            e = Encoder(w, h, 0, qi, pic=pic, inter=inter, keyframe_interval=kf if inter else None)
+            e = Encoder(w, h, 0, qi, pic=pic, inter=inter, keyframe_interval=kf if inter else None, auto_keyframes=ak)
             e.header_packets()
             qq = _timed(e, frames, lambda e, st: e.inter_stats()["key"] == want_key)
             e.close()
@@ -188,6 +202,8 @@ def main_bitrate(args):
             r = dict(size=name, frames=kind, bitrate=args.bitrate, qi=qi, n=len(rr), call_ms=med([x[0] for x in rr]),
                      probe_ms=med([x[2]["probe_ms"] for x in rr]), control_ms=med([x[2]["control_ms"] for x in rr]),
                      device_ms=med([x[1] for x in rr]), q_call_ms=med([x[0] for x in qq]), q_device_ms=med([x[1] for x in qq]))
+            if args.auto_keyframes:
+                r.update(auto_keyframes=ak, measure_ms=med([x[3] for x in rr]), q_measure_ms=med([x[3] for x in qq]))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
