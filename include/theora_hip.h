@@ -195,6 +195,59 @@ typedef struct thip_picture_req {
 int thip_picture_out(const thip_picture_req *reqs, int n, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The other direction: an R'G'B' picture in caller DEVICE memory turned into the picture-sized Y'CbCr planes th_encode_ycbcr_in and
+ * TH_ENCCTL_THIP_YCBCR_IN_DEVICE accept (k_picture_in; up to THIP_MAX_BATCH requests a launch, larger calls are chunked).
+ * TH_ENCCTL_THIP_RGB_IN (theoraenc_hip.h) is this conversion in front of the encoder.
+ *
+ * Source.  width x height R'G'B' pixels, 8 bits a component, top row first: THIP_PIC_RGB24 (src[0]: interleaved R, G, B),
+ * THIP_PIC_RGBA32 (src[0]: interleaved R, G, B, A; A is never used) or THIP_PIC_RGB_PLANAR (src[0..2]: planes R, G, B).
+ * THIP_PIC_YCBCR is THIP_EINVAL here.
+ *
+ * Geometry.  The picture sits in a coded frame at (pic_x, pic_y), display coordinates with row 0 at the top, as in th_info; the
+ * offsets affect only how luma pixels pair up into chroma samples.  hdec / vdec follow pixel_fmt as everywhere.  Plane 0 of the
+ * destination is width x height; planes 1 and 2 are the chroma region of spec 4.4, the one the encoder uses: columns
+ * cx0 = pic_x >> hdec, cw = ((pic_x + width + hdec) >> hdec) - cx0, rows cy0 = pic_y >> vdec, ch = ((pic_y + height + vdec) >> vdec)
+ * - cy0.
+ *
+ * Arithmetic.  int32 throughout; >> is an arithmetic shift.  Luma at picture pixel (i, j):
+ *     Y  = 16  + (( 16829*R + 33039*G +  6416*B + 32768) >> 16)
+ * Chroma at sample (i, j) of the chroma region, s = hdec + vdec: the sample covers frame columns (cx0 + i) << hdec up to + hdec
+ * and frame rows (cy0 + j) << vdec up to + vdec; each covered position is brought to picture coordinates (minus pic_x, pic_y) and
+ * clamped to [0, width - 1] x [0, height - 1] -- the nearest picture pixel, the rule the encoder's block kernels apply outside
+ * the picture --; SR, SG, SB are the sums over those 1 << s pixels:
+ *     Cb = 128 + (( -9714*SR - 19070*SG + 28784*SB + (1 << (15 + s))) >> (16 + s))
+ *     Cr = 128 + (( 28784*SR - 24103*SG -  4681*SB + (1 << (15 + s))) >> (16 + s))
+ * One rounding, after the mean: the box mean Theora's centred chroma siting calls for, the counterpart of THIP_CHROMA_LINEAR on
+ * the way out.  There is no other chroma option.
+ * The integers are round(65536 k) of the specification's matrix (offsets 16 / 128, excursions 219 / 224, Kr = 0.299, Kb = 0.114:
+ * the matrix thip_picture_out inverts), with 33039 and -19070 moved by one so that the rows sum exactly to 56284, 0 and 0: grey
+ * stays grey, Y stays in [16, 235] and Cb, Cr in [16, 240] for every input, so nothing is clamped.  Every result is within 0.51 of
+ * the real-valued formula (0.5 of rounding + 3 * 255 * 0.5 / 65536).
+ *
+ * The contract:
+ *   - asynchronous: the call never waits on the host;
+ *   - it runs on the calling thread's current device, on `stream` (a hipStream_t); NULL is that device's null stream;
+ *   - work queued on the stream before the call is seen, and work queued on it after the call sees the result;
+ *   - all or nothing: every request is checked before anything is queued.  THIP_EFAULT: reqs, or a pointer the format uses, is
+ *     NULL.  THIP_EINVAL: n < 0, a bad format or pixel format, width or height < 1 (or, like pic_x and pic_y, beyond 1 << 20),
+ *     negative offsets, a pitch smaller than the row.  n == 0 does nothing and returns THIP_OK.
+ * Sources and destinations may have any alignment and pitch.  No byte outside the width x height pixels of a source is read (a
+ * row's padding included) and none outside the three destination rectangles is written; chunks of 16 pixels that start on
+ * 16 bytes are read with 16-byte loads, rows that start on 16 (chroma at 4:2:0 / 4:2:2: 8) bytes written with whole stores.
+ * ---------------------------------------------------------------------------------- */
+typedef struct thip_picture_in_req {
+  int32_t format;                 /* THIP_PIC_RGB24 / _RGBA32 / _RGB_PLANAR */
+  int32_t pixel_fmt;              /* TH_PF_420 / TH_PF_422 / TH_PF_444 (0, 2, 3): the destination's subsampling */
+  int32_t pic_x, pic_y;           /* where the picture sits in its coded frame (only the parity matters) */
+  int32_t width, height;          /* the picture, >= 1 */
+  const void *src[3];             /* device memory; [0] only for the interleaved formats */
+  int64_t src_pitch[3];
+  void *dst[3];                   /* device memory: plane 0 width x height, planes 1, 2 the chroma region above */
+  int64_t dst_pitch[3];
+} thip_picture_in_req;
+int thip_picture_in(const thip_picture_in_req *reqs, int n, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Work tiles.  The device walks a frame in the reference's CODED ORDER (state.c:123-190):
  * a tile is 4 consecutive super blocks of one super-block row of one plane -- 16x4
  * fragments, 128x32 pixels, one wavefront -- and lane = 16*(super block within the tile) + (position of the

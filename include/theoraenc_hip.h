@@ -179,9 +179,17 @@
  * thip_enc_pack_stats.fallbacks.  The packet th_encode_packetout returns then lies in pinned host memory owned by the context, valid
  * as always until the next call on it.
  *
- * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / TH_ENCCTL_THIP_GET_DEVICE):
+ * R'G'B' input (TH_ENCCTL_THIP_RGB_IN).  The request takes the picture as R'G'B' pixels, in host or in device memory, and does what
+ * th_encode_ycbcr_in does for the picture-sized Y'CbCr planes thip_picture_in makes of them (theora_hip.h states the arithmetic: an
+ * integer matrix, chroma the mean of the 1 << (hdec + vdec) pixels a sample covers with the picture's edge repeated), pic_x, pic_y
+ * and the pixel format taken from the context's th_info.  The conversion runs on the device into an encoder-owned buffer, and every
+ * mode above -- key and inter frames, eight modes, block qi, bitrate mode's probe, the automatic-key-frame measurement, the device
+ * packetiser -- reads the converted planes as it reads any other input: the stream is a function of the R'G'B' bytes alone
+ * (tests/picture_in_ref.py restates the conversion).
+ *
+ * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / _RGB_IN / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
- * extensions, YCBCR_IN_DEVICE and GET_DEVICE do.
+ * extensions, YCBCR_IN_DEVICE, RGB_IN and GET_DEVICE do.
  */
 #ifndef THEORAENC_HIP_H
 #define THEORAENC_HIP_H
@@ -342,6 +350,28 @@ typedef struct thip_enc_rate_stats {
   double probe_ms;         /* the probe's device time (HIP events, from its first launch to its 512 bytes on the host) */
   double control_ms;       /* the host controller's time */
 } thip_enc_rate_stats;
+
+/* Extension: buf = thip_enc_rgb_in.  What th_encode_ycbcr_in does, for a picture given as R'G'B' ("R'G'B' input" above); width and
+   height must be the context's pic_width and pic_height.  TH_EINVAL in the states where th_encode_ycbcr_in returns it (after the
+   last packet, with a frame pending, with duplicates left), for a wrong size, format or `device` value and for a pitch smaller than
+   the row; TH_EFAULT for NULL pointers (buf, or a src the format uses); every check comes before the device is touched.
+   device = 1: src is device memory on the context's GPU (TH_ENCCTL_THIP_GET_DEVICE), `stream` a hipStream_t (NULL: the null
+   stream), ordered like TH_ENCCTL_THIP_YCBCR_IN_DEVICE: the encoder reads the source only after the work queued on that stream so
+   far, and the work queued on it afterwards waits only until the conversion has read the source, not for the frame's block
+   kernels -- the caller may overwrite its picture at once.  The call does not wait on the host (beyond the waits named above for
+   bitrate mode and for measured frames).
+   device = 0: src is host memory; the rows are copied into a pinned staging buffer made at first use (free again under the rule
+   th_encode_ycbcr_in relies on: the previous packet is out), uploaded with one asynchronous copy and converted on the encoder's
+   stream; `stream` is ignored. */
+#define TH_ENCCTL_THIP_RGB_IN (0x7211)
+typedef struct thip_enc_rgb_in {
+  int32_t format;          /* THIP_PIC_RGB24 / _RGBA32 / _RGB_PLANAR (theora_hip.h) */
+  int32_t device;          /* 0: src is host memory; 1: device memory on the context's GPU (TH_ENCCTL_THIP_GET_DEVICE) */
+  int32_t width, height;   /* must be pic_width, pic_height */
+  const void *src[3];      /* [0] only for the interleaved formats */
+  int64_t pitch[3];        /* bytes a row */
+  void *stream;            /* device = 1: a hipStream_t, as in thip_enc_device_in; ignored for device = 0 */
+} thip_enc_rgb_in;
 
 typedef struct th_enc_ctx th_enc_ctx;
 

@@ -360,6 +360,97 @@ def picture_out(states, outs, fmt="rgb", chroma="linear", rects=None, bufis=None
     _lib.check(_on_stream(device, stream, lambda h: L.thip_picture_out(reqs, n, h)), "thip_picture_out")
 
 
+# ---------------------------------------------------------------------------------------
+# R'G'B' pictures in (thip_picture_in)
+# ---------------------------------------------------------------------------------------
+def picture_in_shapes(width, height, pixel_fmt=PF_420, pic_x=0, pic_y=0):
+    """The three plane shapes thip_picture_in writes for a width x height picture at (pic_x, pic_y) of its coded frame: luma
+    (height, width), chroma the region of spec 4.4 (include/theora_hip.h) -- the picture-sized planes Encoder.encode takes."""
+    hdec, vdec = int(not (pixel_fmt & 1)), int(not (pixel_fmt & 2))
+    cw = ((pic_x + width + hdec) >> hdec) - (pic_x >> hdec)
+    ch = ((pic_y + height + vdec) >> vdec) - (pic_y >> vdec)
+    return [(height, width), (ch, cw), (ch, cw)]
+
+
+def _pic_src(fmt, src):
+    """(width, height, pointers, row pitches) of an R'G'B' source: a uint8 device tensor (H, W, 3) for "rgb", (H, W, 4) for
+    "rgba", (3, H, W) or three (H, W) planes for "rgb_planar"; rows may have a pitch of their own, pixels are contiguous."""
+    import torch
+    if fmt == "rgb_planar":
+        planes = list(src) if isinstance(src, (list, tuple)) else [src[0], src[1], src[2]]
+        if len(planes) != 3:
+            raise ValueError("rgb_planar wants three planes")
+    elif fmt in ("rgb", "rgba"):
+        planes = [src]
+    else:
+        raise ValueError("unknown R'G'B' format %r" % (fmt,))
+    want = {"rgb": (3, 3), "rgba": (3, 4), "rgb_planar": (2, 0)}[fmt]
+    ptrs, pitches = [], []
+    for t in planes:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+            raise TypeError("picture sources are uint8 device tensors")
+        if t.dim() != want[0] or (want[1] and t.shape[2] != want[1]) or tuple(t.shape[:2]) != tuple(planes[0].shape[:2]):
+            raise ValueError("a source of shape %s for format %r" % (tuple(t.shape), fmt))
+        if t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("an empty picture")
+        if t.stride(-1) != 1 or (t.dim() == 3 and t.stride(1) != t.shape[2]) or t.stride(0) < t.shape[1] * (t.shape[2] if t.dim() == 3 else 1):
+            raise ValueError("picture sources need contiguous rows (a row pitch of their own is fine)")
+        ptrs.append(t.data_ptr())
+        pitches.append(t.stride(0))
+    while len(ptrs) < 3:
+        ptrs.append(None)
+        pitches.append(0)
+    return planes[0].shape[1], planes[0].shape[0], ptrs, pitches
+
+
+def picture_in(srcs, pixel_fmt, fmt="rgb", pics=None, outs=None, stream=None):
+    """thip_picture_in: the R'G'B' pictures `srcs` (see _pic_src for their shapes; fmt may be a list, one per source, and so may
+    pixel_fmt) as Y'CbCr planes.  pics: per source (pic_x, pic_y), where the picture sits in its coded frame (default (0, 0));
+    outs: per source three uint8 device tensors of picture_in_shapes' shapes (rows may have a pitch of their own), made here
+    when None.  Returns the three planes per source.  Asynchronous on `stream` (default torch.cuda.current_stream of the
+    sources' device)."""
+    import torch
+    L = _lib.load()
+    n = len(srcs)
+    fmts = [fmt] * n if isinstance(fmt, str) else list(fmt)
+    pfs = [pixel_fmt] * n if isinstance(pixel_fmt, int) else list(pixel_fmt)
+    if len(fmts) != n or len(pfs) != n or (outs is not None and len(outs) != n) or (pics is not None and len(pics) != n):
+        raise ValueError("one format, pixel format, offset and destination per source")
+    if n == 0:
+        return []
+    reqs = (_lib.PictureInReq * n)()
+    res, device = [], None
+    for i in range(n):
+        w, h, ptrs, pitches = _pic_src(fmts[i], srcs[i])
+        dev = (srcs[i][0] if isinstance(srcs[i], (list, tuple)) else srcs[i]).device
+        if device is None:
+            device = dev
+        elif dev != device:
+            raise ValueError("all sources of a call live on one device")
+        px, py = pics[i] if pics is not None and pics[i] is not None else (0, 0)
+        shapes = picture_in_shapes(w, h, pfs[i], px, py)
+        if outs is None or outs[i] is None:
+            out = [torch.empty(sh, dtype=torch.uint8, device=device) for sh in shapes]
+        else:
+            out = list(outs[i])
+            for t, sh in zip(out, shapes):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != device:
+                    raise TypeError("picture destinations are uint8 tensors on the sources' device")
+                if tuple(t.shape) != tuple(sh) or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+                    raise ValueError("a destination of shape %s for a plane of %s" % (tuple(t.shape), tuple(sh)))
+        r = reqs[i]
+        r.format, r.pixel_fmt = PIC_FORMATS[fmts[i]], pfs[i]
+        r.pic_x, r.pic_y, r.width, r.height = px, py, w, h
+        for p in range(3):
+            r.src[p], r.src_pitch[p] = ptrs[p], pitches[p]
+            r.dst[p], r.dst_pitch[p] = out[p].data_ptr(), out[p].stride(0)
+        res.append(out)
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.device(device):   # (the call runs on the calling thread's current device)
+        _lib.check(L.thip_picture_in(reqs, n, s.cuda_stream), "thip_picture_in")
+    return res
+
+
 def decode_frames(states, descs, stream=None):
     """thip_decode_frames over parallel lists of State and FrameDesc; returns per-stream results."""
     L = _lib.load()

@@ -52,6 +52,13 @@ class PictureReq(C.Structure):
                 ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3)]
 
 
+class PictureInReq(C.Structure):
+    """thip_picture_in_req (include/theora_hip.h)."""
+    _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3),
+                ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3)]
+
+
 class TheoraHipError(RuntimeError):
     pass
 
@@ -91,6 +98,7 @@ SYMBOLS = [
     ("thip_state_token_lists_staging", _I, [_P, _P]),
     ("thip_state_read_pp_plane", _I, [_P, _I, _P]),
     ("thip_picture_out", _I, [C.POINTER(PictureReq), _I, _P]),
+    ("thip_picture_in", _I, [C.POINTER(PictureInReq), _I, _P]),
     ("thip_decode_frames", _I, [C.POINTER(_P), C.POINTER(FrameDesc), _I, _P, C.POINTER(C.c_int32)]),
     ("thip_synchronize", _I, []),
     ("thip_frame_begin", _I, [_P, _I]),

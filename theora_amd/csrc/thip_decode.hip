@@ -174,6 +174,7 @@ extern "C" const char *thip_option_name(int index, const char **help) {
 #include "thip_postproc.h"
 #include "thip_tokens.h"
 #include "thip_picture.h"
+#include "thip_picture_in.h"
 
 // ---------------------------------------------------------------------------------------
 // host side
@@ -1820,6 +1821,73 @@ int thip_picture_out(const thip_picture_req *reqs, int n, void *stream) {
       const int rc = picture_launch(grp, m, sv[i]);
       if (rc < 0) return rc;
     }
+  }
+  return THIP_OK;
+}
+
+// ---- R'G'B' pictures in (thip_picture_in, k_picture_in in thip_picture_in.h) ------------------------------------------------
+static int picture_in_check(const thip_picture_in_req &q) {
+  if (q.format != THIP_PIC_RGB24 && q.format != THIP_PIC_RGBA32 && q.format != THIP_PIC_RGB_PLANAR) return THIP_EINVAL;
+  const int ns = q.format == THIP_PIC_RGB_PLANAR ? 3 : 1;
+  for (int p = 0; p < ns; p++)
+    if (!q.src[p]) return THIP_EFAULT;
+  for (int p = 0; p < 3; p++)
+    if (!q.dst[p]) return THIP_EFAULT;
+  if (q.pixel_fmt != 0 && q.pixel_fmt != 2 && q.pixel_fmt != 3) return THIP_EINVAL;   // th_pixel_fmt: 4:2:0, 4:2:2, 4:4:4
+  // (1 << 20 is beyond any Theora frame and keeps every offset inside a row within 32 bits)
+  if (q.width < 1 || q.height < 1 || q.width > (1 << 20) || q.height > (1 << 20) || q.pic_x < 0 || q.pic_y < 0 || q.pic_x > (1 << 20) ||
+      q.pic_y > (1 << 20))
+    return THIP_EINVAL;
+  const int hdec = !(q.pixel_fmt & 1), vdec = !(q.pixel_fmt & 2);
+  const int64_t row = q.format == THIP_PIC_RGB24 ? 3 * (int64_t)q.width : q.format == THIP_PIC_RGBA32 ? 4 * (int64_t)q.width : q.width;
+  for (int p = 0; p < ns; p++)
+    if (q.src_pitch[p] < row) return THIP_EINVAL;
+  const int cw = ((q.pic_x + q.width + hdec) >> hdec) - (q.pic_x >> hdec), ch = ((q.pic_y + q.height + vdec) >> vdec) - (q.pic_y >> vdec);
+  if (q.dst_pitch[0] < q.width || q.dst_pitch[1] < cw || q.dst_pitch[2] < cw) return THIP_EINVAL;
+  if ((int64_t)((cw + (hdec ? 7 : 15)) / (hdec ? 8 : 16)) * ch > INT32_MAX - 256) return THIP_EINVAL;   // (the lanes of one request)
+  return THIP_OK;
+}
+
+static void picture_in_fill(PicInReqK &K, const thip_picture_in_req &q) {
+  memset(&K, 0, sizeof(K));
+  K.format = q.format;
+  K.hdec = !(q.pixel_fmt & 1);
+  K.vdec = !(q.pixel_fmt & 2);
+  K.ox = q.pic_x & K.hdec;
+  K.oy = q.pic_y & K.vdec;
+  K.w = q.width;
+  K.h = q.height;
+  K.cw = ((q.pic_x + q.width + K.hdec) >> K.hdec) - (q.pic_x >> K.hdec);
+  K.ch = ((q.pic_y + q.height + K.vdec) >> K.vdec) - (q.pic_y >> K.vdec);
+  K.cpr = K.hdec ? (K.cw + 7) >> 3 : (K.cw + 15) >> 4;
+  K.units = K.cpr * K.ch;
+  for (int p = 0; p < 3; p++) {
+    K.src[p] = (const uint8_t *)q.src[p];
+    K.spitch[p] = q.src_pitch[p];
+    K.dst[p] = (uint8_t *)q.dst[p];
+    K.dpitch[p] = q.dst_pitch[p];
+  }
+}
+
+int thip_picture_in(const thip_picture_in_req *reqs, int n, void *stream) {
+  if (n < 0) return THIP_EINVAL;
+  if (n == 0) return THIP_OK;
+  if (!reqs) return THIP_EFAULT;
+  for (int i = 0; i < n; i++) {   // all or nothing: every request is checked before anything is queued
+    const int rc = picture_in_check(reqs[i]);
+    if (rc < 0) return rc;
+  }
+  for (int i = 0; i < n; i += THIP_MAX_BATCH) {
+    const int m = std::min(THIP_MAX_BATCH, n - i);
+    PicInBatchK B;
+    int max_units = 0;
+    for (int k = 0; k < m; k++) {
+      picture_in_fill(B.r[k], reqs[i + k]);
+      max_units = std::max(max_units, B.r[k].units);
+    }
+    for (int k = m; k < THIP_MAX_BATCH; k++) memset(&B.r[k], 0, sizeof(B.r[k]));
+    hipLaunchKernelGGL(k_picture_in, dim3((unsigned)((max_units + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream, B);
+    HIP_TRY(hipGetLastError());
   }
   return THIP_OK;
 }

@@ -228,6 +228,8 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   hipStream_t stream = nullptr;
   hipEvent_t ev_in = nullptr, ev_read = nullptr, ev_t0 = nullptr, ev_done = nullptr;
   uint8_t *d_pix = nullptr, *h_pix = nullptr;   // host input: the three picture planes, packed
+  uint8_t *d_rgb = nullptr, *h_rgb = nullptr;   // TH_ENCCTL_THIP_RGB_IN from host memory: the picture's rows, packed (4 bytes a pixel)
+  hipEvent_t ev_conv = nullptr;                 // ... from device memory: the conversion has read the caller's picture
   size_t pix_off[3], pix_bytes = 0;
   int32_t *d_order = nullptr;
   uint16_t *d_dequant = nullptr;                // [64 qi][3][64]
@@ -382,7 +384,8 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
       (void **)&e->d_pgbase, (void **)&e->d_prec,                                                                    // enc_pack_alloc
-      (void **)&e->d_cut};                                                                                           // enc_cut_alloc
+      (void **)&e->d_cut,                                                                                            // enc_cut_alloc
+      (void **)&e->d_rgb};                                                                                           // enc_rgb_in
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
@@ -393,7 +396,8 @@ static void enc_free_device(th_enc_ctx *e) {
                    (void **)&e->h_qii,                                            // enc_bqi_prepare
                    (void **)&e->h_rest,                                           // enc_rate_alloc
                    (void **)&e->h_pk, (void **)&e->h_prec,                        // enc_pack_alloc
-                   (void **)&e->h_cut};                                           // enc_cut_alloc
+                   (void **)&e->h_cut,                                            // enc_cut_alloc
+                   (void **)&e->h_rgb};                                           // enc_rgb_in
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -403,7 +407,7 @@ static void enc_free_device(th_enc_ctx *e) {
   e->pkt_size = 0;
   e->rate_dev = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
-                          &e->ev_c0, &e->ev_c1}) {
+                          &e->ev_c0, &e->ev_c1, &e->ev_conv}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -1024,6 +1028,66 @@ static int enc_ycbcr_in_device(th_enc_ctx *e, const thip_enc_device_in *a) {
   if (rc) return rc;
   ENC_TRY(hipStreamWaitEvent(cs, e->ev_read, 0));
   return 0;
+}
+
+// TH_ENCCTL_THIP_RGB_IN: the picture through thip_picture_in into d_pix (picture-sized planes, stride cw[p]), then the frame as ever
+static int enc_rgb_in(th_enc_ctx *e, const thip_enc_rgb_in *a) {
+  if (e->done || e->frame_pending || e->dups_left) return TH_EINVAL;
+  if (a->format != THIP_PIC_RGB24 && a->format != THIP_PIC_RGBA32 && a->format != THIP_PIC_RGB_PLANAR) return TH_EINVAL;
+  if (a->device != 0 && a->device != 1) return TH_EINVAL;
+  if (a->width != (int32_t)e->info.pic_width || a->height != (int32_t)e->info.pic_height) return TH_EINVAL;
+  const int ns = a->format == THIP_PIC_RGB_PLANAR ? 3 : 1;
+  const int64_t row = (int64_t)a->width * (a->format == THIP_PIC_RGB24 ? 3 : a->format == THIP_PIC_RGBA32 ? 4 : 1);
+  for (int p = 0; p < ns; p++)
+    if (!a->src[p]) return TH_EFAULT;
+  for (int p = 0; p < ns; p++)
+    if (a->pitch[p] < row) return TH_EINVAL;
+  if (enc_ensure_device(e)) return TH_EFAULT;
+  DeviceGuard g(e->device);
+  thip_picture_in_req q;
+  memset(&q, 0, sizeof(q));
+  q.format = a->format;
+  q.pixel_fmt = (int32_t)e->info.pixel_fmt;
+  q.pic_x = (int32_t)e->info.pic_x;
+  q.pic_y = (int32_t)e->info.pic_y;
+  q.width = a->width;
+  q.height = a->height;
+  const uint8_t *src[3];
+  int64_t stride[3];
+  for (int p = 0; p < 3; p++) {
+    q.dst[p] = e->d_pix + e->pix_off[p];
+    q.dst_pitch[p] = e->cw[p];
+    src[p] = e->d_pix + e->pix_off[p];
+    stride[p] = e->cw[p];
+  }
+  if (a->device) {
+    hipStream_t cs = (hipStream_t)a->stream;
+    if (!e->ev_conv) ENC_TRY(hipEventCreateWithFlags(&e->ev_conv, hipEventDisableTiming));
+    for (int p = 0; p < ns; p++) {
+      q.src[p] = a->src[p];
+      q.src_pitch[p] = a->pitch[p];
+    }
+    ENC_TRY(hipEventRecord(e->ev_in, cs));
+    ENC_TRY(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+    if (thip_picture_in(&q, 1, e->stream)) return TH_EFAULT;
+    ENC_TRY(hipEventRecord(e->ev_conv, e->stream));   // the caller's picture has been read
+    ENC_TRY(hipStreamWaitEvent(cs, e->ev_conv, 0));
+  } else {
+    // the previous frame's upload is complete (its packet is out), so the staging buffer is free
+    const size_t plane = (size_t)row * a->height;
+    const size_t cap = (size_t)4 * a->width * a->height;   // (the largest of the three formats)
+    if (!e->h_rgb) ENC_TRY(hipHostMalloc((void **)&e->h_rgb, cap, hipHostMallocDefault));
+    if (!e->d_rgb) ENC_TRY(hipMalloc((void **)&e->d_rgb, cap));
+    for (int p = 0; p < ns; p++) {
+      const uint8_t *in = (const uint8_t *)a->src[p];
+      for (int y = 0; y < a->height; y++) memcpy(e->h_rgb + p * plane + (size_t)y * row, in + (int64_t)y * a->pitch[p], (size_t)row);
+      q.src[p] = e->d_rgb + p * plane;
+      q.src_pitch[p] = row;
+    }
+    ENC_TRY(hipMemcpyAsync(e->d_rgb, e->h_rgb, ns * plane, hipMemcpyHostToDevice, e->stream));
+    if (thip_picture_in(&q, 1, e->stream)) return TH_EFAULT;
+  }
+  return enc_queue_frame(e, src, stride);
 }
 
 static void enc_put_eob_run(std::vector<uint32_t> &m, uint32_t run) {   // token | extra << 5 (a 12-bit run is never 0 here)
@@ -1771,6 +1835,10 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     case TH_ENCCTL_THIP_YCBCR_IN_DEVICE:
       if (!buf || buf_sz != sizeof(thip_enc_device_in)) return TH_EINVAL;
       return enc_ycbcr_in_device(e, (const thip_enc_device_in *)buf);
+    case TH_ENCCTL_THIP_RGB_IN:
+      if (!buf) return TH_EFAULT;
+      if (buf_sz != sizeof(thip_enc_rgb_in)) return TH_EINVAL;
+      return enc_rgb_in(e, (const thip_enc_rgb_in *)buf);
     case TH_ENCCTL_THIP_GET_DEVICE:
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       if (!e->dev_ready && enc_ensure_device(e)) return TH_EFAULT;

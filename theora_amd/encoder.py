@@ -31,6 +31,8 @@ TH_ENCCTL_THIP_SET_DEVICE_PACK = 0x720D
 TH_ENCCTL_THIP_GET_PACK_STATS = 0x720E
 TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES = 0x720F
 TH_ENCCTL_THIP_GET_CUT_STATS = 0x7210
+TH_ENCCTL_THIP_RGB_IN = 0x7211
+RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
 TH_ENCCTL_SET_RATE_FLAGS = 20
 TH_ENCCTL_SET_RATE_BUFFER = 22
@@ -45,6 +47,12 @@ ALL_MODE_NAMES = MODE_NAMES + ("GOLDEN_NOMV", "GOLDEN_MV", "INTER_MV_FOUR")
 class DeviceIn(C.Structure):
     """thip_enc_device_in (include/theoraenc_hip.h)."""
     _fields_ = [("planes", ThImgPlane * 3), ("stream", C.c_void_p)]
+
+
+class RgbIn(C.Structure):
+    """thip_enc_rgb_in (include/theoraenc_hip.h)."""
+    _fields_ = [("format", C.c_int32), ("device", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("src", C.c_void_p * 3), ("pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
 
 
 class FrameStats(C.Structure):
@@ -253,6 +261,45 @@ class Encoder:
         rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_YCBCR_IN_DEVICE, C.byref(a), C.sizeof(a))
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_THIP_YCBCR_IN_DEVICE returned %d" % rc)
+
+    def encode_rgb(self, image, fmt="rgb", stream=None):
+        """Queues one frame given as R'G'B' (TH_ENCCTL_THIP_RGB_IN): the picture, pic_width x pic_height, as (H, W, 3) for "rgb",
+        (H, W, 4) for "rgba", (3, H, W) or three (H, W) planes for "rgb_planar"; uint8 numpy arrays (host memory) or uint8 torch
+        CUDA tensors on the encoder's device (ordered on `stream`, default torch's current stream; the tensor may be overwritten
+        from that stream at once).  Rows may have a pitch of their own; the innermost stride must be 1."""
+        if fmt not in RGB_FORMATS:
+            raise ValueError("unknown R'G'B' format %r" % (fmt,))
+        planes = list(image) if isinstance(image, (list, tuple)) else ([image[0], image[1], image[2]] if fmt == "rgb_planar" else [image])
+        host = isinstance(planes[0], np.ndarray)
+        a = RgbIn()
+        a.format, a.device = RGB_FORMATS[fmt], int(not host)
+        ndim, comps = (2, 1) if fmt == "rgb_planar" else (3, 4 if fmt == "rgba" else 3)
+        if len(planes) != (3 if fmt == "rgb_planar" else 1):
+            raise ValueError("rgb_planar wants three planes")
+        for p, t in enumerate(planes):
+            if host:
+                if not isinstance(t, np.ndarray) or t.dtype != np.uint8:
+                    raise TypeError("an R'G'B' picture is uint8 numpy arrays or uint8 torch CUDA tensors")
+                strides, ptr = t.strides, t.ctypes.data
+            else:
+                import torch
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+                    raise TypeError("an R'G'B' picture is uint8 numpy arrays or uint8 torch CUDA tensors")
+                strides, ptr = t.stride(), t.data_ptr()
+            shape = tuple(t.shape)
+            if len(shape) != ndim or (ndim == 3 and shape[2] != comps) or shape[:2] != tuple(planes[0].shape[:2]):
+                raise ValueError("a picture of shape %s for format %r" % (shape, fmt))
+            if strides[-1] != 1 or (ndim == 3 and strides[1] != comps) or strides[0] < shape[1] * comps:
+                raise ValueError("R'G'B' pictures need contiguous pixels and rows (a row pitch of their own is fine)")
+            a.src[p], a.pitch[p] = ptr, strides[0]
+        a.height, a.width = planes[0].shape[0], planes[0].shape[1]
+        if not host:
+            import torch
+            s = stream if stream is not None else torch.cuda.current_stream(planes[0].device)
+            a.stream = s.cuda_stream
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_RGB_IN, C.byref(a), C.sizeof(a))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_RGB_IN returned %d" % rc)
 
     def packetout(self, last=False):
         """The next packet as (bytes, granulepos, packetno, e_o_s), or None when there is none."""
