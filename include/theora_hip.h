@@ -733,6 +733,11 @@ const char *thip_version_string(void);
  *                k_tok_walk, 0 (default) the second for planes of more than 36 864 coded fragments (4K), the first otherwise -- equal
  *                end to end at every size, the second 22 % less kernel time at 4K; tl_walk_threads: k_tok_walk's work-group size
  *                (256, 512, 1024; 0 = by plane size)
+ *   tl_last_plan   (read-out) what thip_state_token_lists_append launched for the last frame whose lists it took to the end (written
+ *                once per frame, with the group that ends at index 64): bits 0-1 the algorithm as tl_algo numbers them, bit 2 set
+ *                when k_tok_assign kept its map in memory, bit 3 set when the slots took two launches (k_tok_slots_count +
+ *                k_tok_slots_assign: more than 32 768 coded fragments in the frame), bits 4-14 the threads of the walking work
+ *                group (k_tok_assign's or k_tok_walk's, after the doubling that keeps a thread to five groups of 32 fragments)
  *   tl_levels    thip_state_token_lists_* / thip_state_decode_token_lists: 1 (default): the device builds the coefficient slots in
  *                the levels form (THIP_COEFFS_LEVELS: int8 units, wide tiles where a level needs more; the reconstruction kernel
  *                dequantises); 0: dequantised int16 slots, as in round 3

@@ -139,9 +139,11 @@ def test_options_table():
     for nm in names:
         assert (" " + nm) in hdr, nm          # documented in the header
     for nm in ("fuse", "lanes", "ctx_lanes", "chunk", "skip_static", "lf_sparse", "zerocopy", "wait_spin", "dc_global", "debug",
-               "fe_device_dc", "fe_device_tokens", "fe_device_lists", "fe_trace_backend", "fe_prof", "device"):
+               "fe_device_dc", "fe_device_tokens", "fe_device_lists", "fe_trace_backend", "fe_prof", "device", "tl_algo", "tl_walk_threads",
+               "tl_levels", "tl_last_plan"):
         assert nm in names, nm
-    defaults = dict(fuse=3, lanes=2, ctx_lanes=8, skip_static=1, lf_sparse=-1, zerocopy=1, device=-1, fe_device_lists=-1, fe_device_dc=0)
+    defaults = dict(fuse=3, lanes=2, ctx_lanes=8, skip_static=1, lf_sparse=-1, zerocopy=1, device=-1, fe_device_lists=-1, fe_device_dc=0,
+                    tl_algo=0, tl_walk_threads=0, tl_levels=1)
     for nm, dv in defaults.items():
         if "THIP_" + nm.upper() not in os.environ:
             v = C.c_int(12345)

@@ -292,16 +292,11 @@ def test_token_list_groups_come_in_order(hip):
     """thip_state_token_lists_append: the first group starts at index 0, each at the end of the one before, _finish wants
     them all; _abort gives an opened frame up."""
     import ctypes as C
-
-    class TL(C.Structure):
-        _fields_ = [("frame_type", C.c_int32), ("flimit", C.c_int32), ("tokens", C.c_void_p), ("ntokens", C.c_int64),
-                    ("list_off", C.c_uint32 * 64 * 3), ("list_len", C.c_uint32 * 64 * 3), ("eob_carry", C.c_uint32 * 64 * 3),
-                    ("arrivals", C.c_uint32 * 64 * 3), ("coded", C.c_void_p), ("frag_meta", C.c_void_p),
-                    ("ncoded", C.c_int32 * 3), ("dequant", C.c_void_p), ("dc_quant", C.c_uint16 * 2 * 3), ("dc", C.c_void_p)]
+    from tests.tokenlists import TokenLists
 
     L = hip._lib.load()
     st = hip.State(64, 48, 0)
-    tl = TL()
+    tl = TokenLists()
     tl.frame_type = 1   # an inter frame with nothing coded
     z = (C.c_uint32 * 64 * 3)()
     EINVAL = hip._lib.EINVAL
@@ -338,7 +333,8 @@ def test_packets_decode_bit_exact_4k(hip, mode):
     """BASELINE.json's 4K size (3840x2160 4:2:0, 194 400 fragments) through th_decode_*: a key frame and two inter frames with
     matched Huffman trees, by the host front end, with the DC un-prediction on the GPU (k_dc_wave: 480 x 270 luma fragments, the
     64 rows in flight in LDS), and with TH_DECCTL_THIP_SET_DEVICE_LISTS: the token lists themselves on the GPU, the key frame's luma
-    plane (129 600 coded fragments) with k_tok_assign's rank -> fragment map in memory instead of LDS."""
+    plane (129 600 coded fragments, beyond the 36 864 up to which k_tok_assign keeps its map in LDS) with k_tok_rank + k_tok_walk, the
+    default there (k_tok_assign's map in memory, option tl_algo = 1, is tests/test_gpu_token_lists.py's)."""
     assert run_stream(hip, 3840, 2160, 0, seed=2160, nframes=3, kf=3, trees="matched", device_dc=mode in ("device_dc", "device_lists_dc"),
                       device_lists=mode in ("device_lists", "device_lists_dc", "device_lists_lookahead"),
                       lookahead=2 if mode == "device_lists_lookahead" else 0) == 3

@@ -83,6 +83,7 @@ Option g_options[] = {
     {"spec_coeffs", 1, "k_recon_lf, levels form: 1 (default): for a frame with a coefficient unit for every block (nslots == its fragments) the waves of whole tile rows ask for their tile's units when they start, at the address that follows from the tile's place in its plane, and check it against the first-slot word; 0: always after the command words"},
     {"tl_algo", 0, "token lists on the device: 1: k_tok_assign (rank -> fragment map in LDS, or in memory for planes beyond 36 864 coded fragments); 2: k_tok_rank + k_tok_walk (every fragment looked after by one thread, one barrier per index, one byte of LDS per fragment); 0 (default): 2 where 1 would keep its map in memory (4K), 1 otherwise"},
     {"tl_walk_threads", 0, "k_tok_walk: threads of the work group (256, 512, 1024); 0 (default): by plane size"},
+    {"tl_last_plan", 0, "(counter) a read-out, not a count: what thip_state_token_lists_append launched for the last frame whose lists it took to the end (the group that ends at index 64): bits 0-1 the algorithm (1 k_tok_assign, 2 k_tok_rank + k_tok_walk), bit 2 k_tok_assign's map in memory, bit 3 the slots in two launches (k_tok_slots_count + _assign), bits 4-14 the threads of the walking work group"},
     {"tl_levels", 1, "token lists on the device (thip_state_token_lists_*): 1 (default): the device writes the coefficient slots in the levels form (int8 units, the reconstruction kernel dequantises); 0: dequantised int16 slots"},
     {"fe_groups", 6, "th_decode_*, token-list path: the groups of zig-zag indices a frame's lists are handed over in while the packet is still being decoded: 6 (default since round 6: {3, 10, 28, 48, 64} -- what the device walks behind the packet's last bit is sixteen indices instead of thirty-six), 4 ({3, 10, 28, 64}, rounds 4-5), 7 ({3, 10, 28, 44, 56, 64}), 9, 5, 3, 2, or 1: in one piece after the packet's last bit"},
     {"fe_worker", 2, "th_decode_*, token-list path: 1: a second thread per context undoes the DC prediction while the caller decodes the tokens of indices 1..63; 0: the caller does it behind the tokens, while the device walks the last indices; 2 (default): 1 for frames of more than 32 768 fragments (beyond 720p), 0 otherwise"},
@@ -144,6 +145,8 @@ extern "C" int thip_option(const char *name) {
 }
 // ... and for this translation unit's per-frame reads: the entry is looked up once per call site, a read is one relaxed load
 #define THIP_OPT(name) ([]() -> int { static const Option *const o_ = find_option(name); return o_ ? o_->value.load(std::memory_order_relaxed) : 0; }())
+// ... and a read-out the library writes itself (tl_last_plan): the same one look-up per call site, a relaxed store
+#define THIP_OPT_STORE(name, v) ([](int v_) { static Option *const o_ = find_option(name); if (o_) o_->value.store(v_, std::memory_order_relaxed); }(v))
 // (internal, for the counters thip_frontend.cpp keeps in the table)
 extern "C" void thip_option_add(const char *name, int delta) {
   Option *o = find_option(name);
@@ -2630,6 +2633,7 @@ int thip_state_token_lists_append(thip_state *st, int z0, int z1, const uint32_t
   K.z1 = z1;
   int nmax = 0;
   for (int p = 0; p < 3; p++) nmax = std::max(nmax, K.p[p].n);
+  int plan = algo;   // (option tl_last_plan: bits 0-1 the algorithm, 2 the map in memory, 3 two-launch slots, 4-14 the threads)
   if (algo == 2) {
     K.rank = st->d_tl_rank;
     hipLaunchKernelGGL(k_tok_rank, dim3(3 * (unsigned)(z1 - z0)), dim3(kTlRankThreads), 0, s, K);
@@ -2637,6 +2641,7 @@ int thip_state_token_lists_append(thip_state *st, int z0, int z1, const uint32_t
     if (T != 256 && T != 512 && T != 1024) T = nmax <= 2048 ? 256 : (nmax <= 8192 ? 512 : 1024);   // (a round is one barrier: waves are cheap, arrivals per thread are not)
     while (T < 1024 && ((((nmax + 31) & ~31) >> 5) + T - 1) / T > kTlGroups) T *= 2;   // (a thread looks after kTlGroups x 32 fragments at most)
     const size_t lds = (size_t)((nmax + 31) & ~31) + 16;
+    plan |= T << 4;
     if (T == 256) {
       HIP_TRY(set_dynamic_lds(reinterpret_cast<const void *>(k_tok_walk<256>), kTlMaxFrags + 32, 4));
       hipLaunchKernelGGL(k_tok_walk<256>, dim3(3), dim3(256), lds, s, K);
@@ -2651,10 +2656,12 @@ int thip_state_token_lists_append(thip_state *st, int z0, int z1, const uint32_t
     const int lds = 2 * ((nmax + 31) & ~31) + 2 * nmax + 16;
     HIP_TRY(set_dynamic_lds(reinterpret_cast<const void *>(k_tok_assign<false>), 2 * ((kTlLdsFrags + 31) & ~31) + 2 * kTlLdsFrags + 16, 2));
     hipLaunchKernelGGL(k_tok_assign<false>, dim3(3), dim3(tl_threads(nmax)), (size_t)lds, s, K);
+    plan |= tl_threads(nmax) << 4;
   } else {   // (4K luma: the rank -> fragment map in memory, the positions alone in LDS)
     const int lds = ((nmax + 31) & ~31) + 16;
     HIP_TRY(set_dynamic_lds(reinterpret_cast<const void *>(k_tok_assign<true>), kTlMaxFrags + 32, 1));
     hipLaunchKernelGGL(k_tok_assign<true>, dim3(3), dim3(tl_threads(nmax)), (size_t)lds, s, K);
+    plan |= 4 | tl_threads(nmax) << 4;
   }
   if (z1 == 64) {
     if (K.levels) hipLaunchKernelGGL(k_tok_widths, dim3((unsigned)((ncoded + 255) / 256)), dim3(256), 0, s, K);
@@ -2665,7 +2672,9 @@ int thip_state_token_lists_append(thip_state *st, int z0, int z1, const uint32_t
       uint32_t *part = st->d_tl_wide + (((size_t)st->tiles.ntiles + 3) & ~(size_t)3);   // (behind the tiles' words)
       hipLaunchKernelGGL(k_tok_slots_count, dim3(ng), dim3(1024), 0, s, K, part);
       hipLaunchKernelGGL(k_tok_slots_assign, dim3(ng), dim3(1024), 0, s, K, (const uint32_t *)part);
+      plan |= 8;
     }
+    THIP_OPT_STORE("tl_last_plan", plan);
   }
   HIP_TRY(hipGetLastError());
   st->tl_z = z1;
