@@ -195,6 +195,74 @@ typedef struct thip_picture_req {
 int thip_picture_out(const thip_picture_req *reqs, int n, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same picture at another size: a rectangle of a state's finished picture resampled to out_width x out_height, converted
+ * and written to caller DEVICE memory in one pass (k_picture_resize).  For transcoding to a smaller size (THIP_PIC_YCBCR: the
+ * planes th_encode_ycbcr_in and TH_ENCCTL_THIP_YCBCR_IN_DEVICE take) and for consumers that want a fixed size, CHW, float,
+ * (x - mean) / std (THIP_PIC_RGB_PLANAR with THIP_ELEM_F16 / _F32).
+ *
+ * The definition.  All arithmetic is integer, >> is an arithmetic shift, divisions are floor divisions of the stated operands.
+ *
+ * Source planes.  Plane p is the rectangle thip_picture_out would write for THIP_PIC_YCBCR with the same x, y, width, height:
+ * luma width x height, chroma columns [x >> hdec, (x + width + hdec) >> hdec), rows likewise with vdec, rows top first.  Call its
+ * size sw x sh and its samples s[j][i].  Indices are clamped to the rectangle, not to the coded plane: no sample outside the
+ * rectangle influences the output.
+ *
+ * Output sizes.
+ *   THIP_PIC_YCBCR   plane 0 is out_width x out_height, planes 1 and 2 are (out_width + hdec) >> hdec by
+ *                    (out_height + vdec) >> vdec -- the picture-sized planes th_encode_ycbcr_in takes for a picture at offset 0.
+ *                    Each plane is resampled on its own from its rectangle to its output size.
+ *   R'G'B' formats   Y, Cb and Cr are each resampled from their own rectangle straight to out_width x out_height: chroma
+ *                    upsampling and the resize are one step (there is no `chroma` field).  Then thip_picture_out's integer matrix
+ *                    and clamp255.
+ *
+ * THIP_FILTER_BILINEAR, centre-aligned, Q8 weights.  Per axis with source extent S and output extent O, the position of output
+ * index X is
+ *     p = floor(((2X + 1) S - O) * 128 / O)        (int64), clamped to [0, (S - 1) * 256]
+ *     i0 = p >> 8,  f = p & 255,  i1 = min(i0 + 1, S - 1)
+ * and with a, b the samples at columns i0, i1 of row j0 and c, d those of row j1 the output sample is
+ *     ((256 - fy) * ((256 - fx) a + fx b) + fy * ((256 - fx) c + fx d) + 32768) >> 16         (one rounding)
+ * At the rectangle's own size this is the identity; for 4:2:0 chroma taken to the luma size it is exactly THIP_CHROMA_LINEAR's
+ * (9a + 3b + 3c + d + 8) >> 4.  Bilinear reads four samples whatever the scale, so it aliases below half size: THIP_FILTER_AREA is
+ * the filter for downscaling.
+ *
+ * THIP_FILTER_AREA, exact box resampling.  On an axis output index X covers [X S, (X + 1) S) where source sample i covers
+ * [i O, (i + 1) O); the weight of a source sample is the length of the overlap, an integer, and the weights of one output sample
+ * sum to S.  The output sample is
+ *     (sum_j sum_i wy_j wx_i s[j][i] + (sw sh >> 1)) / (sw sh)                                 (unsigned 64-bit, one rounding)
+ * Upscaling makes it nearest-neighbour, equal size the identity.  A source extent of more than 32 times the output extent, on
+ * either axis of any plane, is refused: the filter has at most 34 taps an axis.
+ *
+ * Elements.  THIP_ELEM_U8: the 8-bit sample.  THIP_ELEM_F32 (THIP_PIC_RGB_PLANAR only), with c the clamped 8-bit component of
+ * channel k: v = (float)c * scale[k], rounded to nearest even, then v + bias[k], rounded again -- two separately rounded binary32
+ * operations, not a fused one, so that numpy float32 reproduces every bit.  THIP_ELEM_F16: that value converted to binary16, round
+ * to nearest even.  scale and bias are not validated.
+ *
+ * The contract is thip_picture_out's: asynchronous; ordered behind the frame; visible on the caller's stream; later frames wait
+ * for it; stream NULL sends each request down its state's own stream; all or nothing; calls of more than THIP_MAX_BATCH requests
+ * are chunked; destinations may have any alignment and pitch.  THIP_EFAULT and THIP_EINVAL as there, and THIP_EINVAL also for a bad
+ * filter or elem, a float elem with a format other than THIP_PIC_RGB_PLANAR, out_width or out_height outside 1..16384, a pitch
+ * smaller than the output row in bytes, and the area limit above.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_FILTER_BILINEAR 0
+#define THIP_FILTER_AREA     1
+#define THIP_ELEM_U8  0
+#define THIP_ELEM_F16 1
+#define THIP_ELEM_F32 2
+typedef struct thip_picture_resize_req {
+  thip_state *state;
+  int32_t bufi;                  /* as thip_picture_req */
+  int32_t format;                /* THIP_PIC_* */
+  int32_t filter;                /* THIP_FILTER_* */
+  int32_t elem;                  /* THIP_ELEM_*; F16 / F32 only with THIP_PIC_RGB_PLANAR */
+  int32_t x, y, width, height;   /* source rectangle, display coordinates; 0 x 0: the whole frame */
+  int32_t out_width, out_height; /* 1 .. 16384 */
+  float scale[3], bias[3];       /* per R, G, B; read only when elem != U8 */
+  void *dst[3];
+  int64_t dst_pitch[3];          /* bytes */
+} thip_picture_resize_req;
+int thip_picture_resize(const thip_picture_resize_req *reqs, int n, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The other direction: an R'G'B' picture in caller DEVICE memory turned into the picture-sized Y'CbCr planes th_encode_ycbcr_in and
  * TH_ENCCTL_THIP_YCBCR_IN_DEVICE accept (k_picture_in; up to THIP_MAX_BATCH requests a launch, larger calls are chunked).
  * TH_ENCCTL_THIP_RGB_IN (theoraenc_hip.h) is this conversion in front of the encoder.

@@ -172,7 +172,8 @@ typedef struct {
    take back: TH_DECCTL_SET_GRANPOS (the counters it sets are frame N's), TH_DECCTL_SET_PPLEVEL with a level above 0 (the held
    frame was decoded unfiltered and untracked), TH_DECCTL_SET_STRIPE_CB (the callback is made inside a frame's
    th_decode_packetin), TH_DECCTL_THIP_SET_DEVICE_DC and _SET_DEVICE_TOKENS.  These leave the held frame alone: every
-   TH_DECCTL_GET_*, TH_DECCTL_SET_PPLEVEL 0, TH_DECCTL_THIP_PREFETCH_PACKET, _PICTURE_OUT, _SET_HOST_OUTPUT, _SET_DEVICE_LISTS.
+   TH_DECCTL_GET_*, TH_DECCTL_SET_PPLEVEL 0, TH_DECCTL_THIP_PREFETCH_PACKET, _PICTURE_OUT, _PICTURE_RESIZE, _SET_HOST_OUTPUT,
+   _SET_DEVICE_LISTS.
    The picture th_decode_ycbcr_out handed out for frame N stays valid and unchanged either way.  One frame is held at most: the
    backend can take back one (thip_state_ring_rewind, include/theora_hip.h). */
 #define TH_DECCTL_THIP_PREFETCH_PACKET (0x7105)
@@ -200,6 +201,23 @@ typedef struct thip_picture_out_args {
   int64_t dst_pitch[3];    /* bytes per row */
   void *stream;            /* hipStream_t, or NULL */
 } thip_picture_out_args;
+/* Extension: buf = thip_picture_resize_args.  TH_DECCTL_THIP_PICTURE_OUT at another size: a rectangle of the frame
+   th_decode_packetin last returned (TH_DUPFRAME: the repeated one) resampled, converted and written to device memory as
+   thip_picture_resize does (include/theora_hip.h: the two filters, the element types, scale and bias, and the limits).  The
+   fields are thip_picture_resize_req's without state and bufi; x, y, width, height are display coordinates of the coded frame
+   (0 x 0: the whole frame; th_info's picture region is pic_x, pic_y, pic_width, pic_height).  Stream, device, ordering and the
+   frame it shows are TH_DECCTL_THIP_PICTURE_OUT's: the request never decodes ahead and never waits on the host.  Returns 0, what
+   thip_picture_resize returns for bad arguments, TH_EINVAL before the first frame, TH_EIMPL in slot-trace mode. */
+#define TH_DECCTL_THIP_PICTURE_RESIZE (0x7109)
+typedef struct thip_picture_resize_args {
+  int32_t format, filter, elem;  /* THIP_PIC_*, THIP_FILTER_*, THIP_ELEM_* */
+  int32_t x, y, width, height;   /* source rectangle; 0 x 0: the whole coded frame */
+  int32_t out_width, out_height;
+  float scale[3], bias[3];
+  void *dst[3];                  /* device memory */
+  int64_t dst_pitch[3];          /* bytes per row */
+  void *stream;                  /* hipStream_t, or NULL */
+} thip_picture_resize_args;
 typedef struct thip_slot_trace {
   int64_t ncoded;           /* state_frag_recon calls, in call (= coded) order */
   const int32_t *fragi;     /* _fragi */

@@ -218,6 +218,23 @@ class State:
         picture_out([self], [out], fmt, chroma, [rect], [bufi], stream)
         return out
 
+    def picture_resized(self, size, fmt="rgb_planar", filter="area", rect=None, bufi=-1, dtype=None, scale=None, bias=None,
+                        stream=None):
+        """The state's newest picture (or ring buffer `bufi` as decoded), the rectangle `rect` of it (None: the whole coded frame),
+        resampled to size = (out_width, out_height) as a new device tensor of picture_resize_shapes' shapes: uint8, or for
+        "rgb_planar" torch.float16 / torch.float32 holding c * scale[k] + bias[k] per channel.  filter: "area" (the one for
+        downscaling) or "bilinear".  Asynchronous on `stream` (default: torch's current stream), like picture_resize."""
+        import torch
+        dtype = torch.uint8 if dtype is None else dtype
+        shapes = picture_resize_shapes(fmt, size[0], size[1], self.pixel_fmt)
+        dev = torch.device("cuda", self.device)
+        if fmt == "ycbcr":
+            out = tuple(torch.empty(s, dtype=dtype, device=dev) for s in shapes)
+        else:
+            out = torch.empty(shapes, dtype=dtype, device=dev)
+        picture_resize([self], [out], [size], fmt, filter, [rect], [bufi], dtype, scale, bias, stream)
+        return out
+
     def set_eager_output(self, on):
         _lib.check(self._L.thip_state_set_eager_output(self._h, int(bool(on))), "set_eager_output")
 
@@ -278,10 +295,11 @@ def picture_shapes(fmt, width, height, x=0, pixel_fmt=PF_420, y=0):
     return [(height, width), (ch, cw), (ch, cw)]
 
 
-def _pic_dst(fmt, out, shapes):
-    """Destination pointers and row pitches of `out` after checking it against the request's shapes (the library writes
-    exactly that many rows of that many bytes: a tensor too small for them is refused here)."""
+def _pic_dst(fmt, out, shapes, dtype=None):
+    """Destination pointers and row pitches (bytes) of `out` after checking it against the request's shapes (the library writes
+    exactly that many rows of that many bytes: a tensor too small for them is refused here).  dtype: the elements, default uint8."""
     import torch
+    dtype = torch.uint8 if dtype is None else dtype
     if fmt in ("ycbcr", "rgb_planar"):
         planes = list(out) if isinstance(out, (list, tuple)) else [out[0], out[1], out[2]]
         pshapes = shapes if fmt == "ycbcr" else [shapes[1:]] * 3
@@ -291,14 +309,14 @@ def _pic_dst(fmt, out, shapes):
         planes, pshapes = [out], [shapes]
     ptrs, pitches = [], []
     for t, shp in zip(planes, pshapes):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
-            raise TypeError("picture destinations are uint8 device tensors")
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda:
+            raise TypeError("picture destinations are %s device tensors" % str(dtype).replace("torch.", ""))
         if tuple(t.shape) != tuple(shp):
             raise ValueError("destination of shape %s for a picture of %s" % (tuple(t.shape), tuple(shp)))
         if t.stride(-1) != 1 or (t.dim() == 3 and t.stride(1) != t.shape[2]) or t.stride(0) < t.shape[1] * (t.shape[2] if t.dim() == 3 else 1):
             raise ValueError("picture destinations need contiguous rows (a row pitch of their own is fine)")
         ptrs.append(t.data_ptr())
-        pitches.append(t.stride(0))
+        pitches.append(t.stride(0) * t.element_size())
     while len(ptrs) < 3:
         ptrs.append(None)
         pitches.append(0)
@@ -358,6 +376,68 @@ def picture_out(states, outs, fmt="rgb", chroma="linear", rects=None, bufis=None
         return
     device = states[0].device
     _lib.check(_on_stream(device, stream, lambda h: L.thip_picture_out(reqs, n, h)), "thip_picture_out")
+
+
+# ---------------------------------------------------------------------------------------
+# pictures at another size (thip_picture_resize)
+# ---------------------------------------------------------------------------------------
+FILTERS = {"bilinear": _lib.FILTER_BILINEAR, "area": _lib.FILTER_AREA}
+
+
+def picture_resize_shapes(fmt, out_width, out_height, pixel_fmt=PF_420):
+    """The output shapes of thip_picture_resize: one (H, W, 3) / (H, W, 4) / (3, H, W) shape, or for "ycbcr" three plane shapes --
+    the picture-sized planes Encoder.encode takes for an out_width x out_height picture at offset 0."""
+    return picture_shapes(fmt, out_width, out_height, 0, pixel_fmt, 0)
+
+
+def _elem(dtype):
+    import torch
+    elems = {torch.uint8: _lib.ELEM_U8, torch.float16: _lib.ELEM_F16, torch.float32: _lib.ELEM_F32}
+    if dtype not in elems:
+        raise TypeError("picture elements are uint8, float16 or float32, not %r" % (dtype,))
+    return elems[dtype]
+
+
+def picture_resize(states, outs, sizes, fmt="rgb_planar", filter="area", rects=None, bufis=None, dtype=None, scale=None, bias=None,
+                   stream=None):
+    """thip_picture_resize: per state the rectangle rects[i] (None: the whole coded frame) of its picture resampled to
+    sizes[i] = (out_width, out_height) and written to outs[i], device tensors of picture_resize_shapes' shapes.  fmt, filter and
+    dtype may be lists, one per state; dtype is torch.uint8 (the default), or with "rgb_planar" torch.float16 / torch.float32:
+    the element is then c * scale[k] + bias[k] for channel k (scale and bias: three floats each, default 1 and 0; the same for
+    every state).  bufis, stream: as picture_out."""
+    import torch
+    L = _lib.load()
+    n = len(states)
+    if len(outs) != n or len(sizes) != n:
+        raise ValueError("one destination and one size per state")
+    fmts = [fmt] * n if isinstance(fmt, str) else list(fmt)
+    filters = [filter] * n if isinstance(filter, str) else list(filter)
+    dtypes = list(dtype) if isinstance(dtype, (list, tuple)) else [torch.uint8 if dtype is None else dtype] * n
+    scale = (1.0, 1.0, 1.0) if scale is None else tuple(scale)
+    bias = (0.0, 0.0, 0.0) if bias is None else tuple(bias)
+    if len(scale) != 3 or len(bias) != 3:
+        raise ValueError("scale and bias hold one value per channel")
+    for f, fl in zip(fmts, filters):
+        if f not in PIC_FORMATS or fl not in FILTERS:
+            raise ValueError("format %r / filter %r" % (f, fl))
+    reqs = (_lib.PictureResizeReq * max(n, 1))()
+    for i, st in enumerate(states):
+        x, y, w, h = rects[i] if rects is not None and rects[i] is not None else (0, 0, 0, 0)
+        ow, oh = sizes[i]
+        ptrs, pitches = _pic_dst(fmts[i], outs[i], picture_resize_shapes(fmts[i], ow, oh, st.pixel_fmt), dtypes[i])
+        r = reqs[i]
+        r.state = st.handle
+        r.bufi = -1 if bufis is None else int(bufis[i])
+        r.format, r.filter, r.elem = PIC_FORMATS[fmts[i]], FILTERS[filters[i]], _elem(dtypes[i])
+        r.x, r.y, r.width, r.height = x, y, w, h
+        r.out_width, r.out_height = ow, oh
+        for p in range(3):
+            r.scale[p], r.bias[p] = scale[p], bias[p]
+            r.dst[p] = ptrs[p]
+            r.dst_pitch[p] = pitches[p]
+    if n == 0:
+        return
+    _lib.check(_on_stream(states[0].device, stream, lambda h: L.thip_picture_resize(reqs, n, h)), "thip_picture_resize")
 
 
 # ---------------------------------------------------------------------------------------

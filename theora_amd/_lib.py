@@ -52,6 +52,18 @@ class PictureReq(C.Structure):
                 ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3)]
 
 
+FILTER_BILINEAR, FILTER_AREA = 0, 1
+ELEM_U8, ELEM_F16, ELEM_F32 = 0, 1, 2
+
+
+class PictureResizeReq(C.Structure):
+    """thip_picture_resize_req (include/theora_hip.h)."""
+    _fields_ = [("state", C.c_void_p), ("bufi", C.c_int32), ("format", C.c_int32), ("filter", C.c_int32), ("elem", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("out_width", C.c_int32), ("out_height", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3),
+                ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -98,6 +110,7 @@ SYMBOLS = [
     ("thip_state_token_lists_staging", _I, [_P, _P]),
     ("thip_state_read_pp_plane", _I, [_P, _I, _P]),
     ("thip_picture_out", _I, [C.POINTER(PictureReq), _I, _P]),
+    ("thip_picture_resize", _I, [C.POINTER(PictureResizeReq), _I, _P]),
     ("thip_picture_in", _I, [C.POINTER(PictureInReq), _I, _P]),
     ("thip_decode_frames", _I, [C.POINTER(_P), C.POINTER(FrameDesc), _I, _P, C.POINTER(C.c_int32)]),
     ("thip_synchronize", _I, []),

@@ -177,6 +177,7 @@ extern "C" const char *thip_option_name(int index, const char **help) {
 #include "thip_postproc.h"
 #include "thip_tokens.h"
 #include "thip_picture.h"
+#include "thip_picture_resize.h"
 #include "thip_picture_in.h"
 
 // ---------------------------------------------------------------------------------------
@@ -1692,7 +1693,8 @@ int thip_state_read_pp_plane(thip_state *st, int pli, uint8_t *host_out) {
 
 // ---- device-resident pictures (thip_picture_out, k_picture_out in thip_picture.h) ------------------------------------------
 // The rectangle of a request in display coordinates of the coded frame: false if it does not lie inside the frame.
-static bool picture_rect(const thip_picture_req &q, const thip_state *st, int &x, int &y, int &w, int &h) {
+extern "C++" template <typename Req>   // (thip_picture_req, thip_picture_resize_req)
+static bool picture_rect(const Req &q, const thip_state *st, int &x, int &y, int &w, int &h) {
   if (q.width == 0 && q.height == 0) {
     x = y = 0;
     w = st->frame_width;
@@ -1779,22 +1781,25 @@ static int picture_launch(const thip_picture_req *const *reqs, int n, hipStream_
   return THIP_OK;
 }
 
-int thip_picture_out(const thip_picture_req *reqs, int n, void *stream) {
+// What thip_picture_out and thip_picture_resize share: the checks first, then launches of up to THIP_MAX_BATCH requests a stream.
+extern "C++" template <typename Req>
+static int picture_dispatch(const Req *reqs, int n, void *stream, int (*check)(const Req &),
+                            int (*launch)(const Req *const *, int, hipStream_t)) {
   if (n < 0) return THIP_EINVAL;
   if (n == 0) return THIP_OK;
   if (!reqs) return THIP_EFAULT;
   for (int i = 0; i < n; i++) {   // all or nothing: every request is checked before anything is queued
-    const int rc = picture_check(reqs[i]);
+    const int rc = check(reqs[i]);
     if (rc < 0) return rc;
   }
-  std::vector<const thip_picture_req *> ptrs(n);
+  std::vector<const Req *> ptrs(n);
   for (int i = 0; i < n; i++) ptrs[i] = &reqs[i];
   if (stream) {   // caller-owned stream: all states on its device, in submission order
     for (int i = 1; i < n; i++)
       if (reqs[i].state->device != reqs[0].state->device) return THIP_EINVAL;
     DeviceGuard dg(reqs[0].state->device);
     for (int i = 0; i < n; i += THIP_MAX_BATCH) {
-      const int rc = picture_launch(ptrs.data() + i, std::min(THIP_MAX_BATCH, n - i), (hipStream_t)stream);
+      const int rc = launch(ptrs.data() + i, std::min(THIP_MAX_BATCH, n - i), (hipStream_t)stream);
       if (rc < 0) return rc;
     }
     return THIP_OK;
@@ -1814,18 +1819,121 @@ int thip_picture_out(const thip_picture_req *reqs, int n, void *stream) {
     }
     for (int i = 0; i < n; i++) {
       if (done[i] || reqs[i].state->device != dev) continue;
-      const thip_picture_req *grp[THIP_MAX_BATCH];
+      const Req *grp[THIP_MAX_BATCH];
       int m = 0;
       for (int k = i; k < n && m < THIP_MAX_BATCH; k++)
         if (!done[k] && reqs[k].state->device == dev && sv[k] == sv[i]) {
           grp[m++] = &reqs[k];
           done[k] = 1;
         }
-      const int rc = picture_launch(grp, m, sv[i]);
+      const int rc = launch(grp, m, sv[i]);
       if (rc < 0) return rc;
     }
   }
   return THIP_OK;
+}
+
+int thip_picture_out(const thip_picture_req *reqs, int n, void *stream) {
+  return picture_dispatch<thip_picture_req>(reqs, n, stream, picture_check, picture_launch);
+}
+
+// ---- resized pictures (thip_picture_resize, k_picture_resize in thip_picture_resize.h) --------------------------------------
+// Plane p of a request: the source rectangle's corner and size, and the size it is resampled to.
+struct ResizePlane {
+  int rx, ry, sw, sh, ow, oh;
+};
+static ResizePlane resize_plane(const thip_picture_resize_req &q, int p, int x, int y, int w, int h) {
+  const thip_state *st = q.state;
+  const int hd = p ? st->hdec : 0, vd = p ? st->vdec : 0;
+  ResizePlane g;
+  g.rx = x >> hd;
+  g.ry = y >> vd;
+  g.sw = ((x + w + hd) >> hd) - g.rx;
+  g.sh = ((y + h + vd) >> vd) - g.ry;
+  const bool own = q.format == THIP_PIC_YCBCR;   // R'G'B': every plane goes straight to the output size
+  g.ow = own ? (q.out_width + hd) >> hd : q.out_width;
+  g.oh = own ? (q.out_height + vd) >> vd : q.out_height;
+  return g;
+}
+
+static int picture_resize_check(const thip_picture_resize_req &q) {
+  const thip_state *st = q.state;
+  if (!st) return THIP_EFAULT;
+  if (q.format < THIP_PIC_YCBCR || q.format > THIP_PIC_RGB_PLANAR) return THIP_EINVAL;
+  if (q.filter != THIP_FILTER_BILINEAR && q.filter != THIP_FILTER_AREA) return THIP_EINVAL;
+  if (q.elem != THIP_ELEM_U8 && q.elem != THIP_ELEM_F16 && q.elem != THIP_ELEM_F32) return THIP_EINVAL;
+  if (q.elem != THIP_ELEM_U8 && q.format != THIP_PIC_RGB_PLANAR) return THIP_EINVAL;
+  if (q.out_width < 1 || q.out_width > 16384 || q.out_height < 1 || q.out_height > 16384) return THIP_EINVAL;
+  const int nd = q.format == THIP_PIC_RGB24 || q.format == THIP_PIC_RGBA32 ? 1 : 3;
+  for (int p = 0; p < nd; p++)
+    if (!q.dst[p]) return THIP_EFAULT;
+  if (q.bufi < -1 || q.bufi > 2 || st->last_decoded < 0) return THIP_EINVAL;
+  int x, y, w, h;
+  if (!picture_rect(q, st, x, y, w, h)) return THIP_EINVAL;
+  const int64_t esz = q.elem == THIP_ELEM_F32 ? 4 : q.elem == THIP_ELEM_F16 ? 2 : q.format == THIP_PIC_RGB24 ? 3 : q.format == THIP_PIC_RGBA32 ? 4 : 1;
+  for (int p = 0; p < 3; p++) {
+    const ResizePlane g = resize_plane(q, p, x, y, w, h);
+    if (p < nd && q.dst_pitch[p] < esz * g.ow) return THIP_EINVAL;
+    if (q.filter == THIP_FILTER_AREA && (g.sw > 32 * (int64_t)g.ow || g.sh > 32 * (int64_t)g.oh)) return THIP_EINVAL;
+  }
+  return THIP_OK;
+}
+
+static void picture_resize_fill(PicRszReqK &K, const thip_picture_resize_req &q) {
+  const thip_state *st = q.state;
+  memset(&K, 0, sizeof(K));
+  const bool pp = q.bufi < 0 && st->pp_serial == st->frame_serial;   // (as picture_fill)
+  const uint8_t *frame = st->frames[q.bufi < 0 ? st->last_decoded : q.bufi];
+  int x, y, w, h;
+  (void)picture_rect(q, st, x, y, w, h);
+  K.format = q.format;
+  K.filter = q.filter;
+  K.elem = q.elem;
+  int units = 0;
+  for (int p = 0; p < 3; p++) {
+    const thip_plane_geom &g = st->geom[p];
+    const ResizePlane r = resize_plane(q, p, x, y, w, h);
+    K.src[p] = (pp && st->pp_active[p] ? st->pp_frame : frame) + g.plane_off;
+    K.dst[p] = (uint8_t *)q.dst[p];
+    K.dpitch[p] = q.dst_pitch[p];
+    K.spitch[p] = g.stride;
+    K.ph[p] = g.height;
+    K.rx[p] = r.rx;
+    K.ry[p] = r.ry;
+    rsz_prepare_axis(K.ax[p], r.sw, r.ow);
+    rsz_prepare_axis(K.ay[p], r.sh, r.oh);
+    rsz_prepare_area(K, p, r.sw, r.sh);
+    K.scale[p] = q.scale[p];
+    K.bias[p] = q.bias[p];
+    const int cpr = (r.ow + 15) >> 4;
+    if (p == 0) K.cpr = cpr;
+    else K.ccpr = cpr;
+    if (p == 0 || q.format == THIP_PIC_YCBCR) units += cpr * r.oh;
+    K.unit_end[p] = units;
+  }
+}
+
+static int picture_resize_launch(const thip_picture_resize_req *const *reqs, int n, hipStream_t s) {
+  PicRszBatchK B;
+  int max_units = 0;
+  for (int i = 0; i < n; i++) {
+    const int rc = order_behind_previous(reqs[i]->state, s);
+    if (rc < 0) return rc;
+    picture_resize_fill(B.r[i], *reqs[i]);
+    max_units = std::max(max_units, B.r[i].unit_end[2]);
+  }
+  for (int i = n; i < THIP_MAX_BATCH; i++) memset(&B.r[i], 0, sizeof(B.r[i]));
+  hipLaunchKernelGGL(k_picture_resize, dim3((unsigned)((max_units + 255) / 256), (unsigned)n), dim3(256), 0, s, B);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < n; i++) {
+    const int rc = order_mark(reqs[i]->state, s);
+    if (rc < 0) return rc;
+  }
+  return THIP_OK;
+}
+
+int thip_picture_resize(const thip_picture_resize_req *reqs, int n, void *stream) {
+  return picture_dispatch<thip_picture_resize_req>(reqs, n, stream, picture_resize_check, picture_resize_launch);
 }
 
 // ---- R'G'B' pictures in (thip_picture_in, k_picture_in in thip_picture_in.h) ------------------------------------------------

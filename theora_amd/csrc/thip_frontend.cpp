@@ -38,6 +38,7 @@
 // translation unit still links on its own against a backend that provides just the decoding slots (the front end's native test
 // drivers stub those); inside libtheora_hip.so the definition in thip_decode.hip is always there.
 #pragma weak thip_picture_out
+#pragma weak thip_picture_resize
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -1450,6 +1451,34 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
         q.dst_pitch[p] = a->dst_pitch[p];
       }
       const int rc = thip_picture_out(&q, 1, a->stream);
+      return rc < 0 ? rc : 0;
+    }
+    case TH_DECCTL_THIP_PICTURE_RESIZE: {
+      if (!d || !buf) return TH_EFAULT;
+      if (buf_sz != sizeof(thip_picture_resize_args)) return TH_EINVAL;
+      if (d->trace || !d->hip || !thip_picture_resize) return TH_EIMPL;
+      if (!d->have_frame) return TH_EINVAL;
+      const thip_picture_resize_args *a = (const thip_picture_resize_args *)buf;
+      thip_picture_resize_req q;
+      memset(&q, 0, sizeof(q));
+      q.state = d->hip;
+      q.bufi = d->early.valid ? (int32_t)d->early.mark[3] : -1;   // (the held frame's buffer: as TH_DECCTL_THIP_PICTURE_OUT)
+      q.format = a->format;
+      q.filter = a->filter;
+      q.elem = a->elem;
+      q.x = a->x;
+      q.y = a->y;
+      q.width = a->width;
+      q.height = a->height;
+      q.out_width = a->out_width;
+      q.out_height = a->out_height;
+      for (int p = 0; p < 3; p++) {
+        q.scale[p] = a->scale[p];
+        q.bias[p] = a->bias[p];
+        q.dst[p] = a->dst[p];
+        q.dst_pitch[p] = a->dst_pitch[p];
+      }
+      const int rc = thip_picture_resize(&q, 1, a->stream);
       return rc < 0 ? rc : 0;
     }
     case TH_DECCTL_SET_GRANPOS: {

@@ -25,6 +25,17 @@ class PictureOutArgs(C.Structure):
                 ("dst_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
 
 
+TH_DECCTL_THIP_PICTURE_RESIZE = 0x7109
+
+
+class PictureResizeArgs(C.Structure):
+    """thip_picture_resize_args (include/theoradec_hip.h)."""
+    _fields_ = [("format", C.c_int32), ("filter", C.c_int32), ("elem", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("out_width", C.c_int32), ("out_height", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3),
+                ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
+
+
 STRIPE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ThImgPlane), C.c_int, C.c_int)
 
 
@@ -179,6 +190,40 @@ class Decoder:
         rc = _on_stream(dev, stream, call)
         if rc < 0:
             raise TheoraHipError("TH_DECCTL_THIP_PICTURE_OUT returned %d" % rc)
+        return out
+
+    def picture_resized(self, size, fmt="rgb_planar", filter="area", rect=None, dtype=None, scale=None, bias=None, stream=None,
+                        out=None):
+        """TH_DECCTL_THIP_PICTURE_RESIZE: the rectangle `rect` = (x, y, width, height) of the frame packetin() last returned (None:
+        the whole coded frame) resampled to size = (out_width, out_height), as a device tensor of theora_amd.picture_resize_shapes'
+        shapes: uint8, or for "rgb_planar" torch.float16 / torch.float32 holding c * scale[k] + bias[k].  Asynchronous on `stream`
+        (default: torch's current stream).  `out`: destination(s) of those shapes to write instead."""
+        import torch
+        from . import FILTERS, PIC_FORMATS, _elem, _on_stream, _pic_dst, picture_resize_shapes
+        dtype = torch.uint8 if dtype is None else dtype
+        shapes = picture_resize_shapes(fmt, size[0], size[1], self.info.pixel_fmt)
+        dev = self.device()
+        if out is None:
+            td = torch.device("cuda", dev)
+            out = (tuple(torch.empty(s, dtype=dtype, device=td) for s in shapes) if fmt == "ycbcr"
+                   else torch.empty(shapes, dtype=dtype, device=td))
+        ptrs, pitches = _pic_dst(fmt, out, shapes, dtype)
+        a = PictureResizeArgs()
+        a.format, a.filter, a.elem = PIC_FORMATS[fmt], FILTERS[filter], _elem(dtype)
+        a.x, a.y, a.width, a.height = rect if rect is not None else (0, 0, 0, 0)
+        a.out_width, a.out_height = size
+        for p in range(3):
+            a.scale[p] = 1.0 if scale is None else scale[p]
+            a.bias[p] = 0.0 if bias is None else bias[p]
+            a.dst[p] = ptrs[p]
+            a.dst_pitch[p] = pitches[p]
+
+        def call(hs):
+            a.stream = hs
+            return self._L.th_decode_ctl(self._dec, TH_DECCTL_THIP_PICTURE_RESIZE, C.byref(a), C.sizeof(a))
+        rc = _on_stream(dev, stream, call)
+        if rc < 0:
+            raise TheoraHipError("TH_DECCTL_THIP_PICTURE_RESIZE returned %d" % rc)
         return out
 
     def slot_trace(self):
