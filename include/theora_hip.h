@@ -263,6 +263,74 @@ typedef struct thip_picture_resize_req {
 int thip_picture_resize(const thip_picture_resize_req *reqs, int n, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * How good is that picture: a rectangle of a state's finished picture compared with another picture in caller DEVICE memory
+ * (k_picture_compare; up to THIP_MAX_BATCH requests a launch, larger calls are chunked).  The sum of squared differences per
+ * plane and per 8x8 block, and an SSIM defined in integers, written to a record in device memory: what the reference's dump_psnr
+ * sums, without the picture leaving the device.
+ *
+ * The definition.  All arithmetic is int64; every / is C's division, rounded toward zero.
+ *
+ * Planes.  Plane p of the state's side is the rectangle thip_picture_out would write for THIP_PIC_YCBCR with the same x, y, width,
+ * height: luma width x height, chroma columns [x >> hdec, (x + width + hdec) >> hdec), rows likewise with vdec, rows top first --
+ * the region dump_psnr sums over and, for th_info's picture region, the planes th_encode_ycbcr_in takes.  Call its size sw x sh
+ * and its samples s[j][i].  ref[p] holds a plane r[j][i] of exactly that size, rows top first.  No byte outside either rectangle
+ * is read.
+ *
+ * THIP_CMP_SSE.  sse[p] = sum over the plane of (s - r)^2, samples[p] = sw sh.  PSNR is the caller's arithmetic; dump_psnr's is
+ *     10 (log10(255^2) + log10(samples) - log10(sse))
+ * per plane, and over the sums of the three planes for the frame.
+ *
+ * block_sse[p] (optional, with either flag).  Entry [j][i] is the same sum over rows 8j .. 8j + 7 and columns 8i .. 8i + 7 of the
+ * rectangle: blocks are counted from the rectangle's top-left, edge blocks hold only the samples inside it, and there are
+ * (sw + 7) / 8 by (sh + 7) / 8 entries, each at most 64 * 255^2.
+ *
+ * THIP_CMP_SSIM.  Windows are 8x8 at step 4 from the rectangle's top-left, and only windows wholly inside it count: x = 4i with
+ * x + 8 <= sw, y = 4j with y + 8 <= sh; a plane narrower or shorter than 8 has none.  With sx, sy, sxx, syy, sxy the sums of s, r,
+ * s^2, r^2 and s r over a window's 64 sample pairs, C1 = 26634 and C2 = 239708 (64^2 (0.01 * 255)^2 and 64^2 (0.03 * 255)^2,
+ * rounded down):
+ *     a = 2 sx sy + C1                  b = sx^2 + sy^2 + C1
+ *     c = 2 (64 sxy - sx sy) + C2       d = (64 sxx - sx^2) + (64 syy - sy^2) + C2
+ *     q1 = (a << 20) / b                q2 = (c << 20) / d                w = q1 q2 / 2^20
+ * ssim_q20[p] is the sum of w over the plane's windows and windows[p] their number: the plane's mean SSIM is
+ * ssim_q20 / windows / 2^20.  0 < a <= b < 2^29, |c| <= d < 2^28 and |q1|, |q2| <= 2^20, so nothing overflows and a 4K plane's
+ * sum stays below 2^40.  w / 2^20 is within 1.3e-5 (3 * 2^-20 + 0.24 / 26634 + 0.16 / 239708: the roundings of the divisions, of
+ * the product and of the two constants) of the usual real-valued SSIM of the window (population moments, K1 = 0.01, K2 = 0.03,
+ * L = 255).
+ *
+ * The fields of a metric whose flag is not set are 0.  The result is overwritten, not accumulated, and every bit of it is
+ * reproducible: the arithmetic is integer and the sums do not depend on the order in which the device adds them.
+ *
+ * The contract is thip_picture_out's: asynchronous; ordered behind the frame; the result visible to work queued on `stream` after
+ * the call; a later frame that overwrites the buffer waits for the compare; stream NULL sends each request down its state's own
+ * stream; all or nothing; calls of more than THIP_MAX_BATCH requests are chunked.  ref may have any alignment and pitch (16
+ * columns that start on 16 bytes are read with one load).  result is memory of the state's device (the device zeroes it on the
+ * stream and adds into it with 64-bit atomics: not host memory) and 8-byte aligned.  THIP_EFAULT: reqs, a state, a result or a
+ * ref plane is NULL.  THIP_EINVAL: n < 0, flags 0 or with unknown bits, a rectangle outside the frame, a ref_pitch smaller than
+ * the row, a block_pitch smaller than the block row where block_sse is given, a misaligned result, a state with no decoded frame,
+ * bufi outside -1..2.  n == 0 does nothing and returns THIP_OK.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_CMP_SSE  1
+#define THIP_CMP_SSIM 2
+typedef struct thip_picture_metrics {      /* 96 bytes, written to device memory */
+  int64_t sse[3];        /* sum of squared differences per plane */
+  int64_t samples[3];    /* samples compared per plane */
+  int64_t ssim_q20[3];   /* sum over the plane's windows of the window SSIM in Q20 (0 without THIP_CMP_SSIM) */
+  int64_t windows[3];    /* windows per plane (0 without THIP_CMP_SSIM) */
+} thip_picture_metrics;
+typedef struct thip_picture_compare_req {
+  thip_state *state;
+  int32_t bufi;                  /* as thip_picture_req */
+  int32_t flags;                 /* THIP_CMP_SSE | THIP_CMP_SSIM, at least one */
+  int32_t x, y, width, height;   /* display coordinates; 0 x 0: the whole frame */
+  const void *ref[3];            /* the other picture: device memory, rows top first */
+  int64_t ref_pitch[3];          /* bytes per row */
+  thip_picture_metrics *result;  /* device memory, 8-byte aligned */
+  uint32_t *block_sse[3];        /* NULL: none; device memory, one uint32 per 8x8 block */
+  int64_t block_pitch[3];        /* elements per row of blocks */
+} thip_picture_compare_req;
+int thip_picture_compare(const thip_picture_compare_req *reqs, int n, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The other direction: an R'G'B' picture in caller DEVICE memory turned into the picture-sized Y'CbCr planes th_encode_ycbcr_in and
  * TH_ENCCTL_THIP_YCBCR_IN_DEVICE accept (k_picture_in; up to THIP_MAX_BATCH requests a launch, larger calls are chunked).
  * TH_ENCCTL_THIP_RGB_IN (theoraenc_hip.h) is this conversion in front of the encoder.

@@ -172,8 +172,8 @@ typedef struct {
    take back: TH_DECCTL_SET_GRANPOS (the counters it sets are frame N's), TH_DECCTL_SET_PPLEVEL with a level above 0 (the held
    frame was decoded unfiltered and untracked), TH_DECCTL_SET_STRIPE_CB (the callback is made inside a frame's
    th_decode_packetin), TH_DECCTL_THIP_SET_DEVICE_DC and _SET_DEVICE_TOKENS.  These leave the held frame alone: every
-   TH_DECCTL_GET_*, TH_DECCTL_SET_PPLEVEL 0, TH_DECCTL_THIP_PREFETCH_PACKET, _PICTURE_OUT, _PICTURE_RESIZE, _SET_HOST_OUTPUT,
-   _SET_DEVICE_LISTS.
+   TH_DECCTL_GET_*, TH_DECCTL_SET_PPLEVEL 0, TH_DECCTL_THIP_PREFETCH_PACKET, _PICTURE_OUT, _PICTURE_RESIZE, _PICTURE_COMPARE,
+   _SET_HOST_OUTPUT, _SET_DEVICE_LISTS.
    The picture th_decode_ycbcr_out handed out for frame N stays valid and unchanged either way.  One frame is held at most: the
    backend can take back one (thip_state_ring_rewind, include/theora_hip.h). */
 #define TH_DECCTL_THIP_PREFETCH_PACKET (0x7105)
@@ -218,6 +218,24 @@ typedef struct thip_picture_resize_args {
   int64_t dst_pitch[3];          /* bytes per row */
   void *stream;                  /* hipStream_t, or NULL */
 } thip_picture_resize_args;
+/* Extension: buf = thip_picture_compare_args.  A rectangle of the frame th_decode_packetin last returned (TH_DUPFRAME: the
+   repeated one) compared with a picture in device memory, as thip_picture_compare does (include/theora_hip.h: the planes, the sums,
+   the integer SSIM).  The fields are thip_picture_compare_req's without state and bufi; x, y, width, height are display coordinates
+   of the coded frame (0 x 0: the whole frame; th_info's picture region is pic_x, pic_y, pic_width, pic_height).  Stream, device,
+   ordering and the frame it measures are TH_DECCTL_THIP_PICTURE_RESIZE's: the request never decodes ahead and never waits on the
+   host.  Returns 0, what thip_picture_compare returns for bad arguments, TH_EINVAL before the first frame, TH_EIMPL in slot-trace
+   mode. */
+#define TH_DECCTL_THIP_PICTURE_COMPARE (0x710A)
+typedef struct thip_picture_compare_args {
+  int32_t flags;                 /* THIP_CMP_SSE | THIP_CMP_SSIM */
+  int32_t x, y, width, height;   /* 0 x 0: the whole coded frame */
+  const void *ref[3];            /* device memory, rows top first */
+  int64_t ref_pitch[3];
+  struct thip_picture_metrics *result;  /* (theora_hip.h) device memory, 8-byte aligned */
+  uint32_t *block_sse[3];        /* NULL: none */
+  int64_t block_pitch[3];
+  void *stream;                  /* hipStream_t, or NULL */
+} thip_picture_compare_args;
 typedef struct thip_slot_trace {
   int64_t ncoded;           /* state_frag_recon calls, in call (= coded) order */
   const int32_t *fragi;     /* _fragi */

@@ -187,9 +187,20 @@
  * packetiser -- reads the converted planes as it reads any other input: the stream is a function of the R'G'B' bytes alone
  * (tests/picture_in_ref.py restates the conversion).
  *
+ * Quality statistics (TH_ENCCTL_THIP_SET_QUALITY_STATS / _GET_QUALITY_STATS).  With the switch on the encoder says how good each
+ * packet is: the packet goes through the encoder's own decoder (the one inter frames use; with inter frames off it now runs too),
+ * and th_encode_packetout queues one thip_picture_compare (theora_hip.h states the sums and the integer SSIM) on the encoder's
+ * stream: the decoder's newest picture over th_info's picture region against the source planes, which stay in the encoder's input
+ * buffer until the next frame comes in.  TH_ENCCTL_THIP_YCBCR_IN_DEVICE therefore first copies the picture region into that buffer,
+ * inside the ordering window the call has anyway, and the frame is coded from the copy: the caller may still overwrite its planes
+ * as soon as the call returns.  A frame the rate controller dropped is measured against the picture a decoder goes on showing
+ * (measured = 1); a TH_ENCCTL_SET_DUP_COUNT duplicate has no source (measured = 0, every sum 0).  The numbers are those a caller
+ * gets who decodes the packets and sums (source - decoded)^2 over the picture region, the reference's dump_psnr among them.  The
+ * switch changes no bit of any packet in any mode.
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / _RGB_IN / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
- * extensions, YCBCR_IN_DEVICE, RGB_IN and GET_DEVICE do.
+ * extensions, YCBCR_IN_DEVICE, RGB_IN, GET_DEVICE and GET_QUALITY_STATS do.
  */
 #ifndef THEORAENC_HIP_H
 #define THEORAENC_HIP_H
@@ -372,6 +383,22 @@ typedef struct thip_enc_rgb_in {
   int64_t pitch[3];        /* bytes a row */
   void *stream;            /* device = 1: a hipStream_t, as in thip_enc_device_in; ignored for device = 0 */
 } thip_enc_rgb_in;
+
+/* Extension: buf = int.  0 (the default): off; THIP_CMP_SSE or THIP_CMP_SSE | THIP_CMP_SSIM (theora_hip.h): on, with those metrics
+   ("Quality statistics" above).  Before the first frame only, else TH_EINVAL; TH_EINVAL for any other value.  Never touches the GPU. */
+#define TH_ENCCTL_THIP_SET_QUALITY_STATS (0x7212)
+/* Extension: buf = thip_enc_quality_stats, describing the last packet th_encode_packetout returned.  Waits for the device (the
+   compare was queued by th_encode_packetout).  With the switch off, and before the first packet, everything is 0. */
+#define TH_ENCCTL_THIP_GET_QUALITY_STATS (0x7213)
+typedef struct thip_enc_quality_stats {
+  int32_t measured;        /* 1: the packet's picture was compared with its source; 0: a duplicate, or the switch is off */
+  int32_t flags;           /* the metrics made: THIP_CMP_* */
+  int64_t sse[3];          /* thip_picture_metrics' fields over th_info's picture region ... */
+  int64_t samples[3];
+  int64_t ssim_q20[3];
+  int64_t windows[3];
+  double compare_ms;       /* the compare's device time (HIP events around it on the encoder's stream) */
+} thip_enc_quality_stats;
 
 typedef struct th_enc_ctx th_enc_ctx;
 

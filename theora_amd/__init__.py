@@ -235,6 +235,22 @@ class State:
         picture_resize([self], [out], [size], fmt, filter, [rect], [bufi], dtype, scale, bias, stream)
         return out
 
+    def compare(self, ref, metrics=("sse",), rect=None, bufi=-1, blocks=False, stream=None):
+        """The state's newest picture (or ring buffer `bufi` as decoded), the rectangle `rect` of it (None: the whole coded frame),
+        compared with `ref`, three uint8 device planes of picture_shapes("ycbcr", ...)'s shapes: picture_compare for one state,
+        with result tensors made here.  Returns the (12,) int64 device tensor of thip_picture_metrics (metrics_dict reads it), or
+        with blocks=True that and the three uint32-valued (int32 dtype) block_sse tensors.  Asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        res = torch.empty(12, dtype=torch.int64, device=dev)
+        blk = None
+        if blocks:
+            x, y, w, h = rect if rect is not None else (0, 0, self.frame_width, self.frame_height)
+            blk = [torch.empty(((sh[0] + 7) // 8, (sh[1] + 7) // 8), dtype=torch.int32, device=dev)
+                   for sh in picture_shapes("ycbcr", w, h, x, self.pixel_fmt, y)]
+        picture_compare([self], [ref], [res], metrics, [rect], [bufi], None if blk is None else [blk], stream)
+        return (res, blk) if blocks else res
+
     def set_eager_output(self, on):
         _lib.check(self._L.thip_state_set_eager_output(self._h, int(bool(on))), "set_eager_output")
 
@@ -438,6 +454,90 @@ def picture_resize(states, outs, sizes, fmt="rgb_planar", filter="area", rects=N
     if n == 0:
         return
     _lib.check(_on_stream(states[0].device, stream, lambda h: L.thip_picture_resize(reqs, n, h)), "thip_picture_resize")
+
+
+# ---------------------------------------------------------------------------------------
+# picture metrics (thip_picture_compare)
+# ---------------------------------------------------------------------------------------
+METRICS = {"sse": _lib.CMP_SSE, "ssim": _lib.CMP_SSIM}
+
+
+def _cmp_flags(metrics):
+    if isinstance(metrics, int):
+        return metrics
+    names = [metrics] if isinstance(metrics, str) else list(metrics)
+    for m in names:
+        if m not in METRICS:
+            raise ValueError("unknown metric %r" % (m,))
+    return sum(METRICS[m] for m in set(names))
+
+
+def psnr(sse, samples):
+    """dump_psnr's formula: 10 (log10(255^2) + log10(samples) - log10(sse)); inf for sse == 0."""
+    import math
+    if samples <= 0:
+        return float("nan")
+    if sse <= 0:
+        return float("inf")
+    return 10.0 * (math.log10(255.0 * 255.0) + math.log10(samples) - math.log10(sse))
+
+
+def metrics_dict(rec):
+    """A thip_picture_metrics record (12 int64 values: a tensor, array or list; sse, samples, ssim_q20, windows by plane) as a dict:
+    sse, samples, ssim_q20, windows (lists by plane), psnr (by plane, then over the three planes' sums: dump_psnr's numbers) and
+    ssim (ssim_q20 / windows / 2^20 by plane; None for a plane without windows).  A device tensor is read here (a host wait)."""
+    v = [int(t) for t in (rec.tolist() if hasattr(rec, "tolist") else rec)]
+    sse, samples, q20, win = v[0:3], v[3:6], v[6:9], v[9:12]
+    return dict(sse=sse, samples=samples, ssim_q20=q20, windows=win,
+                psnr=[psnr(e, n) for e, n in zip(sse, samples)] + [psnr(sum(sse), sum(samples))],
+                ssim=[q / n / float(1 << 20) if n else None for q, n in zip(q20, win)])
+
+
+def picture_compare(states, refs, results, metrics=("sse",), rects=None, bufis=None, blocks=None, stream=None):
+    """thip_picture_compare: per state the rectangle rects[i] (None: the whole coded frame) of its picture against refs[i], three
+    uint8 device planes of picture_shapes("ycbcr", ...)'s shapes for that rectangle (rows may have a pitch of their own).
+    results[i]: an int64 device tensor of 12 elements, overwritten with thip_picture_metrics (metrics_dict reads it).  metrics:
+    "sse", "ssim" or both (or the THIP_CMP_* flags).  blocks[i]: None, or three 2-D int32 device tensors of (rows + 7) // 8 by
+    (columns + 7) // 8 elements that take block_sse.  bufis, stream: as picture_out."""
+    import torch
+    L = _lib.load()
+    n = len(states)
+    if len(refs) != n or len(results) != n:
+        raise ValueError("one reference picture and one result per state")
+    flags = _cmp_flags(metrics)
+    reqs = (_lib.PictureCompareReq * max(n, 1))()
+    for i, st in enumerate(states):
+        x, y, w, h = rects[i] if rects is not None and rects[i] is not None else (0, 0, 0, 0)
+        fw, fh = (w, h) if (w or h) else (st.frame_width, st.frame_height)
+        shapes = picture_shapes("ycbcr", fw, fh, x if (w or h) else 0, st.pixel_fmt, y if (w or h) else 0)
+        r = reqs[i]
+        r.state = st.handle
+        r.bufi = -1 if bufis is None else int(bufis[i])
+        r.flags = flags
+        r.x, r.y, r.width, r.height = x, y, w, h
+        for p in range(3):
+            t = refs[i][p]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+                raise TypeError("reference pictures are uint8 device tensors")
+            if tuple(t.shape) != tuple(shapes[p]) or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+                raise ValueError("reference plane %d of shape %s for a plane of %s" % (p, tuple(t.shape), tuple(shapes[p])))
+            r.ref[p], r.ref_pitch[p] = t.data_ptr(), t.stride(0)
+        res = results[i]
+        if not isinstance(res, torch.Tensor) or res.dtype != torch.int64 or not res.is_cuda or res.numel() != 12 or not res.is_contiguous():
+            raise TypeError("a result is a contiguous int64 device tensor of 12 elements")
+        r.result = res.data_ptr()
+        if blocks is not None and blocks[i] is not None:
+            for p in range(3):
+                b = blocks[i][p]
+                want = ((shapes[p][0] + 7) // 8, (shapes[p][1] + 7) // 8)
+                if not isinstance(b, torch.Tensor) or b.dtype != torch.int32 or not b.is_cuda or b.dim() != 2 or b.stride(1) != 1:
+                    raise TypeError("block sums go to 2-D int32 device tensors")
+                if tuple(b.shape) != want:
+                    raise ValueError("block tensor of shape %s for %s blocks" % (tuple(b.shape), want))
+                r.block_sse[p], r.block_pitch[p] = b.data_ptr(), b.stride(0)
+    if n == 0:
+        return
+    _lib.check(_on_stream(states[0].device, stream, lambda h: L.thip_picture_compare(reqs, n, h)), "thip_picture_compare")
 
 
 # ---------------------------------------------------------------------------------------

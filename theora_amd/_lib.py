@@ -64,6 +64,22 @@ class PictureResizeReq(C.Structure):
                 ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3)]
 
 
+CMP_SSE, CMP_SSIM = 1, 2
+
+
+class PictureMetrics(C.Structure):
+    """thip_picture_metrics (include/theora_hip.h)."""
+    _fields_ = [("sse", C.c_int64 * 3), ("samples", C.c_int64 * 3), ("ssim_q20", C.c_int64 * 3), ("windows", C.c_int64 * 3)]
+
+
+class PictureCompareReq(C.Structure):
+    """thip_picture_compare_req (include/theora_hip.h)."""
+    _fields_ = [("state", C.c_void_p), ("bufi", C.c_int32), ("flags", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("ref", C.c_void_p * 3), ("ref_pitch", C.c_int64 * 3), ("result", C.c_void_p),
+                ("block_sse", C.c_void_p * 3), ("block_pitch", C.c_int64 * 3)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -111,6 +127,7 @@ SYMBOLS = [
     ("thip_state_read_pp_plane", _I, [_P, _I, _P]),
     ("thip_picture_out", _I, [C.POINTER(PictureReq), _I, _P]),
     ("thip_picture_resize", _I, [C.POINTER(PictureResizeReq), _I, _P]),
+    ("thip_picture_compare", _I, [C.POINTER(PictureCompareReq), _I, _P]),
     ("thip_picture_in", _I, [C.POINTER(PictureInReq), _I, _P]),
     ("thip_decode_frames", _I, [C.POINTER(_P), C.POINTER(FrameDesc), _I, _P, C.POINTER(C.c_int32)]),
     ("thip_synchronize", _I, []),

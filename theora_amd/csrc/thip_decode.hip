@@ -178,6 +178,7 @@ extern "C" const char *thip_option_name(int index, const char **help) {
 #include "thip_tokens.h"
 #include "thip_picture.h"
 #include "thip_picture_resize.h"
+#include "thip_picture_compare.h"
 #include "thip_picture_in.h"
 
 // ---------------------------------------------------------------------------------------
@@ -1693,7 +1694,7 @@ int thip_state_read_pp_plane(thip_state *st, int pli, uint8_t *host_out) {
 
 // ---- device-resident pictures (thip_picture_out, k_picture_out in thip_picture.h) ------------------------------------------
 // The rectangle of a request in display coordinates of the coded frame: false if it does not lie inside the frame.
-extern "C++" template <typename Req>   // (thip_picture_req, thip_picture_resize_req)
+extern "C++" template <typename Req>   // (thip_picture_req, thip_picture_resize_req, thip_picture_compare_req)
 static bool picture_rect(const Req &q, const thip_state *st, int &x, int &y, int &w, int &h) {
   if (q.width == 0 && q.height == 0) {
     x = y = 0;
@@ -1934,6 +1935,81 @@ static int picture_resize_launch(const thip_picture_resize_req *const *reqs, int
 
 int thip_picture_resize(const thip_picture_resize_req *reqs, int n, void *stream) {
   return picture_dispatch<thip_picture_resize_req>(reqs, n, stream, picture_resize_check, picture_resize_launch);
+}
+
+// ---- picture metrics (thip_picture_compare, k_picture_compare in thip_picture_compare.h) ------------------------------------
+static int picture_compare_check(const thip_picture_compare_req &q) {
+  const thip_state *st = q.state;
+  if (!st || !q.result) return THIP_EFAULT;
+  for (int p = 0; p < 3; p++)
+    if (!q.ref[p]) return THIP_EFAULT;
+  if (q.flags == 0 || (q.flags & ~(THIP_CMP_SSE | THIP_CMP_SSIM))) return THIP_EINVAL;
+  if (((uintptr_t)q.result) & 7) return THIP_EINVAL;
+  if (q.bufi < -1 || q.bufi > 2 || st->last_decoded < 0) return THIP_EINVAL;
+  int x, y, w, h;
+  if (!picture_rect(q, st, x, y, w, h)) return THIP_EINVAL;
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? st->hdec : 0;
+    const int sw = ((x + w + hd) >> hd) - (x >> hd);
+    if (q.ref_pitch[p] < sw) return THIP_EINVAL;
+    if (q.block_sse[p] && q.block_pitch[p] < (sw + 7) / 8) return THIP_EINVAL;
+  }
+  return THIP_OK;
+}
+
+static void picture_compare_fill(PicCmpReqK &K, const thip_picture_compare_req &q) {
+  const thip_state *st = q.state;
+  memset(&K, 0, sizeof(K));
+  const bool pp = q.bufi < 0 && st->pp_serial == st->frame_serial;   // (as picture_fill)
+  const uint8_t *frame = st->frames[q.bufi < 0 ? st->last_decoded : q.bufi];
+  int x, y, w, h;
+  (void)picture_rect(q, st, x, y, w, h);
+  K.flags = q.flags;
+  K.res = q.result;
+  const int T = (q.flags & THIP_CMP_SSIM) ? 15 : 16;   // the lanes of a tile that count, per axis (k_picture_compare)
+  int tiles = 0;
+  for (int p = 0; p < 3; p++) {
+    const thip_plane_geom &g = st->geom[p];
+    const int hd = p ? st->hdec : 0, vd = p ? st->vdec : 0;
+    K.src[p] = (pp && st->pp_active[p] ? st->pp_frame : frame) + g.plane_off;
+    K.ref[p] = (const uint8_t *)q.ref[p];
+    K.rpitch[p] = q.ref_pitch[p];
+    K.blk[p] = q.block_sse[p];
+    K.bpitch[p] = q.block_pitch[p];
+    K.spitch[p] = g.stride;
+    K.ph[p] = g.height;
+    K.rx[p] = x >> hd;
+    K.ry[p] = y >> vd;
+    K.sw[p] = ((x + w + hd) >> hd) - K.rx[p];
+    K.sh[p] = ((y + h + vd) >> vd) - K.ry[p];
+    K.tpr[p] = (K.sw[p] + 16 * T - 1) / (16 * T);
+    tiles += K.tpr[p] * ((K.sh[p] + 8 * T - 1) / (8 * T));
+    K.tile_end[p] = tiles;
+  }
+}
+
+static int picture_compare_launch(const thip_picture_compare_req *const *reqs, int n, hipStream_t s) {
+  PicCmpBatchK B;
+  int max_tiles = 0;
+  for (int i = 0; i < n; i++) {
+    const int rc = order_behind_previous(reqs[i]->state, s);
+    if (rc < 0) return rc;
+    picture_compare_fill(B.r[i], *reqs[i]);
+    max_tiles = std::max(max_tiles, B.r[i].tile_end[2]);
+    HIP_TRY(hipMemsetAsync(reqs[i]->result, 0, sizeof(thip_picture_metrics), s));   // the kernel adds into it
+  }
+  for (int i = n; i < THIP_MAX_BATCH; i++) memset(&B.r[i], 0, sizeof(B.r[i]));
+  hipLaunchKernelGGL(k_picture_compare, dim3((unsigned)max_tiles, (unsigned)n), dim3(256), 0, s, B);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < n; i++) {
+    const int rc = order_mark(reqs[i]->state, s);
+    if (rc < 0) return rc;
+  }
+  return THIP_OK;
+}
+
+int thip_picture_compare(const thip_picture_compare_req *reqs, int n, void *stream) {
+  return picture_dispatch<thip_picture_compare_req>(reqs, n, stream, picture_compare_check, picture_compare_launch);
 }
 
 // ---- R'G'B' pictures in (thip_picture_in, k_picture_in in thip_picture_in.h) ------------------------------------------------

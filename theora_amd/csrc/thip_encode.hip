@@ -230,6 +230,12 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint8_t *d_pix = nullptr, *h_pix = nullptr;   // host input: the three picture planes, packed
   uint8_t *d_rgb = nullptr, *h_rgb = nullptr;   // TH_ENCCTL_THIP_RGB_IN from host memory: the picture's rows, packed (4 bytes a pixel)
   hipEvent_t ev_conv = nullptr;                 // ... from device memory: the conversion has read the caller's picture
+  // quality statistics (TH_ENCCTL_THIP_SET_QUALITY_STATS): the metrics of the last packet, made on the device and copied to h_qm
+  int qflags = 0;
+  bool q_queued = false;
+  thip_picture_metrics *d_qm = nullptr, *h_qm = nullptr;
+  hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr;
+  thip_enc_quality_stats qstats{};
   size_t pix_off[3], pix_bytes = 0;
   int32_t *d_order = nullptr;
   uint16_t *d_dequant = nullptr;                // [64 qi][3][64]
@@ -385,7 +391,8 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
       (void **)&e->d_pgbase, (void **)&e->d_prec,                                                                    // enc_pack_alloc
       (void **)&e->d_cut,                                                                                            // enc_cut_alloc
-      (void **)&e->d_rgb};                                                                                           // enc_rgb_in
+      (void **)&e->d_rgb,                                                                                            // enc_rgb_in
+      (void **)&e->d_qm};                                                                                            // enc_quality_queue
   for (void **p : dev) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
@@ -397,7 +404,8 @@ static void enc_free_device(th_enc_ctx *e) {
                    (void **)&e->h_rest,                                           // enc_rate_alloc
                    (void **)&e->h_pk, (void **)&e->h_prec,                        // enc_pack_alloc
                    (void **)&e->h_cut,                                            // enc_cut_alloc
-                   (void **)&e->h_rgb};                                           // enc_rgb_in
+                   (void **)&e->h_rgb,                                            // enc_rgb_in
+                   (void **)&e->h_qm};                                            // enc_quality_queue
   for (void **p : host) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
@@ -406,8 +414,9 @@ static void enc_free_device(th_enc_ctx *e) {
   e->pkt_data = nullptr;   // (it may have been h_pk)
   e->pkt_size = 0;
   e->rate_dev = false;
+  e->q_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
-                          &e->ev_c0, &e->ev_c1, &e->ev_conv}) {
+                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -1024,6 +1033,18 @@ static int enc_ycbcr_in_device(th_enc_ctx *e, const thip_enc_device_in *a) {
   hipStream_t cs = (hipStream_t)a->stream;
   ENC_TRY(hipEventRecord(e->ev_in, cs));
   ENC_TRY(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+  if (e->qflags) {   // the source has to outlive the call for the packet's compare: the frame is coded from a copy in d_pix
+    if (!e->ev_conv) ENC_TRY(hipEventCreateWithFlags(&e->ev_conv, hipEventDisableTiming));
+    for (int p = 0; p < 3; p++) {
+      ENC_TRY(hipMemcpy2DAsync(e->d_pix + e->pix_off[p], (size_t)e->cw[p], src[p], (size_t)stride[p], (size_t)e->cw[p], (size_t)e->ch[p],
+                               hipMemcpyDeviceToDevice, e->stream));
+      src[p] = e->d_pix + e->pix_off[p];
+      stride[p] = e->cw[p];
+    }
+    ENC_TRY(hipEventRecord(e->ev_conv, e->stream));   // the caller's planes have been read
+    ENC_TRY(hipStreamWaitEvent(cs, e->ev_conv, 0));
+    return enc_queue_frame(e, src, stride);
+  }
   const int rc = enc_queue_frame(e, src, stride);
   if (rc) return rc;
   ENC_TRY(hipStreamWaitEvent(cs, e->ev_read, 0));
@@ -1552,6 +1573,63 @@ static int enc_get_recon(th_enc_ctx *e, th_img_plane *y) {
   return 0;
 }
 
+// Quality statistics: the decoder's newest picture over the picture region against the source planes in d_pix, queued on the
+// encoder's stream; the metrics go to h_qm.  source: the packet has one (a coded or a dropped frame, not a duplicate).
+static int enc_quality_queue(th_enc_ctx *e, bool source) {
+  memset(&e->qstats, 0, sizeof(e->qstats));
+  e->q_queued = false;
+  if (!e->qflags) return 0;
+  e->qstats.flags = e->qflags;
+  thip_state *st = e->dec ? thip_dec_backend(e->dec) : nullptr;
+  if (!source || !e->have_recon || !st) return 0;
+  DeviceGuard g(e->device);
+  if (!e->d_qm) {
+    ENC_TRY(hipMalloc((void **)&e->d_qm, sizeof(thip_picture_metrics)));
+    ENC_TRY(hipHostMalloc((void **)&e->h_qm, sizeof(thip_picture_metrics), hipHostMallocDefault));
+    ENC_TRY(hipEventCreate(&e->ev_m0));
+    ENC_TRY(hipEventCreate(&e->ev_m1));
+  }
+  thip_picture_compare_req q;
+  memset(&q, 0, sizeof(q));
+  q.state = st;
+  q.bufi = -1;
+  q.flags = e->qflags;
+  q.x = (int32_t)e->info.pic_x;
+  q.y = (int32_t)e->info.pic_y;
+  q.width = (int32_t)e->info.pic_width;
+  q.height = (int32_t)e->info.pic_height;
+  for (int p = 0; p < 3; p++) {
+    q.ref[p] = e->d_pix + e->pix_off[p];
+    q.ref_pitch[p] = e->cw[p];
+  }
+  q.result = e->d_qm;
+  ENC_TRY(hipEventRecord(e->ev_m0, e->stream));
+  if (thip_picture_compare(&q, 1, e->stream)) return TH_EFAULT;
+  ENC_TRY(hipEventRecord(e->ev_m1, e->stream));
+  ENC_TRY(hipMemcpyAsync(e->h_qm, e->d_qm, sizeof(thip_picture_metrics), hipMemcpyDeviceToHost, e->stream));
+  e->qstats.measured = 1;
+  e->q_queued = true;
+  return 0;
+}
+
+static int enc_quality_get(th_enc_ctx *e, thip_enc_quality_stats *out) {
+  if (e->q_queued) {
+    DeviceGuard g(e->device);
+    ENC_TRY(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e->ev_m0, e->ev_m1) == hipSuccess) e->qstats.compare_ms = ms;
+    for (int p = 0; p < 3; p++) {
+      e->qstats.sse[p] = e->h_qm->sse[p];
+      e->qstats.samples[p] = e->h_qm->samples[p];
+      e->qstats.ssim_q20[p] = e->h_qm->ssim_q20[p];
+      e->qstats.windows[p] = e->h_qm->windows[p];
+    }
+    e->q_queued = false;
+  }
+  *out = e->qstats;
+  return 0;
+}
+
 int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
   if (!e || !op) return TH_EFAULT;
   if (e->done) return 0;
@@ -1574,6 +1652,8 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->mstats, 0, sizeof(e->mstats));
     memset(&e->bstats, 0, sizeof(e->bstats));
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
+    const int qrc = enc_quality_queue(e, true);   // (against the picture the decoder goes on showing)
+    if (qrc) return qrc;
   } else if (e->frame_pending) {
     e->frame_pending = false;
     const int rc = enc_finish_frame(e);
@@ -1581,10 +1661,12 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->cstats = e->cnext;
     if (e->frame_key) e->key = e->cur + 1;
     ++e->cur;
-    if (e->inter && e->pkt_size) {
+    if ((e->inter || e->qflags) && e->pkt_size) {
       const int drc = enc_recon(e);
       if (drc) return drc;
     }
+    const int qrc = enc_quality_queue(e, true);
+    if (qrc) return qrc;
     if (e->rate) enc_rate_update(e, e->frame_key, (int64_t)e->pkt_size * 8);
     op->packet = const_cast<uint8_t *>(e->pkt_data);
     op->bytes = (long)e->pkt_size;
@@ -1608,6 +1690,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->mstats, 0, sizeof(e->mstats));
     memset(&e->bstats, 0, sizeof(e->bstats));
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
+    (void)enc_quality_queue(e, false);
   } else {
     return 0;
   }
@@ -1752,6 +1835,17 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->cstats.ratio = t;
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_QUALITY_STATS: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int f = *(const int *)buf;
+      if (f != 0 && f != THIP_CMP_SSE && f != (THIP_CMP_SSE | THIP_CMP_SSIM)) return TH_EINVAL;
+      e->qflags = f;   // (its buffers are made at the first packet measured)
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_QUALITY_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_quality_stats)) return TH_EINVAL;
+      return enc_quality_get(e, (thip_enc_quality_stats *)buf);
     case TH_ENCCTL_THIP_GET_CUT_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_cut_stats)) return TH_EINVAL;
       *(thip_enc_cut_stats *)buf = e->cstats;

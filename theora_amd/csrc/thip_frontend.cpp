@@ -39,6 +39,7 @@
 // drivers stub those); inside libtheora_hip.so the definition in thip_decode.hip is always there.
 #pragma weak thip_picture_out
 #pragma weak thip_picture_resize
+#pragma weak thip_picture_compare
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -1479,6 +1480,31 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
         q.dst_pitch[p] = a->dst_pitch[p];
       }
       const int rc = thip_picture_resize(&q, 1, a->stream);
+      return rc < 0 ? rc : 0;
+    }
+    case TH_DECCTL_THIP_PICTURE_COMPARE: {
+      if (!d || !buf) return TH_EFAULT;
+      if (buf_sz != sizeof(thip_picture_compare_args)) return TH_EINVAL;
+      if (d->trace || !d->hip || !thip_picture_compare) return TH_EIMPL;
+      if (!d->have_frame) return TH_EINVAL;
+      const thip_picture_compare_args *a = (const thip_picture_compare_args *)buf;
+      thip_picture_compare_req q;
+      memset(&q, 0, sizeof(q));
+      q.state = d->hip;
+      q.bufi = d->early.valid ? (int32_t)d->early.mark[3] : -1;   // (the held frame's buffer: as TH_DECCTL_THIP_PICTURE_OUT)
+      q.flags = a->flags;
+      q.x = a->x;
+      q.y = a->y;
+      q.width = a->width;
+      q.height = a->height;
+      q.result = a->result;
+      for (int p = 0; p < 3; p++) {
+        q.ref[p] = a->ref[p];
+        q.ref_pitch[p] = a->ref_pitch[p];
+        q.block_sse[p] = a->block_sse[p];
+        q.block_pitch[p] = a->block_pitch[p];
+      }
+      const int rc = thip_picture_compare(&q, 1, a->stream);
       return rc < 0 ? rc : 0;
     }
     case TH_DECCTL_SET_GRANPOS: {

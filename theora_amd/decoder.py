@@ -36,6 +36,16 @@ class PictureResizeArgs(C.Structure):
                 ("dst", C.c_void_p * 3), ("dst_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
 
 
+TH_DECCTL_THIP_PICTURE_COMPARE = 0x710A
+
+
+class PictureCompareArgs(C.Structure):
+    """thip_picture_compare_args (include/theoradec_hip.h)."""
+    _fields_ = [("flags", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("ref", C.c_void_p * 3), ("ref_pitch", C.c_int64 * 3), ("result", C.c_void_p),
+                ("block_sse", C.c_void_p * 3), ("block_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
+
+
 STRIPE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ThImgPlane), C.c_int, C.c_int)
 
 
@@ -225,6 +235,40 @@ class Decoder:
         if rc < 0:
             raise TheoraHipError("TH_DECCTL_THIP_PICTURE_RESIZE returned %d" % rc)
         return out
+
+    def picture_compare(self, ref, metrics=("sse",), rect=None, stream=None, result=None):
+        """TH_DECCTL_THIP_PICTURE_COMPARE: the rectangle `rect` = (x, y, width, height) of the frame packetin() last returned (None:
+        the whole coded frame) against `ref`, three uint8 device planes of theora_amd.picture_shapes("ycbcr", ...)'s shapes.  Returns
+        the (12,) int64 device tensor of thip_picture_metrics (theora_amd.metrics_dict reads it); `result`: such a tensor to write
+        instead.  Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        from . import _cmp_flags, _on_stream, picture_shapes
+        dev = self.device()
+        if result is None:
+            result = torch.empty(12, dtype=torch.int64, device=torch.device("cuda", dev))
+        a = PictureCompareArgs()
+        a.flags = _cmp_flags(metrics)
+        a.x, a.y, a.width, a.height = rect if rect is not None else (0, 0, 0, 0)
+        x, y, w, h = rect if rect is not None else (0, 0, self.info.frame_width, self.info.frame_height)
+        shapes = picture_shapes("ycbcr", w, h, x, self.info.pixel_fmt, y)      # (the library reads exactly these planes)
+        for p in range(3):
+            t = ref[p]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+                raise TypeError("reference pictures are 2-D uint8 device tensors")
+            if tuple(t.shape) != tuple(shapes[p]) or t.stride(0) < t.shape[1]:
+                raise ValueError("reference plane %d of shape %s for a plane of %s" % (p, tuple(t.shape), tuple(shapes[p])))
+            a.ref[p], a.ref_pitch[p] = t.data_ptr(), t.stride(0)
+        if result.dtype != torch.int64 or result.numel() != 12 or not result.is_cuda or not result.is_contiguous():
+            raise TypeError("a result is a contiguous int64 device tensor of 12 elements")
+        a.result = result.data_ptr()
+
+        def call(hs):
+            a.stream = hs
+            return self._L.th_decode_ctl(self._dec, TH_DECCTL_THIP_PICTURE_COMPARE, C.byref(a), C.sizeof(a))
+        rc = _on_stream(dev, stream, call)
+        if rc < 0:
+            raise TheoraHipError("TH_DECCTL_THIP_PICTURE_COMPARE returned %d" % rc)
+        return result
 
     def slot_trace(self):
         """The accel-vtable slot calls of the last frame as numpy arrays; only on a context

@@ -32,6 +32,8 @@ TH_ENCCTL_THIP_GET_PACK_STATS = 0x720E
 TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES = 0x720F
 TH_ENCCTL_THIP_GET_CUT_STATS = 0x7210
 TH_ENCCTL_THIP_RGB_IN = 0x7211
+TH_ENCCTL_THIP_SET_QUALITY_STATS = 0x7212
+TH_ENCCTL_THIP_GET_QUALITY_STATS = 0x7213
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
 TH_ENCCTL_SET_RATE_FLAGS = 20
@@ -87,6 +89,12 @@ class CutStats(C.Structure):
     """thip_enc_cut_stats (include/theoraenc_hip.h)."""
     _fields_ = [("measured", C.c_int32), ("cut", C.c_int32), ("intra_mbs", C.c_int32), ("ratio", C.c_int32), ("pred", C.c_int64),
                 ("intra", C.c_int64), ("measure_ms", C.c_double)]
+
+
+class QualityStats(C.Structure):
+    """thip_enc_quality_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("measured", C.c_int32), ("flags", C.c_int32), ("sse", C.c_int64 * 3), ("samples", C.c_int64 * 3),
+                ("ssim_q20", C.c_int64 * 3), ("windows", C.c_int64 * 3), ("compare_ms", C.c_double)]
 
 
 class RateStats(C.Structure):
@@ -360,6 +368,27 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_CUT_STATS returned %d" % rc)
         return {k: getattr(s, k) for k, _ in CutStats._fields_}
+
+    def set_quality_stats(self, metrics=("sse",)):
+        """TH_ENCCTL_THIP_SET_QUALITY_STATS, before the first frame: metrics "sse", ("sse", "ssim"), the THIP_CMP_* flags, or
+        None / 0 for off."""
+        from . import _cmp_flags
+        flags = 0 if not metrics else _cmp_flags(metrics)
+        rc, _ = self.ctl(TH_ENCCTL_THIP_SET_QUALITY_STATS, flags)
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_SET_QUALITY_STATS returned %d" % rc)
+
+    def quality_stats(self):
+        """TH_ENCCTL_THIP_GET_QUALITY_STATS of the last packet, as a dict: measured, flags, compare_ms and theora_amd.metrics_dict's
+        keys (sse, samples, psnr, ssim, ...) over th_info's picture region.  Waits for the device."""
+        from . import metrics_dict
+        s = QualityStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_QUALITY_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_QUALITY_STATS returned %d" % rc)
+        d = metrics_dict(list(s.sse) + list(s.samples) + list(s.ssim_q20) + list(s.windows))
+        d.update(measured=s.measured, flags=s.flags, compare_ms=s.compare_ms)
+        return d
 
     def recon(self):
         """TH_ENCCTL_THIP_GET_RECON: the encoder's reconstruction of the last frame (the next one's reference) as three uint8 numpy

@@ -1,6 +1,6 @@
 """The intra encoder (th_encode_*) per frame: the device stage (HIP events around its four launches and read-backs,
 TH_ENCCTL_THIP_GET_TIMES), the host's part of th_encode_packetout (EOB runs, tables, bits), packet bytes and Y/Cb/Cr PSNR of the
-decoded picture -- 720p, 1080p and 4K at 4:2:0, the seeded natural image of tests/enc_ref.py, quality 16 and 48.  Kernel times
+decoded picture (the encoder's own quality statistics, TH_ENCCTL_THIP_GET_QUALITY_STATS, from a run of their own) -- 720p, 1080p and 4K at 4:2:0, the seeded natural image of tests/enc_ref.py, quality 16 and 48.  Kernel times
 come from a separate `rocprofv3 --kernel-trace --stats -- python tools/encode_time.py --frames 8` run.
 
 With --inter N: inter frames with a key frame every N frames (TH_ENCCTL_THIP_SET_INTER_FRAMES) on the panning sequence of
@@ -37,9 +37,25 @@ sys.path.insert(0, ROOT)
 SIZES = {"720p": (1280, 720, None), "1080p": (1920, 1088, (0, 0, 1920, 1080)), "4k": (3840, 2160, None)}
 
 
-def psnr(a, b):
-    mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
-    return 99.0 if mse == 0 else 10 * np.log10(255.0 ** 2 / mse)
+def psnr(sse, samples):
+    """From the encoder's quality statistics (TH_ENCCTL_THIP_GET_QUALITY_STATS): the exact sums the device made."""
+    return 99.0 if sse == 0 else 10 * np.log10(255.0 ** 2 / (sse / samples))
+
+
+def quality_pass(frames, *args, **kw):
+    """The frames once more through an encoder of the same configuration with the quality statistics on -- a run of its own, so
+    that the timed run above stays what it was; the switch changes no packet.  Returns per frame the statistics' dict."""
+    from theora_amd.encoder import Encoder
+    e = Encoder(*args, **kw)
+    e.set_quality_stats("sse")
+    e.header_packets()
+    out = []
+    for f, fr in enumerate(frames):
+        e.encode(fr)
+        e.packetout(f == len(frames) - 1)
+        out.append(e.quality_stats())
+    e.close()
+    return out
 
 
 def main():
@@ -59,7 +75,6 @@ def main():
     if args.inter:
         return main_inter(args)
     from tests import enc_ref
-    from theora_amd.decoder import Decoder
     from theora_amd.encoder import Encoder
     rows = []
     for name, (w, h, pic) in SIZES.items():
@@ -82,15 +97,8 @@ def main():
                     pack.append(e.pack_stats()["pack_ms"])
             st = e.stats()
             e.close()
-            dec = Decoder(hdr)
-            dec.packetin(pkt)
-            got = dec.ycbcr_out()
-            dec.close()
-            x0, y0, pw, ph = p
-            ps = []
-            for pl in range(3):
-                cx, cy, cw, ch = enc_ref.chroma_region(p, 0, pl)
-                ps.append(round(psnr(got[pl][cy:cy + ch, cx:cx + cw], frame[pl]), 2))
+            qs = quality_pass([frame], w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp)[0]
+            ps = [round(psnr(qs["sse"][pl], qs["samples"][pl]), 2) for pl in range(3)]
             r = dict(size=name, quality=q, device_ms=round(float(np.median(dev)), 4), host_ms=round(float(np.median(host)), 4),
                      call_ms=round(float(np.median(wall)), 4), bytes=len(pkt), tokens=st["tokens"],
                      tokens_merged=st["tokens_merged"], psnr=ps)
@@ -105,7 +113,6 @@ def main():
 
 def main_inter(args):
     from tests import enc_inter_ref, enc_ref
-    from theora_amd.decoder import Decoder
     from theora_amd.encoder import Encoder
     rows = []
     n = args.frames + 3
@@ -137,13 +144,9 @@ def main_inter(args):
                 keys += key
                 cuts += e.cut_stats()["cut"]
             e.close()
-            dec = Decoder(hdr)
-            ps = []
-            for f, pkt in enumerate(pkts):
-                dec.packetin(pkt)
-                got = dec.ycbcr_out()
-                ps.append(psnr(got[0][:p[3], :p[2]], frames[f][0]))
-            dec.close()
+            ps = [psnr(qs["sse"][0], qs["samples"][0])
+                  for qs in quality_pass(frames, w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am,
+                                         block_qi=args.block_qi, device_pack=dp, auto_keyframes=ak)]
             r = dict(size=name, quality=q, inter=args.inter, all_modes=am, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
