@@ -786,6 +786,37 @@ int thip_enc_fdct_quantize_batch(int16_t *qdct, int32_t *nonzero, int16_t *dct, 
                                  const void *enquant, int64_t n);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: th_encode_*'s device packetiser (TH_ENCCTL_THIP_SET_DEVICE_PACK, theoraenc_hip.h) on the caller's
+ * tokens and tables.  The same launch functions th_encode_* calls -- EOB runs merged into pieces of at most 4095, the four Huffman
+ * tables of least bits (a tie: the lower index), the bits written MSB first -- with everything a picture would fix given instead.
+ *   d_words   device: the frame's tokens in stream order (zig-zag index first, then plane), one word each:
+ *             token | extra bits << 5 | index << 16 | plane << 22; token 0 is a block's EOB, the others are 7..31
+ *   list_len  host: tokens per (index, plane), [64][3]; only the sum T is used (the words carry their own list), T < 2^31
+ *   codes, lens   host: the 80 tables; lengths 1..32.  Nothing is decoded, so they need not be prefix-free
+ *   groups    work groups, 1..512: the stream is cut into that many spans of a multiple of 256 tokens
+ *   phase     0..7: the bit of byte 0 the token bits start at (the frame header's length mod 8); the bits before it stay 0
+ *   d_packet  device, 4-byte aligned, cap_bytes long: DC table indices (8 bits), the tokens, and the AC table indices in front of
+ *             the first token of an index above 0 (at the end when there is none)
+ * res (host) is filled whenever the sums were made: bytes = (phase + 16 + bits + 7) >> 3.  The capacity rule is th_encode_*'s:
+ * the packet is written when bytes + 4 <= cap_bytes, and then no byte at or beyond 4 * ceil(bytes / 4) is touched; otherwise
+ * nothing is written and THIP_ENC_PACK_NOFIT returned.  Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: a NULL pointer, or a HIP call failed.  THIP_EINVAL: groups or phase out of range, a misaligned d_packet, a length
+ * outside 1..32, T >= 2^31 -- all found before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_ENC_PACK_NOFIT 2
+typedef struct thip_enc_pack_result {   /* 48 bytes */
+  uint64_t bits;                /* of the merged tokens (the 16 bits of table indices not counted) */
+  uint64_t bytes;               /* of the packet from byte 0 */
+  uint32_t tokens;              /* T */
+  uint32_t merged, merged_ac;   /* tokens after the merge; those of a list index above 0 */
+  int32_t huff[4];              /* DC luma, DC chroma, AC luma, AC chroma */
+  uint32_t pad;
+} thip_enc_pack_result;
+int thip_enc_pack_tokens(const uint32_t *d_words, const uint32_t list_len[192], const uint32_t codes[80][32],
+                         const uint8_t lens[80][32], int groups, int phase, uint8_t *d_packet, size_t cap_bytes,
+                         thip_enc_pack_result *res);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

@@ -209,7 +209,8 @@ def huff_group(z):
 
 def encode_frame(planes, fw, fh, fmt, pic, qi, setup):
     """The packet of one frame and what went into it: dict(packet, levels [n,64] zig-zag in coded order, coded_order,
-    dequant [3][64] zig-zag, huff, tokens, tokens_merged)."""
+    dequant [3][64] zig-zag, huff, tokens, tokens_merged, words: the tokens before the merge in stream order, in the word format of
+    thip_encode.h, list_len [64][3])."""
     fr = frame_planes(planes, fw, fh, fmt, pic)
     st = oracle.State(fw, fh, fmt)
     geo = [dict(st.planes[p]) for p in range(3)]
@@ -244,6 +245,9 @@ def encode_frame(planes, fw, fh, fmt, pic, qi, setup):
         for t in toks:
             by_z.setdefault((t[0], int(plane_of[fi])), []).append(t[1:])
     ntok = sum(len(v) for v in by_z.values())
+    words = np.array([(z << 16 | p << 22) | (0 if t[0] == "EOB" else t[0] | t[1] << 5)
+                      for z in range(64) for p in range(3) for t in by_z.get((z, p), [])], np.uint32)
+    list_len = np.array([[len(by_z.get((z, p), [])) for p in range(3)] for z in range(64)], np.int64)
     # merge EOB runs across lists and planes, pieces of at most 4095 placed in the list of their first EOB
     lists, run, rstart = {}, 0, None
 
@@ -295,7 +299,8 @@ def encode_frame(planes, fw, fh, fmt, pic, qi, setup):
                 bw.code(codes[tok])
                 bw.write(extra, nb)
     return dict(packet=bw.bytes(), levels=levels, coded_order=coded, dequant=np.array(dq), huff=hti, tokens=ntok,
-                tokens_merged=nmerged, last_zzi=last_zzi, plane_of=plane_of[coded], flimit=setup.lflims[qi])
+                tokens_merged=nmerged, last_zzi=last_zzi, plane_of=plane_of[coded], flimit=setup.lflims[qi], words=words,
+                list_len=list_len)
 
 
 def oracle_decode(ost, ref):

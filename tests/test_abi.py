@@ -65,6 +65,7 @@ def test_argument_validation_without_gpu():
     assert L.thip_state_token_lists_append(None, 0, 64, None, 0, None, None, None, None) == _lib.EFAULT
     assert L.thip_state_token_lists_abort(None) == _lib.EFAULT
     assert L.thip_state_token_lists_staging(None, None) == _lib.EFAULT
+    assert L.thip_enc_pack_tokens(None, None, None, None, 1, 0, None, 0, None) == _lib.EFAULT
 
 
 def test_loop_filter_init_slot_matches_oracle_table():

@@ -80,6 +80,15 @@ class PictureCompareReq(C.Structure):
                 ("block_sse", C.c_void_p * 3), ("block_pitch", C.c_int64 * 3)]
 
 
+ENC_PACK_NOFIT, ENC_PACK_MAX_GROUPS = 2, 512
+
+
+class EncPackResult(C.Structure):
+    """thip_enc_pack_result (include/theora_hip.h)."""
+    _fields_ = [("bits", C.c_uint64), ("bytes", C.c_uint64), ("tokens", C.c_uint32), ("merged", C.c_uint32),
+                ("merged_ac", C.c_uint32), ("huff", C.c_int32 * 4), ("pad", C.c_uint32)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -179,6 +188,7 @@ SYMBOLS = [
     ("thip_enc1_fdct8x8", None, [_P, _P]),
     ("thip_enc_quantize_batch", _I, [_P, _P, _P, _P, _I64]),
     ("thip_enc_fdct_quantize_batch", _I, [_P, _P, _P, _P, _P, _P, _I64]),
+    ("thip_enc_pack_tokens", _I, [_P, _P, _P, _P, _I, _I, _P, C.c_size_t, C.POINTER(EncPackResult)]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

@@ -584,9 +584,8 @@ static int enc_pack_alloc(th_enc_ctx *e) {
   ENC_TRY(hipMalloc((void **)&e->d_pgbase, (size_t)e->pack_groups * sizeof(PackSum)));
   ENC_TRY(hipMalloc((void **)&e->d_prec, sizeof(PackRec)));
   ENC_TRY(hipHostMalloc((void **)&e->h_prec, sizeof(PackRec), hipHostMallocDefault));
-  std::vector<uint32_t> cl(80 * 32);   // code length | extra bits << 8
-  for (int h = 0; h < 80; h++)
-    for (int tok = 0; tok < 32; tok++) cl[h * 32 + tok] = (uint32_t)e->setup.len[h][tok] | (uint32_t)kTokExtraBits[tok] << 8;
+  std::vector<uint32_t> cl(80 * 32);
+  pack_cl_table(cl.data(), e->setup.len);
   ENC_TRY(hipMemcpy(e->d_pcodes, e->setup.code, 80 * 32 * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_pcl, cl.data(), cl.size() * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMalloc((void **)&e->d_pk, cap));
@@ -594,25 +593,20 @@ static int enc_pack_alloc(th_enc_ctx *e) {
   return 0;
 }
 
+// the context's packetiser buffers as the launches of thip_encode_pack.h take them.  The merged words go where the tokens were
+// before the scatter (d_tok is dead by then).
+static PackBufs enc_pack_bufs(const th_enc_ctx *e) {
+  return PackBufs{e->d_pglast, e->d_phist, e->d_pcodes, e->d_pcl, (uint32_t *)e->d_tok, e->d_pgsum, e->d_pgbase, e->d_prec};
+}
+
 // everything that does not need the header's length, queued behind k_enc_intra_scatter with no host wait: the merge, the tables,
-// the scan, and the record's copy.  The merged words go where the tokens were before the scatter (d_tok is dead by then).
+// the scan, and the record's copy
 static int enc_pack_queue(th_enc_ctx *e) {
   e->frame_dpack = false;
   if (!e->dpack || (uint64_t)e->nfrags * kEncTokWords >= (1ull << 31)) return 0;   // (token indices are 32-bit with room for i + 1)
   if (enc_pack_alloc(e)) return TH_EFAULT;
-  const dim3 grid((unsigned)e->pack_groups), wg(256);
   ENC_TRY(hipEventRecord(e->ev_k0, e->stream));
-  hipLaunchKernelGGL(k_enc_pack_edges, grid, wg, 0, e->stream, e->d_pglast, e->d_phist, (const uint32_t *)e->d_out,
-                     (const uint32_t *)e->d_small);
-  ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_pack_merge, grid, wg, 0, e->stream, e->d_tok, e->d_phist, (const uint32_t *)e->d_pglast,
-                     (const uint32_t *)e->d_out, (const uint32_t *)e->d_small);
-  ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_pack_bits, grid, wg, 0, e->stream, e->d_pgsum, e->d_prec, (const uint32_t *)e->d_tok,
-                     (const uint32_t *)e->d_phist, (const uint32_t *)e->d_pcl, (const uint32_t *)e->d_small);
-  ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_pack_scan, dim3(1), wg, 0, e->stream, e->d_pgbase, e->d_prec, (const PackSum *)e->d_pgsum, e->pack_groups);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(pack_launch_sums(enc_pack_bufs(e), (const uint32_t *)e->d_out, (const uint32_t *)e->d_small, e->pack_groups, e->stream));
   ENC_TRY(hipMemcpyAsync(e->h_prec, e->d_prec, sizeof(PackRec), hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_k1, e->stream));
   e->frame_dpack = true;
@@ -1450,11 +1444,11 @@ static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
   float ms = 0;
   const double pack1 = hipEventElapsedTime(&ms, e->ev_k0, e->ev_k1) == hipSuccess ? ms : 0.0;
   const PackRec rec = *e->h_prec;
-  const uint64_t need = ((uint64_t)phase + 16 + rec.bits + 7) >> 3;
+  const uint64_t need = pack_need_bytes(phase, rec.bits);
   const int capopt = thip_option("enc_pack_cap");
   const uint64_t cap = capopt > 0 ? std::min((uint64_t)capopt, (uint64_t)e->pack_cap) : (uint64_t)e->pack_cap;
   if (rec.total != total) return TH_EFAULT;
-  if (need + 4 > cap) {   // (the memset below rounds up to a word)
+  if (!pack_fits(need, cap)) {
     e->pack_fallbacks++;
     const int rc = enc_pack_host(e, total, overflow);
     e->pstats.pack_ms = pack1;
@@ -1468,13 +1462,8 @@ static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
     ENC_TRY(hipHostMalloc((void **)&e->h_pk, hcap, hipHostMallocDefault));
     e->h_pk_cap = hcap;
   }
-  const size_t nwords = (size_t)((need + 3) >> 2);
   ENC_TRY(hipEventRecord(e->ev_q0, e->stream));
-  ENC_TRY(hipMemsetAsync(e->d_pk, 0, nwords * 4, e->stream));
-  hipLaunchKernelGGL(k_enc_pack_place, dim3((unsigned)e->pack_groups), dim3(256), 0, e->stream, (uint32_t *)e->d_pk, (uint32_t)nwords,
-                     (const PackSum *)e->d_pgbase, (const PackRec *)e->d_prec, (const uint32_t *)e->d_tok,
-                     (const uint32_t *)e->d_pcodes, (const uint32_t *)e->d_pcl, (const uint32_t *)e->d_small, phase);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(pack_launch_place(enc_pack_bufs(e), (const uint32_t *)e->d_small, e->pack_groups, phase, e->d_pk, need, e->stream));
   ENC_TRY(hipMemcpyAsync(e->h_pk + hb, e->d_pk, (size_t)need, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_q1, e->stream));
   memcpy(e->h_pk, e->pkt.data(), hb);
@@ -1949,6 +1938,57 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       return 0;
     default: return TH_EIMPL;
   }
+}
+
+// the device packetiser on the caller's tokens and tables (theora_hip.h): thip_encode_pack.h's launches, as enc_pack_queue and
+// enc_pack_device make them, on the current device's null stream
+int thip_enc_pack_tokens(const uint32_t *d_words, const uint32_t list_len[192], const uint32_t codes[80][32], const uint8_t lens[80][32],
+                         int groups, int phase, uint8_t *d_packet, size_t cap_bytes, thip_enc_pack_result *res) {
+  if (!d_words || !list_len || !codes || !lens || !d_packet || !res) return THIP_EFAULT;
+  if (groups < 1 || groups > kPackMaxGroups || phase < 0 || phase > 7 || ((uintptr_t)d_packet & 3)) return THIP_EINVAL;
+  uint64_t T = 0;
+  for (int k = 0; k < 192; k++) T += list_len[k];
+  if (T >= (1ull << 31)) return THIP_EINVAL;   // (token indices are 32-bit with room for i + 1)
+  for (int h = 0; h < 80; h++)
+    for (int tok = 0; tok < 32; tok++)
+      if (lens[h][tok] < 1 || lens[h][tok] > 32) return THIP_EINVAL;
+  std::vector<uint32_t> cl(80 * 32);
+  pack_cl_table(cl.data(), lens);
+  // one allocation: list_len [192] | hist [320] | codes, cl [80 * 32] | glast [groups] | mtok [T] | gsum, gbase [groups] | rec
+  const size_t words = 192 + 320 + 2 * 80 * 32 + (size_t)groups + (size_t)T, words8 = (words + 1) & ~(size_t)1;
+  uint8_t *d = nullptr;
+  ENC_TRY(hipMalloc((void **)&d, words8 * 4 + 2 * (size_t)groups * sizeof(PackSum) + sizeof(PackRec)));
+  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  uint32_t *w = (uint32_t *)d, *d_len = w;
+  PackBufs p;
+  p.hist = w + 192;
+  p.codes = p.hist + 320;
+  p.cl = p.codes + 80 * 32;
+  p.glast = p.cl + 80 * 32;
+  p.mtok = p.glast + groups;
+  p.gsum = (PackSum *)(w + words8);
+  p.gbase = p.gsum + groups;
+  p.rec = (PackRec *)(p.gbase + groups);
+  hipStream_t stream = nullptr;
+  ENC_TRY(hipMemcpy(d_len, list_len, 192 * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(p.codes, codes, 80 * 32 * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(p.cl, cl.data(), 80 * 32 * 4, hipMemcpyHostToDevice));
+  ENC_TRY(pack_launch_sums(p, d_words, d_len, groups, stream));
+  PackRec rec;
+  ENC_TRY(hipMemcpy(&rec, p.rec, sizeof(rec), hipMemcpyDeviceToHost));
+  if (rec.total != T) return THIP_EFAULT;
+  const uint64_t need = pack_need_bytes(phase, rec.bits);
+  res->bits = rec.bits;
+  res->bytes = need;
+  res->tokens = rec.total;
+  res->merged = rec.merged;
+  res->merged_ac = rec.nac;
+  for (int c = 0; c < 4; c++) res->huff[c] = rec.hti[c];
+  res->pad = 0;
+  if (!pack_fits(need, cap_bytes)) return THIP_ENC_PACK_NOFIT;
+  ENC_TRY(pack_launch_place(p, d_len, groups, phase, d_packet, need, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
 }
 
 }  // extern "C"

@@ -29,13 +29,18 @@
 // order is by index first, so every index-0 token precedes every other.  Bit totals are 64-bit; inside a tile 16 bits suffice
 // (256 x 44 < 65536).
 #pragma once
+#include "thip_bitstream.h"
 #include "thip_encode.h"
 
 namespace thip {
 
 constexpr int kPackMaxGroups = 512;
 constexpr uint32_t kPackEmit = 1u << 21;   // merged word: token | extra << 5 (12 bits) | chroma << 17 | Huffman group << 18 | emit
-constexpr int kPackBufWords = 368;         // a tile's bits: 7 + 8 + 256 x 44 + 8 + 8, and the word alignment at both ends
+// a tile's bits: 7 + 8 + 256 x 44 + 8 + 8, and the word alignment at both ends.  44 is the conservative bound -- a code of 32 bits and
+// the 12 extra bits of the long EOB run in every lane, where a tile holds at most 8 such runs (32 EOBs each).  What tables of 32-bit
+// codes reach, and tests/test_gpu_pack_direct.py drives, is 256 x 42 (the value token of 10 extra bits) + 8 + 8 + 7 + 31 = 10 806
+// bits, 338 words.
+constexpr int kPackBufWords = 368;
 
 struct PackSum {   // a span's sums, or (after the scan) those of all spans before it
   unsigned long long bits;
@@ -295,7 +300,10 @@ __global__ __launch_bounds__(256) void k_enc_pack_place(uint32_t *pk, uint32_t c
   uint32_t acb = base.ac;
   const bool g_first = blockIdx.x == 0, g_last = blockIdx.x == gridDim.x - 1;
   uint32_t ntiles = (b - a + 255u) / 256u;
-  if ((g_first || g_last) && !ntiles) ntiles = 1;   // (the table indices in front and, with no AC token, at the end)
+  // the table indices in front and, with no AC token, at the end, also where the span is empty.  (With no token of a class every
+  // table ties at 0 bits and the indices are 0, which the memset wrote: in an empty span this states where they go and changes
+  // no byte.)
+  if ((g_first || g_last) && !ntiles) ntiles = 1;
   const uint32_t hdr_dc = (uint32_t)(hti[0] << 4 | hti[1]), hdr_ac = (uint32_t)(hti[2] << 4 | hti[3]);
   for (uint32_t t = 0; t < ntiles; t++) {
     const uint32_t i = a + t * 256u + threadIdx.x;
@@ -349,6 +357,54 @@ __global__ __launch_bounds__(256) void k_enc_pack_place(uint32_t *pk, uint32_t c
     run += tbits;
     acb += tac;
   }
+}
+
+// ---- the launches, stated once: th_encode_* (thip_encode.hip) and thip_enc_pack_tokens (theora_hip.h) both call these -----------
+struct PackBufs {                  // device memory of one packetiser
+  uint32_t *glast, *hist;          // [groups], [320]
+  uint32_t *codes, *cl;            // [80][32]: the codes; code length | extra bits << 8 (pack_cl_table)
+  uint32_t *mtok;                  // [T]: the merged words
+  PackSum *gsum, *gbase;           // [groups]
+  PackRec *rec;
+};
+
+inline void pack_cl_table(uint32_t cl[80 * 32], const uint8_t len[80][32]) {
+  for (int h = 0; h < 80; h++)
+    for (int tok = 0; tok < 32; tok++) cl[h * 32 + tok] = (uint32_t)len[h][tok] | (uint32_t)kTokExtraBits[tok] << 8;
+}
+
+// everything that does not need the phase: the merge, the tables, the sums and their scan.  words: the token words in stream order;
+// list_len: 192 words whose sum is T; groups: 1..kPackMaxGroups.  p.rec holds the record when the stream gets there.
+inline hipError_t pack_launch_sums(const PackBufs &p, const uint32_t *words, const uint32_t *list_len, int groups, hipStream_t stream) {
+  const dim3 grid((unsigned)groups), wg(256);
+  hipError_t rc;
+  hipLaunchKernelGGL(k_enc_pack_edges, grid, wg, 0, stream, p.glast, p.hist, words, list_len);
+  if ((rc = hipGetLastError()) != hipSuccess) return rc;
+  hipLaunchKernelGGL(k_enc_pack_merge, grid, wg, 0, stream, p.mtok, p.hist, (const uint32_t *)p.glast, words, list_len);
+  if ((rc = hipGetLastError()) != hipSuccess) return rc;
+  hipLaunchKernelGGL(k_enc_pack_bits, grid, wg, 0, stream, p.gsum, p.rec, (const uint32_t *)p.mtok, (const uint32_t *)p.hist,
+                     (const uint32_t *)p.cl, list_len);
+  if ((rc = hipGetLastError()) != hipSuccess) return rc;
+  hipLaunchKernelGGL(k_enc_pack_scan, dim3(1), wg, 0, stream, p.gbase, p.rec, (const PackSum *)p.gsum, groups);
+  return hipGetLastError();
+}
+
+// the bytes the token bits take from bit `phase` of byte 0, given the record's bits; and whether they fit a buffer of `cap` bytes
+// (pack_launch_place zeroes whole words)
+inline uint64_t pack_need_bytes(int phase, uint64_t bits) { return ((uint64_t)phase + 16 + bits + 7) >> 3; }
+inline bool pack_fits(uint64_t need, uint64_t cap) { return need + 4 <= cap; }
+
+// the bits, after pack_launch_sums on the same stream with the same list_len and groups: pk (4-byte aligned, pack_fits(need, its
+// size)) is zeroed over the packet's words and written; nothing at or beyond byte 4 * ceil(need / 4) is touched
+inline hipError_t pack_launch_place(const PackBufs &p, const uint32_t *list_len, int groups, int phase, uint8_t *pk, uint64_t need,
+                                    hipStream_t stream) {
+  const size_t nwords = (size_t)((need + 3) >> 2);
+  const hipError_t rc = hipMemsetAsync(pk, 0, nwords * 4, stream);
+  if (rc != hipSuccess) return rc;
+  hipLaunchKernelGGL(k_enc_pack_place, dim3((unsigned)groups), dim3(256), 0, stream, (uint32_t *)pk, (uint32_t)nwords,
+                     (const PackSum *)p.gbase, (const PackRec *)p.rec, (const uint32_t *)p.mtok, (const uint32_t *)p.codes,
+                     (const uint32_t *)p.cl, list_len, phase);
+  return hipGetLastError();
 }
 
 }  // namespace thip

@@ -433,6 +433,23 @@ class Encoder:
             pass
 
 
+def pack_tokens(words_ptr, list_len, codes, lens, groups, phase, packet_ptr, cap_bytes):
+    """thip_enc_pack_tokens (include/theora_hip.h): the device packetiser on the caller's tokens and tables, a test and diagnostic
+    entry.  words_ptr, packet_ptr: device addresses (a tensor's data_ptr(); None is NULL); list_len [64][3], codes [80][32] and lens
+    [80][32]: anything numpy converts (None is NULL).  Returns (the entry's return code, dict of thip_enc_pack_result); nothing
+    is raised, the refusals are the caller's to look at."""
+    L = _lib.load()
+    keep = [None if a is None else np.ascontiguousarray(a, t).reshape(-1) for a, t in
+            ((list_len, np.uint32), (codes, np.uint32), (lens, np.uint8))]
+    for a, n in zip(keep, (192, 80 * 32, 80 * 32)):
+        if a is not None and a.size != n:
+            raise ValueError("pack_tokens: an array of %d entries where %d are expected" % (a.size, n))
+    res = _lib.EncPackResult()
+    rc = L.thip_enc_pack_tokens(words_ptr, *[None if a is None else a.ctypes.data for a in keep], int(groups), int(phase), packet_ptr,
+                                int(cap_bytes), C.byref(res))
+    return rc, dict(bits=res.bits, bytes=res.bytes, tokens=res.tokens, merged=res.merged, merged_ac=res.merged_ac, huff=list(res.huff))
+
+
 def ogg_stream(header_packets, data_packets, serialno=0x7E0):
     """One Ogg logical stream (bytes) through the library's writer (include/thip_ogg.h): the headers, a flush after the setup
     header, then data_packets as (payload, granulepos, e_o_s)."""
