@@ -817,6 +817,63 @@ int thip_enc_pack_tokens(const uint32_t *d_words, const uint32_t list_len[192], 
                          thip_enc_pack_result *res);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the device stage of a th_encode_* inter frame (theoraenc_hip.h, "Inter frames" and "All eight
+ * modes") on the caller's planes, lambda and tables.  The same launch functions th_encode_* calls -- the motion search, the mode
+ * decision, prediction + transform + quantiser, the DC residuals -- with everything a stream would fix given instead, and their
+ * intermediate results handed out.  Every pointer but `dequant` is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*   as th_info's: the frame a multiple of 16 each way, the picture region inside it (pic_y from the top)
+ *   src, src_pitch   the picture's top-left pixel of each plane, rows top first (as TH_ENCCTL_THIP_YCBCR_IN_DEVICE takes a picture-
+ *                    sized buffer): any base address, any pitch not below the plane's picture width; outside the picture the
+ *                    source is its edge, clamped outward
+ *   prev, gold, ref_pitch   the references: three frame-sized planes each in BITSTREAM row order (row 0 is the bottom row, spec
+ *                    2.2), no border, PREV and GOLD sharing one pitch per plane.  classes 2: five modes, gold all NULL; classes 3:
+ *                    all eight modes and three DC classes, gold all given
+ *   lambda           the search's weight (th_encode_* uses the inter luma step at zig-zag index 1), 0..2^24
+ *   dequant          HOST, [2][3][64]: the intra then the inter table of each plane, zig-zag order, every entry 1..32767
+ *   stages           what to run, an OR of
+ *     THIP_ENC_INTER_SEARCH  the search alone: stats [nmbs] receives x = S0, y = Smv, z = SI, w = mvx & 0xFF | (mvy & 0xFF) << 8 of
+ *                            every macro block (raster order, rows from the bottom; 16 bytes each) against PREV
+ *     THIP_ENC_INTER_DECIDE  the search with the decision: words [nmbs] receives mode | mvx << 8 | mvy << 16 (4 bytes each; classes
+ *                            2) or the 16-byte words of all eight modes (classes 3: x = mode | vector << 8, y, z = the four block
+ *                            vectors of MV_FOUR, w = the GOLD search's vector).  With SEARCH and classes 2, words_from_stats (may be
+ *                            NULL) receives the 4-byte words made from stats and lambda without a second search
+ *     THIP_ENC_INTER_CODE    prediction, transform and quantiser, then the DC residuals, over `words` (the caller's, or DECIDE's
+ *                            when both are asked for).  Out, each may be NULL: levels [nfrags][64] (zig-zag, CODED order), dcq
+ *                            [nfrags] (the quantised DCs, raster order), cmap [nfrags] (0 uncoded, 1 intra, 2 PREV, 3 GOLD), dcr
+ *                            [nfrags] (the DC residual of a coded fragment, 0 of an uncoded one)
+ *     THIP_ENC_INTER_DC      alone: the DC residuals of the caller's cmap and dcq into dcr; no plane is read.  The entry reads
+ *                            cmap back and forms on the host what the quantising kernel leaves for this one: the last coded
+ *                            fragment (+1) of every 256 raster fragments and class
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req NULL, a plane, table, input or stage output that is needed NULL (gold with classes 3 included), or a HIP call
+ * failed.  THIP_EINVAL: stages 0, unknown, or DC combined with another; a frame size not a positive multiple of 16 below 2^20, or
+ * more than 2^24 fragments; a pixel format that is none; classes not 2 or 3; gold given with classes 2; a picture region outside
+ * the frame; a pitch too small (ref_pitch also: above 2^31 - 1); lambda out of range; a table entry out of range;
+ * words_from_stats without SEARCH and DECIDE or with classes 3; stats, 16-byte words or levels not 16-byte aligned, 4-byte words not
+ * 4-byte, dcq or dcr not 2-byte aligned -- all found before a device is touched.  THIP_EINVAL also for a cmap value above
+ * `classes` in stage DC, found when cmap has been read back.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_ENC_INTER_SEARCH 1
+#define THIP_ENC_INTER_DECIDE 2
+#define THIP_ENC_INTER_CODE 4
+#define THIP_ENC_INTER_DC 8
+typedef struct thip_enc_inter_req {   /* 224 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t stages, lambda, classes;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  const uint8_t *prev[3], *gold[3];
+  int64_t ref_pitch[3];
+  const uint16_t *dequant;
+  void *stats, *words, *words_from_stats;
+  int16_t *levels, *dcq;
+  uint8_t *cmap;
+  int16_t *dcr;
+} thip_enc_inter_req;
+int thip_enc_inter_stage(const thip_enc_inter_req *req);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

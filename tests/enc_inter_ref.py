@@ -36,8 +36,9 @@ def predict(ref, x, y, mvx, mvy, qpx, qpy):
     return (a + b) >> 1
 
 
-def motion_search(src, ref, lam):
-    """Luma search of every macro block (raster, rows from the bottom): (pixel mode, mvx, mvy, S0, SI, Smv) arrays."""
+def search_stats(src, ref):
+    """Luma search of every macro block (raster, rows from the bottom), what of it does not depend on lambda: (mvx, mvy, S0, SI,
+    Smv) arrays, the vector the half-pel one found."""
     H, W = src.shape
     nmy, nmx = H // 16, W // 16
     s = src.astype(np.int64)
@@ -69,12 +70,23 @@ def motion_search(src, ref, lam):
     b4 = sblk.reshape(-1, 2, 8, 2, 8).transpose(0, 1, 3, 2, 4).reshape(-1, 4, 64)
     mean = (b4.sum(2) + 32) >> 6
     si = np.abs(b4 - mean[:, :, None]).sum((1, 2))
+    return mvx, mvy, s0, si, smv
+
+
+def decide(stats, lam):
+    """The five-mode rule over search_stats' arrays: (pixel mode, mvx, mvy, S0, SI, Smv), the vector zero unless MV."""
+    mvx, mvy, s0, si, smv = stats
     mode = np.where(smv + lam < s0, MV, NOMV)
     sinter = np.where(mode == MV, smv, s0)
     mode = np.where(si + 4 * lam < sinter, INTRA, mode)
     mvx = np.where(mode == MV, mvx, 0)
     mvy = np.where(mode == MV, mvy, 0)
     return mode, mvx, mvy, s0, si, smv
+
+
+def motion_search(src, ref, lam):
+    """Luma search of every macro block (raster, rows from the bottom): (pixel mode, mvx, mvy, S0, SI, Smv) arrays."""
+    return decide(search_stats(src, ref), lam)
 
 
 class Geometry:
@@ -220,28 +232,8 @@ class InterEncoder:
         lam = int(tabs[(1, 0)][1])
         pix, mvx, mvy = motion_search(src[0], ref[0], lam)[:3]
         # blocks: prediction, residual, transform, quantiser (raster order)
-        lev = np.zeros((geo.nfrags, 64), np.int64)
-        qti_of = np.zeros(geo.nfrags, np.int64)
-        for p, g in enumerate(geo.planes):
-            nh, nv = g["nhfrags"], g["nvfrags"]
-            fi = g["froffset"] + np.arange(g["nfrags"])
-            mb = geo.mb_of[fi]
-            fy, fx = (fi - g["froffset"]) // nh, (fi - g["froffset"]) % nh
-            r = np.arange(8)
-            Y = fy[:, None, None] * 8 + r[None, :, None]
-            X = fx[:, None, None] * 8 + r[None, None, :]
-            pred = predict(ref[p], X, Y, mvx[mb][:, None, None], mvy[mb][:, None, None], p > 0 and geo.hdec, p > 0 and geo.vdec)
-            intra = pix[mb] == INTRA
-            pred[intra] = 128
-            res = (src[p][Y, X] - pred).reshape(-1, 64)
-            qti = np.where(intra, 0, 1)
-            qti_of[fi] = qti
-            dct = oracle.fdct8x8_batch(res.astype(np.int16))
-            for t in range(2):
-                sel = qti == t
-                if sel.any():
-                    q, _ = oracle.quantize_batch(dct[sel], tabs[(t, p)].astype(np.uint16))
-                    lev[fi[sel]] = q
+        from tests import inter_stage_ref   # (it imports this module)
+        lev, qti_of = inter_stage_ref.levels_of(geo, src, ref, None, pix[geo.mb_of], mvx[geo.mb_of], mvy[geo.mb_of], tabs)
         cls = np.where(qti_of == 0, 1, 2)
         coded = (pix[geo.mb_of] != NOMV) | (lev != 0).any(1)
         ncoded = [int(coded[geo.froff[p]:geo.froff[p] + g["nfrags"]].sum()) for p, g in enumerate(geo.planes)]

@@ -68,10 +68,20 @@ def half_pel(s, ref, best, x0, y0, size):
     return cur >> 32, 2 * bdx + k9 % 3 - 1, 2 * bdy + k9 // 3 - 1
 
 
-def motion_search(src, prev, gold, lam):
-    """The eight-mode search and decision of every macro block (raster, rows from the bottom).  Returns a dict of arrays: pix (the
-    pixel mode: NOMV, INTRA, MV, GOLDEN_NOMV, GOLDEN_MV or MV_FOUR), mv [nmbs, 2] (the vector of MV or GOLDEN_MV, else 0),
-    bmv [nmbs, 4, 2] (the block vectors of MV_FOUR, else 0) and the costs."""
+def intra_sad(s):
+    """SI of every macro block of luma s (bitstream rows): the SAD of its four luma blocks against their rounded means."""
+    H, W = s.shape
+    n = (H // 16) * (W // 16)
+    y0 = (np.arange(n) // (W // 16)) * 16
+    x0 = (np.arange(n) % (W // 16)) * 16
+    blk = s[(y0[:, None, None] + np.arange(16)[None, :, None]), (x0[:, None, None] + np.arange(16)[None, None, :])]
+    b4 = blk.reshape(-1, 2, 8, 2, 8).transpose(0, 1, 3, 2, 4).reshape(-1, 4, 64)
+    return np.abs(b4 - ((b4.sum(2) + 32) >> 6)[:, :, None]).sum((1, 2))
+
+
+def search_all(src, prev, gold):
+    """Everything of the eight-mode search that does not depend on lambda, for every macro block (raster, rows from the bottom):
+    a dict of the SADs (s0, smv, s4, g0, gmv, si) and the vectors found (mvx, mvy; gvx, gvy; bvx, bvy [nmbs, 4])."""
     H, W = src.shape
     nmy, nmx = H // 16, W // 16
     n = nmy * nmx
@@ -86,15 +96,23 @@ def motion_search(src, prev, gold, lam):
     s4 = sb.reshape(n, 4).sum(1)
     gbest, _, g0 = full_pel(s, gold, False)
     gmv, gvx, gvy = half_pel(s, gold, gbest, x0, y0, 16)
-    blk = s[(y0[:, None, None] + np.arange(16)[None, :, None]), (x0[:, None, None] + np.arange(16)[None, None, :])]
-    b4 = blk.reshape(-1, 2, 8, 2, 8).transpose(0, 1, 3, 2, 4).reshape(-1, 4, 64)
-    si = np.abs(b4 - ((b4.sum(2) + 32) >> 6)[:, :, None]).sum((1, 2))
+    return dict(s0=s0, smv=smv, s4=s4, g0=g0, gmv=gmv, si=intra_sad(s), mvx=mvx, mvy=mvy, gvx=gvx, gvy=gvy,
+                bvx=bvx.reshape(n, 4), bvy=bvy.reshape(n, 4))
+
+
+def decide(ms, lam):
+    """The eight-mode decision of theoraenc_hip.h over search_all's dict: it gains pix (the pixel mode: NOMV, INTRA, MV,
+    GOLDEN_NOMV, GOLDEN_MV or MV_FOUR), mv [nmbs, 2] (the vector of MV or GOLDEN_MV, else 0) and bmv [nmbs, 4, 2] (the block
+    vectors of MV_FOUR, else 0); margins: left side less right side of the cascade's five inequalities, in its order."""
+    s0, smv, s4, g0, gmv, si = (ms[k] for k in ("s0", "smv", "s4", "g0", "gmv", "si"))
+    n = len(s0)
     # 1. PREV, one vector
     mv_win = smv + lam < s0
     pix = np.where(mv_win, MV, NOMV)
     C = np.where(mv_win, smv + lam, s0)
     S = np.where(mv_win, smv, s0)
     # 2. four vectors
+    C1 = C
     four = s4 + 4 * lam < C
     pix, C, S = np.where(four, MV_FOUR, pix), np.where(four, s4 + 4 * lam, C), np.where(four, s4, S)
     # 3. GOLD
@@ -105,13 +123,19 @@ def motion_search(src, prev, gold, lam):
     gw = CG < C
     pix, S = np.where(gw, gpix, pix), np.where(gw, SG, S)
     # 4. INTRA
+    margins = [smv + lam - s0, s4 + 4 * lam - C1, gmv + 2 * lam - (g0 + lam), CG - C, si + 4 * lam - S]
     pix = np.where(si + 4 * lam < S, INTRA, pix)
     mv = np.zeros((n, 2), np.int64)
-    mv[pix == MV] = np.stack([mvx, mvy], 1)[pix == MV]
-    mv[pix == GOLDEN_MV] = np.stack([gvx, gvy], 1)[pix == GOLDEN_MV]
+    mv[pix == MV] = np.stack([ms["mvx"], ms["mvy"]], 1)[pix == MV]
+    mv[pix == GOLDEN_MV] = np.stack([ms["gvx"], ms["gvy"]], 1)[pix == GOLDEN_MV]
     bmv = np.zeros((n, 4, 2), np.int64)
-    bmv[pix == MV_FOUR] = np.stack([bvx, bvy], 1).reshape(n, 4, 2)[pix == MV_FOUR]
-    return dict(pix=pix, mv=mv, bmv=bmv, s0=s0, smv=smv, s4=s4, g0=g0, gmv=gmv, si=si)
+    bmv[pix == MV_FOUR] = np.stack([ms["bvx"], ms["bvy"]], 2)[pix == MV_FOUR]
+    return dict(ms, pix=pix, mv=mv, bmv=bmv, margins=margins)
+
+
+def motion_search(src, prev, gold, lam):
+    """The eight-mode search and decision of every macro block (raster, rows from the bottom): decide over search_all."""
+    return decide(search_all(src, prev, gold), lam)
 
 
 def fragment_vectors(geo, pix, mv, bmv):
@@ -142,8 +166,9 @@ def fragment_vectors(geo, pix, mv, bmv):
     return vx, vy
 
 
-def dc_residuals(geo, lev, coded, cls, nclasses):
-    """Spec 7.8 with reference classes 1..nclasses: dcr [nfrags] (the coded fragments' DC residuals)."""
+def dc_residuals(geo, lev, coded, cls, nclasses, trace=None):
+    """Spec 7.8 with reference classes 1..nclasses: dcr [nfrags] (the coded fragments' DC residuals).  trace (a list): gains
+    (fragment, class, neighbour mask, which of the three 128-range corrections of mask 7 / 15 applied, else 0) per coded fragment."""
     dcr = np.zeros(geo.nfrags, np.int64)
     tdiv = lambda a, b: int(a / b) if a >= 0 else -int(-a / b)   # C division towards zero
     for p, g in enumerate(geo.planes):
@@ -156,7 +181,7 @@ def dc_residuals(geo, lev, coded, cls, nclasses):
             c = cls[f]
             fy, fx = loc // nh, loc % nh
             same = lambda q: coded[q] and cls[q] == c
-            m, l, ul, u, ur = 0, 0, 0, 0, 0
+            m, l, ul, u, ur, fix = 0, 0, 0, 0, 0, 0
             if fx > 0 and same(f - 1):
                 m, l = m | 1, lev[f - 1, 0]
             if fy > 0:
@@ -187,11 +212,13 @@ def dc_residuals(geo, lev, coded, cls, nclasses):
             else:
                 pred = tdiv(29 * (l + u) - 26 * ul, 32)
                 if abs(pred - u) > 128:
-                    pred = u
+                    pred, fix = u, 1
                 elif abs(pred - l) > 128:
-                    pred = l
+                    pred, fix = l, 2
                 elif abs(pred - ul) > 128:
-                    pred = ul
+                    pred, fix = ul, 3
+            if trace is not None:
+                trace.append((f, int(c), m, fix))
             dcr[f] = lev[f, 0] - pred
             last[c] = int(lev[f, 0])
     return dcr
@@ -222,29 +249,8 @@ class ModesEncoder(IR.InterEncoder):
         fpix = pix[geo.mb_of]
         fgold = (fpix == GOLDEN_NOMV) | (fpix == GOLDEN_MV)
         # blocks: prediction, residual, transform, quantiser (raster order)
-        lev = np.zeros((geo.nfrags, 64), np.int64)
-        qti_of = np.zeros(geo.nfrags, np.int64)
-        for p, g in enumerate(geo.planes):
-            nh = g["nhfrags"]
-            fi = g["froffset"] + np.arange(g["nfrags"])
-            fy, fx = (fi - g["froffset"]) // nh, (fi - g["froffset"]) % nh
-            r = np.arange(8)
-            Y = fy[:, None, None] * 8 + r[None, :, None]
-            X = fx[:, None, None] * 8 + r[None, None, :]
-            qx, qy = p > 0 and geo.hdec, p > 0 and geo.vdec
-            vx, vy = fvx[fi][:, None, None], fvy[fi][:, None, None]
-            pred = np.where(fgold[fi][:, None, None], predict(gold[p], X, Y, vx, vy, qx, qy), predict(prev[p], X, Y, vx, vy, qx, qy))
-            intra = fpix[fi] == INTRA
-            pred[intra] = 128
-            res = (src[p][Y, X] - pred).reshape(-1, 64)
-            qti = np.where(intra, 0, 1)
-            qti_of[fi] = qti
-            dct = oracle.fdct8x8_batch(res.astype(np.int16))
-            for t in range(2):
-                sel = qti == t
-                if sel.any():
-                    q, _ = oracle.quantize_batch(dct[sel], tabs[(t, p)].astype(np.uint16))
-                    lev[fi[sel]] = q
+        from tests import inter_stage_ref   # (it imports this module)
+        lev, qti_of = inter_stage_ref.levels_of(geo, src, prev, gold, fpix, fvx, fvy, tabs)
         cls = np.where(qti_of == 0, 1, np.where(fgold, 3, 2))
         coded = (fpix != NOMV) | (lev != 0).any(1)
         ncoded = [int(coded[geo.froff[p]:geo.froff[p] + g["nfrags"]].sum()) for p, g in enumerate(geo.planes)]

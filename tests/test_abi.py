@@ -66,6 +66,9 @@ def test_argument_validation_without_gpu():
     assert L.thip_state_token_lists_abort(None) == _lib.EFAULT
     assert L.thip_state_token_lists_staging(None, None) == _lib.EFAULT
     assert L.thip_enc_pack_tokens(None, None, None, None, 1, 0, None, 0, None) == _lib.EFAULT
+    assert L.thip_enc_inter_stage(None) == _lib.EFAULT
+    assert C.sizeof(_lib.EncInterReq) == 224
+    assert L.thip_enc_inter_stage(C.byref(_lib.EncInterReq())) == _lib.EINVAL   # (no stage)
 
 
 def test_loop_filter_init_slot_matches_oracle_table():

@@ -89,6 +89,20 @@ class EncPackResult(C.Structure):
                 ("merged_ac", C.c_uint32), ("huff", C.c_int32 * 4), ("pad", C.c_uint32)]
 
 
+ENC_INTER_SEARCH, ENC_INTER_DECIDE, ENC_INTER_CODE, ENC_INTER_DC = 1, 2, 4, 8
+
+
+class EncInterReq(C.Structure):
+    """thip_enc_inter_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
+                ("stages", C.c_int32), ("lam", C.c_int32), ("classes", C.c_int32),
+                ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("prev", C.c_void_p * 3), ("gold", C.c_void_p * 3),
+                ("ref_pitch", C.c_int64 * 3), ("dequant", C.c_void_p), ("stats", C.c_void_p), ("words", C.c_void_p),
+                ("words_from_stats", C.c_void_p), ("levels", C.c_void_p), ("dcq", C.c_void_p), ("cmap", C.c_void_p),
+                ("dcr", C.c_void_p)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -189,6 +203,7 @@ SYMBOLS = [
     ("thip_enc_quantize_batch", _I, [_P, _P, _P, _P, _I64]),
     ("thip_enc_fdct_quantize_batch", _I, [_P, _P, _P, _P, _P, _P, _I64]),
     ("thip_enc_pack_tokens", _I, [_P, _P, _P, _P, _I, _I, _P, C.c_size_t, C.POINTER(EncPackResult)]),
+    ("thip_enc_inter_stage", _I, [C.POINTER(EncInterReq)]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

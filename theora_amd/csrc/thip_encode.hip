@@ -650,35 +650,38 @@ static int enc_modes_alloc(th_enc_ctx *e) {
   return 0;
 }
 
-// The launches of an inter frame, written once for its two sets of kernels: the search, the two quantising kernels and the DC
-// kernel of one macro-block word (d_mb), with `classes` reference classes; gold: GOLD for the kernels that read it, else nothing.
+// The launches of an inter frame, written once for its two sets of kernels: the search, the transform-and-quantise and the DC
+// launch of one macro-block word (d_mb) are the launch functions beside the kernels (thip_encode_inter.h, thip_encode_modes.h),
+// which thip_enc_inter_stage calls too; k_fq_bqi: the block-qi kernel of that word; gold: GOLD for the kernels that read it (three
+// reference classes then), else nothing (two).
 // stats: k_rate_me's words of this frame where the measurement of thip_encode_cut.h left them and d_mb follows from them (five
 // modes) -- k_enc_mb_modes then stands in for the search --, else nullptr
-extern "C++" template <class Me, class Fq, class FqBqi, class Dc, class Word, class... Gold>
-static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, Me k_me, Fq k_fq, FqBqi k_fq_bqi, Dc k_dc,
-                            int classes, Word *d_mb, const uint4 *stats, const EncRef &R, const Gold &...gold) {
+extern "C++" template <class FqBqi, class Word, class... Gold>
+static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, FqBqi k_fq_bqi, Word *d_mb, const uint4 *stats,
+                            const EncRef &R, const Gold &...gold) {
+  constexpr int classes = sizeof...(Gold) ? 3 : 2;
   const int64_t n = e->nfrags;
   const int lambda = e->lambda[e->frame_qi];
   const dim3 gfq((unsigned)((4 * n + 255) / 256)), gch((unsigned)e->nchunks), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
   if constexpr (sizeof(Word) == sizeof(uint32_t)) {
-    if (stats) hipLaunchKernelGGL(k_enc_mb_modes, dim3((unsigned)((e->nmbs + 255) / 256)), wg, 0, e->stream, d_mb, stats, e->nmbs, lambda);
-    else hipLaunchKernelGGL(k_me, dim3((unsigned)e->nmbs), wg, 0, e->stream, d_mb, g, R, gold..., e->nmbx, lambda);
+    if (stats) ENC_TRY(cut_launch_mb_modes(d_mb, stats, e->nmbs, lambda, e->stream));
+    else ENC_TRY(inter_launch_search(d_mb, g, R, e->nmbx, e->nmbs, lambda, e->stream));
   } else {
-    hipLaunchKernelGGL(k_me, dim3((unsigned)e->nmbs), wg, 0, e->stream, d_mb, g, R, gold..., e->nmbx, lambda);
+    ENC_TRY(inter_launch_search(d_mb, g, R, gold..., e->nmbx, e->nmbs, lambda, e->stream));
   }
-  ENC_TRY(hipGetLastError());
-  if (e->bqi)
+  if (e->bqi) {
     hipLaunchKernelGGL(k_fq_bqi, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
                        e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, n);
-  else
-    hipLaunchKernelGGL(k_fq, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192, e->d_order, g, R,
-                       gold..., (const Word *)d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n);
-  ENC_TRY(hipGetLastError());
+    ENC_TRY(hipGetLastError());
+  } else {
+    ENC_TRY(inter_launch_fq(InterBufs{e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192}, e->d_order, g, R, gold...,
+                            (const Word *)d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n, e->stream));
+  }
   ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
-  hipLaunchKernelGGL(k_dc, gch, wg, 0, e->stream, e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n);
-  ENC_TRY(hipGetLastError());
+  if constexpr (classes == 3) ENC_TRY(inter_launch_dc3(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
+  else ENC_TRY(inter_launch_dc(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
   hipLaunchKernelGGL(k_enc_inter_tok, gch, wg, 0, e->stream, e->d_tok, e->d_mask, e->d_cnt, e->d_small + 192, e->d_levels, e->d_dcr,
                      e->d_cmap, e->d_order, g, n);
   ENC_TRY(hipGetLastError());
@@ -690,10 +693,9 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
 static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, const uint4 *stats) {
   EncRef R, G;
   if (enc_ref_frame(e, R)) return TH_EFAULT;
-  if (!e->modes)
-    return enc_launch_inter(e, g, sel, k_enc_me, k_enc_inter_fq, k_enc_inter_fq_bqi, k_enc_inter_dc, 2, e->d_mb, stats, R);
+  if (!e->modes) return enc_launch_inter(e, g, sel, k_enc_inter_fq_bqi, e->d_mb, stats, R);
   if (enc_ref_frame(e, G, THIP_FRAME_GOLD) || enc_modes_alloc(e)) return TH_EFAULT;
-  return enc_launch_inter(e, g, sel, k_enc_me_all, k_enc_inter_fq_all, k_enc_inter_fq_all_bqi, k_enc_inter_dc3, 3, e->d_mb4, nullptr, R, G);
+  return enc_launch_inter(e, g, sel, k_enc_inter_fq_all_bqi, e->d_mb4, nullptr, R, G);
 }
 
 // ---- bitrate mode -----------------------------------------------------------------------------------------------------------
@@ -759,8 +761,7 @@ static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key, bool sear
     EncRef R;
     if (enc_ref_frame(e, R)) return TH_EFAULT;
     if (!searched) {
-      hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
-      ENC_TRY(hipGetLastError());
+      ENC_TRY(rate_launch_me(e->d_rmbs, g, R, e->nmbx, e->nmbs, e->stream));
     }
     hipLaunchKernelGGL(k_rate_fdct_inter, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, R, (const uint4 *)e->d_rmbs, e->nmbx, n);
     ENC_TRY(hipGetLastError());
@@ -907,8 +908,7 @@ static int enc_cut_measure(th_enc_ctx *e, const EncPlanes &g) {
   if (enc_ref_frame(e, R)) return TH_EFAULT;
   ENC_TRY(hipEventRecord(e->ev_c0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_cut, 0, sizeof(CutSums), e->stream));
-  hipLaunchKernelGGL(k_rate_me, dim3((unsigned)e->nmbs), dim3(256), 0, e->stream, e->d_rmbs, g, R, e->nmbx);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(rate_launch_me(e->d_rmbs, g, R, e->nmbx, e->nmbs, e->stream));
   hipLaunchKernelGGL(k_enc_cut_sums, dim3((unsigned)((e->nmbs + 255) / 256)), dim3(256), 0, e->stream, e->d_cut, (const uint4 *)e->d_rmbs,
                      e->nmbs);
   ENC_TRY(hipGetLastError());
@@ -1987,6 +1987,128 @@ int thip_enc_pack_tokens(const uint32_t *d_words, const uint32_t list_len[192], 
   res->pad = 0;
   if (!pack_fits(need, cap_bytes)) return THIP_ENC_PACK_NOFIT;
   ENC_TRY(pack_launch_place(p, d_len, groups, phase, d_packet, need, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the inter stage on the caller's planes, lambda and tables (theora_hip.h): the launch functions of thip_rate.h,
+// thip_encode_inter.h, thip_encode_modes.h and thip_encode_cut.h, as enc_launch_inter makes them, on the current device's null stream
+int thip_enc_inter_stage(const thip_enc_inter_req *q) {
+  if (!q) return THIP_EFAULT;
+  const int st = q->stages;
+  const bool search = st & THIP_ENC_INTER_SEARCH, decide = st & THIP_ENC_INTER_DECIDE, code = st & THIP_ENC_INTER_CODE;
+  const bool dconly = st == THIP_ENC_INTER_DC, planes = search || decide || code;
+  if (st <= 0 || st > 15 || ((st & THIP_ENC_INTER_DC) && !dconly)) return THIP_EINVAL;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  if (q->classes != 2 && q->classes != 3) return THIP_EINVAL;
+  const bool all = q->classes == 3;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
+  if (n64 > ((int64_t)1 << 24)) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (planes) {
+    if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+        q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+      return THIP_EINVAL;
+    int ngold = 0;
+    for (int p = 0; p < 3; p++) {
+      if (!q->src[p] || !q->prev[p]) return THIP_EFAULT;
+      ngold += q->gold[p] != nullptr;
+    }
+    if (ngold != (all ? 3 : 0)) return all && ngold < 3 ? THIP_EFAULT : THIP_EINVAL;
+    for (int p = 0; p < 3; p++) {
+      const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
+      if (q->src_pitch[p] < pw || q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF) return THIP_EINVAL;
+    }
+    if ((decide || code) && (q->lambda < 0 || q->lambda > (1 << 24))) return THIP_EINVAL;
+    if (search && !q->stats) return THIP_EFAULT;
+    if ((decide || code) && !q->words) return THIP_EFAULT;
+    if (q->words_from_stats && (!search || !decide || all)) return THIP_EINVAL;
+    if (misaligned(q->stats, 16) || misaligned(q->words, all ? 16 : 4) || misaligned(q->words_from_stats, 4)) return THIP_EINVAL;
+  }
+  if (code) {
+    if (!q->dequant) return THIP_EFAULT;
+    for (int k = 0; k < 384; k++)
+      if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
+  }
+  if (dconly && (!q->cmap || !q->dcq || !q->dcr)) return THIP_EFAULT;
+  if (misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->dcr, 2)) return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int64_t n = geo.nfrags;
+  const int classes = q->classes, nmbx = geo.nh[0] >> 1, nmbs = nmbx * (geo.nv[0] >> 1);
+  const size_t nchunks = (size_t)((n + kEncChunk - 1) / kEncChunk);
+  EncPlanes g = {};
+  EncRef R = {}, G = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.src[p] = q->src[p];
+    g.stride[p] = q->src_pitch[p];
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+    R.plane[p] = q->prev[p];
+    G.plane[p] = q->gold[p];
+    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
+    R.w[p] = G.w[p] = geo.nh[p] * 8;
+    R.h[p] = G.h[p] = geo.nv[p] * 8;
+  }
+  R.hdec = G.hdec = hdec;
+  R.vdec = G.vdec = vdec;
+  hipStream_t stream = nullptr;
+  if (search) ENC_TRY(rate_launch_me((uint4 *)q->stats, g, R, nmbx, nmbs, stream));
+  if (decide) {
+    if (all) ENC_TRY(inter_launch_search((uint4 *)q->words, g, R, G, nmbx, nmbs, q->lambda, stream));
+    else ENC_TRY(inter_launch_search((uint32_t *)q->words, g, R, nmbx, nmbs, q->lambda, stream));
+    if (q->words_from_stats) ENC_TRY(cut_launch_mb_modes((uint32_t *)q->words_from_stats, (const uint4 *)q->stats, nmbs, q->lambda, stream));
+  }
+  if (code || dconly) {
+    // one allocation: levels [n][64] (when coded and not given) | dclast [chunks][classes] | overflow | order [n] | dequant [384] | dcq, dcr [n] | cmap [n];
+    // the outputs the caller gave are used in place of their part
+    const size_t o_dclast = code && !q->levels ? (size_t)n * 128 : 0, o_ovf = o_dclast + nchunks * classes * 4, o_order = o_ovf + 16, o_dq = o_order + (size_t)n * 4,
+                 o_dcq = o_dq + 768, o_dcr = o_dcq + (((size_t)n * 2 + 15) & ~(size_t)15), o_cmap = o_dcr + (((size_t)n * 2 + 15) & ~(size_t)15);
+    uint8_t *d = nullptr;
+    ENC_TRY(hipMalloc((void **)&d, o_cmap + (size_t)n));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    uint32_t *d_dclast = (uint32_t *)(d + o_dclast);
+    int16_t *dcq = q->dcq ? q->dcq : (int16_t *)(d + o_dcq), *dcr = q->dcr ? q->dcr : (int16_t *)(d + o_dcr);
+    uint8_t *cmap = q->cmap ? q->cmap : d + o_cmap;
+    if (code) {
+      const InterBufs o{q->levels ? q->levels : (int16_t *)d, dcq, cmap, d_dclast, (uint32_t *)(d + o_ovf)};
+      const int32_t *d_order = (const int32_t *)(d + o_order);
+      const uint16_t *d_dq = (const uint16_t *)(d + o_dq);
+      ENC_TRY(hipMemcpy(d + o_order, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+      ENC_TRY(hipMemcpy(d + o_dq, q->dequant, 768, hipMemcpyHostToDevice));
+      ENC_TRY(hipMemsetAsync(d_dclast, 0, nchunks * classes * 4, stream));
+      if (all) ENC_TRY(inter_launch_fq(o, d_order, g, R, G, (const uint4 *)q->words, nmbx, d_dq, n, stream));
+      else ENC_TRY(inter_launch_fq(o, d_order, g, R, (const uint32_t *)q->words, nmbx, d_dq, n, stream));
+    } else {
+      // the last coded fragment (+1) of every 256 fragments and class, formed here as enc_fq_tail's atomicMax leaves it
+      std::vector<uint8_t> h_cmap((size_t)n);
+      std::vector<uint32_t> h_last(nchunks * classes, 0u);
+      ENC_TRY(hipMemcpy(h_cmap.data(), cmap, (size_t)n, hipMemcpyDeviceToHost));
+      for (int64_t fi = 0; fi < n; fi++) {
+        const int cl = h_cmap[(size_t)fi];
+        if (cl > classes) return THIP_EINVAL;
+        if (cl) h_last[(size_t)(fi >> 8) * classes + cl - 1] = (uint32_t)fi + 1u;
+      }
+      ENC_TRY(hipMemcpy(d_dclast, h_last.data(), h_last.size() * 4, hipMemcpyHostToDevice));
+    }
+    ENC_TRY(hipMemsetAsync(dcr, 0, (size_t)n * 2, stream));   // (the kernel writes the coded fragments' only)
+    if (all) ENC_TRY(inter_launch_dc3(dcr, dcq, cmap, d_dclast, g, n, stream));
+    else ENC_TRY(inter_launch_dc(dcr, dcq, cmap, d_dclast, g, n, stream));
+    ENC_TRY(hipStreamSynchronize(stream));
+    return THIP_OK;
+  }
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

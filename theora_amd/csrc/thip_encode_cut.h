@@ -57,4 +57,10 @@ __global__ __launch_bounds__(256) void k_enc_mb_modes(uint32_t *mb_out, const ui
   mb_out[mb] = mode == kEncPixMv ? (uint32_t)mode | (s.w & 0xFFFFu) << 8 : (uint32_t)mode;   // (s.w: mvx, mvy in its two low bytes)
 }
 
+// the launch, stated once (th_encode_* and thip_enc_inter_stage): k_enc_me's words from k_rate_me's
+inline hipError_t cut_launch_mb_modes(uint32_t *mb, const uint4 *stats, int nmbs, int lambda, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_mb_modes, dim3((unsigned)((nmbs + 255) / 256)), dim3(256), 0, stream, mb, stats, nmbs, lambda);
+  return hipGetLastError();
+}
+
 }  // namespace thip

@@ -24,6 +24,8 @@
 //                   raster order -- a segmented "last value" scan (a max-scan of fragment indices, cut at the plane's first fragment).
 //   k_enc_inter_tok k_enc_intra_tok over the coded blocks only (an uncoded block has no tokens and an empty mask), with the DC
 //                   residual of k_enc_inter_dc.  k_enc_intra_scan and k_enc_intra_scatter then serve both frame types.
+// The launches of the search, of k_enc_inter_fq and of k_enc_inter_dc are the launch functions at the end of this file (their
+// eight-mode overloads: thip_encode_modes.h); th_encode_* and the test entry thip_enc_inter_stage (theora_hip.h) both call them.
 #pragma once
 #include "thip_encode.h"
 
@@ -158,7 +160,7 @@ __device__ __forceinline__ bool enc_me_search(EncMe &out, const EncPlanes &g, co
     }
     if (dx == 0 && dy == 0) s_s0 = sad;
     const uint64_t key = (uint64_t)sad << 32 | (uint64_t)(2 * (abs(dx) + abs(dy))) << 16 | (uint64_t)ci;
-    best = key < best ? key : best;
+    best = key < best ? key : best;   // (no two keys are equal: each holds its candidate's index, so `<` and `<=` pick the same)
   }
   best = enc_min64_wave(best);
   if (lane == 0) s_best[w] = best;
@@ -419,6 +421,38 @@ __global__ __launch_bounds__(256) void k_enc_inter_tok(uint32_t *tok, uint64_t *
   }
   __syncthreads();
   if (threadIdx.x < 192) chunk_cnt[(int64_t)blockIdx.x * 192 + threadIdx.x] = s_cnt[threadIdx.x];
+}
+
+// ---- the launches, stated once: th_encode_* (thip_encode.hip) and thip_enc_inter_stage (theora_hip.h) both call these -----------
+// Five modes here; the launches over k_enc_me_all's words are their overloads in thip_encode_modes.h, k_rate_me's and
+// k_enc_mb_modes' are rate_launch_me (thip_rate.h) and cut_launch_mb_modes (thip_encode_cut.h).
+struct InterBufs {        // device memory the transform-and-quantise launch writes
+  int16_t *levels;        // [n][64], coded order
+  int16_t *dcq;           // [n], raster
+  uint8_t *cmap;          // [n], raster
+  uint32_t *dclast;       // [ceil(n / 256)][classes], zeroed on the same stream before
+  uint32_t *overflow;     // one word (zeroed by the launch, for the token kernel)
+};
+
+// the search and the decision: k_enc_me's word of each of the nmbs macro blocks into mb
+inline hipError_t inter_launch_search(uint32_t *mb, const EncPlanes &g, const EncRef &R, int nmbx, int nmbs, int lambda, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_me, dim3((unsigned)nmbs), dim3(256), 0, stream, mb, g, R, nmbx, lambda);
+  return hipGetLastError();
+}
+
+// transform and quantise over k_enc_me's words: order [n] (the coded order), dequant [2][3][64] (device, zig-zag)
+inline hipError_t inter_launch_fq(const InterBufs &o, const int32_t *order, const EncPlanes &g, const EncRef &R, const uint32_t *mb,
+                                  int nmbx, const uint16_t *dequant, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_inter_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, stream, o.levels, o.dcq, o.cmap, o.dclast,
+                     o.overflow, order, g, R, mb, nmbx, dequant, n);
+  return hipGetLastError();
+}
+
+// the DC residuals with two classes: dclast [ceil(n / 256)][2] as inter_launch_fq left it
+inline hipError_t inter_launch_dc(int16_t *dcr, const int16_t *dcq, const uint8_t *cmap, const uint32_t *dclast, const EncPlanes &g,
+                                  int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_inter_dc, dim3((unsigned)((n + kEncChunk - 1) / kEncChunk)), dim3(256), 0, stream, dcr, dcq, cmap, dclast, g, n);
+  return hipGetLastError();
 }
 
 }  // namespace thip

@@ -196,4 +196,24 @@ __global__ __launch_bounds__(256) void k_enc_inter_dc3(int16_t *dcr, const int16
   enc_inter_dc<3>(dcr, dcq, cmap, dclast, g, nfrags);
 }
 
+// ---- the launches over k_enc_me_all's words (all eight modes, three classes): the overloads of thip_encode_inter.h's --------------
+inline hipError_t inter_launch_search(uint4 *mb, const EncPlanes &g, const EncRef &R, const EncRef &G, int nmbx, int nmbs, int lambda,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_me_all, dim3((unsigned)nmbs), dim3(256), 0, stream, mb, g, R, G, nmbx, lambda);
+  return hipGetLastError();
+}
+
+inline hipError_t inter_launch_fq(const InterBufs &o, const int32_t *order, const EncPlanes &g, const EncRef &R, const EncRef &G,
+                                  const uint4 *mb, int nmbx, const uint16_t *dequant, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_inter_fq_all, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, stream, o.levels, o.dcq, o.cmap,
+                     o.dclast, o.overflow, order, g, R, G, mb, nmbx, dequant, n);
+  return hipGetLastError();
+}
+
+inline hipError_t inter_launch_dc3(int16_t *dcr, const int16_t *dcq, const uint8_t *cmap, const uint32_t *dclast, const EncPlanes &g,
+                                   int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_inter_dc3, dim3((unsigned)((n + kEncChunk - 1) / kEncChunk)), dim3(256), 0, stream, dcr, dcq, cmap, dclast, g, n);
+  return hipGetLastError();
+}
+
 }  // namespace thip

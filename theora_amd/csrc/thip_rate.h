@@ -86,6 +86,12 @@ __global__ __launch_bounds__(256) void k_rate_me(uint4 *mb_out, EncPlanes g, Enc
     mb_out[blockIdx.x] = make_uint4((uint32_t)m.s0, (uint32_t)m.smv, (uint32_t)m.si, ((uint32_t)m.mvx & 0xFFu) | ((uint32_t)m.mvy & 0xFFu) << 8);
 }
 
+// the launch, stated once (the probe, the cut measurement and thip_enc_inter_stage): k_rate_me's word of each of the nmbs macro blocks
+inline hipError_t rate_launch_me(uint4 *mb, const EncPlanes &g, const EncRef &R, int nmbx, int nmbs, hipStream_t stream) {
+  hipLaunchKernelGGL(k_rate_me, dim3((unsigned)nmbs), dim3(256), 0, stream, mb, g, R, nmbx);
+  return hipGetLastError();
+}
+
 // grid: ceil(4 nfrags / 256).  coef [3][nfrags][64]: the INTRA, NOMV and MV residuals' coefficients (natural order, raster)
 __global__ __launch_bounds__(256) void k_rate_fdct_inter(int16_t *coef, EncPlanes g, EncRef R, const uint4 *mbs, int nmbx,
                                                          int64_t nfrags) {

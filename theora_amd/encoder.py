@@ -450,6 +450,34 @@ def pack_tokens(words_ptr, list_len, codes, lens, groups, phase, packet_ptr, cap
     return rc, dict(bits=res.bits, bytes=res.bytes, tokens=res.tokens, merged=res.merged, merged_ac=res.merged_ac, huff=list(res.huff))
 
 
+def inter_stage(frame, pixel_fmt, stages, classes, pic=None, lam=0, src=None, src_pitch=None, prev=None, gold=None, ref_pitch=None,
+                dequant=None, stats=None, words=None, words_from_stats=None, levels=None, dcq=None, cmap=None, dcr=None):
+    """thip_enc_inter_stage (include/theora_hip.h): the device stage of an inter frame on the caller's planes, lambda and tables, a
+    test and diagnostic entry.  frame: (width, height); pic: (x, y, width, height), the whole frame when None; stages: an OR of
+    _lib.ENC_INTER_*; src, prev, gold: three device addresses each (a tensor's data_ptr(); None where there is none) with their
+    pitches; dequant [2][3][64]: anything numpy converts; the rest: device addresses, None is NULL.  Returns the entry's return
+    code; nothing is raised, the refusals are the caller's to look at."""
+    L = _lib.load()
+    q = _lib.EncInterReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.stages, q.lam, q.classes = int(stages), int(lam), int(classes)
+    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
+        for p in range(3):
+            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
+    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
+        for p in range(3):
+            getattr(q, name)[p] = 0 if v is None else int(v[p])
+    keep = None
+    if dequant is not None:
+        keep = np.ascontiguousarray(dequant, np.uint16).reshape(-1)
+        if keep.size != 384:
+            raise ValueError("inter_stage: a dequant of %d entries where 384 are expected" % keep.size)
+        q.dequant = keep.ctypes.data
+    q.stats, q.words, q.words_from_stats, q.levels, q.dcq, q.cmap, q.dcr = stats, words, words_from_stats, levels, dcq, cmap, dcr
+    return L.thip_enc_inter_stage(C.byref(q))
+
+
 def ogg_stream(header_packets, data_packets, serialno=0x7E0):
     """One Ogg logical stream (bytes) through the library's writer (include/thip_ogg.h): the headers, a flush after the setup
     header, then data_packets as (payload, granulepos, e_o_s)."""
