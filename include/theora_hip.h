@@ -874,6 +874,67 @@ typedef struct thip_enc_inter_req {   /* 224 bytes */
 int thip_enc_inter_stage(const thip_enc_inter_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the rate probe of th_encode_*'s bitrate mode (theoraenc_hip.h, "Bitrate mode": E[q], the token bits
+ * of a frame at every qi q = 0..63 at once) on the caller's buffers and tables.  The same launch functions th_encode_* calls, with
+ * everything a stream would fix given instead and every intermediate result handed out.  steps, lambda and lens are HOST memory,
+ * every other pointer is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*, src, src_pitch, prev, ref_pitch   as thip_enc_inter_stage takes them (prev: inter only)
+ *   inter            0: a key frame (one coefficient set, every block coded and intra); 1: an inter frame of five modes
+ *   steps            HOST, uint16 [6][64 q][64 z]: the quantiser steps of each table (the intra then the inter table of each plane)
+ *                    at each qi, zig-zag order, every entry 1..32767.  THE PROBE'S PRECONDITION: the step of every (table, z) at
+ *                    qi 63 is the least over q -- the kernels walk only the indices whose coefficient is not zero at qi 63
+ *   lambda           HOST, int32 [64]: the mode decision's weight at each qi (inter), 0..2^24 each
+ *   lens             HOST, uint8 [80][32]: the code lengths of the 80 Huffman tables
+ *   fixed            the bits E[q] starts from (th_encode_*: 28 for a key frame, 25 + nfrags / 8 for an inter frame), >= 0
+ *   groups           the work groups of the token stage (and the partials the bits stage sums): 0 is the library's rule,
+ *                    thip_enc_rate_groups(nfrags); else the caller's count, at most thip_enc_rate_groups(2^24), of which no group
+ *                    may take 1020 blocks or more (a group takes 16 * ceil(ceil(nfrags / 16) / groups))
+ *   stats            k_rate_me's 16-byte words (THIP_ENC_INTER_SEARCH of thip_enc_inter_stage), always the caller's (inter)
+ *   stages           what to run, an OR of these, run in this order; each reads the caller's buffers, whichever other stages ran
+ *     THIP_ENC_RATE_COEF  reads src (inter: prev, stats); writes coef, int16 [1 or 3][nfrags][64]: the unquantised transform of
+ *                         every block (raster order, natural order in the block) -- inter: of the INTRA, NOMV and MV residuals
+ *     THIP_ENC_RATE_DC    reads coef (inter: stats, lambda); writes qdc, int16 [nfrags][64]: the quantised DC at each q, and (inter)
+ *                         coded, cls, uint64 [nfrags]: bit q set when the block is coded at q, and of class PREV (not intra) at q
+ *     THIP_ENC_RATE_TOK   reads coef, qdc (inter: coded, cls, stats, lambda); writes partial, uint32 [groups][64 q][321]: each work
+ *                         group's token counts [luma / chroma][5 Huffman groups][32 tokens] at q, then its side count (3 a macro
+ *                         block with a coded luma block, 12 more when its mode is MV)
+ *     THIP_ENC_RATE_BITS  reads partial; writes est, int64 [64]: E[q] = fixed + the side counts + over the summed counts the least
+ *                         bits of each of the four table choices (a tie: either, the bits are equal) + the tokens' extra bits
+ *                    (a key frame reads and writes neither coded nor cls: they may be NULL)
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req NULL, a buffer or table a stage needs NULL, or a HIP call failed.  THIP_EINVAL: stages 0 or unknown; inter not 0
+ * or 1; the frame size, fragment count, pixel format, picture region and pitches as thip_enc_inter_stage refuses them (region and
+ * pitches: with COEF); groups negative, too many or too few for the frame; a step outside 1..32767 or the precondition broken (with
+ * DC or TOK); a lambda out of range; fixed negative; stats or coef not 16-byte aligned, coded, cls or est not 8-byte, partial not
+ * 4-byte, qdc not 2-byte -- all found before a device is touched.
+ * thip_enc_rate_groups: the rule itself, pure host code: min(256, ceil(n / 16)) work groups, or ceil(n / 960) where that is more;
+ * THIP_EINVAL for n < 1 or n > 2^24.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_ENC_RATE_COEF 1
+#define THIP_ENC_RATE_DC 2
+#define THIP_ENC_RATE_TOK 4
+#define THIP_ENC_RATE_BITS 8
+typedef struct thip_enc_rate_req {   /* 224 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t inter, stages, groups, fixed, pad;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  const uint8_t *prev[3];
+  int64_t ref_pitch[3];
+  const uint16_t *steps;
+  const int32_t *lambda;
+  const uint8_t *lens;
+  const void *stats;
+  int16_t *coef, *qdc;
+  uint64_t *coded, *cls;
+  uint32_t *partial;
+  int64_t *est;
+} thip_enc_rate_req;
+int thip_enc_rate_stage(const thip_enc_rate_req *req);
+int thip_enc_rate_groups(int64_t nfrags);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

@@ -69,6 +69,10 @@ def test_argument_validation_without_gpu():
     assert L.thip_enc_inter_stage(None) == _lib.EFAULT
     assert C.sizeof(_lib.EncInterReq) == 224
     assert L.thip_enc_inter_stage(C.byref(_lib.EncInterReq())) == _lib.EINVAL   # (no stage)
+    assert L.thip_enc_rate_stage(None) == _lib.EFAULT
+    assert C.sizeof(_lib.EncRateReq) == 224
+    assert L.thip_enc_rate_stage(C.byref(_lib.EncRateReq())) == _lib.EINVAL   # (no stage)
+    assert L.thip_enc_rate_groups(0) == _lib.EINVAL and L.thip_enc_rate_groups(1) == 1
 
 
 def test_loop_filter_init_slot_matches_oracle_table():

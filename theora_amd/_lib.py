@@ -103,6 +103,19 @@ class EncInterReq(C.Structure):
                 ("dcr", C.c_void_p)]
 
 
+ENC_RATE_COEF, ENC_RATE_DC, ENC_RATE_TOK, ENC_RATE_BITS = 1, 2, 4, 8
+
+
+class EncRateReq(C.Structure):
+    """thip_enc_rate_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
+                ("inter", C.c_int32), ("stages", C.c_int32), ("groups", C.c_int32), ("fixed", C.c_int32), ("pad", C.c_int32),
+                ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("prev", C.c_void_p * 3), ("ref_pitch", C.c_int64 * 3),
+                ("steps", C.c_void_p), ("lam", C.c_void_p), ("lens", C.c_void_p), ("stats", C.c_void_p), ("coef", C.c_void_p),
+                ("qdc", C.c_void_p), ("coded", C.c_void_p), ("cls", C.c_void_p), ("partial", C.c_void_p), ("est", C.c_void_p)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -204,6 +217,8 @@ SYMBOLS = [
     ("thip_enc_fdct_quantize_batch", _I, [_P, _P, _P, _P, _P, _P, _I64]),
     ("thip_enc_pack_tokens", _I, [_P, _P, _P, _P, _I, _I, _P, C.c_size_t, C.POINTER(EncPackResult)]),
     ("thip_enc_inter_stage", _I, [C.POINTER(EncInterReq)]),
+    ("thip_enc_rate_stage", _I, [C.POINTER(EncRateReq)]),
+    ("thip_enc_rate_groups", _I, [_I64]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

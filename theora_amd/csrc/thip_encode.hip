@@ -705,9 +705,7 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   const int64_t n = e->nfrags;
   ENC_TRY(hipEventCreate(&e->ev_p0));
   ENC_TRY(hipEventCreate(&e->ev_p1));
-  // (a group then takes at most n / nwg + kRateTokWaves blocks)
-  e->rate_nwg = (int)std::max(std::min((int64_t)256, (n + kRateTokWaves - 1) / kRateTokWaves),
-                              (n + kRateMaxBlocksPerGroup - 1) / kRateMaxBlocksPerGroup);
+  e->rate_nwg = rate_groups(n);
   ENC_TRY(hipMalloc((void **)&e->d_coef, (size_t)(e->inter ? 3 : 1) * n * 64 * 2));
   ENC_TRY(hipMalloc((void **)&e->d_qdc, (size_t)n * 64 * 2));
   ENC_TRY(hipMalloc((void **)&e->d_rcoded, (size_t)n * 8));
@@ -719,15 +717,11 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   ENC_TRY(hipMalloc((void **)&e->d_rpart, (size_t)e->rate_nwg * 64 * kRatePartial * 4));
   ENC_TRY(hipMalloc((void **)&e->d_rest, 64 * 8));
   ENC_TRY(hipHostMalloc((void **)&e->h_rest, 64 * 8, hipHostMallocDefault));
-  // oc_enc_quantize's table entries of every (table, z, q), as k_enc_intra_fq forms them: (step | m << 16, l)
-  std::vector<uint2> tab(6 * 64 * 64);
+  std::vector<uint16_t> steps(6 * 64 * 64);
   for (int t = 0; t < 6; t++)
-    for (int q = 0; q < 64; q++) {
-      uint16_t step[64];
-      compute_qmat(e->setup.qp, t / 3, t % 3, q, step);
-      // (rate_quant reads the second word as l alone: no zig-zag index in it)
-      for (int z = 0; z < 64; z++) tab[(t * 64 + z) * 64 + q] = enc_quant_entry(step[z], 0);
-    }
+    for (int q = 0; q < 64; q++) compute_qmat(e->setup.qp, t / 3, t % 3, q, &steps[(t * 64 + q) * 64]);
+  std::vector<uint2> tab(6 * 64 * 64);
+  rate_form_table(tab.data(), steps.data());
   ENC_TRY(hipMemcpy(e->d_rtab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_rlam, e->lambda, sizeof(e->lambda), hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_rlens, e->setup.len, 80 * 32, hipMemcpyHostToDevice));
@@ -747,35 +741,22 @@ static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key, bool sear
   a.nmbx = e->nmbx;
   a.hdec = e->hdec;
   a.vdec = e->vdec;
-  const unsigned g4 = (unsigned)((4 * n + 255) / 256), gw = (unsigned)((n + 3) / 4);
   ENC_TRY(hipEventRecord(e->ev_p0, e->stream));
   if (key) {
-    hipLaunchKernelGGL(k_rate_fdct_key, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, n);
-    ENC_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_rate_dc<false>, dim3(gw), dim3(256), 0, e->stream, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n);
-    ENC_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_rate_tok<false>, dim3((unsigned)e->rate_nwg), dim3(64 * kRateTokWaves), 0, e->stream, e->d_rpart, e->d_qdc, e->d_rcoded,
-                       e->d_rcls, a, g, n);
-    ENC_TRY(hipGetLastError());
+    ENC_TRY(rate_launch_coef(e->d_coef, g, n, e->stream));
   } else {
     EncRef R;
     if (enc_ref_frame(e, R)) return TH_EFAULT;
     if (!searched) {
       ENC_TRY(rate_launch_me(e->d_rmbs, g, R, e->nmbx, e->nmbs, e->stream));
     }
-    hipLaunchKernelGGL(k_rate_fdct_inter, dim3(g4), dim3(256), 0, e->stream, e->d_coef, g, R, (const uint4 *)e->d_rmbs, e->nmbx, n);
-    ENC_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_rate_dc<true>, dim3(gw), dim3(256), 0, e->stream, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n);
-    ENC_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_rate_tok<true>, dim3((unsigned)e->rate_nwg), dim3(64 * kRateTokWaves), 0, e->stream, e->d_rpart, e->d_qdc, e->d_rcoded,
-                       e->d_rcls, a, g, n);
-    ENC_TRY(hipGetLastError());
+    ENC_TRY(rate_launch_coef(e->d_coef, g, R, (const uint4 *)e->d_rmbs, e->nmbx, n, e->stream));
   }
+  ENC_TRY(rate_launch_dc(!key, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n, e->stream));
+  ENC_TRY(rate_launch_tok(!key, e->d_rpart, e->rate_nwg, e->d_qdc, e->d_rcoded, e->d_rcls, a, g, n, e->stream));
   // header bits: 0, frame type, qi, 0 (+ 3 reserved bits in a key frame) and the four table indices; an inter frame adds nfrags / 8
   const int fixed = key ? 12 + 16 : 9 + 16 + (int)(n / 8);
-  hipLaunchKernelGGL(k_rate_bits, dim3(64), dim3(1024), 0, e->stream, e->d_rest, (const uint32_t *)e->d_rpart, e->rate_nwg,
-                     (const uint8_t *)e->d_rlens, fixed);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(rate_launch_bits(e->d_rest, (const uint32_t *)e->d_rpart, e->rate_nwg, (const uint8_t *)e->d_rlens, fixed, e->stream));
   ENC_TRY(hipMemcpyAsync(e->h_rest, e->d_rest, 64 * 8, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_p1, e->stream));
   ENC_TRY(hipEventSynchronize(e->ev_p1));
@@ -2109,6 +2090,111 @@ int thip_enc_inter_stage(const thip_enc_inter_req *q) {
     ENC_TRY(hipStreamSynchronize(stream));
     return THIP_OK;
   }
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+int thip_enc_rate_groups(int64_t nfrags) { return nfrags < 1 || nfrags > kRateMaxFrags ? THIP_EINVAL : rate_groups(nfrags); }
+
+// the rate probe's stages on the caller's buffers and tables (theora_hip.h): the launch functions of thip_rate.h, as enc_rate_probe
+// makes them, on the current device's null stream
+int thip_enc_rate_stage(const thip_enc_rate_req *q) {
+  if (!q) return THIP_EFAULT;
+  const int st = q->stages;
+  if (st <= 0 || st > 15 || (q->inter != 0 && q->inter != 1)) return THIP_EINVAL;
+  const bool coef = st & THIP_ENC_RATE_COEF, dc = st & THIP_ENC_RATE_DC, tok = st & THIP_ENC_RATE_TOK, bits = st & THIP_ENC_RATE_BITS;
+  const bool inter = q->inter == 1;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
+  if (n64 > kRateMaxFrags) return THIP_EINVAL;
+  if (q->groups < 0 || q->groups > rate_groups(kRateMaxFrags)) return THIP_EINVAL;
+  const int groups = q->groups ? q->groups : rate_groups(n64);
+  if (rate_blocks_per_group(n64, groups) >= kRateBlocksPerGroupLimit) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (coef) {
+    if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+        q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+      return THIP_EINVAL;
+    for (int p = 0; p < 3; p++)
+      if (!q->src[p] || (inter && !q->prev[p])) return THIP_EFAULT;
+    for (int p = 0; p < 3; p++) {
+      const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
+      if (q->src_pitch[p] < pw) return THIP_EINVAL;
+      if (inter && (q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF)) return THIP_EINVAL;
+    }
+  }
+  if ((coef || dc || tok) && (!q->coef || (inter && !q->stats))) return THIP_EFAULT;
+  if (dc || tok) {
+    if (!q->steps || !q->qdc || (inter && (!q->lambda || !q->coded || !q->cls))) return THIP_EFAULT;
+    if (!rate_steps_ok(q->steps)) return THIP_EINVAL;
+    if (inter)
+      for (int k = 0; k < 64; k++)
+        if (q->lambda[k] < 0 || q->lambda[k] > (1 << 24)) return THIP_EINVAL;
+  }
+  if ((tok || bits) && !q->partial) return THIP_EFAULT;
+  if (bits && (!q->lens || !q->est)) return THIP_EFAULT;
+  if (bits && q->fixed < 0) return THIP_EINVAL;
+  if (misaligned(q->stats, 16) || misaligned(q->coef, 16) || misaligned(q->qdc, 2) || misaligned(q->coded, 8) || misaligned(q->cls, 8) ||
+      misaligned(q->partial, 4) || misaligned(q->est, 8))
+    return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int64_t n = geo.nfrags;
+  const int nmbx = geo.nh[0] >> 1;
+  EncPlanes g = {};
+  EncRef R = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.src[p] = q->src[p];
+    g.stride[p] = q->src_pitch[p];
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+    R.plane[p] = q->prev[p];
+    R.stride[p] = (int)q->ref_pitch[p];
+    R.w[p] = geo.nh[p] * 8;
+    R.h[p] = geo.nv[p] * 8;
+  }
+  R.hdec = hdec;
+  R.vdec = vdec;
+  // one allocation: tab [6][64][64] uint2 | lambda [64] | lens [80][32]
+  constexpr size_t o_lam = 6 * 64 * 64 * sizeof(uint2), o_lens = o_lam + 64 * sizeof(int);
+  uint8_t *d = nullptr;
+  ENC_TRY(hipMalloc((void **)&d, o_lens + 80 * 32));
+  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  if (dc || tok) {
+    std::vector<uint2> tab(6 * 64 * 64);
+    rate_form_table(tab.data(), q->steps);
+    ENC_TRY(hipMemcpy(d, tab.data(), o_lam, hipMemcpyHostToDevice));
+    if (inter) ENC_TRY(hipMemcpy(d + o_lam, q->lambda, 64 * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (bits) ENC_TRY(hipMemcpy(d + o_lens, q->lens, 80 * 32, hipMemcpyHostToDevice));
+  RateArgs a;
+  a.coef = q->coef;
+  a.tab = (const uint2 *)d;
+  a.mbs = (const uint4 *)q->stats;
+  a.lam = (const int *)(d + o_lam);
+  a.nmbx = nmbx;
+  a.hdec = hdec;
+  a.vdec = vdec;
+  hipStream_t stream = nullptr;
+  if (coef) {
+    if (inter) ENC_TRY(rate_launch_coef(q->coef, g, R, a.mbs, nmbx, n, stream));
+    else ENC_TRY(rate_launch_coef(q->coef, g, n, stream));
+  }
+  if (dc) ENC_TRY(rate_launch_dc(inter, q->qdc, q->coded, q->cls, a, g, n, stream));
+  if (tok) ENC_TRY(rate_launch_tok(inter, q->partial, groups, q->qdc, q->coded, q->cls, a, g, n, stream));
+  if (bits) ENC_TRY(rate_launch_bits(q->est, q->partial, groups, d + o_lens, q->fixed, stream));
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

@@ -14,8 +14,9 @@
 //                      which class (ballots into one 64-bit word each).
 //   k_rate_tok         a persistent grid, one wave a block, lane q: DC prediction at q, the AC levels at q and the block's tokens,
 //                      counted into the work group's LDS histogram [q][luma / chroma][Huffman group][token] (u16 pairs).  The
-//                      levels are walked over the indices that are non-zero at ANY q (a ballot at qi 63, whose steps are the least),
-//                      so a sparse block costs a few iterations.  The quantiser tables of the frame type sit in LDS beside the
+//                      levels are walked over the indices that are non-zero at ANY q (a ballot at qi 63, whose steps are the least:
+//                      the probe's precondition, rate_steps_ok below; tests/test_rate_stage_cpu.py asserts it of the setup's
+//                      tables), so a sparse block costs a few iterations.  The quantiser tables of the frame type sit in LDS beside the
 //                      histogram (48 KB key, 96 KB inter).  Each work group writes its histogram once, as a partial.
 //   k_rate_bits        one work group per q (one group alone reads the partials too slowly): the partials summed, the least bits of
 //                      each of the four table choices (the setup's code lengths), the extra bits and the frame header -> E[q] (int64;
@@ -29,7 +30,14 @@ constexpr int kRateBins = 2 * 5 * 32;        // luma / chroma, Huffman group, to
 constexpr int kRateHistStride = 161;         // u16-pair words a qi in LDS: 160 + 1, so the 64 lanes spread over the 64 banks
 constexpr int kRatePartial = kRateBins + 1;  // a partial's row per qi: the bins and the side count (M, V of the inter estimate)
 constexpr int kRateTokWaves = 16;             // waves a work group of k_rate_tok (four a SIMD: the histogram allows one group a CU)
-constexpr int kRateMaxBlocksPerGroup = 960;  // a bin grows by at most 64 a block: k_rate_tok's grid keeps a group's blocks below 1020
+// A u16 bin of k_rate_tok's histogram holds what one lane (one qi) counts over all the blocks its work group takes.  One block adds
+// at most 36 to one bin: a bin is one token starting in one Huffman group, the largest group is the indices 28..63, and a token
+// starts at an index once.  rate_groups keeps a group's blocks at or below 960 + 16 = 976 (976 * 36 = 35136), and
+// thip_enc_rate_stage refuses a caller's count that would give a group kRateBlocksPerGroupLimit blocks or more (1019 * 36 = 36684):
+// both stay below 65536.  tests/test_rate_stage_cpu.py derives the 36 from the reference's token counting and checks both products
+// (test_grid_rule_keeps_every_bin_below_16_bits); tests/test_gpu_rate_direct.py loads one bin with it (test_tok_heaviest_bin).
+constexpr int kRateMaxBlocksPerGroup = 960;
+constexpr int kRateBlocksPerGroupLimit = 1020;
 
 // one coefficient through the quantiser, table entry (d | m << 16, l): enc_quant_entry's with zig-zag index 0
 __device__ __forceinline__ int rate_quant(int coef, uint2 e) {
@@ -181,8 +189,8 @@ __device__ __forceinline__ void rate_count(uint32_t *h, int cc, int z, int t) {
   atomicAdd(&h[i >> 1], 1u << (16 * (i & 1)));
 }
 
-// grid: nwg persistent work groups of kRateTokWaves waves; wave w of work group wg takes the blocks wg * 16 + w + k * 16 nwg (with
-// nwg >= nfrags / kRateMaxBlocksPerGroup, fewer than 1020 of them a group).  partial [nwg][64][kRatePartial] u32: the work group's
+// grid: nwg persistent work groups of kRateTokWaves waves; wave w of work group wg takes the blocks wg * 16 + w + k * 16 nwg (nwg
+// from rate_groups, or a caller's count below kRateBlocksPerGroupLimit blocks a group: see kRateMaxBlocksPerGroup).  partial [nwg][64][kRatePartial] u32: the work group's
 // token histogram per q, then (inter) its side count 3 M + 12 V
 template <bool kInter>
 __global__ __launch_bounds__(64 * kRateTokWaves) void k_rate_tok(uint32_t *partial, const int16_t *qdc, const uint64_t *coded, const uint64_t *cls,
@@ -311,6 +319,77 @@ __global__ __launch_bounds__(1024) void k_rate_bits(int64_t *est, const uint32_t
     for (int i = 0; i < kRateBins; i++) e += (uint64_t)s_h[i] * kRateExtraBits[i & 31];
     est[q] = (int64_t)e;
   }
+}
+
+// ---- the launches, the table and the grid rule, stated once: the probe (enc_rate_probe, thip_encode.hip) and thip_enc_rate_stage
+// (theora_hip.h) both call these ---------------------------------------------------------------------------------------------------
+
+// k_rate_tok's work groups for nfrags blocks: one wave a block up to 256 groups, then as many as keep a group's blocks at or below
+// kRateMaxBlocksPerGroup + kRateTokWaves (a group takes at most ceil(nfrags / groups) + kRateTokWaves blocks)
+inline int rate_groups(int64_t nfrags) {
+  const int64_t rounds = (nfrags + kRateTokWaves - 1) / kRateTokWaves, a = rounds < 256 ? rounds : 256;
+  const int64_t b = (nfrags + kRateMaxBlocksPerGroup - 1) / kRateMaxBlocksPerGroup;
+  return (int)(a > b ? a : b);
+}
+constexpr int64_t kRateMaxFrags = (int64_t)1 << 24;
+
+// the blocks the busiest work group of `groups` takes: its 16 waves take a block each per round
+inline int64_t rate_blocks_per_group(int64_t nfrags, int groups) {
+  const int64_t rounds = (nfrags + kRateTokWaves - 1) / kRateTokWaves;
+  return (rounds + groups - 1) / groups * kRateTokWaves;
+}
+
+// oc_enc_quantize's table entries of every (table, z, q) from the steps [6][64 q][64 z] (zig-zag; intra then inter per plane), as
+// k_enc_intra_fq forms them: (step | m << 16, l).  rate_quant reads the second word as l alone: no zig-zag index in it.
+inline void rate_form_table(uint2 *tab, const uint16_t *steps) {
+  for (int t = 0; t < 6; t++)
+    for (int q = 0; q < 64; q++)
+      for (int z = 0; z < 64; z++) tab[(t * 64 + z) * 64 + q] = enc_quant_entry(steps[(t * 64 + q) * 64 + z], 0);
+}
+
+// the probe's precondition: k_rate_dc and k_rate_tok ballot the indices that are non-zero at qi 63, so the step of every (table, z)
+// at qi 63 must be the least over q.  (Steps outside 1..32767 fail too.)
+inline bool rate_steps_ok(const uint16_t *steps) {
+  for (int t = 0; t < 6; t++)
+    for (int q = 0; q < 64; q++)
+      for (int z = 0; z < 64; z++) {
+        const int d = steps[(t * 64 + q) * 64 + z];
+        if (d < 1 || d > 32767 || d < steps[(t * 64 + 63) * 64 + z]) return false;
+      }
+  return true;
+}
+
+// coef [1 or 3][nfrags][64]; R, mbs: the inter frame's reference and k_rate_me's words
+inline hipError_t rate_launch_coef(int16_t *coef, const EncPlanes &g, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_rate_fdct_key, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, stream, coef, g, n);
+  return hipGetLastError();
+}
+inline hipError_t rate_launch_coef(int16_t *coef, const EncPlanes &g, const EncRef &R, const uint4 *mbs, int nmbx, int64_t n,
+                                   hipStream_t stream) {
+  hipLaunchKernelGGL(k_rate_fdct_inter, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, stream, coef, g, R, mbs, nmbx, n);
+  return hipGetLastError();
+}
+
+inline hipError_t rate_launch_dc(bool inter, int16_t *qdc, uint64_t *coded, uint64_t *cls, const RateArgs &a, const EncPlanes &g,
+                                 int64_t n, hipStream_t stream) {
+  const dim3 grid((unsigned)((n + 3) / 4));
+  if (inter) hipLaunchKernelGGL(k_rate_dc<true>, grid, dim3(256), 0, stream, qdc, coded, cls, a, g, n);
+  else hipLaunchKernelGGL(k_rate_dc<false>, grid, dim3(256), 0, stream, qdc, coded, cls, a, g, n);
+  return hipGetLastError();
+}
+
+inline hipError_t rate_launch_tok(bool inter, uint32_t *partial, int groups, const int16_t *qdc, const uint64_t *coded,
+                                  const uint64_t *cls, const RateArgs &a, const EncPlanes &g, int64_t n, hipStream_t stream) {
+  const dim3 grid((unsigned)groups), block(64 * kRateTokWaves);
+  if (inter) hipLaunchKernelGGL(k_rate_tok<true>, grid, block, 0, stream, partial, qdc, coded, cls, a, g, n);
+  else hipLaunchKernelGGL(k_rate_tok<false>, grid, block, 0, stream, partial, qdc, coded, cls, a, g, n);
+  return hipGetLastError();
+}
+
+inline hipError_t rate_launch_bits(int64_t *est, const uint32_t *partial, int groups, const uint8_t *lens, int fixed,
+                                   hipStream_t stream) {
+  hipLaunchKernelGGL(k_rate_bits, dim3(64), dim3(1024), 0, stream, est, partial, groups, lens, fixed);
+  return hipGetLastError();
 }
 
 }  // namespace thip

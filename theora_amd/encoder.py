@@ -478,6 +478,41 @@ def inter_stage(frame, pixel_fmt, stages, classes, pic=None, lam=0, src=None, sr
     return L.thip_enc_inter_stage(C.byref(q))
 
 
+def rate_stage(frame, pixel_fmt, inter, stages, pic=None, groups=0, fixed=0, src=None, src_pitch=None, prev=None, ref_pitch=None,
+               steps=None, lam=None, lens=None, stats=None, coef=None, qdc=None, coded=None, cls=None, partial=None, est=None):
+    """thip_enc_rate_stage (include/theora_hip.h): the rate probe's stages on the caller's buffers and tables, a test and diagnostic
+    entry.  frame: (width, height); pic: (x, y, width, height), the whole frame when None; stages: an OR of _lib.ENC_RATE_*; src,
+    prev: three device addresses each (None where there is none) with their pitches; steps [6][64][64], lam [64] and lens [80][32]:
+    anything numpy converts (None is NULL); the rest: device addresses, None is NULL.  Returns the entry's return code; nothing is
+    raised, the refusals are the caller's to look at."""
+    L = _lib.load()
+    q = _lib.EncRateReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.inter, q.stages, q.groups, q.fixed = int(inter), int(stages), int(groups), int(fixed)
+    for name, ptrs in (("src", src), ("prev", prev)):
+        for p in range(3):
+            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
+    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
+        for p in range(3):
+            getattr(q, name)[p] = 0 if v is None else int(v[p])
+    keep = []
+    for name, v, t, size in (("steps", steps, np.uint16, 6 * 64 * 64), ("lam", lam, np.int32, 64), ("lens", lens, np.uint8, 80 * 32)):
+        if v is not None:
+            a = np.ascontiguousarray(v, t).reshape(-1)
+            if a.size != size:
+                raise ValueError("rate_stage: %s of %d entries where %d are expected" % (name, a.size, size))
+            keep.append(a)
+            setattr(q, name, a.ctypes.data)
+    q.stats, q.coef, q.qdc, q.coded, q.cls, q.partial, q.est = stats, coef, qdc, coded, cls, partial, est
+    return L.thip_enc_rate_stage(C.byref(q))
+
+
+def rate_groups(nfrags):
+    """thip_enc_rate_groups (include/theora_hip.h): the work groups the probe's token stage takes for nfrags blocks (host code)."""
+    return _lib.load().thip_enc_rate_groups(int(nfrags))
+
+
 def ogg_stream(header_packets, data_packets, serialno=0x7E0):
     """One Ogg logical stream (bytes) through the library's writer (include/thip_ogg.h): the headers, a flush after the setup
     header, then data_packets as (payload, granulepos, e_o_s)."""
