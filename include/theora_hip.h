@@ -995,6 +995,8 @@ const char *thip_version_string(void);
  *   dc_global    DC un-prediction through memory even where the LDS kernel fits (default 0)
  *   debug        k_recon ablation switches (profiling); 256: k_recon_lf's cells copy without filtering; 512: tile 1 of every
  *                stream mis-tags its edge units, so that a hand-over fails and the recovery below can be tested
+ *   cell_fast    k_recon_lf: 1 (default) a tile whose blocks, and the neighbours' edge blocks its cells read, are all coded runs its
+ *                filter cells in the all-coded form; 0: every tile takes the general cell (the same pictures; tests decode both ways)
  *   faults_recovered   (counter) frames decoded a second time with the two passes because a bounded wait of k_recon_lf ran out
  *   tl_dc_copy     thip_state_token_lists_finish: 0 (default) a kernel copies the DC values out of the pinned staging buffer, 1 a copy engine
  *   spec_coeffs    k_recon_lf, levels form: 1 (default) frames with a unit for every block get their coefficients asked for at wave start (address from the tile number, checked later), 0 never

@@ -76,6 +76,7 @@ Option g_options[] = {
     {"wait_spin", 0, "wait for a frame with hipEventSynchronize instead of polling with 20 us sleeps"},
     {"dc_global", 0, "DC un-prediction with the work-group kernel that goes through memory (planes beyond k_dc_wave's LDS take it anyway)"},
     {"debug", 0, "k_recon ablation switches for profiling"},
+    {"cell_fast", 1, "k_recon_lf: 1 (default): a tile whose blocks and neighbouring edge blocks are all coded runs its filter cells in the all-coded form; 0: every tile takes the general cell (tests decode the same frames both ways)"},
     {"fe_device_dc", 0, "th_decode_*: DC un-prediction on the device"},
     {"fe_device_tokens", 0, "th_decode_*: token expansion + dequantisation on the device (host-delimited tokens)"},
     {"fe_device_lists", -1, "th_decode_*: the token lists themselves on the device (1 on, 0 off, -1 on while at most four decoder contexts are alive)"},
@@ -1228,7 +1229,7 @@ static int prepare_stream(Chunk &C, thip_state *st, const thip_frame_desc &d, in
   st->buf_serial[bufi] = serial;
   st->buf_touched[bufi] = serial;
   K.flimit2 = 2 * d.flimit;
-  K.debug = THIP_OPT("debug");
+  K.debug = THIP_OPT("debug") | (THIP_OPT("cell_fast") ? 0 : 1024);
   // a unit for every block of the frame: the first unit of a tile in the whole tile rows of a plane is the plane's first +
   // 4 nhfrags * its tile row + 64 * its place in the row (StreamK::spec_*)
   K.spec_on = d.coeff_format == THIP_COEFFS_LEVELS && d.nslots == st->nfrags && d.ncoded == st->nfrags && THIP_OPT("spec_coeffs") != 0;

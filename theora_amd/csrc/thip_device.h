@@ -135,6 +135,21 @@ __device__ __forceinline__ Row12 load_row12(const uint8_t *p) {
   r.c = q[2];
   return r;
 }
+// ... out of a buffer resource: `bytes` from p on (raw, no stride: the range check is on the byte offset), the lane's offset in a
+// register and a wave-uniform one beside it
+typedef __amdgpu_buffer_rsrc_t BufRsrc;
+__device__ __forceinline__ BufRsrc buf_rsrc(const uint8_t *p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p), 0, (int)bytes, 0x00020000);   // (dword 3: 32-bit data format, gfx9)
+}
+__device__ __forceinline__ Row12 load_row12(BufRsrc b, uint32_t lane_off, int wave_off) {
+  typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+  const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(b, (int)lane_off, wave_off, 0);
+  Row12 r;
+  r.a = v.x;
+  r.b = v.y;
+  r.c = v.z;
+  return r;
+}
 // bytes off..off+7 of the window, off in 0..4: one v_perm_b32 per dword with the selector extract_sel(off) -- the lane's
 // selector is computed once for all its rows (v_alignbyte_b32 looks at two bits of the shift only: off = 4 cost two selects a row)
 __device__ __forceinline__ uint32_t extract_sel(int off) { return 0x03020100u + (uint32_t)off * 0x01010101u; }

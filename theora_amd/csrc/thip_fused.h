@@ -166,7 +166,9 @@ __device__ __forceinline__ uint4 tf_fetch_unit(const uint8_t *src, uint32_t ep, 
 // operations; `ext` cells (cell row 3) own the two rows below them as well, pixel rows 28 and 29 of the tile: nothing touches
 // those but the vertical edge of the cell's lower half (Vhi, one more row pair of the same operation), so they need not wait
 // for the tile below.
-template <class G>
+// ALL_CODED: the wave knows that all four blocks around every corner it closes are coded where they exist (k_recon_lf's step 6 decides,
+// wave-uniformly, from the tile's own flags and the neighbours' tags): no flag bytes, and lf_cell_ops reduces to the cell's position.
+template <class G, bool ALL_CODED = false>
 __device__ __forceinline__ void tf_cell(const uint8_t *lds, uint8_t *plane, int stride, int nh, int nv, int t, int sby, int kx, int m,
                                         bool active, int L2, int fy0, int fy1, int r_lo, int r_hi, uint32_t opmask, bool ext) {
   constexpr int kTfPitch = G::kPitch, kTfX0 = G::kX0, kTfFlagOff = G::kFlagOff, kTfFlagPitch = G::kFlagPitch;
@@ -191,7 +193,7 @@ __device__ __forceinline__ void tf_cell(const uint8_t *lds, uint8_t *plane, int 
     }
   }
   const uint8_t *fl = lds + kTfFlagOff + m * kTfFlagPitch + kx;   // flag of block (kx-1, m-1)
-  const bool a = fl[0] != 0, b = fl[1] != 0, c = fl[kTfFlagPitch] != 0, d = fl[kTfFlagPitch + 1] != 0;
+  const bool a = ALL_CODED || fl[0] != 0, b = ALL_CODED || fl[1] != 0, c = ALL_CODED || fl[kTfFlagPitch] != 0, d = ALL_CODED || fl[kTfFlagPitch + 1] != 0;
   uint32_t ops = lf_cell_ops(k, mm, nh, nv, a, b, c, d, fy0, fy1) & opmask;
   if (L2 == 0 || !active) ops = 0;
   lf_cell_apply_pk(C, ops, L2);
@@ -233,14 +235,25 @@ __device__ __forceinline__ void tf_cell(const uint8_t *lds, uint8_t *plane, int 
   }
 }
 
-// The same cell when the whole wave knows the answer to every question tf_cell asks (k_recon_lf decides, wave-uniformly): the tile
-// touches no border of its plane and no band boundary above it, every block of the tile and of the neighbours' edges is coded, the
-// filter is on and the whole tile lies inside the fragment-row range.  Then every cell applies T3, T5, T7, T8 of lf_cell_ops'
-// list -- the vertical edge of its upper half, the horizontal edge's left half, the vertical edge of its lower half, the horizontal
-// edge's right half, in that order (state.c:1083-1104 with all four blocks coded) -- and stores both halves of its rows: no flag
-// bytes, no per-lane operation word, no exec masks but the two that follow from the cell row (m = 0: rows 2..7; m = 3: rows 8, 9 too).
-template <class G>
-__device__ __forceinline__ void tf_cell_all_coded(const uint8_t *lds, uint8_t *plane, int stride, int t, int sby, int kx, int m, int L2) {
+// The same cell when the whole wave knows the answer to every question tf_cell asks (k_recon_lf decides, wave-uniformly): every block
+// of the tile and of the neighbours' edges it reads is coded, the filter is on and the whole tile lies inside the fragment-row range.
+// Then every cell away from the plane's border applies T3, T5, T7, T8 of lf_cell_ops' list -- the vertical edge of its upper half, the
+// horizontal edge's left half, the vertical edge of its lower half, the horizontal edge's right half, in that order (state.c:1083-1104
+// with all four blocks coded) -- and stores both halves of its rows: no flag bytes, no per-lane operation word, no row-mask loop.
+// EDGE = false is the tile that touches no border of its plane and no band boundary above it: no exec masks but the two that follow
+// from the cell row (m = 0: rows 2..7; m = 3: rows 8, 9 too).  EDGE = true takes what lf_cell_ops leaves of that list where the
+// tile lies on the plane's left border or top, or opens a band (tests/test_gpu_recon_lf_paths.py holds the list against lf_cell_ops'
+// rules, cell by cell, through the pictures):
+//   left_border (the tile has no left neighbour), cells k = 0: no vertical edge at x = 0 (kin) and no left half of the horizontal one
+//       (T5 wants k >= 1): T8 alone, and only the right half is stored;
+//   top_lo = 4 (plane top), cell row 0: no horizontal edge at y = 0 (min_) and nothing from fragment row -1: T7 alone, rows 4..7;
+//   top_lo = 6 (the tile above belongs to another band and closes the shared cells itself): T7 alone (k_recon_lf's top_mask), rows 6, 7;
+//   top_lo = 2 (the tile above is of this band): the whole list, rows 2..7.
+// A tile that ends its row is no special case here: all of its 16 block columns are coded, so its last cell column is k = nh - 1 and
+// the plane's right border cells (k = nh) belong to step 6.
+template <class G, bool EDGE>
+__device__ __forceinline__ void tf_cell_all_coded(const uint8_t *lds, uint8_t *plane, int stride, int t, int sby, int kx, int m, int L2, int top_lo,
+                                                  bool left_border) {
   constexpr int kTfPitch = G::kPitch, kTfX0 = G::kX0;
   const int k = G::kBW * t + kx, mm = 4 * sby + m;
   CellPix C;
@@ -258,38 +271,67 @@ __device__ __forceinline__ void tf_cell_all_coded(const uint8_t *lds, uint8_t *p
     xlo[r] = q[0];
     xhi[r] = q[1];
   }
-  lf_vert_pk(C, 0, L2);
-  lf_horz_pk(C, 0, L2);
-  lf_vert_pk(C, 4, L2);
-  lf_horz_pk(C, 1, L2);
-  lf_vert_pair(xlo[0], xlo[1], xhi[0], xhi[1], L2);   // (rows 28, 29 of the tile: stored by cell row 3 only)
+  const bool vert = !EDGE || !left_border || kx != 0;   // a vertical edge runs through the cell
+  const bool horz = !EDGE || m != 0 || top_lo == 2;     // a horizontal edge does, and fragment row mm - 1 triggers operations
+  const int r0 = m != 0 ? 0 : (EDGE ? top_lo : 2);      // the cell's first stored row
+  if (vert && horz) {
+    lf_vert_pk(C, 0, L2);
+    lf_horz_pk(C, 0, L2);
+  }
+  if (vert) {
+    lf_vert_pk(C, 4, L2);
+    lf_vert_pair(xlo[0], xlo[1], xhi[0], xhi[1], L2);   // (rows 28, 29 of the tile: stored by cell row 3 only)
+  }
+  if (horz) lf_horz_pk(C, 1, L2);
   uint8_t *base = plane + (ptrdiff_t)(8 * mm - 4) * stride + (8 * k - 4);
-  if (m != 0) {
+  if (vert) {
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
+    for (int r = 0; r < 8; r++) {
+      if (r < 6 && r0 > (r & ~1)) continue;   // (r0 is even: a row pair shares its test)
       Pix8 o;
       o.x = C.lo[r];
       o.y = C.hi[r];
       *reinterpret_cast<Pix8 *>(base + (ptrdiff_t)r * stride) = o;
     }
-  }
+    if (m == 3) {
 #pragma unroll
-  for (int r = 2; r < 8; r++) {
-    Pix8 o;
-    o.x = C.lo[r];
-    o.y = C.hi[r];
-    *reinterpret_cast<Pix8 *>(base + (ptrdiff_t)r * stride) = o;
-  }
-  if (m == 3) {
+      for (int r = 0; r < 2; r++) {
+        Pix8 o;
+        o.x = xlo[r];
+        o.y = xhi[r];
+        *reinterpret_cast<Pix8 *>(base + (ptrdiff_t)(8 + r) * stride) = o;
+      }
+    }
+  } else {
+    // (the four cells on the plane's left border: the right half alone)
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
-      Pix8 o;
-      o.x = xlo[r];
-      o.y = xhi[r];
-      *reinterpret_cast<Pix8 *>(base + (ptrdiff_t)(8 + r) * stride) = o;
+    for (int r = 0; r < 8; r++) {
+      if (r < 6 && r0 > (r & ~1)) continue;
+      *reinterpret_cast<uint32_t *>(base + (ptrdiff_t)r * stride + 4) = C.hi[r];
+    }
+    if (m == 3) {
+#pragma unroll
+      for (int r = 0; r < 2; r++) *reinterpret_cast<uint32_t *>(base + (ptrdiff_t)(8 + r) * stride + 4) = xhi[r];
     }
   }
 }
+
+// The neighbours' coded flags out of their tags into the image's flag rows: block row -1 (columns 0..15), block column -1 (rows 0..3),
+// block (-1, -1).  Only the general tf_cell reads them.
+__device__ __forceinline__ void tf_neighbour_flags(uint8_t *lds, int lane, uint32_t w_up, uint32_t w_left, uint32_t w_ul) {
+  if (lane < 16)
+    lds[kTfFlagOff + lane + 1] = (uint8_t)((w_up >> lane) & 1u);
+  else if (lane < 20)
+    lds[kTfFlagOff + (lane - 16 + 1) * kTfFlagPitch] = (uint8_t)((w_left >> lane) & 1u);
+  else if (lane == 20)
+    lds[kTfFlagOff] = (uint8_t)((w_ul >> 19) & 1u);
+}
+// (A/B switch: THIP_NO_FLAGS_LAZY writes and reads the flag bytes whether a cell will look at them or not, as before)
+#ifdef THIP_NO_FLAGS_LAZY
+constexpr bool flags_lazy = false;
+#else
+constexpr bool flags_lazy = true;
+#endif
 
 // Experiment hooks: the wave's issue priority by phase (0 start, 1 loads out, 2 pixels done, 3 cells).  THIP_PRIO_SEQ is four digits,
 // e.g. 0x3003: priority 3 until the loads are out, 0 through the transforms and the hand-over, 3 for the cells.  Not defined: nothing.
@@ -323,6 +365,8 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
   // (test switch, option debug = 512: tile 1 of every stream tags its units with the WRONG serial number, so that its neighbours'
   //  waits run out -- quickly -- and the host's recovery can be exercised: tests/test_gpu_frames.py::test_a_failed_hand_over_is_decoded_again)
   const bool poison = (S.debug & 512) != 0;
+  // (option cell_fast = 0, debug bit 1024: every tile's cells take the general tf_cell, so that a test can decode the same frames both ways)
+  const bool cell_general = (S.debug & 1024) != 0;
   const int max_spins = poison ? 256 : (1 << 20);
   uint32_t *fault_p = S.fault;
   const uint32_t ep = S.epoch;
@@ -432,18 +476,18 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
   const uint32_t fill = L.dc_only ? L.dcp : 0u;   // DC-only: the rounded value (state.c:972); uncoded: zero residual
   uint32_t Y[32];
   if (nown == 0) {
-    if (valid) recon_issue(R, L, Q, inter, ref);
+    if (valid) recon_issue<true>(R, L, Q, inter, ref);
     THIP_PRIO_AT(1);
   } else if (nown <= 16) {
     int4 Wc[1][2];
     residual_shared_load<4>(coeffs_p, F, nown, lane, Wc);
-    if (valid) recon_issue(R, L, Q, inter, ref);
+    if (valid) recon_issue<true>(R, L, Q, inter, ref);
     THIP_PRIO_AT(1);
     residual_shared<4>(Wc, F, lds_dw, meta, lane, L, prefix, Y);
   } else if (nown <= 32) {
     int4 Wc[2][2];
     residual_shared_load<2>(coeffs_p, F, nown, lane, Wc);
-    if (valid) recon_issue(R, L, Q, inter, ref);
+    if (valid) recon_issue<true>(R, L, Q, inter, ref);
     THIP_PRIO_AT(1);
     residual_shared<2, true>(Wc, F, lds_dw, meta, lane, L, prefix, Y);
   } else {
@@ -451,7 +495,7 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
     // (the units asked for in step 0 are this tile's: all 64 blocks own one, in lane order from the guessed first unit)
     const bool spec_hit = spec && nown == 64 && !F.wide && F.slot0 == spec_slot0;
     if (!spec_hit) dense_issue<7>(coeffs_p, F, L.has_coeff, prefix, s_tf, w7);
-    if (valid) recon_issue(R, L, Q, inter, ref);
+    if (valid) recon_issue<true>(R, L, Q, inter, ref);
     THIP_PRIO_AT(1);
     // LDS-DMA data has landed (see k_recon) -- on a hit it has landed already: the guess was asked for before the command words, loads
     // come back in order, and the command words are here; the transform then runs UNDER the predictor windows' round trip instead
@@ -468,7 +512,7 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
   THIP_TR(tr, 11);  // residual there (coefficients had arrived, transform done); the predictor windows may still be on their way
 #endif
   uint2 rows[8];
-  recon_rows(R, Q, inter, Y, rows, L.coded ? L.flags : 0u, L.x0);
+  recon_rows<true>(R, Q, inter, Y, rows, L.coded ? L.flags : 0u, L.x0);
 #ifdef THIP_TRACE
   asm volatile("" : "+v"(rows[0].x), "+v"(rows[7].y));
   THIP_TR(tr, 2);   // pixels done (coefficients and predictor windows had arrived)
@@ -492,8 +536,11 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
     // the coded flags of the published edges, one ballot: bits 0..15 block row 3, 16..19 block column 15, 32..47 block row 0
     const int fi = lane < 16 ? 4 * kTfFlagPitch + lane + 1
                              : (lane < 20 ? (lane - 16 + 1) * kTfFlagPitch + 16 : (lane >= 32 && lane < 48 ? kTfFlagPitch + (lane - 32) + 1 : 0));
-    const bool fb = (lane < 20 || (lane >= 32 && lane < 48)) && lds[kTfFlagOff + fi] != 0;
-    const uint64_t fm = __ballot(fb);
+    uint64_t fm = 0x0000FFFF000FFFFFull;   // (a tile with all its blocks coded knows the answer)
+    if (!flags_lazy || !own_all_coded) {
+      const bool fb = (lane < 20 || (lane >= 32 && lane < 48)) && lds[kTfFlagOff + fi] != 0;
+      fm = __ballot(fb);
+    }
     const uint32_t tag_ep = (poison && u == 1) ? 0u : ep;   // (serial numbers are never 0)
     tf_publish_units<Tf16>(lds, myrec + kTfBot, myrec + kTfRight, 34, true, tag_ep << 20 | (uint32_t)(fm & 0xFFFFFu), lane, xb_up);
     if (xb_up) tf_publish_units<Tf16>(lds, myrec + kTfTop, nullptr, 4, false, tag_ep << 20 | ((uint32_t)(fm >> 32) & 0xFFFFu), lane, true);
@@ -502,6 +549,8 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
   }
 
   bool nb_all_coded = false;   // every block on the upper, left and upper-left neighbours' edges is coded (their tags)
+  bool cells_coded = false;    // step 5 takes the all-coded cell
+  uint32_t w_up = 0, w_left = 0, w_ul = 0;   // the neighbours' tags
   // ---- 4. the neighbours' edges into the image margins: lanes 0..21 the upper tile's rows 30, 31, 22..32 the left tile's
   //         columns 124..127, 33 the upper-left tile's corner (dwords 30, 31 of its column: unit 10) ------------------------
   {
@@ -534,16 +583,18 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
     }
     // their coded flags (the tags of the first unit of each record): block row -1 (columns 0..15), block column -1 (rows 0..3),
     // block (-1, -1)
-    const uint32_t w_up = (uint32_t)__builtin_amdgcn_readlane((int)un.w, 0);
-    const uint32_t w_left = (uint32_t)__builtin_amdgcn_readlane((int)un.w, kTfBotUnits);
-    const uint32_t w_ul = (uint32_t)__builtin_amdgcn_readlane((int)un.w, kTfBotUnits + kTfRightUnits);
-    nb_all_coded = (w_up & 0xFFFFu) == 0xFFFFu && (w_left & 0xF0000u) == 0xF0000u && (w_ul & 0x80000u) != 0;
-    if (lane < 16)
-      lds[kTfFlagOff + lane + 1] = (uint8_t)((w_up >> lane) & 1u);
-    else if (lane < 20)
-      lds[kTfFlagOff + (lane - 16 + 1) * kTfFlagPitch] = (uint8_t)((w_left >> lane) & 1u);
-    else if (lane == 20)
-      lds[kTfFlagOff] = (uint8_t)((w_ul >> 19) & 1u);
+    w_up = (uint32_t)__builtin_amdgcn_readlane((int)un.w, 0);
+    w_left = (uint32_t)__builtin_amdgcn_readlane((int)un.w, kTfBotUnits);
+    w_ul = (uint32_t)__builtin_amdgcn_readlane((int)un.w, kTfBotUnits + kTfRightUnits);
+    // (of the neighbours that exist and belong to this band: no cell reads another's flags)
+    nb_all_coded = (!up_in || (w_up & 0xFFFFu) == 0xFFFFu) && (!has_left || (w_left & 0xF0000u) == 0xF0000u) && (!need_ul || (w_ul & 0x80000u) != 0);
+#ifndef THIP_NO_CELL_FAST
+    // (wave-uniform, scalar: see tf_cell_all_coded.  own_all_coded says that the tile has all its 16 x 4 blocks, so its cells end at
+    //  k = nh - 1 and mm = nv - 1 at the most; fragment row 4 sby - 1 triggers operations only in a cell row 0 that runs its horizontal edge)
+    cells_coded = own_all_coded && nb_all_coded && L2 != 0 && !cell_general && fy0 <= 4 * sby - (up_in ? 1 : 0) && fy1 >= 4 * sby + 4;
+#endif
+    // (the all-coded cell reads no flag byte: the neighbours' go into the image only for the general cell -- here, or in step 6)
+    if (!flags_lazy || !cells_coded) tf_neighbour_flags(lds, lane, w_up, w_left, w_ul);
     lds_settle();
     THIP_TR(tr, 6);   // ... and in the margins
   }
@@ -557,11 +608,13 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
   {
     const int m = lane >> 4;
 #ifndef THIP_NO_CELL_FAST
-    // (wave-uniform, scalar: see tf_cell_all_coded)
-    const bool plain = own_all_coded && nb_all_coded && L2 != 0 && has_left && !row_end && up_in && 4 * sby + 3 <= nv - 1 &&
-                       fy0 <= 4 * sby - 1 && fy1 >= 4 * sby + 4;
-    if (plain)
-      tf_cell_all_coded<Tf16>(lds, R.self, R.stride, t, sby, lane & 15, m, L2);
+    const bool coded = cells_coded;
+    if (coded && has_left && up_in)
+      tf_cell_all_coded<Tf16, false>(lds, R.self, R.stride, t, sby, lane & 15, m, L2, 2, false);
+#ifndef THIP_NO_CELL_EDGE
+    else if (coded)
+      tf_cell_all_coded<Tf16, true>(lds, R.self, R.stride, t, sby, lane & 15, m, L2, has_up ? (xb_up ? 6 : 2) : 4, !has_left);
+#endif
     else
 #endif
       tf_cell<Tf16>(lds, R.self, R.stride, nh, nv, t, sby, lane & 15, m, true, L2, fy0, fy1, m == 0 ? top_lo : 0, 8, m == 0 ? top_mask : 0xFFu, m == 3);
@@ -573,6 +626,8 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
   const bool extra_col = row_end && (nh & 15) == 0;
   const bool extra_row = xb_dn || (!has_dn && (nv & 3) == 0);
   if (extra_col || extra_row) {
+    [[maybe_unused]] bool dn_all_coded = true;   // every block of the lower and lower-left tiles' edges that these cells read is coded (their tags)
+    uint32_t w_dn = 0, w_dl = 0;
     if (xb_dn) {
       // the tile below ran at the start of the launch: its first two rows (lanes 0..21) and the lower-left tile's corner
       // (dwords 0, 1 of its column: unit 0, lane 22), into image rows 36, 37
@@ -593,19 +648,38 @@ __global__ __launch_bounds__(64, THIP_TF_WAVES_PER_EU) void k_recon_lf(const Bat
         for (int j = 0; j < 2; j++) *reinterpret_cast<uint32_t *>(lds + tf_col_at<Tf16>(j, 36, -4)) = d[j];
       }
       // block row 4: the lower tile's first block row (its top units' tags), the lower-left tile's block (15, 0)
-      const uint32_t w_dn = (uint32_t)__builtin_amdgcn_readlane((int)un.w, 0);
-      const uint32_t w_dl = (uint32_t)__builtin_amdgcn_readlane((int)un.w, kTfBotUnits);
+      w_dn = (uint32_t)__builtin_amdgcn_readlane((int)un.w, 0);
+      w_dl = (uint32_t)__builtin_amdgcn_readlane((int)un.w, kTfBotUnits);
+      dn_all_coded = (w_dn & 0xFFFFu) == 0xFFFFu && (!has_left || (w_dl & 0x10000u) != 0);
+    }
+    // (wave-uniform: the blocks around these corners are this tile's last block row and column, the left, upper and upper-left
+    //  neighbours' edge blocks of step 5 and, of another band's tiles below, their first block row; the fragment-row range and a
+    //  filter that is off are lf_cell_ops' and tf_cell's business as ever)
+#if !defined(THIP_NO_CELL_FAST) && !defined(THIP_NO_CELL_EXTRA_FAST)
+    const bool extra_coded = own_all_coded && nb_all_coded && dn_all_coded && !cell_general;
+#else
+    const bool extra_coded = false;
+#endif
+    const bool late_flags = !extra_coded && flags_lazy && cells_coded;   // the general cell after all: the flags step 4 left out
+    if (late_flags) tf_neighbour_flags(lds, lane, w_up, w_left, w_ul);
+    if (xb_dn && !extra_coded) {
       if (lane < 16)
         lds[kTfFlagOff + 5 * kTfFlagPitch + lane + 1] = (uint8_t)((w_dn >> lane) & 1u);
       else if (lane == 16)
         lds[kTfFlagOff + 5 * kTfFlagPitch] = (uint8_t)((w_dl >> 16) & 1u);
-      lds_settle();
     }
+    if (xb_dn || late_flags) lds_settle();
     // lanes 0..16: cells (lane, 4); lanes 32..35: cells (16, lane - 32)
     const bool rowl = lane <= 16, coll = lane >= 32 && lane < 36;
     const int kx = rowl ? lane : 16, m = rowl ? 4 : (lane - 32) & 3;
     const bool act = rowl ? (extra_row && (lane < 16 || extra_col)) : (coll && extra_col);
     // row cells: pixel rows 30, 31 and, of another band's tile below, its rows 0 and 1 (28 and 29 went out with cell row 3)
+#if !defined(THIP_NO_CELL_FAST) && !defined(THIP_NO_CELL_EXTRA_FAST)
+    if (extra_coded)
+      tf_cell<Tf16, true>(lds, R.self, R.stride, nh, nv, t, sby, kx, m, act, L2, fy0, fy1, rowl ? 2 : (m == 0 ? top_lo : 0), rowl ? (xb_dn ? 6 : 8) : 8,
+                          (!rowl && m == 0) ? top_mask : 0xFFu, !rowl && m == 3);
+    else
+#endif
     tf_cell<Tf16>(lds, R.self, R.stride, nh, nv, t, sby, kx, m, act, L2, fy0, fy1, rowl ? 2 : (m == 0 ? top_lo : 0), rowl ? (xb_dn ? 6 : 8) : 8,
             (!rowl && m == 0) ? top_mask : 0xFFu, !rowl && m == 3);
   }

@@ -318,8 +318,11 @@ struct PredWin {
 // the reference's replicated UMV border amounts to (state.c:770-835) -- lies inside it.
 __device__ __forceinline__ int pred_xw(int xs, int W) { return max(min(xs, W - 12), 0) & ~3; }
 
-__device__ __forceinline__ void pred_issue(PredWin &Q, const uint8_t *ref, int stride, int W, int H, int x0, int y0,
-                                           uint32_t flags, bool qpx, bool qpy) {
+// INFRAME (k_recon_lf): a wave none of whose footprints leaves the plane, and whose lanes all read the same reference frame, takes a
+// second form of the loads -- see below.
+template <bool INFRAME = false>
+__device__ __forceinline__ void pred_issue(PredWin &Q, const uint8_t *prev, const uint8_t *gold, bool use_prev, int stride, int W, int H, int x0,
+                                           int y0, uint32_t flags, bool qpx, bool qpy) {
   const int dx = (int)(int8_t)(flags >> THIP_INFO_MVX_SHIFT);
   const int dy = (int)(int8_t)(flags >> THIP_INFO_MVY_SHIFT);
   int mx, my;
@@ -334,7 +337,27 @@ __device__ __forceinline__ void pred_issue(PredWin &Q, const uint8_t *ref, int s
   // aligned down to 4: one dword-aligned dwordx3 load per source row.  Vertical half-pel needs
   // 9 source rows, not 16; without it the ninth load re-reads row 7.  Row and column clamps are
   // no-ops for a footprint inside the frame, so there is one code path and no straggler waves.
-  const uint8_t *p1 = ref + pred_xw(xs, W);
+#ifndef THIP_NO_PRED_INFRAME
+  if (INFRAME) {
+    // The in-frame form: the row clamps ARE no-ops (rows ys .. ys + 7 and, with vertical half-pel, ys + 8 lie inside the plane), so the
+    // rows are one 32-bit offset from the plane's start plus multiples of the stride -- the stride is wave-uniform, and so is the
+    // plane's address once every lane reads the same frame.  That is a buffer load: the plane as the resource (scalar), the first
+    // row's offset in a register, r * stride as the scalar offset -- no address arithmetic per row at all, and the ninth row costs a
+    // select and an add.  (An offset inside a plane fits 32 bits; the resource ends with the plane, so an offset beyond it would read
+    // zero, not memory.  The window's column keeps pred_xw: a footprint that ends at the plane's last column starts less than 12
+    // bytes before the end of the row, and the 12-byte window must not reach past it.)
+    const bool all_prev = __all(use_prev);
+    if ((all_prev || !__any(use_prev)) && !__any(Q.border)) {
+      const BufRsrc plane = buf_rsrc(all_prev ? prev : gold, (uint32_t)(H * stride));
+      const uint32_t o0 = (uint32_t)(ys * stride + pred_xw(xs, W));
+#pragma unroll
+      for (int r = 0; r < 8; r++) Q.w[r] = load_row12(plane, o0, r * stride);
+      Q.w[8] = load_row12(plane, o0 + (Q.my2 != 0 ? (uint32_t)stride : 0u), 7 * stride);
+      return;
+    }
+  }
+#endif
+  const uint8_t *p1 = (use_prev ? prev : gold) + pred_xw(xs, W);
 #pragma unroll
   for (int r = 0; r < 9; r++) {
     const int y = min(max(ys + (r < 8 ? r : (Q.my2 != 0 ? 8 : 7)), 0), H - 1);
@@ -537,24 +560,40 @@ __device__ __forceinline__ void tables_to_lds(const uint4 *dequant, int pli, int
 }
 
 // ---- k_recon in three parts, so that the residual can be computed by ALL lanes of the wave ------
+template <bool INFRAME = false>
 __device__ __forceinline__ void recon_issue(const ReconPlane &R, const ReconLane &L, PredWin &Q, bool &inter,
                                             const uint8_t *&ref, bool write_map = true) {
   const int refi = L.coded ? (int)((L.flags >> THIP_INFO_REFI_SHIFT) & 3u) : THIP_FRAME_PREV;
   inter = refi != THIP_FRAME_SELF && !(R.debug & 2);
   ref = refi == THIP_FRAME_PREV ? R.prev : R.gold;
   Q.border = false;
-  if (inter) pred_issue(Q, ref, R.stride, R.nh * 8, R.nv * 8, L.x0, L.y0, L.coded ? L.flags : 0u, R.qpx, R.qpy);
+  if (inter) pred_issue<INFRAME>(Q, R.prev, R.gold, refi == THIP_FRAME_PREV, R.stride, R.nh * 8, R.nv * 8, L.x0, L.y0, L.coded ? L.flags : 0u, R.qpx, R.qpy);
   if (write_map) R.coded_map[(L.y0 >> 3) * R.nh + (L.x0 >> 3)] = L.coded ? 1 : 0;
 }
 
 // The eight reconstructed rows of this lane's block: predictor (fragment.c:49-80: 128, one block, or the
-// average of two) + residual, clamped.
+// average of two) + residual, clamped.  INTRA_LATE (k_recon_lf): the intra constant is set behind the inter lanes' predictor and only
+// in a wave that has a lane without one -- a tile of an inter frame rarely has.
+template <bool INTRA_LATE = false>
 __device__ __forceinline__ void recon_rows(const ReconPlane &R, const PredWin &Q, bool inter, const uint32_t Y[32],
                                            uint2 rows[8], uint32_t Lflags, int Lx0) {
   uint2 pred[8];
+#ifdef THIP_NO_PRED_INFRAME
+  constexpr bool late = false;
+#else
+  constexpr bool late = INTRA_LATE;
+#endif
+  if (!late) {
 #pragma unroll
-  for (int r = 0; r < 8; r++) pred[r] = make_uint2(0x80808080u, 0x80808080u);
+    for (int r = 0; r < 8; r++) pred[r] = make_uint2(0x80808080u, 0x80808080u);
+  }
   if (inter) pred_finish(Q, R.nh * 8, pred, Lflags, Lx0, R.qpx, R.qpy);
+  if (late && !__all(inter)) {
+    if (!inter) {
+#pragma unroll
+      for (int r = 0; r < 8; r++) pred[r] = make_uint2(0x80808080u, 0x80808080u);
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 8; r++)
     rows[r] = pk_recon_row(as_pk(Y[r * 4 + 0]), as_pk(Y[r * 4 + 1]), as_pk(Y[r * 4 + 2]), as_pk(Y[r * 4 + 3]), pred[r]);
