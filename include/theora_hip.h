@@ -935,6 +935,33 @@ int thip_enc_rate_stage(const thip_enc_rate_req *req);
 int thip_enc_rate_groups(int64_t nfrags);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the activity map and the per-block lambda scales of th_encode_*'s activity masking (theoraenc_hip.h,
+ * "Activity masking") on the caller's planes.  The same two launch functions th_encode_* calls in front of its block-qi kernel.
+ * Every pointer is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*, src, src_pitch   as thip_enc_inter_stage takes them (only the luma plane is read)
+ *   ratio            k, 2..16
+ *   act              uint32 [nluma]: every luma fragment's activity (oc_mb_activity's value over the picture region clamped
+ *                    outward), fragment raster order, rows from the bottom
+ *   avg              uint64 [2]: A (the frame average, at least 64) and the largest activity
+ *   iscale           uint16 [nfrags]: every fragment's scale, Q11, the three planes in fragment raster order
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req, a plane or an output NULL, or a HIP call failed.  THIP_EINVAL: the frame size, fragment count, pixel format,
+ * picture region and pitches as thip_enc_inter_stage refuses them; ratio outside 2..16; act not 4-byte aligned, avg not 8-byte,
+ * iscale not 2-byte -- all found before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+typedef struct thip_enc_mask_req {   /* 104 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t ratio;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  uint32_t *act;
+  uint64_t *avg;
+  uint16_t *iscale;
+} thip_enc_mask_req;
+int thip_enc_mask_stage(const thip_enc_mask_req *req);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

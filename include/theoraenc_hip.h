@@ -113,6 +113,28 @@
  *     chosen qi).
  *   - Bitrate mode: the probe is unchanged (it models one qi) and the controller chooses qis[0]; c_key and c_inter absorb the rest.
  *
+ * Activity masking (TH_ENCCTL_THIP_SET_MASKING with a ratio k in 2..16), stated likewise (tests/enc_mask_ref.py restates it).  It
+ * scales the lambda of the block-qi choice above per block by how well the block's texture hides quantisation noise (libtheora's
+ * oc_mb_activity and oc_mb_masking, carried by the only channel the format has for it, the block's qi).  It acts where block qi
+ * does and only with it; off (k = 0, the default) and with block qi off every packet is as without the call.  Integer arithmetic
+ * throughout, 64-bit where a product needs it; every division rounds down.
+ *   - Activity: for every luma fragment, a = oc_mb_activity's _activity value of the block (analyze.c:1152-1237: 64 x the block's
+ *     variance, capped at 5 << 12 where it is under 8 << 12, and damped through the integer logarithm and exponential where one of
+ *     the four directional edge energies holds more than 40 % of their sum -- thip_enc_mb_cost_maps' `activity`, theora_hip.h),
+ *     computed over the frame-size luma plane obtained by extending the picture region with clamped coordinates: the source the
+ *     block kernels code from.  Where the picture region is the whole frame it is thip_enc_mb_cost_maps of the input, value for
+ *     value.  It is the activity of the source frame, for key and inter frames alike, whatever a block's mode.
+ *   - Average: A = max(64, (sum of a + n / 2) / n) over the n luma fragments of the frame.
+ *   - Luma scale, Q11: i = (2048 (k a + A) + (a + k A) / 2) / (a + k A); it lies in [2048 / k, 2048 k] and is 2048 at a = A.
+ *   - Chroma scale: a chroma fragment belongs to the macro block that holds it.  With that macro block's four luma scales sorted,
+ *     i0 <= i1 <= i2 <= i3: m = i0 if i0 >= 2048, else i1; the chroma scale is max(m, 2048) (the reference's rule: chroma's weight
+ *     is never lowered, and one flat luma block is ignored).
+ *   - Use: lambda_b = (lambda i_b + 1024) >> 11 replaces lambda in every J_k of the block, the term for k != 0 included.  It may
+ *     be 0.  Nothing else changes: the qi list, the DC at qis[0], the flags, the mode decision's L, the rate probe and controller
+ *     (c_key and c_inter absorb it), the automatic-key-frame measurement, the quality statistics, the device packetiser.
+ *   - No wait: two launches (the activity, then the scales) are queued in front of the frame's block-qi kernel; A and the largest
+ *     activity come back with the frame's other read-backs (thip_enc_mask_stats).
+ *
  * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
  * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
  *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
@@ -399,6 +421,22 @@ typedef struct thip_enc_quality_stats {
   int64_t windows[3];
   double compare_ms;       /* the compare's device time (HIP events around it on the encoder's stream) */
 } thip_enc_quality_stats;
+
+/* Extension: buf = int k: 0 off (the default: every packet as without the call), 2..16 activity masking with that ratio ("Activity
+   masking" above; recommended 4, libtheora's); any other value TH_EINVAL.  Before the first frame only (else TH_EINVAL); the call
+   never touches the GPU.  Accepted with block qi off, where it has no effect. */
+#define TH_ENCCTL_THIP_SET_MASKING (0x7214)
+/* Extension: buf = thip_enc_mask_stats, describing the last packet th_encode_packetout returned (with the switch off too).  For a
+   frame coded without masking -- a duplicate, a dropped frame, a zero-byte packet, any frame with block qi or the switch off --
+   every field is 0 except ratio. */
+#define TH_ENCCTL_THIP_GET_MASK_STATS (0x7215)
+typedef struct thip_enc_mask_stats {
+  int32_t ratio;          /* k in force (0: off) */
+  int32_t measured;       /* 1: the frame's block-qi choice used the scales */
+  int64_t activity_avg;   /* A */
+  int64_t activity_max;   /* the largest activity of a luma fragment */
+  double mask_ms;         /* HIP events around the two launches */
+} thip_enc_mask_stats;
 
 typedef struct th_enc_ctx th_enc_ctx;
 

@@ -116,6 +116,13 @@ class EncRateReq(C.Structure):
                 ("qdc", C.c_void_p), ("coded", C.c_void_p), ("cls", C.c_void_p), ("partial", C.c_void_p), ("est", C.c_void_p)]
 
 
+class EncMaskReq(C.Structure):
+    """thip_enc_mask_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32), ("ratio", C.c_int32),
+                ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("act", C.c_void_p), ("avg", C.c_void_p), ("iscale", C.c_void_p)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -219,6 +226,7 @@ SYMBOLS = [
     ("thip_enc_inter_stage", _I, [C.POINTER(EncInterReq)]),
     ("thip_enc_rate_stage", _I, [C.POINTER(EncRateReq)]),
     ("thip_enc_rate_groups", _I, [_I64]),
+    ("thip_enc_mask_stage", _I, [C.POINTER(EncMaskReq)]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

@@ -17,6 +17,7 @@
 // Results go to the macro block's entry in the reference's numbering: mbi = super block << 2 | quadrant (state.c:300-330), luma
 // blocks in sb_maps order (state.c:134-139), chroma blocks in OC_MB_MAP_IDXS order (internal.c:67-76).
 #pragma once
+#include "thip_activity.h"
 
 namespace thip {
 
@@ -34,28 +35,10 @@ struct CostMapK {
   uint32_t *activity_fast; // [nmbs][4], may be null
 };
 
-// mathops.c:294-314
-__device__ __forceinline__ uint32_t cm_bexp32_q10(int z) {
-  const int ipart = z >> 10;
-  uint32_t n = (uint32_t)(z & 1023) << 4;
-  n = (n * ((n * ((n * ((n * 3548u >> 15) + 6817u) >> 15) + 15823u) >> 15) + 22708u) >> 15) + 16384u;
-  return 14 - ipart > 0 ? (n + (1u << (13 - ipart))) >> (14 - ipart) : n << (ipart - 14);
-}
-__device__ __forceinline__ int cm_blog32_q10(uint32_t w) {
-  if (w == 0) return -1;
-  const int ipart = 32 - __builtin_clz(w);
-  const int n = (int)(ipart - 16 > 0 ? w >> (ipart - 16) : w << (16 - ipart)) - 32768 - 16384;
-  const int fpart = ((n * ((n * ((n * ((n * -1402 >> 15) + 2546) >> 15) - 5216) >> 15) + 15745)) >> 15) - 6793;
-  return (ipart << 10) + (fpart >> 4);
-}
-
-// One source row of a luma block as twelve bytes N = columns -1 .. 10 of the block (clamped into the plane): the 16-byte
+// One source row of a luma block as CmRow's twelve bytes N = columns -1 .. 10 of the block (clamped into the plane): the 16-byte
 // aligned window that starts at xw, shifted so that column -1 sits in byte 0.  Three cases: the window starts 4 pixels left of
 // the block (interior), AT the block (x0 = 0: column -1 is column 0 again), or 8 pixels left of it (x0 = W - 8: column 8 is
 // column 7 again).
-struct CmRow {
-  uint32_t n0, n1, n2;
-};
 __device__ __forceinline__ CmRow cm_row(const uint8_t *row_xw, int edge /* 0 interior, 1 left, 2 right */) {
   uint4 w;   // (the caller's planes: no alignment beyond the byte is promised)
   __builtin_memcpy(&w, row_xw, 16);
@@ -82,20 +65,6 @@ __device__ __forceinline__ CmRow cm_row(const uint8_t *row_xw, int edge /* 0 int
   r.n2 = __builtin_amdgcn_alignbyte(a3, a2, 3u);
   return r;
 }
-// the pairs of a row as 16-bit lanes: R[k] = {c(2k-1), c(2k)}, k = 0..4; S[k] = {c(2k), c(2k+1)}, k = 0..3
-__device__ __forceinline__ void cm_pairs(const CmRow &r, pk16 R[5], pk16 S[4]) {
-  R[0] = as_pk(__builtin_amdgcn_perm(0u, r.n0, 0x0c010c00u));
-  R[1] = as_pk(__builtin_amdgcn_perm(0u, r.n0, 0x0c030c02u));
-  R[2] = as_pk(__builtin_amdgcn_perm(0u, r.n1, 0x0c010c00u));
-  R[3] = as_pk(__builtin_amdgcn_perm(0u, r.n1, 0x0c030c02u));
-  R[4] = as_pk(__builtin_amdgcn_perm(0u, r.n2, 0x0c010c00u));
-  S[0] = as_pk(__builtin_amdgcn_perm(0u, r.n0, 0x0c020c01u));
-  S[1] = as_pk(__builtin_amdgcn_perm(r.n1, r.n0, 0x0c040c03u));
-  S[2] = as_pk(__builtin_amdgcn_perm(0u, r.n1, 0x0c020c01u));
-  S[3] = as_pk(__builtin_amdgcn_perm(r.n2, r.n1, 0x0c040c03u));
-}
-__device__ __forceinline__ uint32_t cm_abs_sum(pk16 v, uint32_t acc) { return sum2_u16(pk_abs(v), acc); }
-
 // where a block's results go: luma block (bx, by) -> (mbi, entry of sb_maps); SB_MAP of state.c:134-139 as two nibble tables
 __device__ __forceinline__ void cm_luma_slot(int bx, int by, int nsbw, uint32_t &mbi, int &bi) {
   // position on the 4x4 Hilbert curve of block (row, column) of a super block, four bits per entry: quadrant = h >> 2, entry of
@@ -174,11 +143,8 @@ __global__ __launch_bounds__(256) void k_enc_cost_maps(const CostMapK K) {
     const int y = min(max(y0 - 1 + r, 0), H - 1);
     rows[r] = cm_row(base + (ptrdiff_t)y * K.stride[0], edge);
   }
-  // the block itself: columns 0..7 = bytes 1..8 of N
   uint2 s[8];
-#pragma unroll
-  for (int r = 0; r < 8; r++)
-    s[r] = make_uint2(__builtin_amdgcn_alignbyte(rows[r + 1].n1, rows[r + 1].n0, 1u), __builtin_amdgcn_alignbyte(rows[r + 1].n2, rows[r + 1].n1, 1u));
+  cm_block_rows(s, rows);
   uint32_t satd;
   int dc;
   {
@@ -187,55 +153,7 @@ __global__ __launch_bounds__(256) void k_enc_cost_maps(const CostMapK K) {
     for (int r = 0; r < 8; r++) row_sd(D[r], s[r]);
     satd = satd_sd(D, dc);
   }
-  uint32_t x = 0, x2 = 0;
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    x = sad_row(s[r], make_uint2(0u, 0u), x);
-    x2 = dot4(s[r].x, s[r].x, x2);
-    x2 = dot4(s[r].y, s[r].y, x2);
-  }
-  uint32_t act = (x2 << 6) - x * x;
-  if (act < (8u << 12)) {
-    act = min(act, 5u << 12);   // the region is flat
-  } else {
-    uint32_t e1 = 0, e2 = 0, e3 = 0, e4 = 0;
-    pk16 Ru[5], Su[4], Rm[5], Sm[4], Rd[5], Sd[4];
-    cm_pairs(rows[0], Ru, Su);
-    cm_pairs(rows[1], Rm, Sm);
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-      cm_pairs(rows[r + 2], Rd, Sd);
-      pk16 V[5], D[5], Ds[4];
-#pragma unroll
-      for (int k = 0; k < 5; k++) {
-        V[k] = Ru[k] + Rm[k] + Rm[k] + Rd[k];
-        D[k] = Rd[k] - Ru[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) Ds[k] = Sd[k] - Su[k];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        e1 = cm_abs_sum(V[k + 1] - V[k], e1);
-        e2 = cm_abs_sum(D[k] + Ds[k] + Ds[k] + D[k + 1], e2);
-        const pk16 t3 = Rd[k + 1] - Ru[k], t4 = Rd[k] - Ru[k + 1];
-        e3 = cm_abs_sum(t3 + t3 + Sd[k] - Rm[k] + Rm[k + 1] - Su[k], e3);
-        e4 = cm_abs_sum(t4 + t4 + Sd[k] - Rm[k + 1] + Rm[k] - Su[k], e4);
-      }
-#pragma unroll
-      for (int k = 0; k < 5; k++) {
-        Ru[k] = Rm[k];
-        Rm[k] = Rd[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        Su[k] = Sm[k];
-        Sm[k] = Sd[k];
-      }
-    }
-    // an edge block when the largest component is at least 40 % of the total (analyze.c:1224-1231)
-    if (5u * max(max(e1, e2), max(e3, e4)) > 2u * (e1 + e2 + e3 + e4))
-      act = cm_bexp32_q10(0x394A + (7 * (cm_blog32_q10(act) - 0x394A + 5) / 10));
-  }
+  const uint32_t act = cm_block_activity(rows, s);   // (thip_activity.h)
   uint32_t mbi;
   int bi;
   cm_luma_slot(bx, by, K.nsbw, mbi, bi);

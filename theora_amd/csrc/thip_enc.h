@@ -22,6 +22,7 @@
 //     reference rows it needs are loaded and prepared once and serve its three dy; results are stored candidate
 //     by candidate (out[c * nblocks + block]).
 #pragma once
+#include "thip_activity.h"
 
 namespace thip {
 
@@ -31,10 +32,7 @@ __device__ __forceinline__ void load_rows8(uint2 r[8], const uint8_t *p, int yst
 }
 __device__ __forceinline__ uint2 avg_row(uint2 a, uint2 b) { return make_uint2(avg4_trunc(a.x, b.x), avg4_trunc(a.y, b.y)); }
 
-// sum |a - b| over one row, added to acc
-__device__ __forceinline__ uint32_t sad_row(uint2 a, uint2 b, uint32_t acc) {
-  return __builtin_amdgcn_sad_u8(a.y, b.y, __builtin_amdgcn_sad_u8(a.x, b.x, acc));
-}
+// (sad_row, dot4, pk_abs and sum2_u16 are thip_activity.h's: the block-activity body there uses them too)
 // encfrag.c:42-86: whole-block SAD; with a threshold the rows after the one that crosses it are not added
 template <bool THRESH>
 __device__ __forceinline__ uint32_t sad_rows(const uint2 a[8], const uint2 b[8], uint32_t thresh) {
@@ -66,9 +64,6 @@ __device__ __forceinline__ uint32_t intra_sad_rows(const uint2 a[8]) {
   return v;
 }
 // encfrag.c:338-350
-// (the builtin, not inline assembly: the dot instructions have issue hazards against their neighbours that only the compiler
-//  can pad when it knows what the instruction is)
-__device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 __device__ __forceinline__ uint32_t ssd_rows(const uint2 a[8], const uint2 b[8]) {
   uint32_t sq = 0, ab = 0;
 #pragma unroll
@@ -104,15 +99,6 @@ __device__ __forceinline__ void bfly(pk16 &a, pk16 &b) {
   const pk16 s = a + b;
   b = a - b;
   a = s;
-}
-__device__ __forceinline__ pk16 pk_abs(pk16 x) {
-  const pk16 z = {0, 0};
-  return __builtin_elementwise_max(x, z - x);
-}
-typedef unsigned short upk16 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t sum2_u16(pk16 m, uint32_t acc) {   // acc + m.lo + m.hi, both halves unsigned
-  const upk16 one = {(unsigned short)1, (unsigned short)1};
-  return __builtin_amdgcn_udot2(__builtin_bit_cast(upk16, m), one, acc, false);
 }
 // The remaining horizontal levels (c1, c2) of one row whose c0 level is in R[0..3]
 __device__ __forceinline__ void row_h12(pk16 R[4]) {

@@ -30,6 +30,7 @@
 #include "thip_rate.h"
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
+#include "thip_encode_mask.h"
 #include "thip_encode_pack.h"
 #include "thip_encode_cut.h"
 #include "thip_bitstream.h"
@@ -210,6 +211,8 @@ void enc_put_mv(BitW &bw, int v, int mvs) {
 
 }  // namespace
 
+constexpr int kEncSmallMask = 194;   // d_small / h_small: the word at which a masked frame's MaskRec lies (8-byte aligned)
+
 struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bitstream.h)
   int device_req, device = -1;
   bool dev_ready = false;
@@ -242,7 +245,7 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   int16_t *d_levels = nullptr, *d_dcq = nullptr;
   uint32_t *d_tok = nullptr, *d_cnt = nullptr, *d_base = nullptr, *d_small = nullptr, *d_out = nullptr;
   uint64_t *d_mask = nullptr;
-  uint32_t *h_small = nullptr;                  // list lengths [3][64], overflow
+  uint32_t *h_small = nullptr;                  // list lengths [3][64], overflow; with activity masking its record at kEncSmallMask
   uint32_t *h_tok = nullptr;
   size_t h_tok_cap = 0;
   int nchunks = 0;
@@ -267,6 +270,14 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   int bqi_hti[2][2] = {{5, 5}, {5, 5}};   // AC luma, AC chroma tables of the last packet of each type (key, inter)
   uint8_t *d_qii = nullptr, *h_qii = nullptr, *d_bqbits = nullptr;
   thip_enc_block_qi_stats bstats;
+  // activity masking (TH_ENCCTL_THIP_SET_MASKING; thip_encode_mask.h): the ratio k (0 off); the frame queued has its scales in d_iscale
+  int mask = 0;
+  bool mask_queued = false;
+  uint32_t *d_act = nullptr;
+  MaskPart *d_mpart = nullptr;
+  uint16_t *d_iscale = nullptr;
+  hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr;
+  thip_enc_mask_stats kstats;
   // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
   bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
   int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
@@ -359,6 +370,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->istats, 0, sizeof(e->istats));
   memset(&e->mstats, 0, sizeof(e->mstats));
   memset(&e->bstats, 0, sizeof(e->bstats));
+  memset(&e->kstats, 0, sizeof(e->kstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
   memset(&e->pstats, 0, sizeof(e->pstats));
   memset(&e->cnext, 0, sizeof(e->cnext));
@@ -386,6 +398,7 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_mb, (void **)&e->d_dclast, (void **)&e->d_cmap, (void **)&e->d_dcr, (void **)&e->d_dqi,       // ... inter frames
       (void **)&e->d_mb4,                                                                                            // enc_modes_alloc
       (void **)&e->d_qii, (void **)&e->d_bqbits,                                                                     // enc_bqi_prepare
+      (void **)&e->d_act, (void **)&e->d_mpart, (void **)&e->d_iscale,                                               // enc_mask_queue
       (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
@@ -415,8 +428,9 @@ static void enc_free_device(th_enc_ctx *e) {
   e->pkt_size = 0;
   e->rate_dev = false;
   e->q_queued = false;
+  e->mask_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
-                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1}) {
+                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -565,6 +579,41 @@ static int enc_bqi_prepare(th_enc_ctx *e, BqiSel &sel) {
   return 0;
 }
 
+// activity masking (thip_encode_mask.h), with block qi on: the activity of the frame's source and every fragment's scale, queued in
+// front of the block-qi kernel; A and the largest activity go to d_small behind the list lengths and come back with them
+// (enc_queue_tail).  The buffers at the first such frame (TH_ENCCTL_THIP_SET_MASKING never touches the GPU)
+static int enc_mask_queue(th_enc_ctx *e, const EncPlanes &g) {
+  e->mask_queued = false;
+  if (!e->mask || !e->bqi) return 0;
+  const int64_t nluma = (int64_t)e->nh[0] * e->nv[0];
+  if (!e->d_act) {
+    for (hipEvent_t *ev : {&e->ev_a0, &e->ev_a1})
+      if (!*ev) ENC_TRY(hipEventCreate(ev));
+    ENC_TRY(hipMalloc((void **)&e->d_mpart, (size_t)mask_parts(nluma) * sizeof(MaskPart)));
+    ENC_TRY(hipMalloc((void **)&e->d_iscale, (size_t)e->nfrags * 2));
+    ENC_TRY(hipMalloc((void **)&e->d_act, (size_t)nluma * 4));
+  }
+  ENC_TRY(hipEventRecord(e->ev_a0, e->stream));
+  ENC_TRY(mask_launch_act(e->d_act, e->d_mpart, g, e->stream));
+  ENC_TRY(mask_launch_scale(e->d_iscale, (MaskRec *)(e->d_small + kEncSmallMask), e->d_act, e->d_mpart, g, e->nfrags, e->mask, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_a1, e->stream));
+  e->mask_queued = true;
+  return 0;
+}
+
+// the last packet's thip_enc_mask_stats: those of a frame coded without masking, or (queued: after the frame's wait) the frame's own
+static void enc_mask_stats(th_enc_ctx *e, bool queued) {
+  memset(&e->kstats, 0, sizeof(e->kstats));
+  e->kstats.ratio = e->mask;
+  if (!queued) return;
+  float ms = 0;
+  e->kstats.measured = 1;
+  const MaskRec *rec = (const MaskRec *)(e->h_small + kEncSmallMask);
+  e->kstats.activity_avg = (int64_t)rec->avg;
+  e->kstats.activity_max = (int64_t)rec->max;
+  e->kstats.mask_ms = hipEventElapsedTime(&ms, e->ev_a0, e->ev_a1) == hipSuccess ? ms : 0.0;
+}
+
 // ---- the device packetiser (thip_encode_pack.h) ----------------------------------------------------------------------------------
 // its buffers and tables, at the first frame that needs them.  The packet buffer holds 128 bytes a block -- 16 bits a coefficient,
 // twice the raw picture; the natural image of tools/encode_time.py takes 9.5 bytes a block at quality 48 -- where the worst case, 65
@@ -628,7 +677,8 @@ static int enc_queue_tail(th_enc_ctx *e) {
   hipLaunchKernelGGL(k_enc_intra_scatter, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_out, e->d_tok, e->d_mask,
                      e->d_base, e->d_small, n);
   ENC_TRY(hipGetLastError());
-  ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, 193 * 4, hipMemcpyDeviceToHost, e->stream));
+  const size_t nsmall = e->mask_queued ? kEncSmallMask + sizeof(MaskRec) / 4 : 193;   // (a masked frame: its record too)
+  ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, nsmall * 4, hipMemcpyDeviceToHost, e->stream));
   if (!e->frame_key) {
     if (e->modes) ENC_TRY(hipMemcpyAsync(e->h_mb4, e->d_mb4, (size_t)e->nmbs * sizeof(uint4), hipMemcpyDeviceToHost, e->stream));
     else ENC_TRY(hipMemcpyAsync(e->h_mb, e->d_mb, (size_t)e->nmbs * 4, hipMemcpyDeviceToHost, e->stream));
@@ -656,22 +706,27 @@ static int enc_modes_alloc(th_enc_ctx *e) {
 // reference classes then), else nothing (two).
 // stats: k_rate_me's words of this frame where the measurement of thip_encode_cut.h left them and d_mb follows from them (five
 // modes) -- k_enc_mb_modes then stands in for the search --, else nullptr
-extern "C++" template <class FqBqi, class Word, class... Gold>
-static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, FqBqi k_fq_bqi, Word *d_mb, const uint4 *stats,
-                            const EncRef &R, const Gold &...gold) {
+extern "C++" template <class FqBqi, class FqMask, class Word, class... Gold>
+static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, FqBqi k_fq_bqi, FqMask k_fq_mask, Word *d_mb,
+                            const uint4 *stats, const EncRef &R, const Gold &...gold) {
   constexpr int classes = sizeof...(Gold) ? 3 : 2;
   const int64_t n = e->nfrags;
   const int lambda = e->lambda[e->frame_qi];
   const dim3 gfq((unsigned)((4 * n + 255) / 256)), gch((unsigned)e->nchunks), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
+  if (enc_mask_queue(e, g)) return TH_EFAULT;
   if constexpr (sizeof(Word) == sizeof(uint32_t)) {
     if (stats) ENC_TRY(cut_launch_mb_modes(d_mb, stats, e->nmbs, lambda, e->stream));
     else ENC_TRY(inter_launch_search(d_mb, g, R, e->nmbx, e->nmbs, lambda, e->stream));
   } else {
     ENC_TRY(inter_launch_search(d_mb, g, R, gold..., e->nmbx, e->nmbs, lambda, e->stream));
   }
-  if (e->bqi) {
+  if (e->mask_queued) {
+    hipLaunchKernelGGL(k_fq_mask, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
+                       e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
+    ENC_TRY(hipGetLastError());
+  } else if (e->bqi) {
     hipLaunchKernelGGL(k_fq_bqi, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
                        e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, n);
     ENC_TRY(hipGetLastError());
@@ -693,9 +748,9 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
 static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, const uint4 *stats) {
   EncRef R, G;
   if (enc_ref_frame(e, R)) return TH_EFAULT;
-  if (!e->modes) return enc_launch_inter(e, g, sel, k_enc_inter_fq_bqi, e->d_mb, stats, R);
+  if (!e->modes) return enc_launch_inter(e, g, sel, k_enc_inter_fq_bqi, k_enc_inter_fq_bqi_mask, e->d_mb, stats, R);
   if (enc_ref_frame(e, G, THIP_FRAME_GOLD) || enc_modes_alloc(e)) return TH_EFAULT;
-  return enc_launch_inter(e, g, sel, k_enc_inter_fq_all_bqi, e->d_mb4, nullptr, R, G);
+  return enc_launch_inter(e, g, sel, k_enc_inter_fq_all_bqi, k_enc_inter_fq_all_bqi_mask, e->d_mb4, nullptr, R, G);
 }
 
 // ---- bitrate mode -----------------------------------------------------------------------------------------------------------
@@ -922,6 +977,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     g.froff[p] = e->fro[p];
   }
   const int64_t n = e->nfrags;
+  e->mask_queued = false;   // (enc_mask_queue says otherwise; a dropped frame never gets there)
   if (!e->rate) e->frame_qi = e->qi;   // (bitrate mode: the controller's choice, below)
   // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
   const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
@@ -957,7 +1013,11 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   if (enc_bqi_prepare(e, sel)) return TH_EFAULT;
   if (!e->frame_key) return enc_queue_inter(e, g, sel, searched ? (const uint4 *)e->d_rmbs : nullptr);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
-  if (e->bqi)
+  if (enc_mask_queue(e, g)) return TH_EFAULT;
+  if (e->mask_queued)
+    hipLaunchKernelGGL(k_enc_intra_fq_bqi_mask, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
+                       e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
+  else if (e->bqi)
     hipLaunchKernelGGL(k_enc_intra_fq_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
                        e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, sel, n);
   else
@@ -1280,6 +1340,7 @@ static void enc_empty_packet(th_enc_ctx *e) {
   e->stats.overflow = 0;
   e->stats.qi = e->frame_qi;
   memset(&e->bstats, 0, sizeof(e->bstats));
+  enc_mask_stats(e, false);
 }
 
 // what both packers leave behind: the frame's statistics, and the AC tables the next block-qi choice of this frame type counts with
@@ -1476,6 +1537,7 @@ static int enc_finish_frame(th_enc_ctx *e) {
   const uint32_t overflow = e->h_small[192];
   if (total > (size_t)e->nfrags * kEncTokWords) return TH_EFAULT;
   memset(&e->pstats, 0, sizeof(e->pstats));
+  enc_mask_stats(e, e->mask_queued);   // (an empty packet takes them back)
   const int rc = e->frame_dpack ? enc_pack_device(e, total, overflow) : enc_pack_host(e, total, overflow);
   e->pstats.fallbacks = e->pack_fallbacks;
   return rc;
@@ -1621,6 +1683,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->istats, 0, sizeof(e->istats));
     memset(&e->mstats, 0, sizeof(e->mstats));
     memset(&e->bstats, 0, sizeof(e->bstats));
+    enc_mask_stats(e, false);
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
     const int qrc = enc_quality_queue(e, true);   // (against the picture the decoder goes on showing)
     if (qrc) return qrc;
@@ -1659,6 +1722,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->istats, 0, sizeof(e->istats));
     memset(&e->mstats, 0, sizeof(e->mstats));
     memset(&e->bstats, 0, sizeof(e->bstats));
+    enc_mask_stats(e, false);
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
     (void)enc_quality_queue(e, false);
   } else {
@@ -1789,6 +1853,15 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->bqi = d;   // (its buffers are made at the first frame that uses it)
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_MASKING: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int k = *(const int *)buf;
+      if (k != 0 && (k < 2 || k > 16)) return TH_EINVAL;
+      e->mask = k;   // (its buffers are made at the first frame that uses it)
+      e->kstats.ratio = k;
+      return 0;
+    }
     case TH_ENCCTL_THIP_SET_DEVICE_PACK: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       const int v = *(const int *)buf;
@@ -1827,6 +1900,10 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     case TH_ENCCTL_THIP_GET_BLOCK_QI_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_block_qi_stats)) return TH_EINVAL;
       *(thip_enc_block_qi_stats *)buf = e->bstats;
+      return 0;
+    case TH_ENCCTL_THIP_GET_MASK_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_mask_stats)) return TH_EINVAL;
+      *(thip_enc_mask_stats *)buf = e->kstats;
       return 0;
     case TH_ENCCTL_THIP_GET_MODE_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_mode_stats)) return TH_EINVAL;
@@ -2195,6 +2272,57 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   if (dc) ENC_TRY(rate_launch_dc(inter, q->qdc, q->coded, q->cls, a, g, n, stream));
   if (tok) ENC_TRY(rate_launch_tok(inter, q->partial, groups, q->qdc, q->coded, q->cls, a, g, n, stream));
   if (bits) ENC_TRY(rate_launch_bits(q->est, q->partial, groups, d + o_lens, q->fixed, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the masking stage on the caller's planes (theora_hip.h): thip_encode_mask.h's launch functions, as enc_mask_queue makes them, on the
+// current device's null stream
+int thip_enc_mask_stage(const thip_enc_mask_req *q) {
+  if (!q) return THIP_EFAULT;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
+  if (n64 > ((int64_t)1 << 24)) return THIP_EINVAL;
+  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+    return THIP_EINVAL;
+  for (int p = 0; p < 3; p++)
+    if (!q->src[p]) return THIP_EFAULT;
+  if (!q->act || !q->avg || !q->iscale) return THIP_EFAULT;
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
+    if (q->src_pitch[p] < pw) return THIP_EINVAL;
+  }
+  if (q->ratio < 2 || q->ratio > 16) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (misaligned(q->act, 4) || misaligned(q->avg, 8) || misaligned(q->iscale, 2)) return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  EncPlanes g = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.src[p] = q->src[p];
+    g.stride[p] = q->src_pitch[p];
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+  }
+  MaskPart *d_part = nullptr;
+  ENC_TRY(hipMalloc((void **)&d_part, (size_t)mask_parts(nluma) * sizeof(MaskPart)));
+  struct Free { MaskPart *p; ~Free() { (void)hipFree(p); } } guard{d_part};
+  hipStream_t stream = nullptr;
+  ENC_TRY(mask_launch_act(q->act, d_part, g, stream));
+  ENC_TRY(mask_launch_scale(q->iscale, (MaskRec *)q->avg, q->act, d_part, g, geo.nfrags, q->ratio, stream));
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

@@ -60,12 +60,13 @@ __device__ __forceinline__ int64_t bqi_sum4(int64_t v) {   // over the four lane
 // The body of the three kernels.  kClasses: the reference classes of enc_fq_tail -- 0 a key frame (no prediction, mbw not read), 2
 // with k_enc_me's words, 3 with k_enc_me_all's.  levels [n][64], dcq [nfrags], qii [n] (coded order); inter: cmap, dclast as the
 // plain kernels.  dequant: [64 qi][kTabs][64] zig-zag (key: the three intra tables; inter: intra then inter).  bqbits
-// [16 tables][4][32]: code length of table t in Huffman group 1..4 + extra bits.
-template <int kClasses, class Word>
+// [16 tables][4][32]: code length of table t in Huffman group 1..4 + extra bits.  kMask: activity masking (thip_encode_mask.h has
+// the kernels): the block's lambda is scaled by iscale[fi] (Q11); else iscale is not read.
+template <int kClasses, bool kMask, class Word>
 __device__ __forceinline__ void enc_fq_bqi(int16_t *levels, int16_t *dcq, uint8_t *qii, uint8_t *cmap, uint32_t *dclast,
                                            uint32_t *overflow, const int32_t *coded_order, const EncPlanes &g, const EncRef &R,
                                            const EncRef &G, const Word *mbw, int nmbx, const uint16_t *dequant, const uint8_t *bqbits,
-                                           const BqiSel &sel, int64_t n) {
+                                           const BqiSel &sel, int64_t n, const uint16_t *iscale = nullptr) {
   constexpr int kTabs = kClasses ? 6 : 3;
   if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0;   // (the token kernel counts into it)
   __shared__ __attribute__((aligned(16))) uint2 s_t[3 * kTabs * 64];   // per (qi k, table), by natural position
@@ -117,7 +118,8 @@ __device__ __forceinline__ void enc_fq_bqi(int16_t *levels, int16_t *dcq, uint8_
   const int r0 = __shfl(rbits, lb), r1 = __shfl(rbits, lb + 1), r2 = __shfl(rbits, lb + 2);
   const int64_t d0 = bqi_sum4(dist0), d1 = bqi_sum4(dist1), d2 = bqi_sum4(dist2);
   const int64_t s1 = (int64_t)(s_t[tab * 64 + 1].x & 0xFFFFu);   // qis[0]'s step at zig-zag index 1 (natural position 1)
-  const int64_t lam = (s1 * s1 * 40) >> 7;
+  int64_t lam = (s1 * s1 * 40) >> 7;
+  if constexpr (kMask) lam = (lam * (int64_t)iscale[fi] + 1024) >> 11;
   int64_t best = d0 + lam * r0;
   int kb = 0;
   if (sel.nqis > 1 && d1 + lam * (r1 + 1) < best) {
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256) void k_enc_intra_fq_bqi(int16_t *levels, int16
                                                           const int32_t *coded_order, EncPlanes g, const uint16_t *dequant,
                                                           const uint8_t *bqbits, BqiSel sel, int64_t n) {
   EncRef R = {};
-  enc_fq_bqi<0>(levels, dcq, qii, nullptr, nullptr, overflow, coded_order, g, R, R, (const uint32_t *)nullptr, 0, dequant, bqbits,
+  enc_fq_bqi<0, false>(levels, dcq, qii, nullptr, nullptr, overflow, coded_order, g, R, R, (const uint32_t *)nullptr, 0, dequant, bqbits,
                 sel, n);
 }
 
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(256) void k_enc_inter_fq_bqi(int16_t *levels, int16
                                                           uint32_t *overflow, const int32_t *coded_order, EncPlanes g, EncRef R,
                                                           const uint32_t *mb_mode, int nmbx, const uint16_t *dequant,
                                                           const uint8_t *bqbits, BqiSel sel, int64_t n) {
-  enc_fq_bqi<2>(levels, dcq, qii, cmap, dclast, overflow, coded_order, g, R, R, mb_mode, nmbx, dequant, bqbits, sel, n);
+  enc_fq_bqi<2, false>(levels, dcq, qii, cmap, dclast, overflow, coded_order, g, R, R, mb_mode, nmbx, dequant, bqbits, sel, n);
 }
 
 // k_enc_inter_fq_all with block qi
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(256) void k_enc_inter_fq_all_bqi(int16_t *levels, i
                                                               EncPlanes g, EncRef R, EncRef G, const uint4 *mb_word, int nmbx,
                                                               const uint16_t *dequant, const uint8_t *bqbits, BqiSel sel,
                                                               int64_t n) {
-  enc_fq_bqi<3>(levels, dcq, qii, cmap, dclast, overflow, coded_order, g, R, G, mb_word, nmbx, dequant, bqbits, sel, n);
+  enc_fq_bqi<3, false>(levels, dcq, qii, cmap, dclast, overflow, coded_order, g, R, G, mb_word, nmbx, dequant, bqbits, sel, n);
 }
 
 }  // namespace thip

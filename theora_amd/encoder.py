@@ -34,6 +34,8 @@ TH_ENCCTL_THIP_GET_CUT_STATS = 0x7210
 TH_ENCCTL_THIP_RGB_IN = 0x7211
 TH_ENCCTL_THIP_SET_QUALITY_STATS = 0x7212
 TH_ENCCTL_THIP_GET_QUALITY_STATS = 0x7213
+TH_ENCCTL_THIP_SET_MASKING = 0x7214
+TH_ENCCTL_THIP_GET_MASK_STATS = 0x7215
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
 TH_ENCCTL_SET_RATE_FLAGS = 20
@@ -97,6 +99,12 @@ class QualityStats(C.Structure):
                 ("ssim_q20", C.c_int64 * 3), ("windows", C.c_int64 * 3), ("compare_ms", C.c_double)]
 
 
+class MaskStats(C.Structure):
+    """thip_enc_mask_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("ratio", C.c_int32), ("measured", C.c_int32), ("activity_avg", C.c_int64), ("activity_max", C.c_int64),
+                ("mask_ms", C.c_double)]
+
+
 class RateStats(C.Structure):
     """thip_enc_rate_stats (include/theoraenc_hip.h)."""
     _fields_ = [("qi", C.c_int32), ("dropped", C.c_int32), ("key", C.c_int32), ("duplicate", C.c_int32), ("target", C.c_int64),
@@ -129,7 +137,7 @@ class Encoder:
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
-                 block_qi=0, device_pack=None, auto_keyframes=None):
+                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -140,7 +148,8 @@ class Encoder:
         default) leaves the context as option "enc_device_pack" made it, which is off unless THIP_ENC_DEVICE_PACK says otherwise.
         auto_keyframes: a key frame wherever prediction stops paying, the interval becoming a maximum
         (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES): True for the recommended ratio AUTO_KEYFRAMES_DEFAULT, or the ratio t itself, 1..4096;
-        None, False or 0 leave it off.  No effect without inter=True."""
+        None, False or 0 leave it off.  No effect without inter=True.  masking: activity masking with that ratio, 2..16
+        (TH_ENCCTL_THIP_SET_MASKING; 0 off; recommended 4).  No effect without block_qi."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -173,6 +182,9 @@ class Encoder:
             rc, _ = self.ctl(TH_ENCCTL_THIP_SET_BLOCK_QI, self.block_qi)
             if rc < 0:
                 raise ValueError("block_qi must be 0..31 (TH_ENCCTL_THIP_SET_BLOCK_QI returned %d)" % rc)
+        self.masking = 0
+        if masking:
+            self.set_masking(masking)
         if device_pack is not None:
             self.set_device_pack(device_pack)
         self.auto_keyframes = AUTO_KEYFRAMES_DEFAULT if auto_keyframes is True else int(auto_keyframes or 0)
@@ -200,6 +212,13 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_SET_BITRATE returned %d" % rc)
         self.bitrate = bitrate
+
+    def set_masking(self, k):
+        """TH_ENCCTL_THIP_SET_MASKING, before the first frame: activity masking with ratio k, 2..16 (0: off)."""
+        rc, _ = self.ctl(TH_ENCCTL_THIP_SET_MASKING, int(k))
+        if rc < 0:
+            raise ValueError("masking must be 0 or 2..16, set before the first frame (TH_ENCCTL_THIP_SET_MASKING returned %d)" % rc)
+        self.masking = int(k)
 
     def set_device_pack(self, on):
         """TH_ENCCTL_THIP_SET_DEVICE_PACK: from the next frame on (not between encode() and packetout())."""
@@ -369,6 +388,14 @@ class Encoder:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_CUT_STATS returned %d" % rc)
         return {k: getattr(s, k) for k, _ in CutStats._fields_}
 
+    def mask_stats(self):
+        """TH_ENCCTL_THIP_GET_MASK_STATS of the last packet, as a dict."""
+        s = MaskStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_MASK_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_MASK_STATS returned %d" % rc)
+        return {k: getattr(s, k) for k, _ in MaskStats._fields_}
+
     def set_quality_stats(self, metrics=("sse",)):
         """TH_ENCCTL_THIP_SET_QUALITY_STATS, before the first frame: metrics "sse", ("sse", "ssim"), the THIP_CMP_* flags, or
         None / 0 for off."""
@@ -506,6 +533,24 @@ def rate_stage(frame, pixel_fmt, inter, stages, pic=None, groups=0, fixed=0, src
             setattr(q, name, a.ctypes.data)
     q.stats, q.coef, q.qdc, q.coded, q.cls, q.partial, q.est = stats, coef, qdc, coded, cls, partial, est
     return L.thip_enc_rate_stage(C.byref(q))
+
+
+def mask_stage(frame, pixel_fmt, ratio, pic=None, src=None, src_pitch=None, act=None, avg=None, iscale=None):
+    """thip_enc_mask_stage (include/theora_hip.h): the activity map and the scales of activity masking on the caller's planes, a test
+    and diagnostic entry.  frame: (width, height); pic: (x, y, width, height), the whole frame when None; ratio: k; src: three
+    device addresses (None where there is none) with their pitches; act (uint32 [nluma]), avg (uint64 [2]) and iscale (uint16
+    [nfrags]): device addresses, None is NULL.  Returns the entry's return code; nothing is raised, the refusals are the caller's to
+    look at."""
+    L = _lib.load()
+    q = _lib.EncMaskReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.ratio = int(ratio)
+    for p in range(3):
+        q.src[p] = None if src is None else src[p]
+        q.src_pitch[p] = 0 if src_pitch is None else int(src_pitch[p])
+    q.act, q.avg, q.iscale = act, avg, iscale
+    return L.thip_enc_mask_stage(C.byref(q))
 
 
 def rate_groups(nfrags):

@@ -20,7 +20,10 @@ With --auto-keyframes [T] (with --inter or --bitrate) each case runs with automa
 (TH_ENCCTL_THIP_GET_CUT_STATS: the search, the sums and the 32 bytes on the host), which device_ms does not include, and cut_frames
 counts the key frames it made (none on the panning sequence).
 
-  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D] [--device-pack]
+With --masking K (with --block-qi, in quality mode): activity masking at ratio K (TH_ENCCTL_THIP_SET_MASKING); mask_ms is the device
+time of its two launches (TH_ENCCTL_THIP_GET_MASK_STATS), which device_ms includes.
+
+  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
                               [--auto-keyframes [T]] [--json out.json]
 """
 import argparse
@@ -65,6 +68,7 @@ def main():
     ap.add_argument("--bitrate", type=int, default=0)
     ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
     ap.add_argument("--block-qi", type=int, default=0, help="block-level qi with this delta (TH_ENCCTL_THIP_SET_BLOCK_QI)")
+    ap.add_argument("--masking", type=int, default=0, help="with --block-qi: activity masking at this ratio (TH_ENCCTL_THIP_SET_MASKING)")
     ap.add_argument("--device-pack", action="store_true", help="each case with the device packetiser off, then on")
     ap.add_argument("--auto-keyframes", type=int, nargs="?", const=230, default=0, metavar="T",
                     help="with --inter or --bitrate: each case with automatic key frames off, then on at ratio T (default 230)")
@@ -81,9 +85,9 @@ def main():
         p = pic or (0, 0, w, h)
         frame = enc_ref.picture("natural", w, h, 0, p, picture_size=True, seed=5)
         for q, dp in [(q, dp) for q in (16, 48) for dp in ((False, True) if args.device_pack else (False,))]:
-            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp)
+            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking)
             hdr = e.header_packets()
-            dev, host, wall, pack = [], [], [], []
+            dev, host, wall, pack, mask = [], [], [], [], []
             for f in range(args.frames + 3):
                 t0 = time.perf_counter()
                 e.encode(frame)
@@ -95,9 +99,10 @@ def main():
                     host.append(hm)
                     wall.append((t1 - t0) * 1e3)
                     pack.append(e.pack_stats()["pack_ms"])
+                    mask.append(e.mask_stats()["mask_ms"])
             st = e.stats()
             e.close()
-            qs = quality_pass([frame], w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp)[0]
+            qs = quality_pass([frame], w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking)[0]
             ps = [round(psnr(qs["sse"][pl], qs["samples"][pl]), 2) for pl in range(3)]
             r = dict(size=name, quality=q, device_ms=round(float(np.median(dev)), 4), host_ms=round(float(np.median(host)), 4),
                      call_ms=round(float(np.median(wall)), 4), bytes=len(pkt), tokens=st["tokens"],
@@ -105,6 +110,8 @@ def main():
             if args.device_pack:
                 r.update(device_pack=dp, pack_ms=round(float(np.median(pack)), 4),
                          call_spread=[round(float(min(wall)), 4), round(float(max(wall)), 4)])
+            if args.masking:
+                r.update(masking=args.masking, mask_ms=round(float(np.median(mask)), 4))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
@@ -124,9 +131,9 @@ def main_inter(args):
                               for dp in ((False, True) if args.device_pack else (False,))
                               for ak in ((0, args.auto_keyframes) if args.auto_keyframes else (0,))]:
             e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi,
-                        device_pack=dp, auto_keyframes=ak)
+                        device_pack=dp, auto_keyframes=ak, masking=args.masking)
             hdr = e.header_packets()
-            dev, host, wall, pkts, keys, pack, meas, cuts = [], [], [], [], 0, [], [], 0
+            dev, host, wall, pkts, keys, pack, meas, cuts, mask = [], [], [], [], 0, [], [], 0, []
             for f in range(n):
                 t0 = time.perf_counter()
                 e.encode(frames[f])
@@ -141,12 +148,13 @@ def main_inter(args):
                     wall.append((t1 - t0) * 1e3)
                     pack.append(e.pack_stats()["pack_ms"])
                     meas.append(e.cut_stats()["measure_ms"])
+                    mask.append(e.mask_stats()["mask_ms"])
                 keys += key
                 cuts += e.cut_stats()["cut"]
             e.close()
             ps = [psnr(qs["sse"][0], qs["samples"][0])
                   for qs in quality_pass(frames, w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am,
-                                         block_qi=args.block_qi, device_pack=dp, auto_keyframes=ak)]
+                                         block_qi=args.block_qi, device_pack=dp, auto_keyframes=ak, masking=args.masking)]
             r = dict(size=name, quality=q, inter=args.inter, all_modes=am, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
@@ -155,6 +163,8 @@ def main_inter(args):
                          call_spread=[round(float(min(wall)), 4), round(float(max(wall)), 4)])
             if args.auto_keyframes:
                 r.update(auto_keyframes=ak, measure_ms=round(float(np.median(meas)), 4), cut_frames=cuts)
+            if args.masking:
+                r.update(masking=args.masking, mask_ms=round(float(np.median(mask)), 4))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
