@@ -962,6 +962,46 @@ typedef struct thip_enc_mask_req {   /* 104 bytes */
 int thip_enc_mask_stage(const thip_enc_mask_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the rate-distortion mode decision of th_encode_*'s eight-mode inter frames (theoraenc_hip.h,
+ * "Rate-distortion mode decision") on the caller's planes, lambdas and tables.  The same launch function th_encode_* calls in place
+ * of its eight-mode search.  dequant and bits are HOST memory, every other pointer is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*, src, src_pitch, prev, gold, ref_pitch   as thip_enc_inter_stage takes them with classes 3 (gold given)
+ *   dequant          HOST, [2][3][64]: the intra then the inter table of each plane, zig-zag order, every entry 1..32767
+ *   lambda_search    as thip_enc_inter_stage's lambda, 0..2^24; the candidate form of the search does not read it
+ *   lambda_rd        the rule's lambda, 0..2^24 (th_encode_*: (s1 * s1 * 40) >> 7, s1 the inter luma step at zig-zag index 1)
+ *   bits             HOST, uint8 [2][5][32]: luma then chroma, code length + extra bits of each token in each Huffman group
+ *   stages           what to run, an OR of
+ *     THIP_ENC_RD_CAND    the search without a decision: cand [nmbs][2] receives 32 bytes a macro block (raster order, rows from
+ *                         the bottom), as two uint4: x = pack(mvx, mvy) | pack(gx, gy) << 16 (pack(x, y) = x & 0xFF | (y & 0xFF) << 8),
+ *                         y = block vectors 0, 1, z = block vectors 2, 3, w = S0 | Smv << 16; then x = S4 | SI << 16,
+ *                         y = G0 | Gmv << 16, z = w = 0
+ *     THIP_ENC_RD_DECIDE  the decision over cand (the caller's, or CAND's when both are asked for): words [nmbs] receives the
+ *                         16-byte words of all eight modes (thip_enc_inter_stage's, classes 3), costs [nmbs][6] (may be NULL) the
+ *                         six J of every macro block
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req, a plane, a table, cand, or words with DECIDE NULL, or a HIP call failed.  THIP_EINVAL: stages 0 or unknown; the
+ * frame size, fragment count, pixel format, picture region and pitches as thip_enc_inter_stage refuses them; a lambda out of range;
+ * a table entry outside 1..32767; cand or words not 16-byte aligned, costs not 8-byte -- all found before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_ENC_RD_CAND 1
+#define THIP_ENC_RD_DECIDE 2
+typedef struct thip_enc_rd_req {   /* 200 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t stages, lambda_search, lambda_rd;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  const uint8_t *prev[3], *gold[3];
+  int64_t ref_pitch[3];
+  const uint16_t *dequant;
+  const uint8_t *bits;
+  void *cand;
+  int64_t *costs;
+  void *words;
+} thip_enc_rd_req;
+int thip_enc_rd_stage(const thip_enc_rd_req *req);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

@@ -135,6 +135,39 @@
  *   - No wait: two launches (the activity, then the scales) are queued in front of the frame's block-qi kernel; A and the largest
  *     activity come back with the frame's other read-backs (thip_enc_mask_stats).
  *
+ * Rate-distortion mode decision (TH_ENCCTL_THIP_SET_RD_MODES), stated likewise (tests/enc_rd_ref.py restates it).  It replaces the
+ * cascade of SAD comparisons of "All eight modes" by the least D + lambda R over six candidates, computed from the quantised levels
+ * and the token code lengths.  Off (the default) every packet is as without the call.  Integer arithmetic throughout, 64-bit where a
+ * product needs it.
+ *   - Where it acts: on inter frames with inter frames and all eight modes on; with eight modes off the request is accepted and does
+ *     nothing.  It does not touch key frames, the search (S0, Smv, S4, G0, Gmv, SI and their vectors are those of "All eight modes"),
+ *     the rate probe, the controller, the automatic-key-frame measurement, the coded-block rule, or anything after the macro-block
+ *     words: block qi is chosen afterwards, as always, on the winning mode's residual.
+ *   - Candidates, per macro block, in this order: 0 INTER_NOMV (PREV, vector 0); 1 INTER_MV (PREV, (mvx, mvy)); 2 INTER_MV_FOUR (the
+ *     four block vectors, chroma through the vector the decoder derives); 3 GOLDEN_NOMV (GOLD, vector 0); 4 GOLDEN_MV (GOLD, (gx, gy));
+ *     5 INTRA (pixel - 128).
+ *   - Blocks of a macro block: its four luma blocks and the chroma fragments that belong to it: 1 + 1 (4:2:0), 2 + 2 (4:2:2),
+ *     4 + 4 (4:4:4).
+ *   - Per block b under candidate m: c = the fDCT of the residual under m (the clamped source exactly as the block kernels take it);
+ *     l = oc_enc_quantize(c) with the table of (intra for INTRA, else inter; plane) at the frame's qi, qis[0]; s that table's steps;
+ *       D_b = sum over all 64 z of (c_z - l_z s_z)^2;
+ *       R_b = the bits of the block's tokens counted as the rate probe counts a block: the walk starts at index 0, with the block's
+ *             own EOB; each token costs its code length in the table of its start index's Huffman group for the block's plane plus
+ *             its extra bits (a value no value token carries, |v| > 580, costs the largest one).  For R_b only, the level at index 0
+ *             is replaced by the charged DC d': d' = l_0 for the five inter candidates; for INTRA d' = l_0 for luma block 0 and for
+ *             every chroma block, and l_0 less luma block 0's l_0 for luma blocks 1..3.  No prediction across macro blocks: the cost
+ *             depends on nothing outside the macro block.
+ *     The four tables (DC luma, DC chroma, AC luma, AC chroma) are those the previous inter packet chose; before there is one, 5.
+ *     Exception, following the coded rule: under candidate 0 a block whose 64 levels are all zero is uncoded: R_b = 0 and
+ *     D_b = sum c_z^2.
+ *   - lambda = (s1 * s1 * 40) >> 7, s1 the inter luma step at zig-zag index 1 of the frame's qi (block qi's lambda; neither masking
+ *     nor the search's L enters).
+ *   - Header bits H_m for candidates 0..5: 1, 15, 55, 5, 18, 4 (a mode code plus six bits a component for each vector written, flat;
+ *     LAST / LAST2 are a serial matter and stay with the packet writer).
+ *   - J_m = sum over the blocks of (D_b + lambda R_b) + lambda H_m, in 64-bit integers.  The macro block takes the least J_m; on a
+ *     tie the lower index, so while GOLD is PREV candidate 3 never wins.  The word written is k_enc_me_all's, field for field.
+ *   - No wait: two launches (the candidates, then the choice) stand in for the search's one (thip_enc_rd_stats).
+ *
  * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
  * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
  *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
@@ -437,6 +470,23 @@ typedef struct thip_enc_mask_stats {
   int64_t activity_max;   /* the largest activity of a luma fragment */
   double mask_ms;         /* HIP events around the two launches */
 } thip_enc_mask_stats;
+
+/* Extension: buf = int 0 / 1: the macro-block modes of eight-mode inter frames by the least D + lambda R ("Rate-distortion mode
+   decision" above); any other value TH_EINVAL.  Off by default: every packet as without the call.  Before the first frame only (else
+   TH_EINVAL); the call never touches the GPU.  Accepted with inter frames or all eight modes off, where it has no effect.
+   (0x7216 and 0x7217 are not used.) */
+#define TH_ENCCTL_THIP_SET_RD_MODES (0x7218)
+/* Extension: buf = thip_enc_rd_stats, describing the last packet th_encode_packetout returned (with the switch off too).  For a frame
+   not decided this way -- a key frame, a duplicate, a dropped frame, a zero-byte packet, any frame with five modes or the switch off
+   -- every field is 0 except on. */
+#define TH_ENCCTL_THIP_GET_RD_STATS (0x7219)
+typedef struct thip_enc_rd_stats {
+  int32_t on;             /* the switch */
+  int32_t measured;       /* 1: the frame's macro-block modes were chosen by the rule */
+  int32_t huff[4];        /* the tables the rule counted with: DC luma, DC chroma, AC luma, AC chroma */
+  int64_t lambda;         /* the rule's lambda */
+  double rd_ms;           /* HIP events around the two launches */
+} thip_enc_rd_stats;
 
 typedef struct th_enc_ctx th_enc_ctx;
 

@@ -123,6 +123,19 @@ class EncMaskReq(C.Structure):
                 ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("act", C.c_void_p), ("avg", C.c_void_p), ("iscale", C.c_void_p)]
 
 
+ENC_RD_CAND, ENC_RD_DECIDE = 1, 2
+
+
+class EncRdReq(C.Structure):
+    """thip_enc_rd_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
+                ("stages", C.c_int32), ("lambda_search", C.c_int32), ("lambda_rd", C.c_int32),
+                ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("prev", C.c_void_p * 3), ("gold", C.c_void_p * 3),
+                ("ref_pitch", C.c_int64 * 3), ("dequant", C.c_void_p), ("bits", C.c_void_p), ("cand", C.c_void_p),
+                ("costs", C.c_void_p), ("words", C.c_void_p)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -227,6 +240,7 @@ SYMBOLS = [
     ("thip_enc_rate_stage", _I, [C.POINTER(EncRateReq)]),
     ("thip_enc_rate_groups", _I, [_I64]),
     ("thip_enc_mask_stage", _I, [C.POINTER(EncMaskReq)]),
+    ("thip_enc_rd_stage", _I, [C.POINTER(EncRdReq)]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

@@ -31,6 +31,7 @@
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_mask.h"
+#include "thip_encode_rd.h"
 #include "thip_encode_pack.h"
 #include "thip_encode_cut.h"
 #include "thip_bitstream.h"
@@ -278,6 +279,15 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint16_t *d_iscale = nullptr;
   hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr;
   thip_enc_mask_stats kstats;
+  // the rate-distortion mode decision (TH_ENCCTL_THIP_SET_RD_MODES; thip_encode_rd.h): the frame queued was decided by it (rd_queued)
+  // with lambda rd_lam and the tables rd_used; rd_hti: DC luma, DC chroma, AC luma, AC chroma of the last inter packet
+  bool rd = false, rd_queued = false;
+  int rd_hti[4] = {5, 5, 5, 5}, rd_used[4] = {0, 0, 0, 0};
+  int64_t rd_lam = 0;
+  uint4 *d_cand = nullptr;
+  uint8_t *d_rdbits = nullptr;   // [16 tables][5 Huffman groups][32 tokens]: code length + extra bits
+  hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
+  thip_enc_rd_stats dstats;
   // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
   bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
   int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
@@ -371,6 +381,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->mstats, 0, sizeof(e->mstats));
   memset(&e->bstats, 0, sizeof(e->bstats));
   memset(&e->kstats, 0, sizeof(e->kstats));
+  memset(&e->dstats, 0, sizeof(e->dstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
   memset(&e->pstats, 0, sizeof(e->pstats));
   memset(&e->cnext, 0, sizeof(e->cnext));
@@ -399,6 +410,7 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_mb4,                                                                                            // enc_modes_alloc
       (void **)&e->d_qii, (void **)&e->d_bqbits,                                                                     // enc_bqi_prepare
       (void **)&e->d_act, (void **)&e->d_mpart, (void **)&e->d_iscale,                                               // enc_mask_queue
+      (void **)&e->d_cand, (void **)&e->d_rdbits,                                                                    // enc_rd_queue
       (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
@@ -429,8 +441,9 @@ static void enc_free_device(th_enc_ctx *e) {
   e->rate_dev = false;
   e->q_queued = false;
   e->mask_queued = false;
+  e->rd_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
-                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1}) {
+                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -614,6 +627,43 @@ static void enc_mask_stats(th_enc_ctx *e, bool queued) {
   e->kstats.mask_ms = hipEventElapsedTime(&ms, e->ev_a0, e->ev_a1) == hipSuccess ? ms : 0.0;
 }
 
+// the rate-distortion mode decision in place of k_enc_me_all's (thip_encode_rd.h): the candidates, then the choice into d_mb4.  Its
+// buffers and the bits table at the first such frame (TH_ENCCTL_THIP_SET_RD_MODES never touches the GPU); no host wait
+static int enc_rd_queue(th_enc_ctx *e, const EncPlanes &g, const EncRef &R, const EncRef &G) {
+  if (!e->d_cand) {
+    for (hipEvent_t *ev : {&e->ev_r0, &e->ev_r1})
+      if (!*ev) ENC_TRY(hipEventCreate(ev));
+    ENC_TRY(hipMalloc((void **)&e->d_cand, (size_t)e->nmbs * 2 * sizeof(uint4)));
+    ENC_TRY(hipMalloc((void **)&e->d_rdbits, 16 * 5 * 32));
+    std::vector<uint8_t> bits(16 * 5 * 32);
+    for (int t = 0; t < 16; t++)
+      for (int hg = 0; hg < 5; hg++)
+        for (int tok = 0; tok < 32; tok++) bits[(t * 5 + hg) * 32 + tok] = (uint8_t)(e->setup.len[16 * hg + t][tok] + kTokExtraBits[tok]);
+    ENC_TRY(hipMemcpy(e->d_rdbits, bits.data(), bits.size(), hipMemcpyHostToDevice));
+  }
+  e->rd_lam = rd_lambda(e->lambda[e->frame_qi]);
+  for (int c = 0; c < 4; c++) e->rd_used[c] = e->rd_hti[c];
+  ENC_TRY(hipEventRecord(e->ev_r0, e->stream));
+  ENC_TRY(rd_launch(RdBufs{e->d_cand, e->d_mb4, nullptr}, true, true, g, R, G, e->nmbx, e->nmbs, e->lambda[e->frame_qi], e->rd_lam,
+                    e->d_dqi + (size_t)e->frame_qi * 384, e->d_rdbits, make_int4(e->rd_hti[0], e->rd_hti[1], e->rd_hti[2], e->rd_hti[3]),
+                    e->stream));
+  ENC_TRY(hipEventRecord(e->ev_r1, e->stream));
+  e->rd_queued = true;
+  return 0;
+}
+
+// the last packet's thip_enc_rd_stats: those of a frame not decided this way, or (queued: after the frame's wait) the frame's own
+static void enc_rd_stats(th_enc_ctx *e, bool queued) {
+  memset(&e->dstats, 0, sizeof(e->dstats));
+  e->dstats.on = e->rd ? 1 : 0;
+  if (!queued) return;
+  float ms = 0;
+  e->dstats.measured = 1;
+  for (int c = 0; c < 4; c++) e->dstats.huff[c] = e->rd_used[c];
+  e->dstats.lambda = e->rd_lam;
+  e->dstats.rd_ms = hipEventElapsedTime(&ms, e->ev_r0, e->ev_r1) == hipSuccess ? ms : 0.0;
+}
+
 // ---- the device packetiser (thip_encode_pack.h) ----------------------------------------------------------------------------------
 // its buffers and tables, at the first frame that needs them.  The packet buffer holds 128 bytes a block -- 16 bits a coefficient,
 // twice the raw picture; the natural image of tools/encode_time.py takes 9.5 bytes a block at quality 48 -- where the worst case, 65
@@ -719,6 +769,8 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   if constexpr (sizeof(Word) == sizeof(uint32_t)) {
     if (stats) ENC_TRY(cut_launch_mb_modes(d_mb, stats, e->nmbs, lambda, e->stream));
     else ENC_TRY(inter_launch_search(d_mb, g, R, e->nmbx, e->nmbs, lambda, e->stream));
+  } else if (e->rd) {
+    if (enc_rd_queue(e, g, R, gold...)) return TH_EFAULT;
   } else {
     ENC_TRY(inter_launch_search(d_mb, g, R, gold..., e->nmbx, e->nmbs, lambda, e->stream));
   }
@@ -978,6 +1030,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   }
   const int64_t n = e->nfrags;
   e->mask_queued = false;   // (enc_mask_queue says otherwise; a dropped frame never gets there)
+  e->rd_queued = false;     // (enc_rd_queue likewise)
   if (!e->rate) e->frame_qi = e->qi;   // (bitrate mode: the controller's choice, below)
   // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
   const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
@@ -1341,10 +1394,14 @@ static void enc_empty_packet(th_enc_ctx *e) {
   e->stats.qi = e->frame_qi;
   memset(&e->bstats, 0, sizeof(e->bstats));
   enc_mask_stats(e, false);
+  enc_rd_stats(e, false);
 }
 
-// what both packers leave behind: the frame's statistics, and the AC tables the next block-qi choice of this frame type counts with
+// what both packers leave behind: the frame's statistics, the AC tables the next block-qi choice of this frame type counts with, and
+// all four tables of an inter packet for the next rate-distortion mode decision
 static void enc_packet_done(th_enc_ctx *e, size_t total, size_t merged, const int hti[4], uint32_t overflow) {
+  if (!e->frame_key)
+    for (int c = 0; c < 4; c++) e->rd_hti[c] = hti[c];
   e->bqi_hti[e->frame_key ? 0 : 1][0] = hti[2];
   e->bqi_hti[e->frame_key ? 0 : 1][1] = hti[3];
   e->stats.tokens = (int64_t)total;
@@ -1538,6 +1595,7 @@ static int enc_finish_frame(th_enc_ctx *e) {
   if (total > (size_t)e->nfrags * kEncTokWords) return TH_EFAULT;
   memset(&e->pstats, 0, sizeof(e->pstats));
   enc_mask_stats(e, e->mask_queued);   // (an empty packet takes them back)
+  enc_rd_stats(e, e->rd_queued);
   const int rc = e->frame_dpack ? enc_pack_device(e, total, overflow) : enc_pack_host(e, total, overflow);
   e->pstats.fallbacks = e->pack_fallbacks;
   return rc;
@@ -1684,6 +1742,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->mstats, 0, sizeof(e->mstats));
     memset(&e->bstats, 0, sizeof(e->bstats));
     enc_mask_stats(e, false);
+    enc_rd_stats(e, false);
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
     const int qrc = enc_quality_queue(e, true);   // (against the picture the decoder goes on showing)
     if (qrc) return qrc;
@@ -1723,6 +1782,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->mstats, 0, sizeof(e->mstats));
     memset(&e->bstats, 0, sizeof(e->bstats));
     enc_mask_stats(e, false);
+    enc_rd_stats(e, false);
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
     (void)enc_quality_queue(e, false);
   } else {
@@ -1862,6 +1922,15 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->kstats.ratio = k;
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_RD_MODES: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int v = *(const int *)buf;
+      if (v != 0 && v != 1) return TH_EINVAL;
+      e->rd = v != 0;   // (its buffers are made at the first frame that uses it)
+      e->dstats.on = v;
+      return 0;
+    }
     case TH_ENCCTL_THIP_SET_DEVICE_PACK: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       const int v = *(const int *)buf;
@@ -1904,6 +1973,10 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     case TH_ENCCTL_THIP_GET_MASK_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_mask_stats)) return TH_EINVAL;
       *(thip_enc_mask_stats *)buf = e->kstats;
+      return 0;
+    case TH_ENCCTL_THIP_GET_RD_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_rd_stats)) return TH_EINVAL;
+      *(thip_enc_rd_stats *)buf = e->dstats;
       return 0;
     case TH_ENCCTL_THIP_GET_MODE_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_mode_stats)) return TH_EINVAL;
@@ -2167,6 +2240,77 @@ int thip_enc_inter_stage(const thip_enc_inter_req *q) {
     ENC_TRY(hipStreamSynchronize(stream));
     return THIP_OK;
   }
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the rate-distortion mode decision on the caller's planes, lambdas and tables (theora_hip.h): thip_encode_rd.h's launch function, as
+// enc_rd_queue makes it, on the current device's null stream
+int thip_enc_rd_stage(const thip_enc_rd_req *q) {
+  if (!q) return THIP_EFAULT;
+  const int st = q->stages;
+  if (st <= 0 || st > 3) return THIP_EINVAL;
+  const bool cand = st & THIP_ENC_RD_CAND, decide = st & THIP_ENC_RD_DECIDE;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
+  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+    return THIP_EINVAL;
+  for (int p = 0; p < 3; p++)
+    if (!q->src[p] || !q->prev[p] || !q->gold[p]) return THIP_EFAULT;
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
+    if (q->src_pitch[p] < pw || q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF) return THIP_EINVAL;
+  }
+  if (q->lambda_search < 0 || q->lambda_search > (1 << 24) || q->lambda_rd < 0 || q->lambda_rd > (1 << 24)) return THIP_EINVAL;
+  if (!q->cand || (decide && (!q->words || !q->dequant || !q->bits))) return THIP_EFAULT;
+  if (decide)
+    for (int k = 0; k < 384; k++)
+      if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (misaligned(q->cand, 16) || misaligned(q->words, 16) || misaligned(q->costs, 8)) return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int nmbx = geo.nh[0] >> 1, nmbs = nmbx * (geo.nv[0] >> 1);
+  EncPlanes g = {};
+  EncRef R = {}, G = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.src[p] = q->src[p];
+    g.stride[p] = q->src_pitch[p];
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+    R.plane[p] = q->prev[p];
+    G.plane[p] = q->gold[p];
+    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
+    R.w[p] = G.w[p] = geo.nh[p] * 8;
+    R.h[p] = G.h[p] = geo.nv[p] * 8;
+  }
+  R.hdec = G.hdec = hdec;
+  R.vdec = G.vdec = vdec;
+  // one allocation: dequant [384] | bits [2][5][32]
+  uint8_t *d = nullptr;
+  ENC_TRY(hipMalloc((void **)&d, 768 + 320));
+  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  if (decide) {
+    ENC_TRY(hipMemcpy(d, q->dequant, 768, hipMemcpyHostToDevice));
+    ENC_TRY(hipMemcpy(d + 768, q->bits, 320, hipMemcpyHostToDevice));
+  }
+  hipStream_t stream = nullptr;
+  // (the caller's two tables are tables 0 and 1 of the kernel's list: luma, chroma for the DC and the AC groups alike)
+  ENC_TRY(rd_launch(RdBufs{(uint4 *)q->cand, (uint4 *)q->words, q->costs}, cand, decide, g, R, G, nmbx, nmbs, q->lambda_search,
+                    (int64_t)q->lambda_rd, (const uint16_t *)d, d + 768, make_int4(0, 1, 0, 1), stream));
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

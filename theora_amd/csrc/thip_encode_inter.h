@@ -224,9 +224,9 @@ struct EncPred {   // how a block is predicted: the pixel mode, the vector of it
 // the prediction of block (p, fx, fy) from its macro block's word.  Word: uint32_t (k_enc_me's: mode | mvx << 8 | mvy << 16, PREV
 // only; G is not read) or uint4 (k_enc_me_all's, thip_encode_modes.h: GOLD modes, and MV_FOUR with the block's own vector in luma
 // and the vector the decoder derives in chroma -- thip_frontend.cpp, spec 7.5)
+// (enc_word_pred: from the word itself -- k_enc_mb_rd of thip_encode_rd.h predicts from each candidate's word before one is written)
 template <class Word>
-__device__ __forceinline__ EncPred enc_block_pred(const Word *mbw, int nmbx, const EncRef &R, const EncRef &G, int p, int fx, int fy) {
-  const Word mw = mbw[enc_mb_of(p, fx, fy, R.hdec, R.vdec, nmbx)];
+__device__ __forceinline__ EncPred enc_word_pred(const Word &mw, const EncRef &R, const EncRef &G, int p, int fx, int fy) {
   if constexpr (sizeof(Word) == sizeof(uint32_t)) {
     return {(int)(mw & 0xFF), (int)(int8_t)(mw >> 8), (int)(int8_t)(mw >> 16), R.plane[p]};
   } else {
@@ -252,6 +252,10 @@ __device__ __forceinline__ EncPred enc_block_pred(const Word *mbw, int nmbx, con
     const uint8_t *pr = R.plane[p], *pg = G.plane[p];   // (both loaded, then the value chosen: choosing the struct copied both to scratch)
     return {pix, mvx, mvy, enc_pix_gold(pix) ? pg : pr};
   }
+}
+template <class Word>
+__device__ __forceinline__ EncPred enc_block_pred(const Word *mbw, int nmbx, const EncRef &R, const EncRef &G, int p, int fx, int fy) {
+  return enc_word_pred(mbw[enc_mb_of(p, fx, fy, R.hdec, R.vdec, nmbx)], R, G, p, fx, fy);
 }
 
 // The predictor pixels of block (p, fx, fy) under `pr`, as EncSrcBlock holds the source's: the decoder's offsets (mv_axis, quarter

@@ -9,6 +9,8 @@
 //                    (PREV and GOLD macro block, four blocks).  Out: one uint4 a macro block: x the pixel mode | vector << 8 (the
 //                    vector of MV or GOLDEN_MV, else 0), y, z the block vectors 0, 1 and 2, 3 of MV_FOUR (16 bits each, else 0),
 //                    w the GOLD search's vector.
+//   k_enc_me_cand    the same search (one body, enc_me_all) without the decision: every candidate's vector and SAD, for the
+//                    rate-distortion mode decision of thip_encode_rd.h.
 //   k_enc_inter_fq_all  enc_inter_fq (thip_encode_inter.h) over those words: the prediction is from PREV or GOLD, through the
 //                    block's own vector in MV_FOUR luma and the vector the decoder derives for its chroma (enc_block_pred);
 //                    cmap 1 intra, 2 PREV, 3 GOLD.
@@ -37,8 +39,12 @@ __device__ __forceinline__ uint32_t enc_hp_row_sad(const uint32_t *win32, const 
   return sad;
 }
 
-// grid: one work group per macro block (raster, rows from the bottom).  lambda: the frame's inter luma step at zig-zag index 1.
-__global__ __launch_bounds__(256) void k_enc_me_all(uint4 *mb_out, EncPlanes g, EncRef R, EncRef G, int nmbx, int lambda) {
+// The body of k_enc_me_all and, with kCand, of k_enc_me_cand: the same search without the decision, which thip_encode_rd.h's
+// k_enc_mb_rd makes from real costs.  kCand writes two uint4 a macro block: x = pack(mvx, mvy) | pack(gx, gy) << 16, y = block
+// vectors 0, 1, z = block vectors 2, 3, w = S0 | Smv << 16; then x = S4 | SI << 16, y = G0 | Gmv << 16, z = w = 0 (a SAD is at most
+// 65 280).  lambda is not read then.
+template <bool kCand>
+__device__ __forceinline__ void enc_me_all(uint4 *mb_out, const EncPlanes &g, const EncRef &R, const EncRef &G, int nmbx, int lambda) {
   __shared__ uint32_t s_win[kMeWin * kMeWin / 4], s_gwin[kMeWin * kMeWin / 4];
   __shared__ uint32_t s_src[16 * 4];
   __shared__ uint64_t s_best[6][4];   // PREV macro block, PREV blocks 0..3, GOLD macro block; per wave
@@ -152,6 +158,12 @@ __global__ __launch_bounds__(256) void k_enc_me_all(uint4 *mb_out, EncPlanes g, 
 #pragma unroll
     for (int b = 0; b < 4; b++) s4 += enc_hp_choose(kb[1 + b], s_hp + 16 + 8 * b, bx[b], by[b]);
     const int s0 = (int)s_s0, g0 = (int)s_g0, si = (int)s_si;
+    if constexpr (kCand) {
+      mb_out[2 * (int64_t)mb] = make_uint4(enc_mv_pack(mvx, mvy) | enc_mv_pack(gx, gy) << 16, enc_mv_pack(bx[0], by[0]) | enc_mv_pack(bx[1], by[1]) << 16,
+                                            enc_mv_pack(bx[2], by[2]) | enc_mv_pack(bx[3], by[3]) << 16, (uint32_t)s0 | (uint32_t)smv << 16);
+      mb_out[2 * (int64_t)mb + 1] = make_uint4((uint32_t)s4 | (uint32_t)si << 16, (uint32_t)g0 | (uint32_t)gmv << 16, 0u, 0u);
+      return;
+    }
     // the mode rule of theoraenc_hip.h: PREV with one vector, four vectors, GOLD, INTRA; ties keep the earlier choice
     int mode = kEncPixNomv, C = s0, S = s0;
     if (smv + lambda < s0) {
@@ -180,6 +192,16 @@ __global__ __launch_bounds__(256) void k_enc_me_all(uint4 *mb_out, EncPlanes g, 
     mb_out[mb] = make_uint4((uint32_t)mode | v << 8, four ? enc_mv_pack(bx[0], by[0]) | enc_mv_pack(bx[1], by[1]) << 16 : 0u,
                             four ? enc_mv_pack(bx[2], by[2]) | enc_mv_pack(bx[3], by[3]) << 16 : 0u, enc_mv_pack(gx, gy));
   }
+}
+
+// grid: one work group per macro block (raster, rows from the bottom).  lambda: the frame's inter luma step at zig-zag index 1.
+__global__ __launch_bounds__(256) void k_enc_me_all(uint4 *mb_out, EncPlanes g, EncRef R, EncRef G, int nmbx, int lambda) {
+  enc_me_all<false>(mb_out, g, R, G, nmbx, lambda);
+}
+
+// the candidate form: cand [nmbs][2] (enc_me_all<true>)
+__global__ __launch_bounds__(256) void k_enc_me_cand(uint4 *cand, EncPlanes g, EncRef R, EncRef G, int nmbx, int lambda) {
+  enc_me_all<true>(cand, g, R, G, nmbx, lambda);
 }
 
 // k_enc_inter_fq reading k_enc_me_all's words; G: GOLD (R's geometry), dclast [ceil(nfrags / 256)][3] (zeroed before)

@@ -36,6 +36,8 @@ TH_ENCCTL_THIP_SET_QUALITY_STATS = 0x7212
 TH_ENCCTL_THIP_GET_QUALITY_STATS = 0x7213
 TH_ENCCTL_THIP_SET_MASKING = 0x7214
 TH_ENCCTL_THIP_GET_MASK_STATS = 0x7215
+TH_ENCCTL_THIP_SET_RD_MODES = 0x7218
+TH_ENCCTL_THIP_GET_RD_STATS = 0x7219
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
 TH_ENCCTL_SET_RATE_FLAGS = 20
@@ -105,6 +107,11 @@ class MaskStats(C.Structure):
                 ("mask_ms", C.c_double)]
 
 
+class RdStats(C.Structure):
+    """thip_enc_rd_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("on", C.c_int32), ("measured", C.c_int32), ("huff", C.c_int32 * 4), ("lam", C.c_int64), ("rd_ms", C.c_double)]
+
+
 class RateStats(C.Structure):
     """thip_enc_rate_stats (include/theoraenc_hip.h)."""
     _fields_ = [("qi", C.c_int32), ("dropped", C.c_int32), ("key", C.c_int32), ("duplicate", C.c_int32), ("target", C.c_int64),
@@ -137,7 +144,7 @@ class Encoder:
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
-                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0):
+                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -149,7 +156,8 @@ class Encoder:
         auto_keyframes: a key frame wherever prediction stops paying, the interval becoming a maximum
         (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES): True for the recommended ratio AUTO_KEYFRAMES_DEFAULT, or the ratio t itself, 1..4096;
         None, False or 0 leave it off.  No effect without inter=True.  masking: activity masking with that ratio, 2..16
-        (TH_ENCCTL_THIP_SET_MASKING; 0 off; recommended 4).  No effect without block_qi."""
+        (TH_ENCCTL_THIP_SET_MASKING; 0 off; recommended 4).  No effect without block_qi.  rd_modes: the macro-block modes of
+        eight-mode inter frames by the least D + lambda R (TH_ENCCTL_THIP_SET_RD_MODES).  No effect without all_modes."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -185,6 +193,9 @@ class Encoder:
         self.masking = 0
         if masking:
             self.set_masking(masking)
+        self.rd_modes = False
+        if rd_modes:
+            self.set_rd_modes(rd_modes)
         if device_pack is not None:
             self.set_device_pack(device_pack)
         self.auto_keyframes = AUTO_KEYFRAMES_DEFAULT if auto_keyframes is True else int(auto_keyframes or 0)
@@ -219,6 +230,23 @@ class Encoder:
         if rc < 0:
             raise ValueError("masking must be 0 or 2..16, set before the first frame (TH_ENCCTL_THIP_SET_MASKING returned %d)" % rc)
         self.masking = int(k)
+
+    def set_rd_modes(self, on):
+        """TH_ENCCTL_THIP_SET_RD_MODES, before the first frame: the rate-distortion mode decision on (True) or off."""
+        rc, _ = self.ctl(TH_ENCCTL_THIP_SET_RD_MODES, int(bool(on)))
+        if rc < 0:
+            raise ValueError("rd_modes is set before the first frame (TH_ENCCTL_THIP_SET_RD_MODES returned %d)" % rc)
+        self.rd_modes = bool(on)
+
+    def rd_stats(self):
+        """TH_ENCCTL_THIP_GET_RD_STATS of the last packet, as a dict (lam: the struct's lambda)."""
+        s = RdStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_RD_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_RD_STATS returned %d" % rc)
+        d = {k: getattr(s, k) for k, _ in RdStats._fields_}
+        d["huff"] = list(s.huff)
+        return d
 
     def set_device_pack(self, on):
         """TH_ENCCTL_THIP_SET_DEVICE_PACK: from the next frame on (not between encode() and packetout())."""
@@ -551,6 +579,36 @@ def mask_stage(frame, pixel_fmt, ratio, pic=None, src=None, src_pitch=None, act=
         q.src_pitch[p] = 0 if src_pitch is None else int(src_pitch[p])
     q.act, q.avg, q.iscale = act, avg, iscale
     return L.thip_enc_mask_stage(C.byref(q))
+
+
+def rd_stage(frame, pixel_fmt, stages, pic=None, lambda_search=0, lambda_rd=0, src=None, src_pitch=None, prev=None, gold=None,
+             ref_pitch=None, dequant=None, bits=None, cand=None, costs=None, words=None):
+    """thip_enc_rd_stage (include/theora_hip.h): the rate-distortion mode decision on the caller's planes, lambdas and tables, a test
+    and diagnostic entry.  frame: (width, height); pic: (x, y, width, height), the whole frame when None; stages: an OR of
+    _lib.ENC_RD_*; src, prev, gold: three device addresses each (None where there is none) with their pitches; dequant [2][3][64]
+    and bits [2][5][32]: anything numpy converts (None is NULL); cand, costs, words: device addresses, None is NULL.  Returns the
+    entry's return code; nothing is raised, the refusals are the caller's to look at."""
+    L = _lib.load()
+    q = _lib.EncRdReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.stages, q.lambda_search, q.lambda_rd = int(stages), int(lambda_search), int(lambda_rd)
+    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
+        for p in range(3):
+            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
+    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
+        for p in range(3):
+            getattr(q, name)[p] = 0 if v is None else int(v[p])
+    keep = []
+    for name, v, t, size in (("dequant", dequant, np.uint16, 384), ("bits", bits, np.uint8, 320)):
+        if v is not None:
+            a = np.ascontiguousarray(v, t).reshape(-1)
+            if a.size != size:
+                raise ValueError("rd_stage: %s of %d entries where %d are expected" % (name, a.size, size))
+            keep.append(a)
+            setattr(q, name, a.ctypes.data)
+    q.cand, q.costs, q.words = cand, costs, words
+    return L.thip_enc_rd_stage(C.byref(q))
 
 
 def rate_groups(nfrags):

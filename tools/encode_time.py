@@ -23,7 +23,11 @@ counts the key frames it made (none on the panning sequence).
 With --masking K (with --block-qi, in quality mode): activity masking at ratio K (TH_ENCCTL_THIP_SET_MASKING); mask_ms is the device
 time of its two launches (TH_ENCCTL_THIP_GET_MASK_STATS), which device_ms includes.
 
-  python tools/encode_time.py [--frames 20] [--inter N [--all-modes]] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
+With --rd-modes (with --inter N --all-modes): the eight-mode cases run with the rate-distortion mode decision on
+(TH_ENCCTL_THIP_SET_RD_MODES); rd_ms is the device time of its two launches (TH_ENCCTL_THIP_GET_RD_STATS), which device_ms includes.
+Switch off and on are two runs of the tool.
+
+  python tools/encode_time.py [--frames 20] [--inter N [--all-modes [--rd-modes]]] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
                               [--auto-keyframes [T]] [--json out.json]
 """
 import argparse
@@ -69,6 +73,7 @@ def main():
     ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
     ap.add_argument("--block-qi", type=int, default=0, help="block-level qi with this delta (TH_ENCCTL_THIP_SET_BLOCK_QI)")
     ap.add_argument("--masking", type=int, default=0, help="with --block-qi: activity masking at this ratio (TH_ENCCTL_THIP_SET_MASKING)")
+    ap.add_argument("--rd-modes", action="store_true", help="with --inter --all-modes: the eight-mode cases with TH_ENCCTL_THIP_SET_RD_MODES on")
     ap.add_argument("--device-pack", action="store_true", help="each case with the device packetiser off, then on")
     ap.add_argument("--auto-keyframes", type=int, nargs="?", const=230, default=0, metavar="T",
                     help="with --inter or --bitrate: each case with automatic key frames off, then on at ratio T (default 230)")
@@ -131,9 +136,9 @@ def main_inter(args):
                               for dp in ((False, True) if args.device_pack else (False,))
                               for ak in ((0, args.auto_keyframes) if args.auto_keyframes else (0,))]:
             e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi,
-                        device_pack=dp, auto_keyframes=ak, masking=args.masking)
+                        device_pack=dp, auto_keyframes=ak, masking=args.masking, rd_modes=args.rd_modes and am)
             hdr = e.header_packets()
-            dev, host, wall, pkts, keys, pack, meas, cuts, mask = [], [], [], [], 0, [], [], 0, []
+            dev, host, wall, pkts, keys, pack, meas, cuts, mask, rdms = [], [], [], [], 0, [], [], 0, [], []
             for f in range(n):
                 t0 = time.perf_counter()
                 e.encode(frames[f])
@@ -149,12 +154,14 @@ def main_inter(args):
                     pack.append(e.pack_stats()["pack_ms"])
                     meas.append(e.cut_stats()["measure_ms"])
                     mask.append(e.mask_stats()["mask_ms"])
+                    rdms.append(e.rd_stats()["rd_ms"])
                 keys += key
                 cuts += e.cut_stats()["cut"]
             e.close()
             ps = [psnr(qs["sse"][0], qs["samples"][0])
                   for qs in quality_pass(frames, w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am,
-                                         block_qi=args.block_qi, device_pack=dp, auto_keyframes=ak, masking=args.masking)]
+                                         block_qi=args.block_qi, device_pack=dp, auto_keyframes=ak, masking=args.masking,
+                                         rd_modes=args.rd_modes and am)]
             r = dict(size=name, quality=q, inter=args.inter, all_modes=am, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
@@ -165,6 +172,8 @@ def main_inter(args):
                 r.update(auto_keyframes=ak, measure_ms=round(float(np.median(meas)), 4), cut_frames=cuts)
             if args.masking:
                 r.update(masking=args.masking, mask_ms=round(float(np.median(mask)), 4))
+            if args.rd_modes:
+                r.update(rd_modes=bool(am), rd_ms=round(float(np.median(rdms)), 4))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
