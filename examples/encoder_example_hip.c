@@ -1,7 +1,8 @@
 /* encoder_example_hip.c -- YUV4MPEG2 in, Ogg/Theora out, through this library's intra-only th_encode_* (include/theoraenc_hip.h)
  * and its Ogg writer (include/thip_ogg.h).
  *
- *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta] [-V kbps] [-o out.ogv] in.y4m
+ *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta] [-V kbps]
+ *                       [--first-pass FILE | --second-pass FILE | --two-pass] [-o out.ogv] in.y4m
  *
  * Input: C420jpeg, C420, C420paldv, C420mpeg2 (4:2:0), C422 or C444, any size; no C tag means 4:2:0.  The frame is the picture
  * padded to multiples of 16, the picture region at (0, 0); the picture-size planes go to th_encode_ycbcr_in as they are.  Every
@@ -11,6 +12,11 @@
  * (TH_ENCCTL_THIP_SET_BLOCK_QI).  --device-pack: the packets' token bits are made on the GPU (TH_ENCCTL_THIP_SET_DEVICE_PACK; the
  * same bytes).  -V: bitrate mode at kbps * 1000 bits a second
  * (TH_ENCCTL_SET_BITRATE), as libtheora's encoder_example -V.  Output on stdout without -o.
+ *
+ * Two-pass, with libtheora's encoder_example's option names (TH_ENCCTL_THIP_2PASS_OUT / _IN, "Two-pass" in theoraenc_hip.h):
+ * --first-pass FILE encodes once, writes the pass file and no video (with -V the first pass runs in bitrate mode, else at -q);
+ * --second-pass FILE (needs -V) encodes to that file's curves; --two-pass (needs -V) does both through a temporary file, the first
+ * pass at -q, and reads the input twice, so the input must be a file.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -59,30 +65,39 @@ static int read_frame(FILE *in, unsigned char *buf, size_t bytes) {
   return fread(buf, 1, bytes, in) == bytes ? 1 : -1;
 }
 
-int main(int argc, char **argv) {
-  int quality = 48, kf = 0, all_modes = 0, bqi = 0, device_pack = 0, auto_kf = 0;
-  long kbps = 0;
-  const char *in_path = NULL, *out_path = NULL;
-  for (int i = 1; i < argc; i++) {
-    if (strcmp(argv[i], "-q") == 0 && i + 1 < argc) quality = atoi(argv[++i]);
-    else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) out_path = argv[++i];
-    else if (strcmp(argv[i], "-k") == 0 && i + 1 < argc) kf = atoi(argv[++i]);
-    else if (strcmp(argv[i], "-V") == 0 && i + 1 < argc) kbps = atol(argv[++i]);
-    else if (strcmp(argv[i], "-m") == 0) all_modes = 1;
-    else if (strcmp(argv[i], "-a") == 0) auto_kf = i + 2 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' ? atoi(argv[++i]) : 230;
-    else if (strcmp(argv[i], "-b") == 0 && i + 1 < argc) bqi = atoi(argv[++i]);
-    else if (strcmp(argv[i], "--device-pack") == 0) device_pack = 1;
-    else in_path = argv[i];
+typedef struct {
+  int quality, kf, all_modes, bqi, device_pack, auto_kf;
+  long kbps;
+} options;
+
+/* feeds the second pass until it can take the next frame (libtheora's encoder_example loop); 0 on success */
+static int feed_pass_file(th_enc_ctx *enc, FILE *pf) {
+  unsigned char chunk[4096];
+  for (;;) {
+    const int want = th_encode_ctl(enc, TH_ENCCTL_THIP_2PASS_IN, NULL, 0);
+    if (want < 0) return -1;
+    if (want == 0) return 0;
+    const size_t n = fread(chunk, 1, (size_t)want < sizeof(chunk) ? (size_t)want : sizeof(chunk), pf);
+    if (n == 0) return -1;   /* the pass file is shorter than the input */
+    const int used = th_encode_ctl(enc, TH_ENCCTL_THIP_2PASS_IN, chunk, n);
+    if (used < 0 || (size_t)used != n) return -1;
   }
-  if (!in_path || ((all_modes || auto_kf) && kf <= 0)) {
-    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi] [--device-pack] [-V kbps] [-o out.ogv] in.y4m\n", argv[0]);
-    return 1;
-  }
-  FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
-  if (!in) {
-    fprintf(stderr, "cannot open %s\n", in_path);
-    return 1;
-  }
+}
+
+/* one record (or header) of the first pass to the pass file; 0 on success */
+static int write_pass_bytes(th_enc_ctx *enc, FILE *pf) {
+  unsigned char *p = NULL;
+  const int n = th_encode_ctl(enc, TH_ENCCTL_THIP_2PASS_OUT, &p, sizeof(p));
+  if (n < 0 || (n > 0 && fwrite(p, 1, (size_t)n, pf) != (size_t)n)) return -1;
+  return 0;
+}
+
+/* one pass over the input.  pass 0: plain; 1: the first pass, the pass file to pf and no video (out is NULL); 2: the second pass,
+   the pass file from pf */
+static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
+  const int quality = o->quality, kf = o->kf;
+  int bqi = o->bqi, all_modes = o->all_modes, device_pack = o->device_pack, auto_kf = o->auto_kf;
+  const long kbps = o->kbps;
   int w, h, fn, fd, an, ad, fmt;
   if (parse_header(in, &w, &h, &fn, &fd, &an, &ad, &fmt)) {
     fprintf(stderr, "not a YUV4MPEG2 file this example reads\n");
@@ -145,9 +160,12 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
-  FILE *out = out_path ? fopen(out_path, "wb") : stdout;
-  if (!out) {
-    fprintf(stderr, "cannot open %s\n", out_path);
+  if (pass == 1 && write_pass_bytes(enc, pf)) {   /* the header's placeholder */
+    fprintf(stderr, "first pass refused\n");
+    return 1;
+  }
+  if (pass == 2 && feed_pass_file(enc, pf)) {      /* enters the second pass: the header */
+    fprintf(stderr, "second pass refused (not a pass file of this input and these options?)\n");
     return 1;
   }
   thip_ogg_writer *ow = thip_ogg_writer_new(0x7E0u);
@@ -159,7 +177,7 @@ int main(int argc, char **argv) {
     if (thip_ogg_writer_packetin(ow, &op)) rc = -1;
   th_comment_clear(&tc);
   thip_ogg_writer_flush(ow);   /* the headers end a page: data starts on a fresh one */
-  if (rc < 0 || write_pages(ow, out)) {
+  if (rc < 0 || (out && write_pages(ow, out))) {
     fprintf(stderr, "header error\n");
     return 1;
   }
@@ -175,13 +193,21 @@ int main(int argc, char **argv) {
     yb[0].width = w, yb[0].height = h, yb[0].stride = w, yb[0].data = buf[cur];
     yb[1].width = cw, yb[1].height = ch, yb[1].stride = cw, yb[1].data = buf[cur] + ysz;
     yb[2].width = cw, yb[2].height = ch, yb[2].stride = cw, yb[2].data = buf[cur] + ysz + csz;
+    if (pass == 2 && feed_pass_file(enc, pf)) {
+      fprintf(stderr, "the pass file ends before the input\n");
+      return 1;
+    }
     if (th_encode_ycbcr_in(enc, yb)) {
       fprintf(stderr, "th_encode_ycbcr_in failed\n");
       return 1;
     }
     while ((rc = th_encode_packetout(enc, next == 0, &op)) > 0) {
-      if (thip_ogg_writer_packetin(ow, &op) || write_pages(ow, out)) {
+      if (out && (thip_ogg_writer_packetin(ow, &op) || write_pages(ow, out))) {
         fprintf(stderr, "write error\n");
+        return 1;
+      }
+      if (pass == 1 && write_pass_bytes(enc, pf)) {   /* the packet's record */
+        fprintf(stderr, "pass file write error\n");
         return 1;
       }
     }
@@ -198,13 +224,72 @@ int main(int argc, char **argv) {
     return 1;
   }
   thip_ogg_writer_flush(ow);
-  if (write_pages(ow, out)) return 1;
-  fprintf(stderr, "%d frames\n", nframes);
+  if (out && write_pages(ow, out)) return 1;
+  if (pass == 1) {   /* the finished header over the placeholder */
+    if (fseek(pf, 0, SEEK_SET) || write_pass_bytes(enc, pf) || fflush(pf)) {
+      fprintf(stderr, "pass file write error\n");
+      return 1;
+    }
+  }
+  fprintf(stderr, "%d frames%s\n", nframes, pass == 1 ? " (first pass)" : pass == 2 ? " (second pass)" : "");
   thip_ogg_writer_free(ow);
   th_encode_free(enc);
   free(buf[0]);
   free(buf[1]);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  options o = {48, 0, 0, 0, 0, 0, 0};
+  const char *in_path = NULL, *out_path = NULL, *first = NULL, *second = NULL;
+  int two_pass = 0;
+  for (int i = 1; i < argc; i++) {
+    if (strcmp(argv[i], "-q") == 0 && i + 1 < argc) o.quality = atoi(argv[++i]);
+    else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) out_path = argv[++i];
+    else if (strcmp(argv[i], "-k") == 0 && i + 1 < argc) o.kf = atoi(argv[++i]);
+    else if (strcmp(argv[i], "-V") == 0 && i + 1 < argc) o.kbps = atol(argv[++i]);
+    else if (strcmp(argv[i], "-m") == 0) o.all_modes = 1;
+    else if (strcmp(argv[i], "-a") == 0) o.auto_kf = i + 2 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' ? atoi(argv[++i]) : 230;
+    else if (strcmp(argv[i], "-b") == 0 && i + 1 < argc) o.bqi = atoi(argv[++i]);
+    else if (strcmp(argv[i], "--device-pack") == 0) o.device_pack = 1;
+    else if (strcmp(argv[i], "--first-pass") == 0 && i + 1 < argc) first = argv[++i];
+    else if (strcmp(argv[i], "--second-pass") == 0 && i + 1 < argc) second = argv[++i];
+    else if (strcmp(argv[i], "--two-pass") == 0) two_pass = 1;
+    else in_path = argv[i];
+  }
+  const int npass = (first != NULL) + (second != NULL) + two_pass;
+  if (!in_path || ((o.all_modes || o.auto_kf) && o.kf <= 0) || npass > 1 || ((second || two_pass) && o.kbps <= 0) ||
+      (two_pass && strcmp(in_path, "-") == 0)) {
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file)] [-o out.ogv] in.y4m\n", argv[0]);
+    return 1;
+  }
+  FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
+  if (!in) {
+    fprintf(stderr, "cannot open %s\n", in_path);
+    return 1;
+  }
+  FILE *pf = NULL;
+  if (first || second || two_pass) {
+    pf = two_pass ? tmpfile() : fopen(first ? first : second, first ? "wb" : "rb");
+    if (!pf) {
+      fprintf(stderr, "cannot open the pass file\n");
+      return 1;
+    }
+  }
+  if (first) return encode(&o, in, NULL, 1, pf) || fclose(pf) ? 1 : 0;
+  if (two_pass) {   /* the first pass at -q, then the input again */
+    options p1 = o;
+    p1.kbps = 0;
+    if (encode(&p1, in, NULL, 1, pf) || fseek(pf, 0, SEEK_SET) || fseek(in, 0, SEEK_SET)) return 1;
+  }
+  FILE *out = out_path ? fopen(out_path, "wb") : stdout;
+  if (!out) {
+    fprintf(stderr, "cannot open %s\n", out_path);
+    return 1;
+  }
+  const int rc = encode(&o, in, out, pf ? 2 : 0, pf);
   if (out != stdout) fclose(out);
   if (in != stdin) fclose(in);
-  return 0;
+  if (pf) fclose(pf);
+  return rc;
 }

@@ -5,8 +5,9 @@
  *
  * What it is not, by default: every data packet is a key frame.  There is no mode decision, motion search or rate control by
  * default.  Bitrate mode is entered through TH_ENCCTL_SET_BITRATE after th_encode_alloc ("Bitrate mode" below); th_info.target_bitrate
- * != 0 at th_encode_alloc is refused (NULL).  2-pass, custom Huffman codes or quantisation parameters and VP3 compatibility are not
- * available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
+ * != 0 at th_encode_alloc is refused (NULL).  Two-pass encoding goes through TH_ENCCTL_THIP_2PASS_OUT / _IN ("Two-pass" below;
+ * libtheora's own requests 24 and 26 answer TH_EIMPL, their record format is not this one).  Custom Huffman codes or quantisation
+ * parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
  *
  * The bitstream, stated so that a restatement reproduces the packets byte for byte (tests/enc_ref.py does):
  *   - Setup header.  Loop-filter limits lflim[qi] = (31 * (63 - qi) + 31) / 63.  AC and DC scales fall geometrically,
@@ -253,6 +254,48 @@
  * gets who decodes the packets and sums (source - decoded)^2 over the picture region, the reference's dump_psnr among them.  The
  * switch changes no bit of any packet in any mode.
  *
+ * Two-pass (TH_ENCCTL_THIP_2PASS_OUT, TH_ENCCTL_THIP_2PASS_IN), stated so that a restatement reproduces every byte and every choice
+ * (tests/enc_2pass_ref.py does).  A first pass writes down, per packet, the curve E[0..63] the rate probe measured for the frame; a
+ * second pass reads the whole file's curves and spends the file's bits at the most even qi that fits.
+ *   - The pass file, little-endian throughout: a header of 1084 bytes, then one record of 264 bytes a packet, in packet order.
+ *     Header: the magic "THP2" (bytes 0x54 0x48 0x50 0x32), u32 version = 1, then eleven u32: frame_width, frame_height, pic_x,
+ *     pic_y, pic_width, pic_height, pixel_fmt, fps_numerator, fps_denominator, keyframe_granule_shift, the inter-frame switch (0 / 1);
+ *     u32 frames (the records that are not duplicates), u32 duplicates (the records of type 2); then Tot[0][0..63] and Tot[1][0..63]
+ *     as u64: per class (0 key, 1 inter) the sums of the records' E[q].  The placeholder the first call returns is the header with
+ *     frames, duplicates and the sums 0.
+ *     Record: u8 type (0 key, 1 inter, 2 a TH_ENCCTL_SET_DUP_COUNT duplicate, 3 a frame the rate controller dropped), u8 qi (the
+ *     frame's qis[0]; for types 2 and 3 the last frame's), u16 0, u32 the packet's bits (saturating), E[0..63] as u32, each
+ *     min(E[q], 2^32 - 1) (type 2: all 0).  A record's class: its type for 0 and 1; a dropped frame counts as class 1 with inter
+ *     frames on, else 0; a duplicate has none and enters no sum.
+ *   - Pass 1 changes no bit of any packet, in quality mode or in bitrate mode.  Every frame that is not a duplicate gets the probe
+ *     of "Bitrate mode" against the reference it is really coded from, with the type it really has (interval rule, or a cut by
+ *     automatic key frames).  In bitrate mode that probe runs anyway.  In quality mode its launches are queued on the encoder's
+ *     stream in front of the frame's, the 512 bytes are copied asynchronously and read in th_encode_packetout: th_encode_ycbcr_in
+ *     still never waits.
+ *   - Pass 2 (bitrate mode only) is a controller of its own beside the one above.  N = frames + duplicates of the header, T as in
+ *     "Bitrate mode" from the bitrate in force, B = T N, A = the bits of the packets so far; c_key = c_0, c_inter = c_1 as above; per
+ *     class the recorded and the fresh curves of the frames so far, Seen[2][64] = Fresh[2][64] = 0.
+ *   - Frame n (counted with the duplicates) needs record n.  Its type comes from the record: a key frame when the record's type is 0,
+ *     an inter frame when it is 1; the interval rule and the cut measurement are not consulted.  Whatever the record says the frame
+ *     is a key frame when it is the first, when inter frames are off, or when its offset from the last key frame plus its own
+ *     duplicates reaches 1 << keyframe_granule_shift (with the same duplicates pass 1 decided the same).  Where the caller submits a
+ *     frame whose record is a drop or a duplicate, it is coded as an inter frame under the same conditions; no frame is dropped in
+ *     pass 2.  The caller repeats its own TH_ENCCTL_SET_DUP_COUNT calls: a duplicate packet consults no record and adds nothing to A.
+ *   - The probe of "Bitrate mode" gives the fresh E.  The record's class t' (if it has one): for all q, Seen[t'][q] += Rec[q] and
+ *     Fresh[t'][q] = min(Fresh[t'][q] + E[q], 2^62).  With t the frame's own type, Cur(q) = E[q] c_t >> 16.  Per class u,
+ *     X = max(Tot[u][q] - Seen[u][q], 0), what the recorded curves leave; Y = X where Seen[u][q] = 0, else
+ *     min(X Fresh[u][q] / Seen[u][q], 2^62) (128-bit product, the division rounding down): the rest of the file is taken to relate
+ *     to its records as the fresh curves so far do to theirs, which absorbs the second pass's different reference; Future(q) = the
+ *     sum over u of (Y c_u >> 16), c absorbing the flags, modes and vectors as in "Bitrate mode".  qi = the largest q with
+ *     Cur(q) + Future(q) <= B - A, else 0.
+ *   - After the packet of A_n bits: A += A_n, and c_t as in "Bitrate mode".  (A second Q16 correction per class averaged in after
+ *     each packet, r = (r + A_n / Rec[qi]) / 2, was tried first: it learns a frame later and from one qi only, and landed farther
+ *     from B; DESIGN.md section 5.17 has the figures.)
+ *   - TH_ENCCTL_SET_RATE_FLAGS and TH_ENCCTL_SET_RATE_BUFFER are accepted in pass 2 and have no effect (there is no buffer and no
+ *     drop).  thip_enc_rate_stats in pass 2: qi, key, target, estimate, actual, probe, corr as above; fullness_before, spend =
+ *     B - A before the packet, fullness_after = B - A after it.  Block qi, masking, RD modes, the device packetiser and the quality
+ *     statistics compose as with bitrate mode: the controller chooses qis[0].
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / _RGB_IN / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
  * extensions, YCBCR_IN_DEVICE, RGB_IN, GET_DEVICE and GET_QUALITY_STATS do.
@@ -290,8 +333,8 @@ extern "C" {
 #define TH_ENCCTL_SET_QUANT_PARAMS (2)
 #define TH_ENCCTL_SET_VP3_COMPATIBLE (10)
 #define TH_ENCCTL_GET_SPLEVEL (16)
-#define TH_ENCCTL_2PASS_OUT (24)
-#define TH_ENCCTL_2PASS_IN (26)
+#define TH_ENCCTL_2PASS_OUT (24)                   /* (libtheora's two-pass requests and its record format: not these.  A caller */
+#define TH_ENCCTL_2PASS_IN (26)                    /*  ported from libtheora uses TH_ENCCTL_THIP_2PASS_OUT / _IN below instead) */
 #define TH_ENCCTL_SET_COMPAT_CONFIG (32)
 
 /* Extension: buf = thip_enc_device_in.  What th_encode_ycbcr_in does, with plane pointers in device memory on the context's GPU
@@ -487,6 +530,46 @@ typedef struct thip_enc_rd_stats {
   int64_t lambda;         /* the rule's lambda */
   double rd_ms;           /* HIP events around the two launches */
 } thip_enc_rd_stats;
+
+/* Extension: the first pass of "Two-pass" above, with TH_ENCCTL_2PASS_OUT's calling convention: buf = unsigned char **, buf_sz ==
+   sizeof(unsigned char *) (else TH_EINVAL).  The first call must come before the first frame (else TH_EINVAL; TH_EINVAL too on a
+   context that has had TH_ENCCTL_THIP_2PASS_IN); it enters pass 1, in quality or in bitrate mode, and returns the length of the header
+   placeholder, *buf pointing at it.  After each th_encode_packetout one call returns that packet's record (264) and a second call 0;
+   after the record of the packet that ended the stream (last != 0) the next call returns the finished header (1084), which the
+   caller writes over the placeholder at offset 0.  *buf points at memory of the context, valid until the next call on it.  The call
+   never touches the GPU.  (Requests 24 and 26, libtheora's numbers, keep answering TH_EIMPL: the records are not libtheora's.
+   0x721A is not used, like 0x7216 and 0x7217: it stays an unknown request, TH_EIMPL whatever the buffer.) */
+#define TH_ENCCTL_THIP_2PASS_OUT (0x721D)
+/* Extension: the second pass, with TH_ENCCTL_2PASS_IN's calling convention: buf = the pass file's bytes, buf_sz their count; returns
+   the number of bytes consumed (all of them, until every record the header counts is in: further bytes are not consumed).  The bytes may
+   come in any chunking and ahead of time.  buf == NULL: returns how many more bytes the encoder wants before it can take the next
+   frame (0: none).  The first call must come before the first frame and in bitrate mode, on a context not in pass 1, else TH_EINVAL;
+   set the other switches (inter frames among them) first.  TH_ENOTFORMAT for a bad magic or version, TH_EINVAL for a header whose
+   geometry, fps, key-frame shift or inter-frame switch is not the context's; either leaves the context as it was before the pass file's
+   first byte.  While frame n's record has not arrived, and for n >= frames + duplicates of the header, th_encode_ycbcr_in,
+   TH_ENCCTL_THIP_YCBCR_IN_DEVICE and TH_ENCCTL_THIP_RGB_IN return TH_EINVAL (before the device is touched).  Never touches the GPU. */
+#define TH_ENCCTL_THIP_2PASS_IN (0x721B)
+/* Extension: buf = thip_enc_2pass_stats, describing the last packet th_encode_packetout returned (all 0 but pass before the first). */
+#define TH_ENCCTL_THIP_GET_2PASS_STATS (0x721C)
+#define THIP_2PASS_HEADER_BYTES (1084)
+#define THIP_2PASS_RECORD_BYTES (264)
+typedef struct thip_enc_2pass_stats {
+  int32_t pass;            /* 0: neither; 1: TH_ENCCTL_THIP_2PASS_OUT; 2: TH_ENCCTL_THIP_2PASS_IN */
+  int32_t type;            /* pass 1: the record's type (0 key, 1 inter, 2 duplicate, 3 dropped); pass 2: the type of the record the
+                              frame followed (a duplicate packet: 2); pass 0: 0 */
+  int64_t frame;           /* the packet's index, counted from 0 with the duplicates */
+  int32_t qi;              /* the frame's qis[0] */
+  int32_t reserved;
+  int64_t recorded[64];    /* pass 1: E[q] as written to the record; pass 2: the record's E[q] */
+  int64_t fresh[64];       /* the probe of this pass (a duplicate: 0) */
+  int64_t budget_left;     /* pass 2: B - A after the packet */
+  int64_t recorded_left;   /* pass 2: the sum over the classes of Tot[qi] - Seen[qi] after the frame's record was added */
+  int64_t corr[4];         /* pass 2: c_key, c_inter after the packet, and Fresh[u][qi] / Seen[u][qi] in Q16 for u = 0, 1 as the
+                              choice saw them (65536 where Seen is 0) */
+  double wait_ms;          /* pass 1 in quality mode: the host's wait in th_encode_packetout for the probe's 512 bytes */
+  double probe_ms;         /* the probe's device time in this pass (HIP events, from its first launch to its 512 bytes on the host);
+                              in bitrate mode thip_enc_rate_stats.probe_ms */
+} thip_enc_2pass_stats;
 
 typedef struct th_enc_ctx th_enc_ctx;
 

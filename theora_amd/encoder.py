@@ -38,6 +38,10 @@ TH_ENCCTL_THIP_SET_MASKING = 0x7214
 TH_ENCCTL_THIP_GET_MASK_STATS = 0x7215
 TH_ENCCTL_THIP_SET_RD_MODES = 0x7218
 TH_ENCCTL_THIP_GET_RD_STATS = 0x7219
+TH_ENCCTL_THIP_2PASS_OUT = 0x721D   # (0x721A is not used)
+TH_ENCCTL_THIP_2PASS_IN = 0x721B
+TH_ENCCTL_THIP_GET_2PASS_STATS = 0x721C
+TWO_PASS_HEADER_BYTES, TWO_PASS_RECORD_BYTES = 1084, 264   # THIP_2PASS_HEADER_BYTES, THIP_2PASS_RECORD_BYTES
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
 TH_ENCCTL_SET_RATE_FLAGS = 20
@@ -110,6 +114,13 @@ class MaskStats(C.Structure):
 class RdStats(C.Structure):
     """thip_enc_rd_stats (include/theoraenc_hip.h)."""
     _fields_ = [("on", C.c_int32), ("measured", C.c_int32), ("huff", C.c_int32 * 4), ("lam", C.c_int64), ("rd_ms", C.c_double)]
+
+
+class TwoPassStats(C.Structure):
+    """thip_enc_2pass_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("pass_", C.c_int32), ("type", C.c_int32), ("frame", C.c_int64), ("qi", C.c_int32), ("reserved", C.c_int32),
+                ("recorded", C.c_int64 * 64), ("fresh", C.c_int64 * 64), ("budget_left", C.c_int64), ("recorded_left", C.c_int64),
+                ("corr", C.c_int64 * 4), ("wait_ms", C.c_double), ("probe_ms", C.c_double)]
 
 
 class RateStats(C.Structure):
@@ -468,6 +479,43 @@ class Encoder:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_RATE_STATS returned %d" % rc)
         d = {k: getattr(s, k) for k, _ in RateStats._fields_}
         d["probe"], d["corr"] = list(s.probe), list(s.corr)
+        return d
+
+    def two_pass_out(self):
+        """TH_ENCCTL_THIP_2PASS_OUT: the next bytes of the pass file (include/theoraenc_hip.h, "Two-pass").  The first call, before
+        the first frame, enters pass 1 and returns the header's placeholder; after each packetout() one call returns the packet's
+        record and a second b""; after the last packet's record the next call returns the finished header, to be written over the
+        placeholder at offset 0."""
+        p = C.POINTER(C.c_ubyte)()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_2PASS_OUT, C.byref(p), C.sizeof(p))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_2PASS_OUT returned %d" % rc)
+        return C.string_at(p, rc) if rc else b""
+
+    def two_pass_in(self, data):
+        """TH_ENCCTL_THIP_2PASS_IN: feeds bytes of the pass file, in any chunking and ahead of time; returns the bytes consumed.
+        data=None asks how many more bytes the encoder wants before it can take the next frame.  The first call, before the first
+        frame and in bitrate mode, enters pass 2."""
+        if data is None:
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_2PASS_IN, None, 0)
+        else:
+            data = bytes(data)
+            buf = (C.c_ubyte * max(len(data), 1)).from_buffer_copy(data or b"\0")
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_2PASS_IN, buf, len(data))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_2PASS_IN returned %d" % rc)
+        return rc
+
+    def two_pass_stats(self):
+        """TH_ENCCTL_THIP_GET_2PASS_STATS of the last packet, as a dict (the struct's `pass` under "pass"; corr: [c_key, c_inter,
+        and the fresh-to-recorded ratios of the two classes at the chosen qi, Q16])."""
+        s = TwoPassStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_2PASS_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_2PASS_STATS returned %d" % rc)
+        d = {k: getattr(s, k) for k, _ in TwoPassStats._fields_ if k not in ("pass_", "reserved")}
+        d["pass"] = s.pass_
+        d["recorded"], d["fresh"], d["corr"] = list(s.recorded), list(s.fresh), list(s.corr)
         return d
 
     def device(self):

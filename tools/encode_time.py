@@ -27,7 +27,13 @@ With --rd-modes (with --inter N --all-modes): the eight-mode cases run with the 
 (TH_ENCCTL_THIP_SET_RD_MODES); rd_ms is the device time of its two launches (TH_ENCCTL_THIP_GET_RD_STATS), which device_ms includes.
 Switch off and on are two runs of the tool.
 
-  python tools/encode_time.py [--frames 20] [--inter N [--all-modes [--rd-modes]]] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
+With --two-pass (with --bitrate B for the second pass's target, default 8 Mbit/s; --inter N as with --bitrate): per size and frame
+type, quality mode at 32 without and with TH_ENCCTL_THIP_2PASS_OUT -- in_ms is the time inside th_encode_ycbcr_in alone (it never
+waits in quality mode, first pass or not), call_ms the whole call with th_encode_packetout, p1_probe_ms the probe's device time and
+p1_wait_ms the host's wait in th_encode_packetout for its 512 bytes (TH_ENCCTL_THIP_GET_2PASS_STATS) -- and then the second pass over
+that pass file (p2_*; its probe is waited for, as in bitrate mode).
+
+  python tools/encode_time.py [--two-pass] [--frames 20] [--inter N [--all-modes [--rd-modes]]] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
                               [--auto-keyframes [T]] [--json out.json]
 """
 import argparse
@@ -77,8 +83,11 @@ def main():
     ap.add_argument("--device-pack", action="store_true", help="each case with the device packetiser off, then on")
     ap.add_argument("--auto-keyframes", type=int, nargs="?", const=230, default=0, metavar="T",
                     help="with --inter or --bitrate: each case with automatic key frames off, then on at ratio T (default 230)")
+    ap.add_argument("--two-pass", action="store_true", help="quality mode without and with the first pass, then the second pass")
     ap.add_argument("--json")
     args = ap.parse_args()
+    if args.two_pass:
+        return main_two_pass(args)
     if args.bitrate:
         return main_bitrate(args)
     if args.inter:
@@ -226,6 +235,59 @@ def main_bitrate(args):
                      device_ms=med([x[1] for x in rr]), q_call_ms=med([x[0] for x in qq]), q_device_ms=med([x[1] for x in qq]))
             if args.auto_keyframes:
                 r.update(auto_keyframes=ak, measure_ms=med([x[3] for x in rr]), q_measure_ms=med([x[3] for x in qq]))
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if args.json:
+        json.dump(rows, open(args.json, "w"), indent=1)
+
+
+def main_two_pass(args):
+    from tests import enc_inter_ref, enc_ref
+    from theora_amd.encoder import Encoder
+    rows = []
+    n = args.frames + 3
+    kf = args.inter or 12
+    bitrate = args.bitrate or 8000000
+    med = lambda xs: round(float(np.median(xs)), 4)
+    for name, (w, h, pic) in SIZES.items():
+        p = pic or (0, 0, w, h)
+        frames = [[a[:enc_ref.chroma_region(p, 0, k)[3], :enc_ref.chroma_region(p, 0, k)[2]] for k, a in enumerate(fr)]
+                  for fr in enc_inter_ref.sequence("pan", w, h, 0, n, seed=5)]
+        for kind in ("key", "inter"):
+            inter = kind == "inter"
+            kw = dict(pic=pic, inter=inter, keyframe_interval=kf if inter else None)
+
+            def run(e, record, feed=None):
+                """Per kept frame (in ms, call ms, device ms, two-pass stats); the pass file when recording."""
+                e.header_packets()
+                data = [e.two_pass_out()] if record else []
+                if feed is not None:
+                    assert e.two_pass_in(feed) == len(feed)
+                out = []
+                for f, fr in enumerate(frames):
+                    t0 = time.perf_counter()
+                    e.encode(fr)
+                    t1 = time.perf_counter()
+                    e.packetout(f == n - 1)
+                    t2 = time.perf_counter()
+                    tp = e.two_pass_stats()
+                    if record:
+                        data.append(e.two_pass_out())
+                    if f >= 3 and bool(e.inter_stats()["key"]) == (not inter):
+                        out.append(((t1 - t0) * 1e3, (t2 - t0) * 1e3, e.times()[0], tp))
+                if record:
+                    data[0] = e.two_pass_out()   # the finished header over the placeholder
+                e.close()
+                return out, b"".join(data)
+            q0, _ = run(Encoder(w, h, 0, 32, **kw), False)
+            q1, data = run(Encoder(w, h, 0, 32, **kw), True)
+            p2, _ = run(Encoder(w, h, 0, 32, bitrate=bitrate, **kw), False, feed=data)
+            r = dict(size=name, frames=kind, n=len(q1), q_in_ms=med([x[0] for x in q0]), q_call_ms=med([x[1] for x in q0]),
+                     q_device_ms=med([x[2] for x in q0]), p1_in_ms=med([x[0] for x in q1]), p1_call_ms=med([x[1] for x in q1]),
+                     p1_device_ms=med([x[2] for x in q1]), p1_probe_ms=med([x[3]["probe_ms"] for x in q1]),
+                     p1_wait_ms=med([x[3]["wait_ms"] for x in q1]), p1_wait_max_ms=round(max(x[3]["wait_ms"] for x in q1), 4),
+                     bitrate=bitrate, p2_qi=int(np.median([x[3]["qi"] for x in p2])), p2_in_ms=med([x[0] for x in p2]),
+                     p2_call_ms=med([x[1] for x in p2]), p2_probe_ms=med([x[3]["probe_ms"] for x in p2]))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
