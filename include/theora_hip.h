@@ -1002,6 +1002,46 @@ typedef struct thip_enc_rd_req {   /* 200 bytes */
 int thip_enc_rd_stage(const thip_enc_rd_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the skip decision of th_encode_*'s inter frames (theoraenc_hip.h, "Skip decision") on the caller's
+ * planes, words and tables: the same launch function th_encode_* calls in place of its quantising kernel (two launches: the luma
+ * blocks, then the chroma blocks).  dequant and bits are HOST memory, every other pointer is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*, src, src_pitch, prev, gold, ref_pitch, classes   as thip_enc_inter_stage takes them
+ *   words     the macro-block words: [nmbs] uint32 with classes 2, [nmbs] 16-byte words with classes 3 (thip_enc_inter_stage's)
+ *   nqis      1..3: the length of the frame's qi list
+ *   dequant   HOST, [nqis][2][3][64]: at each qi of the list the intra then the inter table of each plane, zig-zag order, 1..32767
+ *   bits      HOST, uint8 [2][4][32]: luma then chroma, code length + extra bits of each token in the AC Huffman groups 1..4
+ *   lambda    the unscaled lambda of every block, 0..2^40; -1: each block's own, (s1 * s1 * 40) >> 7 from its table at qis[0], as
+ *             th_encode_* runs it
+ *   iscale    masking's scales, [nfrags] uint16 in fragment raster order (thip_enc_mask_stage's), or NULL: no masking
+ * Out, all required: levels [nfrags][64] (coded order, zig-zag), dcq [nfrags] (raster), qii [nfrags] (coded order), cmap [nfrags]
+ * (raster: 0 uncoded, else the block's class 1 intra, 2 PREV, 3 GOLD), skf [nfrags] (raster: 1 where the test left the block uncoded),
+ * and in coded order for every block, coded or not, dcode, rate, dskip [nfrags] int64: D_code, R and D_skip.
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req, a plane, words, a table or an output NULL, or a HIP call failed.  THIP_EINVAL: the frame size, fragment count, pixel
+ * format, picture region, pitches, classes and gold as thip_enc_inter_stage refuses them; nqis outside 1..3; lambda outside
+ * -1..2^40; a table entry outside 1..32767; a bits entry above 64; words or levels not 16-byte aligned (words 4-byte with classes 2),
+ * dcq or iscale not 2-byte, dcode, rate or dskip not 8-byte -- all found before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+typedef struct thip_enc_skip_req {   /* 264 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t classes, nqis, reserved;
+  int64_t lambda;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  const uint8_t *prev[3], *gold[3];
+  int64_t ref_pitch[3];
+  const void *words;
+  const uint16_t *dequant;
+  const uint8_t *bits;
+  const uint16_t *iscale;
+  int16_t *levels, *dcq;
+  uint8_t *qii, *cmap, *skf;
+  int64_t *dcode, *rate, *dskip;
+} thip_enc_skip_req;
+int thip_enc_skip_stage(const thip_enc_skip_req *req);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

@@ -169,6 +169,36 @@
  *     tie the lower index, so while GOLD is PREV candidate 3 never wins.  The word written is k_enc_me_all's, field for field.
  *   - No wait: two launches (the candidates, then the choice) stand in for the search's one (thip_enc_rd_stats).
  *
+ * Skip decision (TH_ENCCTL_THIP_SET_RD_SKIP), stated likewise (tests/enc_skip_ref.py restates it).  After a block has been coded it
+ * asks whether leaving it uncoded -- the decoder then keeps PREV's pixels there -- would have cost less (libtheora's oc_skip_cost,
+ * analyze.c:829-867).  Off (the default) every packet is as without the call.  Integer arithmetic throughout, all of it 64-bit.
+ *   - Where it acts: on inter frames, with five or eight modes, with or without block qi, masking, the rate-distortion mode decision,
+ *     bitrate mode, two-pass, automatic key frames, the device packetiser and the quality statistics.  It does not touch key frames,
+ *     the search, the mode decision (the SAD cascade or the rate-distortion one), the rate probe, the controllers (c_inter absorbs
+ *     it) or the automatic-key-frame measurement.  With inter frames off the request is accepted and does nothing.
+ *   - Which blocks: every block the rules above would code (any block of an INTRA, MV, MV_FOUR or golden macro block; a block of an
+ *     INTER_NOMV macro block with a level that is not zero), except the luma blocks of an INTER_MV_FOUR macro block: an uncoded luma
+ *     block there changes the vectors the decoder derives (spec 7.5.2).
+ *   - Per block, after the block-qi choice k (k = 0 with block qi off), with c the fDCT of the block's residual, l its levels and s
+ *     the steps of its table -- the DC (z = 0) at qis[0], the AC at qis[k]:
+ *       D_code = sum over all 64 z of (c_z - l_z s_z)^2;
+ *       R      = block qi's R_k: the AC tokens from index 1 with the block's own EOB, counted with the AC tables the previous inter
+ *                packet chose (5 before there is one);
+ *       lambda_b = block qi's lambda, (s1 * s1 * 40) >> 7 with s1 the step at zig-zag index 1 of the block's table at qis[0], and
+ *                where masking acts (block qi and masking on) (lambda i_b + 1024) >> 11;
+ *       SSD    = sum over the block's 64 pixels of (source - PREV at the same position)^2, the source clamped outward exactly as the
+ *                block kernels read it;
+ *       D_skip = 16 SSD, doubled when the vector the block is predicted through -- the vector of its plane that follows from the
+ *                macro block's word, for an MV_FOUR chroma block the one the decoder derives -- is not (0, 0) (the reference's
+ *                coded_ssd <<= 4 and its doubling, analyze.c:2008-2012).
+ *     The block is left uncoded when D_skip <= D_code + lambda_b R.
+ *   - Luma is decided first.  A macro block whose four luma blocks all end uncoded writes no mode and is INTER_NOMV to the decoder.
+ *     Its chroma blocks are then coded as INTER_NOMV blocks whatever the macro block's word says: the residual against PREV at
+ *     vector 0 through the inter tables, class PREV, coded when a level is not zero and the test (not doubled) does not leave the
+ *     block out.  The chroma blocks of every other macro block follow the word as ever, then the test.
+ *   - A frame with no coded block is the zero-byte packet, as ever.
+ *   - No wait: two launches (the luma blocks, then the chroma blocks) stand in for the quantising kernel's one (thip_enc_skip_stats).
+ *
  * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
  * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
  *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
@@ -530,6 +560,23 @@ typedef struct thip_enc_rd_stats {
   int64_t lambda;         /* the rule's lambda */
   double rd_ms;           /* HIP events around the two launches */
 } thip_enc_rd_stats;
+
+/* Extension: buf = int 0 / 1: coded blocks of inter frames are left uncoded where that costs less ("Skip decision" above); any other
+   value TH_EINVAL.  Off by default: every packet as without the call.  Before the first frame only (else TH_EINVAL); the call never
+   touches the GPU.  Accepted with inter frames off, where it has no effect. */
+#define TH_ENCCTL_THIP_SET_RD_SKIP (0x721E)
+/* Extension: buf = thip_enc_skip_stats, describing the last packet th_encode_packetout returned (with the switch off too).  For a
+   frame not decided this way -- a key frame, a duplicate, a dropped frame, a zero-byte packet, any frame with the switch off -- every
+   field is 0 except on. */
+#define TH_ENCCTL_THIP_GET_SKIP_STATS (0x721F)
+typedef struct thip_enc_skip_stats {   /* 40 bytes */
+  int32_t on;             /* the switch */
+  int32_t measured;       /* 1: the frame's coded blocks went through the test */
+  int32_t skipped[3];     /* per plane: the blocks the test left uncoded (blocks uncoded by the rules before it are not counted) */
+  int32_t demoted;        /* macro blocks that lost their mode: no luma block coded, and the test left at least one of the four out */
+  int64_t lambda;         /* the frame's unscaled lambda: (s1 * s1 * 40) >> 7, s1 the inter luma step at zig-zag index 1 of qis[0] */
+  double skip_ms;         /* HIP events around the two launches */
+} thip_enc_skip_stats;
 
 /* Extension: the first pass of "Two-pass" above, with TH_ENCCTL_2PASS_OUT's calling convention: buf = unsigned char **, buf_sz ==
    sizeof(unsigned char *) (else TH_EINVAL).  The first call must come before the first frame (else TH_EINVAL; TH_EINVAL too on a

@@ -32,6 +32,7 @@
 #include "thip_encode_bqi.h"
 #include "thip_encode_mask.h"
 #include "thip_encode_rd.h"
+#include "thip_encode_skip.h"
 #include "thip_encode_pack.h"
 #include "thip_encode_cut.h"
 #include "thip_bitstream.h"
@@ -288,6 +289,13 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint8_t *d_rdbits = nullptr;   // [16 tables][5 Huffman groups][32 tokens]: code length + extra bits
   hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
   thip_enc_rd_stats dstats;
+  // the skip decision (TH_ENCCTL_THIP_SET_RD_SKIP; thip_encode_skip.h): the frame queued was decided by it (skip_queued) with the
+  // unscaled lambda skip_lam; one flag a fragment (raster) where the test left a block uncoded
+  bool skip = false, skip_queued = false;
+  int64_t skip_lam = 0;
+  uint8_t *d_skf = nullptr, *h_skf = nullptr;
+  hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;
+  thip_enc_skip_stats sstats;
   // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
   bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
   int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
@@ -396,6 +404,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->bstats, 0, sizeof(e->bstats));
   memset(&e->kstats, 0, sizeof(e->kstats));
   memset(&e->dstats, 0, sizeof(e->dstats));
+  memset(&e->sstats, 0, sizeof(e->sstats));
   memset(&e->rstats, 0, sizeof(e->rstats));
   memset(&e->pstats, 0, sizeof(e->pstats));
   memset(&e->cnext, 0, sizeof(e->cnext));
@@ -430,6 +439,7 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_qii, (void **)&e->d_bqbits,                                                                     // enc_bqi_prepare
       (void **)&e->d_act, (void **)&e->d_mpart, (void **)&e->d_iscale,                                               // enc_mask_queue
       (void **)&e->d_cand, (void **)&e->d_rdbits,                                                                    // enc_rd_queue
+      (void **)&e->d_skf,                                                                                            // enc_skip_queue
       (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
@@ -445,6 +455,7 @@ static void enc_free_device(th_enc_ctx *e) {
                    (void **)&e->h_mb, (void **)&e->h_cmap,                        // ... inter frames
                    (void **)&e->h_mb4,                                            // enc_modes_alloc
                    (void **)&e->h_qii,                                            // enc_bqi_prepare
+                   (void **)&e->h_skf,                                            // enc_skip_queue
                    (void **)&e->h_rest,                                           // enc_rate_alloc
                    (void **)&e->h_pk, (void **)&e->h_prec,                        // enc_pack_alloc
                    (void **)&e->h_cut,                                            // enc_cut_alloc
@@ -461,9 +472,10 @@ static void enc_free_device(th_enc_ctx *e) {
   e->q_queued = false;
   e->mask_queued = false;
   e->rd_queued = false;
+  e->skip_queued = false;
   e->tp_probe_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
-                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1}) {
+                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1, &e->ev_s0, &e->ev_s1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -587,15 +599,16 @@ static int enc_ref_frame(th_enc_ctx *e, EncRef &R, int which = THIP_FRAME_PREV) 
 }
 
 // the frame's qi list (theoraenc_hip.h, "Block-level qi"; one qi with block qi off) and, with block qi on, the selection of the
-// block-qi kernels (thip_encode_bqi.h); their buffers at the first such frame (TH_ENCCTL_THIP_SET_BLOCK_QI never touches the GPU)
+// block-qi kernels (thip_encode_bqi.h); their buffers at the first such frame (TH_ENCCTL_THIP_SET_BLOCK_QI never touches the GPU).
+// An inter frame with the skip decision on runs the same selection, with a one-entry list where block qi is off
 static int enc_bqi_prepare(th_enc_ctx *e, BqiSel &sel) {
   const int q0 = e->frame_qi;
   e->fnqis = 1;
   e->fqis[0] = q0;
   e->fqis[1] = e->fqis[2] = 0;
-  if (!e->bqi) return 0;
+  if (!e->bqi && !(e->skip && !e->frame_key)) return 0;
   const int coarse = std::max(q0 - e->bqi, 0), fine = std::min(q0 + e->bqi, 63);
-  if (coarse != q0) e->fqis[e->fnqis++] = coarse;
+  if (coarse != q0) e->fqis[e->fnqis++] = coarse;   // (block qi off: q0 alone)
   if (fine != q0 && fine != coarse) e->fqis[e->fnqis++] = fine;
   if (!e->d_qii) {
     ENC_TRY(hipMalloc((void **)&e->d_qii, (size_t)e->nfrags));
@@ -684,6 +697,48 @@ static void enc_rd_stats(th_enc_ctx *e, bool queued) {
   e->dstats.rd_ms = hipEventElapsedTime(&ms, e->ev_r0, e->ev_r1) == hipSuccess ? ms : 0.0;
 }
 
+// the skip decision (thip_encode_skip.h): its two launches in place of the frame's quantising kernel, between HIP events.  The flags
+// and the events at the first such frame (TH_ENCCTL_THIP_SET_RD_SKIP never touches the GPU); no host wait
+extern "C++" template <class Word>
+static int enc_skip_queue(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, const Word *d_mb, const EncRef &R, const EncRef &G) {
+  if (!e->d_skf) {
+    for (hipEvent_t *ev : {&e->ev_s0, &e->ev_s1})
+      if (!*ev) ENC_TRY(hipEventCreate(ev));
+    ENC_TRY(hipMalloc((void **)&e->d_skf, (size_t)e->nfrags));
+    ENC_TRY(hipHostMalloc((void **)&e->h_skf, (size_t)e->nfrags, hipHostMallocDefault));
+  }
+  e->skip_lam = rd_lambda(e->lambda[e->frame_qi]);
+  ENC_TRY(hipEventRecord(e->ev_s0, e->stream));
+  ENC_TRY(skip_launch(InterBufs{e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192}, e->d_qii,
+                      SkipOut{e->d_skf, nullptr, nullptr, nullptr}, e->d_order, g, R, G, d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel,
+                      e->mask_queued ? (const uint16_t *)e->d_iscale : nullptr, -1, e->nfrags, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_s1, e->stream));
+  e->skip_queued = true;
+  return 0;
+}
+
+// the last packet's thip_enc_skip_stats: those of a frame not decided this way, or (queued: after the frame's wait) the frame's own
+// from the flags and the coded map
+static void enc_skip_stats(th_enc_ctx *e, bool queued) {
+  memset(&e->sstats, 0, sizeof(e->sstats));
+  e->sstats.on = e->skip ? 1 : 0;
+  if (!queued) return;
+  float ms = 0;
+  e->sstats.measured = 1;
+  for (int p = 0; p < 3; p++)
+    for (int f = e->fro[p]; f < e->fro[p] + e->nh[p] * e->nv[p]; f++) e->sstats.skipped[p] += e->h_skf[f] != 0;
+  for (const MacroBlock &m : e->mbs) {
+    bool coded = false, flagged = false;
+    for (int k = 0; k < 4; k++) {
+      coded |= e->h_cmap[m.luma[k]] != 0;
+      flagged |= e->h_skf[m.luma[k]] != 0;
+    }
+    e->sstats.demoted += !coded && flagged;
+  }
+  e->sstats.lambda = e->skip_lam;
+  e->sstats.skip_ms = hipEventElapsedTime(&ms, e->ev_s0, e->ev_s1) == hipSuccess ? ms : 0.0;
+}
+
 // ---- the device packetiser (thip_encode_pack.h) ----------------------------------------------------------------------------------
 // its buffers and tables, at the first frame that needs them.  The packet buffer holds 128 bytes a block -- 16 bits a coefficient,
 // twice the raw picture; the natural image of tools/encode_time.py takes 9.5 bytes a block at quality 48 -- where the worst case, 65
@@ -755,6 +810,7 @@ static int enc_queue_tail(th_enc_ctx *e) {
     ENC_TRY(hipMemcpyAsync(e->h_cmap, e->d_cmap, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   }
   if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (e->skip_queued) ENC_TRY(hipMemcpyAsync(e->h_skf, e->d_skf, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
   if (enc_pack_queue(e)) return TH_EFAULT;
   enc_frame_queued(e);
@@ -794,7 +850,10 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   } else {
     ENC_TRY(inter_launch_search(d_mb, g, R, gold..., e->nmbx, e->nmbs, lambda, e->stream));
   }
-  if (e->mask_queued) {
+  if (e->skip) {
+    const EncRef *G[] = {&R, &gold...};   // (GOLD where the word has it, else PREV, which is not read)
+    if (enc_skip_queue(e, g, sel, (const Word *)d_mb, R, *G[sizeof...(Gold)])) return TH_EFAULT;
+  } else if (e->mask_queued) {
     hipLaunchKernelGGL(k_fq_mask, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
                        e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
     ENC_TRY(hipGetLastError());
@@ -1279,6 +1338,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   const int64_t n = e->nfrags;
   e->mask_queued = false;   // (enc_mask_queue says otherwise; a dropped frame never gets there)
   e->rd_queued = false;     // (enc_rd_queue likewise)
+  e->skip_queued = false;   // (enc_skip_queue likewise)
   if (!e->rate) e->frame_qi = e->qi;   // (bitrate mode: the controller's choice, below)
   // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
   const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
@@ -1653,6 +1713,7 @@ static void enc_empty_packet(th_enc_ctx *e) {
   memset(&e->bstats, 0, sizeof(e->bstats));
   enc_mask_stats(e, false);
   enc_rd_stats(e, false);
+  enc_skip_stats(e, false);
 }
 
 // what both packers leave behind: the frame's statistics, the AC tables the next block-qi choice of this frame type counts with, and
@@ -1855,6 +1916,7 @@ static int enc_finish_frame(th_enc_ctx *e) {
   memset(&e->pstats, 0, sizeof(e->pstats));
   enc_mask_stats(e, e->mask_queued);   // (an empty packet takes them back)
   enc_rd_stats(e, e->rd_queued);
+  enc_skip_stats(e, e->skip_queued);
   const int rc = e->frame_dpack ? enc_pack_device(e, total, overflow) : enc_pack_host(e, total, overflow);
   e->pstats.fallbacks = e->pack_fallbacks;
   return rc;
@@ -2004,6 +2066,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->bstats, 0, sizeof(e->bstats));
     enc_mask_stats(e, false);
     enc_rd_stats(e, false);
+    enc_skip_stats(e, false);
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
     const int qrc = enc_quality_queue(e, true);   // (against the picture the decoder goes on showing)
     if (qrc) return qrc;
@@ -2047,6 +2110,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     memset(&e->bstats, 0, sizeof(e->bstats));
     enc_mask_stats(e, false);
     enc_rd_stats(e, false);
+    enc_skip_stats(e, false);
     e->istats.mode_scheme = e->istats.mv_scheme = -1;
     (void)enc_quality_queue(e, false);
   } else {
@@ -2196,6 +2260,15 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->dstats.on = v;
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_RD_SKIP: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int v = *(const int *)buf;
+      if (v != 0 && v != 1) return TH_EINVAL;
+      e->skip = v != 0;   // (its buffers are made at the first frame that uses it)
+      e->sstats.on = v;
+      return 0;
+    }
     case TH_ENCCTL_THIP_SET_DEVICE_PACK: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       const int v = *(const int *)buf;
@@ -2242,6 +2315,10 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     case TH_ENCCTL_THIP_GET_RD_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_rd_stats)) return TH_EINVAL;
       *(thip_enc_rd_stats *)buf = e->dstats;
+      return 0;
+    case TH_ENCCTL_THIP_GET_SKIP_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_skip_stats)) return TH_EINVAL;
+      *(thip_enc_skip_stats *)buf = e->sstats;
       return 0;
     case TH_ENCCTL_THIP_2PASS_OUT: {
       if (buf_sz != sizeof(unsigned char *)) return TH_EINVAL;
@@ -2615,6 +2692,94 @@ int thip_enc_rd_stage(const thip_enc_rd_req *q) {
   // (the caller's two tables are tables 0 and 1 of the kernel's list: luma, chroma for the DC and the AC groups alike)
   ENC_TRY(rd_launch(RdBufs{(uint4 *)q->cand, (uint4 *)q->words, q->costs}, cand, decide, g, R, G, nmbx, nmbs, q->lambda_search,
                     (int64_t)q->lambda_rd, (const uint16_t *)d, d + 768, make_int4(0, 1, 0, 1), stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the skip decision on the caller's planes, words and tables (theora_hip.h): thip_encode_skip.h's launch function, as enc_skip_queue
+// makes it, on the current device's null stream
+int thip_enc_skip_stage(const thip_enc_skip_req *q) {
+  if (!q) return THIP_EFAULT;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  if (q->classes != 2 && q->classes != 3) return THIP_EINVAL;
+  const bool all = q->classes == 3;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
+  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+    return THIP_EINVAL;
+  int ngold = 0;
+  for (int p = 0; p < 3; p++) {
+    if (!q->src[p] || !q->prev[p]) return THIP_EFAULT;
+    ngold += q->gold[p] != nullptr;
+  }
+  if (ngold != (all ? 3 : 0)) return all && ngold < 3 ? THIP_EFAULT : THIP_EINVAL;
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
+    if (q->src_pitch[p] < pw || q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF) return THIP_EINVAL;
+  }
+  if (q->nqis < 1 || q->nqis > 3 || q->lambda < -1 || q->lambda > ((int64_t)1 << 40)) return THIP_EINVAL;
+  if (!q->words || !q->dequant || !q->bits) return THIP_EFAULT;
+  if (!q->levels || !q->dcq || !q->qii || !q->cmap || !q->skf || !q->dcode || !q->rate || !q->dskip) return THIP_EFAULT;
+  for (int k = 0; k < q->nqis * 384; k++)
+    if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
+  for (int k = 0; k < 256; k++)
+    if (q->bits[k] > 64) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (misaligned(q->words, all ? 16 : 4) || misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->iscale, 2) ||
+      misaligned(q->dcode, 8) || misaligned(q->rate, 8) || misaligned(q->dskip, 8))
+    return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int64_t n = geo.nfrags;
+  const int classes = q->classes, nmbx = geo.nh[0] >> 1;
+  const size_t nchunks = (size_t)((n + kEncChunk - 1) / kEncChunk);
+  EncPlanes g = {};
+  EncRef R = {}, G = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.src[p] = q->src[p];
+    g.stride[p] = q->src_pitch[p];
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+    R.plane[p] = q->prev[p];
+    G.plane[p] = all ? q->gold[p] : q->prev[p];
+    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
+    R.w[p] = G.w[p] = geo.nh[p] * 8;
+    R.h[p] = G.h[p] = geo.nv[p] * 8;
+  }
+  R.hdec = G.hdec = hdec;
+  R.vdec = G.vdec = vdec;
+  // one allocation: dclast [chunks][classes] | overflow | order [n] | dequant [nqis][384] | bits [256]
+  const size_t o_ovf = nchunks * classes * 4, o_order = o_ovf + 16, o_dq = o_order + (size_t)n * 4, o_bits = o_dq + (size_t)q->nqis * 768;
+  uint8_t *d = nullptr;
+  ENC_TRY(hipMalloc((void **)&d, o_bits + 256));
+  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  hipStream_t stream = nullptr;
+  ENC_TRY(hipMemcpy(d + o_order, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(d + o_dq, q->dequant, (size_t)q->nqis * 768, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(d + o_bits, q->bits, 256, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemsetAsync(d, 0, o_ovf, stream));
+  // (the caller's tables are qi 0, 1, 2 of the kernel's table set and AC tables 0, 1 of its bits)
+  const InterBufs o{q->levels, q->dcq, q->cmap, (uint32_t *)d, (uint32_t *)(d + o_ovf)};
+  const SkipOut so{q->skf, q->dcode, q->rate, q->dskip};
+  const BqiSel sel{q->nqis, 0, 1, 2, 0, 1};
+  if (all)
+    ENC_TRY(skip_launch(o, q->qii, so, (const int32_t *)(d + o_order), g, R, G, (const uint4 *)q->words, nmbx, (const uint16_t *)(d + o_dq),
+                        d + o_bits, sel, q->iscale, q->lambda, n, stream));
+  else
+    ENC_TRY(skip_launch(o, q->qii, so, (const int32_t *)(d + o_order), g, R, G, (const uint32_t *)q->words, nmbx,
+                        (const uint16_t *)(d + o_dq), d + o_bits, sel, q->iscale, q->lambda, n, stream));
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

@@ -57,6 +57,19 @@ __device__ __forceinline__ int64_t bqi_sum4(int64_t v) {   // over the four lane
   return v;
 }
 
+// The choice among the nqis candidates of a block (theoraenc_hip.h, "Block-level qi"): the least D_k + lam R_k, plus lam for k != 0;
+// on a tie the lower k.  enc_fq_bqi and enc_fq_skip (thip_encode_skip.h) both choose with it
+__device__ __forceinline__ int bqi_choose(int nqis, int64_t lam, int64_t d0, int64_t d1, int64_t d2, int r0, int r1, int r2) {
+  int64_t best = d0 + lam * r0;
+  int kb = 0;
+  if (nqis > 1 && d1 + lam * (r1 + 1) < best) {
+    best = d1 + lam * (r1 + 1);
+    kb = 1;
+  }
+  if (nqis > 2 && d2 + lam * (r2 + 1) < best) kb = 2;
+  return kb;
+}
+
 // The body of the three kernels.  kClasses: the reference classes of enc_fq_tail -- 0 a key frame (no prediction, mbw not read), 2
 // with k_enc_me's words, 3 with k_enc_me_all's.  levels [n][64], dcq [nfrags], qii [n] (coded order); inter: cmap, dclast as the
 // plain kernels.  dequant: [64 qi][kTabs][64] zig-zag (key: the three intra tables; inter: intra then inter).  bqbits
@@ -120,13 +133,7 @@ __device__ __forceinline__ void enc_fq_bqi(int16_t *levels, int16_t *dcq, uint8_
   const int64_t s1 = (int64_t)(s_t[tab * 64 + 1].x & 0xFFFFu);   // qis[0]'s step at zig-zag index 1 (natural position 1)
   int64_t lam = (s1 * s1 * 40) >> 7;
   if constexpr (kMask) lam = (lam * (int64_t)iscale[fi] + 1024) >> 11;
-  int64_t best = d0 + lam * r0;
-  int kb = 0;
-  if (sel.nqis > 1 && d1 + lam * (r1 + 1) < best) {
-    best = d1 + lam * (r1 + 1);
-    kb = 1;
-  }
-  if (sel.nqis > 2 && d2 + lam * (r2 + 1) < best) kb = 2;
+  const int kb = bqi_choose(sel.nqis, lam, d0, d1, d2, r0, r1, r2);
   int4 *chosen = lds + kb * kLv;
   // the DC stays at qis[0]
   if (kb && j == 0) reinterpret_cast<int16_t *>(chosen)[lds_block_at(b, 0)] = reinterpret_cast<const int16_t *>(lds)[lds_block_at(b, 0)];

@@ -41,6 +41,8 @@ TH_ENCCTL_THIP_GET_RD_STATS = 0x7219
 TH_ENCCTL_THIP_2PASS_OUT = 0x721D   # (0x721A is not used)
 TH_ENCCTL_THIP_2PASS_IN = 0x721B
 TH_ENCCTL_THIP_GET_2PASS_STATS = 0x721C
+TH_ENCCTL_THIP_SET_RD_SKIP = 0x721E
+TH_ENCCTL_THIP_GET_SKIP_STATS = 0x721F
 TWO_PASS_HEADER_BYTES, TWO_PASS_RECORD_BYTES = 1084, 264   # THIP_2PASS_HEADER_BYTES, THIP_2PASS_RECORD_BYTES
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
@@ -116,6 +118,12 @@ class RdStats(C.Structure):
     _fields_ = [("on", C.c_int32), ("measured", C.c_int32), ("huff", C.c_int32 * 4), ("lam", C.c_int64), ("rd_ms", C.c_double)]
 
 
+class SkipStats(C.Structure):
+    """thip_enc_skip_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("on", C.c_int32), ("measured", C.c_int32), ("skipped", C.c_int32 * 3), ("demoted", C.c_int32), ("lam", C.c_int64),
+                ("skip_ms", C.c_double)]
+
+
 class TwoPassStats(C.Structure):
     """thip_enc_2pass_stats (include/theoraenc_hip.h)."""
     _fields_ = [("pass_", C.c_int32), ("type", C.c_int32), ("frame", C.c_int64), ("qi", C.c_int32), ("reserved", C.c_int32),
@@ -155,7 +163,7 @@ class Encoder:
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
-                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False):
+                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False, rd_skip=False):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -168,7 +176,8 @@ class Encoder:
         (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES): True for the recommended ratio AUTO_KEYFRAMES_DEFAULT, or the ratio t itself, 1..4096;
         None, False or 0 leave it off.  No effect without inter=True.  masking: activity masking with that ratio, 2..16
         (TH_ENCCTL_THIP_SET_MASKING; 0 off; recommended 4).  No effect without block_qi.  rd_modes: the macro-block modes of
-        eight-mode inter frames by the least D + lambda R (TH_ENCCTL_THIP_SET_RD_MODES).  No effect without all_modes."""
+        eight-mode inter frames by the least D + lambda R (TH_ENCCTL_THIP_SET_RD_MODES).  No effect without all_modes.  rd_skip: coded
+        blocks of inter frames are left uncoded where that costs less (TH_ENCCTL_THIP_SET_RD_SKIP).  No effect without inter."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -207,6 +216,9 @@ class Encoder:
         self.rd_modes = False
         if rd_modes:
             self.set_rd_modes(rd_modes)
+        self.rd_skip = False
+        if rd_skip:
+            self.set_rd_skip(rd_skip)
         if device_pack is not None:
             self.set_device_pack(device_pack)
         self.auto_keyframes = AUTO_KEYFRAMES_DEFAULT if auto_keyframes is True else int(auto_keyframes or 0)
@@ -257,6 +269,23 @@ class Encoder:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_RD_STATS returned %d" % rc)
         d = {k: getattr(s, k) for k, _ in RdStats._fields_}
         d["huff"] = list(s.huff)
+        return d
+
+    def set_rd_skip(self, on):
+        """TH_ENCCTL_THIP_SET_RD_SKIP, before the first frame: the skip decision on (True) or off."""
+        rc, _ = self.ctl(TH_ENCCTL_THIP_SET_RD_SKIP, int(bool(on)))
+        if rc < 0:
+            raise ValueError("rd_skip is set before the first frame (TH_ENCCTL_THIP_SET_RD_SKIP returned %d)" % rc)
+        self.rd_skip = bool(on)
+
+    def skip_stats(self):
+        """TH_ENCCTL_THIP_GET_SKIP_STATS of the last packet, as a dict (lam: the struct's lambda)."""
+        s = SkipStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_SKIP_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_SKIP_STATS returned %d" % rc)
+        d = {k: getattr(s, k) for k, _ in SkipStats._fields_}
+        d["skipped"] = list(s.skipped)
         return d
 
     def set_device_pack(self, on):
@@ -657,6 +686,39 @@ def rd_stage(frame, pixel_fmt, stages, pic=None, lambda_search=0, lambda_rd=0, s
             setattr(q, name, a.ctypes.data)
     q.cand, q.costs, q.words = cand, costs, words
     return L.thip_enc_rd_stage(C.byref(q))
+
+
+def skip_stage(frame, pixel_fmt, classes, nqis, pic=None, lam=-1, src=None, src_pitch=None, prev=None, gold=None, ref_pitch=None,
+               words=None, dequant=None, bits=None, iscale=None, levels=None, dcq=None, qii=None, cmap=None, skf=None, dcode=None,
+               rate=None, dskip=None):
+    """thip_enc_skip_stage (include/theora_hip.h): the skip decision on the caller's planes, words and tables, a test and diagnostic
+    entry.  frame: (width, height); pic: (x, y, width, height), the whole frame when None; classes: 2 (32-bit words) or 3 (16-byte
+    words, gold given); lam: the unscaled lambda of every block, -1 for each block's own; src, prev, gold: three device addresses each
+    (None where there is none) with their pitches; dequant [nqis][2][3][64] and bits [2][4][32]: anything numpy converts (None is
+    NULL); the rest: device addresses, None is NULL.  Returns the entry's return code; nothing is raised, the refusals are the
+    caller's to look at."""
+    L = _lib.load()
+    q = _lib.EncSkipReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.classes, q.nqis, q.lam = int(classes), int(nqis), int(lam)
+    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
+        for p in range(3):
+            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
+    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
+        for p in range(3):
+            getattr(q, name)[p] = 0 if v is None else int(v[p])
+    keep = []
+    for name, v, t, size in (("dequant", dequant, np.uint16, 384 * int(nqis)), ("bits", bits, np.uint8, 256)):
+        if v is not None:
+            a = np.ascontiguousarray(v, t).reshape(-1)
+            if a.size != size and not (name == "dequant" and not 1 <= int(nqis) <= 3):   # (an nqis the entry refuses: its refusal)
+                raise ValueError("skip_stage: %s of %d entries where %d are expected" % (name, a.size, size))
+            keep.append(a)
+            setattr(q, name, a.ctypes.data)
+    q.words, q.iscale, q.levels, q.dcq, q.qii, q.cmap, q.skf = words, iscale, levels, dcq, qii, cmap, skf
+    q.dcode, q.rate, q.dskip = dcode, rate, dskip
+    return L.thip_enc_skip_stage(C.byref(q))
 
 
 def rate_groups(nfrags):
