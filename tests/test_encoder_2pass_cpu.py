@@ -1,7 +1,9 @@
 """th_encode_* two-pass without a GPU (include/theoraenc_hip.h, "Two-pass"): the calling conventions and refusals of
 TH_ENCCTL_THIP_2PASS_OUT / _IN / _GET_2PASS_STATS, none of which touches a device (on a machine without one, a call that tried
 would answer TH_EFAULT, not the code asserted); the pass file's codec; the count _2PASS_IN(NULL) answers; and the second pass's
-controller on planted curves, against tests/enc_rate_ref.py's one-pass controller."""
+controller on planted curves, against tests/enc_rate_ref.py's one-pass controller.  Then the library's own pass-file writer, reader
+and second controller (theora_amd/csrc/thip_ratectl.h's TwoPass), replayed by tests/native/ratectl_host.cpp under AddressSanitizer
+and UBSan and compared byte by byte and field by field with the restatement (tests/ratectl_host.py)."""
 import ctypes as C
 import struct
 
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import enc_2pass_ref as TP
+from tests import ratectl_host as RH
 
 ENOTFORMAT = -21
 W, H = 64, 48
@@ -267,3 +270,167 @@ def test_doubled_packets_converge():
     qis, total, B, ctl = _planted([E] * N, T, scale=2, rule="halving")
     assert abs(ctl.r[0] - 131072) <= 131072 // 100 and ctl.r[1] == 65536
     assert abs(total - B) <= 12 * T // 2 + T
+
+
+# ---- the library's TwoPass, replayed on the host (tests/ratectl_host.py) ------------------------------------------------------------
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return RH.build(tmp_path_factory)
+
+
+def _frames(got):
+    return [d for step, d in got if step == "frame"]
+
+
+def _file(fields, recs):
+    return TP.finish_header(fields, recs) + b"".join(TP.pack_record(r["type"], r["qi"], r["bits"], r["E"]) for r in recs)
+
+
+@pytest.mark.parametrize("inter", [False, True], ids=["intra", "inter"])
+@pytest.mark.parametrize("mode", ["quality", "bitrate"])
+def test_pass_one_writes_the_restatements_bytes(host, tmp_path, mode, inter):
+    """The placeholder, every packet's record and the finished header are pack_header's, pack_record's and finish_header's bytes
+    (Model.run compares them), and between them TH_ENCCTL_THIP_2PASS_OUT has nothing to say.  Quality mode: probe entries above
+    2^32 - 1 and below 0 (the record saturates and clamps them) and a packet whose bits saturate the record's u32.  Bitrate mode:
+    the controller's drops are records of type 3."""
+    m = RH.Model(inter=inter, K=4 if inter else 1, quality=17)
+    easy = [500 * (q + 1) for q in range(64)]
+    wild = [(1 << 32) + 5, 1 << 50, -7, (1 << 32) - 1] + easy[4:]
+    if mode == "bitrate":
+        m.bitrate(30 * 10000)
+    assert m.out() == TP.pack_header(m.fields) and m.out() == b""
+    for f in range(12):
+        dups = 2 if f == 2 else 1 if f == 7 else 0
+        if mode == "bitrate":
+            m.frame(easy, dups=dups, mul=0, add=80000)
+        else:
+            m.frame(wild if f % 2 else easy, dups=dups, mul=0, add=1 << 35 if f == 5 else 8000 * (f + 1))
+        assert len(m.out()) == TP.RECORD_BYTES
+        for _ in range(dups):
+            m.dup()
+            assert len(m.out()) == TP.RECORD_BYTES
+        assert m.out() == b""
+    m.done()
+    final = m.out()
+    assert m.out() == b""
+    m.run(host, tmp_path)
+    h, recs = TP.parse(_file(m.fields, m.records))
+    assert final == TP.finish_header(m.fields, recs) and h["dups"] == 3 and h["frames"] == 12
+    want = {TP.KEY, TP.DUP} | ({TP.INTER} if inter else set()) | ({TP.DROPPED} if mode == "bitrate" else set())
+    assert {r["type"] for r in recs} == want
+    if mode == "quality":
+        assert recs[1]["E"][:4] == [TP.U32, TP.U32, 0, TP.U32] and TP.U32 in [r["bits"] for r in recs]
+        assert max(h["tot"][1 if inter else 0]) > 1 << 32
+
+
+PASS2_RECS = [dict(type=t, qi=20 + k, bits=999 * k, E=[0] * 64 if t == TP.DUP else [(k + 1) * (q + 1) for q in range(64)])
+              for k, t in enumerate((TP.KEY, TP.DUP, TP.KEY, TP.KEY))]
+
+
+@pytest.mark.parametrize("chunk", [1, 7, TP.RECORD_BYTES, 10 ** 6])
+def test_pass_two_takes_the_file_in_chunks(host, tmp_path, chunk):
+    """After every chunk the bytes consumed and the count TH_ENCCTL_THIP_2PASS_IN(NULL) answers are the restatement's; a frame is
+    refused exactly while its record is missing, and after the file's last."""
+    m = RH.Model()
+    m.bitrate(100000)
+    data = _file(m.fields, PASS2_RECS)
+    frames = [(PASS2_RECS[0]["E"], 1), (PASS2_RECS[2]["E"], 0), (PASS2_RECS[3]["E"], 0)]
+    assert m.wanted() == TP.HEADER_BYTES and m.gate() == RH.EINVAL
+    have = 0
+    while have < len(data):
+        part = data[have:have + chunk]
+        assert m.feed(part) == len(part)
+        have += len(part)
+        m.wanted()
+        while frames:
+            n = m._n()
+            assert (m.gate() == 0) == (have >= TP.HEADER_BYTES + (n + 1) * TP.RECORD_BYTES), (have, n)
+            if m.gate():
+                break
+            E, dups = frames.pop(0)
+            assert m.frame(E, dups=dups) is not None
+            m.wanted()
+            for _ in range(dups):
+                m.dup()
+    assert not frames and m.gate() == RH.EINVAL and m.frame(PASS2_RECS[0]["E"]) is None   # after the last
+    assert m.feed(b"more") == 0 and m.wanted() == 0
+    m.run(host, tmp_path)
+
+
+def test_pass_two_refuses_a_bad_header_and_starts_over(host, tmp_path):
+    """A bad magic or version: TH_ENOTFORMAT as soon as 8 bytes are in; each of the eleven fields mismatched: TH_EINVAL.  After
+    either the object is as before the first byte (Model.run compares its state), and a good file is then accepted."""
+    m = RH.Model()
+    m.bitrate(100000)
+    good = _file(m.fields, PASS2_RECS)
+    for bad in (b"THP1" + good[4:], good[:4] + struct.pack("<I", 2) + good[8:]):
+        assert m.feed(bad[:7]) == 7 and m.feed(bad[7:20]) == RH.ENOTFORMAT
+        assert m.feed(bad) == RH.ENOTFORMAT and m.wanted() == TP.HEADER_BYTES
+    for k in range(11):
+        f = list(m.fields)
+        f[k] += 1
+        assert m.feed(TP.pack_header(f, 3, 1)[:-1]) == TP.HEADER_BYTES - 1 and m.feed(b"\0" + good[TP.HEADER_BYTES:]) == RH.EINVAL, k
+    assert m.feed(good) == len(good) and m.gate() == 0
+    assert m.frame(PASS2_RECS[0]["E"], dups=1) is not None
+    m.run(host, tmp_path)
+
+
+def _replayed(host, tmp_path, recs, fresh, T, scale=1, **kw):
+    """Pass 2 over `recs` with the fresh probes `fresh` (one a record), each packet taking scale x E[qi] bits: the library's
+    controller against Controller2 (Model.run compares qi, estimate, budget left, recorded_left, the ratios and the corrections
+    of every frame) -> the model and the frames' lines."""
+    m = RH.Model(fps=(1, 1), **kw)
+    m.bitrate(T)
+    data = _file(m.fields, recs)
+    assert m.feed(data) == len(data)
+    for k, r in enumerate(recs):
+        if r["type"] == TP.DUP:
+            m.dup()
+        else:
+            dups = 0
+            while k + dups + 1 < len(recs) and recs[k + dups + 1]["type"] == TP.DUP:
+                dups += 1
+            assert m.frame(fresh[k], dups=dups, mul=scale) is not None
+    return m, _frames(m.run(host, tmp_path))
+
+
+def _key_recs(curves):
+    return [dict(type=TP.KEY, qi=0, bits=0, E=list(E)) for E in curves]
+
+
+def test_library_on_equal_curves(host, tmp_path):
+    E = [1000 * (q + 1) for q in range(64)]
+    m, fr = _replayed(host, tmp_path, _key_recs([E] * 20), [E] * 20, E[40] + 10)
+    assert [d["qi"] for d in fr] == _planted([E] * 20, E[40] + 10)[0] == [40] * 20
+    assert fr[-1]["c"] == [65536, 65536] and fr[-1]["tp_corr"] == [65536] * 4 and 0 <= fr[-1]["budget_left"] < 1000
+
+
+def test_library_on_alternating_curves(host, tmp_path):
+    easy, hard = [500 * (q + 1) for q in range(64)], [3000 * (q + 1) for q in range(64)]
+    curves = [easy, hard] * 12
+    T = (12 * (easy[30] + hard[30]) + 240) // 24
+    m, fr = _replayed(host, tmp_path, _key_recs(curves), curves, T)
+    assert [d["qi"] for d in fr] == _planted(curves, T)[0] == [30] * 24 and 0 <= fr[-1]["budget_left"] < 500
+
+
+def test_library_on_doubled_packets(host, tmp_path):
+    E = [1000 + 200 * q for q in range(64)]
+    m, fr = _replayed(host, tmp_path, _key_recs([E] * 24), [E] * 24, 2 * E[32], scale=2)
+    qis, total, B, ctl = _planted([E] * 24, 2 * E[32], scale=2)
+    assert [d["qi"] for d in fr] == qis and fr[-1]["budget_left"] == B - total
+    assert fr[-1]["tp_corr"] == ctl.c + [65536, 65536] and abs(fr[-1]["c"][0] - 131072) <= 131072 // 100
+
+
+def test_library_on_mixed_records_and_fresh_curves_half_again_as_large(host, tmp_path):
+    """Inter frames on; key, inter, dropped and duplicate records; every fresh curve 1.5 x its record, so fresh / recorded leaves
+    1.0; the file's one key frame is the first, so that class has Tot <= Seen from then on and leaves nothing."""
+    types = [TP.KEY, TP.INTER, TP.INTER, TP.DUP, TP.DROPPED, TP.INTER, TP.DUP, TP.DUP, TP.INTER, TP.DROPPED, TP.INTER, TP.INTER]
+    recs = [dict(type=t, qi=k, bits=8 * k, E=[0] * 64 if t == TP.DUP else [(3000 if t == TP.KEY else 400 + 100 * (k % 3)) * (q + 1)
+                                                                       for q in range(64)]) for k, t in enumerate(types)]
+    fresh = [[3 * x // 2 for x in r["E"]] for r in recs]
+    m, fr = _replayed(host, tmp_path, recs, fresh, 40000, inter=True, K=4)
+    assert len(fr) == 9 and [d["key"] for d in fr] == [1] + [0] * 8 and [d["tp_type"] for d in fr] == [t for t in types if t != TP.DUP]
+    assert m.c2.seen[0] == m.hdr["tot"][0] and m.c2.seen[1] == m.hdr["tot"][1]
+    assert all(d["tp_corr"][2:] == [98304, 98304 if n else 65536] for n, d in enumerate(fr))
+    qis = [d["qi"] for d in fr]
+    assert 0 < min(qis) and max(qis) < 63 and fr[-1]["recorded_left"] == 0 and fr[0]["recorded_left"] > 0

@@ -13,6 +13,10 @@
 // library fed with every packet the encoder returns (loop filter included): the encoder's reference is then the decoder's picture by
 // construction, bit for bit, and the decoder's kernels do the work (dequantisation, iDCT, prediction, the uncoded copies, the loop
 // filter).  The price is a host round trip between frames: the packet must exist before the next frame's search can start.
+//
+// The rate controllers -- bitrate mode's, and two-pass with its pass file -- are host arithmetic in thip_ratectl.h (RateCtl, TwoPass),
+// tested without a GPU.  This file keeps what touches the device (the probe's buffers, launches and read-back), hands the
+// controllers the stream's facts by value (enc_stream), and times them.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +32,7 @@
 #include "../../include/theoraenc_hip.h"
 #include "thip_device.h"
 #include "thip_rate.h"
+#include "thip_ratectl.h"
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_mask.h"
@@ -296,14 +301,9 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint8_t *d_skf = nullptr, *h_skf = nullptr;
   hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;
   thip_enc_skip_stats sstats;
-  // bitrate mode (TH_ENCCTL_SET_BITRATE; the controller is stated in theoraenc_hip.h)
-  bool rate = false, rate_started = false, rate_dropped = false, rate_dev = false;
-  int rate_flags = TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW, rate_buf = 0;   // rate_buf: D when set explicitly, else 0
-  int64_t bitrate = 0, rT = 0, rD = 0, rR = 0, rFstar = 0, rF = 0;
-  int64_t rc_corr[2] = {65536, 65536};   // c_key, c_inter (Q16)
-  int64_t rL[2][64];                     // the last probe of each frame type
-  bool rL_have[2] = {false, false};
-  int64_t rE[64];                        // the probe of the frame queued
+  // bitrate mode (TH_ENCCTL_SET_BITRATE): the controller (thip_ratectl.h) and the probe's device state
+  bool rate = false, rate_dropped = false, rate_dev = false;
+  RateCtl ratectl;
   int rate_nwg = 0;
   int16_t *d_coef = nullptr, *d_qdc = nullptr;
   uint64_t *d_rcoded = nullptr, *d_rcls = nullptr;
@@ -314,7 +314,6 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint32_t *d_rpart = nullptr;
   int64_t *d_rest = nullptr, *h_rest = nullptr;
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
-  thip_enc_rate_stats rstats;
   // the device packetiser (TH_ENCCTL_THIP_SET_DEVICE_PACK; thip_encode_pack.h): on from the next frame; queued for the frame pending
   bool dpack = false, frame_dpack = false;
   int pack_groups = 0, pack_fallbacks = 0;
@@ -331,20 +330,9 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   CutSums *d_cut = nullptr, *h_cut = nullptr;
   hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
   thip_enc_cut_stats cnext, cstats;
-  // two-pass (TH_ENCCTL_THIP_2PASS_OUT / _IN; the pass file and the second controller are stated in theoraenc_hip.h)
-  int tp_pass = 0;                       // 0, 1 (out), 2 (in)
-  bool tp_probe_queued = false;          // pass 1, quality mode: the frame queued has its probe in flight (read in packetout)
-  bool tp_rec_ready = false, tp_final_out = false;
-  int64_t tp_frames = 0, tp_dups = 0;    // pass 1: the counts so far; pass 2: the header's
-  uint64_t tp_tot[2][64];                // pass 1: the sums so far; pass 2: the header's
-  uint64_t tp_seen[2][64], tp_fresh[2][64];   // pass 2: per class, the recorded and the fresh curves of the frames so far
-  int64_t tp_A = 0, tp_ratio[2] = {65536, 65536};
-  int tp_cls = -1;                       // pass 2: the class of the record the frame queued follows (-1: none)
-  int64_t tp_rec[64];                    // ... and its curve
-  bool tp_hdr_ok = false;
-  std::vector<uint8_t> tp_buf;           // pass 1: what the last TH_ENCCTL_THIP_2PASS_OUT returned; pass 2: the pass file so far
-  uint8_t tp_record[THIP_2PASS_RECORD_BYTES];
-  thip_enc_2pass_stats tstats;
+  // two-pass (TH_ENCCTL_THIP_2PASS_OUT / _IN): the pass file and the second controller (thip_ratectl.h)
+  TwoPass twopass;
+  bool probe_queued = false;   // pass 1, quality mode: the frame queued has its probe in flight (read in packetout)
   // output: pkt_data is pkt's (the host packer, empty packets) or h_pk (the device packetiser)
   const uint8_t *pkt_data = nullptr;
   size_t pkt_size = 0;
@@ -405,15 +393,9 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->kstats, 0, sizeof(e->kstats));
   memset(&e->dstats, 0, sizeof(e->dstats));
   memset(&e->sstats, 0, sizeof(e->sstats));
-  memset(&e->rstats, 0, sizeof(e->rstats));
   memset(&e->pstats, 0, sizeof(e->pstats));
   memset(&e->cnext, 0, sizeof(e->cnext));
   memset(&e->cstats, 0, sizeof(e->cstats));
-  memset(&e->tstats, 0, sizeof(e->tstats));
-  memset(e->tp_tot, 0, sizeof(e->tp_tot));
-  memset(e->tp_seen, 0, sizeof(e->tp_seen));
-  memset(e->tp_fresh, 0, sizeof(e->tp_fresh));
-  memset(e->tp_rec, 0, sizeof(e->tp_rec));
   e->dpack =thip_option("enc_device_pack") != 0;
   e->kf_interval = (int64_t)1 << i.keyframe_granule_shift;
   return e;
@@ -473,7 +455,7 @@ static void enc_free_device(th_enc_ctx *e) {
   e->mask_queued = false;
   e->rd_queued = false;
   e->skip_queued = false;
-  e->tp_probe_queued = false;
+  e->probe_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
                           &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1, &e->ev_s0, &e->ev_s1}) {
     if (*ev) (void)hipEventDestroy(*ev);
@@ -915,9 +897,16 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   return 0;
 }
 
-// E[0..63] of the frame about to be coded (thip_rate.h) into e->rE: queued on the encoder's stream behind its input, waited for.
-// searched: d_rmbs holds k_rate_me's words of this frame already (enc_cut_measure).  wait = false (pass 1 of two-pass in quality
-// mode): nothing is waited for; the 512 bytes are in h_rest once ev_p1 has passed (enc_2pass_collect)
+// the probe's 512 bytes are on the host (ev_p1 has passed): the controller's E, and the probe's device time
+static void enc_rate_read(th_enc_ctx *e) {
+  float ms = 0;
+  e->ratectl.stats.probe_ms = hipEventElapsedTime(&ms, e->ev_p0, e->ev_p1) == hipSuccess ? ms : 0.0;
+  memcpy(e->ratectl.E, e->h_rest, sizeof(e->ratectl.E));
+}
+
+// E[0..63] of the frame about to be coded (thip_rate.h) into the controller's E: queued on the encoder's stream behind its input,
+// waited for.  searched: d_rmbs holds k_rate_me's words of this frame already (enc_cut_measure).  wait = false (pass 1 of two-pass
+// in quality mode): nothing is waited for; the 512 bytes are in h_rest once ev_p1 has passed (enc_2pass_collect)
 static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key, bool searched, bool wait = true) {
   const int64_t n = e->nfrags;
   RateArgs a;
@@ -948,339 +937,27 @@ static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key, bool sear
   ENC_TRY(hipEventRecord(e->ev_p1, e->stream));
   if (!wait) return 0;
   ENC_TRY(hipEventSynchronize(e->ev_p1));
-  float ms = 0;
-  e->rstats.probe_ms = hipEventElapsedTime(&ms, e->ev_p0, e->ev_p1) == hipSuccess ? ms : 0.0;
-  memcpy(e->rE, e->h_rest, sizeof(e->rE));
+  enc_rate_read(e);
   return 0;
 }
-
-static int64_t rate_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// T, R, F* of the bitrate in force (D kept)
-static void enc_rate_targets(th_enc_ctx *e) {
-  const th_info &i = e->info;
-  e->rT = rate_clamp((int64_t)((__int128)e->bitrate * i.fps_denominator / i.fps_numerator), 32, (int64_t)1 << 40);
-  e->rR = e->rT * e->rD;
-  e->rFstar = e->rR / 2;
-}
-
-static void enc_rate_caps(th_enc_ctx *e) {
-  if (e->rate_flags & TH_RATECTL_CAP_OVERFLOW) e->rF = std::min(e->rF, e->rR);
-  if (e->rate_flags & TH_RATECTL_CAP_UNDERFLOW) e->rF = std::max(e->rF, (int64_t)0);
-}
-
-// the controller's choice for frame f (theoraenc_hip.h, "Bitrate mode"): returns the qi, or -1 to drop the frame
-static int enc_rate_choose(th_enc_ctx *e, bool key, int64_t f, int64_t keypos) {
-  const double t0 = thip_now();
-  if (!e->rate_started) {
-    e->rD = e->rate_buf ? e->rate_buf : rate_clamp(e->inter ? e->kf_interval : 1, 12, 256);
-    enc_rate_targets(e);
-    e->rF = e->rFstar;
-    e->rate_started = true;
-  }
-  const int t = key ? 0 : 1;
-  memcpy(e->rL[t], e->rE, sizeof(e->rE));
-  e->rL_have[t] = true;
-  // the next D - 1 frames: key or inter by the interval rule from the current key position
-  int64_t nk = 0, ni = 0;
-  for (int64_t m = f + 1; m < f + e->rD; m++) {
-    if (!e->inter || (m - keypos) % e->kf_interval == 0) nk++;
-    else ni++;
-  }
-  int64_t cur[64], fut[64];
-  for (int q = 0; q < 64; q++) {
-    cur[q] = e->rE[q] * e->rc_corr[t] >> 16;
-    int64_t kt = e->rL_have[0] ? e->rL[0][q] * e->rc_corr[0] >> 16 : -1;
-    int64_t it = e->rL_have[1] ? e->rL[1][q] * e->rc_corr[1] >> 16 : -1;
-    if (it < 0) it = kt / 4;
-    if (kt < 0) kt = 4 * it;
-    fut[q] = nk * kt + ni * it;
-  }
-  const int64_t S = e->rF + e->rD * e->rT - e->rFstar;
-  int qi = 0;
-  for (int q = 63; q >= 0; q--)
-    if (cur[q] + fut[q] <= S) {
-      qi = q;
-      break;
-    }
-  const int64_t full = (int64_t)1 << e->info.keyframe_granule_shift;
-  const bool drop = (e->rate_flags & TH_RATECTL_DROP_FRAMES) && e->cur >= 0 && e->rF + e->rT - cur[0] < 0 && e->key >= 0 &&
-                    f - e->key + e->dup_next < full;
-  thip_enc_rate_stats &r = e->rstats;
-  r.qi = drop ? e->frame_qi : qi;
-  r.dropped = drop;
-  r.key = key && !drop;
-  r.duplicate = 0;
-  r.target = e->rT;
-  r.fullness_before = e->rF;
-  r.spend = S;
-  r.estimate = cur[qi];
-  r.actual = 0;
-  memcpy(r.probe, e->rE, sizeof(r.probe));
-  if (drop) {
-    e->rF += e->rT;
-    enc_rate_caps(e);
-  }
-  r.fullness_after = e->rF;
-  r.corr[0] = e->rc_corr[0];
-  r.corr[1] = e->rc_corr[1];
-  r.control_ms = (thip_now() - t0) * 1e3;
-  return drop ? -1 : qi;
-}
-
-// after a coded frame of A bits
-static void enc_rate_update(th_enc_ctx *e, bool key, int64_t A) {
-  const int t = key ? 0 : 1;
-  e->rF += e->rT - A;
-  enc_rate_caps(e);
-  const int64_t est = std::max(e->rE[e->frame_qi], (int64_t)1);
-  e->rc_corr[t] = rate_clamp((e->rc_corr[t] + (A << 16) / est) / 2, 4096, (int64_t)1 << 20);
-  e->rstats.actual = A;
-  e->rstats.fullness_after = e->rF;
-  e->rstats.corr[0] = e->rc_corr[0];
-  e->rstats.corr[1] = e->rc_corr[1];
-}
-
-// a duplicate (TH_ENCCTL_SET_DUP_COUNT) in bitrate mode
-static void enc_rate_dup(th_enc_ctx *e) {
-  if (!e->rate_started) return;
-  thip_enc_rate_stats &r = e->rstats;
-  r.dropped = r.key = 0;
-  r.duplicate = 1;
-  r.qi = e->frame_qi;
-  r.fullness_before = e->rF;
-  e->rF += e->rT;
-  enc_rate_caps(e);
-  r.fullness_after = e->rF;
-  if (e->tp_pass == 2) r.fullness_before = r.fullness_after = e->rT * (e->tp_frames + e->tp_dups) - e->tp_A;   // (no buffer: B - A)
-  r.spend = r.estimate = r.actual = 0;
-  memset(r.probe, 0, sizeof(r.probe));
-  r.probe_ms = r.control_ms = 0;
-}
-
-// ---- two-pass (theoraenc_hip.h, "Two-pass") -----------------------------------------------------------------------------------------
-// host code throughout: neither request touches the GPU
-static void tp_put(uint8_t *p, uint64_t v, int bytes) {
-  for (int k = 0; k < bytes; k++) p[k] = (uint8_t)(v >> (8 * k));
-}
-
-static uint64_t tp_get(const uint8_t *p, int bytes) {
-  uint64_t v = 0;
-  for (int k = 0; k < bytes; k++) v |= (uint64_t)p[k] << (8 * k);
-  return v;
-}
-
-// the eleven u32 of the header that must be the context's
-static void enc_2pass_fields(const th_enc_ctx *e, uint32_t f[11]) {
-  const th_info &i = e->info;
-  const uint32_t v[11] = {i.frame_width, i.frame_height, i.pic_x, i.pic_y, i.pic_width, i.pic_height, (uint32_t)i.pixel_fmt,
-                          i.fps_numerator, i.fps_denominator, (uint32_t)i.keyframe_granule_shift, e->inter ? 1u : 0u};
-  memcpy(f, v, sizeof(v));
-}
-
-// pass 1: the header of the pass file with the counts and sums so far (all 0 for the placeholder) into tp_buf
-static void enc_2pass_header(th_enc_ctx *e) {
-  e->tp_buf.assign(THIP_2PASS_HEADER_BYTES, 0);
-  uint8_t *p = e->tp_buf.data();
-  memcpy(p, "THP2", 4);
-  tp_put(p + 4, 1, 4);
-  uint32_t f[11];
-  enc_2pass_fields(e, f);
-  for (int k = 0; k < 11; k++) tp_put(p + 8 + 4 * k, f[k], 4);
-  tp_put(p + 52, (uint64_t)e->tp_frames, 4);
-  tp_put(p + 56, (uint64_t)e->tp_dups, 4);
-  for (int t = 0; t < 2; t++)
-    for (int q = 0; q < 64; q++) tp_put(p + 60 + 8 * (t * 64 + q), e->tp_tot[t][q], 8);
-}
-
-// a record's class: the sum its curve enters (-1: none)
-static int enc_2pass_class(const th_enc_ctx *e, int type) { return type <= 1 ? type : type == 3 ? (e->inter ? 1 : 0) : -1; }
 
 // pass 1, quality mode: the probe queued with the frame has its 512 bytes on the host
 static int enc_2pass_collect(th_enc_ctx *e) {
-  if (!e->tp_probe_queued) return 0;
-  e->tp_probe_queued = false;
+  if (!e->probe_queued) return 0;
+  e->probe_queued = false;
   const double t0 = thip_now();
   ENC_TRY(hipEventSynchronize(e->ev_p1));
-  e->tstats.wait_ms = (thip_now() - t0) * 1e3;
-  float ms = 0;
-  e->rstats.probe_ms = hipEventElapsedTime(&ms, e->ev_p0, e->ev_p1) == hipSuccess ? ms : 0.0;
-  memcpy(e->rE, e->h_rest, sizeof(e->rE));
+  e->twopass.stats.wait_ms = (thip_now() - t0) * 1e3;
+  enc_rate_read(e);
   return 0;
 }
 
-// every packet: the statistics of the pass, and in pass 1 the packet's record.  type: 0 key, 1 inter, 2 duplicate, 3 dropped
-static void enc_2pass_packet(th_enc_ctx *e, int type) {
-  thip_enc_2pass_stats &s = e->tstats;
-  s.pass = e->tp_pass;
-  s.frame = e->cur;
-  s.qi = e->frame_qi;
-  if (e->tp_pass == 0) return;
-  const bool probed = type != 2;
-  s.probe_ms = probed ? e->rstats.probe_ms : 0.0;
-  for (int q = 0; q < 64; q++) s.fresh[q] = probed ? e->rE[q] : 0;
-  if (e->tp_pass == 2) {
-    s.type = type == 2 ? 2 : s.type;   // (a frame: the record's type, set when the frame was queued)
-    if (type == 2) memset(s.recorded, 0, sizeof(s.recorded));
-    s.budget_left = e->rT * (e->tp_frames + e->tp_dups) - e->tp_A;
-    s.corr[0] = e->rc_corr[0];
-    s.corr[1] = e->rc_corr[1];
-    s.corr[2] = e->tp_ratio[0];
-    s.corr[3] = e->tp_ratio[1];
-    return;
-  }
-  s.type = type;
-  uint8_t *p = e->tp_record;
-  memset(p, 0, sizeof(e->tp_record));
-  p[0] = (uint8_t)type;
-  p[1] = (uint8_t)e->frame_qi;
-  tp_put(p + 4, std::min<uint64_t>((uint64_t)e->pkt_size * 8, 0xFFFFFFFFu), 4);
-  const int cls = enc_2pass_class(e, type);
-  for (int q = 0; q < 64; q++) {
-    const uint64_t v = probed ? (uint64_t)std::min<int64_t>(std::max<int64_t>(e->rE[q], 0), 0xFFFFFFFFll) : 0;
-    tp_put(p + 8 + 4 * q, v, 4);
-    s.recorded[q] = (int64_t)v;
-    if (cls >= 0) e->tp_tot[cls][q] += v;
-  }
-  if (type == 2) e->tp_dups++;
-  else e->tp_frames++;
-  e->tp_rec_ready = true;
-}
-
-// pass 2: the bytes still wanted before frame n can be taken (n: the next frame's index)
-static int64_t enc_2pass_wanted(const th_enc_ctx *e) {
-  const int64_t have = (int64_t)e->tp_buf.size();
-  if (!e->tp_hdr_ok) return THIP_2PASS_HEADER_BYTES - have;
-  const int64_t n = e->cur + 1 + (e->frame_pending ? 1 : 0) + e->dups_left;
-  if (n >= e->tp_frames + e->tp_dups) return 0;
-  return std::max<int64_t>(THIP_2PASS_HEADER_BYTES + (n + 1) * THIP_2PASS_RECORD_BYTES - have, 0);
-}
-
-// pass 2: bytes of the pass file; returns how many were consumed
-static int enc_2pass_in(th_enc_ctx *e, const uint8_t *p, size_t n) {
-  e->tp_pass = e->tstats.pass = 2;
-  n = std::min(n, (size_t)0x7FFFFFFF);
-  size_t used = 0;
-  int bad = 0;
-  if (!e->tp_hdr_ok) {
-    used = std::min(n, (size_t)THIP_2PASS_HEADER_BYTES - e->tp_buf.size());
-    e->tp_buf.insert(e->tp_buf.end(), p, p + used);
-    const uint8_t *h = e->tp_buf.data();
-    if (e->tp_buf.size() >= 8 && (memcmp(h, "THP2", 4) != 0 || tp_get(h + 4, 4) != 1)) bad = TH_ENOTFORMAT;
-    if (!bad && e->tp_buf.size() == THIP_2PASS_HEADER_BYTES) {
-      uint32_t f[11];
-      enc_2pass_fields(e, f);
-      for (int k = 0; k < 11; k++)
-        if (tp_get(h + 8 + 4 * k, 4) != f[k]) bad = TH_EINVAL;
-      if (!bad) {
-        e->tp_frames = (int64_t)tp_get(h + 52, 4);
-        e->tp_dups = (int64_t)tp_get(h + 56, 4);
-        for (int t = 0; t < 2; t++)
-          for (int q = 0; q < 64; q++) e->tp_tot[t][q] = tp_get(h + 60 + 8 * (t * 64 + q), 8);
-        e->tp_hdr_ok = true;
-      }
-    }
-    if (bad) {   // the context is as it was before the pass file's first byte
-      e->tp_buf.clear();
-      e->tp_pass = e->tstats.pass = 0;
-      return bad;
-    }
-    if (!e->tp_hdr_ok) return (int)used;
-  }
-  const size_t total = (size_t)THIP_2PASS_HEADER_BYTES + (size_t)(e->tp_frames + e->tp_dups) * THIP_2PASS_RECORD_BYTES;
-  const size_t take = std::min(n - used, total - e->tp_buf.size());
-  e->tp_buf.insert(e->tp_buf.end(), p + used, p + used + take);
-  return (int)(used + take);
-}
-
-// pass 2: may the next frame be taken?  (before the device is touched)
-static int enc_2pass_gate(const th_enc_ctx *e) {
-  if (e->tp_pass != 2) return 0;
-  if (!e->tp_hdr_ok || e->cur + 1 >= e->tp_frames + e->tp_dups || enc_2pass_wanted(e) > 0) return TH_EINVAL;
-  return 0;
-}
-
-// pass 2: frame f's type from its record (theoraenc_hip.h); the record's curve enters Seen
-static void enc_2pass_type(th_enc_ctx *e, int64_t f) {
-  const uint8_t *rec = e->tp_buf.data() + THIP_2PASS_HEADER_BYTES + (size_t)f * THIP_2PASS_RECORD_BYTES;
-  const int type = rec[0] <= 3 ? rec[0] : 1;
-  const int64_t full = (int64_t)1 << e->info.keyframe_granule_shift;
-  e->frame_key = type == 0 || !e->inter || e->key < 0 || f - e->key + e->dup_next >= full;
-  e->tp_cls = enc_2pass_class(e, type);
-  e->tstats.type = type;
-  for (int q = 0; q < 64; q++) {
-    e->tp_rec[q] = (int64_t)tp_get(rec + 8 + 4 * q, 4);
-    e->tstats.recorded[q] = e->tp_rec[q];
-    if (e->tp_cls >= 0) e->tp_seen[e->tp_cls][q] += (uint64_t)e->tp_rec[q];
-  }
-}
-
-// pass 2: Y_u(q), what the recorded curves leave of class u at q, scaled by fresh / recorded of the frames so far and by c_u
-static __int128 enc_2pass_rest(const th_enc_ctx *e, int u, int q) {
-  if (e->tp_tot[u][q] <= e->tp_seen[u][q]) return 0;
-  unsigned __int128 y = e->tp_tot[u][q] - e->tp_seen[u][q];
-  if (e->tp_seen[u][q]) y = std::min<unsigned __int128>(y * e->tp_fresh[u][q] / e->tp_seen[u][q], (unsigned __int128)1 << 62);
-  return (__int128)y * e->rc_corr[u] >> 16;
-}
-
-// pass 2: the controller's choice for the frame probed into rE
-static int enc_2pass_choose(th_enc_ctx *e, bool key) {
-  const double t0 = thip_now();
-  if (!e->rate_started) {
-    e->rD = e->rate_buf ? e->rate_buf : rate_clamp(e->inter ? e->kf_interval : 1, 12, 256);
-    enc_rate_targets(e);
-    e->rF = e->rFstar;
-    e->rate_started = true;
-  }
-  const int t = key ? 0 : 1;
-  if (e->tp_cls >= 0)
-    for (int q = 0; q < 64; q++)
-      e->tp_fresh[e->tp_cls][q] = std::min<uint64_t>(e->tp_fresh[e->tp_cls][q] + (uint64_t)std::max<int64_t>(e->rE[q], 0), 1ull << 62);
-  const int64_t left = e->rT * (e->tp_frames + e->tp_dups) - e->tp_A;
-  int qi = 0;
-  int64_t est = 0;
-  for (int q = 63; q >= 0; q--) {
-    const int64_t cur = e->rE[q] * e->rc_corr[t] >> 16;
-    const __int128 fut = enc_2pass_rest(e, 0, q) + enc_2pass_rest(e, 1, q);
-    if (q == 0) est = cur;
-    if ((__int128)cur + fut <= left) {
-      qi = q;
-      est = cur;
-      break;
-    }
-  }
-  int64_t rl = 0;
-  for (int u = 0; u < 2; u++) {
-    if (e->tp_tot[u][qi] > e->tp_seen[u][qi]) rl += (int64_t)(e->tp_tot[u][qi] - e->tp_seen[u][qi]);
-    e->tp_ratio[u] = e->tp_seen[u][qi] ? (int64_t)std::min<unsigned __int128>(((unsigned __int128)e->tp_fresh[u][qi] << 16) /
-                                                                                   e->tp_seen[u][qi], (unsigned __int128)1 << 62)
-                                       : 65536;
-  }
-  e->tstats.recorded_left = rl;
-  thip_enc_rate_stats &r = e->rstats;
-  r.qi = qi;
-  r.dropped = r.duplicate = 0;
-  r.key = key;
-  r.target = e->rT;
-  r.fullness_before = r.fullness_after = r.spend = left;
-  r.estimate = est;
-  r.actual = 0;
-  memcpy(r.probe, e->rE, sizeof(r.probe));
-  r.corr[0] = e->rc_corr[0];
-  r.corr[1] = e->rc_corr[1];
-  r.control_ms = (thip_now() - t0) * 1e3;
-  return qi;
-}
-
-// pass 2: after a coded frame of A bits
-static void enc_2pass_update(th_enc_ctx *e, bool key, int64_t A) {
-  const int t = key ? 0 : 1;
-  e->tp_A += A;
-  e->rc_corr[t] = rate_clamp((e->rc_corr[t] + (A << 16) / std::max(e->rE[e->frame_qi], (int64_t)1)) / 2, 4096, (int64_t)1 << 20);
-  e->rstats.actual = A;
-  e->rstats.fullness_after = e->rT * (e->tp_frames + e->tp_dups) - e->tp_A;
-  e->rstats.corr[0] = e->rc_corr[0];
-  e->rstats.corr[1] = e->rc_corr[1];
+// what the controllers read of the stream (thip_ratectl.h)
+static EncStream enc_stream(const th_enc_ctx *e) {
+  const th_info &i = e->info;
+  return {i.frame_width, i.frame_height, i.pic_x, i.pic_y, i.pic_width, i.pic_height, (uint32_t)i.pixel_fmt, i.fps_numerator,
+          i.fps_denominator, i.keyframe_granule_shift, e->inter, e->kf_interval, e->cur, e->key, e->dup_next, e->frame_qi,
+          e->frame_pending, e->dups_left};
 }
 
 // ---- automatic key frames (thip_encode_cut.h) ---------------------------------------------------------------------------------------
@@ -1347,21 +1024,22 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   memset(&e->cnext, 0, sizeof(e->cnext));
   e->cnext.ratio = e->auto_kf;
   bool searched = false;   // d_rmbs holds this frame's search
-  if (e->tp_pass == 2) {
-    enc_2pass_type(e, f);   // the second pass: the type is the record's; neither the interval nor a measurement is consulted
+  if (e->twopass.pass == 2) {
+    // the second pass: the type is the record's; neither the interval nor a measurement is consulted
+    e->frame_key = e->twopass.type(enc_stream(e), f);
   } else if (e->auto_kf && !e->frame_key) {
     const int mrc = enc_cut_measure(e, g);
     if (mrc) return mrc;
     e->frame_key = e->cnext.cut != 0;
     searched = !e->frame_key;
   }
-  e->tp_probe_queued = false;
-  if (e->tp_pass == 1 && !e->rate) {
+  e->probe_queued = false;
+  if (e->twopass.pass == 1 && !e->rate) {
     // the first pass in quality mode: the probe's launches in front of the frame's, its 512 bytes read in th_encode_packetout
     if (enc_rate_alloc(e)) return TH_EFAULT;
     const int prc = enc_rate_probe(e, g, e->frame_key, searched, false);
     if (prc) return prc;
-    e->tp_probe_queued = true;
+    e->probe_queued = true;
   }
   if (e->rate) {
     // bitrate mode: the probe, then the controller's qi -- or a dropped frame, a zero-byte packet with nothing more queued
@@ -1369,7 +1047,11 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     const int prc = enc_rate_probe(e, g, e->frame_key, searched);
     if (prc) return prc;
     ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the launches below record it again)
-    const int qi = e->tp_pass == 2 ? enc_2pass_choose(e, e->frame_key) : enc_rate_choose(e, e->frame_key, f, e->frame_key ? f : e->key);
+    const double t0 = thip_now();
+    const EncStream s = enc_stream(e);
+    const int qi = e->twopass.pass == 2 ? e->twopass.choose(s, e->ratectl, e->frame_key)
+                                        : e->ratectl.choose(s, e->frame_key, f, e->frame_key ? f : e->key);
+    e->ratectl.stats.control_ms = (thip_now() - t0) * 1e3;
     if (qi < 0) {
       e->frame_key = false;
       e->cnext.cut = 0;   // (a dropped frame is not a key frame, whatever was measured)
@@ -1404,7 +1086,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
 
 int th_encode_ycbcr_in(th_enc_ctx *e, th_ycbcr_buffer ycbcr) {
   if (!e || !ycbcr) return TH_EFAULT;
-  if (e->done || e->frame_pending || e->dups_left || enc_2pass_gate(e)) return TH_EINVAL;
+  if (e->done || e->frame_pending || e->dups_left || e->twopass.gate(enc_stream(e))) return TH_EINVAL;
   const int kind = enc_buffer_kind(e, ycbcr);
   if (kind < 0) return TH_EINVAL;
   if (enc_ensure_device(e)) return TH_EFAULT;
@@ -1425,7 +1107,7 @@ int th_encode_ycbcr_in(th_enc_ctx *e, th_ycbcr_buffer ycbcr) {
 }
 
 static int enc_ycbcr_in_device(th_enc_ctx *e, const thip_enc_device_in *a) {
-  if (e->done || e->frame_pending || e->dups_left || enc_2pass_gate(e)) return TH_EINVAL;
+  if (e->done || e->frame_pending || e->dups_left || e->twopass.gate(enc_stream(e))) return TH_EINVAL;
   const int kind = enc_buffer_kind(e, a->planes);
   if (kind < 0) return TH_EINVAL;
   if (enc_ensure_device(e)) return TH_EFAULT;
@@ -1459,7 +1141,7 @@ static int enc_ycbcr_in_device(th_enc_ctx *e, const thip_enc_device_in *a) {
 
 // TH_ENCCTL_THIP_RGB_IN: the picture through thip_picture_in into d_pix (picture-sized planes, stride cw[p]), then the frame as ever
 static int enc_rgb_in(th_enc_ctx *e, const thip_enc_rgb_in *a) {
-  if (e->done || e->frame_pending || e->dups_left || enc_2pass_gate(e)) return TH_EINVAL;
+  if (e->done || e->frame_pending || e->dups_left || e->twopass.gate(enc_stream(e))) return TH_EINVAL;
   if (a->format != THIP_PIC_RGB24 && a->format != THIP_PIC_RGBA32 && a->format != THIP_PIC_RGB_PLANAR) return TH_EINVAL;
   if (a->device != 0 && a->device != 1) return TH_EINVAL;
   if (a->width != (int32_t)e->info.pic_width || a->height != (int32_t)e->info.pic_height) return TH_EINVAL;
@@ -1714,6 +1396,18 @@ static void enc_empty_packet(th_enc_ctx *e) {
   enc_mask_stats(e, false);
   enc_rd_stats(e, false);
   enc_skip_stats(e, false);
+}
+
+// the packet of no frame of its own (one the rate controller dropped, a duplicate): empty, and no packer, search or mode choice ran
+static void enc_repeat_packet(th_enc_ctx *e, ogg_packet *op) {
+  enc_empty_packet(e);
+  op->packet = e->pkt.data();
+  op->bytes = 0;
+  memset(&e->pstats, 0, sizeof(e->pstats));
+  e->pstats.fallbacks = e->pack_fallbacks;
+  memset(&e->istats, 0, sizeof(e->istats));
+  memset(&e->mstats, 0, sizeof(e->mstats));
+  e->istats.mode_scheme = e->istats.mv_scheme = -1;
 }
 
 // what both packers leave behind: the frame's statistics, the AC tables the next block-qi choice of this frame type counts with, and
@@ -2051,23 +1745,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     e->frame_pending = e->rate_dropped = false;
     ++e->cur;
     e->cstats = e->cnext;
-    e->pkt.clear();
-    e->pkt_data = e->pkt.data();
-    e->pkt_size = 0;
-    op->packet = e->pkt.data();
-    op->bytes = 0;
-    memset(&e->pstats, 0, sizeof(e->pstats));
-    e->pstats.fallbacks = e->pack_fallbacks;
-    memset(&e->stats, 0, sizeof(e->stats));
-    e->stats.qi = e->frame_qi;
-    e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
-    memset(&e->istats, 0, sizeof(e->istats));
-    memset(&e->mstats, 0, sizeof(e->mstats));
-    memset(&e->bstats, 0, sizeof(e->bstats));
-    enc_mask_stats(e, false);
-    enc_rd_stats(e, false);
-    enc_skip_stats(e, false);
-    e->istats.mode_scheme = e->istats.mv_scheme = -1;
+    enc_repeat_packet(e, op);
     const int qrc = enc_quality_queue(e, true);   // (against the picture the decoder goes on showing)
     if (qrc) return qrc;
   } else if (e->frame_pending) {
@@ -2083,8 +1761,8 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     }
     const int qrc = enc_quality_queue(e, true);
     if (qrc) return qrc;
-    if (e->tp_pass == 2) enc_2pass_update(e, e->frame_key, (int64_t)e->pkt_size * 8);
-    else if (e->rate) enc_rate_update(e, e->frame_key, (int64_t)e->pkt_size * 8);
+    if (e->twopass.pass == 2) e->twopass.coded(enc_stream(e), e->ratectl, e->frame_key, (int64_t)e->pkt_size * 8);
+    else if (e->rate) e->ratectl.coded(enc_stream(e), e->frame_key, (int64_t)e->pkt_size * 8);
     ptype = e->frame_key ? 0 : 1;
     op->packet = const_cast<uint8_t *>(e->pkt_data);
     op->bytes = (long)e->pkt_size;
@@ -2092,26 +1770,11 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
     ptype = 2;
     e->dups_left--;
     ++e->cur;
-    if (e->rate) enc_rate_dup(e);
+    if (e->twopass.pass == 2) e->twopass.dup(enc_stream(e), e->ratectl);
+    else if (e->rate) e->ratectl.dup(enc_stream(e));
     memset(&e->cstats, 0, sizeof(e->cstats));
     e->cstats.ratio = e->auto_kf;
-    e->pkt.clear();
-    e->pkt_data = e->pkt.data();
-    e->pkt_size = 0;
-    op->packet = e->pkt.data();
-    op->bytes = 0;
-    memset(&e->pstats, 0, sizeof(e->pstats));
-    e->pstats.fallbacks = e->pack_fallbacks;
-    memset(&e->stats, 0, sizeof(e->stats));
-    e->stats.qi = e->frame_qi;
-    e->stats.huff[0] = e->stats.huff[1] = e->stats.huff[2] = e->stats.huff[3] = -1;
-    memset(&e->istats, 0, sizeof(e->istats));
-    memset(&e->mstats, 0, sizeof(e->mstats));
-    memset(&e->bstats, 0, sizeof(e->bstats));
-    enc_mask_stats(e, false);
-    enc_rd_stats(e, false);
-    enc_skip_stats(e, false);
-    e->istats.mode_scheme = e->istats.mv_scheme = -1;
+    enc_repeat_packet(e, op);
     (void)enc_quality_queue(e, false);
   } else {
     return 0;
@@ -2121,7 +1784,7 @@ int th_encode_packetout(th_enc_ctx *e, int last, ogg_packet *op) {
   op->granulepos = ((e->key + e->granpos_bias) << shift) + (e->cur - e->key);
   op->packetno = e->packetno++;
   if (op->e_o_s) e->done = true;
-  enc_2pass_packet(e, ptype);
+  e->twopass.packet(enc_stream(e), e->ratectl, ptype, e->pkt_size);
   return 1;
 }
 
@@ -2198,6 +1861,9 @@ int th_encode_flushheader(th_enc_ctx *e, th_comment *tc, ogg_packet *op) {
   return 1;
 }
 
+// a frame has come in: the requests that hold "before the first frame only" are refused from here on
+static bool enc_begun(const th_enc_ctx *e) { return e->cur >= 0 || e->frame_pending || e->done; }
+
 int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
   if (!e) return TH_EFAULT;
   switch (req) {
@@ -2222,7 +1888,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_INTER_FRAMES: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const bool on = *(const int *)buf != 0;
       if (on != e->inter && e->dev_ready) enc_free_device(e);   // (GET_DEVICE made the buffers of the other kind)
       e->inter = on;
@@ -2230,13 +1896,13 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_INTER_MODES: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       e->modes = *(const int *)buf != 0;   // (its buffers are made at the first inter frame)
       return 0;
     }
     case TH_ENCCTL_THIP_SET_BLOCK_QI: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const int d = *(const int *)buf;
       if (d < 0 || d > 31) return TH_EINVAL;
       e->bqi = d;   // (its buffers are made at the first frame that uses it)
@@ -2244,7 +1910,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_MASKING: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const int k = *(const int *)buf;
       if (k != 0 && (k < 2 || k > 16)) return TH_EINVAL;
       e->mask = k;   // (its buffers are made at the first frame that uses it)
@@ -2253,7 +1919,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_RD_MODES: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const int v = *(const int *)buf;
       if (v != 0 && v != 1) return TH_EINVAL;
       e->rd = v != 0;   // (its buffers are made at the first frame that uses it)
@@ -2262,7 +1928,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_RD_SKIP: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const int v = *(const int *)buf;
       if (v != 0 && v != 1) return TH_EINVAL;
       e->skip = v != 0;   // (its buffers are made at the first frame that uses it)
@@ -2278,7 +1944,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const int t = *(const int *)buf;
       if (t < 0 || t > 4096) return TH_EINVAL;
       e->auto_kf = t;   // (its buffers are made at the first frame measured)
@@ -2287,7 +1953,7 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     }
     case TH_ENCCTL_THIP_SET_QUALITY_STATS: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      if (enc_begun(e)) return TH_EINVAL;
       const int f = *(const int *)buf;
       if (f != 0 && f != THIP_CMP_SSE && f != (THIP_CMP_SSE | THIP_CMP_SSIM)) return TH_EINVAL;
       e->qflags = f;   // (its buffers are made at the first packet measured)
@@ -2323,41 +1989,15 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     case TH_ENCCTL_THIP_2PASS_OUT: {
       if (buf_sz != sizeof(unsigned char *)) return TH_EINVAL;
       if (!buf) return TH_EFAULT;
-      if (e->tp_pass == 2) return TH_EINVAL;
-      unsigned char **out = (unsigned char **)buf;
-      if (e->tp_pass == 0) {
-        if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // the first call: before the first frame only
-        e->tp_pass = e->tstats.pass = 1;
-        enc_2pass_header(e);   // the placeholder
-        *out = e->tp_buf.data();
-        return THIP_2PASS_HEADER_BYTES;
-      }
-      if (e->tp_rec_ready) {
-        e->tp_rec_ready = false;
-        *out = e->tp_record;
-        return THIP_2PASS_RECORD_BYTES;
-      }
-      if (e->done && !e->tp_final_out) {
-        e->tp_final_out = true;
-        enc_2pass_header(e);
-        *out = e->tp_buf.data();
-        return THIP_2PASS_HEADER_BYTES;
-      }
-      *out = nullptr;
-      return 0;
+      if (e->twopass.pass == 2 || (e->twopass.pass == 0 && enc_begun(e))) return TH_EINVAL;   // (the first call)
+      return e->twopass.out(enc_stream(e), e->done, (unsigned char **)buf);
     }
-    case TH_ENCCTL_THIP_2PASS_IN: {
-      if (e->tp_pass == 1) return TH_EINVAL;
-      if (e->tp_pass == 0 && (!e->rate || e->cur >= 0 || e->frame_pending || e->done)) return TH_EINVAL;   // the first call
-      if (!buf) {
-        e->tp_pass = e->tstats.pass = 2;
-        return (int)std::min<int64_t>(enc_2pass_wanted(e), 0x7FFFFFFF);
-      }
-      return enc_2pass_in(e, (const uint8_t *)buf, buf_sz);
-    }
+    case TH_ENCCTL_THIP_2PASS_IN:
+      if (e->twopass.pass == 1 || (e->twopass.pass == 0 && (!e->rate || enc_begun(e)))) return TH_EINVAL;   // (the first call)
+      return e->twopass.in(enc_stream(e), (const uint8_t *)buf, buf_sz);
     case TH_ENCCTL_THIP_GET_2PASS_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_2pass_stats)) return TH_EINVAL;
-      *(thip_enc_2pass_stats *)buf = e->tstats;
+      *(thip_enc_2pass_stats *)buf = e->twopass.stats;
       return 0;
     case TH_ENCCTL_THIP_GET_MODE_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_mode_stats)) return TH_EINVAL;
@@ -2371,37 +2011,25 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       else return TH_EINVAL;
       if (v < 0) return TH_EINVAL;
       if (v == 0) return TH_EIMPL;   // (leaving bitrate mode)
-      e->bitrate = (int64_t)v;
       e->rate = true;
       if (e->nheaders_out == 0) e->info.target_bitrate = (int)std::min(v, (long)((1 << 24) - 1));
-      if (e->rate_started) {
-        enc_rate_targets(e);
-        e->rF = std::min(e->rF, e->rR);
-      }
+      e->ratectl.set_bitrate(enc_stream(e), (int64_t)v);
       return 0;
     }
     case TH_ENCCTL_SET_RATE_FLAGS:
       if (!e->rate) return TH_EIMPL;
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      e->rate_flags = *(const int *)buf & (TH_RATECTL_DROP_FRAMES | TH_RATECTL_CAP_OVERFLOW | TH_RATECTL_CAP_UNDERFLOW);
+      e->ratectl.set_flags(*(const int *)buf);
       return 0;
-    case TH_ENCCTL_SET_RATE_BUFFER: {
+    case TH_ENCCTL_SET_RATE_BUFFER:
       if (!e->rate) return TH_EIMPL;
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
-      const int d = (int)rate_clamp(*(const int *)buf, 12, 256);
-      *(int *)buf = d;
-      e->rate_buf = d;
-      if (e->rate_started) {
-        e->rD = d;
-        enc_rate_targets(e);
-        e->rF = std::min(e->rF, e->rR);
-      }
+      *(int *)buf = e->ratectl.set_buffer(enc_stream(e), *(const int *)buf);
       return 0;
-    }
     case TH_ENCCTL_THIP_GET_RATE_STATS:
       if (!e->rate) return TH_EINVAL;
       if (!buf || buf_sz != sizeof(thip_enc_rate_stats)) return TH_EINVAL;
-      *(thip_enc_rate_stats *)buf = e->rstats;
+      *(thip_enc_rate_stats *)buf = e->ratectl.stats;
       return 0;
     case TH_ENCCTL_THIP_GET_INTER_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_inter_stats)) return TH_EINVAL;
