@@ -1042,6 +1042,46 @@ typedef struct thip_enc_skip_req {   /* 264 bytes */
 int thip_enc_skip_stage(const thip_enc_skip_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the level choice of th_encode_* (theoraenc_hip.h, "Level choice") on the caller's planes, words,
+ * tables and LEVELS: the same launch function th_encode_* calls behind its quantising kernels.  The levels are the caller's, so any
+ * pattern of levels can be put on any content.  dequant and bits are HOST memory, every other pointer is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*, src, src_pitch   as thip_enc_inter_stage takes them
+ *   classes   0: a key frame (every block INTRA and coded; prev, gold, words and cmap are not read and may be NULL); 2, 3: an inter
+ *             frame with prev, gold, ref_pitch and words as thip_enc_skip_stage takes them
+ *   nqis, dequant, bits, lambda, iscale   as thip_enc_skip_stage takes them (lambda: the unscaled lambda_b of every block, or -1)
+ *   weight    w, 0..64: lambda_q = (lambda_b w) >> 4
+ *   levels    IN and OUT, [nfrags][64] int16 (coded order, zig-zag): the choice is written over the AC levels of the coded blocks
+ *   qii       [nfrags] (coded order), each below nqis, or NULL: every block at qis[0]
+ *   cmap      [nfrags] (raster): 0 an uncoded block, which is left alone; with classes 0 not read
+ * Out, each optional, [nfrags] int64 in coded order, 0 for an uncoded block: jbefore = J of the levels as they came, jafter = J of
+ * the levels as they went, rate = R of the levels as they went.
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req, src, levels, a table, or with classes 2 / 3 prev, words or cmap NULL, or a HIP call failed.  THIP_EINVAL: the frame
+ * size, fragment count, pixel format, picture region, pitches and gold as thip_enc_skip_stage refuses them; classes not 0, 2 or 3;
+ * nqis outside 1..3; lambda outside -1..2^40; weight outside 0..64; a table entry outside 1..32767; a bits entry above 64; levels
+ * or words not 16-byte aligned (words 4-byte with classes 2), iscale not 2-byte, jbefore, jafter or rate not 8-byte -- all found
+ * before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+typedef struct thip_enc_rdq_req {   /* 248 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t classes, nqis, weight;
+  int64_t lambda;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  const uint8_t *prev[3], *gold[3];
+  int64_t ref_pitch[3];
+  const void *words;
+  const uint16_t *dequant;
+  const uint8_t *bits;
+  const uint16_t *iscale;
+  int16_t *levels;
+  const uint8_t *qii, *cmap;
+  int64_t *jbefore, *jafter, *rate;
+} thip_enc_rdq_req;
+int thip_enc_rdq_stage(const thip_enc_rdq_req *req);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

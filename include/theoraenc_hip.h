@@ -199,6 +199,34 @@
  *   - A frame with no coded block is the zero-byte packet, as ever.
  *   - No wait: two launches (the luma blocks, then the chroma blocks) stand in for the quantising kernel's one (thip_enc_skip_stats).
  *
+ * Level choice (TH_ENCCTL_THIP_SET_RD_QUANT = w), stated likewise (tests/enc_rdq_ref.py restates it).  After the frame's blocks have
+ * been quantised -- every level oc_enc_quantize(c), round to nearest -- it asks of each coded block which of its AC levels are worth
+ * their tokens (libtheora's oc_enc_tokenize_ac, tokenize.c:457-744, decides the same question).  Off (w = 0, the default) every packet
+ * is as without the call.  Integer arithmetic throughout, all of it 64-bit.
+ *   - Where it acts: on every coded block of every frame: all blocks of a key frame; on an inter frame the blocks with a coded flag,
+ *     after the mode decision, the block-qi choice and the skip decision, all three of which are made on the plain levels as ever.
+ *     With five or eight modes, block qi, masking, the rate-distortion mode decision, the skip decision, bitrate mode and two-pass (the
+ *     probe is unchanged; c_key and c_inter absorb it), automatic key frames, the device packetiser, the quality statistics, RGB and
+ *     device input.  It changes AC levels (z >= 1) of coded blocks only: never the DC, the block's qii, a coded flag, a mode or a
+ *     vector.  A block whose AC levels all become zero stays coded (an EOB at its first index).
+ *   - Per block: c the fDCT of the block's residual under the mode it was coded with (the chroma of a macro block none of whose luma
+ *     blocks is coded: against PREV at vector 0, as "Skip decision" has it); l its levels as the quantising kernel left them, the AC at
+ *     qis[k] of the block's qii k; s the steps of its table at qis[k].
+ *   - Candidates at z = 1..63: a level 0 stays 0; |l_z| = 1 may stay or become 0; |l_z| >= 2 may stay or become l_z - sgn(l_z).
+ *     a_z = 0 names the original, a_z = 1 the alternative; l' the levels under a.
+ *   - J(a) = sum over z >= 1 of (c_z - l'_z s_z)^2 + lambda_q R(l'), with R block qi's R_k: the AC tokens of l' from index 1 with the
+ *     block's own EOB, each its code length in the AC table of its start index's Huffman group for luma or chroma plus its extra bits,
+ *     the tables those the previous packet of the same frame type chose (5 before there is one); and lambda_q = (lambda_b w) >> 4
+ *     with lambda_b the block's lambda of "Skip decision": (s1 * s1 * 40) >> 7 from its table at qis[0], and where masking acts
+ *     (lambda i_b + 1024) >> 11.
+ *   - The block takes the a of least J(a); among those the first in lexicographic order of (a_1, ..., a_63): it rather keeps an earlier
+ *     coefficient as it is.  With lambda_q = 0 the block is left as it is (what the least J gives for levels rounded to nearest).
+ *     The minimum is exact: a level with |l| >= 2 stays non-zero under both candidates, so a backward programme over the non-zero
+ *     positions finds it -- F[i] the least cost of everything behind a kept position i, over the next kept position up to and
+ *     including the first with |l| >= 2, or over the block's EOB when only +-1 remain.
+ *   - No wait: one launch behind the frame's quantising (or skip) launches, in front of the DC and token kernels
+ *     (thip_enc_rd_quant_stats).
+ *
  * Bitrate mode (TH_ENCCTL_SET_BITRATE), stated so that a restatement reproduces the choices (tests/enc_rate_ref.py does).  Integer
  * arithmetic throughout; x >> 16 of a product is an arithmetic shift.
  *   - The probe.  Before a frame is coded (key or inter by the rule above), the device measures E[q], q = 0..63: the frame's bits
@@ -577,6 +605,30 @@ typedef struct thip_enc_skip_stats {   /* 40 bytes */
   int64_t lambda;         /* the frame's unscaled lambda: (s1 * s1 * 40) >> 7, s1 the inter luma step at zig-zag index 1 of qis[0] */
   double skip_ms;         /* HIP events around the two launches */
 } thip_enc_skip_stats;
+
+/* Extension: buf = int w: 0 off (the default: every packet as without the call), 1..64 the AC levels of coded blocks are chosen by the
+   least D + lambda R with lambda's weight w / 16 ("Level choice" above); any other value TH_EINVAL.  Before the first frame only (else
+   TH_EINVAL); the call never touches the GPU.  Recommended: 3 (DESIGN.md section 5.19 has the measurements). */
+#define TH_ENCCTL_THIP_SET_RD_QUANT (0x7222)
+/* Extension: buf = thip_enc_rd_quant_stats, describing the last packet th_encode_packetout returned (with the switch off too).  For a
+   frame not treated -- a duplicate, a dropped frame, a zero-byte packet, any frame with the switch off -- every field is 0 except
+   weight.  (0x7220 and 0x7221 are not used: unknown requests, TH_EIMPL.) */
+#define TH_ENCCTL_THIP_GET_RD_QUANT_STATS (0x7223)
+typedef struct thip_enc_rd_quant_stats {   /* 88 bytes */
+  int32_t weight;         /* the switch: w */
+  int32_t measured;       /* 1: the frame's coded blocks went through the choice */
+  int32_t zeroed[3];      /* per plane: levels +-1 that became 0 */
+  int32_t lowered[3];     /* per plane: levels with |l| >= 2 that became l - sgn(l) */
+  int32_t emptied;        /* coded blocks that had a non-zero AC level and were left with none */
+  int32_t reserved;
+  int64_t rate_before;    /* the sums over the coded blocks of R(l) and R(l'), */
+  int64_t rate_after;
+  int64_t dist_before;    /* ... and of sum over z >= 1 of (c_z - l_z s_z)^2 with l and with l' */
+  int64_t dist_after;
+  int64_t lambda;         /* the frame's unscaled lambda: (s1 * s1 * 40) >> 7, s1 the luma step at zig-zag index 1 of qis[0] in the
+                             frame's own tables (intra on a key frame, inter on an inter frame) */
+  double rdq_ms;          /* HIP events around the launch */
+} thip_enc_rd_quant_stats;
 
 /* Extension: the first pass of "Two-pass" above, with TH_ENCCTL_2PASS_OUT's calling convention: buf = unsigned char **, buf_sz ==
    sizeof(unsigned char *) (else TH_EINVAL).  The first call must come before the first frame (else TH_EINVAL; TH_EINVAL too on a

@@ -147,6 +147,17 @@ class EncSkipReq(C.Structure):
                 ("skf", C.c_void_p), ("dcode", C.c_void_p), ("rate", C.c_void_p), ("dskip", C.c_void_p)]
 
 
+class EncRdqReq(C.Structure):
+    """thip_enc_rdq_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
+                ("classes", C.c_int32), ("nqis", C.c_int32), ("weight", C.c_int32), ("lam", C.c_int64),
+                ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("prev", C.c_void_p * 3), ("gold", C.c_void_p * 3),
+                ("ref_pitch", C.c_int64 * 3), ("words", C.c_void_p), ("dequant", C.c_void_p), ("bits", C.c_void_p),
+                ("iscale", C.c_void_p), ("levels", C.c_void_p), ("qii", C.c_void_p), ("cmap", C.c_void_p),
+                ("jbefore", C.c_void_p), ("jafter", C.c_void_p), ("rate", C.c_void_p)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -253,6 +264,7 @@ SYMBOLS = [
     ("thip_enc_mask_stage", _I, [C.POINTER(EncMaskReq)]),
     ("thip_enc_rd_stage", _I, [C.POINTER(EncRdReq)]),
     ("thip_enc_skip_stage", _I, [C.POINTER(EncSkipReq)]),
+    ("thip_enc_rdq_stage", _I, [C.POINTER(EncRdqReq)]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

@@ -38,6 +38,7 @@
 #include "thip_encode_mask.h"
 #include "thip_encode_rd.h"
 #include "thip_encode_skip.h"
+#include "thip_encode_rdq.h"
 #include "thip_encode_pack.h"
 #include "thip_encode_cut.h"
 #include "thip_bitstream.h"
@@ -301,6 +302,14 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint8_t *d_skf = nullptr, *h_skf = nullptr;
   hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;
   thip_enc_skip_stats sstats;
+  // the level choice (TH_ENCCTL_THIP_SET_RD_QUANT; thip_encode_rdq.h): its weight (0: off); the frame queued went through it
+  // (rdq_queued) with the unscaled lambda rdq_lam; the frame's sums (RdqOut::sums) on the device and where they are read back
+  int rdq = 0;
+  bool rdq_queued = false;
+  int64_t rdq_lam = 0;
+  unsigned long long *d_rdqsums = nullptr, *h_rdqsums = nullptr;
+  hipEvent_t ev_z0 = nullptr, ev_z1 = nullptr;
+  thip_enc_rd_quant_stats zstats;
   // bitrate mode (TH_ENCCTL_SET_BITRATE): the controller (thip_ratectl.h) and the probe's device state
   bool rate = false, rate_dropped = false, rate_dev = false;
   RateCtl ratectl;
@@ -393,6 +402,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->kstats, 0, sizeof(e->kstats));
   memset(&e->dstats, 0, sizeof(e->dstats));
   memset(&e->sstats, 0, sizeof(e->sstats));
+  memset(&e->zstats, 0, sizeof(e->zstats));
   memset(&e->pstats, 0, sizeof(e->pstats));
   memset(&e->cnext, 0, sizeof(e->cnext));
   memset(&e->cstats, 0, sizeof(e->cstats));
@@ -422,6 +432,7 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_act, (void **)&e->d_mpart, (void **)&e->d_iscale,                                               // enc_mask_queue
       (void **)&e->d_cand, (void **)&e->d_rdbits,                                                                    // enc_rd_queue
       (void **)&e->d_skf,                                                                                            // enc_skip_queue
+      (void **)&e->d_rdqsums,                                                                                        // enc_rdq_queue
       (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
       (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
@@ -438,6 +449,7 @@ static void enc_free_device(th_enc_ctx *e) {
                    (void **)&e->h_mb4,                                            // enc_modes_alloc
                    (void **)&e->h_qii,                                            // enc_bqi_prepare
                    (void **)&e->h_skf,                                            // enc_skip_queue
+                   (void **)&e->h_rdqsums,                                        // enc_rdq_queue
                    (void **)&e->h_rest,                                           // enc_rate_alloc
                    (void **)&e->h_pk, (void **)&e->h_prec,                        // enc_pack_alloc
                    (void **)&e->h_cut,                                            // enc_cut_alloc
@@ -455,9 +467,11 @@ static void enc_free_device(th_enc_ctx *e) {
   e->mask_queued = false;
   e->rd_queued = false;
   e->skip_queued = false;
+  e->rdq_queued = false;
   e->probe_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
-                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1, &e->ev_s0, &e->ev_s1}) {
+                          &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1, &e->ev_s0, &e->ev_s1,
+                          &e->ev_z0, &e->ev_z1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -582,13 +596,14 @@ static int enc_ref_frame(th_enc_ctx *e, EncRef &R, int which = THIP_FRAME_PREV) 
 
 // the frame's qi list (theoraenc_hip.h, "Block-level qi"; one qi with block qi off) and, with block qi on, the selection of the
 // block-qi kernels (thip_encode_bqi.h); their buffers at the first such frame (TH_ENCCTL_THIP_SET_BLOCK_QI never touches the GPU).
-// An inter frame with the skip decision on runs the same selection, with a one-entry list where block qi is off
+// An inter frame with the skip decision on, and any frame with the level choice on, runs the same selection, with a one-entry list
+// where block qi is off
 static int enc_bqi_prepare(th_enc_ctx *e, BqiSel &sel) {
   const int q0 = e->frame_qi;
   e->fnqis = 1;
   e->fqis[0] = q0;
   e->fqis[1] = e->fqis[2] = 0;
-  if (!e->bqi && !(e->skip && !e->frame_key)) return 0;
+  if (!e->bqi && !(e->skip && !e->frame_key) && !e->rdq) return 0;
   const int coarse = std::max(q0 - e->bqi, 0), fine = std::min(q0 + e->bqi, 63);
   if (coarse != q0) e->fqis[e->fnqis++] = coarse;   // (block qi off: q0 alone)
   if (fine != q0 && fine != coarse) e->fqis[e->fnqis++] = fine;
@@ -721,6 +736,55 @@ static void enc_skip_stats(th_enc_ctx *e, bool queued) {
   e->sstats.skip_ms = hipEventElapsedTime(&ms, e->ev_s0, e->ev_s1) == hipSuccess ? ms : 0.0;
 }
 
+// the level choice (thip_encode_rdq.h): its launch behind the frame's quantising (or skip) launches and in front of the DC and token
+// kernels, between HIP events; classes 0 for a key frame.  The kernel reads the source once more: the caller records "the planes have
+// been read" behind it.  The sums and the events at the first such frame (TH_ENCCTL_THIP_SET_RD_QUANT never touches the GPU); no
+// host wait
+extern "C++" template <class Word>
+static int enc_rdq_queue(th_enc_ctx *e, int classes, const EncPlanes &g, const BqiSel &sel, const Word *d_mb, const EncRef &R, const EncRef &G) {
+  if (!e->rdq) return 0;
+  if (!e->d_rdqsums) {
+    for (hipEvent_t *ev : {&e->ev_z0, &e->ev_z1})
+      if (!*ev) ENC_TRY(hipEventCreate(ev));
+    ENC_TRY(hipMalloc((void **)&e->d_rdqsums, kRdqSums * sizeof(unsigned long long)));
+    ENC_TRY(hipHostMalloc((void **)&e->h_rdqsums, kRdqSums * sizeof(unsigned long long), hipHostMallocDefault));
+  }
+  uint16_t step[64];
+  compute_qmat(e->setup.qp, classes ? 1 : 0, 0, e->frame_qi, step);
+  e->rdq_lam = rd_lambda(step[1]);
+  // the quantising kernel wrote qii with block qi on, and the skip launches always do
+  const uint8_t *qii = e->bqi || e->skip_queued ? e->d_qii : nullptr;
+  ENC_TRY(hipEventRecord(e->ev_z0, e->stream));
+  ENC_TRY(hipMemsetAsync(e->d_rdqsums, 0, kRdqSums * sizeof(unsigned long long), e->stream));
+  ENC_TRY(rdq_launch(classes, e->d_levels, qii, e->d_cmap, RdqOut{nullptr, nullptr, nullptr, e->d_rdqsums}, e->d_order, g, R, G, d_mb,
+                     e->nmbx, classes ? e->d_dqi : e->d_dequant, classes ? 6 : 3, e->d_bqbits, sel,
+                     e->mask_queued ? (const uint16_t *)e->d_iscale : nullptr, -1, e->rdq, e->nfrags, e->stream));
+  ENC_TRY(hipEventRecord(e->ev_z1, e->stream));
+  e->rdq_queued = true;
+  return 0;
+}
+
+// the last packet's thip_enc_rd_quant_stats: those of a frame not treated, or (queued: after the frame's wait) the frame's own sums
+static void enc_rdq_stats(th_enc_ctx *e, bool queued) {
+  memset(&e->zstats, 0, sizeof(e->zstats));
+  e->zstats.weight = e->rdq;
+  if (!queued) return;
+  float ms = 0;
+  const unsigned long long *s = e->h_rdqsums;
+  e->zstats.measured = 1;
+  for (int p = 0; p < 3; p++) {
+    e->zstats.zeroed[p] = (int32_t)s[kRdqZeroed + p];
+    e->zstats.lowered[p] = (int32_t)s[kRdqLowered + p];
+  }
+  e->zstats.emptied = (int32_t)s[kRdqEmptied];
+  e->zstats.rate_before = (int64_t)s[kRdqRateBefore];
+  e->zstats.rate_after = (int64_t)s[kRdqRateAfter];
+  e->zstats.dist_before = (int64_t)s[kRdqDistBefore];
+  e->zstats.dist_after = (int64_t)s[kRdqDistAfter];
+  e->zstats.lambda = e->rdq_lam;
+  e->zstats.rdq_ms = hipEventElapsedTime(&ms, e->ev_z0, e->ev_z1) == hipSuccess ? ms : 0.0;
+}
+
 // ---- the device packetiser (thip_encode_pack.h) ----------------------------------------------------------------------------------
 // its buffers and tables, at the first frame that needs them.  The packet buffer holds 128 bytes a block -- 16 bits a coefficient,
 // twice the raw picture; the natural image of tools/encode_time.py takes 9.5 bytes a block at quality 48 -- where the worst case, 65
@@ -793,6 +857,8 @@ static int enc_queue_tail(th_enc_ctx *e) {
   }
   if (e->bqi) ENC_TRY(hipMemcpyAsync(e->h_qii, e->d_qii, (size_t)n, hipMemcpyDeviceToHost, e->stream));
   if (e->skip_queued) ENC_TRY(hipMemcpyAsync(e->h_skf, e->d_skf, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  if (e->rdq_queued)
+    ENC_TRY(hipMemcpyAsync(e->h_rdqsums, e->d_rdqsums, kRdqSums * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_done, e->stream));
   if (enc_pack_queue(e)) return TH_EFAULT;
   enc_frame_queued(e);
@@ -847,7 +913,11 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
     ENC_TRY(inter_launch_fq(InterBufs{e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192}, e->d_order, g, R, gold...,
                             (const Word *)d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n, e->stream));
   }
-  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+  {
+    const EncRef *G[] = {&R, &gold...};
+    if (enc_rdq_queue(e, classes, g, sel, (const Word *)d_mb, R, *G[sizeof...(Gold)])) return TH_EFAULT;
+  }
+  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the level choice reads them too)
   if constexpr (classes == 3) ENC_TRY(inter_launch_dc3(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
   else ENC_TRY(inter_launch_dc(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
   hipLaunchKernelGGL(k_enc_inter_tok, gch, wg, 0, e->stream, e->d_tok, e->d_mask, e->d_cnt, e->d_small + 192, e->d_levels, e->d_dcr,
@@ -1016,6 +1086,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   e->mask_queued = false;   // (enc_mask_queue says otherwise; a dropped frame never gets there)
   e->rd_queued = false;     // (enc_rd_queue likewise)
   e->skip_queued = false;   // (enc_skip_queue likewise)
+  e->rdq_queued = false;    // (enc_rdq_queue likewise)
   if (!e->rate) e->frame_qi = e->qi;   // (bitrate mode: the controller's choice, below)
   // a key frame: the first, every kf_interval-th (duplicates counted), and one whose duplicates would reach 1 << shift
   const int64_t f = e->cur + 1, off = f - e->key, full = (int64_t)1 << e->info.keyframe_granule_shift;
@@ -1077,7 +1148,8 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
     hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
                        e->d_small + 192, e->d_order, g, e->d_dequant + (size_t)e->frame_qi * 192, n);
   ENC_TRY(hipGetLastError());
-  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read
+  if (enc_rdq_queue(e, 0, g, sel, (const uint32_t *)nullptr, EncRef{}, EncRef{})) return TH_EFAULT;
+  ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the level choice reads them too)
   hipLaunchKernelGGL(k_enc_intra_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
                      e->d_small + 192, e->d_levels, e->d_dcq, e->d_order, g, n);
   ENC_TRY(hipGetLastError());
@@ -1396,6 +1468,7 @@ static void enc_empty_packet(th_enc_ctx *e) {
   enc_mask_stats(e, false);
   enc_rd_stats(e, false);
   enc_skip_stats(e, false);
+  enc_rdq_stats(e, false);
 }
 
 // the packet of no frame of its own (one the rate controller dropped, a duplicate): empty, and no packer, search or mode choice ran
@@ -1611,6 +1684,7 @@ static int enc_finish_frame(th_enc_ctx *e) {
   enc_mask_stats(e, e->mask_queued);   // (an empty packet takes them back)
   enc_rd_stats(e, e->rd_queued);
   enc_skip_stats(e, e->skip_queued);
+  enc_rdq_stats(e, e->rdq_queued);
   const int rc = e->frame_dpack ? enc_pack_device(e, total, overflow) : enc_pack_host(e, total, overflow);
   e->pstats.fallbacks = e->pack_fallbacks;
   return rc;
@@ -1935,6 +2009,15 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->sstats.on = v;
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_RD_QUANT: {
+      if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
+      if (e->cur >= 0 || e->frame_pending || e->done) return TH_EINVAL;   // before the first frame only
+      const int v = *(const int *)buf;
+      if (v < 0 || v > 64) return TH_EINVAL;
+      e->rdq = v;   // (its buffers are made at the first frame that uses it)
+      e->zstats.weight = v;
+      return 0;
+    }
     case TH_ENCCTL_THIP_SET_DEVICE_PACK: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       const int v = *(const int *)buf;
@@ -1985,6 +2068,10 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
     case TH_ENCCTL_THIP_GET_SKIP_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_skip_stats)) return TH_EINVAL;
       *(thip_enc_skip_stats *)buf = e->sstats;
+      return 0;
+    case TH_ENCCTL_THIP_GET_RD_QUANT_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_rd_quant_stats)) return TH_EINVAL;
+      *(thip_enc_rd_quant_stats *)buf = e->zstats;
       return 0;
     case TH_ENCCTL_THIP_2PASS_OUT: {
       if (buf_sz != sizeof(unsigned char *)) return TH_EINVAL;
@@ -2408,6 +2495,92 @@ int thip_enc_skip_stage(const thip_enc_skip_req *q) {
   else
     ENC_TRY(skip_launch(o, q->qii, so, (const int32_t *)(d + o_order), g, R, G, (const uint32_t *)q->words, nmbx,
                         (const uint16_t *)(d + o_dq), d + o_bits, sel, q->iscale, q->lambda, n, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the level choice on the caller's planes, words, tables and levels (theora_hip.h): thip_encode_rdq.h's launch function, as
+// enc_rdq_queue makes it, on the current device's null stream
+int thip_enc_rdq_stage(const thip_enc_rdq_req *q) {
+  if (!q) return THIP_EFAULT;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  if (q->classes != 0 && q->classes != 2 && q->classes != 3) return THIP_EINVAL;
+  const bool all = q->classes == 3, key = q->classes == 0;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
+  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+    return THIP_EINVAL;
+  int ngold = 0;
+  for (int p = 0; p < 3; p++) {
+    if (!q->src[p] || (!key && !q->prev[p])) return THIP_EFAULT;
+    ngold += q->gold[p] != nullptr;
+  }
+  if (!key && ngold != (all ? 3 : 0)) return all && ngold < 3 ? THIP_EFAULT : THIP_EINVAL;
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
+    if (q->src_pitch[p] < pw) return THIP_EINVAL;
+    if (!key && (q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF)) return THIP_EINVAL;
+  }
+  if (q->nqis < 1 || q->nqis > 3 || q->lambda < -1 || q->lambda > ((int64_t)1 << 40) || q->weight < 0 || q->weight > 64) return THIP_EINVAL;
+  if (!q->dequant || !q->bits || !q->levels || (!key && (!q->words || !q->cmap))) return THIP_EFAULT;
+  for (int k = 0; k < q->nqis * 384; k++)
+    if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
+  for (int k = 0; k < 256; k++)
+    if (q->bits[k] > 64) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if ((!key && misaligned(q->words, all ? 16 : 4)) || misaligned(q->levels, 16) || misaligned(q->iscale, 2) || misaligned(q->jbefore, 8) ||
+      misaligned(q->jafter, 8) || misaligned(q->rate, 8))
+    return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int64_t n = geo.nfrags;
+  const int nmbx = geo.nh[0] >> 1;
+  EncPlanes g = {};
+  EncRef R = {}, G = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.src[p] = q->src[p];
+    g.stride[p] = q->src_pitch[p];
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+    if (key) continue;
+    R.plane[p] = q->prev[p];
+    G.plane[p] = all ? q->gold[p] : q->prev[p];
+    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
+    R.w[p] = G.w[p] = geo.nh[p] * 8;
+    R.h[p] = G.h[p] = geo.nv[p] * 8;
+  }
+  R.hdec = G.hdec = hdec;
+  R.vdec = G.vdec = vdec;
+  // one allocation: order [n] | dequant [nqis][384] | bits [256]
+  const size_t o_dq = (size_t)n * 4, o_bits = o_dq + (size_t)q->nqis * 768;
+  uint8_t *d = nullptr;
+  ENC_TRY(hipMalloc((void **)&d, o_bits + 256));
+  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  hipStream_t stream = nullptr;
+  ENC_TRY(hipMemcpy(d, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(d + o_dq, q->dequant, (size_t)q->nqis * 768, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(d + o_bits, q->bits, 256, hipMemcpyHostToDevice));
+  // (the caller's tables are qi 0, 1, 2 of the kernel's table set and AC tables 0, 1 of its bits)
+  const RdqOut out{q->jbefore, q->jafter, q->rate, nullptr};
+  const BqiSel sel{q->nqis, 0, 1, 2, 0, 1};
+  if (all)
+    ENC_TRY(rdq_launch(3, q->levels, q->qii, q->cmap, out, (const int32_t *)d, g, R, G, (const uint4 *)q->words, nmbx,
+                       (const uint16_t *)(d + o_dq), 6, d + o_bits, sel, q->iscale, q->lambda, q->weight, n, stream));
+  else
+    ENC_TRY(rdq_launch(q->classes, q->levels, q->qii, q->cmap, out, (const int32_t *)d, g, R, G, (const uint32_t *)q->words, nmbx,
+                       (const uint16_t *)(d + o_dq), 6, d + o_bits, sel, q->iscale, q->lambda, q->weight, n, stream));
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

@@ -43,6 +43,9 @@ TH_ENCCTL_THIP_2PASS_IN = 0x721B
 TH_ENCCTL_THIP_GET_2PASS_STATS = 0x721C
 TH_ENCCTL_THIP_SET_RD_SKIP = 0x721E
 TH_ENCCTL_THIP_GET_SKIP_STATS = 0x721F
+TH_ENCCTL_THIP_SET_RD_QUANT = 0x7222   # (0x7220 and 0x7221 are not used)
+TH_ENCCTL_THIP_GET_RD_QUANT_STATS = 0x7223
+RD_QUANT_DEFAULT = 3   # the recommended weight w (lambda's weight w / 16): include/theoraenc_hip.h, "Level choice"
 TWO_PASS_HEADER_BYTES, TWO_PASS_RECORD_BYTES = 1084, 264   # THIP_2PASS_HEADER_BYTES, THIP_2PASS_RECORD_BYTES
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
 AUTO_KEYFRAMES_DEFAULT = 230   # the recommended ratio t (t / 256 = 0.9): include/theoraenc_hip.h, "Automatic key frames"
@@ -124,6 +127,13 @@ class SkipStats(C.Structure):
                 ("skip_ms", C.c_double)]
 
 
+class RdQuantStats(C.Structure):
+    """thip_enc_rd_quant_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("weight", C.c_int32), ("measured", C.c_int32), ("zeroed", C.c_int32 * 3), ("lowered", C.c_int32 * 3),
+                ("emptied", C.c_int32), ("reserved", C.c_int32), ("rate_before", C.c_int64), ("rate_after", C.c_int64),
+                ("dist_before", C.c_int64), ("dist_after", C.c_int64), ("lam", C.c_int64), ("rdq_ms", C.c_double)]
+
+
 class TwoPassStats(C.Structure):
     """thip_enc_2pass_stats (include/theoraenc_hip.h)."""
     _fields_ = [("pass_", C.c_int32), ("type", C.c_int32), ("frame", C.c_int64), ("qi", C.c_int32), ("reserved", C.c_int32),
@@ -163,7 +173,8 @@ class Encoder:
 
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
-                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False, rd_skip=False):
+                 block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False, rd_skip=False,
+                 rd_quant=0):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -177,7 +188,9 @@ class Encoder:
         None, False or 0 leave it off.  No effect without inter=True.  masking: activity masking with that ratio, 2..16
         (TH_ENCCTL_THIP_SET_MASKING; 0 off; recommended 4).  No effect without block_qi.  rd_modes: the macro-block modes of
         eight-mode inter frames by the least D + lambda R (TH_ENCCTL_THIP_SET_RD_MODES).  No effect without all_modes.  rd_skip: coded
-        blocks of inter frames are left uncoded where that costs less (TH_ENCCTL_THIP_SET_RD_SKIP).  No effect without inter."""
+        blocks of inter frames are left uncoded where that costs less (TH_ENCCTL_THIP_SET_RD_SKIP).  No effect without inter.
+        rd_quant: the AC levels of coded blocks by the least D + lambda R with lambda's weight rd_quant / 16, 1..64
+        (TH_ENCCTL_THIP_SET_RD_QUANT; 0 off; True for the recommended RD_QUANT_DEFAULT)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -219,6 +232,9 @@ class Encoder:
         self.rd_skip = False
         if rd_skip:
             self.set_rd_skip(rd_skip)
+        self.rd_quant = 0
+        if rd_quant:
+            self.set_rd_quant(RD_QUANT_DEFAULT if rd_quant is True else rd_quant)
         if device_pack is not None:
             self.set_device_pack(device_pack)
         self.auto_keyframes = AUTO_KEYFRAMES_DEFAULT if auto_keyframes is True else int(auto_keyframes or 0)
@@ -286,6 +302,23 @@ class Encoder:
             raise TheoraHipError("TH_ENCCTL_THIP_GET_SKIP_STATS returned %d" % rc)
         d = {k: getattr(s, k) for k, _ in SkipStats._fields_}
         d["skipped"] = list(s.skipped)
+        return d
+
+    def set_rd_quant(self, w):
+        """TH_ENCCTL_THIP_SET_RD_QUANT, before the first frame: the level choice with weight w (1..64), or off (0)."""
+        rc, _ = self.ctl(TH_ENCCTL_THIP_SET_RD_QUANT, int(w))
+        if rc < 0:
+            raise ValueError("rd_quant is 0..64, set before the first frame (TH_ENCCTL_THIP_SET_RD_QUANT returned %d)" % rc)
+        self.rd_quant = int(w)
+
+    def rd_quant_stats(self):
+        """TH_ENCCTL_THIP_GET_RD_QUANT_STATS of the last packet, as a dict (lam: the struct's lambda; without reserved)."""
+        s = RdQuantStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_RD_QUANT_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_RD_QUANT_STATS returned %d" % rc)
+        d = {k: getattr(s, k) for k, _ in RdQuantStats._fields_ if k != "reserved"}
+        d["zeroed"], d["lowered"] = list(s.zeroed), list(s.lowered)
         return d
 
     def set_device_pack(self, on):
@@ -719,6 +752,36 @@ def skip_stage(frame, pixel_fmt, classes, nqis, pic=None, lam=-1, src=None, src_
     q.words, q.iscale, q.levels, q.dcq, q.qii, q.cmap, q.skf = words, iscale, levels, dcq, qii, cmap, skf
     q.dcode, q.rate, q.dskip = dcode, rate, dskip
     return L.thip_enc_skip_stage(C.byref(q))
+
+
+def rdq_stage(frame, pixel_fmt, classes, nqis, weight, pic=None, lam=-1, src=None, src_pitch=None, prev=None, gold=None,
+              ref_pitch=None, words=None, dequant=None, bits=None, iscale=None, levels=None, qii=None, cmap=None, jbefore=None,
+              jafter=None, rate=None):
+    """thip_enc_rdq_stage (include/theora_hip.h): the level choice on the caller's planes, words, tables and levels, a test and
+    diagnostic entry.  classes: 0 (a key frame: prev, gold, words, cmap unused), 2 or 3; weight: w; levels: device address, in and
+    out; the rest as skip_stage takes them.  Returns the entry's return code; nothing is raised."""
+    L = _lib.load()
+    q = _lib.EncRdqReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.classes, q.nqis, q.weight, q.lam = int(classes), int(nqis), int(weight), int(lam)
+    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
+        for p in range(3):
+            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
+    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
+        for p in range(3):
+            getattr(q, name)[p] = 0 if v is None else int(v[p])
+    keep = []
+    for name, v, t, size in (("dequant", dequant, np.uint16, 384 * int(nqis)), ("bits", bits, np.uint8, 256)):
+        if v is not None:
+            a = np.ascontiguousarray(v, t).reshape(-1)
+            if a.size != size and not (name == "dequant" and not 1 <= int(nqis) <= 3):   # (an nqis the entry refuses: its refusal)
+                raise ValueError("rdq_stage: %s of %d entries where %d are expected" % (name, a.size, size))
+            keep.append(a)
+            setattr(q, name, a.ctypes.data)
+    q.words, q.iscale, q.levels, q.qii, q.cmap = words, iscale, levels, qii, cmap
+    q.jbefore, q.jafter, q.rate = jbefore, jafter, rate
+    return L.thip_enc_rdq_stage(C.byref(q))
 
 
 def rate_groups(nfrags):

@@ -27,6 +27,9 @@ With --rd-modes (with --inter N --all-modes): the eight-mode cases run with the 
 (TH_ENCCTL_THIP_SET_RD_MODES); rd_ms is the device time of its two launches (TH_ENCCTL_THIP_GET_RD_STATS), which device_ms includes.
 --rd-skip: with --inter, every case with the skip decision on (TH_ENCCTL_THIP_SET_RD_SKIP); skip_ms is the device time of its two
 launches (TH_ENCCTL_THIP_GET_SKIP_STATS), which device_ms includes.
+--rd-quant W: every case (key-only and --inter) with the level choice on at weight W (TH_ENCCTL_THIP_SET_RD_QUANT); rdq_ms is the
+device time of its launch (TH_ENCCTL_THIP_GET_RD_QUANT_STATS), which device_ms includes, rdq_zeroed / rdq_lowered the levels it changed
+a frame.
 Switch off and on are two runs of the tool.
 
 With --two-pass (with --bitrate B for the second pass's target, default 8 Mbit/s; --inter N as with --bitrate): per size and frame
@@ -35,7 +38,7 @@ waits in quality mode, first pass or not), call_ms the whole call with th_encode
 p1_wait_ms the host's wait in th_encode_packetout for its 512 bytes (TH_ENCCTL_THIP_GET_2PASS_STATS) -- and then the second pass over
 that pass file (p2_*; its probe is waited for, as in bitrate mode).
 
-  python tools/encode_time.py [--two-pass] [--frames 20] [--inter N [--all-modes [--rd-modes]] [--rd-skip]] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
+  python tools/encode_time.py [--two-pass] [--frames 20] [--inter N [--all-modes [--rd-modes]] [--rd-skip]] [--rd-quant W] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
                               [--auto-keyframes [T]] [--json out.json]
 """
 import argparse
@@ -83,6 +86,7 @@ def main():
     ap.add_argument("--masking", type=int, default=0, help="with --block-qi: activity masking at this ratio (TH_ENCCTL_THIP_SET_MASKING)")
     ap.add_argument("--rd-modes", action="store_true", help="with --inter --all-modes: the eight-mode cases with TH_ENCCTL_THIP_SET_RD_MODES on")
     ap.add_argument("--rd-skip", action="store_true", help="with --inter: every case with TH_ENCCTL_THIP_SET_RD_SKIP on")
+    ap.add_argument("--rd-quant", type=int, default=0, metavar="W", help="every case with TH_ENCCTL_THIP_SET_RD_QUANT = W (1..64)")
     ap.add_argument("--device-pack", action="store_true", help="each case with the device packetiser off, then on")
     ap.add_argument("--auto-keyframes", type=int, nargs="?", const=230, default=0, metavar="T",
                     help="with --inter or --bitrate: each case with automatic key frames off, then on at ratio T (default 230)")
@@ -102,9 +106,9 @@ def main():
         p = pic or (0, 0, w, h)
         frame = enc_ref.picture("natural", w, h, 0, p, picture_size=True, seed=5)
         for q, dp in [(q, dp) for q in (16, 48) for dp in ((False, True) if args.device_pack else (False,))]:
-            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking)
+            e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking, rd_quant=args.rd_quant)
             hdr = e.header_packets()
-            dev, host, wall, pack, mask = [], [], [], [], []
+            dev, host, wall, pack, mask, zqms = [], [], [], [], [], []
             for f in range(args.frames + 3):
                 t0 = time.perf_counter()
                 e.encode(frame)
@@ -117,9 +121,11 @@ def main():
                     wall.append((t1 - t0) * 1e3)
                     pack.append(e.pack_stats()["pack_ms"])
                     mask.append(e.mask_stats()["mask_ms"])
+                    zqms.append(e.rd_quant_stats()["rdq_ms"])
             st = e.stats()
             e.close()
-            qs = quality_pass([frame], w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking)[0]
+            qs = quality_pass([frame], w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking,
+                              rd_quant=args.rd_quant)[0]
             ps = [round(psnr(qs["sse"][pl], qs["samples"][pl]), 2) for pl in range(3)]
             r = dict(size=name, quality=q, device_ms=round(float(np.median(dev)), 4), host_ms=round(float(np.median(host)), 4),
                      call_ms=round(float(np.median(wall)), 4), bytes=len(pkt), tokens=st["tokens"],
@@ -129,6 +135,8 @@ def main():
                          call_spread=[round(float(min(wall)), 4), round(float(max(wall)), 4)])
             if args.masking:
                 r.update(masking=args.masking, mask_ms=round(float(np.median(mask)), 4))
+            if args.rd_quant:
+                r.update(rd_quant=args.rd_quant, rdq_ms=round(float(np.median(zqms)), 4))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
@@ -148,9 +156,10 @@ def main_inter(args):
                               for dp in ((False, True) if args.device_pack else (False,))
                               for ak in ((0, args.auto_keyframes) if args.auto_keyframes else (0,))]:
             e = Encoder(w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am, block_qi=args.block_qi,
-                        device_pack=dp, auto_keyframes=ak, masking=args.masking, rd_modes=args.rd_modes and am, rd_skip=args.rd_skip)
+                        device_pack=dp, auto_keyframes=ak, masking=args.masking, rd_modes=args.rd_modes and am, rd_skip=args.rd_skip,
+                        rd_quant=args.rd_quant)
             hdr = e.header_packets()
-            dev, host, wall, pkts, keys, pack, meas, cuts, mask, rdms, skms = [], [], [], [], 0, [], [], 0, [], [], []
+            dev, host, wall, pkts, keys, pack, meas, cuts, mask, rdms, skms, zqms, zq0, zq1 = [], [], [], [], 0, [], [], 0, [], [], [], [], [], []
             for f in range(n):
                 t0 = time.perf_counter()
                 e.encode(frames[f])
@@ -168,13 +177,17 @@ def main_inter(args):
                     mask.append(e.mask_stats()["mask_ms"])
                     rdms.append(e.rd_stats()["rd_ms"])
                     skms.append(e.skip_stats()["skip_ms"])
+                    zq = e.rd_quant_stats()
+                    zqms.append(zq["rdq_ms"])
+                    zq0.append(sum(zq["zeroed"]))
+                    zq1.append(sum(zq["lowered"]))
                 keys += key
                 cuts += e.cut_stats()["cut"]
             e.close()
             ps = [psnr(qs["sse"][0], qs["samples"][0])
                   for qs in quality_pass(frames, w, h, 0, q, pic=pic, inter=True, keyframe_interval=args.inter, all_modes=am,
                                          block_qi=args.block_qi, device_pack=dp, auto_keyframes=ak, masking=args.masking,
-                                         rd_modes=args.rd_modes and am, rd_skip=args.rd_skip)]
+                                         rd_modes=args.rd_modes and am, rd_skip=args.rd_skip, rd_quant=args.rd_quant)]
             r = dict(size=name, quality=q, inter=args.inter, all_modes=am, key_frames=keys, device_ms=round(float(np.median(dev)), 4),
                      host_ms=round(float(np.median(host)), 4), call_ms=round(float(np.median(wall)), 4),
                      bytes=int(np.mean([len(x) for x in pkts])), psnr_y=round(float(np.mean(ps)), 2))
@@ -189,6 +202,9 @@ def main_inter(args):
                 r.update(rd_modes=bool(am), rd_ms=round(float(np.median(rdms)), 4))
             if args.rd_skip:
                 r.update(rd_skip=True, skip_ms=round(float(np.median(skms)), 4))
+            if args.rd_quant:
+                r.update(rd_quant=args.rd_quant, rdq_ms=round(float(np.median(zqms)), 4), rdq_zeroed=int(np.mean(zq0)),
+                         rdq_lowered=int(np.mean(zq1)))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
