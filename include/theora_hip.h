@@ -1082,6 +1082,52 @@ typedef struct thip_enc_rdq_req {   /* 248 bytes */
 int thip_enc_rdq_stage(const thip_enc_rdq_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the tokeniser of th_encode_* on the caller's levels, DCs and map -- the same launch functions
+ * th_encode_* calls between its quantising kernels and its packetiser (thip_enc_pack_tokens), with every intermediate result handed
+ * out.  Every pointer is DEVICE memory.
+ *   frame_*, pixel_fmt   as thip_enc_inter_stage takes them; nfrags follows, nchunks = ceil(nfrags / 256).  The coded order is the
+ *             library's own, the one th_encode_* walks
+ *   classes   0: a key frame; 2, 3: an inter frame (the tokeniser asks only whether a block's cmap is zero)
+ *   levels    int16 [nfrags][64], coded order, zig-zag
+ *   dcq       int16 [nfrags], raster: a key frame's quantised DCs.  A block's predictor (spec 7.8) is formed from its neighbours'
+ *             dcq, and its OWN DC is read from levels[k][0]: the quantising kernels keep the two equal, a caller need not
+ *   dcr, cmap int16, uint8 [nfrags], raster: an inter frame's DC residuals and its map (0: the block is not coded; its levels and
+ *             dcr are not read, its mask is 0 and its tok words are left alone)
+ *   stages    what to run, an OR of these, run in this order; each reads the caller's buffers, whichever other stages ran
+ *     THIP_ENC_TOK_TOK      reads levels and dcq (inter: dcr, cmap); writes tok, uint32 [nfrags][65]: block k's tokens from word 65 k
+ *                           on (token | extra bits << 5 | index << 16 | plane << 22; an EOB is token 0), the words behind them left
+ *                           alone; mask, uint64 [nfrags]: the indices at which block k's tokens start; chunk_cnt, uint32
+ *                           [nchunks][3][64]: the tokens of each 256 blocks by (plane, index); overflow, one word, zeroed first: the
+ *                           levels beyond +-580, which go out as token 22 with the extra bits s << 9 | 511
+ *     THIP_ENC_TOK_SCAN     reads chunk_cnt; writes chunk_base, uint32 [nchunks][64]: the tokens of index z in the chunks before
+ *                           chunk c, and list_len, uint32 [3][64]: the tokens by (plane, index)
+ *     THIP_ENC_TOK_SCATTER  reads tok, mask, chunk_base, list_len; writes out, out_cap words long: the tokens in stream order (index,
+ *                           then plane, then coded order).  The token of block k at index z goes to word (the list_len of all lower
+ *                           indices) + chunk_base[chunk of k][z] + (the blocks of that chunk before k whose mask has bit z).  The
+ *                           entry reads list_len, chunk_base and mask back first and refuses when a word would fall outside out
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req NULL, a buffer a requested stage reads or writes NULL, or a HIP call failed.  THIP_EINVAL: stages 0 or unknown;
+ * the frame size, fragment count and pixel format as thip_enc_inter_stage refuses them; classes not 0, 2 or 3; levels not 16-byte
+ * aligned, mask not 8-byte, tok, chunk_cnt, chunk_base, list_len, overflow or out not 4-byte, dcq or dcr not 2-byte -- all found
+ * before a device is touched.  THIP_EINVAL also from SCATTER when the sum of list_len exceeds out_cap or a token's place is at or
+ * beyond it, found when they have been read back: nothing is written to out then.
+ * ---------------------------------------------------------------------------------- */
+#define THIP_ENC_TOK_TOK 1
+#define THIP_ENC_TOK_SCAN 2
+#define THIP_ENC_TOK_SCATTER 4
+typedef struct thip_enc_tok_req {   /* 120 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t classes, stages, pad;
+  const int16_t *levels, *dcq, *dcr;
+  const uint8_t *cmap;
+  uint32_t *tok;
+  uint64_t *mask;
+  uint32_t *chunk_cnt, *chunk_base, *list_len, *overflow, *out;
+  uint64_t out_cap;
+} thip_enc_tok_req;
+int thip_enc_tok_stage(const thip_enc_tok_req *req);
+
+/* ------------------------------------------------------------------------------------
  * The single-block slots of oc_enc_opt_vtable (encint.h:292-326) with the reference's signatures:
  * HOST pointers, one 8x8 block per call, each bound to a one-element batch of the kernels above.
  * oc_enc_accel_init_hip fills the vtable with these; they exist so that every

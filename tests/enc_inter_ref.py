@@ -123,9 +123,11 @@ class Geometry:
             self.mb_of[g["froffset"] + loc] = (fy >> sy) * self.nmbx + (fx >> sx)
 
 
-def token_packet_tail(bw, vals_by_block, plane_of, setup):
+def token_packet_tail(bw, vals_by_block, plane_of, setup, detail=None):
     """Tokens of the coded blocks (zig-zag values, DC the residual; coded order) appended to bw as enc_ref.encode_frame writes them:
-    EOB runs merged across lists and planes, the tables of least bits.  Returns (hti, ntok, nmerged, last_zzi)."""
+    EOB runs merged across lists and planes, the tables of least bits.  Returns (hti, ntok, nmerged, last_zzi).  detail: a dict that
+    receives words (the tokens before the merge in stream order, in the word format of thip_encode.h) and list_len [64][3], as
+    enc_ref.encode_frame hands them out."""
     by_z, last_zzi = {}, []
     for v, p in zip(vals_by_block, plane_of):
         toks = block_tokens(v)
@@ -133,6 +135,10 @@ def token_packet_tail(bw, vals_by_block, plane_of, setup):
         for t in toks:
             by_z.setdefault((t[0], int(p)), []).append(t[1:])
     ntok = sum(len(v) for v in by_z.values())
+    if detail is not None:
+        detail["words"] = np.array([(z << 16 | p << 22) | (0 if t[0] == "EOB" else t[0] | t[1] << 5)
+                                    for z in range(64) for p in range(3) for t in by_z.get((z, p), [])], np.uint32)
+        detail["list_len"] = np.array([[len(by_z.get((z, p), [])) for p in range(3)] for z in range(64)], np.int64)
     lists, run, rstart = {}, 0, None
 
     def flush():
@@ -358,7 +364,8 @@ class InterEncoder:
         cf = geo.coded_order[coded[geo.coded_order]]
         vals = lev[cf].copy()
         vals[:, 0] = dcr[cf]
-        hti, ntok, nmerged, last_zzi = token_packet_tail(bw, vals, geo.plane_of[cf], setup)
+        detail = {}
+        hti, ntok, nmerged, last_zzi = token_packet_tail(bw, vals, geo.plane_of[cf], setup, detail)
         # the reconstruction: the oracle decodes the frame from the same lists, modes and vectors
         dq = np.stack([tabs[(int(qti_of[f]), int(geo.plane_of[f]))] for f in cf])
         coeffs = np.zeros((len(cf), 64), np.int64)
@@ -375,7 +382,8 @@ class InterEncoder:
         ost.decode_frame(frame_type=1, coded_fragis=cf, ncoded=ncoded, coeffs=coeffs.astype(np.int16), last_zzi=last_zzi,
                          dc_quant=dq[:, 0].astype(np.uint16), uncoded_fragis=unc, flimit=setup.lflims[qi])
         return dict(packet=bw.bytes(), modes=counts, coded=ncoded, mode_scheme=scheme, mv_scheme=mvmode, huff=hti, tokens=ntok,
-                    tokens_merged=nmerged, coded_fragis=cf, mvx=mvx, mvy=mvy, pix=pix)
+                    tokens_merged=nmerged, coded_fragis=cf, mvx=mvx, mvy=mvy, pix=pix, levels=lev[geo.coded_order], dcr=dcr,
+                    cmap=np.where(coded, cls, 0).astype(np.uint8), words=detail["words"], list_len=detail["list_len"])
 
 
 # ---- content ------------------------------------------------------------------------------------------------------------------

@@ -73,6 +73,13 @@ def test_argument_validation_without_gpu():
     assert C.sizeof(_lib.EncRateReq) == 224
     assert L.thip_enc_rate_stage(C.byref(_lib.EncRateReq())) == _lib.EINVAL   # (no stage)
     assert L.thip_enc_rate_groups(0) == _lib.EINVAL and L.thip_enc_rate_groups(1) == 1
+    assert L.thip_enc_tok_stage(None) == _lib.EFAULT
+    T = _lib.EncTokReq
+    assert C.sizeof(T) == 120
+    assert [getattr(T, f).offset for f in ("frame_width", "frame_height", "pixel_fmt", "classes", "stages", "pad", "levels", "dcq", "dcr",
+                                          "cmap", "tok", "mask", "chunk_cnt", "chunk_base", "list_len", "overflow", "out", "out_cap")] == \
+        [0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 56, 64, 72, 80, 88, 96, 104, 112]
+    assert L.thip_enc_tok_stage(C.byref(T())) == _lib.EINVAL   # (no stage)
 
 
 def test_loop_filter_init_slot_matches_oracle_table():

@@ -158,6 +158,19 @@ class EncRdqReq(C.Structure):
                 ("jbefore", C.c_void_p), ("jafter", C.c_void_p), ("rate", C.c_void_p)]
 
 
+ENC_TOK_TOK, ENC_TOK_SCAN, ENC_TOK_SCATTER = 1, 2, 4
+ENC_TOK_WORDS, ENC_CHUNK = 65, 256
+
+
+class EncTokReq(C.Structure):
+    """thip_enc_tok_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("classes", C.c_int32), ("stages", C.c_int32), ("pad", C.c_int32),
+                ("levels", C.c_void_p), ("dcq", C.c_void_p), ("dcr", C.c_void_p), ("cmap", C.c_void_p), ("tok", C.c_void_p),
+                ("mask", C.c_void_p), ("chunk_cnt", C.c_void_p), ("chunk_base", C.c_void_p), ("list_len", C.c_void_p),
+                ("overflow", C.c_void_p), ("out", C.c_void_p), ("out_cap", C.c_uint64)]
+
+
 class PictureInReq(C.Structure):
     """thip_picture_in_req (include/theora_hip.h)."""
     _fields_ = [("format", C.c_int32), ("pixel_fmt", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32),
@@ -265,6 +278,7 @@ SYMBOLS = [
     ("thip_enc_rd_stage", _I, [C.POINTER(EncRdReq)]),
     ("thip_enc_skip_stage", _I, [C.POINTER(EncSkipReq)]),
     ("thip_enc_rdq_stage", _I, [C.POINTER(EncRdqReq)]),
+    ("thip_enc_tok_stage", _I, [C.POINTER(EncTokReq)]),
     ("thip_profile_enable", _I, [_I]),
     ("thip_profile_read", _I, [C.POINTER(_I64), C.POINTER(C.c_double)]),
     ("thip_profile_reset", _I, []),

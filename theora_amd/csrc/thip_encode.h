@@ -472,4 +472,36 @@ __global__ __launch_bounds__(256) void k_enc_intra_scatter(uint32_t *out, const 
   }
 }
 
+// ---- the launches, stated once: th_encode_* (thip_encode.hip) and thip_enc_tok_stage (theora_hip.h) both call these -------------
+// The inter frame's token launch is tok_launch_inter of thip_encode_inter.h.
+struct TokBufs {          // device memory a token launch writes
+  uint32_t *tok;          // [n][kEncTokWords]: a block's tokens from its first word on, the words behind them untouched
+  uint64_t *mask;         // [n]
+  uint32_t *chunk_cnt;    // [enc_chunks(n)][3][64]
+  uint32_t *overflow;     // one word, zeroed on the same stream before (the quantising kernels do)
+};
+
+inline unsigned enc_chunks(int64_t n) { return (unsigned)((n + kEncChunk - 1) / kEncChunk); }
+
+// a key frame's tokens: levels [n][64] (coded order), dcq [n] (raster), order [n] (the coded order)
+inline hipError_t tok_launch_intra(const TokBufs &o, const int16_t *levels, const int16_t *dcq, const int32_t *order, const EncPlanes &g,
+                                   int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_intra_tok, dim3(enc_chunks(n)), dim3(256), 0, stream, o.tok, o.mask, o.chunk_cnt, o.overflow, levels, dcq,
+                     order, g, n);
+  return hipGetLastError();
+}
+
+// the chunks' counts into their places: chunk_base [enc_chunks(n)][64], list_len [3][64]
+inline hipError_t tok_launch_scan(uint32_t *chunk_base, uint32_t *list_len, const uint32_t *chunk_cnt, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_intra_scan, dim3(64), dim3(256), 0, stream, chunk_base, list_len, chunk_cnt, (int)enc_chunks(n));
+  return hipGetLastError();
+}
+
+// the blocks' tokens into stream order: out holds the sum of list_len words
+inline hipError_t tok_launch_scatter(uint32_t *out, const uint32_t *tok, const uint64_t *mask, const uint32_t *chunk_base,
+                                     const uint32_t *list_len, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_intra_scatter, dim3(enc_chunks(n)), dim3(256), 0, stream, out, tok, mask, chunk_base, list_len, n);
+  return hipGetLastError();
+}
+
 }  // namespace thip

@@ -840,14 +840,15 @@ static void enc_frame_queued(th_enc_ctx *e) {
   e->dup_next = 0;
 }
 
+// the context's token buffers as the launches of thip_encode.h and thip_encode_inter.h take them: the overflow count lies behind
+// the list lengths in d_small
+static TokBufs enc_tok_bufs(const th_enc_ctx *e) { return TokBufs{e->d_tok, e->d_mask, e->d_cnt, e->d_small + 192}; }
+
 // everything behind the token kernel, for both frame types: the scan, the scatter, the read-backs, the device packetiser
 static int enc_queue_tail(th_enc_ctx *e) {
   const int64_t n = e->nfrags;
-  hipLaunchKernelGGL(k_enc_intra_scan, dim3(64), dim3(256), 0, e->stream, e->d_base, e->d_small, e->d_cnt, e->nchunks);
-  ENC_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_enc_intra_scatter, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_out, e->d_tok, e->d_mask,
-                     e->d_base, e->d_small, n);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(tok_launch_scan(e->d_base, e->d_small, e->d_cnt, n, e->stream));
+  ENC_TRY(tok_launch_scatter(e->d_out, e->d_tok, e->d_mask, e->d_base, e->d_small, n, e->stream));
   const size_t nsmall = e->mask_queued ? kEncSmallMask + sizeof(MaskRec) / 4 : 193;   // (a masked frame: its record too)
   ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, nsmall * 4, hipMemcpyDeviceToHost, e->stream));
   if (!e->frame_key) {
@@ -886,7 +887,7 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   constexpr int classes = sizeof...(Gold) ? 3 : 2;
   const int64_t n = e->nfrags;
   const int lambda = e->lambda[e->frame_qi];
-  const dim3 gfq((unsigned)((4 * n + 255) / 256)), gch((unsigned)e->nchunks), wg(256);
+  const dim3 gfq((unsigned)((4 * n + 255) / 256)), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
   if (enc_mask_queue(e, g)) return TH_EFAULT;
@@ -920,9 +921,7 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the level choice reads them too)
   if constexpr (classes == 3) ENC_TRY(inter_launch_dc3(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
   else ENC_TRY(inter_launch_dc(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
-  hipLaunchKernelGGL(k_enc_inter_tok, gch, wg, 0, e->stream, e->d_tok, e->d_mask, e->d_cnt, e->d_small + 192, e->d_levels, e->d_dcr,
-                     e->d_cmap, e->d_order, g, n);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(tok_launch_inter(enc_tok_bufs(e), e->d_levels, e->d_dcr, e->d_cmap, e->d_order, g, n, e->stream));
   return enc_queue_tail(e);
 }
 
@@ -1150,9 +1149,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   ENC_TRY(hipGetLastError());
   if (enc_rdq_queue(e, 0, g, sel, (const uint32_t *)nullptr, EncRef{}, EncRef{})) return TH_EFAULT;
   ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the level choice reads them too)
-  hipLaunchKernelGGL(k_enc_intra_tok, dim3((unsigned)e->nchunks), dim3(256), 0, e->stream, e->d_tok, e->d_mask, e->d_cnt,
-                     e->d_small + 192, e->d_levels, e->d_dcq, e->d_order, g, n);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(tok_launch_intra(enc_tok_bufs(e), e->d_levels, e->d_dcq, e->d_order, g, n, e->stream));
   return enc_queue_tail(e);
 }
 
@@ -2737,6 +2734,82 @@ int thip_enc_mask_stage(const thip_enc_mask_req *q) {
   hipStream_t stream = nullptr;
   ENC_TRY(mask_launch_act(q->act, d_part, g, stream));
   ENC_TRY(mask_launch_scale(q->iscale, (MaskRec *)q->avg, q->act, d_part, g, geo.nfrags, q->ratio, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the tokeniser on the caller's levels, DCs and map (theora_hip.h): the launch functions of thip_encode.h and thip_encode_inter.h, as
+// th_encode_ycbcr_in, enc_launch_inter and enc_queue_tail make them, on the current device's null stream
+int thip_enc_tok_stage(const thip_enc_tok_req *q) {
+  if (!q) return THIP_EFAULT;
+  const int st = q->stages;
+  if (st <= 0 || st > 7) return THIP_EINVAL;
+  const bool tok = st & THIP_ENC_TOK_TOK, scan = st & THIP_ENC_TOK_SCAN, scatter = st & THIP_ENC_TOK_SCATTER;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  if (q->classes != 0 && q->classes != 2 && q->classes != 3) return THIP_EINVAL;
+  const bool inter = q->classes != 0;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
+  if (tok && (!q->levels || (inter ? !q->dcr || !q->cmap : !q->dcq) || !q->overflow)) return THIP_EFAULT;
+  if ((tok || scatter) && (!q->tok || !q->mask)) return THIP_EFAULT;
+  if ((tok || scan) && !q->chunk_cnt) return THIP_EFAULT;
+  if ((scan || scatter) && (!q->chunk_base || !q->list_len)) return THIP_EFAULT;
+  if (scatter && !q->out) return THIP_EFAULT;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->dcr, 2) || misaligned(q->mask, 8) || misaligned(q->tok, 4) ||
+      misaligned(q->chunk_cnt, 4) || misaligned(q->chunk_base, 4) || misaligned(q->list_len, 4) || misaligned(q->overflow, 4) ||
+      misaligned(q->out, 4))
+    return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int64_t n = geo.nfrags;
+  const size_t nchunks = enc_chunks(n);
+  EncPlanes g = {};   // (the token kernels read the fragment geometry alone)
+  for (int p = 0; p < 3; p++) {
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+  }
+  hipStream_t stream = nullptr;
+  int32_t *d_order = nullptr;
+  struct Free { int32_t *&p; ~Free() { (void)hipFree(p); } } guard{d_order};
+  if (tok) {
+    ENC_TRY(hipMalloc((void **)&d_order, (size_t)n * 4));
+    ENC_TRY(hipMemcpy(d_order, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    ENC_TRY(hipMemsetAsync(q->overflow, 0, 4, stream));   // (th_encode_*: the quantising kernel zeroes it)
+    const TokBufs o{q->tok, q->mask, q->chunk_cnt, q->overflow};
+    if (inter) ENC_TRY(tok_launch_inter(o, q->levels, q->dcr, q->cmap, d_order, g, n, stream));
+    else ENC_TRY(tok_launch_intra(o, q->levels, q->dcq, d_order, g, n, stream));
+  }
+  if (scan) ENC_TRY(tok_launch_scan(q->chunk_base, q->list_len, q->chunk_cnt, n, stream));
+  if (scatter) {
+    // every word the scatter would write lies inside out: the lists' lengths, the chunks' places and the masks read back (th_encode_*
+    // sizes its buffer for the worst case and needs none of this)
+    std::vector<uint32_t> h_len(192), h_base(nchunks * 64);
+    std::vector<uint64_t> h_mask((size_t)n);
+    ENC_TRY(hipMemcpy(h_len.data(), q->list_len, 192 * 4, hipMemcpyDeviceToHost));   // (the null stream: behind the launches above)
+    ENC_TRY(hipMemcpy(h_base.data(), q->chunk_base, h_base.size() * 4, hipMemcpyDeviceToHost));
+    ENC_TRY(hipMemcpy(h_mask.data(), q->mask, (size_t)n * 8, hipMemcpyDeviceToHost));
+    uint64_t start[64], total = 0;
+    for (int z = 0; z < 64; z++) {
+      start[z] = total;
+      total += (uint64_t)h_len[z] + h_len[64 + z] + h_len[128 + z];
+    }
+    if (total > q->out_cap) return THIP_EINVAL;
+    for (size_t c = 0; c < nchunks; c++) {
+      uint32_t cnt[64] = {};
+      for (int64_t k = (int64_t)c * kEncChunk; k < std::min(n, (int64_t)(c + 1) * kEncChunk); k++)
+        for (uint64_t m = h_mask[(size_t)k]; m; m &= m - 1) cnt[__builtin_ctzll(m)]++;
+      for (int z = 0; z < 64; z++)
+        if (cnt[z] && start[z] + h_base[c * 64 + z] + cnt[z] > q->out_cap) return THIP_EINVAL;
+    }
+    ENC_TRY(tok_launch_scatter(q->out, q->tok, q->mask, q->chunk_base, q->list_len, n, stream));
+  }
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

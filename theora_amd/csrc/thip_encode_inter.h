@@ -459,4 +459,13 @@ inline hipError_t inter_launch_dc(int16_t *dcr, const int16_t *dcq, const uint8_
   return hipGetLastError();
 }
 
+// an inter frame's tokens (th_encode_* and thip_enc_tok_stage): the coded blocks' of levels [n][64] (coded order) with the DC residuals
+// dcr [n] and the map cmap [n] (raster); an uncoded block gets mask 0 and nothing else
+inline hipError_t tok_launch_inter(const TokBufs &o, const int16_t *levels, const int16_t *dcr, const uint8_t *cmap, const int32_t *order,
+                                   const EncPlanes &g, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_enc_inter_tok, dim3(enc_chunks(n)), dim3(256), 0, stream, o.tok, o.mask, o.chunk_cnt, o.overflow, levels, dcr,
+                     cmap, order, g, n);
+  return hipGetLastError();
+}
+
 }  // namespace thip

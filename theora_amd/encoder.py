@@ -615,6 +615,21 @@ def pack_tokens(words_ptr, list_len, codes, lens, groups, phase, packet_ptr, cap
     return rc, dict(bits=res.bits, bytes=res.bytes, tokens=res.tokens, merged=res.merged, merged_ac=res.merged_ac, huff=list(res.huff))
 
 
+def tok_stage(frame, pixel_fmt, classes, stages, levels=None, dcq=None, dcr=None, cmap=None, tok=None, mask=None, chunk_cnt=None,
+              chunk_base=None, list_len=None, overflow=None, out=None, out_cap=0):
+    """thip_enc_tok_stage (include/theora_hip.h): the tokeniser on the caller's levels, DCs and map, a test and diagnostic entry.
+    frame: (width, height); classes: 0 (a key frame), 2 or 3; stages: an OR of _lib.ENC_TOK_*; out_cap: the words of out; the rest:
+    device addresses (a tensor's data_ptr(); None is NULL).  Returns the entry's return code; nothing is raised, the refusals are the
+    caller's to look at."""
+    L = _lib.load()
+    q = _lib.EncTokReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.classes, q.stages, q.out_cap = int(classes), int(stages), int(out_cap)
+    q.levels, q.dcq, q.dcr, q.cmap, q.tok, q.mask = levels, dcq, dcr, cmap, tok, mask
+    q.chunk_cnt, q.chunk_base, q.list_len, q.overflow, q.out = chunk_cnt, chunk_base, list_len, overflow, out
+    return L.thip_enc_tok_stage(C.byref(q))
+
+
 def inter_stage(frame, pixel_fmt, stages, classes, pic=None, lam=0, src=None, src_pitch=None, prev=None, gold=None, ref_pitch=None,
                 dequant=None, stats=None, words=None, words_from_stats=None, levels=None, dcq=None, cmap=None, dcr=None):
     """thip_enc_inter_stage (include/theora_hip.h): the device stage of an inter frame on the caller's planes, lambda and tables, a
