@@ -1,7 +1,7 @@
 /* encoder_example_hip.c -- YUV4MPEG2 in, Ogg/Theora out, through this library's intra-only th_encode_* (include/theoraenc_hip.h)
  * and its Ogg writer (include/thip_ogg.h).
  *
- *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta] [-V kbps]
+ *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta [--roi x,y,w,h,v]] [-V kbps]
  *                       [--first-pass FILE | --second-pass FILE | --two-pass] [-o out.ogv] in.y4m
  *
  * Input: C420jpeg, C420, C420paldv, C420mpeg2 (4:2:0), C422 or C444, any size; no C tag means 4:2:0.  The frame is the picture
@@ -9,7 +9,9 @@
  * frame is a key frame at qi = quality (default 48).  -k: inter frames; -m with it: all eight macro-block modes
  * (TH_ENCCTL_THIP_SET_INTER_MODES: golden-frame prediction, four vectors a macro block); -a with it: a key frame at every scene
  * cut as well, the interval becoming a maximum (TH_ENCCTL_THIP_SET_AUTO_KEYFRAMES with the ratio t, 1..4096; 230 without one).  -b: block-level qi with that delta, 1..31
- * (TH_ENCCTL_THIP_SET_BLOCK_QI).  --device-pack: the packets' token bits are made on the GPU (TH_ENCCTL_THIP_SET_DEVICE_PACK; the
+ * (TH_ENCCTL_THIP_SET_BLOCK_QI).  --roi x,y,w,h,v with it: a region of interest (TH_ENCCTL_THIP_SET_ROI_MAP), the rectangle in picture
+ * coordinates (y from the top) at importance v, -64..64 in 1/16 octave of lambda, as a map at macro-block resolution: a cell whose
+ * top-left pixel lies in the rectangle holds v, the others 0.  --device-pack: the packets' token bits are made on the GPU (TH_ENCCTL_THIP_SET_DEVICE_PACK; the
  * same bytes).  -V: bitrate mode at kbps * 1000 bits a second
  * (TH_ENCCTL_SET_BITRATE), as libtheora's encoder_example -V.  Output on stdout without -o.
  *
@@ -68,6 +70,7 @@ static int read_frame(FILE *in, unsigned char *buf, size_t bytes) {
 typedef struct {
   int quality, kf, all_modes, bqi, device_pack, auto_kf;
   long kbps;
+  int roi, roi_rect[5];   /* --roi: x, y, w, h, v */
 } options;
 
 /* feeds the second pass until it can take the next frame (libtheora's encoder_example loop); 0 on success */
@@ -148,6 +151,21 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
   if (bqi && th_encode_ctl(enc, TH_ENCCTL_THIP_SET_BLOCK_QI, &bqi, sizeof(bqi))) {
     fprintf(stderr, "block qi refused (delta 1..31)\n");
     return 1;
+  }
+  if (o->roi) {   /* a map at macro-block resolution: v where the cell's top-left pixel lies in the rectangle */
+    const int wm = (w + 15) / 16, hm = (h + 15) / 16, *r = o->roi_rect;
+    int8_t *map = calloc((size_t)wm * hm, 1);
+    for (int cy = 0; map && cy < hm; cy++)
+      for (int cx = 0; cx < wm; cx++)
+        if (cx * 16 >= r[0] && cx * 16 < r[0] + r[2] && cy * 16 >= r[1] && cy * 16 < r[1] + r[3]) map[cy * wm + cx] = (int8_t)r[4];
+    thip_enc_roi_map rm;
+    memset(&rm, 0, sizeof(rm));
+    rm.width = wm, rm.height = hm, rm.pitch = wm, rm.map = map;
+    if (!map || r[4] < -64 || r[4] > 64 || th_encode_ctl(enc, TH_ENCCTL_THIP_SET_ROI_MAP, &rm, sizeof(rm))) {
+      fprintf(stderr, "region of interest refused (v -64..64)\n");
+      return 1;
+    }
+    free(map);   /* the encoder has its own copy */
   }
   if (device_pack && th_encode_ctl(enc, TH_ENCCTL_THIP_SET_DEVICE_PACK, &device_pack, sizeof(device_pack))) {
     fprintf(stderr, "device packetiser refused\n");
@@ -240,7 +258,7 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
 }
 
 int main(int argc, char **argv) {
-  options o = {48, 0, 0, 0, 0, 0, 0};
+  options o = {48, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0}};
   const char *in_path = NULL, *out_path = NULL, *first = NULL, *second = NULL;
   int two_pass = 0;
   for (int i = 1; i < argc; i++) {
@@ -251,6 +269,8 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[i], "-m") == 0) o.all_modes = 1;
     else if (strcmp(argv[i], "-a") == 0) o.auto_kf = i + 2 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' ? atoi(argv[++i]) : 230;
     else if (strcmp(argv[i], "-b") == 0 && i + 1 < argc) o.bqi = atoi(argv[++i]);
+    else if (strcmp(argv[i], "--roi") == 0 && i + 1 < argc)
+      o.roi = sscanf(argv[++i], "%d,%d,%d,%d,%d", &o.roi_rect[0], &o.roi_rect[1], &o.roi_rect[2], &o.roi_rect[3], &o.roi_rect[4]) == 5 ? 1 : -1;
     else if (strcmp(argv[i], "--device-pack") == 0) o.device_pack = 1;
     else if (strcmp(argv[i], "--first-pass") == 0 && i + 1 < argc) first = argv[++i];
     else if (strcmp(argv[i], "--second-pass") == 0 && i + 1 < argc) second = argv[++i];
@@ -258,9 +278,9 @@ int main(int argc, char **argv) {
     else in_path = argv[i];
   }
   const int npass = (first != NULL) + (second != NULL) + two_pass;
-  if (!in_path || ((o.all_modes || o.auto_kf) && o.kf <= 0) || npass > 1 || ((second || two_pass) && o.kbps <= 0) ||
+  if (!in_path || o.roi < 0 || (o.roi && !o.bqi) || ((o.all_modes || o.auto_kf) && o.kf <= 0) || npass > 1 || ((second || two_pass) && o.kbps <= 0) ||
       (two_pass && strcmp(in_path, "-") == 0)) {
-    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file)] [-o out.ogv] in.y4m\n", argv[0]);
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi [--roi x,y,w,h,v: a region of interest, v in -64..64]] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file)] [-o out.ogv] in.y4m\n", argv[0]);
     return 1;
   }
   FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");

@@ -962,6 +962,36 @@ typedef struct thip_enc_mask_req {   /* 104 bytes */
 int thip_enc_mask_stage(const thip_enc_mask_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the per-block lambda scales of th_encode_*'s region-of-interest maps (theoraenc_hip.h, "Region of
+ * interest") for a caller's map.  The same launch function th_encode_* calls in front of its block-qi kernel.  Every pointer is
+ * DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*   as thip_enc_mask_stage takes them (no plane is read)
+ *   map_width, map_height, map_pitch, map   the map, int8 [map_height] rows of map_width entries at map_pitch bytes (it may be
+ *                    negative), row 0 the picture's top row; any base and pitch.  The entries are taken as they are: th_encode_*
+ *                    hands the kernel its own copy, which has none outside -64..64; here one outside it only cannot carry a
+ *                    fragment's exponent outside -64..64
+ *   mask_iscale      masking's scales, uint16 [nfrags] (thip_enc_mask_stage's), or NULL: 2048 everywhere.  It may be iscale itself
+ *   iscale           uint16 [nfrags]: every fragment's final scale, Q11, the three planes in fragment raster order
+ *   stats            int32 [8]: exp_min, exp_max, exp_sum (the low then the high word of an int64), scale_min, scale_max, 0, 0 --
+ *                    thip_enc_roi_stats' fields of the frame
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req, map or an output NULL, or a HIP call failed.  THIP_EINVAL: the frame size, fragment count, pixel format and
+ * picture region as thip_enc_mask_stage refuses them; map_width or map_height outside 1..16384; |map_pitch| < map_width;
+ * mask_iscale or iscale not 2-byte aligned, stats not 8-byte -- all found before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+typedef struct thip_enc_roi_req {   /* 80 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t map_width, map_height, pad;
+  int64_t map_pitch;
+  const int8_t *map;
+  const uint16_t *mask_iscale;
+  uint16_t *iscale;
+  int32_t *stats;
+} thip_enc_roi_req;
+int thip_enc_roi_stage(const thip_enc_roi_req *req);
+
+/* ------------------------------------------------------------------------------------
  * A test and diagnostic entry: the rate-distortion mode decision of th_encode_*'s eight-mode inter frames (theoraenc_hip.h,
  * "Rate-distortion mode decision") on the caller's planes, lambdas and tables.  The same launch function th_encode_* calls in place
  * of its eight-mode search.  dequant and bits are HOST memory, every other pointer is DEVICE memory.

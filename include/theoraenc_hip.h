@@ -136,6 +136,30 @@
  *   - No wait: two launches (the activity, then the scales) are queued in front of the frame's block-qi kernel; A and the largest
  *     activity come back with the frame's other read-backs (thip_enc_mask_stats).
  *
+ * Region of interest (TH_ENCCTL_THIP_SET_ROI_MAP), stated likewise (tests/enc_roi_ref.py restates it).  A caller's importance map
+ * scales the lambda of the block-qi choice per block, alone or on top of activity masking's scale.  It acts where block qi does and
+ * only with it; without a map, and with a map that is 0 everywhere, every packet is byte for byte as without the call.  Integer
+ * arithmetic throughout; every division rounds down and every >> is arithmetic.
+ *   - The map: v[Hm][Wm], int8, every entry in -64..64, row 0 the picture's top row; it covers th_info's picture region (pic_x,
+ *     pic_y, pw = pic_width, ph = pic_height) exactly.  Wm and Hm each lie in 1..16384, whatever the picture's size: the map may be
+ *     coarser or finer than pixels.  Positive means more important; the unit is 1/16 of an octave of lambda.
+ *   - The cell of a luma pixel (x, y) in picture coordinates, rows from the top: x' = min(max(x, 0), pw - 1), y' = min(max(y, 0),
+ *     ph - 1) -- the clamp the block kernels apply to the source --, and (cx, cy) = (x' Wm / pw, y' Hm / ph).
+ *   - The sum of a fragment of plane p: S = the sum of v[cy][cx] over its 64 samples, the sample at plane coordinates (X, Y) (rows
+ *     from the top of the frame) evaluated at the luma pixel ((X << hdec_p) - pic_x, (Y << vdec_p) - pic_y); the shifts are 0 for
+ *     luma and the plane's decimation for chroma.  One rule for the three planes and the three pixel formats.
+ *   - The exponent: e = (S + 32) >> 6, in -64..64; n = -e, o = n >> 4, f = n & 15.
+ *   - The ROI scale, Q11: r = T[f] << o when o >= 0, else (T[f] + (1 << (-o - 1))) >> -o, with T[f] = round(2048 2^(f / 16)):
+ *       T = 2048, 2139, 2233, 2332, 2435, 2543, 2656, 2774, 2896, 3025, 3158, 3298, 3444, 3597, 3756, 3922.
+ *     r lies in [128, 32768] and is 2048 where the map is 0.
+ *   - The fragment's scale: i_b = min(max((m_b r_b + 1024) >> 11, 128), 32768), m_b masking's scale of the fragment when masking is
+ *     on, else 2048.
+ *   - Use: i_b is the i_b of "Activity masking", of "Skip decision" and of "Level choice", wherever masking's scale is used.  Nothing
+ *     else changes: the qi list, the DC at qis[0], the mode decision's L, the rate probe and controllers, the pass file, automatic key
+ *     frames, the quality statistics, the device packetiser.
+ *   - No wait: one kernel a lane a fragment and a one-group fold are queued in front of the frame's block-qi kernel, behind masking's
+ *     launches; the frame's extremes come back with its other read-backs (thip_enc_roi_stats).
+ *
  * Rate-distortion mode decision (TH_ENCCTL_THIP_SET_RD_MODES), stated likewise (tests/enc_rd_ref.py restates it).  It replaces the
  * cascade of SAD comparisons of "All eight modes" by the least D + lambda R over six candidates, computed from the quantised levels
  * and the token code lengths.  Off (the default) every packet is as without the call.  Integer arithmetic throughout, 64-bit where a
@@ -629,6 +653,45 @@ typedef struct thip_enc_rd_quant_stats {   /* 88 bytes */
                              frame's own tables (intra on a key frame, inter on an inter frame) */
   double rdq_ms;          /* HIP events around the launch */
 } thip_enc_rd_quant_stats;
+
+/* Extension: buf = thip_enc_roi_map: the importance map of "Region of interest" above, for every frame submitted after the call until
+   it is replaced; map == NULL clears it (the other fields are then ignored).  Allowed before and between frames -- a map follows the
+   content --, but TH_EINVAL with a frame pending and after the last packet.  The encoder takes its own copy at the call:
+   device = 0: map is host memory; every entry is checked (one outside -64..64: TH_EINVAL, and the map in force stays) and the rows
+   are copied before the call returns; `stream` is ignored.
+   device = 1: map is device memory on the context's GPU (TH_ENCCTL_THIP_GET_DEVICE), `stream` a hipStream_t (NULL: the null stream),
+   ordered as TH_ENCCTL_THIP_RGB_IN orders its source: the copy reads the map only after the work queued on that stream so far, and
+   work queued on it afterwards waits for the copy alone, so the caller may overwrite its tensor from that stream at once.  The
+   entries are checked on the device, which cannot refuse: unlike a host map's, an entry outside -64..64 is clamped to +-64 and
+   counted (thip_enc_roi_stats.clamped).  The call does not wait on the host.
+   TH_EFAULT: enc or buf NULL.  TH_EINVAL: a wrong buf_sz, width or height outside 1..16384, |pitch| < width, device not 0 or 1, a
+   host entry out of range -- all found before a device is touched.  Accepted with block qi off, where it has no effect.
+   Set the switches first: a TH_ENCCTL_THIP_SET_INTER_FRAMES that changes the switch rebuilds the device state, and the map goes with it.
+   (0x7224 is not used: an unknown request, TH_EIMPL.) */
+#define TH_ENCCTL_THIP_SET_ROI_MAP (0x7225)
+typedef struct thip_enc_roi_map {   /* 40 bytes */
+  int32_t width, height;   /* Wm, Hm */
+  int32_t device;          /* 0: map is host memory; 1: device memory on the context's GPU */
+  int32_t pad;
+  int64_t pitch;           /* bytes from one row to the next one down; it may be negative */
+  const int8_t *map;       /* row 0 (the picture's top row), or NULL: no map */
+  void *stream;            /* device = 1: a hipStream_t, as in thip_enc_rgb_in; ignored for device = 0 */
+} thip_enc_roi_map;
+/* Extension: buf = thip_enc_roi_stats, describing the last packet th_encode_packetout returned.  For a frame coded without a map -- a
+   duplicate, a dropped frame, a zero-byte packet, any frame with block qi off or no map set -- every field is 0 except active,
+   map_width and map_height. */
+#define TH_ENCCTL_THIP_GET_ROI_STATS (0x7226)
+typedef struct thip_enc_roi_stats {   /* 56 bytes */
+  int32_t active;          /* 1: a map is set */
+  int32_t measured;        /* 1: the frame's block-qi choice used it */
+  int32_t map_width, map_height;   /* of the map in force */
+  int32_t exp_min, exp_max;        /* the least and greatest exponent e of a luma fragment */
+  int64_t exp_sum;                 /* ... and their sum */
+  int32_t scale_min, scale_max;    /* the least and greatest final scale i_b of a fragment of any plane */
+  int32_t clamped;         /* entries of the frame's map that the device copy clamped (a host map: 0) */
+  int32_t reserved;
+  double roi_ms;           /* HIP events around the two launches */
+} thip_enc_roi_stats;
 
 /* Extension: the first pass of "Two-pass" above, with TH_ENCCTL_2PASS_OUT's calling convention: buf = unsigned char **, buf_sz ==
    sizeof(unsigned char *) (else TH_EINVAL).  The first call must come before the first frame (else TH_EINVAL; TH_EINVAL too on a

@@ -123,6 +123,14 @@ class EncMaskReq(C.Structure):
                 ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("act", C.c_void_p), ("avg", C.c_void_p), ("iscale", C.c_void_p)]
 
 
+class EncRoiReq(C.Structure):
+    """thip_enc_roi_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
+                ("map_width", C.c_int32), ("map_height", C.c_int32), ("pad", C.c_int32), ("map_pitch", C.c_int64),
+                ("map", C.c_void_p), ("mask_iscale", C.c_void_p), ("iscale", C.c_void_p), ("stats", C.c_void_p)]
+
+
 ENC_RD_CAND, ENC_RD_DECIDE = 1, 2
 
 
@@ -275,6 +283,7 @@ SYMBOLS = [
     ("thip_enc_rate_stage", _I, [C.POINTER(EncRateReq)]),
     ("thip_enc_rate_groups", _I, [_I64]),
     ("thip_enc_mask_stage", _I, [C.POINTER(EncMaskReq)]),
+    ("thip_enc_roi_stage", _I, [C.POINTER(EncRoiReq)]),
     ("thip_enc_rd_stage", _I, [C.POINTER(EncRdReq)]),
     ("thip_enc_skip_stage", _I, [C.POINTER(EncSkipReq)]),
     ("thip_enc_rdq_stage", _I, [C.POINTER(EncRdqReq)]),

@@ -36,6 +36,7 @@
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_mask.h"
+#include "thip_encode_roi.h"
 #include "thip_encode_rd.h"
 #include "thip_encode_skip.h"
 #include "thip_encode_rdq.h"
@@ -220,6 +221,7 @@ void enc_put_mv(BitW &bw, int v, int mvs) {
 }  // namespace
 
 constexpr int kEncSmallMask = 194;   // d_small / h_small: the word at which a masked frame's MaskRec lies (8-byte aligned)
+constexpr int kEncSmallRoi = 198;    // ... and a frame's with a region-of-interest map its RoiRec (behind the MaskRec)
 
 struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bitstream.h)
   int device_req, device = -1;
@@ -286,6 +288,16 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   uint16_t *d_iscale = nullptr;
   hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr;
   thip_enc_mask_stats kstats;
+  // region of interest (TH_ENCCTL_THIP_SET_ROI_MAP; thip_encode_roi.h): the encoder's copy of the map in force (roi_on), tight rows;
+  // the frame queued has its scales, on top of masking's, in d_iscale (roi_queued)
+  bool roi_on = false, roi_queued = false;
+  int roi_w = 0, roi_h = 0;
+  size_t roi_cap = 0;            // bytes of d_roimap
+  int8_t *d_roimap = nullptr;
+  uint32_t *d_roiclamp = nullptr;   // what the copy of a device map clamped
+  RoiPart *d_roipart = nullptr;
+  hipEvent_t ev_o0 = nullptr, ev_o1 = nullptr;
+  thip_enc_roi_stats ostats;
   // the rate-distortion mode decision (TH_ENCCTL_THIP_SET_RD_MODES; thip_encode_rd.h): the frame queued was decided by it (rd_queued)
   // with lambda rd_lam and the tables rd_used; rd_hti: DC luma, DC chroma, AC luma, AC chroma of the last inter packet
   bool rd = false, rd_queued = false;
@@ -400,6 +412,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   memset(&e->mstats, 0, sizeof(e->mstats));
   memset(&e->bstats, 0, sizeof(e->bstats));
   memset(&e->kstats, 0, sizeof(e->kstats));
+  memset(&e->ostats, 0, sizeof(e->ostats));
   memset(&e->dstats, 0, sizeof(e->dstats));
   memset(&e->sstats, 0, sizeof(e->sstats));
   memset(&e->zstats, 0, sizeof(e->zstats));
@@ -430,6 +443,7 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_mb4,                                                                                            // enc_modes_alloc
       (void **)&e->d_qii, (void **)&e->d_bqbits,                                                                     // enc_bqi_prepare
       (void **)&e->d_act, (void **)&e->d_mpart, (void **)&e->d_iscale,                                               // enc_mask_queue
+      (void **)&e->d_roimap, (void **)&e->d_roiclamp, (void **)&e->d_roipart,                                        // enc_roi_set, enc_roi_queue
       (void **)&e->d_cand, (void **)&e->d_rdbits,                                                                    // enc_rd_queue
       (void **)&e->d_skf,                                                                                            // enc_skip_queue
       (void **)&e->d_rdqsums,                                                                                        // enc_rdq_queue
@@ -465,13 +479,16 @@ static void enc_free_device(th_enc_ctx *e) {
   e->rate_dev = false;
   e->q_queued = false;
   e->mask_queued = false;
+  e->roi_on = e->roi_queued = false;   // (the map went with the buffers)
+  e->roi_cap = 0;
+  e->ostats.active = 0;
   e->rd_queued = false;
   e->skip_queued = false;
   e->rdq_queued = false;
   e->probe_queued = false;
   for (hipEvent_t *ev : {&e->ev_in, &e->ev_read, &e->ev_t0, &e->ev_done, &e->ev_p0, &e->ev_p1, &e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1,
                           &e->ev_c0, &e->ev_c1, &e->ev_conv, &e->ev_m0, &e->ev_m1, &e->ev_a0, &e->ev_a1, &e->ev_r0, &e->ev_r1, &e->ev_s0, &e->ev_s1,
-                          &e->ev_z0, &e->ev_z1}) {
+                          &e->ev_z0, &e->ev_z1, &e->ev_o0, &e->ev_o1}) {
     if (*ev) (void)hipEventDestroy(*ev);
     *ev = nullptr;
   }
@@ -633,9 +650,9 @@ static int enc_mask_queue(th_enc_ctx *e, const EncPlanes &g) {
     for (hipEvent_t *ev : {&e->ev_a0, &e->ev_a1})
       if (!*ev) ENC_TRY(hipEventCreate(ev));
     ENC_TRY(hipMalloc((void **)&e->d_mpart, (size_t)mask_parts(nluma) * sizeof(MaskPart)));
-    ENC_TRY(hipMalloc((void **)&e->d_iscale, (size_t)e->nfrags * 2));
     ENC_TRY(hipMalloc((void **)&e->d_act, (size_t)nluma * 4));
   }
+  if (!e->d_iscale) ENC_TRY(hipMalloc((void **)&e->d_iscale, (size_t)e->nfrags * 2));   // (enc_roi_queue's too)
   ENC_TRY(hipEventRecord(e->ev_a0, e->stream));
   ENC_TRY(mask_launch_act(e->d_act, e->d_mpart, g, e->stream));
   ENC_TRY(mask_launch_scale(e->d_iscale, (MaskRec *)(e->d_small + kEncSmallMask), e->d_act, e->d_mpart, g, e->nfrags, e->mask, e->stream));
@@ -655,6 +672,88 @@ static void enc_mask_stats(th_enc_ctx *e, bool queued) {
   e->kstats.activity_avg = (int64_t)rec->avg;
   e->kstats.activity_max = (int64_t)rec->max;
   e->kstats.mask_ms = hipEventElapsedTime(&ms, e->ev_a0, e->ev_a1) == hipSuccess ? ms : 0.0;
+}
+
+// region of interest (thip_encode_roi.h), with block qi on and a map in force: every fragment's final scale -- on top of masking's,
+// whose launches the caller has queued -- in front of the block-qi kernel; the frame's extremes go to d_small behind masking's record
+// and come back with it (enc_queue_tail).  No host wait
+static int enc_roi_queue(th_enc_ctx *e, const EncPlanes &g) {
+  e->roi_queued = false;
+  if (!e->roi_on || !e->bqi) return 0;
+  if (!e->d_roipart) {
+    for (hipEvent_t *ev : {&e->ev_o0, &e->ev_o1})
+      if (!*ev) ENC_TRY(hipEventCreate(ev));
+    ENC_TRY(hipMalloc((void **)&e->d_roipart, (size_t)roi_parts(e->nfrags) * sizeof(RoiPart)));
+  }
+  if (!e->d_iscale) ENC_TRY(hipMalloc((void **)&e->d_iscale, (size_t)e->nfrags * 2));   // (enc_mask_queue's too)
+  ENC_TRY(hipEventRecord(e->ev_o0, e->stream));
+  ENC_TRY(roi_launch_scale(e->d_iscale, e->mask_queued ? (const uint16_t *)e->d_iscale : nullptr, e->d_roipart,
+                           (RoiRec *)(e->d_small + kEncSmallRoi), e->d_roimap, e->roi_w, e->roi_h, e->roi_w, e->d_roiclamp, g, e->nfrags,
+                           e->stream));
+  ENC_TRY(hipEventRecord(e->ev_o1, e->stream));
+  e->roi_queued = true;
+  return 0;
+}
+
+// the last packet's thip_enc_roi_stats: those of a frame coded without a map, or (queued: after the frame's wait) the frame's own
+static void enc_roi_stats(th_enc_ctx *e, bool queued) {
+  memset(&e->ostats, 0, sizeof(e->ostats));
+  e->ostats.active = e->roi_on ? 1 : 0;
+  e->ostats.map_width = e->roi_on ? e->roi_w : 0;
+  e->ostats.map_height = e->roi_on ? e->roi_h : 0;
+  if (!queued) return;
+  float ms = 0;
+  const RoiRec *rec = (const RoiRec *)(e->h_small + kEncSmallRoi);
+  e->ostats.measured = 1;
+  e->ostats.exp_min = rec->exp_min;
+  e->ostats.exp_max = rec->exp_max;
+  e->ostats.exp_sum = rec->exp_sum;
+  e->ostats.scale_min = (int32_t)rec->scale_min;
+  e->ostats.scale_max = (int32_t)rec->scale_max;
+  e->ostats.clamped = (int32_t)rec->clamped;
+  e->ostats.roi_ms = hipEventElapsedTime(&ms, e->ev_o0, e->ev_o1) == hipSuccess ? ms : 0.0;
+}
+
+// the scales the frame queued has in d_iscale (masking's, the map's, or both), or nullptr: the plain block-qi forms
+static const uint16_t *enc_iscale(const th_enc_ctx *e) { return e->mask_queued || e->roi_queued ? e->d_iscale : nullptr; }
+
+// TH_ENCCTL_THIP_SET_ROI_MAP, its checks made: the encoder's tight copy of the map.  A host map goes up before the call returns; a
+// device map is copied, clamped and counted behind the caller's stream, which then waits for the copy alone
+static int enc_roi_set(th_enc_ctx *e, const thip_enc_roi_map *a) {
+  if (enc_ensure_device(e)) return TH_EFAULT;
+  DeviceGuard g(e->device);
+  const size_t bytes = (size_t)a->width * a->height;
+  if (!e->d_roiclamp) ENC_TRY(hipMalloc((void **)&e->d_roiclamp, 4));
+  if (e->roi_cap < bytes) {
+    e->roi_on = false;
+    if (e->d_roimap) ENC_TRY(hipFree(e->d_roimap));   // (no frame is pending: nothing reads it)
+    e->d_roimap = nullptr;
+    e->roi_cap = 0;
+    ENC_TRY(hipMalloc((void **)&e->d_roimap, bytes));
+    e->roi_cap = bytes;
+  }
+  if (a->device) {
+    hipStream_t cs = (hipStream_t)a->stream;
+    if (!e->ev_conv) ENC_TRY(hipEventCreateWithFlags(&e->ev_conv, hipEventDisableTiming));
+    ENC_TRY(hipEventRecord(e->ev_in, cs));
+    ENC_TRY(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+    ENC_TRY(roi_launch_copy(e->d_roimap, e->d_roiclamp, a->map, a->pitch, a->width, a->height, e->stream));
+    ENC_TRY(hipEventRecord(e->ev_conv, e->stream));   // the caller's map has been read
+    ENC_TRY(hipStreamWaitEvent(cs, e->ev_conv, 0));
+  } else {
+    ENC_TRY(hipMemsetAsync(e->d_roiclamp, 0, 4, e->stream));
+    ENC_TRY(hipMemcpy2DAsync(e->d_roimap, (size_t)a->width, a->pitch < 0 ? a->map + (int64_t)(a->height - 1) * a->pitch : a->map,
+                             (size_t)(a->pitch < 0 ? -a->pitch : a->pitch), (size_t)a->width, (size_t)a->height, hipMemcpyHostToDevice,
+                             e->stream));
+    ENC_TRY(hipStreamSynchronize(e->stream));   // (the caller's memory is free at return)
+  }
+  e->roi_w = a->width;
+  e->roi_h = a->height;
+  e->roi_on = true;
+  e->ostats.active = 1;
+  e->ostats.map_width = a->width;
+  e->ostats.map_height = a->height;
+  return 0;
 }
 
 // the rate-distortion mode decision in place of k_enc_me_all's (thip_encode_rd.h): the candidates, then the choice into d_mb4.  Its
@@ -708,7 +807,7 @@ static int enc_skip_queue(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, 
   ENC_TRY(hipEventRecord(e->ev_s0, e->stream));
   ENC_TRY(skip_launch(InterBufs{e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192}, e->d_qii,
                       SkipOut{e->d_skf, nullptr, nullptr, nullptr}, e->d_order, g, R, G, d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel,
-                      e->mask_queued ? (const uint16_t *)e->d_iscale : nullptr, -1, e->nfrags, e->stream));
+                      enc_iscale(e), -1, e->nfrags, e->stream));
   ENC_TRY(hipEventRecord(e->ev_s1, e->stream));
   e->skip_queued = true;
   return 0;
@@ -758,7 +857,7 @@ static int enc_rdq_queue(th_enc_ctx *e, int classes, const EncPlanes &g, const B
   ENC_TRY(hipMemsetAsync(e->d_rdqsums, 0, kRdqSums * sizeof(unsigned long long), e->stream));
   ENC_TRY(rdq_launch(classes, e->d_levels, qii, e->d_cmap, RdqOut{nullptr, nullptr, nullptr, e->d_rdqsums}, e->d_order, g, R, G, d_mb,
                      e->nmbx, classes ? e->d_dqi : e->d_dequant, classes ? 6 : 3, e->d_bqbits, sel,
-                     e->mask_queued ? (const uint16_t *)e->d_iscale : nullptr, -1, e->rdq, e->nfrags, e->stream));
+                     enc_iscale(e), -1, e->rdq, e->nfrags, e->stream));
   ENC_TRY(hipEventRecord(e->ev_z1, e->stream));
   e->rdq_queued = true;
   return 0;
@@ -849,7 +948,8 @@ static int enc_queue_tail(th_enc_ctx *e) {
   const int64_t n = e->nfrags;
   ENC_TRY(tok_launch_scan(e->d_base, e->d_small, e->d_cnt, n, e->stream));
   ENC_TRY(tok_launch_scatter(e->d_out, e->d_tok, e->d_mask, e->d_base, e->d_small, n, e->stream));
-  const size_t nsmall = e->mask_queued ? kEncSmallMask + sizeof(MaskRec) / 4 : 193;   // (a masked frame: its record too)
+  // (a masked frame: its record too; a frame with a map: both places)
+  const size_t nsmall = e->roi_queued ? kEncSmallRoi + sizeof(RoiRec) / 4 : e->mask_queued ? kEncSmallMask + sizeof(MaskRec) / 4 : 193;
   ENC_TRY(hipMemcpyAsync(e->h_small, e->d_small, nsmall * 4, hipMemcpyDeviceToHost, e->stream));
   if (!e->frame_key) {
     if (e->modes) ENC_TRY(hipMemcpyAsync(e->h_mb4, e->d_mb4, (size_t)e->nmbs * sizeof(uint4), hipMemcpyDeviceToHost, e->stream));
@@ -890,7 +990,7 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   const dim3 gfq((unsigned)((4 * n + 255) / 256)), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
-  if (enc_mask_queue(e, g)) return TH_EFAULT;
+  if (enc_mask_queue(e, g) || enc_roi_queue(e, g)) return TH_EFAULT;
   if constexpr (sizeof(Word) == sizeof(uint32_t)) {
     if (stats) ENC_TRY(cut_launch_mb_modes(d_mb, stats, e->nmbs, lambda, e->stream));
     else ENC_TRY(inter_launch_search(d_mb, g, R, e->nmbx, e->nmbs, lambda, e->stream));
@@ -902,7 +1002,7 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   if (e->skip) {
     const EncRef *G[] = {&R, &gold...};   // (GOLD where the word has it, else PREV, which is not read)
     if (enc_skip_queue(e, g, sel, (const Word *)d_mb, R, *G[sizeof...(Gold)])) return TH_EFAULT;
-  } else if (e->mask_queued) {
+  } else if (enc_iscale(e)) {
     hipLaunchKernelGGL(k_fq_mask, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
                        e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
     ENC_TRY(hipGetLastError());
@@ -1083,6 +1183,7 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   }
   const int64_t n = e->nfrags;
   e->mask_queued = false;   // (enc_mask_queue says otherwise; a dropped frame never gets there)
+  e->roi_queued = false;    // (enc_roi_queue likewise)
   e->rd_queued = false;     // (enc_rd_queue likewise)
   e->skip_queued = false;   // (enc_skip_queue likewise)
   e->rdq_queued = false;    // (enc_rdq_queue likewise)
@@ -1136,8 +1237,8 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   if (enc_bqi_prepare(e, sel)) return TH_EFAULT;
   if (!e->frame_key) return enc_queue_inter(e, g, sel, searched ? (const uint4 *)e->d_rmbs : nullptr);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
-  if (enc_mask_queue(e, g)) return TH_EFAULT;
-  if (e->mask_queued)
+  if (enc_mask_queue(e, g) || enc_roi_queue(e, g)) return TH_EFAULT;
+  if (enc_iscale(e))
     hipLaunchKernelGGL(k_enc_intra_fq_bqi_mask, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
                        e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
   else if (e->bqi)
@@ -1463,6 +1564,7 @@ static void enc_empty_packet(th_enc_ctx *e) {
   e->stats.qi = e->frame_qi;
   memset(&e->bstats, 0, sizeof(e->bstats));
   enc_mask_stats(e, false);
+  enc_roi_stats(e, false);
   enc_rd_stats(e, false);
   enc_skip_stats(e, false);
   enc_rdq_stats(e, false);
@@ -1679,6 +1781,7 @@ static int enc_finish_frame(th_enc_ctx *e) {
   if (total > (size_t)e->nfrags * kEncTokWords) return TH_EFAULT;
   memset(&e->pstats, 0, sizeof(e->pstats));
   enc_mask_stats(e, e->mask_queued);   // (an empty packet takes them back)
+  enc_roi_stats(e, e->roi_queued);
   enc_rd_stats(e, e->rd_queued);
   enc_skip_stats(e, e->skip_queued);
   enc_rdq_stats(e, e->rdq_queued);
@@ -1988,6 +2091,30 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       e->kstats.ratio = k;
       return 0;
     }
+    case TH_ENCCTL_THIP_SET_ROI_MAP: {
+      if (!buf) return TH_EFAULT;
+      if (buf_sz != sizeof(thip_enc_roi_map)) return TH_EINVAL;
+      const thip_enc_roi_map *a = (const thip_enc_roi_map *)buf;
+      if (e->frame_pending || e->done) return TH_EINVAL;
+      if (!a->map) {
+        e->roi_on = false;   // (its buffers stay)
+        e->ostats.active = e->ostats.map_width = e->ostats.map_height = 0;
+        return 0;
+      }
+      if (a->width < 1 || a->width > 16384 || a->height < 1 || a->height > 16384 || (a->device != 0 && a->device != 1)) return TH_EINVAL;
+      if ((a->pitch < 0 ? -a->pitch : a->pitch) < a->width) return TH_EINVAL;
+      if (!a->device)
+        for (int y = 0; y < a->height; y++)
+          for (int x = 0; x < a->width; x++) {
+            const int v = a->map[(int64_t)y * a->pitch + x];
+            if (v < -64 || v > 64) return TH_EINVAL;
+          }
+      return enc_roi_set(e, a);
+    }
+    case TH_ENCCTL_THIP_GET_ROI_STATS:
+      if (!buf || buf_sz != sizeof(thip_enc_roi_stats)) return TH_EINVAL;
+      *(thip_enc_roi_stats *)buf = e->ostats;
+      return 0;
     case TH_ENCCTL_THIP_SET_RD_MODES: {
       if (!buf || buf_sz != sizeof(int)) return TH_EINVAL;
       if (enc_begun(e)) return TH_EINVAL;
@@ -2734,6 +2861,50 @@ int thip_enc_mask_stage(const thip_enc_mask_req *q) {
   hipStream_t stream = nullptr;
   ENC_TRY(mask_launch_act(q->act, d_part, g, stream));
   ENC_TRY(mask_launch_scale(q->iscale, (MaskRec *)q->avg, q->act, d_part, g, geo.nfrags, q->ratio, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the region-of-interest stage on the caller's map (theora_hip.h): thip_encode_roi.h's launch function, as enc_roi_queue makes it, on
+// the current device's null stream
+int thip_enc_roi_stage(const thip_enc_roi_req *q) {
+  if (!q) return THIP_EFAULT;
+  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
+      q->frame_height >= (1 << 20))
+    return THIP_EINVAL;
+  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
+  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
+  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
+  if (n64 > ((int64_t)1 << 24)) return THIP_EINVAL;
+  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
+      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
+    return THIP_EINVAL;
+  if (!q->map || !q->iscale || !q->stats) return THIP_EFAULT;
+  if (q->map_width < 1 || q->map_width > 16384 || q->map_height < 1 || q->map_height > 16384) return THIP_EINVAL;
+  if ((q->map_pitch < 0 ? -q->map_pitch : q->map_pitch) < q->map_width) return THIP_EINVAL;
+  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (misaligned(q->mask_iscale, 2) || misaligned(q->iscale, 2) || misaligned(q->stats, 8)) return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  EncPlanes g = {};
+  for (int p = 0; p < 3; p++) {
+    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
+    g.px0[p] = q->pic_x >> hd;
+    g.py0[p] = q->pic_y >> vd;
+    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
+    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
+    g.nh[p] = geo.nh[p];
+    g.nv[p] = geo.nv[p];
+    g.froff[p] = geo.fro[p];
+  }
+  RoiPart *d_part = nullptr;
+  ENC_TRY(hipMalloc((void **)&d_part, (size_t)roi_parts(geo.nfrags) * sizeof(RoiPart)));
+  struct Free { RoiPart *p; ~Free() { (void)hipFree(p); } } guard{d_part};
+  hipStream_t stream = nullptr;
+  ENC_TRY(roi_launch_scale(q->iscale, q->mask_iscale, d_part, (RoiRec *)q->stats, q->map, q->map_width, q->map_height, q->map_pitch, nullptr,
+                           g, geo.nfrags, stream));
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

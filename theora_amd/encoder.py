@@ -45,6 +45,8 @@ TH_ENCCTL_THIP_SET_RD_SKIP = 0x721E
 TH_ENCCTL_THIP_GET_SKIP_STATS = 0x721F
 TH_ENCCTL_THIP_SET_RD_QUANT = 0x7222   # (0x7220 and 0x7221 are not used)
 TH_ENCCTL_THIP_GET_RD_QUANT_STATS = 0x7223
+TH_ENCCTL_THIP_SET_ROI_MAP = 0x7225   # (0x7224 is not used)
+TH_ENCCTL_THIP_GET_ROI_STATS = 0x7226
 RD_QUANT_DEFAULT = 3   # the recommended weight w (lambda's weight w / 16): include/theoraenc_hip.h, "Level choice"
 TWO_PASS_HEADER_BYTES, TWO_PASS_RECORD_BYTES = 1084, 264   # THIP_2PASS_HEADER_BYTES, THIP_2PASS_RECORD_BYTES
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
@@ -114,6 +116,19 @@ class MaskStats(C.Structure):
     """thip_enc_mask_stats (include/theoraenc_hip.h)."""
     _fields_ = [("ratio", C.c_int32), ("measured", C.c_int32), ("activity_avg", C.c_int64), ("activity_max", C.c_int64),
                 ("mask_ms", C.c_double)]
+
+
+class RoiMap(C.Structure):
+    """thip_enc_roi_map (include/theoraenc_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("device", C.c_int32), ("pad", C.c_int32), ("pitch", C.c_int64),
+                ("map", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class RoiStats(C.Structure):
+    """thip_enc_roi_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("active", C.c_int32), ("measured", C.c_int32), ("map_width", C.c_int32), ("map_height", C.c_int32),
+                ("exp_min", C.c_int32), ("exp_max", C.c_int32), ("exp_sum", C.c_int64), ("scale_min", C.c_int32),
+                ("scale_max", C.c_int32), ("clamped", C.c_int32), ("reserved", C.c_int32), ("roi_ms", C.c_double)]
 
 
 class RdStats(C.Structure):
@@ -269,6 +284,63 @@ class Encoder:
         if rc < 0:
             raise ValueError("masking must be 0 or 2..16, set before the first frame (TH_ENCCTL_THIP_SET_MASKING returned %d)" % rc)
         self.masking = int(k)
+
+    def set_roi(self, map, stream=None):
+        """TH_ENCCTL_THIP_SET_ROI_MAP: the importance map of every frame queued from now on, until the next call (include/theoraenc_hip.h,
+        "Region of interest"); not between encode() and packetout().  map: a 2-D int8 numpy array or torch CUDA tensor on the
+        encoder's device, entries -64..64 in 1/16 octave of lambda, positive more important, row 0 the picture's top row, of any size
+        up to 16384 x 16384 (it is stretched over the picture); or a 2-D float array or tensor in octaves, read as
+        clamp(round(16 x), -64, 64); or None: no map.  A tensor is read ordered on `stream` (default torch's current stream) and may
+        be overwritten from that stream at once; rows may have a pitch of their own, the innermost stride must be 1.  No effect
+        without block_qi."""
+        a = RoiMap()
+        if map is None:
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_SET_ROI_MAP, C.byref(a), C.sizeof(a))
+            if rc < 0:
+                raise TheoraHipError("TH_ENCCTL_THIP_SET_ROI_MAP returned %d" % rc)
+            return
+        host = isinstance(map, np.ndarray)
+        if host:
+            if map.ndim != 2:
+                raise ValueError("a region-of-interest map is 2-D")
+            if map.dtype.kind == "f":
+                map = np.clip(np.rint(16.0 * map.astype(np.float64)), -64, 64).astype(np.int8)
+            elif map.dtype != np.int8:
+                raise TypeError("a region-of-interest map is int8 (1/16 octave) or float (octaves)")
+            if map.strides[1] != 1:
+                map = np.ascontiguousarray(map)
+            shape, pitch, ptr = map.shape, map.strides[0], map.ctypes.data
+        else:
+            import torch
+            if not isinstance(map, torch.Tensor) or not map.is_cuda:
+                raise TypeError("a region-of-interest map is a numpy array or a torch CUDA tensor")
+            if map.dim() != 2:
+                raise ValueError("a region-of-interest map is 2-D")
+            s = stream if stream is not None else torch.cuda.current_stream(map.device)
+            with torch.cuda.stream(s):
+                if map.dtype.is_floating_point:
+                    map = torch.clamp(torch.round(16.0 * map.to(torch.float64)), -64, 64).to(torch.int8)
+                elif map.dtype != torch.int8:
+                    raise TypeError("a region-of-interest map is int8 (1/16 octave) or float (octaves)")
+                if map.stride(1) != 1:
+                    map = map.contiguous()
+            shape, pitch, ptr = tuple(map.shape), map.stride(0), map.data_ptr()
+            a.stream = s.cuda_stream
+        if shape[0] == 0 or shape[1] == 0:
+            raise ValueError("a region-of-interest map has at least one entry")
+        a.height, a.width, a.device, a.pitch, a.map = shape[0], shape[1], int(not host), pitch if shape[0] > 1 else max(pitch, shape[1]), ptr
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_SET_ROI_MAP, C.byref(a), C.sizeof(a))
+        if rc < 0:
+            raise ValueError("the map is 1..16384 a side with entries in -64..64, set with no frame pending "
+                             "(TH_ENCCTL_THIP_SET_ROI_MAP returned %d)" % rc)
+
+    def roi_stats(self):
+        """TH_ENCCTL_THIP_GET_ROI_STATS of the last packet, as a dict (without reserved)."""
+        s = RoiStats()
+        rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_ROI_STATS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise TheoraHipError("TH_ENCCTL_THIP_GET_ROI_STATS returned %d" % rc)
+        return {k: getattr(s, k) for k, _ in RoiStats._fields_ if k != "reserved"}
 
     def set_rd_modes(self, on):
         """TH_ENCCTL_THIP_SET_RD_MODES, before the first frame: the rate-distortion mode decision on (True) or off."""
@@ -704,6 +776,20 @@ def mask_stage(frame, pixel_fmt, ratio, pic=None, src=None, src_pitch=None, act=
         q.src_pitch[p] = 0 if src_pitch is None else int(src_pitch[p])
     q.act, q.avg, q.iscale = act, avg, iscale
     return L.thip_enc_mask_stage(C.byref(q))
+
+
+def roi_stage(frame, pixel_fmt, map_size, map_pitch, map, pic=None, mask_iscale=None, iscale=None, stats=None):
+    """thip_enc_roi_stage (include/theora_hip.h): the scales of a region-of-interest map, a test and diagnostic entry.  frame: (width,
+    height); pic: (x, y, width, height), the whole frame when None; map_size: (width, height) of the map; map (int8 rows at
+    map_pitch), mask_iscale (uint16 [nfrags], masking's scales), iscale (uint16 [nfrags]) and stats (int32 [8]): device addresses,
+    None is NULL.  Returns the entry's return code; nothing is raised, the refusals are the caller's to look at."""
+    L = _lib.load()
+    q = _lib.EncRoiReq()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q.map_width, q.map_height, q.map_pitch = int(map_size[0]), int(map_size[1]), int(map_pitch)
+    q.map, q.mask_iscale, q.iscale, q.stats = map, mask_iscale, iscale, stats
+    return L.thip_enc_roi_stage(C.byref(q))
 
 
 def rd_stage(frame, pixel_fmt, stages, pic=None, lambda_search=0, lambda_rd=0, src=None, src_pitch=None, prev=None, gold=None,

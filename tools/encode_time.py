@@ -23,6 +23,10 @@ counts the key frames it made (none on the panning sequence).
 With --masking K (with --block-qi, in quality mode): activity masking at ratio K (TH_ENCCTL_THIP_SET_MASKING); mask_ms is the device
 time of its two launches (TH_ENCCTL_THIP_GET_MASK_STATS), which device_ms includes.
 
+With --roi RES (with --block-qi, key frames in quality mode): a region-of-interest map (TH_ENCCTL_THIP_SET_ROI_MAP) at macro-block
+resolution (RES = mb) or pixel resolution (RES = pixel), seeded noise in +-32 set once from host memory; roi_ms is the device time of
+its two launches (TH_ENCCTL_THIP_GET_ROI_STATS), which device_ms includes.
+
 With --rd-modes (with --inter N --all-modes): the eight-mode cases run with the rate-distortion mode decision on
 (TH_ENCCTL_THIP_SET_RD_MODES); rd_ms is the device time of its two launches (TH_ENCCTL_THIP_GET_RD_STATS), which device_ms includes.
 --rd-skip: with --inter, every case with the skip decision on (TH_ENCCTL_THIP_SET_RD_SKIP); skip_ms is the device time of its two
@@ -38,7 +42,7 @@ waits in quality mode, first pass or not), call_ms the whole call with th_encode
 p1_wait_ms the host's wait in th_encode_packetout for its 512 bytes (TH_ENCCTL_THIP_GET_2PASS_STATS) -- and then the second pass over
 that pass file (p2_*; its probe is waited for, as in bitrate mode).
 
-  python tools/encode_time.py [--two-pass] [--frames 20] [--inter N [--all-modes [--rd-modes]] [--rd-skip]] [--rd-quant W] [--bitrate B] [--block-qi D [--masking K]] [--device-pack]
+  python tools/encode_time.py [--two-pass] [--frames 20] [--inter N [--all-modes [--rd-modes]] [--rd-skip]] [--rd-quant W] [--bitrate B] [--block-qi D [--masking K] [--roi mb|pixel]] [--device-pack]
                               [--auto-keyframes [T]] [--json out.json]
 """
 import argparse
@@ -84,6 +88,7 @@ def main():
     ap.add_argument("--all-modes", action="store_true", help="with --inter: each case with all eight modes off, then on")
     ap.add_argument("--block-qi", type=int, default=0, help="block-level qi with this delta (TH_ENCCTL_THIP_SET_BLOCK_QI)")
     ap.add_argument("--masking", type=int, default=0, help="with --block-qi: activity masking at this ratio (TH_ENCCTL_THIP_SET_MASKING)")
+    ap.add_argument("--roi", choices=("mb", "pixel"), help="with --block-qi, key frames: a region-of-interest map at this resolution")
     ap.add_argument("--rd-modes", action="store_true", help="with --inter --all-modes: the eight-mode cases with TH_ENCCTL_THIP_SET_RD_MODES on")
     ap.add_argument("--rd-skip", action="store_true", help="with --inter: every case with TH_ENCCTL_THIP_SET_RD_SKIP on")
     ap.add_argument("--rd-quant", type=int, default=0, metavar="W", help="every case with TH_ENCCTL_THIP_SET_RD_QUANT = W (1..64)")
@@ -108,7 +113,10 @@ def main():
         for q, dp in [(q, dp) for q in (16, 48) for dp in ((False, True) if args.device_pack else (False,))]:
             e = Encoder(w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking, rd_quant=args.rd_quant)
             hdr = e.header_packets()
-            dev, host, wall, pack, mask, zqms = [], [], [], [], [], []
+            dev, host, wall, pack, mask, zqms, roims = [], [], [], [], [], [], []
+            if args.roi:
+                mw, mh = (p[2], p[3]) if args.roi == "pixel" else ((p[2] + 15) // 16, (p[3] + 15) // 16)
+                e.set_roi(np.random.default_rng(7).integers(-32, 33, (mh, mw)).astype(np.int8))
             for f in range(args.frames + 3):
                 t0 = time.perf_counter()
                 e.encode(frame)
@@ -122,6 +130,7 @@ def main():
                     pack.append(e.pack_stats()["pack_ms"])
                     mask.append(e.mask_stats()["mask_ms"])
                     zqms.append(e.rd_quant_stats()["rdq_ms"])
+                    roims.append(e.roi_stats()["roi_ms"])
             st = e.stats()
             e.close()
             qs = quality_pass([frame], w, h, 0, q, pic=pic, block_qi=args.block_qi, device_pack=dp, masking=args.masking,
@@ -137,6 +146,8 @@ def main():
                 r.update(masking=args.masking, mask_ms=round(float(np.median(mask)), 4))
             if args.rd_quant:
                 r.update(rd_quant=args.rd_quant, rdq_ms=round(float(np.median(zqms)), 4))
+            if args.roi:
+                r.update(roi=args.roi, roi_ms=round(float(np.median(roims)), 4))
             print(json.dumps(r), flush=True)
             rows.append(r)
     if args.json:
