@@ -2,7 +2,7 @@
  * and its Ogg writer (include/thip_ogg.h).
  *
  *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta [--roi x,y,w,h,v]] [-V kbps]
- *                       [--first-pass FILE | --second-pass FILE | --two-pass] [-o out.ogv] in.y4m
+ *                       [--first-pass FILE | --second-pass FILE | --two-pass | --train-huffman] [-o out.ogv] in.y4m
  *
  * Input: C420jpeg, C420, C420paldv, C420mpeg2 (4:2:0), C422 or C444, any size; no C tag means 4:2:0.  The frame is the picture
  * padded to multiples of 16, the picture region at (0, 0); the picture-size planes go to th_encode_ycbcr_in as they are.  Every
@@ -19,6 +19,11 @@
  * --first-pass FILE encodes once, writes the pass file and no video (with -V the first pass runs in bitrate mode, else at -q);
  * --second-pass FILE (needs -V) encodes to that file's curves; --two-pass (needs -V) does both through a temporary file, the first
  * pass at -q, and reads the input twice, so the input must be a file.
+ *
+ * --train-huffman ("Huffman codes" in theoraenc_hip.h): encodes the input once with the built-in Huffman codes and keeps every
+ * packet's token histogram (TH_ENCCTL_THIP_GET_TOKEN_HIST), trains codes on them (thip_huff_train, 8 rounds), and encodes the input
+ * again with the trained codes (TH_ENCCTL_SET_HUFFMAN_CODES) into the output.  It reads the input twice too, so the input must be a
+ * seekable file; not together with the two-pass options.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,7 +76,26 @@ typedef struct {
   int quality, kf, all_modes, bqi, device_pack, auto_kf;
   long kbps;
   int roi, roi_rect[5];   /* --roi: x, y, w, h, v */
+  const th_huff_code (*codes)[TH_NDCT_TOKENS];   /* --train-huffman, the second run: the trained codes (NULL: the built-in ones) */
+  struct hist_pool *pool;                        /* ... the first run: every packet's histogram goes here (NULL: none is kept) */
 } options;
+
+typedef struct hist_pool {
+  thip_enc_token_hist *h;
+  size_t n, cap;
+} hist_pool;
+
+/* the last packet's histogram into the pool; 0 on success */
+static int keep_hist(th_enc_ctx *enc, hist_pool *pool) {
+  if (pool->n == pool->cap) {
+    const size_t cap = pool->cap ? 2 * pool->cap : 64;
+    thip_enc_token_hist *h = realloc(pool->h, cap * sizeof(*h));
+    if (!h) return -1;
+    pool->h = h;
+    pool->cap = cap;
+  }
+  return th_encode_ctl(enc, TH_ENCCTL_THIP_GET_TOKEN_HIST, &pool->h[pool->n++], sizeof(*pool->h));
+}
 
 /* feeds the second pass until it can take the next frame (libtheora's encoder_example loop); 0 on success */
 static int feed_pass_file(th_enc_ctx *enc, FILE *pf) {
@@ -129,6 +153,10 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
   th_enc_ctx *enc = th_encode_alloc(&ti);
   if (!enc) {
     fprintf(stderr, "th_encode_alloc refused the parameters\n");
+    return 1;
+  }
+  if (o->codes && th_encode_ctl(enc, TH_ENCCTL_SET_HUFFMAN_CODES, (void *)o->codes, sizeof(th_huff_code) * TH_NHUFFMAN_TABLES * TH_NDCT_TOKENS)) {
+    fprintf(stderr, "Huffman codes refused\n");
     return 1;
   }
   if (kf > 0) {   /* inter frames, a key frame every kf frames (clamped to 1 << keyframe_granule_shift) */
@@ -224,6 +252,10 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
         fprintf(stderr, "write error\n");
         return 1;
       }
+      if (o->pool && keep_hist(enc, o->pool)) {
+        fprintf(stderr, "out of memory\n");
+        return 1;
+      }
       if (pass == 1 && write_pass_bytes(enc, pf)) {   /* the packet's record */
         fprintf(stderr, "pass file write error\n");
         return 1;
@@ -249,7 +281,7 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
       return 1;
     }
   }
-  fprintf(stderr, "%d frames%s\n", nframes, pass == 1 ? " (first pass)" : pass == 2 ? " (second pass)" : "");
+  fprintf(stderr, "%d frames%s\n", nframes, pass == 1 ? " (first pass)" : pass == 2 ? " (second pass)" : o->pool ? " (histograms)" : "");
   thip_ogg_writer_free(ow);
   th_encode_free(enc);
   free(buf[0]);
@@ -258,9 +290,9 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
 }
 
 int main(int argc, char **argv) {
-  options o = {48, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0}};
+  options o = {48, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0}, NULL, NULL};
   const char *in_path = NULL, *out_path = NULL, *first = NULL, *second = NULL;
-  int two_pass = 0;
+  int two_pass = 0, train = 0;
   for (int i = 1; i < argc; i++) {
     if (strcmp(argv[i], "-q") == 0 && i + 1 < argc) o.quality = atoi(argv[++i]);
     else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) out_path = argv[++i];
@@ -275,12 +307,13 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[i], "--first-pass") == 0 && i + 1 < argc) first = argv[++i];
     else if (strcmp(argv[i], "--second-pass") == 0 && i + 1 < argc) second = argv[++i];
     else if (strcmp(argv[i], "--two-pass") == 0) two_pass = 1;
+    else if (strcmp(argv[i], "--train-huffman") == 0) train = 1;
     else in_path = argv[i];
   }
-  const int npass = (first != NULL) + (second != NULL) + two_pass;
+  const int npass = (first != NULL) + (second != NULL) + two_pass + train;
   if (!in_path || o.roi < 0 || (o.roi && !o.bqi) || ((o.all_modes || o.auto_kf) && o.kf <= 0) || npass > 1 || ((second || two_pass) && o.kbps <= 0) ||
-      (two_pass && strcmp(in_path, "-") == 0)) {
-    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi [--roi x,y,w,h,v: a region of interest, v in -64..64]] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file)] [-o out.ogv] in.y4m\n", argv[0]);
+      ((two_pass || train) && strcmp(in_path, "-") == 0)) {
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi [--roi x,y,w,h,v: a region of interest, v in -64..64]] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file) | --train-huffman (the input a file)] [-o out.ogv] in.y4m\n", argv[0]);
     return 1;
   }
   FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
@@ -301,6 +334,26 @@ int main(int argc, char **argv) {
     options p1 = o;
     p1.kbps = 0;
     if (encode(&p1, in, NULL, 1, pf) || fseek(pf, 0, SEEK_SET) || fseek(in, 0, SEEK_SET)) return 1;
+  }
+  static th_huff_code codes[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS];
+  if (train) {   /* the histograms with the built-in codes, the training, then the input again */
+    hist_pool pool = {NULL, 0, 0};
+    options p1 = o;
+    p1.pool = &pool;
+    thip_huff_train_stats st;
+    if (fseek(in, 0, SEEK_CUR)) {
+      fprintf(stderr, "--train-huffman reads the input twice: it must be a seekable file\n");
+      return 1;
+    }
+    if (encode(&p1, in, NULL, 0, NULL) || fseek(in, 0, SEEK_SET)) return 1;
+    if (thip_huff_train(pool.h, pool.n, NULL, 8, codes, &st)) {
+      fprintf(stderr, "thip_huff_train failed\n");
+      return 1;
+    }
+    fprintf(stderr, "trained on %zu packets: code bits %llu -> %llu in %d rounds, %d DC and %d AC tables in use\n", pool.n,
+            (unsigned long long)st.bits_start, (unsigned long long)st.bits_end, st.rounds, st.dc_tables, st.ac_tables);
+    free(pool.h);
+    o.codes = (const th_huff_code(*)[TH_NDCT_TOKENS])codes;
   }
   FILE *out = out_path ? fopen(out_path, "wb") : stdout;
   if (!out) {

@@ -42,6 +42,15 @@ typedef struct {
 } th_img_plane; /* codec.h:144-153 */
 typedef th_img_plane th_ycbcr_buffer[3];
 
+/* A Huffman code of one DCT token (codec.h): the low nbits bits of pattern, the first bit of the code the most significant of
+   them.  TH_ENCCTL_SET_HUFFMAN_CODES (theoraenc_hip.h) takes a th_huff_code[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS]. */
+#define TH_NHUFFMAN_TABLES (80)
+#define TH_NDCT_TOKENS (32)
+typedef struct {
+  uint32_t pattern;
+  int nbits;
+} th_huff_code;
+
 typedef struct { /* codec.h:206-299 */
   unsigned char version_major, version_minor, version_subminor;
   uint32_t frame_width, frame_height;

@@ -6,8 +6,8 @@
  * What it is not, by default: every data packet is a key frame.  There is no mode decision, motion search or rate control by
  * default.  Bitrate mode is entered through TH_ENCCTL_SET_BITRATE after th_encode_alloc ("Bitrate mode" below); th_info.target_bitrate
  * != 0 at th_encode_alloc is refused (NULL).  Two-pass encoding goes through TH_ENCCTL_THIP_2PASS_OUT / _IN ("Two-pass" below;
- * libtheora's own requests 24 and 26 answer TH_EIMPL, their record format is not this one).  Custom Huffman codes or quantisation
- * parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
+ * libtheora's own requests 24 and 26 answer TH_EIMPL, their record format is not this one).  Custom Huffman codes are taken through TH_ENCCTL_SET_HUFFMAN_CODES
+ * ("Huffman codes" below); custom quantisation parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
  *
  * The bitstream, stated so that a restatement reproduces the packets byte for byte (tests/enc_ref.py does):
  *   - Setup header.  Loop-filter limits lflim[qi] = (31 * (63 - qi) + 31) / 63.  AC and DC scales fall geometrically,
@@ -17,8 +17,9 @@
  *     whose two ends are the same base matrix, so every quantiser step of spec 6.4.3 is max(qmin, min(scale[qi] bm / 100 * 4,
  *     4096)): non-increasing in qi.  80 Huffman trees: for Huffman group hg (0..4) and table t (0..15), t = 4 a + b, the
  *     Huffman code of 32 token weights with a sparsity s = {0.1, 0.3, 0.55, 0.8}[b] and a magnitude ratio q = {0.15, 0.35,
- *     0.55, 0.75}[a] (thip_encode.hip, enc_token_weights); every token has a code, none longer than 31 bits.  (The header is the same with
- *     inter frames on; the inter matrices are then used.)
+ *     0.55, 0.75}[a] (thip_encode.hip, enc_token_weights); every token has a code, none longer than 31 bits.  These built-in trees are
+ *     the default; TH_ENCCTL_SET_HUFFMAN_CODES replaces them ("Huffman codes" below) and changes nothing else of the header.  (The
+ *     header is the same with inter frames on; the inter matrices are then used.)
  *   - Frame.  An intra frame with one qi, qi = quality (TH_ENCCTL_SET_QUALITY changes it from the next frame); no block qi.
  *   - Blocks.  In coded order, each 8x8 block is pixel - 128, oc_enc_fdct8x8, oc_enc_quantize with the intra table of (plane,
  *     qi).  Pixels outside the picture region take the value of the nearest picture pixel (clamped coordinates) in every plane;
@@ -378,6 +379,34 @@
  *     B - A before the packet, fullness_after = B - A after it.  Block qi, masking, RD modes, the device packetiser and the quality
  *     statistics compose as with bitrate mode: the controller chooses qis[0].
  *
+ * Huffman codes (TH_ENCCTL_SET_HUFFMAN_CODES, TH_ENCCTL_THIP_GET_TOKEN_HIST, thip_huff_train), stated likewise (tests/enc_huff_ref.py
+ * restates them).  The 80 code sets are data to everything that counts or writes token bits: both packers, the block-qi choice, the
+ * rate-distortion mode, skip and level decisions and the rate probe read the code lengths in force, so a caller's codes change their
+ * prices with them; the rules above ("the table of least bits", "before there is one, 5") stay as stated.  With the same levels a
+ * different code set gives the same pictures: the codes are lossless.
+ *   - A code set is valid when every one of the 32 tokens has a code of 1..32 bits and the 32 codes form a full, prefix-free binary
+ *     code (what libtheora's oc_huff_codes_pack accepts; a full code of 32 leaves is at most 31 deep); bits of `pattern` above `nbits`
+ *     are ignored.  The setup header's tree of a set is then a function of its codes: pre-order, the 0 branch first.
+ *   - The histogram of a packet (thip_enc_token_hist): the packet's merged tokens -- after the EOB runs are merged, what the packet
+ *     holds -- counted per Huffman group of the list the token stands in (index 0; 1..5; 6..14; 15..27; 28..63), luma or chroma, and
+ *     token.  It is the histogram the packer chooses the packet's four tables from, whichever packer made the packet.
+ *   - thip_huff_train(hists, n, start, rounds, out, stats).  Samples: each histogram gives, for each class c (0 luma, 1 chroma), a DC
+ *     sample count[0][c] and an AC sample count[1..4][c]; a sample whose counts are all 0 is dropped.  The samples are kept in the
+ *     order packet, class, DC before AC.  DC and AC are trained apart, 16 tables each: DC table t is set t, AC table t the sets
+ *     16 hg + t for hg = 1..4.
+ *     Cost of a sample under table t: the sum of count x code length over its group or groups (the extra bits do not depend on the
+ *     table and are left out).  Assignment: every sample goes to the table of least cost, on a tie the lower index (the packet
+ *     writer's rule); the total cost is the sum of those least costs.
+ *     Rebuild: for a table with at least one sample, and each group it covers, H[tok] = the sum of its samples' counts; the set
+ *     becomes the Huffman code of the 32 weights 1024 H[tok] + 1 by the rule of the built-in trees: always merge the two lightest
+ *     nodes, ties to the lower node id (leaves are 0..31, internal nodes are numbered from 32 in creation order), child 0 (code bit 0)
+ *     the lighter of the two.  A table with no sample keeps its codes.
+ *     Loop: the codes are `start` (patterns masked to nbits), B = the total cost of the assignment under them.  Up to `rounds` times:
+ *     rebuild from the current assignment, assign anew under the rebuilt codes, giving B'; if B' < B the rebuilt codes, the new
+ *     assignment and B = B' are accepted, otherwise the loop stops and the codes stay.  So bits_end <= bits_start always.  All sums
+ *     are unsigned 64-bit and wrap; they are exact while the counts of all histograms together stay below 2^49.
+ *     Empty tables are not reseeded or split: a pool whose samples all prefer a few tables trains those few.
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / _RGB_IN / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
  * extensions, YCBCR_IN_DEVICE, RGB_IN, GET_DEVICE and GET_QUALITY_STATS do.
@@ -410,8 +439,13 @@ extern "C" {
 #define TH_RATECTL_DROP_FRAMES (0x1)
 #define TH_RATECTL_CAP_OVERFLOW (0x2)
 #define TH_RATECTL_CAP_UNDERFLOW (0x4)
-/* Known, and answered TH_EIMPL: */
+/* buf = th_huff_code[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS] and buf_sz exactly its size (2560 x sizeof(th_huff_code)): the codes
+   replace the context's ("Huffman codes" above).  buf = NULL with buf_sz = 0: the built-in codes again.  Both only before the first
+   th_encode_flushheader has returned a packet and before the first frame, else TH_EINVAL.  A code set that is not valid: TH_EINVAL,
+   and the context's codes stay as they were.  ANY OTHER buf_sz: TH_EIMPL, where libtheora answers TH_EINVAL -- the one deviation,
+   kept because callers probe this request with an int to learn that custom codes were not available.  Never touches the GPU. */
 #define TH_ENCCTL_SET_HUFFMAN_CODES (0)
+/* Known, and answered TH_EIMPL: */
 #define TH_ENCCTL_SET_QUANT_PARAMS (2)
 #define TH_ENCCTL_SET_VP3_COMPATIBLE (10)
 #define TH_ENCCTL_GET_SPLEVEL (16)
@@ -692,6 +726,35 @@ typedef struct thip_enc_roi_stats {   /* 56 bytes */
   int32_t reserved;
   double roi_ms;           /* HIP events around the two launches */
 } thip_enc_roi_stats;
+
+/* Extension: buf = thip_enc_token_hist, describing the last packet th_encode_packetout returned ("Huffman codes" above).  A
+   zero-byte packet, a duplicate and a dropped frame give all zeros.  With the device packetiser the counts come back with the
+   record the packet waits for anyway (1 280 more bytes in the same copy); the request itself never touches the GPU. */
+#define TH_ENCCTL_THIP_GET_TOKEN_HIST (0x7227)
+typedef struct thip_enc_token_hist {   /* 1304 bytes */
+  uint32_t count[5][2][32];  /* merged tokens of the last packet: Huffman group, luma / chroma, token (EOB runs after the merge) */
+  int32_t huff[4];           /* the tables the packet used: DC luma, DC chroma, AC luma, AC chroma */
+  int32_t key;               /* 1 key frame, 0 inter */
+  int32_t device;            /* 1: counted by the device packetiser */
+} thip_enc_token_hist;
+/* Extension: buf = th_huff_code[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS] (buf_sz its size, else TH_EINVAL), receives the codes in force
+   (patterns masked to nbits), at any time.  Never touches the GPU. */
+#define TH_ENCCTL_THIP_GET_HUFFMAN_CODES (0x7228)
+
+/* The trainer of "Huffman codes" above: out = codes trained on the n histograms, from `start` (NULL: the built-in codes).  Host
+   arithmetic only, deterministic, no context and no GPU.  rounds 1..64.  stats may be NULL.  hists may be NULL when n = 0 (out =
+   start).  Returns 0; THIP_EFAULT (-1) for out NULL or hists NULL with n > 0; THIP_EINVAL (-10) for n > 2^20, rounds out of range
+   or a `start` that is not valid.  out may not overlap start. */
+typedef struct thip_huff_train_stats {   /* 32 bytes */
+  uint64_t bits_start;       /* the total cost under start */
+  uint64_t bits_end;         /* ... and under out: <= bits_start */
+  int32_t rounds;            /* rounds accepted */
+  int32_t dc_tables;         /* DC tables with at least one sample under out */
+  int32_t ac_tables;         /* AC tables with at least one sample under out */
+  int32_t samples;           /* samples kept, DC and AC together */
+} thip_huff_train_stats;
+int thip_huff_train(const thip_enc_token_hist *hists, size_t n, const th_huff_code start[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS], int rounds,
+                    th_huff_code out[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS], thip_huff_train_stats *stats);
 
 /* Extension: the first pass of "Two-pass" above, with TH_ENCCTL_2PASS_OUT's calling convention: buf = unsigned char **, buf_sz ==
    sizeof(unsigned char *) (else TH_EINVAL).  The first call must come before the first frame (else TH_EINVAL; TH_EINVAL too on a

@@ -359,6 +359,10 @@ ENC_SYMBOLS = [
     ("th_encode_packetout", _I, [_P, _I, C.POINTER(OggPacket)]),
     ("th_encode_free", None, [_P]),
 ]
+# ... and its trainer of Huffman codes (no context, no GPU)
+ENC_TOOL_SYMBOLS = [
+    ("thip_huff_train", _I, [_P, C.c_size_t, _P, _I, _P, _P]),
+]
 
 # include/thip_ogg.h
 OGG_SYMBOLS = [
@@ -392,7 +396,7 @@ def load():
             "%s not found: build it with `python -m theora_amd.build` (hipcc, gfx950). "
             "theora_amd has no CPU fallback." % SO_PATH)
     L = C.CDLL(SO_PATH)
-    for name, restype, argtypes in SYMBOLS + DEC_SYMBOLS + ENC_SYMBOLS + OGG_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + DEC_SYMBOLS + ENC_SYMBOLS + ENC_TOOL_SYMBOLS + OGG_SYMBOLS:
         fn = getattr(L, name)   # AttributeError if the library does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -33,6 +33,7 @@
 #include "thip_device.h"
 #include "thip_rate.h"
 #include "thip_ratectl.h"
+#include "thip_hufftrain.h"
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_mask.h"
@@ -108,43 +109,33 @@ void enc_token_weights(int hg, int t, double w[32]) {
   w[31] = (1 - s) * s * s * q;                                             // RUN_CAT2B
 }
 
-// Huffman code of 32 weights: always merge the two lightest (ties: the lower node id); child 0 = the lighter
-void huffman(const double w[32], uint32_t code[32], uint8_t len[32], BitW &tree) {
-  struct Node { uint64_t w; int c0, c1; };
-  std::vector<Node> nodes;
-  std::vector<int> live;
-  for (int k = 0; k < 32; k++) {
-    nodes.push_back({1 + (uint64_t)(w[k] * (double)(1ull << 40)), -1, k});
-    live.push_back(k);
-  }
-  while (live.size() > 1) {
-    int a = -1, b = -1;
-    for (size_t i = 0; i < live.size(); i++) {
-      const int x = live[i];
-      if (a < 0 || nodes[x].w < nodes[a].w || (nodes[x].w == nodes[a].w && x < a)) { b = a; a = x; }
-      else if (b < 0 || nodes[x].w < nodes[b].w || (nodes[x].w == nodes[b].w && x < b)) b = x;
+// the setup's codes and lengths from a valid code set, and the 80 trees as the header writes them (thip_hufftrain.h)
+void enc_setup_codes(EncSetup &s, const th_huff_code codes[80][32]) {
+  s.trees.clear();
+  BitW t{&s.trees};
+  for (int h = 0; h < 80; h++) {
+    for (int tok = 0; tok < 32; tok++) {
+      s.len[h][tok] = (uint8_t)codes[h][tok].nbits;
+      s.code[h][tok] = (uint32_t)((uint64_t)codes[h][tok].pattern & (((uint64_t)1 << codes[h][tok].nbits) - 1));
     }
-    nodes.push_back({nodes[a].w + nodes[b].w, a, b});
-    std::vector<int> nl;
-    for (int x : live)
-      if (x != a && x != b) nl.push_back(x);
-    nl.push_back((int)nodes.size() - 1);
-    live.swap(nl);
+    huff_tree_write(codes[h], [&](uint32_t v, int nb) { t.put(v, nb); });
   }
-  // pre-order walk: 0 = internal node, 1 + token = leaf
-  struct Walk { static void go(const std::vector<Node> &nd, int x, uint32_t c, int l, uint32_t *code, uint8_t *len, BitW &t) {
-    if (nd[x].c0 < 0) {
-      t.put(1, 1);
-      t.put((uint32_t)nd[x].c1, 5);
-      code[nd[x].c1] = c;
-      len[nd[x].c1] = (uint8_t)l;
-      return;
-    }
-    t.put(0, 1);
-    go(nd, nd[x].c0, c << 1, l + 1, code, len, t);
-    go(nd, nd[x].c1, c << 1 | 1, l + 1, code, len, t);
-  } };
-  Walk::go(nodes, live[0], 0, 0, code, len, tree);
+  s.tree_bits = (int64_t)s.trees.size() * 8 + t.n;
+  t.flush();
+}
+
+// the built-in codes: the Huffman code (thip_hufftrain.h, huff_build) of enc_token_weights in 40-bit fixed point
+void enc_builtin_codes(th_huff_code codes[80][32]) {
+  for (int h = 0; h < 80; h++) {
+    double w[32];
+    uint64_t wi[32];
+    uint32_t code[32];
+    uint8_t len[32];
+    enc_token_weights(h >> 4, h & 15, w);
+    for (int k = 0; k < 32; k++) wi[k] = 1 + (uint64_t)(w[k] * (double)(1ull << 40));
+    huff_build(wi, code, len);
+    for (int k = 0; k < 32; k++) codes[h][k] = th_huff_code{code[k], (int)len[k]};
+  }
 }
 
 void enc_setup_init(EncSetup &s) {
@@ -168,15 +159,9 @@ void enc_setup_init(EncSetup &s) {
       q.qrsizes[qti][pli][0] = 63;
       q.qrbmis[qti][pli][0] = q.qrbmis[qti][pli][1] = qti ? 2 : pli ? 1 : 0;
     }
-  s.trees.clear();
-  BitW t{&s.trees};
-  for (int h = 0; h < 80; h++) {
-    double w[32];
-    enc_token_weights(h >> 4, h & 15, w);
-    huffman(w, s.code[h], s.len[h], t);
-  }
-  s.tree_bits = (int64_t)s.trees.size() * 8 + t.n;
-  t.flush();
+  std::vector<th_huff_code> codes(80 * 32);
+  enc_builtin_codes((th_huff_code(*)[32])codes.data());
+  enc_setup_codes(s, (const th_huff_code(*)[32])codes.data());
 }
 
 // spec 7.2.1 (long: runs up to 4129, a new bit after a run of 4129) and 7.2.2 (short: runs up to 30, the bit always flips; the
@@ -220,6 +205,7 @@ void enc_put_mv(BitW &bw, int v, int mvs) {
 
 }  // namespace
 
+constexpr size_t kEncPackRecBytes = sizeof(PackRec) + 320 * 4;   // d_prec / h_prec: the packetiser's record, then its histogram
 constexpr int kEncSmallMask = 194;   // d_small / h_small: the word at which a masked frame's MaskRec lies (8-byte aligned)
 constexpr int kEncSmallRoi = 198;    // ... and a frame's with a region-of-interest map its RoiRec (behind the MaskRec)
 
@@ -360,6 +346,7 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   std::vector<uint8_t> pkt;
   std::vector<uint32_t> merged;
   thip_enc_frame_stats stats;
+  thip_enc_token_hist thist;   // TH_ENCCTL_THIP_GET_TOKEN_HIST: the last packet's
   double device_ms = 0, host_ms = 0;
 };
 
@@ -408,6 +395,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
     e->lambda[qi] = step[1];
   }
   memset(&e->stats, 0, sizeof(e->stats));
+  memset(&e->thist, 0, sizeof(e->thist));
   memset(&e->istats, 0, sizeof(e->istats));
   memset(&e->mstats, 0, sizeof(e->mstats));
   memset(&e->bstats, 0, sizeof(e->bstats));
@@ -449,7 +437,7 @@ static void enc_free_device(th_enc_ctx *e) {
       (void **)&e->d_rdqsums,                                                                                        // enc_rdq_queue
       (void **)&e->d_coef, (void **)&e->d_qdc, (void **)&e->d_rcoded, (void **)&e->d_rcls, (void **)&e->d_rmbs, (void **)&e->d_rtab,
       (void **)&e->d_rlam, (void **)&e->d_rlens, (void **)&e->d_rpart, (void **)&e->d_rest,                         // enc_rate_alloc
-      (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_phist, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
+      (void **)&e->d_pk, (void **)&e->d_pglast, (void **)&e->d_pcodes, (void **)&e->d_pcl, (void **)&e->d_pgsum,
       (void **)&e->d_pgbase, (void **)&e->d_prec,                                                                    // enc_pack_alloc
       (void **)&e->d_cut,                                                                                            // enc_cut_alloc
       (void **)&e->d_rgb,                                                                                            // enc_rgb_in
@@ -473,6 +461,7 @@ static void enc_free_device(th_enc_ctx *e) {
     if (*p) (void)hipHostFree(*p);
     *p = nullptr;
   }
+  e->d_phist = nullptr;   // (it lay in d_prec's allocation)
   e->h_tok_cap = e->h_pk_cap = e->pack_cap = 0;
   e->pkt_data = nullptr;   // (it may have been h_pk)
   e->pkt_size = 0;
@@ -896,13 +885,14 @@ static int enc_pack_alloc(th_enc_ctx *e) {
   for (hipEvent_t *ev : {&e->ev_k0, &e->ev_k1, &e->ev_q0, &e->ev_q1})
     if (!*ev) ENC_TRY(hipEventCreate(ev));
   ENC_TRY(hipMalloc((void **)&e->d_pglast, (size_t)e->pack_groups * 4));
-  ENC_TRY(hipMalloc((void **)&e->d_phist, 320 * 4));
   ENC_TRY(hipMalloc((void **)&e->d_pcodes, 80 * 32 * 4));
   ENC_TRY(hipMalloc((void **)&e->d_pcl, 80 * 32 * 4));
   ENC_TRY(hipMalloc((void **)&e->d_pgsum, (size_t)e->pack_groups * sizeof(PackSum)));
   ENC_TRY(hipMalloc((void **)&e->d_pgbase, (size_t)e->pack_groups * sizeof(PackSum)));
-  ENC_TRY(hipMalloc((void **)&e->d_prec, sizeof(PackRec)));
-  ENC_TRY(hipHostMalloc((void **)&e->h_prec, sizeof(PackRec), hipHostMallocDefault));
+  // the record and, behind it, the histogram: one copy brings both back (thip_enc_token_hist is the histogram's)
+  ENC_TRY(hipMalloc((void **)&e->d_prec, kEncPackRecBytes));
+  e->d_phist = (uint32_t *)(e->d_prec + 1);
+  ENC_TRY(hipHostMalloc((void **)&e->h_prec, kEncPackRecBytes, hipHostMallocDefault));
   std::vector<uint32_t> cl(80 * 32);
   pack_cl_table(cl.data(), e->setup.len);
   ENC_TRY(hipMemcpy(e->d_pcodes, e->setup.code, 80 * 32 * 4, hipMemcpyHostToDevice));
@@ -926,7 +916,7 @@ static int enc_pack_queue(th_enc_ctx *e) {
   if (enc_pack_alloc(e)) return TH_EFAULT;
   ENC_TRY(hipEventRecord(e->ev_k0, e->stream));
   ENC_TRY(pack_launch_sums(enc_pack_bufs(e), (const uint32_t *)e->d_out, (const uint32_t *)e->d_small, e->pack_groups, e->stream));
-  ENC_TRY(hipMemcpyAsync(e->h_prec, e->d_prec, sizeof(PackRec), hipMemcpyDeviceToHost, e->stream));
+  ENC_TRY(hipMemcpyAsync(e->h_prec, e->d_prec, kEncPackRecBytes, hipMemcpyDeviceToHost, e->stream));
   ENC_TRY(hipEventRecord(e->ev_k1, e->stream));
   e->frame_dpack = true;
   return 0;
@@ -1562,6 +1552,7 @@ static void enc_empty_packet(th_enc_ctx *e) {
   for (int c = 0; c < 4; c++) e->stats.huff[c] = -1;
   e->stats.overflow = 0;
   e->stats.qi = e->frame_qi;
+  memset(&e->thist, 0, sizeof(e->thist));
   memset(&e->bstats, 0, sizeof(e->bstats));
   enc_mask_stats(e, false);
   enc_roi_stats(e, false);
@@ -1584,7 +1575,12 @@ static void enc_repeat_packet(th_enc_ctx *e, ogg_packet *op) {
 
 // what both packers leave behind: the frame's statistics, the AC tables the next block-qi choice of this frame type counts with, and
 // all four tables of an inter packet for the next rate-distortion mode decision
-static void enc_packet_done(th_enc_ctx *e, size_t total, size_t merged, const int hti[4], uint32_t overflow) {
+static void enc_packet_done(th_enc_ctx *e, size_t total, size_t merged, const int hti[4], uint32_t overflow, const uint32_t *hist,
+                            bool device) {
+  memcpy(e->thist.count, hist, sizeof(e->thist.count));   // [5][2][32], the packer's own
+  for (int c = 0; c < 4; c++) e->thist.huff[c] = hti[c];
+  e->thist.key = e->frame_key ? 1 : 0;
+  e->thist.device = device ? 1 : 0;
   if (!e->frame_key)
     for (int c = 0; c < 4; c++) e->rd_hti[c] = hti[c];
   e->bqi_hti[e->frame_key ? 0 : 1][0] = hti[2];
@@ -1702,7 +1698,7 @@ static int enc_pack_host(th_enc_ctx *e, size_t total, uint32_t overflow) {
   e->host_ms = (thip_now() - t0) * 1e3;
   e->pkt_data = e->pkt.data();
   e->pkt_size = e->pkt.size();
-  enc_packet_done(e, total, m.size(), hti, overflow);
+  enc_packet_done(e, total, m.size(), hti, overflow, &hist[0][0][0], false);
   return overflow ? TH_EFAULT : 0;
 }
 
@@ -1763,7 +1759,7 @@ static int enc_pack_device(th_enc_ctx *e, size_t total, uint32_t overflow) {
   e->pstats.token_bits = (int64_t)rec.bits + 16;
   e->pstats.phase = phase;
   e->pstats.pack_ms = pack1 + pack2;
-  enc_packet_done(e, total, rec.merged, rec.hti, overflow);
+  enc_packet_done(e, total, rec.merged, rec.hti, overflow, (const uint32_t *)(e->h_prec + 1), true);
   e->host_ms = (thip_now() - t0 - waited) * 1e3;   // (the host's own work: the waits for the packetiser are in pack_ms)
   return overflow ? TH_EFAULT : 0;
 }
@@ -2278,6 +2274,32 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       if (!e->dev_ready && enc_ensure_device(e)) return TH_EFAULT;
       *(int *)buf = e->device;
       return 0;
+    case TH_ENCCTL_SET_HUFFMAN_CODES: {
+      const bool restore = !buf && buf_sz == 0;
+      if (!restore && (!buf || buf_sz != sizeof(th_huff_code) * 80 * 32)) return TH_EIMPL;   // (theoraenc_hip.h: the one deviation)
+      // every table of code lengths on the device is filled at the first frame that needs it: none exists yet
+      if (e->nheaders_out > 0 || enc_begun(e)) return TH_EINVAL;
+      if (restore) {
+        std::vector<th_huff_code> codes(80 * 32);
+        enc_builtin_codes((th_huff_code(*)[32])codes.data());
+        enc_setup_codes(e->setup, (const th_huff_code(*)[32])codes.data());
+        return 0;
+      }
+      if (!huff_codes_valid((const th_huff_code(*)[32])buf)) return TH_EINVAL;
+      enc_setup_codes(e->setup, (const th_huff_code(*)[32])buf);
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_HUFFMAN_CODES: {
+      if (!buf || buf_sz != sizeof(th_huff_code) * 80 * 32) return TH_EINVAL;
+      th_huff_code(*out)[32] = (th_huff_code(*)[32])buf;
+      for (int h = 0; h < 80; h++)
+        for (int tok = 0; tok < 32; tok++) out[h][tok] = th_huff_code{e->setup.code[h][tok], (int)e->setup.len[h][tok]};
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_TOKEN_HIST:
+      if (!buf || buf_sz != sizeof(thip_enc_token_hist)) return TH_EINVAL;
+      *(thip_enc_token_hist *)buf = e->thist;
+      return 0;
     case TH_ENCCTL_THIP_GET_FRAME_STATS:
       if (!buf || buf_sz != sizeof(thip_enc_frame_stats)) return TH_EINVAL;
       *(thip_enc_frame_stats *)buf = e->stats;
@@ -2289,6 +2311,18 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       return 0;
     default: return TH_EIMPL;
   }
+}
+
+// the trainer of theoraenc_hip.h's "Huffman codes" (thip_hufftrain.h); start == NULL: the built-in codes
+int thip_huff_train(const thip_enc_token_hist *hists, size_t n, const th_huff_code start[80][32], int rounds, th_huff_code out[80][32],
+                    thip_huff_train_stats *stats) {
+  std::vector<th_huff_code> builtin;
+  if (!start) {
+    builtin.resize(80 * 32);
+    enc_builtin_codes((th_huff_code(*)[32])builtin.data());
+    start = (const th_huff_code(*)[32])builtin.data();
+  }
+  return huff_train(hists, n, start, rounds, out, stats);
 }
 
 // the device packetiser on the caller's tokens and tables (theora_hip.h): thip_encode_pack.h's launches, as enc_pack_queue and

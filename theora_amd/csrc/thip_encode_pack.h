@@ -39,7 +39,8 @@ constexpr uint32_t kPackEmit = 1u << 21;   // merged word: token | extra << 5 (1
 // a tile's bits: 7 + 8 + 256 x 44 + 8 + 8, and the word alignment at both ends.  44 is the conservative bound -- a code of 32 bits and
 // the 12 extra bits of the long EOB run in every lane, where a tile holds at most 8 such runs (32 EOBs each).  What tables of 32-bit
 // codes reach, and tests/test_gpu_pack_direct.py drives, is 256 x 42 (the value token of 10 extra bits) + 8 + 8 + 7 + 31 = 10 806
-// bits, 338 words.
+// bits, 338 words.  A caller's code set (TH_ENCCTL_SET_HUFFMAN_CODES) may put a 31-bit code on the long EOB run: 43 bits a token, 51
+// with the AC table indices in front, which tests/test_gpu_encoder_huff.py drives through a packet and through one tile.
 constexpr int kPackBufWords = 368;
 
 struct PackSum {   // a span's sums, or (after the scan) those of all spans before it

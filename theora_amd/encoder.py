@@ -47,6 +47,10 @@ TH_ENCCTL_THIP_SET_RD_QUANT = 0x7222   # (0x7220 and 0x7221 are not used)
 TH_ENCCTL_THIP_GET_RD_QUANT_STATS = 0x7223
 TH_ENCCTL_THIP_SET_ROI_MAP = 0x7225   # (0x7224 is not used)
 TH_ENCCTL_THIP_GET_ROI_STATS = 0x7226
+TH_ENCCTL_THIP_GET_TOKEN_HIST = 0x7227
+TH_ENCCTL_THIP_GET_HUFFMAN_CODES = 0x7228
+TH_ENCCTL_SET_HUFFMAN_CODES = 0
+TH_NHUFFMAN_TABLES, TH_NDCT_TOKENS = 80, 32
 RD_QUANT_DEFAULT = 3   # the recommended weight w (lambda's weight w / 16): include/theoraenc_hip.h, "Level choice"
 TWO_PASS_HEADER_BYTES, TWO_PASS_RECORD_BYTES = 1084, 264   # THIP_2PASS_HEADER_BYTES, THIP_2PASS_RECORD_BYTES
 RGB_FORMATS = {"rgb": _lib.PIC_RGB24, "rgba": _lib.PIC_RGBA32, "rgb_planar": _lib.PIC_RGB_PLANAR}
@@ -156,6 +160,68 @@ class TwoPassStats(C.Structure):
                 ("corr", C.c_int64 * 4), ("wait_ms", C.c_double), ("probe_ms", C.c_double)]
 
 
+class HuffCode(C.Structure):
+    """th_huff_code (include/theoradec_hip.h)."""
+    _fields_ = [("pattern", C.c_uint32), ("nbits", C.c_int)]
+
+
+HuffCodes = (HuffCode * TH_NDCT_TOKENS) * TH_NHUFFMAN_TABLES
+
+
+class TokenHist(C.Structure):
+    """thip_enc_token_hist (include/theoraenc_hip.h)."""
+    _fields_ = [("count", ((C.c_uint32 * 32) * 2) * 5), ("huff", C.c_int32 * 4), ("key", C.c_int32), ("device", C.c_int32)]
+
+
+class HuffTrainStats(C.Structure):
+    """thip_huff_train_stats (include/theoraenc_hip.h)."""
+    _fields_ = [("bits_start", C.c_uint64), ("bits_end", C.c_uint64), ("rounds", C.c_int32), ("dc_tables", C.c_int32),
+                ("ac_tables", C.c_int32), ("samples", C.c_int32)]
+
+
+def _huff_codes_in(codes):
+    """An (80, 32, 2) array of (pattern, nbits) -> th_huff_code[80][32]."""
+    a = np.asarray(codes, np.int64)
+    if a.shape != (TH_NHUFFMAN_TABLES, TH_NDCT_TOKENS, 2):
+        raise ValueError("Huffman codes are an (80, 32, 2) array of (pattern, nbits)")
+    if a[..., 0].min() < 0 or a[..., 0].max() >= 1 << 32 or abs(a[..., 1]).max() >= 1 << 31:
+        raise ValueError("a pattern is 32 bits wide and nbits an int")
+    buf = np.zeros((TH_NHUFFMAN_TABLES, TH_NDCT_TOKENS), np.dtype([("pattern", np.uint32), ("nbits", np.int32)]))
+    buf["pattern"], buf["nbits"] = a[..., 0], a[..., 1]
+    return HuffCodes.from_buffer_copy(buf.tobytes())
+
+
+def _huff_codes_out(buf):
+    a = np.frombuffer(bytes(buf), np.dtype([("pattern", np.uint32), ("nbits", np.int32)])).reshape(TH_NHUFFMAN_TABLES, TH_NDCT_TOKENS)
+    return np.stack([a["pattern"].astype(np.int64), a["nbits"].astype(np.int64)], axis=-1)
+
+
+def _token_hist_dict(h):
+    return dict(count=np.frombuffer(bytes(h.count), np.uint32).reshape(5, 2, 32).astype(np.int64), huff=list(h.huff), key=int(h.key),
+                device=int(h.device))
+
+
+def train_huffman(hists, start=None, rounds=8):
+    """thip_huff_train (include/theoraenc_hip.h, "Huffman codes"): codes trained on the packets' token histograms, from `start`
+    (None: the built-in codes) -> (codes, stats).  hists: Encoder.token_hist() dicts, or (5, 2, 32) count arrays.  codes is an
+    (80, 32, 2) array of (pattern, nbits) for Encoder(huffman=...); stats has bits_start, bits_end, rounds, dc_tables, ac_tables,
+    samples.  Host arithmetic: no GPU."""
+    L = _lib.load()
+    hists = list(hists)
+    arr = (TokenHist * max(len(hists), 1))()
+    for k, h in enumerate(hists):
+        cnt = np.asarray(h["count"] if isinstance(h, dict) else h, np.int64)
+        if cnt.shape != (5, 2, 32) or cnt.min() < 0 or cnt.max() >= 1 << 32:
+            raise ValueError("a histogram is a (5, 2, 32) array of 32-bit counts")
+        C.memmove(arr[k].count, cnt.astype(np.uint32).tobytes(), 5 * 2 * 32 * 4)
+    out, st = HuffCodes(), HuffTrainStats()
+    rc = L.thip_huff_train(arr if hists else None, len(hists), None if start is None else _huff_codes_in(start), int(rounds), out,
+                           C.byref(st))
+    if rc < 0:
+        raise ValueError("thip_huff_train returned %d (rounds 1..64, at most 2^20 histograms, a valid start)" % rc)
+    return _huff_codes_out(out), {n: int(getattr(st, n)) for n, _ in HuffTrainStats._fields_}
+
+
 class RateStats(C.Structure):
     """thip_enc_rate_stats (include/theoraenc_hip.h)."""
     _fields_ = [("qi", C.c_int32), ("dropped", C.c_int32), ("key", C.c_int32), ("duplicate", C.c_int32), ("target", C.c_int64),
@@ -189,7 +255,7 @@ class Encoder:
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
                  block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False, rd_skip=False,
-                 rd_quant=0):
+                 rd_quant=0, huffman=None):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -205,7 +271,9 @@ class Encoder:
         eight-mode inter frames by the least D + lambda R (TH_ENCCTL_THIP_SET_RD_MODES).  No effect without all_modes.  rd_skip: coded
         blocks of inter frames are left uncoded where that costs less (TH_ENCCTL_THIP_SET_RD_SKIP).  No effect without inter.
         rd_quant: the AC levels of coded blocks by the least D + lambda R with lambda's weight rd_quant / 16, 1..64
-        (TH_ENCCTL_THIP_SET_RD_QUANT; 0 off; True for the recommended RD_QUANT_DEFAULT)."""
+        (TH_ENCCTL_THIP_SET_RD_QUANT; 0 off; True for the recommended RD_QUANT_DEFAULT).  huffman: an (80, 32, 2) array of
+        (pattern, nbits), the Huffman codes of the stream in place of the built-in ones (TH_ENCCTL_SET_HUFFMAN_CODES;
+        train_huffman makes them)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -213,6 +281,8 @@ class Encoder:
         if not self._enc:
             raise TheoraHipError("th_encode_alloc failed")
         self.comments = list(comments)
+        if huffman is not None:
+            self.set_huffman_codes(huffman)
         self.hdec, self.vdec = int(not (fmt & 1)), int(not (fmt & 2))
         self.inter = bool(inter)
         self.keyframe_interval = None
@@ -277,6 +347,33 @@ class Encoder:
         if rc < 0:
             raise TheoraHipError("TH_ENCCTL_SET_BITRATE returned %d" % rc)
         self.bitrate = bitrate
+
+    def set_huffman_codes(self, codes):
+        """TH_ENCCTL_SET_HUFFMAN_CODES, before header_packets(): an (80, 32, 2) array of (pattern, nbits), or None for the built-in
+        codes.  ValueError for codes that are no full prefix code of all 32 tokens, or too late."""
+        if codes is None:
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_SET_HUFFMAN_CODES, None, 0)
+        else:
+            buf = _huff_codes_in(codes)
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_SET_HUFFMAN_CODES, C.byref(buf), C.sizeof(buf))
+        if rc < 0:
+            raise ValueError("TH_ENCCTL_SET_HUFFMAN_CODES returned %d: every set must be a full prefix-free code of all 32 tokens, "
+                             "set before the first header packet" % rc)
+
+    def huffman_codes(self):
+        """TH_ENCCTL_THIP_GET_HUFFMAN_CODES: the codes in force, an (80, 32, 2) array of (pattern, nbits)."""
+        buf = HuffCodes()
+        _lib.check(self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_HUFFMAN_CODES, C.byref(buf), C.sizeof(buf)),
+                   "TH_ENCCTL_THIP_GET_HUFFMAN_CODES")
+        return _huff_codes_out(buf)
+
+    def token_hist(self):
+        """TH_ENCCTL_THIP_GET_TOKEN_HIST: the last packet's merged tokens -> dict(count (5, 2, 32): Huffman group, luma / chroma,
+        token; huff; key; device).  train_huffman takes a list of these."""
+        h = TokenHist()
+        _lib.check(self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_TOKEN_HIST, C.byref(h), C.sizeof(h)),
+                   "TH_ENCCTL_THIP_GET_TOKEN_HIST")
+        return _token_hist_dict(h)
 
     def set_masking(self, k):
         """TH_ENCCTL_THIP_SET_MASKING, before the first frame: activity masking with ratio k, 2..16 (0: off)."""
