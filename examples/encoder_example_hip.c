@@ -2,7 +2,8 @@
  * and its Ogg writer (include/thip_ogg.h).
  *
  *   encoder_example_hip [-q quality] [-k keyframe_interval [-m] [-a [t]]] [-b delta [--roi x,y,w,h,v]] [-V kbps]
- *                       [--first-pass FILE | --second-pass FILE | --two-pass | --train-huffman] [-o out.ogv] in.y4m
+ *                       [--first-pass FILE | --second-pass FILE | --two-pass | --train-huffman] [--quant-from FILE.ogv]
+ *                       [-o out.ogv] in.y4m
  *
  * Input: C420jpeg, C420, C420paldv, C420mpeg2 (4:2:0), C422 or C444, any size; no C tag means 4:2:0.  The frame is the picture
  * padded to multiples of 16, the picture region at (0, 0); the picture-size planes go to th_encode_ycbcr_in as they are.  Every
@@ -24,6 +25,10 @@
  * packet's token histogram (TH_ENCCTL_THIP_GET_TOKEN_HIST), trains codes on them (thip_huff_train, 8 rounds), and encodes the input
  * again with the trained codes (TH_ENCCTL_SET_HUFFMAN_CODES) into the output.  It reads the input twice too, so the input must be a
  * seekable file; not together with the two-pass options.
+ *
+ * --quant-from FILE.ogv ("Quantisation parameters" in theoraenc_hip.h): codes with the quantisation parameters of another Ogg/Theora
+ * stream -- the first setup header thip_ogg_reader finds in FILE, through thip_quant_info_from_setup and TH_ENCCTL_SET_QUANT_PARAMS.
+ * With every other option; both passes of a two-pass encode must be given the same file.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -78,6 +83,7 @@ typedef struct {
   int roi, roi_rect[5];   /* --roi: x, y, w, h, v */
   const th_huff_code (*codes)[TH_NDCT_TOKENS];   /* --train-huffman, the second run: the trained codes (NULL: the built-in ones) */
   struct hist_pool *pool;                        /* ... the first run: every packet's histogram goes here (NULL: none is kept) */
+  const th_quant_info *quant;                    /* --quant-from: another stream's quantisation parameters (NULL: the built-in ones) */
 } options;
 
 typedef struct hist_pool {
@@ -157,6 +163,10 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
   }
   if (o->codes && th_encode_ctl(enc, TH_ENCCTL_SET_HUFFMAN_CODES, (void *)o->codes, sizeof(th_huff_code) * TH_NHUFFMAN_TABLES * TH_NDCT_TOKENS)) {
     fprintf(stderr, "Huffman codes refused\n");
+    return 1;
+  }
+  if (o->quant && th_encode_ctl(enc, TH_ENCCTL_SET_QUANT_PARAMS, (void *)o->quant, sizeof(*o->quant))) {
+    fprintf(stderr, "quantisation parameters refused\n");
     return 1;
   }
   if (kf > 0) {   /* inter frames, a key frame every kf frames (clamped to 1 << keyframe_granule_shift) */
@@ -289,9 +299,29 @@ static int encode(const options *o, FILE *in, FILE *out, int pass, FILE *pf) {
   return 0;
 }
 
+/* the quantisation parameters of the first Theora setup header in an Ogg file ("Quantisation parameters" in theoraenc_hip.h);
+   0 on success, qi then owns its arrays (thip_quant_info_free) */
+static int quant_from_file(const char *path, th_quant_info *qi) {
+  thip_ogg_reader *r = thip_ogg_open_file(path);
+  if (!r) return -1;
+  ogg_packet op;
+  uint32_t serial;
+  int rc = -1;
+  while (rc && thip_ogg_next_packet(r, &op, &serial) > 0) {
+    if (op.bytes < 7 || op.packet[0] != 0x82 || memcmp(op.packet + 1, "theora", 6) != 0) {
+      if (op.bytes > 0 && !(op.packet[0] & 0x80)) break;   /* a data packet: the headers are over */
+      continue;
+    }
+    rc = thip_quant_info_from_setup(op.packet, (size_t)op.bytes, qi);
+    break;
+  }
+  thip_ogg_close(r);
+  return rc;
+}
+
 int main(int argc, char **argv) {
-  options o = {48, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0}, NULL, NULL};
-  const char *in_path = NULL, *out_path = NULL, *first = NULL, *second = NULL;
+  options o = {48, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0}, NULL, NULL, NULL};
+  const char *in_path = NULL, *out_path = NULL, *first = NULL, *second = NULL, *quant_from = NULL;
   int two_pass = 0, train = 0;
   for (int i = 1; i < argc; i++) {
     if (strcmp(argv[i], "-q") == 0 && i + 1 < argc) o.quality = atoi(argv[++i]);
@@ -308,13 +338,22 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[i], "--second-pass") == 0 && i + 1 < argc) second = argv[++i];
     else if (strcmp(argv[i], "--two-pass") == 0) two_pass = 1;
     else if (strcmp(argv[i], "--train-huffman") == 0) train = 1;
+    else if (strcmp(argv[i], "--quant-from") == 0 && i + 1 < argc) quant_from = argv[++i];
     else in_path = argv[i];
   }
   const int npass = (first != NULL) + (second != NULL) + two_pass + train;
   if (!in_path || o.roi < 0 || (o.roi && !o.bqi) || ((o.all_modes || o.auto_kf) && o.kf <= 0) || npass > 1 || ((second || two_pass) && o.kbps <= 0) ||
       ((two_pass || train) && strcmp(in_path, "-") == 0)) {
-    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi [--roi x,y,w,h,v: a region of interest, v in -64..64]] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file) | --train-huffman (the input a file)] [-o out.ogv] in.y4m\n", argv[0]);
+    fprintf(stderr, "usage: %s [-q quality] [-k keyframe_interval: inter frames [-m: all modes] [-a [t]: key frames at cuts]] [-b delta: block qi [--roi x,y,w,h,v: a region of interest, v in -64..64]] [--device-pack] [-V kbps] [--first-pass FILE | --second-pass FILE (with -V) | --two-pass (with -V; the input a file) | --train-huffman (the input a file)] [--quant-from FILE.ogv: the quantisers of that stream] [-o out.ogv] in.y4m\n", argv[0]);
     return 1;
+  }
+  static th_quant_info quant;
+  if (quant_from) {
+    if (quant_from_file(quant_from, &quant)) {
+      fprintf(stderr, "no Theora setup header read from %s\n", quant_from);
+      return 1;
+    }
+    o.quant = &quant;
   }
   FILE *in = strcmp(in_path, "-") == 0 ? stdin : fopen(in_path, "rb");
   if (!in) {
@@ -364,5 +403,6 @@ int main(int argc, char **argv) {
   if (out != stdout) fclose(out);
   if (in != stdin) fclose(in);
   if (pf) fclose(pf);
+  thip_quant_info_free(&quant);
   return rc;
 }

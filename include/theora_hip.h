@@ -881,8 +881,14 @@ int thip_enc_inter_stage(const thip_enc_inter_req *req);
  *   frame_*, pixel_fmt, pic_*, src, src_pitch, prev, ref_pitch   as thip_enc_inter_stage takes them (prev: inter only)
  *   inter            0: a key frame (one coefficient set, every block coded and intra); 1: an inter frame of five modes
  *   steps            HOST, uint16 [6][64 q][64 z]: the quantiser steps of each table (the intra then the inter table of each plane)
- *                    at each qi, zig-zag order, every entry 1..32767.  THE PROBE'S PRECONDITION: the step of every (table, z) at
- *                    qi 63 is the least over q -- the kernels walk only the indices whose coefficient is not zero at qi 63
+ *                    at each qi, zig-zag order, every entry 1..32767.  With any_order 0, besides: the step of every (table, z)
+ *                    at qi 63 is the least over q (what the kernels once rested on, and this call form goes on asking)
+ *   any_order        0, or 1: the steps may rise and fall with q in any way.  The kernels walk the indices whose coefficient is not
+ *                    zero under the least step over q of its (table, z), a superset at every q whatever the order (th_encode_*
+ *                    runs them so, under a caller's TH_ENCCTL_SET_QUANT_PARAMS); another value: THIP_EINVAL (with DC or TOK)
+ *                    A CHANGE FOR OLD CALLERS: this word was padding, named `pad`, and was not read.  A caller who left it
+ *                    uninitialised is now refused (THIP_EINVAL) unless it happens to hold 0 or 1, and with 1 loses the qi-63
+ *                    check: zero the request before filling it, as the entry's other callers do
  *   lambda           HOST, int32 [64]: the mode decision's weight at each qi (inter), 0..2^24 each
  *   lens             HOST, uint8 [80][32]: the code lengths of the 80 Huffman tables
  *   fixed            the bits E[q] starts from (th_encode_*: 28 for a key frame, 25 + nfrags / 8 for an inter frame), >= 0
@@ -904,8 +910,8 @@ int thip_enc_inter_stage(const thip_enc_inter_req *req);
  * Synchronous, on the calling thread's current device (its null stream).
  * THIP_EFAULT: req NULL, a buffer or table a stage needs NULL, or a HIP call failed.  THIP_EINVAL: stages 0 or unknown; inter not 0
  * or 1; the frame size, fragment count, pixel format, picture region and pitches as thip_enc_inter_stage refuses them (region and
- * pitches: with COEF); groups negative, too many or too few for the frame; a step outside 1..32767 or the precondition broken (with
- * DC or TOK); a lambda out of range; fixed negative; stats or coef not 16-byte aligned, coded, cls or est not 8-byte, partial not
+ * pitches: with COEF); groups negative, too many or too few for the frame; a step outside 1..32767 or, with any_order 0, a step
+ * below that at qi 63 (with DC or TOK); a lambda out of range; fixed negative; stats or coef not 16-byte aligned, coded, cls or est not 8-byte, partial not
  * 4-byte, qdc not 2-byte -- all found before a device is touched.
  * thip_enc_rate_groups: the rule itself, pure host code: min(256, ceil(n / 16)) work groups, or ceil(n / 960) where that is more;
  * THIP_EINVAL for n < 1 or n > 2^24.
@@ -917,7 +923,7 @@ int thip_enc_inter_stage(const thip_enc_inter_req *req);
 typedef struct thip_enc_rate_req {   /* 224 bytes */
   int32_t frame_width, frame_height, pixel_fmt;
   int32_t pic_x, pic_y, pic_width, pic_height;
-  int32_t inter, stages, groups, fixed, pad;
+  int32_t inter, stages, groups, fixed, any_order;   /* (any_order: the word that was padding, so the size and every offset stay) */
   const uint8_t *src[3];
   int64_t src_pitch[3];
   const uint8_t *prev[3];

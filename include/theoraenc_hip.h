@@ -7,7 +7,8 @@
  * default.  Bitrate mode is entered through TH_ENCCTL_SET_BITRATE after th_encode_alloc ("Bitrate mode" below); th_info.target_bitrate
  * != 0 at th_encode_alloc is refused (NULL).  Two-pass encoding goes through TH_ENCCTL_THIP_2PASS_OUT / _IN ("Two-pass" below;
  * libtheora's own requests 24 and 26 answer TH_EIMPL, their record format is not this one).  Custom Huffman codes are taken through TH_ENCCTL_SET_HUFFMAN_CODES
- * ("Huffman codes" below); custom quantisation parameters and VP3 compatibility are not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
+ * ("Huffman codes" below) and custom quantisation parameters through TH_ENCCTL_SET_QUANT_PARAMS ("Quantisation parameters" below); VP3
+ * compatibility is not available (TH_EIMPL).  An all-key-frame stream is valid Theora; every decoder plays it.
  *
  * The bitstream, stated so that a restatement reproduces the packets byte for byte (tests/enc_ref.py does):
  *   - Setup header.  Loop-filter limits lflim[qi] = (31 * (63 - qi) + 31) / 63.  AC and DC scales fall geometrically,
@@ -19,7 +20,9 @@
  *     Huffman code of 32 token weights with a sparsity s = {0.1, 0.3, 0.55, 0.8}[b] and a magnitude ratio q = {0.15, 0.35,
  *     0.55, 0.75}[a] (thip_encode.hip, enc_token_weights); every token has a code, none longer than 31 bits.  These built-in trees are
  *     the default; TH_ENCCTL_SET_HUFFMAN_CODES replaces them ("Huffman codes" below) and changes nothing else of the header.  (The
- *     header is the same with inter frames on; the inter matrices are then used.)
+ *     header is the same with inter frames on; the inter matrices are then used.)  These limits, scales, matrices and ranges are the
+ *     built-in quantisation parameters; TH_ENCCTL_SET_QUANT_PARAMS replaces them ("Quantisation parameters" below) and changes
+ *     nothing of the trees.
  *   - Frame.  An intra frame with one qi, qi = quality (TH_ENCCTL_SET_QUALITY changes it from the next frame); no block qi.
  *   - Blocks.  In coded order, each 8x8 block is pixel - 128, oc_enc_fdct8x8, oc_enc_quantize with the intra table of (plane,
  *     qi).  Pixels outside the picture region take the value of the nearest picture pixel (clamped coordinates) in every plane;
@@ -407,6 +410,40 @@
  *     are unsigned 64-bit and wrap; they are exact while the counts of all histograms together stay below 2^49.
  *     Empty tables are not reseeded or split: a pool whose samples all prefer a few tables trains those few.
  *
+ * Quantisation parameters (TH_ENCCTL_SET_QUANT_PARAMS, TH_ENCCTL_THIP_GET_QUANT_PARAMS, thip_quant_info_from_setup), stated likewise
+ * (tests/enc_quant_ref.py restates them).  The setup is data to everything that reads a step: every quantiser table, on the host
+ * and on the device, is spec 6.4.3's over the parameters in force and is made at the first frame that needs it, so with a
+ * caller's parameters every rule above holds as stated, with "the step" read from them.
+ *   - A parameter set is valid when, for every (qti, pli), nranges is 1..63, sizes and base_matrices are not NULL, every size is
+ *     >= 1 and the sizes sum to exactly 63; and no loop-filter limit is above 127 (the header's 3 bits of width carry at most 7 bits
+ *     a limit).  Everything else is legal, as it is to a decoder: any 16-bit scale, 0 included, and any base-matrix byte -- qmin of
+ *     spec 6.4.3 bounds every step from below (and 4096 from above), so the overflow rule (|v| > 580) stays unreachable; the
+ *     TH_EFAULT path is kept.  libtheora trusts the caller; this library checks.
+ *   - The setup header's quantiser part under a caller's parameters is what libtheora's oc_quant_params_pack writes.  Limits:
+ *     3 bits of width w = ilog(the largest limit), then 64 x w bits.  AC scales, then DC scales: 4 bits of w - 1 with w =
+ *     max(1, ilog(the largest scale)), then 64 x w bits.  The base matrices are consolidated by content, in first-seen order over
+ *     (qti, pli, range end 0..nranges): 9 bits of their count - 1 (at most 384), then 64 bytes each; an index takes ilog(count - 1)
+ *     bits, none when there is one matrix.  The six (qti, pli), intra Y, Cb, Cr then inter Y, Cb, Cr: the first writes its ranges;
+ *     each later one writes, tested in this order, "01" when qti > 0 and its ranges (count, sizes, consolidated indices) equal
+ *     those of (qti - 1, pli); "0" (qti = 0) or "00" (qti > 0) when they equal those of the (qti, pli) before it in that order; else
+ *     "1" and its ranges.  Ranges: the index of the first matrix, then for each range its size - 1 in ilog(62 - the qi steps
+ *     written so far) bits and the index of the matrix at its end.  The 80 trees follow unchanged.
+ *   - The built-in header is NOT written this way: each of its six (qti, pli) states its ranges (the "1"), and it stays byte for
+ *     byte what it was.  A caller who passes a copy of the built-in values (what TH_ENCCTL_THIP_GET_QUANT_PARAMS returns before any
+ *     SET) gets a header that differs from the built-in one in those few bits, and the same pictures.  buf = NULL restores the
+ *     built-in header itself.
+ *   - lambda[qi], the weight of the motion search and, through it, of block qi, the RD modes, skip and the level choice, is the
+ *     inter luma step at zig-zag index 1 at qi under the parameters in force.  The loop-filter limit of a frame is the
+ *     parameters' limit at its qis[0].  The encoder's own decoder is set up from the header in force.
+ *   - Block qi's list ("Block qi") goes by INDEX: qis[0] +- delta.  With scales that do not fall with qi, "coarser" and "finer" are
+ *     only names for the lower and the higher index; the choice is still the least D + lambda R over the list.
+ *   - Bitrate mode: the probe measures E[q] under the parameters in force at every q; E need not fall or rise with q, and the
+ *     controller's choice is as stated, the LARGEST q whose estimate fits.  The probe's kernels walk, for each block, the indices
+ *     whose coefficient is not zero under the least step over q of its (table, index): a superset at every q whatever the order of
+ *     the steps.
+ *   - Two-pass: the pass file's header does not carry the quantisers.  Both passes must be given the same ones, as for the
+ *     Huffman codes; a second pass under other quantisers reads curves that are not its own.
+ *
  * Device memory is allocated at the first th_encode_ycbcr_in (or TH_ENCCTL_THIP_YCBCR_IN_DEVICE / _RGB_IN / TH_ENCCTL_THIP_GET_DEVICE):
  * th_encode_alloc, th_encode_flushheader and th_encode_ctl with the libtheoraenc requests never touch the GPU; of the 0x72xx
  * extensions, YCBCR_IN_DEVICE, RGB_IN, GET_DEVICE and GET_QUALITY_STATS do.
@@ -445,8 +482,29 @@ extern "C" {
    and the context's codes stay as they were.  ANY OTHER buf_sz: TH_EIMPL, where libtheora answers TH_EINVAL -- the one deviation,
    kept because callers probe this request with an int to learn that custom codes were not available.  Never touches the GPU. */
 #define TH_ENCCTL_SET_HUFFMAN_CODES (0)
-/* Known, and answered TH_EIMPL: */
+/* The quantisation parameters of a stream, libtheora's types (codec.h) with its layout: sizeof(th_quant_info) is 464.  A base
+   matrix is in natural order.  qi_ranges[qti][pli] (qti 0 intra, 1 inter; pli Y, Cb, Cr): nranges ranges of sizes[] qi steps each,
+   summing to 63, and the nranges + 1 base matrices at their ends (spec 6.4.2, 6.4.3). */
+typedef uint16_t ogg_uint16_t;
+typedef unsigned char th_quant_base[64];
+typedef struct th_quant_ranges {
+  int nranges;
+  const int *sizes;
+  const th_quant_base *base_matrices;
+} th_quant_ranges;
+typedef struct th_quant_info {
+  ogg_uint16_t dc_scale[64];
+  ogg_uint16_t ac_scale[64];
+  unsigned char loop_filter_limits[64];
+  th_quant_ranges qi_ranges[2][3];
+} th_quant_info;
+/* buf = th_quant_info * and buf_sz exactly sizeof(th_quant_info): the parameters replace the context's ("Quantisation parameters"
+   above); the encoder takes a deep copy, the caller's arrays may go away.  buf = NULL with buf_sz = 0: the built-in parameters
+   again.  Both only before the first th_encode_flushheader has returned a packet and before the first frame, else TH_EINVAL.  A
+   set that is not valid: TH_EINVAL, and the context's parameters stay as they were.  ANY OTHER buf_sz: TH_EIMPL, the deviation
+   request 0 keeps, for the same reason.  Never touches the GPU. */
 #define TH_ENCCTL_SET_QUANT_PARAMS (2)
+/* Known, and answered TH_EIMPL: */
 #define TH_ENCCTL_SET_VP3_COMPATIBLE (10)
 #define TH_ENCCTL_GET_SPLEVEL (16)
 #define TH_ENCCTL_2PASS_OUT (24)                   /* (libtheora's two-pass requests and its record format: not these.  A caller */
@@ -740,6 +798,18 @@ typedef struct thip_enc_token_hist {   /* 1304 bytes */
 /* Extension: buf = th_huff_code[TH_NHUFFMAN_TABLES][TH_NDCT_TOKENS] (buf_sz its size, else TH_EINVAL), receives the codes in force
    (patterns masked to nbits), at any time.  Never touches the GPU. */
 #define TH_ENCCTL_THIP_GET_HUFFMAN_CODES (0x7228)
+
+/* Extension: buf = th_quant_info (buf_sz its size, else TH_EINVAL), receives the quantisation parameters in force, at any time:
+   the built-in ones, or the deep copy of what TH_ENCCTL_SET_QUANT_PARAMS was given.  The pointers point into the context and stay
+   valid until the next TH_ENCCTL_SET_QUANT_PARAMS or th_encode_free.  Never touches the GPU. */
+#define TH_ENCCTL_THIP_GET_QUANT_PARAMS (0x7229)
+/* The quantisation parameters of any Theora setup header packet (the decoder's own parser reads it), for
+   TH_ENCCTL_SET_QUANT_PARAMS: a transcoder keeps its source's quantisers with it.  `out` owns its arrays until
+   thip_quant_info_free (which zeroes it; a zeroed or NULL argument is fine).  Each (qti, pli) gets arrays of its own.  Host only, no
+   context.  0, or THIP_EFAULT for a NULL argument, TH_EFAULT without memory, and TH_ENOTFORMAT / TH_EBADHEADER as th_decode_headerin
+   answers for the same bytes given as the third header (a packet that is no setup header: TH_EBADHEADER). */
+int thip_quant_info_from_setup(const unsigned char *packet, size_t bytes, th_quant_info *out);
+void thip_quant_info_free(th_quant_info *qi);
 
 /* The trainer of "Huffman codes" above: out = codes trained on the n histograms, from `start` (NULL: the built-in codes).  Host
    arithmetic only, deterministic, no context and no GPU.  rounds 1..64.  stats may be NULL.  hists may be NULL when n = 0 (out =

@@ -110,7 +110,7 @@ class EncRateReq(C.Structure):
     """thip_enc_rate_req (include/theora_hip.h)."""
     _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
                 ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
-                ("inter", C.c_int32), ("stages", C.c_int32), ("groups", C.c_int32), ("fixed", C.c_int32), ("pad", C.c_int32),
+                ("inter", C.c_int32), ("stages", C.c_int32), ("groups", C.c_int32), ("fixed", C.c_int32), ("any_order", C.c_int32),
                 ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("prev", C.c_void_p * 3), ("ref_pitch", C.c_int64 * 3),
                 ("steps", C.c_void_p), ("lam", C.c_void_p), ("lens", C.c_void_p), ("stats", C.c_void_p), ("coef", C.c_void_p),
                 ("qdc", C.c_void_p), ("coded", C.c_void_p), ("cls", C.c_void_p), ("partial", C.c_void_p), ("est", C.c_void_p)]
@@ -362,6 +362,8 @@ ENC_SYMBOLS = [
 # ... and its trainer of Huffman codes (no context, no GPU)
 ENC_TOOL_SYMBOLS = [
     ("thip_huff_train", _I, [_P, C.c_size_t, _P, _I, _P, _P]),
+    ("thip_quant_info_from_setup", _I, [_P, C.c_size_t, _P]),
+    ("thip_quant_info_free", None, [_P]),
 ]
 
 # include/thip_ogg.h

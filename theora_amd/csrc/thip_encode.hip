@@ -34,6 +34,7 @@
 #include "thip_rate.h"
 #include "thip_ratectl.h"
 #include "thip_hufftrain.h"
+#include "thip_quant.h"
 #include "thip_encode_modes.h"
 #include "thip_encode_bqi.h"
 #include "thip_encode_mask.h"
@@ -83,7 +84,10 @@ struct BitW {
 
 // ---- the setup header's contents (theoraenc_hip.h) -------------------------------------------------------------------
 struct EncSetup {
-  QuantParams qp;               // three base matrices (luma intra, chroma intra, inter); one range of 63 a (qti, pli), both ends alike
+  QuantParams qp;               // built in: three base matrices (luma intra, chroma intra, inter); one range of 63 a (qti, pli), both
+                                // ends alike.  A caller's (TH_ENCCTL_SET_QUANT_PARAMS): consolidated, as the header carries them
+  bool custom_quant = false;    // qp is a caller's: the header's quantiser part is then libtheora's packing (thip_quant.h)
+  QuantCopy quant;              // qp as a th_quant_info, what TH_ENCCTL_THIP_GET_QUANT_PARAMS hands out
   uint32_t code[80][32];        // Huffman codes (MSB first), lengths
   uint8_t len[80][32];
   std::vector<uint8_t> trees;   // the 80 trees as written (spec 6.4.4), a bit string packed MSB first ...
@@ -138,7 +142,8 @@ void enc_builtin_codes(th_huff_code codes[80][32]) {
   }
 }
 
-void enc_setup_init(EncSetup &s) {
+// the built-in quantisation parameters (theoraenc_hip.h, "Setup header")
+void enc_setup_builtin_quant(EncSetup &s) {
   QuantParams &q = s.qp;
   for (int qi = 0; qi < 64; qi++) {
     q.lflims[qi] = (uint8_t)((31 * (63 - qi) + 31) / 63);
@@ -159,6 +164,12 @@ void enc_setup_init(EncSetup &s) {
       q.qrsizes[qti][pli][0] = 63;
       q.qrbmis[qti][pli][0] = q.qrbmis[qti][pli][1] = qti ? 2 : pli ? 1 : 0;
     }
+  s.custom_quant = false;
+  s.quant.assign(q);
+}
+
+void enc_setup_init(EncSetup &s) {
+  enc_setup_builtin_quant(s);
   std::vector<th_huff_code> codes(80 * 32);
   enc_builtin_codes((th_huff_code(*)[32])codes.data());
   enc_setup_codes(s, (const th_huff_code(*)[32])codes.data());
@@ -352,6 +363,15 @@ struct th_enc_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
 
 extern "C" {
 
+// lambda[qi], the weight of every decision made at qi: the inter luma step at zig-zag index 1 of the parameters in force
+static void enc_setup_lambda(th_enc_ctx *e) {
+  for (int qi = 0; qi < 64; qi++) {
+    uint16_t step[64];
+    compute_qmat(e->setup.qp, 1, 0, qi, step);
+    e->lambda[qi] = step[1];
+  }
+}
+
 th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   if (!info) return nullptr;
   const th_info &i = *info;
@@ -389,11 +409,7 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   e->nmbs = (int)e->mbs.size();
   e->nchunks = (e->nfrags + kEncChunk - 1) / kEncChunk;
   enc_setup_init(e->setup);
-  for (int qi = 0; qi < 64; qi++) {
-    uint16_t step[64];
-    compute_qmat(e->setup.qp, 1, 0, qi, step);
-    e->lambda[qi] = step[1];
-  }
+  enc_setup_lambda(e);
   memset(&e->stats, 0, sizeof(e->stats));
   memset(&e->thist, 0, sizeof(e->thist));
   memset(&e->istats, 0, sizeof(e->istats));
@@ -1038,18 +1054,20 @@ static int enc_rate_alloc(th_enc_ctx *e) {
   ENC_TRY(hipMalloc((void **)&e->d_rcoded, (size_t)n * 8));
   ENC_TRY(hipMalloc((void **)&e->d_rcls, (size_t)n * 8));
   if (!e->d_rmbs) ENC_TRY(hipMalloc((void **)&e->d_rmbs, (size_t)std::max(e->nmbs, 1) * sizeof(uint4)));   // (enc_cut_alloc's, else)
-  ENC_TRY(hipMalloc((void **)&e->d_rtab, 6 * 64 * 64 * sizeof(uint2)));
+  ENC_TRY(hipMalloc((void **)&e->d_rtab, 6 * 64 * 64 * sizeof(uint2) + 6 * 64 * sizeof(uint16_t)));   // the table, then its floor
   ENC_TRY(hipMalloc((void **)&e->d_rlam, 64 * sizeof(int)));
   ENC_TRY(hipMalloc((void **)&e->d_rlens, 80 * 32));
   ENC_TRY(hipMalloc((void **)&e->d_rpart, (size_t)e->rate_nwg * 64 * kRatePartial * 4));
   ENC_TRY(hipMalloc((void **)&e->d_rest, 64 * 8));
   ENC_TRY(hipHostMalloc((void **)&e->h_rest, 64 * 8, hipHostMallocDefault));
-  std::vector<uint16_t> steps(6 * 64 * 64);
-  for (int t = 0; t < 6; t++)
-    for (int q = 0; q < 64; q++) compute_qmat(e->setup.qp, t / 3, t % 3, q, &steps[(t * 64 + q) * 64]);
+  std::vector<uint16_t> steps(6 * 64 * 64), floor(6 * 64);
+  quant_all_steps(e->setup.qp, steps.data());
+  if (!rate_steps_ok(steps.data(), true)) return TH_EFAULT;   // (qmin and the cap of spec 6.4.3 keep every step in 8..4096)
   std::vector<uint2> tab(6 * 64 * 64);
   rate_form_table(tab.data(), steps.data());
+  rate_form_floor(floor.data(), steps.data());
   ENC_TRY(hipMemcpy(e->d_rtab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(e->d_rtab + tab.size(), floor.data(), floor.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_rlam, e->lambda, sizeof(e->lambda), hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(e->d_rlens, e->setup.len, 80 * 32, hipMemcpyHostToDevice));
   e->rate_dev = true;
@@ -1073,6 +1091,7 @@ static int enc_rate_probe(th_enc_ctx *e, const EncPlanes &g, bool key, bool sear
   a.tab = e->d_rtab;
   a.mbs = e->d_rmbs;
   a.lam = e->d_rlam;
+  a.floor = (const uint16_t *)(e->d_rtab + 6 * 64 * 64);
   a.nmbx = e->nmbx;
   a.hdec = e->hdec;
   a.vdec = e->vdec;
@@ -1990,28 +2009,32 @@ static void enc_header(const th_enc_ctx *e, int which, const th_comment *tc, std
     const EncSetup &s = e->setup;
     const QuantParams &q = s.qp;
     int nb = 0;
-    for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(q.lflims[qi]));
-    bw.put((uint32_t)nb, 3);
-    for (int qi = 0; qi < 64; qi++) bw.put(q.lflims[qi], nb);
-    for (const uint16_t *sc : {q.acscale, q.dcscale}) {
-      nb = 1;
-      for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(sc[qi]));
-      bw.put((uint32_t)nb - 1, 4);
-      for (int qi = 0; qi < 64; qi++) bw.put(sc[qi], nb);
-    }
-    bw.put((uint32_t)q.nbms - 1, 9);
-    for (uint8_t b : q.bms) bw.put(b, 8);
-    const int bmbits = ilog((uint32_t)q.nbms - 1);
-    for (int qti = 0; qti < 2; qti++)
-      for (int pli = 0; pli < 3; pli++) {
-        if (qti > 0 || pli > 0) bw.put(1, 1);   // NEWQR: every (qti, pli) states its ranges
-        bw.put((uint32_t)q.qrbmis[qti][pli][0], bmbits);
-        for (int qri = 0, qi = 0; qri < q.nqrs[qti][pli]; qri++) {
-          bw.put((uint32_t)q.qrsizes[qti][pli][qri] - 1, ilog((uint32_t)(62 - qi)));
-          qi += q.qrsizes[qti][pli][qri];
-          bw.put((uint32_t)q.qrbmis[qti][pli][qri + 1], bmbits);
-        }
+    if (s.custom_quant) {   // a caller's parameters: libtheora's packing, with its duplicate codes (thip_quant.h)
+      quant_pack(q, [&](uint32_t v, int n) { bw.put(v, n); });
+    } else {
+      for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(q.lflims[qi]));
+      bw.put((uint32_t)nb, 3);
+      for (int qi = 0; qi < 64; qi++) bw.put(q.lflims[qi], nb);
+      for (const uint16_t *sc : {q.acscale, q.dcscale}) {
+        nb = 1;
+        for (int qi = 0; qi < 64; qi++) nb = std::max(nb, ilog(sc[qi]));
+        bw.put((uint32_t)nb - 1, 4);
+        for (int qi = 0; qi < 64; qi++) bw.put(sc[qi], nb);
       }
+      bw.put((uint32_t)q.nbms - 1, 9);
+      for (uint8_t b : q.bms) bw.put(b, 8);
+      const int bmbits = ilog((uint32_t)q.nbms - 1);
+      for (int qti = 0; qti < 2; qti++)
+        for (int pli = 0; pli < 3; pli++) {
+          if (qti > 0 || pli > 0) bw.put(1, 1);   // NEWQR: every (qti, pli) states its ranges
+          bw.put((uint32_t)q.qrbmis[qti][pli][0], bmbits);
+          for (int qri = 0, qi = 0; qri < q.nqrs[qti][pli]; qri++) {
+            bw.put((uint32_t)q.qrsizes[qti][pli][qri] - 1, ilog((uint32_t)(62 - qi)));
+            qi += q.qrsizes[qti][pli][qri];
+            bw.put((uint32_t)q.qrbmis[qti][pli][qri + 1], bmbits);
+          }
+        }
+    }
     for (int64_t k = 0; k < s.tree_bits; k++) bw.put((s.trees[k >> 3] >> (7 - (k & 7))) & 1, 1);
   }
   bw.flush();
@@ -2289,6 +2312,28 @@ int th_encode_ctl(th_enc_ctx *e, int req, void *buf, size_t buf_sz) {
       enc_setup_codes(e->setup, (const th_huff_code(*)[32])buf);
       return 0;
     }
+    case TH_ENCCTL_SET_QUANT_PARAMS: {
+      const bool restore = !buf && buf_sz == 0;
+      if (!restore && (!buf || buf_sz != sizeof(th_quant_info))) return TH_EIMPL;   // (theoraenc_hip.h: the deviation of request 0)
+      // every table of steps, on the host and on the device, is made at the first frame that needs it: none exists yet
+      if (e->nheaders_out > 0 || enc_begun(e)) return TH_EINVAL;
+      if (restore) {
+        enc_setup_builtin_quant(e->setup);
+      } else {
+        if (!quant_info_valid((const th_quant_info *)buf)) return TH_EINVAL;
+        QuantParams q;
+        quant_params_from_info(*(const th_quant_info *)buf, q);   // (before the copy is replaced: buf may be the copy itself)
+        e->setup.qp = q;
+        e->setup.quant.assign(q);
+        e->setup.custom_quant = true;
+      }
+      enc_setup_lambda(e);
+      return 0;
+    }
+    case TH_ENCCTL_THIP_GET_QUANT_PARAMS:
+      if (!buf || buf_sz != sizeof(th_quant_info)) return TH_EINVAL;
+      *(th_quant_info *)buf = e->setup.quant.qi;
+      return 0;
     case TH_ENCCTL_THIP_GET_HUFFMAN_CODES: {
       if (!buf || buf_sz != sizeof(th_huff_code) * 80 * 32) return TH_EINVAL;
       th_huff_code(*out)[32] = (th_huff_code(*)[32])buf;
@@ -2780,7 +2825,8 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   if ((coef || dc || tok) && (!q->coef || (inter && !q->stats))) return THIP_EFAULT;
   if (dc || tok) {
     if (!q->steps || !q->qdc || (inter && (!q->lambda || !q->coded || !q->cls))) return THIP_EFAULT;
-    if (!rate_steps_ok(q->steps)) return THIP_EINVAL;
+    if (q->any_order != 0 && q->any_order != 1) return THIP_EINVAL;
+    if (!rate_steps_ok(q->steps, q->any_order == 1)) return THIP_EINVAL;
     if (inter)
       for (int k = 0; k < 64; k++)
         if (q->lambda[k] < 0 || q->lambda[k] > (1 << 24)) return THIP_EINVAL;
@@ -2816,15 +2862,18 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   }
   R.hdec = hdec;
   R.vdec = vdec;
-  // one allocation: tab [6][64][64] uint2 | lambda [64] | lens [80][32]
-  constexpr size_t o_lam = 6 * 64 * 64 * sizeof(uint2), o_lens = o_lam + 64 * sizeof(int);
+  // one allocation: tab [6][64][64] uint2 | lambda [64] | lens [80][32] | floor [6][64] uint16
+  constexpr size_t o_lam = 6 * 64 * 64 * sizeof(uint2), o_lens = o_lam + 64 * sizeof(int), o_floor = o_lens + 80 * 32;
   uint8_t *d = nullptr;
-  ENC_TRY(hipMalloc((void **)&d, o_lens + 80 * 32));
+  ENC_TRY(hipMalloc((void **)&d, o_floor + 6 * 64 * sizeof(uint16_t)));
   struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
   if (dc || tok) {
     std::vector<uint2> tab(6 * 64 * 64);
+    std::vector<uint16_t> floor(6 * 64);
     rate_form_table(tab.data(), q->steps);
+    rate_form_floor(floor.data(), q->steps);
     ENC_TRY(hipMemcpy(d, tab.data(), o_lam, hipMemcpyHostToDevice));
+    ENC_TRY(hipMemcpy(d + o_floor, floor.data(), floor.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     if (inter) ENC_TRY(hipMemcpy(d + o_lam, q->lambda, 64 * sizeof(int), hipMemcpyHostToDevice));
   }
   if (bits) ENC_TRY(hipMemcpy(d + o_lens, q->lens, 80 * 32, hipMemcpyHostToDevice));
@@ -2833,6 +2882,7 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   a.tab = (const uint2 *)d;
   a.mbs = (const uint4 *)q->stats;
   a.lam = (const int *)(d + o_lam);
+  a.floor = (const uint16_t *)(d + o_floor);
   a.nmbx = nmbx;
   a.hdec = hdec;
   a.vdec = vdec;

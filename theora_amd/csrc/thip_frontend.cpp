@@ -34,6 +34,7 @@
 #include "../../include/theoradec_hip.h"
 #include "thip_bitstream.h"
 #include "thip_ctx.h"
+#include "thip_quant.h"
 // The one backend entry point the front end reaches only on request (TH_DECCTL_THIP_PICTURE_OUT): referenced weakly, so that this
 // translation unit still links on its own against a backend that provides just the decoding slots (the front end's native test
 // drivers stub those); inside libtheora_hip.so the definition in thip_decode.hip is always there.
@@ -428,50 +429,7 @@ void build_huff_lut(HuffTree &t) {
 }
 
 int parse_setup(BitReader &br, th_setup_info *s) {   // spec 6.4
-  QuantParams &q = s->qp;
-  int nbits = (int)br.read(3);   // 6.4.1 loop filter limits
-  for (int qi = 0; qi < 64; qi++) q.lflims[qi] = (uint8_t)br.read(nbits);
-  nbits = (int)br.read(4) + 1;   // 6.4.2 quantization parameters
-  for (int qi = 0; qi < 64; qi++) q.acscale[qi] = (uint16_t)br.read(nbits);
-  nbits = (int)br.read(4) + 1;
-  for (int qi = 0; qi < 64; qi++) q.dcscale[qi] = (uint16_t)br.read(nbits);
-  q.nbms = (int)br.read(9) + 1;
-  if (q.nbms > 384 || br.overrun()) return TH_EBADHEADER;
-  q.bms.resize((size_t)q.nbms * 64);
-  for (int i = 0; i < q.nbms * 64; i++) q.bms[i] = (uint8_t)br.read(8);
-  for (int qti = 0; qti < 2; qti++)
-    for (int pli = 0; pli < 3; pli++) {
-      int newqr = 1;
-      if (qti > 0 || pli > 0) newqr = (int)br.bit();
-      if (!newqr) {
-        int rpqr = 0;
-        if (qti > 0) rpqr = (int)br.bit();
-        int qtj, plj;
-        if (rpqr) {
-          qtj = qti - 1;
-          plj = pli;
-        } else {
-          qtj = (3 * qti + pli - 1) / 3;
-          plj = (pli + 2) % 3;
-        }
-        q.nqrs[qti][pli] = q.nqrs[qtj][plj];
-        memcpy(q.qrsizes[qti][pli], q.qrsizes[qtj][plj], sizeof(q.qrsizes[0][0]));
-        memcpy(q.qrbmis[qti][pli], q.qrbmis[qtj][plj], sizeof(q.qrbmis[0][0]));
-      } else {
-        int qri = 0, qi = 0;
-        q.qrbmis[qti][pli][0] = (int)br.read(ilog((uint32_t)q.nbms - 1));
-        if (q.qrbmis[qti][pli][0] >= q.nbms) return TH_EBADHEADER;
-        do {
-          q.qrsizes[qti][pli][qri] = (int)br.read(ilog((uint32_t)(62 - qi))) + 1;
-          qi += q.qrsizes[qti][pli][qri];
-          qri++;
-          q.qrbmis[qti][pli][qri] = (int)br.read(ilog((uint32_t)q.nbms - 1));
-          if (q.qrbmis[qti][pli][qri] >= q.nbms) return TH_EBADHEADER;
-        } while (qi < 63 && qri < 63);
-        if (qi != 63) return TH_EBADHEADER;
-        q.nqrs[qti][pli] = qri;
-      }
-    }
+  if (const int rc = quant_parse(br, s->qp)) return rc;   // 6.4.1 - 6.4.2 (thip_quant.h)
   for (int hti = 0; hti < 80; hti++) {   // 6.4.4
     HuffTree &t = s->huff[hti];
     t.nnodes = 0;
@@ -1276,6 +1234,32 @@ int th_decode_headerin(th_info *info, th_comment *tc, th_setup_info **setup, ogg
 }
 
 void th_setup_free(th_setup_info *setup) { delete setup; }
+
+// theoraenc_hip.h: the quantisation parameters of a setup header packet, read by th_decode_headerin itself as the third header of a
+// stream (so the answers to bad bytes are its own)
+int thip_quant_info_from_setup(const unsigned char *packet, size_t bytes, th_quant_info *out) {
+  if (!packet || !out) return THIP_EFAULT;
+  th_info info;
+  th_comment tc;
+  th_info_init(&info);
+  th_comment_init(&tc);
+  char vendor[1] = {0};
+  info.frame_width = info.frame_height = 16;   // (the first two headers have come)
+  tc.vendor = vendor;
+  th_setup_info *s = nullptr;
+  ogg_packet op;
+  memset(&op, 0, sizeof(op));
+  op.packet = const_cast<unsigned char *>(packet);
+  op.bytes = (long)bytes;
+  const int rc = th_decode_headerin(&info, &tc, &s, &op);
+  if (rc < 0) return rc;
+  if (!s) return TH_EBADHEADER;   // (only a setup header gives a setup)
+  const int rc2 = quant_info_alloc(s->qp, out);
+  th_setup_free(s);
+  return rc2;
+}
+
+void thip_quant_info_free(th_quant_info *qi) { quant_info_free(qi); }
 
 th_dec_ctx *th_decode_alloc(const th_info *info, const th_setup_info *setup) { return th_decode_alloc_on(info, setup, -1); }
 

@@ -14,15 +14,16 @@
 //                      which class (ballots into one 64-bit word each).
 //   k_rate_tok         a persistent grid, one wave a block, lane q: DC prediction at q, the AC levels at q and the block's tokens,
 //                      counted into the work group's LDS histogram [q][luma / chroma][Huffman group][token] (u16 pairs).  The
-//                      levels are walked over the indices that are non-zero at ANY q (a ballot at qi 63, whose steps are the least:
-//                      the probe's precondition, rate_steps_ok below; tests/test_rate_stage_cpu.py asserts it of the setup's
-//                      tables), so a sparse block costs a few iterations.  The quantiser tables of the frame type sit in LDS beside the
+//                      levels are walked over the indices that are non-zero at ANY q (a ballot against the floor, the least step
+//                      over q of each (table, z): rate_form_floor of thip_quant.h.  With steps that fall with q, the built-in
+//                      ones, the floor is the step at qi 63), so a sparse block costs a few iterations.  The quantiser tables of the frame type sit in LDS beside the
 //                      histogram (48 KB key, 96 KB inter).  Each work group writes its histogram once, as a partial.
 //   k_rate_bits        one work group per q (one group alone reads the partials too slowly): the partials summed, the least bits of
 //                      each of the four table choices (the setup's code lengths), the extra bits and the frame header -> E[q] (int64;
 //                      the host reads back 512 bytes).
 #pragma once
 #include "thip_encode_inter.h"
+#include "thip_quant.h"
 
 namespace thip {
 
@@ -145,6 +146,7 @@ struct RateArgs {
   const uint2 *tab;      // [6 tables][64 z][64 q]: (d | m << 16, l) of oc_enc_quantize
   const uint4 *mbs;      // k_rate_me's words (inter)
   const int *lam;        // [64]: the inter luma step at zig-zag index 1 of each qi
+  const uint16_t *floor; // [6 tables][64 z]: the least step over q (rate_form_floor)
   int nmbx, hdec, vdec;
 };
 
@@ -162,11 +164,10 @@ __global__ __launch_bounds__(256) void k_rate_dc(int16_t *qdc, uint64_t *coded, 
   const int16_t *cb = a.coef + ((int64_t)s.var * nfrags + fi) * 64;
   qdc[fi * 64 + q] = (int16_t)rate_quant(cb[0], a.tab[(s.tab * 64 + 0) * 64 + q]);
   if (!kInter) return;
-  // a NOMV block is coded when a level is not zero: test the indices that are non-zero at qi 63 (a superset at every q)
+  // a NOMV block is coded when a level is not zero: test the indices that are non-zero under the floor (a superset at every q)
   const int16_t *cn = a.coef + (nfrags + fi) * 64;
   const int cz = cn[kFZigZag[q]];   // lane z holds zig-zag index z of the NOMV residual
-  const uint2 e63 = a.tab[((3 + p) * 64 + q) * 64 + 63];
-  uint64_t m = __ballot(abs(cz << 1) >= (int)(e63.x & 0xFFFFu));
+  uint64_t m = __ballot(abs(cz << 1) >= (int)a.floor[(3 + p) * 64 + q]);
   bool nz = false;
   while (m) {
     const int z = __builtin_ctzll(m);
@@ -199,14 +200,22 @@ __global__ __launch_bounds__(64 * kRateTokWaves) void k_rate_tok(uint32_t *parti
   __shared__ uint32_t s_h[64 * kRateHistStride];
   __shared__ uint32_t s_side[64];
   // the quantiser entries (d | m << 16) of the tables this frame type uses, [table][z][q]: lane q reads a word of its own bank.
-  // (Read from global memory, every index a lane quantises cost a dependent round trip.)  l follows from d (rate_entry).  s_d63:
-  // the qi-63 step of each (table, z), for the ballot of the indices any q may find non-zero.
+  // (Read from global memory, every index a lane quantises cost a dependent round trip.)  l follows from d (rate_entry).  s_floor:
+  // the least step over q of each (table, z), for the ballot of the indices any q may find non-zero -- the minimum of the row's 64
+  // entries in s_tab, one thread a row.  Thread i starts at entry i & 63, so that the lanes of a wave, whose rows lie 64 words
+  // apart, read 64 different banks.
   __shared__ uint32_t s_tab[kTabs * 64 * 64];
-  __shared__ uint32_t s_d63[kTabs * 64];
+  __shared__ uint32_t s_floor[kTabs * 64];
   for (int i = (int)threadIdx.x; i < 64 * kRateHistStride; i += 64 * kRateTokWaves) s_h[i] = 0;
   for (int i = (int)threadIdx.x; i < kTabs * 64 * 64; i += 64 * kRateTokWaves) s_tab[i] = a.tab[i].x;
-  for (int i = (int)threadIdx.x; i < kTabs * 64; i += 64 * kRateTokWaves) s_d63[i] = a.tab[i * 64 + 63].x & 0xFFFFu;
   if (threadIdx.x < 64) s_side[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = (int)threadIdx.x; i < kTabs * 64; i += 64 * kRateTokWaves) {
+    uint32_t m = 0xFFFFu;
+#pragma unroll 8
+    for (int k = 0; k < 64; k++) m = min(m, s_tab[i * 64 + ((k + i) & 63)] & 0xFFFFu);
+    s_floor[i] = m;
+  }
   __syncthreads();
   const int q = (int)threadIdx.x & 63;
   uint32_t *h = s_h + q * kRateHistStride;
@@ -236,7 +245,7 @@ __global__ __launch_bounds__(64 * kRateTokWaves) void k_rate_tok(uint32_t *parti
     for (int v = 0; v < nvar; v++) {
       cz[v] = a.coef[((int64_t)v * nfrags + fi) * 64 + kFZigZag[q]];
       const int t = v == 0 ? p : 3 + p;
-      any |= __ballot(abs(cz[v] << 1) >= (int)s_d63[t * 64 + q]);
+      any |= __ballot(abs(cz[v] << 1) >= (int)s_floor[t * 64 + q]);
     }
     any &= ~1ull;
     const int cc = p > 0;
@@ -347,17 +356,7 @@ inline void rate_form_table(uint2 *tab, const uint16_t *steps) {
       for (int z = 0; z < 64; z++) tab[(t * 64 + z) * 64 + q] = enc_quant_entry(steps[(t * 64 + q) * 64 + z], 0);
 }
 
-// the probe's precondition: k_rate_dc and k_rate_tok ballot the indices that are non-zero at qi 63, so the step of every (table, z)
-// at qi 63 must be the least over q.  (Steps outside 1..32767 fail too.)
-inline bool rate_steps_ok(const uint16_t *steps) {
-  for (int t = 0; t < 6; t++)
-    for (int q = 0; q < 64; q++)
-      for (int z = 0; z < 64; z++) {
-        const int d = steps[(t * 64 + q) * 64 + z];
-        if (d < 1 || d > 32767 || d < steps[(t * 64 + 63) * 64 + z]) return false;
-      }
-  return true;
-}
+// (rate_steps_ok, what the probe asks of a table set, and rate_form_floor are host arithmetic: thip_quant.h)
 
 // coef [1 or 3][nfrags][64]; R, mbs: the inter frame's reference and k_rate_me's words
 inline hipError_t rate_launch_coef(int16_t *coef, const EncPlanes &g, int64_t n, hipStream_t stream) {

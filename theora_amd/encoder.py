@@ -50,6 +50,8 @@ TH_ENCCTL_THIP_GET_ROI_STATS = 0x7226
 TH_ENCCTL_THIP_GET_TOKEN_HIST = 0x7227
 TH_ENCCTL_THIP_GET_HUFFMAN_CODES = 0x7228
 TH_ENCCTL_SET_HUFFMAN_CODES = 0
+TH_ENCCTL_SET_QUANT_PARAMS = 2
+TH_ENCCTL_THIP_GET_QUANT_PARAMS = 0x7229
 TH_NHUFFMAN_TABLES, TH_NDCT_TOKENS = 80, 32
 RD_QUANT_DEFAULT = 3   # the recommended weight w (lambda's weight w / 16): include/theoraenc_hip.h, "Level choice"
 TWO_PASS_HEADER_BYTES, TWO_PASS_RECORD_BYTES = 1084, 264   # THIP_2PASS_HEADER_BYTES, THIP_2PASS_RECORD_BYTES
@@ -196,6 +198,96 @@ def _huff_codes_out(buf):
     return np.stack([a["pattern"].astype(np.int64), a["nbits"].astype(np.int64)], axis=-1)
 
 
+class QuantRanges(C.Structure):
+    """th_quant_ranges (include/theoraenc_hip.h)."""
+    _fields_ = [("nranges", C.c_int), ("sizes", C.POINTER(C.c_int)), ("base_matrices", C.POINTER(C.c_ubyte * 64))]
+
+
+class QuantInfoStruct(C.Structure):
+    """th_quant_info (include/theoraenc_hip.h): 464 bytes."""
+    _fields_ = [("dc_scale", C.c_uint16 * 64), ("ac_scale", C.c_uint16 * 64), ("loop_filter_limits", C.c_ubyte * 64),
+                ("qi_ranges", (QuantRanges * 3) * 2)]
+
+
+class QuantInfo:
+    """The quantisation parameters of a stream (include/theoraenc_hip.h, "Quantisation parameters"): dc_scale, ac_scale (64 each,
+    0..65535), loop_filter_limits (64, 0..127), and per (qti, pli) sizes[qti][pli] (the ranges' sizes, summing to 63) and
+    matrices[qti][pli] ((ranges + 1, 64), natural order), all numpy arrays.  struct() builds the th_quant_info and keeps its arrays
+    alive with this object."""
+
+    def __init__(self, dc_scale, ac_scale, loop_filter_limits, sizes, matrices):
+        self.dc_scale = np.asarray(dc_scale, np.int64).reshape(64)
+        self.ac_scale = np.asarray(ac_scale, np.int64).reshape(64)
+        self.loop_filter_limits = np.asarray(loop_filter_limits, np.int64).reshape(64)
+        self.sizes = [[np.asarray(sizes[qti][pli], np.int64).reshape(-1) for pli in range(3)] for qti in range(2)]
+        self.matrices = [[np.asarray(matrices[qti][pli], np.int64).reshape(-1, 64) for pli in range(3)] for qti in range(2)]
+        self._keep = None
+
+    def struct(self):
+        """-> th_quant_info as the arrays are now (no check beyond the widths of the fields: the library checks validity)."""
+        for a, top in ((self.dc_scale, 65535), (self.ac_scale, 65535), (self.loop_filter_limits, 255)):
+            if a.min() < 0 or a.max() > top:
+                raise ValueError("a scale is 16 bits wide and a loop-filter limit 8")
+        s, keep = QuantInfoStruct(), []
+        s.dc_scale[:], s.ac_scale[:] = [int(v) for v in self.dc_scale], [int(v) for v in self.ac_scale]
+        s.loop_filter_limits[:] = [int(v) for v in self.loop_filter_limits]
+        for qti in range(2):
+            for pli in range(3):
+                sz, m = self.sizes[qti][pli], self.matrices[qti][pli]
+                if len(m) != len(sz) + 1 or (m.size and (m.min() < 0 or m.max() > 255)) or (sz.size and abs(sz).max() >= 1 << 31):
+                    raise ValueError("(qti %d, pli %d): n sizes go with n + 1 matrices of 64 bytes" % (qti, pli))
+                csz = (C.c_int * max(len(sz), 1))(*[int(v) for v in sz])
+                cm = ((C.c_ubyte * 64) * len(m)).from_buffer_copy(m.astype(np.uint8).tobytes())
+                keep += [csz, cm]
+                r = s.qi_ranges[qti][pli]
+                r.nranges, r.sizes, r.base_matrices = len(sz), csz, C.cast(cm, C.POINTER(C.c_ubyte * 64))
+        self._keep = (s, keep)
+        return s
+
+    @classmethod
+    def from_struct(cls, s):
+        """A th_quant_info -> QuantInfo (copies everything: the struct's arrays may go away)."""
+        sizes, mats = [[None] * 3 for _ in range(2)], [[None] * 3 for _ in range(2)]
+        for qti in range(2):
+            for pli in range(3):
+                r = s.qi_ranges[qti][pli]
+                sizes[qti][pli] = np.array([r.sizes[k] for k in range(r.nranges)], np.int64)
+                mats[qti][pli] = np.array([list(r.base_matrices[k]) for k in range(r.nranges + 1)], np.int64).reshape(-1, 64)
+        return cls(list(s.dc_scale), list(s.ac_scale), list(s.loop_filter_limits), sizes, mats)
+
+    def __eq__(self, o):
+        return (isinstance(o, QuantInfo) and np.array_equal(self.dc_scale, o.dc_scale) and np.array_equal(self.ac_scale, o.ac_scale)
+                and np.array_equal(self.loop_filter_limits, o.loop_filter_limits)
+                and all(np.array_equal(self.sizes[t][p], o.sizes[t][p]) and np.array_equal(self.matrices[t][p], o.matrices[t][p])
+                        for t in range(2) for p in range(3)))
+
+    __hash__ = None
+
+
+def quant_from_setup(packet):
+    """thip_quant_info_from_setup: the quantisation parameters of a Theora setup header packet -> QuantInfo.  ValueError for bytes
+    th_decode_headerin refuses as a setup header.  Host only."""
+    L = _lib.load()
+    s = QuantInfoStruct()
+    data = bytes(packet)
+    rc = L.thip_quant_info_from_setup(data, len(data), C.byref(s))
+    if rc < 0:
+        raise ValueError("thip_quant_info_from_setup returned %d" % rc)
+    try:
+        return QuantInfo.from_struct(s)
+    finally:
+        L.thip_quant_info_free(C.byref(s))
+
+
+def quant_from_headers(header_packets):
+    """The quantisation parameters of a stream from its header packets (the setup header is the one of type 0x82) -> QuantInfo,
+    for Encoder(quant=...)."""
+    for pkt in header_packets:
+        if len(pkt) and bytes(pkt)[0] == 0x82:
+            return quant_from_setup(pkt)
+    raise ValueError("no setup header among the packets")
+
+
 def _token_hist_dict(h):
     return dict(count=np.frombuffer(bytes(h.count), np.uint32).reshape(5, 2, 32).astype(np.int64), huff=list(h.huff), key=int(h.key),
                 device=int(h.device))
@@ -255,7 +347,7 @@ class Encoder:
     def __init__(self, w, h, fmt, quality, pic=None, fps=(30, 1), kfgshift=6, device=None, comments=(), inter=False,
                  keyframe_interval=None, bitrate=None, rate_flags=None, rate_buffer=None, all_modes=False,
                  block_qi=0, device_pack=None, auto_keyframes=None, masking=0, rd_modes=False, rd_skip=False,
-                 rd_quant=0, huffman=None):
+                 rd_quant=0, huffman=None, quant=None):
         """inter: motion-compensated inter frames (TH_ENCCTL_THIP_SET_INTER_FRAMES); keyframe_interval: then
         TH_ENCCTL_SET_KEYFRAME_FREQUENCY_FORCE (clamped to [1, 1 << kfgshift]; the value in force is self.keyframe_interval).
         bitrate: bits a second, bitrate mode (TH_ENCCTL_SET_BITRATE after th_encode_alloc); then rate_flags (TH_RATECTL_*) and
@@ -273,7 +365,8 @@ class Encoder:
         rd_quant: the AC levels of coded blocks by the least D + lambda R with lambda's weight rd_quant / 16, 1..64
         (TH_ENCCTL_THIP_SET_RD_QUANT; 0 off; True for the recommended RD_QUANT_DEFAULT).  huffman: an (80, 32, 2) array of
         (pattern, nbits), the Huffman codes of the stream in place of the built-in ones (TH_ENCCTL_SET_HUFFMAN_CODES;
-        train_huffman makes them)."""
+        train_huffman makes them).  quant: a QuantInfo, the quantisation parameters of the stream in place of the built-in ones
+        (TH_ENCCTL_SET_QUANT_PARAMS; quant_from_headers reads another stream's)."""
         L = self._L = _lib.load()
         self.info = make_info(w, h, fmt, quality, pic, fps, kfgshift)
         self._enc = (L.th_encode_alloc(C.byref(self.info)) if device is None
@@ -283,6 +376,8 @@ class Encoder:
         self.comments = list(comments)
         if huffman is not None:
             self.set_huffman_codes(huffman)
+        if quant is not None:
+            self.set_quant_params(quant)
         self.hdec, self.vdec = int(not (fmt & 1)), int(not (fmt & 2))
         self.inter = bool(inter)
         self.keyframe_interval = None
@@ -359,6 +454,25 @@ class Encoder:
         if rc < 0:
             raise ValueError("TH_ENCCTL_SET_HUFFMAN_CODES returned %d: every set must be a full prefix-free code of all 32 tokens, "
                              "set before the first header packet" % rc)
+
+    def set_quant_params(self, quant):
+        """TH_ENCCTL_SET_QUANT_PARAMS, before header_packets(): a QuantInfo, or None for the built-in parameters.  ValueError for
+        a set that is not valid, or too late."""
+        if quant is None:
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_SET_QUANT_PARAMS, None, 0)
+        else:
+            s = quant.struct()
+            rc = self._L.th_encode_ctl(self._enc, TH_ENCCTL_SET_QUANT_PARAMS, C.byref(s), C.sizeof(s))
+        if rc < 0:
+            raise ValueError("TH_ENCCTL_SET_QUANT_PARAMS returned %d: every (qti, pli) needs 1..63 ranges of sizes >= 1 summing to "
+                             "63, every loop-filter limit is at most 127, set before the first header packet" % rc)
+
+    def quant_params(self):
+        """TH_ENCCTL_THIP_GET_QUANT_PARAMS: the quantisation parameters in force -> QuantInfo (a copy)."""
+        s = QuantInfoStruct()
+        _lib.check(self._L.th_encode_ctl(self._enc, TH_ENCCTL_THIP_GET_QUANT_PARAMS, C.byref(s), C.sizeof(s)),
+                   "TH_ENCCTL_THIP_GET_QUANT_PARAMS")
+        return QuantInfo.from_struct(s)
 
     def huffman_codes(self):
         """TH_ENCCTL_THIP_GET_HUFFMAN_CODES: the codes in force, an (80, 32, 2) array of (pattern, nbits)."""
@@ -828,14 +942,17 @@ def inter_stage(frame, pixel_fmt, stages, classes, pic=None, lam=0, src=None, sr
 
 
 def rate_stage(frame, pixel_fmt, inter, stages, pic=None, groups=0, fixed=0, src=None, src_pitch=None, prev=None, ref_pitch=None,
-               steps=None, lam=None, lens=None, stats=None, coef=None, qdc=None, coded=None, cls=None, partial=None, est=None):
+               steps=None, lam=None, lens=None, stats=None, coef=None, qdc=None, coded=None, cls=None, partial=None, est=None,
+               any_order=0):
     """thip_enc_rate_stage (include/theora_hip.h): the rate probe's stages on the caller's buffers and tables, a test and diagnostic
     entry.  frame: (width, height); pic: (x, y, width, height), the whole frame when None; stages: an OR of _lib.ENC_RATE_*; src,
     prev: three device addresses each (None where there is none) with their pitches; steps [6][64][64], lam [64] and lens [80][32]:
-    anything numpy converts (None is NULL); the rest: device addresses, None is NULL.  Returns the entry's return code; nothing is
-    raised, the refusals are the caller's to look at."""
+    anything numpy converts (None is NULL); the rest: device addresses, None is NULL.  any_order: 1 lets the steps rise and fall
+    with q in any way (thip_enc_rate_req.any_order).  Returns the entry's return code; nothing is raised, the refusals are the
+    caller's to look at."""
     L = _lib.load()
     q = _lib.EncRateReq()
+    q.any_order = int(any_order)
     q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
     q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
     q.inter, q.stages, q.groups, q.fixed = int(inter), int(stages), int(groups), int(fixed)
