@@ -44,6 +44,7 @@
 #include "thip_encode_rdq.h"
 #include "thip_encode_pack.h"
 #include "thip_encode_cut.h"
+#include "thip_encode_entry.h"
 #include "thip_bitstream.h"
 #include "thip_ctx.h"
 #include "thip_device_guard.h"
@@ -378,9 +379,9 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   if (!i.frame_width || !i.frame_height || (i.frame_width & 15) || (i.frame_height & 15) || i.frame_width >= (1u << 20) ||
       i.frame_height >= (1u << 20))
     return nullptr;
-  if (!i.pic_width || !i.pic_height || i.pic_width > i.frame_width || i.pic_height > i.frame_height ||
-      i.pic_x > i.frame_width - i.pic_width || i.pic_y > i.frame_height - i.pic_height || i.pic_x > 255 ||
-      i.frame_height - i.pic_height - i.pic_y > 255)
+  // (the frame's sides are below 1 << 20: an unsigned field too large for an int is a negative one, which the rule refuses as well)
+  const PicRect pic{(int)i.pic_x, (int)i.pic_y, (int)i.pic_width, (int)i.pic_height};
+  if (pic_outside(pic, (int)i.frame_width, (int)i.frame_height) || i.pic_x > 255 || i.frame_height - i.pic_height - i.pic_y > 255)
     return nullptr;
   if ((int)i.pixel_fmt < 0 || (int)i.pixel_fmt >= TH_PF_NFORMATS || i.pixel_fmt == TH_PF_RSVD) return nullptr;
   if (i.quality < 0 || i.quality > 63 || i.keyframe_granule_shift < 0 || i.keyframe_granule_shift > 31) return nullptr;
@@ -399,11 +400,11 @@ th_enc_ctx *th_encode_alloc_on(const th_info *info, int device) {
   e->qi = i.quality;
   build_geometry(*e, (int)i.frame_width, (int)i.frame_height, (int)i.pixel_fmt);
   for (int p = 0; p < 3; p++) {
-    const int hd = p ? e->hdec : 0, vd = p ? e->vdec : 0;
-    e->cx0[p] = (int)i.pic_x >> hd;
-    e->cy0[p] = (int)i.pic_y >> vd;
-    e->cw[p] = (((int)(i.pic_x + i.pic_width) + hd) >> hd) - e->cx0[p];
-    e->ch[p] = (((int)(i.pic_y + i.pic_height) + vd) >> vd) - e->cy0[p];
+    const PicSpan sx = pic_span(pic.x, pic.w, p ? e->hdec : 0), sy = pic_span(pic.y, pic.h, p ? e->vdec : 0);
+    e->cx0[p] = sx.x0;
+    e->cy0[p] = sy.x0;
+    e->cw[p] = sx.n;
+    e->ch[p] = sy.n;
   }
   e->nmbx = e->nh[0] >> 1;
   e->nmbs = (int)e->mbs.size();
@@ -1178,18 +1179,8 @@ static int enc_cut_measure(th_enc_ctx *e, const EncPlanes &g) {
 
 // the four launches of a frame, reading the picture through `src` / `stride` (top-left pixel of the picture of each plane)
 static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int64_t stride[3]) {
-  EncPlanes g;
-  for (int p = 0; p < 3; p++) {
-    g.src[p] = src[p];
-    g.stride[p] = stride[p];
-    g.px0[p] = e->cx0[p];
-    g.py0[p] = e->cy0[p];
-    g.pw[p] = e->cw[p];
-    g.ph[p] = e->ch[p];
-    g.nh[p] = e->nh[p];
-    g.nv[p] = e->nv[p];
-    g.froff[p] = e->fro[p];
-  }
+  const th_info &i = e->info;
+  const EncPlanes g = enc_planes(*e, PicRect{(int)i.pic_x, (int)i.pic_y, (int)i.pic_width, (int)i.pic_height}, src, stride);
   const int64_t n = e->nfrags;
   e->mask_queued = false;   // (enc_mask_queue says otherwise; a dropped frame never gets there)
   e->roi_queued = false;    // (enc_roi_queue likewise)
@@ -2375,21 +2366,18 @@ int thip_huff_train(const thip_enc_token_hist *hists, size_t n, const th_huff_co
 int thip_enc_pack_tokens(const uint32_t *d_words, const uint32_t list_len[192], const uint32_t codes[80][32], const uint8_t lens[80][32],
                          int groups, int phase, uint8_t *d_packet, size_t cap_bytes, thip_enc_pack_result *res) {
   if (!d_words || !list_len || !codes || !lens || !d_packet || !res) return THIP_EFAULT;
-  if (groups < 1 || groups > kPackMaxGroups || phase < 0 || phase > 7 || ((uintptr_t)d_packet & 3)) return THIP_EINVAL;
+  if (groups < 1 || groups > kPackMaxGroups || phase < 0 || phase > 7 || misaligned(d_packet, 4)) return THIP_EINVAL;
   uint64_t T = 0;
   for (int k = 0; k < 192; k++) T += list_len[k];
   if (T >= (1ull << 31)) return THIP_EINVAL;   // (token indices are 32-bit with room for i + 1)
-  for (int h = 0; h < 80; h++)
-    for (int tok = 0; tok < 32; tok++)
-      if (lens[h][tok] < 1 || lens[h][tok] > 32) return THIP_EINVAL;
+  if (!table_within(&lens[0][0], 80 * 32, 1, 32)) return THIP_EINVAL;
   std::vector<uint32_t> cl(80 * 32);
   pack_cl_table(cl.data(), lens);
   // one allocation: list_len [192] | hist [320] | codes, cl [80 * 32] | glast [groups] | mtok [T] | gsum, gbase [groups] | rec
   const size_t words = 192 + 320 + 2 * 80 * 32 + (size_t)groups + (size_t)T, words8 = (words + 1) & ~(size_t)1;
-  uint8_t *d = nullptr;
-  ENC_TRY(hipMalloc((void **)&d, words8 * 4 + 2 * (size_t)groups * sizeof(PackSum) + sizeof(PackRec)));
-  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
-  uint32_t *w = (uint32_t *)d, *d_len = w;
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc(words8 * 4 + 2 * (size_t)groups * sizeof(PackSum) + sizeof(PackRec)));
+  uint32_t *w = (uint32_t *)buf.p, *d_len = w;
   PackBufs p;
   p.hist = w + 192;
   p.codes = p.hist + 320;
@@ -2429,31 +2417,14 @@ int thip_enc_inter_stage(const thip_enc_inter_req *q) {
   const bool search = st & THIP_ENC_INTER_SEARCH, decide = st & THIP_ENC_INTER_DECIDE, code = st & THIP_ENC_INTER_CODE;
   const bool dconly = st == THIP_ENC_INTER_DC, planes = search || decide || code;
   if (st <= 0 || st > 15 || ((st & THIP_ENC_INTER_DC) && !dconly)) return THIP_EINVAL;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
   if (q->classes != 2 && q->classes != 3) return THIP_EINVAL;
   const bool all = q->classes == 3;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
-  if (n64 > ((int64_t)1 << 24)) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  const PicRect pic = pic_rect(*q);
   if (planes) {
-    if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-        q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-      return THIP_EINVAL;
-    int ngold = 0;
-    for (int p = 0; p < 3; p++) {
-      if (!q->src[p] || !q->prev[p]) return THIP_EFAULT;
-      ngold += q->gold[p] != nullptr;
-    }
-    if (ngold != (all ? 3 : 0)) return all && ngold < 3 ? THIP_EFAULT : THIP_EINVAL;
-    for (int p = 0; p < 3; p++) {
-      const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
-      if (q->src_pitch[p] < pw || q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF) return THIP_EINVAL;
-    }
+    const EntryPlanes pl{q->src, q->src_pitch, q->prev, q->gold, q->ref_pitch};
+    if (const int rc = check_picture_planes(f, pic, pl, true, all ? Gold::required : Gold::forbidden)) return rc;
     if ((decide || code) && (q->lambda < 0 || q->lambda > (1 << 24))) return THIP_EINVAL;
     if (search && !q->stats) return THIP_EFAULT;
     if ((decide || code) && !q->words) return THIP_EFAULT;
@@ -2462,8 +2433,7 @@ int thip_enc_inter_stage(const thip_enc_inter_req *q) {
   }
   if (code) {
     if (!q->dequant) return THIP_EFAULT;
-    for (int k = 0; k < 384; k++)
-      if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
+    if (!table_within(q->dequant, 384, 1, 32767)) return THIP_EINVAL;
   }
   if (dconly && (!q->cmap || !q->dcq || !q->dcr)) return THIP_EFAULT;
   if (misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->dcr, 2)) return THIP_EINVAL;
@@ -2473,27 +2443,8 @@ int thip_enc_inter_stage(const thip_enc_inter_req *q) {
   const int64_t n = geo.nfrags;
   const int classes = q->classes, nmbx = geo.nh[0] >> 1, nmbs = nmbx * (geo.nv[0] >> 1);
   const size_t nchunks = (size_t)((n + kEncChunk - 1) / kEncChunk);
-  EncPlanes g = {};
-  EncRef R = {}, G = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.src[p] = q->src[p];
-    g.stride[p] = q->src_pitch[p];
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-    R.plane[p] = q->prev[p];
-    G.plane[p] = q->gold[p];
-    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
-    R.w[p] = G.w[p] = geo.nh[p] * 8;
-    R.h[p] = G.h[p] = geo.nv[p] * 8;
-  }
-  R.hdec = G.hdec = hdec;
-  R.vdec = G.vdec = vdec;
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  const EncRef R = enc_ref(geo, q->prev, q->ref_pitch), G = enc_ref(geo, q->gold, q->ref_pitch);
   hipStream_t stream = nullptr;
   if (search) ENC_TRY(rate_launch_me((uint4 *)q->stats, g, R, nmbx, nmbs, stream));
   if (decide) {
@@ -2506,9 +2457,9 @@ int thip_enc_inter_stage(const thip_enc_inter_req *q) {
     // the outputs the caller gave are used in place of their part
     const size_t o_dclast = code && !q->levels ? (size_t)n * 128 : 0, o_ovf = o_dclast + nchunks * classes * 4, o_order = o_ovf + 16, o_dq = o_order + (size_t)n * 4,
                  o_dcq = o_dq + 768, o_dcr = o_dcq + (((size_t)n * 2 + 15) & ~(size_t)15), o_cmap = o_dcr + (((size_t)n * 2 + 15) & ~(size_t)15);
-    uint8_t *d = nullptr;
-    ENC_TRY(hipMalloc((void **)&d, o_cmap + (size_t)n));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    DeviceBuf buf;
+    ENC_TRY(buf.alloc(o_cmap + (size_t)n));
+    uint8_t *const d = buf.p;
     uint32_t *d_dclast = (uint32_t *)(d + o_dclast);
     int16_t *dcq = q->dcq ? q->dcq : (int16_t *)(d + o_dcq), *dcr = q->dcr ? q->dcr : (int16_t *)(d + o_dcr);
     uint8_t *cmap = q->cmap ? q->cmap : d + o_cmap;
@@ -2550,58 +2501,25 @@ int thip_enc_rd_stage(const thip_enc_rd_req *q) {
   const int st = q->stages;
   if (st <= 0 || st > 3) return THIP_EINVAL;
   const bool cand = st & THIP_ENC_RD_CAND, decide = st & THIP_ENC_RD_DECIDE;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
-  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-    return THIP_EINVAL;
-  for (int p = 0; p < 3; p++)
-    if (!q->src[p] || !q->prev[p] || !q->gold[p]) return THIP_EFAULT;
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
-    if (q->src_pitch[p] < pw || q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF) return THIP_EINVAL;
-  }
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
+  const PicRect pic = pic_rect(*q);
+  const EntryPlanes pl{q->src, q->src_pitch, q->prev, q->gold, q->ref_pitch};
+  if (const int rc = check_picture_planes(f, pic, pl, true, Gold::required)) return rc;
   if (q->lambda_search < 0 || q->lambda_search > (1 << 24) || q->lambda_rd < 0 || q->lambda_rd > (1 << 24)) return THIP_EINVAL;
   if (!q->cand || (decide && (!q->words || !q->dequant || !q->bits))) return THIP_EFAULT;
-  if (decide)
-    for (int k = 0; k < 384; k++)
-      if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (decide && !table_within(q->dequant, 384, 1, 32767)) return THIP_EINVAL;
   if (misaligned(q->cand, 16) || misaligned(q->words, 16) || misaligned(q->costs, 8)) return THIP_EINVAL;
   // ---- nothing above touched a device ----
   FrameGeometry geo;
   build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
   const int nmbx = geo.nh[0] >> 1, nmbs = nmbx * (geo.nv[0] >> 1);
-  EncPlanes g = {};
-  EncRef R = {}, G = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.src[p] = q->src[p];
-    g.stride[p] = q->src_pitch[p];
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-    R.plane[p] = q->prev[p];
-    G.plane[p] = q->gold[p];
-    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
-    R.w[p] = G.w[p] = geo.nh[p] * 8;
-    R.h[p] = G.h[p] = geo.nv[p] * 8;
-  }
-  R.hdec = G.hdec = hdec;
-  R.vdec = G.vdec = vdec;
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  const EncRef R = enc_ref(geo, q->prev, q->ref_pitch), G = enc_ref(geo, q->gold, q->ref_pitch);
   // one allocation: dequant [384] | bits [2][5][32]
-  uint8_t *d = nullptr;
-  ENC_TRY(hipMalloc((void **)&d, 768 + 320));
-  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc(768 + 320));
+  uint8_t *const d = buf.p;
   if (decide) {
     ENC_TRY(hipMemcpy(d, q->dequant, 768, hipMemcpyHostToDevice));
     ENC_TRY(hipMemcpy(d + 768, q->bits, 320, hipMemcpyHostToDevice));
@@ -2618,36 +2536,17 @@ int thip_enc_rd_stage(const thip_enc_rd_req *q) {
 // makes it, on the current device's null stream
 int thip_enc_skip_stage(const thip_enc_skip_req *q) {
   if (!q) return THIP_EFAULT;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
   if (q->classes != 2 && q->classes != 3) return THIP_EINVAL;
   const bool all = q->classes == 3;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
-  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-    return THIP_EINVAL;
-  int ngold = 0;
-  for (int p = 0; p < 3; p++) {
-    if (!q->src[p] || !q->prev[p]) return THIP_EFAULT;
-    ngold += q->gold[p] != nullptr;
-  }
-  if (ngold != (all ? 3 : 0)) return all && ngold < 3 ? THIP_EFAULT : THIP_EINVAL;
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
-    if (q->src_pitch[p] < pw || q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF) return THIP_EINVAL;
-  }
+  const PicRect pic = pic_rect(*q);
+  const EntryPlanes pl{q->src, q->src_pitch, q->prev, q->gold, q->ref_pitch};
+  if (const int rc = check_picture_planes(f, pic, pl, true, all ? Gold::required : Gold::forbidden)) return rc;
   if (q->nqis < 1 || q->nqis > 3 || q->lambda < -1 || q->lambda > ((int64_t)1 << 40)) return THIP_EINVAL;
   if (!q->words || !q->dequant || !q->bits) return THIP_EFAULT;
   if (!q->levels || !q->dcq || !q->qii || !q->cmap || !q->skf || !q->dcode || !q->rate || !q->dskip) return THIP_EFAULT;
-  for (int k = 0; k < q->nqis * 384; k++)
-    if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
-  for (int k = 0; k < 256; k++)
-    if (q->bits[k] > 64) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!table_within(q->dequant, (size_t)q->nqis * 384, 1, 32767) || !table_within(q->bits, 256, 0, 64)) return THIP_EINVAL;
   if (misaligned(q->words, all ? 16 : 4) || misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->iscale, 2) ||
       misaligned(q->dcode, 8) || misaligned(q->rate, 8) || misaligned(q->dskip, 8))
     return THIP_EINVAL;
@@ -2657,32 +2556,13 @@ int thip_enc_skip_stage(const thip_enc_skip_req *q) {
   const int64_t n = geo.nfrags;
   const int classes = q->classes, nmbx = geo.nh[0] >> 1;
   const size_t nchunks = (size_t)((n + kEncChunk - 1) / kEncChunk);
-  EncPlanes g = {};
-  EncRef R = {}, G = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.src[p] = q->src[p];
-    g.stride[p] = q->src_pitch[p];
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-    R.plane[p] = q->prev[p];
-    G.plane[p] = all ? q->gold[p] : q->prev[p];
-    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
-    R.w[p] = G.w[p] = geo.nh[p] * 8;
-    R.h[p] = G.h[p] = geo.nv[p] * 8;
-  }
-  R.hdec = G.hdec = hdec;
-  R.vdec = G.vdec = vdec;
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  const EncRef R = enc_ref(geo, q->prev, q->ref_pitch), G = enc_ref(geo, all ? q->gold : q->prev, q->ref_pitch);   // (no GOLD: PREV in its place)
   // one allocation: dclast [chunks][classes] | overflow | order [n] | dequant [nqis][384] | bits [256]
   const size_t o_ovf = nchunks * classes * 4, o_order = o_ovf + 16, o_dq = o_order + (size_t)n * 4, o_bits = o_dq + (size_t)q->nqis * 768;
-  uint8_t *d = nullptr;
-  ENC_TRY(hipMalloc((void **)&d, o_bits + 256));
-  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc(o_bits + 256));
+  uint8_t *const d = buf.p;
   hipStream_t stream = nullptr;
   ENC_TRY(hipMemcpy(d + o_order, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(d + o_dq, q->dequant, (size_t)q->nqis * 768, hipMemcpyHostToDevice));
@@ -2706,36 +2586,17 @@ int thip_enc_skip_stage(const thip_enc_skip_req *q) {
 // enc_rdq_queue makes it, on the current device's null stream
 int thip_enc_rdq_stage(const thip_enc_rdq_req *q) {
   if (!q) return THIP_EFAULT;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
   if (q->classes != 0 && q->classes != 2 && q->classes != 3) return THIP_EINVAL;
   const bool all = q->classes == 3, key = q->classes == 0;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
-  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-    return THIP_EINVAL;
-  int ngold = 0;
-  for (int p = 0; p < 3; p++) {
-    if (!q->src[p] || (!key && !q->prev[p])) return THIP_EFAULT;
-    ngold += q->gold[p] != nullptr;
-  }
-  if (!key && ngold != (all ? 3 : 0)) return all && ngold < 3 ? THIP_EFAULT : THIP_EINVAL;
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
-    if (q->src_pitch[p] < pw) return THIP_EINVAL;
-    if (!key && (q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF)) return THIP_EINVAL;
-  }
+  const PicRect pic = pic_rect(*q);
+  const EntryPlanes pl{q->src, q->src_pitch, q->prev, q->gold, q->ref_pitch};
+  // (a key frame reads no reference: whatever prev, gold and ref_pitch hold is let be)
+  if (const int rc = check_picture_planes(f, pic, pl, !key, key ? Gold::ignored : all ? Gold::required : Gold::forbidden)) return rc;
   if (q->nqis < 1 || q->nqis > 3 || q->lambda < -1 || q->lambda > ((int64_t)1 << 40) || q->weight < 0 || q->weight > 64) return THIP_EINVAL;
   if (!q->dequant || !q->bits || !q->levels || (!key && (!q->words || !q->cmap))) return THIP_EFAULT;
-  for (int k = 0; k < q->nqis * 384; k++)
-    if (q->dequant[k] < 1 || q->dequant[k] > 32767) return THIP_EINVAL;
-  for (int k = 0; k < 256; k++)
-    if (q->bits[k] > 64) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!table_within(q->dequant, (size_t)q->nqis * 384, 1, 32767) || !table_within(q->bits, 256, 0, 64)) return THIP_EINVAL;
   if ((!key && misaligned(q->words, all ? 16 : 4)) || misaligned(q->levels, 16) || misaligned(q->iscale, 2) || misaligned(q->jbefore, 8) ||
       misaligned(q->jafter, 8) || misaligned(q->rate, 8))
     return THIP_EINVAL;
@@ -2744,33 +2605,14 @@ int thip_enc_rdq_stage(const thip_enc_rdq_req *q) {
   build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
   const int64_t n = geo.nfrags;
   const int nmbx = geo.nh[0] >> 1;
-  EncPlanes g = {};
-  EncRef R = {}, G = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.src[p] = q->src[p];
-    g.stride[p] = q->src_pitch[p];
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-    if (key) continue;
-    R.plane[p] = q->prev[p];
-    G.plane[p] = all ? q->gold[p] : q->prev[p];
-    R.stride[p] = G.stride[p] = (int)q->ref_pitch[p];
-    R.w[p] = G.w[p] = geo.nh[p] * 8;
-    R.h[p] = G.h[p] = geo.nv[p] * 8;
-  }
-  R.hdec = G.hdec = hdec;
-  R.vdec = G.vdec = vdec;
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  // (a key frame: no planes; no GOLD: PREV in its place)
+  const EncRef R = enc_ref(geo, key ? nullptr : q->prev, q->ref_pitch), G = enc_ref(geo, key ? nullptr : all ? q->gold : q->prev, q->ref_pitch);
   // one allocation: order [n] | dequant [nqis][384] | bits [256]
   const size_t o_dq = (size_t)n * 4, o_bits = o_dq + (size_t)q->nqis * 768;
-  uint8_t *d = nullptr;
-  ENC_TRY(hipMalloc((void **)&d, o_bits + 256));
-  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc(o_bits + 256));
+  uint8_t *const d = buf.p;
   hipStream_t stream = nullptr;
   ENC_TRY(hipMemcpy(d, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   ENC_TRY(hipMemcpy(d + o_dq, q->dequant, (size_t)q->nqis * 768, hipMemcpyHostToDevice));
@@ -2798,38 +2640,22 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   if (st <= 0 || st > 15 || (q->inter != 0 && q->inter != 1)) return THIP_EINVAL;
   const bool coef = st & THIP_ENC_RATE_COEF, dc = st & THIP_ENC_RATE_DC, tok = st & THIP_ENC_RATE_TOK, bits = st & THIP_ENC_RATE_BITS;
   const bool inter = q->inter == 1;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
-  if (n64 > kRateMaxFrags) return THIP_EINVAL;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt, kRateMaxFrags)) return THIP_EINVAL;
   if (q->groups < 0 || q->groups > rate_groups(kRateMaxFrags)) return THIP_EINVAL;
-  const int groups = q->groups ? q->groups : rate_groups(n64);
-  if (rate_blocks_per_group(n64, groups) >= kRateBlocksPerGroupLimit) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
-  if (coef) {
-    if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-        q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-      return THIP_EINVAL;
-    for (int p = 0; p < 3; p++)
-      if (!q->src[p] || (inter && !q->prev[p])) return THIP_EFAULT;
-    for (int p = 0; p < 3; p++) {
-      const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
-      if (q->src_pitch[p] < pw) return THIP_EINVAL;
-      if (inter && (q->ref_pitch[p] < (q->frame_width >> hd) || q->ref_pitch[p] > 0x7FFFFFFF)) return THIP_EINVAL;
-    }
+  const int groups = q->groups ? q->groups : rate_groups(f.nfrags);
+  if (rate_blocks_per_group(f.nfrags, groups) >= kRateBlocksPerGroupLimit) return THIP_EINVAL;
+  const PicRect pic = pic_rect(*q);
+  if (coef) {   // (the one stage that reads pixels: the source's, and PREV's in an inter frame)
+    const EntryPlanes pl{q->src, q->src_pitch, q->prev, nullptr, q->ref_pitch};
+    if (const int rc = check_picture_planes(f, pic, pl, inter, Gold::ignored)) return rc;
   }
   if ((coef || dc || tok) && (!q->coef || (inter && !q->stats))) return THIP_EFAULT;
   if (dc || tok) {
     if (!q->steps || !q->qdc || (inter && (!q->lambda || !q->coded || !q->cls))) return THIP_EFAULT;
     if (q->any_order != 0 && q->any_order != 1) return THIP_EINVAL;
     if (!rate_steps_ok(q->steps, q->any_order == 1)) return THIP_EINVAL;
-    if (inter)
-      for (int k = 0; k < 64; k++)
-        if (q->lambda[k] < 0 || q->lambda[k] > (1 << 24)) return THIP_EINVAL;
+    if (inter && !table_within(q->lambda, 64, 0, 1 << 24)) return THIP_EINVAL;
   }
   if ((tok || bits) && !q->partial) return THIP_EFAULT;
   if (bits && (!q->lens || !q->est)) return THIP_EFAULT;
@@ -2842,31 +2668,13 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
   const int64_t n = geo.nfrags;
   const int nmbx = geo.nh[0] >> 1;
-  EncPlanes g = {};
-  EncRef R = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.src[p] = q->src[p];
-    g.stride[p] = q->src_pitch[p];
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-    R.plane[p] = q->prev[p];
-    R.stride[p] = (int)q->ref_pitch[p];
-    R.w[p] = geo.nh[p] * 8;
-    R.h[p] = geo.nv[p] * 8;
-  }
-  R.hdec = hdec;
-  R.vdec = vdec;
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  const EncRef R = enc_ref(geo, q->prev, q->ref_pitch);
   // one allocation: tab [6][64][64] uint2 | lambda [64] | lens [80][32] | floor [6][64] uint16
   constexpr size_t o_lam = 6 * 64 * 64 * sizeof(uint2), o_lens = o_lam + 64 * sizeof(int), o_floor = o_lens + 80 * 32;
-  uint8_t *d = nullptr;
-  ENC_TRY(hipMalloc((void **)&d, o_floor + 6 * 64 * sizeof(uint16_t)));
-  struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc(o_floor + 6 * 64 * sizeof(uint16_t)));
+  uint8_t *const d = buf.p;
   if (dc || tok) {
     std::vector<uint2> tab(6 * 64 * 64);
     std::vector<uint16_t> floor(6 * 64);
@@ -2884,8 +2692,8 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
   a.lam = (const int *)(d + o_lam);
   a.floor = (const uint16_t *)(d + o_floor);
   a.nmbx = nmbx;
-  a.hdec = hdec;
-  a.vdec = vdec;
+  a.hdec = geo.hdec;
+  a.vdec = geo.vdec;
   hipStream_t stream = nullptr;
   if (coef) {
     if (inter) ENC_TRY(rate_launch_coef(q->coef, g, R, a.mbs, nmbx, n, stream));
@@ -2902,46 +2710,24 @@ int thip_enc_rate_stage(const thip_enc_rate_req *q) {
 // current device's null stream
 int thip_enc_mask_stage(const thip_enc_mask_req *q) {
   if (!q) return THIP_EFAULT;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
-  if (n64 > ((int64_t)1 << 24)) return THIP_EINVAL;
-  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-    return THIP_EINVAL;
-  for (int p = 0; p < 3; p++)
-    if (!q->src[p]) return THIP_EFAULT;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
+  const PicRect pic = pic_rect(*q);
+  const EntryPlanes pl{q->src, q->src_pitch, nullptr, nullptr, nullptr};
+  // (check_picture_planes' three steps, with every NULL pointer refused before any pitch: this entry's order)
+  if (pic_outside(pic, f.width, f.height)) return THIP_EINVAL;
+  if (const int rc = check_plane_pointers(pl, false, Gold::ignored)) return rc;
   if (!q->act || !q->avg || !q->iscale) return THIP_EFAULT;
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, pw = ((q->pic_x + q->pic_width + hd) >> hd) - (q->pic_x >> hd);
-    if (q->src_pitch[p] < pw) return THIP_EINVAL;
-  }
+  if (pitches_outside(f, pic, pl, false)) return THIP_EINVAL;
   if (q->ratio < 2 || q->ratio > 16) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
   if (misaligned(q->act, 4) || misaligned(q->avg, 8) || misaligned(q->iscale, 2)) return THIP_EINVAL;
   // ---- nothing above touched a device ----
   FrameGeometry geo;
   build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
-  EncPlanes g = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.src[p] = q->src[p];
-    g.stride[p] = q->src_pitch[p];
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-  }
-  MaskPart *d_part = nullptr;
-  ENC_TRY(hipMalloc((void **)&d_part, (size_t)mask_parts(nluma) * sizeof(MaskPart)));
-  struct Free { MaskPart *p; ~Free() { (void)hipFree(p); } } guard{d_part};
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc((size_t)mask_parts(f.nluma) * sizeof(MaskPart)));
+  MaskPart *const d_part = (MaskPart *)buf.p;
   hipStream_t stream = nullptr;
   ENC_TRY(mask_launch_act(q->act, d_part, g, stream));
   ENC_TRY(mask_launch_scale(q->iscale, (MaskRec *)q->avg, q->act, d_part, g, geo.nfrags, q->ratio, stream));
@@ -2953,39 +2739,21 @@ int thip_enc_mask_stage(const thip_enc_mask_req *q) {
 // the current device's null stream
 int thip_enc_roi_stage(const thip_enc_roi_req *q) {
   if (!q) return THIP_EFAULT;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  const int64_t n64 = nluma + 2 * (nluma >> (hdec + vdec));
-  if (n64 > ((int64_t)1 << 24)) return THIP_EINVAL;
-  if (q->pic_width <= 0 || q->pic_height <= 0 || q->pic_x < 0 || q->pic_y < 0 || q->pic_width > q->frame_width ||
-      q->pic_height > q->frame_height || q->pic_x > q->frame_width - q->pic_width || q->pic_y > q->frame_height - q->pic_height)
-    return THIP_EINVAL;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
+  const PicRect pic = pic_rect(*q);
+  if (pic_outside(pic, f.width, f.height)) return THIP_EINVAL;   // (a picture, and no planes: the kernel reads the map alone)
   if (!q->map || !q->iscale || !q->stats) return THIP_EFAULT;
   if (q->map_width < 1 || q->map_width > 16384 || q->map_height < 1 || q->map_height > 16384) return THIP_EINVAL;
   if ((q->map_pitch < 0 ? -q->map_pitch : q->map_pitch) < q->map_width) return THIP_EINVAL;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
   if (misaligned(q->mask_iscale, 2) || misaligned(q->iscale, 2) || misaligned(q->stats, 8)) return THIP_EINVAL;
   // ---- nothing above touched a device ----
   FrameGeometry geo;
   build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
-  EncPlanes g = {};
-  for (int p = 0; p < 3; p++) {
-    const int hd = p ? hdec : 0, vd = p ? vdec : 0;
-    g.px0[p] = q->pic_x >> hd;
-    g.py0[p] = q->pic_y >> vd;
-    g.pw[p] = ((q->pic_x + q->pic_width + hd) >> hd) - g.px0[p];
-    g.ph[p] = ((q->pic_y + q->pic_height + vd) >> vd) - g.py0[p];
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-  }
-  RoiPart *d_part = nullptr;
-  ENC_TRY(hipMalloc((void **)&d_part, (size_t)roi_parts(geo.nfrags) * sizeof(RoiPart)));
-  struct Free { RoiPart *p; ~Free() { (void)hipFree(p); } } guard{d_part};
+  const EncPlanes g = enc_planes(geo, pic, nullptr, nullptr);
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc((size_t)roi_parts(geo.nfrags) * sizeof(RoiPart)));
+  RoiPart *const d_part = (RoiPart *)buf.p;
   hipStream_t stream = nullptr;
   ENC_TRY(roi_launch_scale(q->iscale, q->mask_iscale, d_part, (RoiRec *)q->stats, q->map, q->map_width, q->map_height, q->map_pitch, nullptr,
                            g, geo.nfrags, stream));
@@ -3000,21 +2768,15 @@ int thip_enc_tok_stage(const thip_enc_tok_req *q) {
   const int st = q->stages;
   if (st <= 0 || st > 7) return THIP_EINVAL;
   const bool tok = st & THIP_ENC_TOK_TOK, scan = st & THIP_ENC_TOK_SCAN, scatter = st & THIP_ENC_TOK_SCATTER;
-  if (q->frame_width <= 0 || q->frame_height <= 0 || (q->frame_width & 15) || (q->frame_height & 15) || q->frame_width >= (1 << 20) ||
-      q->frame_height >= (1 << 20))
-    return THIP_EINVAL;
-  if (q->pixel_fmt < 0 || q->pixel_fmt >= TH_PF_NFORMATS || q->pixel_fmt == TH_PF_RSVD) return THIP_EINVAL;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
   if (q->classes != 0 && q->classes != 2 && q->classes != 3) return THIP_EINVAL;
   const bool inter = q->classes != 0;
-  const int hdec = !(q->pixel_fmt & 1), vdec = !(q->pixel_fmt & 2);
-  const int64_t nluma = (int64_t)(q->frame_width >> 3) * (q->frame_height >> 3);
-  if (nluma + 2 * (nluma >> (hdec + vdec)) > ((int64_t)1 << 24)) return THIP_EINVAL;
   if (tok && (!q->levels || (inter ? !q->dcr || !q->cmap : !q->dcq) || !q->overflow)) return THIP_EFAULT;
   if ((tok || scatter) && (!q->tok || !q->mask)) return THIP_EFAULT;
   if ((tok || scan) && !q->chunk_cnt) return THIP_EFAULT;
   if ((scan || scatter) && (!q->chunk_base || !q->list_len)) return THIP_EFAULT;
   if (scatter && !q->out) return THIP_EFAULT;
-  const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
   if (misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->dcr, 2) || misaligned(q->mask, 8) || misaligned(q->tok, 4) ||
       misaligned(q->chunk_cnt, 4) || misaligned(q->chunk_base, 4) || misaligned(q->list_len, 4) || misaligned(q->overflow, 4) ||
       misaligned(q->out, 4))
@@ -3024,17 +2786,12 @@ int thip_enc_tok_stage(const thip_enc_tok_req *q) {
   build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
   const int64_t n = geo.nfrags;
   const size_t nchunks = enc_chunks(n);
-  EncPlanes g = {};   // (the token kernels read the fragment geometry alone)
-  for (int p = 0; p < 3; p++) {
-    g.nh[p] = geo.nh[p];
-    g.nv[p] = geo.nv[p];
-    g.froff[p] = geo.fro[p];
-  }
+  const EncPlanes g = enc_planes(geo, PicRect{}, nullptr, nullptr);   // (the token kernels read the fragment geometry alone: no picture)
   hipStream_t stream = nullptr;
-  int32_t *d_order = nullptr;
-  struct Free { int32_t *&p; ~Free() { (void)hipFree(p); } } guard{d_order};
+  DeviceBuf buf;   // (order [n], for TOK alone)
   if (tok) {
-    ENC_TRY(hipMalloc((void **)&d_order, (size_t)n * 4));
+    ENC_TRY(buf.alloc((size_t)n * 4));
+    int32_t *const d_order = (int32_t *)buf.p;
     ENC_TRY(hipMemcpy(d_order, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     ENC_TRY(hipMemsetAsync(q->overflow, 0, 4, stream));   // (th_encode_*: the quantising kernel zeroes it)
     const TokBufs o{q->tok, q->mask, q->chunk_cnt, q->overflow};

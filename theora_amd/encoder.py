@@ -898,6 +898,43 @@ def pack_tokens(words_ptr, list_len, codes, lens, groups, phase, packet_ptr, cap
     return rc, dict(bits=res.bits, bytes=res.bytes, tokens=res.tokens, merged=res.merged, merged_ac=res.merged_ac, huff=list(res.huff))
 
 
+def _stage_req(cls, frame, pixel_fmt, pic=False, planes=None, pitches=None):
+    """A direct entry's request with its common part filled: frame (width, height), the pixel format, the picture where the request
+    has one (pic: (x, y, width, height), None for the whole frame, False for a request without), and the groups of three it has, by
+    field name: planes (device addresses, None where there is none) and pitches (None is 0)."""
+    q = cls()
+    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    if pic is not False:
+        q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    for group, null, conv in ((planes or {}, None, lambda v: v), (pitches or {}, 0, int)):
+        for name, v in group.items():
+            for p in range(3):
+                getattr(q, name)[p] = null if v is None else conv(v[p])
+    return q
+
+
+def _host_tables(q, who, tables):
+    """Sets the request's host tables: (field, value, dtype, entries) each, the value anything numpy converts; None stays NULL, and
+    entries None takes any size.  who: what a ValueError for a wrong size begins with.  Returns the arrays, to be kept alive over
+    the call."""
+    keep = []
+    for name, v, t, size in tables:
+        if v is None:
+            continue
+        a = np.ascontiguousarray(v, t).reshape(-1)
+        if size is not None and a.size != size:
+            raise ValueError("%s %s of %d entries where %d are expected" % (who, name, a.size, size))
+        keep.append(a)
+        setattr(q, name, a.ctypes.data)
+    return keep
+
+
+def _qi_tables(nqis, dequant, bits):
+    """skip_stage's and rdq_stage's tables: dequant [nqis][2][3][64] -- of any size with an nqis the entry refuses: the refusal is its
+    to make -- and bits [2][4][32]."""
+    return [("dequant", dequant, np.uint16, 384 * int(nqis) if 1 <= int(nqis) <= 3 else None), ("bits", bits, np.uint8, 256)]
+
+
 def tok_stage(frame, pixel_fmt, classes, stages, levels=None, dcq=None, dcr=None, cmap=None, tok=None, mask=None, chunk_cnt=None,
               chunk_base=None, list_len=None, overflow=None, out=None, out_cap=0):
     """thip_enc_tok_stage (include/theora_hip.h): the tokeniser on the caller's levels, DCs and map, a test and diagnostic entry.
@@ -905,8 +942,7 @@ def tok_stage(frame, pixel_fmt, classes, stages, levels=None, dcq=None, dcr=None
     device addresses (a tensor's data_ptr(); None is NULL).  Returns the entry's return code; nothing is raised, the refusals are the
     caller's to look at."""
     L = _lib.load()
-    q = _lib.EncTokReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
+    q = _stage_req(_lib.EncTokReq, frame, pixel_fmt)
     q.classes, q.stages, q.out_cap = int(classes), int(stages), int(out_cap)
     q.levels, q.dcq, q.dcr, q.cmap, q.tok, q.mask = levels, dcq, dcr, cmap, tok, mask
     q.chunk_cnt, q.chunk_base, q.list_len, q.overflow, q.out = chunk_cnt, chunk_base, list_len, overflow, out
@@ -921,22 +957,9 @@ def inter_stage(frame, pixel_fmt, stages, classes, pic=None, lam=0, src=None, sr
     pitches; dequant [2][3][64]: anything numpy converts; the rest: device addresses, None is NULL.  Returns the entry's return
     code; nothing is raised, the refusals are the caller's to look at."""
     L = _lib.load()
-    q = _lib.EncInterReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q = _stage_req(_lib.EncInterReq, frame, pixel_fmt, pic, dict(src=src, prev=prev, gold=gold), dict(src_pitch=src_pitch, ref_pitch=ref_pitch))
     q.stages, q.lam, q.classes = int(stages), int(lam), int(classes)
-    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
-        for p in range(3):
-            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
-    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
-        for p in range(3):
-            getattr(q, name)[p] = 0 if v is None else int(v[p])
-    keep = None
-    if dequant is not None:
-        keep = np.ascontiguousarray(dequant, np.uint16).reshape(-1)
-        if keep.size != 384:
-            raise ValueError("inter_stage: a dequant of %d entries where 384 are expected" % keep.size)
-        q.dequant = keep.ctypes.data
+    keep = _host_tables(q, "inter_stage: a", [("dequant", dequant, np.uint16, 384)])
     q.stats, q.words, q.words_from_stats, q.levels, q.dcq, q.cmap, q.dcr = stats, words, words_from_stats, levels, dcq, cmap, dcr
     return L.thip_enc_inter_stage(C.byref(q))
 
@@ -951,25 +974,9 @@ def rate_stage(frame, pixel_fmt, inter, stages, pic=None, groups=0, fixed=0, src
     with q in any way (thip_enc_rate_req.any_order).  Returns the entry's return code; nothing is raised, the refusals are the
     caller's to look at."""
     L = _lib.load()
-    q = _lib.EncRateReq()
-    q.any_order = int(any_order)
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
-    q.inter, q.stages, q.groups, q.fixed = int(inter), int(stages), int(groups), int(fixed)
-    for name, ptrs in (("src", src), ("prev", prev)):
-        for p in range(3):
-            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
-    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
-        for p in range(3):
-            getattr(q, name)[p] = 0 if v is None else int(v[p])
-    keep = []
-    for name, v, t, size in (("steps", steps, np.uint16, 6 * 64 * 64), ("lam", lam, np.int32, 64), ("lens", lens, np.uint8, 80 * 32)):
-        if v is not None:
-            a = np.ascontiguousarray(v, t).reshape(-1)
-            if a.size != size:
-                raise ValueError("rate_stage: %s of %d entries where %d are expected" % (name, a.size, size))
-            keep.append(a)
-            setattr(q, name, a.ctypes.data)
+    q = _stage_req(_lib.EncRateReq, frame, pixel_fmt, pic, dict(src=src, prev=prev), dict(src_pitch=src_pitch, ref_pitch=ref_pitch))
+    q.inter, q.stages, q.groups, q.fixed, q.any_order = int(inter), int(stages), int(groups), int(fixed), int(any_order)
+    keep = _host_tables(q, "rate_stage:", [("steps", steps, np.uint16, 6 * 64 * 64), ("lam", lam, np.int32, 64), ("lens", lens, np.uint8, 80 * 32)])
     q.stats, q.coef, q.qdc, q.coded, q.cls, q.partial, q.est = stats, coef, qdc, coded, cls, partial, est
     return L.thip_enc_rate_stage(C.byref(q))
 
@@ -981,13 +988,8 @@ def mask_stage(frame, pixel_fmt, ratio, pic=None, src=None, src_pitch=None, act=
     [nfrags]): device addresses, None is NULL.  Returns the entry's return code; nothing is raised, the refusals are the caller's to
     look at."""
     L = _lib.load()
-    q = _lib.EncMaskReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q = _stage_req(_lib.EncMaskReq, frame, pixel_fmt, pic, dict(src=src), dict(src_pitch=src_pitch))
     q.ratio = int(ratio)
-    for p in range(3):
-        q.src[p] = None if src is None else src[p]
-        q.src_pitch[p] = 0 if src_pitch is None else int(src_pitch[p])
     q.act, q.avg, q.iscale = act, avg, iscale
     return L.thip_enc_mask_stage(C.byref(q))
 
@@ -998,9 +1000,7 @@ def roi_stage(frame, pixel_fmt, map_size, map_pitch, map, pic=None, mask_iscale=
     map_pitch), mask_iscale (uint16 [nfrags], masking's scales), iscale (uint16 [nfrags]) and stats (int32 [8]): device addresses,
     None is NULL.  Returns the entry's return code; nothing is raised, the refusals are the caller's to look at."""
     L = _lib.load()
-    q = _lib.EncRoiReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q = _stage_req(_lib.EncRoiReq, frame, pixel_fmt, pic)
     q.map_width, q.map_height, q.map_pitch = int(map_size[0]), int(map_size[1]), int(map_pitch)
     q.map, q.mask_iscale, q.iscale, q.stats = map, mask_iscale, iscale, stats
     return L.thip_enc_roi_stage(C.byref(q))
@@ -1014,24 +1014,9 @@ def rd_stage(frame, pixel_fmt, stages, pic=None, lambda_search=0, lambda_rd=0, s
     and bits [2][5][32]: anything numpy converts (None is NULL); cand, costs, words: device addresses, None is NULL.  Returns the
     entry's return code; nothing is raised, the refusals are the caller's to look at."""
     L = _lib.load()
-    q = _lib.EncRdReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q = _stage_req(_lib.EncRdReq, frame, pixel_fmt, pic, dict(src=src, prev=prev, gold=gold), dict(src_pitch=src_pitch, ref_pitch=ref_pitch))
     q.stages, q.lambda_search, q.lambda_rd = int(stages), int(lambda_search), int(lambda_rd)
-    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
-        for p in range(3):
-            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
-    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
-        for p in range(3):
-            getattr(q, name)[p] = 0 if v is None else int(v[p])
-    keep = []
-    for name, v, t, size in (("dequant", dequant, np.uint16, 384), ("bits", bits, np.uint8, 320)):
-        if v is not None:
-            a = np.ascontiguousarray(v, t).reshape(-1)
-            if a.size != size:
-                raise ValueError("rd_stage: %s of %d entries where %d are expected" % (name, a.size, size))
-            keep.append(a)
-            setattr(q, name, a.ctypes.data)
+    keep = _host_tables(q, "rd_stage:", [("dequant", dequant, np.uint16, 384), ("bits", bits, np.uint8, 320)])
     q.cand, q.costs, q.words = cand, costs, words
     return L.thip_enc_rd_stage(C.byref(q))
 
@@ -1046,24 +1031,9 @@ def skip_stage(frame, pixel_fmt, classes, nqis, pic=None, lam=-1, src=None, src_
     NULL); the rest: device addresses, None is NULL.  Returns the entry's return code; nothing is raised, the refusals are the
     caller's to look at."""
     L = _lib.load()
-    q = _lib.EncSkipReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q = _stage_req(_lib.EncSkipReq, frame, pixel_fmt, pic, dict(src=src, prev=prev, gold=gold), dict(src_pitch=src_pitch, ref_pitch=ref_pitch))
     q.classes, q.nqis, q.lam = int(classes), int(nqis), int(lam)
-    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
-        for p in range(3):
-            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
-    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
-        for p in range(3):
-            getattr(q, name)[p] = 0 if v is None else int(v[p])
-    keep = []
-    for name, v, t, size in (("dequant", dequant, np.uint16, 384 * int(nqis)), ("bits", bits, np.uint8, 256)):
-        if v is not None:
-            a = np.ascontiguousarray(v, t).reshape(-1)
-            if a.size != size and not (name == "dequant" and not 1 <= int(nqis) <= 3):   # (an nqis the entry refuses: its refusal)
-                raise ValueError("skip_stage: %s of %d entries where %d are expected" % (name, a.size, size))
-            keep.append(a)
-            setattr(q, name, a.ctypes.data)
+    keep = _host_tables(q, "skip_stage:", _qi_tables(nqis, dequant, bits))
     q.words, q.iscale, q.levels, q.dcq, q.qii, q.cmap, q.skf = words, iscale, levels, dcq, qii, cmap, skf
     q.dcode, q.rate, q.dskip = dcode, rate, dskip
     return L.thip_enc_skip_stage(C.byref(q))
@@ -1076,24 +1046,9 @@ def rdq_stage(frame, pixel_fmt, classes, nqis, weight, pic=None, lam=-1, src=Non
     diagnostic entry.  classes: 0 (a key frame: prev, gold, words, cmap unused), 2 or 3; weight: w; levels: device address, in and
     out; the rest as skip_stage takes them.  Returns the entry's return code; nothing is raised."""
     L = _lib.load()
-    q = _lib.EncRdqReq()
-    q.frame_width, q.frame_height, q.pixel_fmt = int(frame[0]), int(frame[1]), int(pixel_fmt)
-    q.pic_x, q.pic_y, q.pic_width, q.pic_height = (0, 0, q.frame_width, q.frame_height) if pic is None else [int(v) for v in pic]
+    q = _stage_req(_lib.EncRdqReq, frame, pixel_fmt, pic, dict(src=src, prev=prev, gold=gold), dict(src_pitch=src_pitch, ref_pitch=ref_pitch))
     q.classes, q.nqis, q.weight, q.lam = int(classes), int(nqis), int(weight), int(lam)
-    for name, ptrs in (("src", src), ("prev", prev), ("gold", gold)):
-        for p in range(3):
-            getattr(q, name)[p] = None if ptrs is None else ptrs[p]
-    for name, v in (("src_pitch", src_pitch), ("ref_pitch", ref_pitch)):
-        for p in range(3):
-            getattr(q, name)[p] = 0 if v is None else int(v[p])
-    keep = []
-    for name, v, t, size in (("dequant", dequant, np.uint16, 384 * int(nqis)), ("bits", bits, np.uint8, 256)):
-        if v is not None:
-            a = np.ascontiguousarray(v, t).reshape(-1)
-            if a.size != size and not (name == "dequant" and not 1 <= int(nqis) <= 3):   # (an nqis the entry refuses: its refusal)
-                raise ValueError("rdq_stage: %s of %d entries where %d are expected" % (name, a.size, size))
-            keep.append(a)
-            setattr(q, name, a.ctypes.data)
+    keep = _host_tables(q, "rdq_stage:", _qi_tables(nqis, dequant, bits))
     q.words, q.iscale, q.levels, q.qii, q.cmap = words, iscale, levels, qii, cmap
     q.jbefore, q.jafter, q.rate = jbefore, jafter, rate
     return L.thip_enc_rdq_stage(C.byref(q))
