@@ -1078,6 +1078,52 @@ typedef struct thip_enc_skip_req {   /* 264 bytes */
 int thip_enc_skip_stage(const thip_enc_skip_req *req);
 
 /* ------------------------------------------------------------------------------------
+ * A test and diagnostic entry: the transform-and-quantise kernels of th_encode_* -- the plain ones, their block-qi forms
+ * (theoraenc_hip.h, "Block-level qi") and their masked forms ("Activity masking") -- on the caller's planes, words and tables: the
+ * same launch functions th_encode_* calls for every frame it codes without the skip decision.  dequant and bits are HOST memory,
+ * every other pointer is DEVICE memory.
+ *   frame_*, pixel_fmt, pic_*, src, src_pitch   as thip_enc_inter_stage takes them
+ *   classes   0: a key frame (every block INTRA and coded; prev, ref_pitch and words are not read, prev and words may be NULL); 2, 3:
+ *             an inter frame with prev, gold, ref_pitch and words as thip_enc_skip_stage takes them
+ *   nqis      0: the plain kernel, one qi and no choice (bits and qii are not read and may be NULL); 1..3: the block-qi kernel over
+ *             a list of that length
+ *   dequant   HOST, zig-zag order, 1..32767: with classes 2 / 3 [max(nqis, 1)][2][3][64], at each qi of the list the intra then the
+ *             inter table of each plane; with classes 0 [max(nqis, 1)][3][64], the intra tables alone
+ *   bits      HOST, uint8 [2][4][32], as thip_enc_skip_stage takes it
+ *   iscale    masking's scales, [nfrags] uint16 in fragment raster order: the masked kernel, lambda_b = (lambda iscale + 1024) >> 11
+ *             with lambda = (s1 * s1 * 40) >> 7 from the block's table at qis[0]; or NULL: no masking.  Not with nqis 0
+ * Out: levels [nfrags][64] (coded order, zig-zag; the DC at qis[0], the AC at the block's chosen qi) and dcq [nfrags] (raster),
+ * required; qii [nfrags] (coded order), required with nqis >= 1; cmap [nfrags] (raster: 0 uncoded, else the block's class 1 intra,
+ * 2 PREV, 3 GOLD), required with classes 2 / 3 and not written with classes 0; dcr [nfrags] (raster), optional, with classes 2 / 3:
+ * the DC launch runs over what the kernel left, as thip_enc_inter_stage's CODE runs it (0 for an uncoded block); overflow, one word,
+ * optional: the kernels leave it 0 (only the token kernel counts into it: a level beyond +-580 goes out as it is).
+ * Synchronous, on the calling thread's current device (its null stream).
+ * THIP_EFAULT: req, a plane the call reads, a table or a required output NULL, words NULL with classes 2 / 3, or a HIP call failed.
+ * THIP_EINVAL: the frame size, fragment count, pixel format, picture region and pitches as thip_enc_inter_stage refuses them; classes
+ * not 0, 2 or 3; a gold plane with classes below 3; nqis outside 0..3; iscale with nqis 0; a table entry outside 1..32767; a bits
+ * entry above 64; levels or words not 16-byte aligned (words 4-byte with classes 2), dcq, dcr or iscale not 2-byte, overflow not
+ * 4-byte -- all found before a device is touched.
+ * ---------------------------------------------------------------------------------- */
+typedef struct thip_enc_fq_req {   /* 240 bytes */
+  int32_t frame_width, frame_height, pixel_fmt;
+  int32_t pic_x, pic_y, pic_width, pic_height;
+  int32_t classes, nqis, reserved;
+  const uint8_t *src[3];
+  int64_t src_pitch[3];
+  const uint8_t *prev[3], *gold[3];
+  int64_t ref_pitch[3];
+  const void *words;
+  const uint16_t *dequant;
+  const uint8_t *bits;
+  const uint16_t *iscale;
+  int16_t *levels, *dcq;
+  uint8_t *qii, *cmap;
+  int16_t *dcr;
+  uint32_t *overflow;
+} thip_enc_fq_req;
+int thip_enc_fq_stage(const thip_enc_fq_req *req);
+
+/* ------------------------------------------------------------------------------------
  * A test and diagnostic entry: the level choice of th_encode_* (theoraenc_hip.h, "Level choice") on the caller's planes, words,
  * tables and LEVELS: the same launch function th_encode_* calls behind its quantising kernels.  The levels are the caller's, so any
  * pattern of levels can be put on any content.  dequant and bits are HOST memory, every other pointer is DEVICE memory.

@@ -37,17 +37,30 @@ def code_block(c, tabs, bits, lam_b, bias=B.FLAG_BIAS):
     """One block: c [64] its fDCT (zig-zag), tabs the block's table at each qi of the list, bits [4][32] of its plane, lam_b its
     lambda.  Returns (levels with the DC at qis[0] and the AC at the chosen qi, qii, D_code, R)."""
     c = [int(v) for v in c]
-    cand = []
-    for k, tab in enumerate(tabs):
-        q = oracle.quantize_batch(np.asarray([c], np.int16), np.asarray(tab, np.uint16))[0][0].astype(np.int64)
-        d = sum((c[z] - int(q[z]) * int(tab[z])) ** 2 for z in range(1, 64))
-        r = B.ac_bits(q, bits)
-        cand.append((d + lam_b * (r + (bias if k else 0)), k, q, d, r))
-    _, k, q, d, r = min(cand, key=lambda t: (t[0], t[1]))   # the least J, a tie to the lower k
-    lev = cand[0][2].copy()
+    cand = block_candidates(c, tabs, bits)
+    k = choose_candidate(cand, lam_b, bias)
+    q, d, r = cand[k]
+    lev = cand[0][0].copy()
     lev[1:] = q[1:]
     d_code = d + (c[0] - int(lev[0]) * int(tabs[0][0])) ** 2
     return lev, k, d_code, r
+
+
+def block_candidates(c, tabs, bits):
+    """The block's candidates, one a qi of the list: [(levels [64] int64, D_k: the squared error at z >= 1, R_k: the AC bits)], on
+    Python ints.  A level beyond +-580 counts as token 22 does, whose length does not depend on the value."""
+    c = [int(v) for v in c]
+    cand = []
+    for tab in tabs:
+        q = oracle.quantize_batch(np.asarray([c], np.int16), np.asarray(tab, np.uint16))[0][0].astype(np.int64)
+        d = sum((c[z] - int(q[z]) * int(tab[z])) ** 2 for z in range(1, 64))
+        cand.append((q, d, B.ac_bits(np.clip(q, -580, 580), bits)))
+    return cand
+
+
+def choose_candidate(cand, lam_b, bias=B.FLAG_BIAS):
+    """The choice rule: the least D_k + lam_b (R_k + bias for k != 0), a tie to the lower k."""
+    return min((d + int(lam_b) * (r + (bias if k else 0)), k) for k, (_, d, r) in enumerate(cand))[1]
 
 
 def skip_test(ssd, moving, d_code, lam_b, r):

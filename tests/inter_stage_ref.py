@@ -77,12 +77,12 @@ def decide8(ms, lam):
 
 
 # ---- (c): prediction, transform, quantiser, then the DC --------------------------------------------------------------------------
-def levels_of(geo, src, prev, gold, fpix, fvx, fvy, tabs):
-    """Every fragment's quantised levels (raster order, zig-zag) and its table type: the prediction of its pixel mode fpix [nfrags]
-    with its vector (fvx, fvy) from PREV or GOLD (gold may be None without GOLD modes), 128 for INTRA; tabs[(qti, plane)]: the
-    zig-zag tables.  (The block loop of InterEncoder._inter and ModesEncoder._inter, which call this.)"""
+def coefficients_of(geo, src, prev, gold, fpix, fvx, fvy):
+    """Every fragment's fDCT (raster order, zig-zag, int16) and its table type: the residual against the prediction of its pixel mode
+    fpix [nfrags] with its vector (fvx, fvy) from PREV or GOLD (gold may be None without GOLD modes), 128 for INTRA (prev may be None
+    when every block is INTRA)."""
     fgold = (fpix == GOLDEN_NOMV) | (fpix == GOLDEN_MV)
-    lev = np.zeros((geo.nfrags, 64), np.int64)
+    dct = np.zeros((geo.nfrags, 64), np.int16)
     qti_of = np.zeros(geo.nfrags, np.int64)
     for p, g in enumerate(geo.planes):
         nh = g["nhfrags"]
@@ -93,19 +93,33 @@ def levels_of(geo, src, prev, gold, fpix, fvx, fvy, tabs):
         X = fx[:, None, None] * 8 + r[None, None, :]
         qx, qy = p > 0 and geo.hdec, p > 0 and geo.vdec
         vx, vy = fvx[fi][:, None, None], fvy[fi][:, None, None]
-        pred = predict(prev[p], X, Y, vx, vy, qx, qy)
-        if gold is not None:
-            pred = np.where(fgold[fi][:, None, None], predict(gold[p], X, Y, vx, vy, qx, qy), pred)
         intra = fpix[fi] == INTRA
-        pred[intra] = 128
+        if prev is None:
+            assert intra.all()
+            pred = np.full(Y.shape[:1] + (8, 8), 128, np.int64)
+        else:
+            pred = predict(prev[p], X, Y, vx, vy, qx, qy)
+            if gold is not None:
+                pred = np.where(fgold[fi][:, None, None], predict(gold[p], X, Y, vx, vy, qx, qy), pred)
+            pred[intra] = 128
         res = (src[p][Y, X] - pred).reshape(-1, 64)
-        qti = np.where(intra, 0, 1)
-        qti_of[fi] = qti
-        dct = oracle.fdct8x8_batch(res.astype(np.int16))
+        qti_of[fi] = np.where(intra, 0, 1)
+        dct[fi] = oracle.fdct8x8_batch(res.astype(np.int16))
+    return dct, qti_of
+
+
+def levels_of(geo, src, prev, gold, fpix, fvx, fvy, tabs):
+    """Every fragment's quantised levels (raster order, zig-zag) and its table type: the prediction of its pixel mode fpix [nfrags]
+    with its vector (fvx, fvy) from PREV or GOLD (gold may be None without GOLD modes), 128 for INTRA; tabs[(qti, plane)]: the
+    zig-zag tables.  (The block loop of InterEncoder._inter and ModesEncoder._inter, which call this.)"""
+    dct, qti_of = coefficients_of(geo, src, prev, gold, fpix, fvx, fvy)
+    lev = np.zeros((geo.nfrags, 64), np.int64)
+    for p, g in enumerate(geo.planes):
+        fi = g["froffset"] + np.arange(g["nfrags"])
         for t in range(2):
-            sel = qti == t
+            sel = qti_of[fi] == t
             if sel.any():
-                q, _ = oracle.quantize_batch(dct[sel], tabs[(t, p)].astype(np.uint16))
+                q, _ = oracle.quantize_batch(dct[fi[sel]], tabs[(t, p)].astype(np.uint16))
                 lev[fi[sel]] = q
     return lev, qti_of
 

@@ -80,6 +80,14 @@ def test_argument_validation_without_gpu():
                                           "cmap", "tok", "mask", "chunk_cnt", "chunk_base", "list_len", "overflow", "out", "out_cap")] == \
         [0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 56, 64, 72, 80, 88, 96, 104, 112]
     assert L.thip_enc_tok_stage(C.byref(T())) == _lib.EINVAL   # (no stage)
+    assert L.thip_enc_fq_stage(None) == _lib.EFAULT
+    Q = _lib.EncFqReq
+    assert C.sizeof(Q) == 240
+    assert [getattr(Q, f).offset for f in ("frame_width", "frame_height", "pixel_fmt", "pic_x", "pic_y", "pic_width", "pic_height", "classes",
+                                          "nqis", "reserved", "src", "src_pitch", "prev", "gold", "ref_pitch", "words", "dequant", "bits",
+                                          "iscale", "levels", "dcq", "qii", "cmap", "dcr", "overflow")] == \
+        [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 64, 88, 112, 136, 160, 168, 176, 184, 192, 200, 208, 216, 224, 232]
+    assert L.thip_enc_fq_stage(C.byref(Q())) == _lib.EINVAL   # (no frame)
 
 
 def test_loop_filter_init_slot_matches_oracle_table():

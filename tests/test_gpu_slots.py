@@ -384,6 +384,27 @@ def test_enc_quantize(hip):
         assert np.array_equal(want_q, q.cpu().numpy()) and np.array_equal(want_nz, nz.cpu().numpy()), trial
 
 
+def test_enc_quantize_every_step_and_coefficient(hip):
+    """Every step 8..4096 against every int16 coefficient: 64 calls, each with a table of 64 distinct steps (the 4089 steps fill 64
+    tables less seven entries, which start over at 8) over 65536 blocks whose every column sweeps -32768..32767 -- the quantiser
+    every transform-and-quantise kernel runs (quant_recip, quant_level of thip_fdct.h) against oc_enc_quantize.  The full sweep: the
+    oracle's share is under a second of CPU time."""
+    from theora_amd import _lib
+    import torch
+    L = _lib.load()
+    dct = np.ascontiguousarray(np.repeat(np.arange(-32768, 32768, dtype=np.int16)[:, None], 64, 1))
+    n = dct.shape[0]
+    tabs = np.resize(np.arange(8, 4097), (64, 64)).astype(np.uint16)
+    assert set(tabs.reshape(-1).tolist()) == set(range(8, 4097)) and all(len(set(t.tolist())) == 64 for t in tabs)
+    d_dct = dev(dct)
+    q = torch.empty((n, 64), dtype=torch.int16, device="cuda")
+    nz = torch.empty(n, dtype=torch.int32, device="cuda")
+    for k, dq in enumerate(tabs):
+        want_q, want_nz = oracle.quantize_batch(dct, dq)
+        assert L.thip_enc_quantize_batch(q.data_ptr(), nz.data_ptr(), d_dct.data_ptr(), dev(dq).data_ptr(), n) == 0
+        assert np.array_equal(want_q, q.cpu().numpy()) and np.array_equal(want_nz, nz.cpu().numpy()), (k, int(dq[0]))
+
+
 def test_enc_chain_on_a_caller_stream(hip):
     """thip_set_batch_stream(stream, 0): residual -> forward DCT -> quantiser enqueued back to back
     on a caller-owned stream, no host wait in between, one synchronisation at the end -- the result

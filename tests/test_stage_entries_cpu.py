@@ -1,4 +1,4 @@
-"""The direct stage entries (thip_enc_{inter,rate,mask,roi,rd,skip,rdq,tok}_stage of include/theora_hip.h) refuse alike: one table
+"""The direct stage entries (thip_enc_{inter,rate,mask,roi,rd,skip,rdq,tok,fq}_stage of include/theora_hip.h) refuse alike: one table
 of requests that are wrong in two ways at once, or wrong at an edge, with the code each entry answers.  The codes are the contract of
 the entries' shared frame, picture and plane rules (the order of the checks included): they were recorded from the entries as they
 stood when each still carried its own copy of those rules.  No GPU: every request here is refused before a device is touched, the
@@ -42,6 +42,9 @@ ENTRIES = {
     "tok": (E.tok_stage, dict(_FRAME, classes=0, stages=7, levels=A, dcq=A, dcr=A, cmap=A + 1, tok=A, mask=A, chunk_cnt=A, chunk_base=A,
                               list_len=A, overflow=A, out=A, out_cap=1 << 20),
             {}, ("levels", "dcq", "dcr", "mask", "tok", "chunk_cnt", "chunk_base", "list_len", "overflow", "out")),
+    "fq": (E.fq_stage, dict(_FRAME, **_PLANES, **_REFS, gold=[A] * 3, classes=3, nqis=2, words=A, dequant=_DQ2, bits=_BITS, iscale=A,
+                            levels=A, dcq=A, qii=A + 1, cmap=A + 1, dcr=A, overflow=A),
+           dict(dequant=(1, 32767), bits=(0, 64)), ("words", "levels", "dcq", "dcr", "iscale", "overflow")),
 }
 
 # one macro block row over every entry's cap of 1 << 24 blocks: 4:2:0 at 16384 pixels a row has 6144 blocks a macro block row, and
@@ -181,12 +184,29 @@ EXPECTED = {
     'tok: (g) list_len off by a byte': EINVAL,
     'tok: (g) overflow off by a byte': EINVAL,
     'tok: (g) out off by a byte': EINVAL,
+    'fq: (a) a bad rectangle and a NULL src plane': EINVAL,
+    'fq: (b) a NULL src plane and a small src_pitch': EFAULT,
+    'fq: (c) gold with classes 2 and a small ref_pitch': EINVAL,
+    'fq: (d) classes 3 with one gold plane missing': EFAULT,
+    'fq: (e) one macro block row over the cap': EINVAL,
+    'fq: (f) dequant[0] = 0': EINVAL,
+    'fq: (f) dequant[0] = 32768': EINVAL,
+    'fq: (f) dequant[last] = 0': EINVAL,
+    'fq: (f) dequant[last] = 32768': EINVAL,
+    'fq: (f) bits[0] = 65': EINVAL,
+    'fq: (f) bits[last] = 65': EINVAL,
+    'fq: (g) words off by a byte': EINVAL,
+    'fq: (g) levels off by a byte': EINVAL,
+    'fq: (g) dcq off by a byte': EINVAL,
+    'fq: (g) dcr off by a byte': EINVAL,
+    'fq: (g) iscale off by a byte': EINVAL,
+    'fq: (g) overflow off by a byte': EINVAL,
 }
 
 
 def test_the_table_is_whole():
     assert [c[0] for c in CASES] == list(EXPECTED)
-    assert {c[0].split(":")[0] for c in CASES} == set(ENTRIES) and len(ENTRIES) == 8
+    assert {c[0].split(":")[0] for c in CASES} == set(ENTRIES) and len(ENTRIES) == 9
 
 
 @pytest.mark.parametrize("what,fn,kw", CASES, ids=[c[0] for c in CASES])

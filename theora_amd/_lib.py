@@ -155,6 +155,17 @@ class EncSkipReq(C.Structure):
                 ("skf", C.c_void_p), ("dcode", C.c_void_p), ("rate", C.c_void_p), ("dskip", C.c_void_p)]
 
 
+class EncFqReq(C.Structure):
+    """thip_enc_fq_req (include/theora_hip.h)."""
+    _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
+                ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("pic_width", C.c_int32), ("pic_height", C.c_int32),
+                ("classes", C.c_int32), ("nqis", C.c_int32), ("reserved", C.c_int32),
+                ("src", C.c_void_p * 3), ("src_pitch", C.c_int64 * 3), ("prev", C.c_void_p * 3), ("gold", C.c_void_p * 3),
+                ("ref_pitch", C.c_int64 * 3), ("words", C.c_void_p), ("dequant", C.c_void_p), ("bits", C.c_void_p),
+                ("iscale", C.c_void_p), ("levels", C.c_void_p), ("dcq", C.c_void_p), ("qii", C.c_void_p), ("cmap", C.c_void_p),
+                ("dcr", C.c_void_p), ("overflow", C.c_void_p)]
+
+
 class EncRdqReq(C.Structure):
     """thip_enc_rdq_req (include/theora_hip.h)."""
     _fields_ = [("frame_width", C.c_int32), ("frame_height", C.c_int32), ("pixel_fmt", C.c_int32),
@@ -286,6 +297,7 @@ SYMBOLS = [
     ("thip_enc_roi_stage", _I, [C.POINTER(EncRoiReq)]),
     ("thip_enc_rd_stage", _I, [C.POINTER(EncRdReq)]),
     ("thip_enc_skip_stage", _I, [C.POINTER(EncSkipReq)]),
+    ("thip_enc_fq_stage", _I, [C.POINTER(EncFqReq)]),
     ("thip_enc_rdq_stage", _I, [C.POINTER(EncRdqReq)]),
     ("thip_enc_tok_stage", _I, [C.POINTER(EncTokReq)]),
     ("thip_profile_enable", _I, [_I]),

@@ -723,6 +723,10 @@ static void enc_roi_stats(th_enc_ctx *e, bool queued) {
 // the scales the frame queued has in d_iscale (masking's, the map's, or both), or nullptr: the plain block-qi forms
 static const uint16_t *enc_iscale(const th_enc_ctx *e) { return e->mask_queued || e->roi_queued ? e->d_iscale : nullptr; }
 
+// what the quantising launch (fq_launch_key, fq_launch_inter of thip_encode_mask.h) selects by: the frame's list with block qi on,
+// else the plain kernel at the frame's qi -- also where the skip decision or the level choice made sel a one-entry list
+static BqiSel enc_fq_sel(const th_enc_ctx *e, const BqiSel &sel) { return e->bqi ? sel : BqiSel{0, e->frame_qi, 0, 0, 0, 0}; }
+
 // TH_ENCCTL_THIP_SET_ROI_MAP, its checks made: the encoder's tight copy of the map.  A host map goes up before the call returns; a
 // device map is copied, clamped and counted behind the caller's stream, which then waits for the copy alone
 static int enc_roi_set(th_enc_ctx *e, const thip_enc_roi_map *a) {
@@ -984,17 +988,16 @@ static int enc_modes_alloc(th_enc_ctx *e) {
 
 // The launches of an inter frame, written once for its two sets of kernels: the search, the transform-and-quantise and the DC
 // launch of one macro-block word (d_mb) are the launch functions beside the kernels (thip_encode_inter.h, thip_encode_modes.h),
-// which thip_enc_inter_stage calls too; k_fq_bqi: the block-qi kernel of that word; gold: GOLD for the kernels that read it (three
-// reference classes then), else nothing (two).
+// which thip_enc_inter_stage calls too; the quantising kernel of that word is fq_launch_inter's choice (thip_encode_mask.h), which
+// thip_enc_fq_stage calls too; gold: GOLD for the kernels that read it (three reference classes then), else nothing (two).
 // stats: k_rate_me's words of this frame where the measurement of thip_encode_cut.h left them and d_mb follows from them (five
 // modes) -- k_enc_mb_modes then stands in for the search --, else nullptr
-extern "C++" template <class FqBqi, class FqMask, class Word, class... Gold>
-static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, FqBqi k_fq_bqi, FqMask k_fq_mask, Word *d_mb,
-                            const uint4 *stats, const EncRef &R, const Gold &...gold) {
+extern "C++" template <class Word, class... Gold>
+static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, Word *d_mb, const uint4 *stats, const EncRef &R,
+                            const Gold &...gold) {
   constexpr int classes = sizeof...(Gold) ? 3 : 2;
   const int64_t n = e->nfrags;
   const int lambda = e->lambda[e->frame_qi];
-  const dim3 gfq((unsigned)((4 * n + 255) / 256)), wg(256);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   ENC_TRY(hipMemsetAsync(e->d_dclast, 0, (size_t)e->nchunks * classes * 4, e->stream));
   if (enc_mask_queue(e, g) || enc_roi_queue(e, g)) return TH_EFAULT;
@@ -1006,25 +1009,15 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
   } else {
     ENC_TRY(inter_launch_search(d_mb, g, R, gold..., e->nmbx, e->nmbs, lambda, e->stream));
   }
+  const EncRef *G[] = {&R, &gold...};   // (GOLD where the word has it, else PREV, which is not read)
   if (e->skip) {
-    const EncRef *G[] = {&R, &gold...};   // (GOLD where the word has it, else PREV, which is not read)
     if (enc_skip_queue(e, g, sel, (const Word *)d_mb, R, *G[sizeof...(Gold)])) return TH_EFAULT;
-  } else if (enc_iscale(e)) {
-    hipLaunchKernelGGL(k_fq_mask, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
-                       e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
-    ENC_TRY(hipGetLastError());
-  } else if (e->bqi) {
-    hipLaunchKernelGGL(k_fq_bqi, gfq, wg, 0, e->stream, e->d_levels, e->d_dcq, e->d_qii, e->d_cmap, e->d_dclast, e->d_small + 192,
-                       e->d_order, g, R, gold..., (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, sel, n);
-    ENC_TRY(hipGetLastError());
   } else {
-    ENC_TRY(inter_launch_fq(InterBufs{e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192}, e->d_order, g, R, gold...,
-                            (const Word *)d_mb, e->nmbx, e->d_dqi + (size_t)e->frame_qi * 384, n, e->stream));
+    ENC_TRY(fq_launch_inter(InterBufs{e->d_levels, e->d_dcq, e->d_cmap, e->d_dclast, e->d_small + 192}, e->d_qii, e->d_order, g, R,
+                            *G[sizeof...(Gold)], (const Word *)d_mb, e->nmbx, e->d_dqi, e->d_bqbits, enc_fq_sel(e, sel), enc_iscale(e), n,
+                            e->stream));
   }
-  {
-    const EncRef *G[] = {&R, &gold...};
-    if (enc_rdq_queue(e, classes, g, sel, (const Word *)d_mb, R, *G[sizeof...(Gold)])) return TH_EFAULT;
-  }
+  if (enc_rdq_queue(e, classes, g, sel, (const Word *)d_mb, R, *G[sizeof...(Gold)])) return TH_EFAULT;
   ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the level choice reads them too)
   if constexpr (classes == 3) ENC_TRY(inter_launch_dc3(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
   else ENC_TRY(inter_launch_dc(e->d_dcr, e->d_dcq, e->d_cmap, e->d_dclast, g, n, e->stream));
@@ -1037,9 +1030,9 @@ static int enc_launch_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel
 static int enc_queue_inter(th_enc_ctx *e, const EncPlanes &g, const BqiSel &sel, const uint4 *stats) {
   EncRef R, G;
   if (enc_ref_frame(e, R)) return TH_EFAULT;
-  if (!e->modes) return enc_launch_inter(e, g, sel, k_enc_inter_fq_bqi, k_enc_inter_fq_bqi_mask, e->d_mb, stats, R);
+  if (!e->modes) return enc_launch_inter(e, g, sel, e->d_mb, stats, R);
   if (enc_ref_frame(e, G, THIP_FRAME_GOLD) || enc_modes_alloc(e)) return TH_EFAULT;
-  return enc_launch_inter(e, g, sel, k_enc_inter_fq_all_bqi, k_enc_inter_fq_all_bqi_mask, e->d_mb4, nullptr, R, G);
+  return enc_launch_inter(e, g, sel, e->d_mb4, nullptr, R, G);
 }
 
 // ---- bitrate mode -----------------------------------------------------------------------------------------------------------
@@ -1238,16 +1231,8 @@ static int enc_queue_frame(th_enc_ctx *e, const uint8_t *const src[3], const int
   if (!e->frame_key) return enc_queue_inter(e, g, sel, searched ? (const uint4 *)e->d_rmbs : nullptr);
   ENC_TRY(hipEventRecord(e->ev_t0, e->stream));
   if (enc_mask_queue(e, g) || enc_roi_queue(e, g)) return TH_EFAULT;
-  if (enc_iscale(e))
-    hipLaunchKernelGGL(k_enc_intra_fq_bqi_mask, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                       e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, sel, (const uint16_t *)e->d_iscale, n);
-  else if (e->bqi)
-    hipLaunchKernelGGL(k_enc_intra_fq_bqi, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                       e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, sel, n);
-  else
-    hipLaunchKernelGGL(k_enc_intra_fq, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, e->stream, e->d_levels, e->d_dcq,
-                       e->d_small + 192, e->d_order, g, e->d_dequant + (size_t)e->frame_qi * 192, n);
-  ENC_TRY(hipGetLastError());
+  ENC_TRY(fq_launch_key(e->d_levels, e->d_dcq, e->d_qii, e->d_small + 192, e->d_order, g, e->d_dequant, e->d_bqbits, enc_fq_sel(e, sel),
+                        enc_iscale(e), n, e->stream));
   if (enc_rdq_queue(e, 0, g, sel, (const uint32_t *)nullptr, EncRef{}, EncRef{})) return TH_EFAULT;
   ENC_TRY(hipEventRecord(e->ev_read, e->stream));   // the planes have been read (the level choice reads them too)
   ENC_TRY(tok_launch_intra(enc_tok_bufs(e), e->d_levels, e->d_dcq, e->d_order, g, n, e->stream));
@@ -2578,6 +2563,66 @@ int thip_enc_skip_stage(const thip_enc_skip_req *q) {
   else
     ENC_TRY(skip_launch(o, q->qii, so, (const int32_t *)(d + o_order), g, R, G, (const uint32_t *)q->words, nmbx,
                         (const uint16_t *)(d + o_dq), d + o_bits, sel, q->iscale, q->lambda, n, stream));
+  ENC_TRY(hipStreamSynchronize(stream));
+  return THIP_OK;
+}
+
+// the quantising kernels on the caller's planes, words and tables (theora_hip.h): thip_encode_mask.h's launch functions, as
+// enc_queue_frame and enc_launch_inter make them, and the DC launch behind an inter frame's, on the current device's null stream
+int thip_enc_fq_stage(const thip_enc_fq_req *q) {
+  if (!q) return THIP_EFAULT;
+  EntryFrame f;
+  if (check_frame(f, q->frame_width, q->frame_height, q->pixel_fmt)) return THIP_EINVAL;
+  if (q->classes != 0 && q->classes != 2 && q->classes != 3) return THIP_EINVAL;
+  const bool all = q->classes == 3, key = q->classes == 0;
+  const PicRect pic = pic_rect(*q);
+  const EntryPlanes pl{q->src, q->src_pitch, q->prev, q->gold, q->ref_pitch};
+  // (a key frame reads no reference: whatever prev and ref_pitch hold is let be)
+  if (const int rc = check_picture_planes(f, pic, pl, !key, all ? Gold::required : Gold::forbidden)) return rc;
+  if (q->nqis < 0 || q->nqis > 3 || (q->iscale && !q->nqis)) return THIP_EINVAL;
+  const int ntabs = key ? 3 : 6, nlist = q->nqis ? q->nqis : 1;
+  if (!q->dequant || (q->nqis && (!q->bits || !q->qii)) || !q->levels || !q->dcq || (!key && (!q->words || !q->cmap))) return THIP_EFAULT;
+  if (!table_within(q->dequant, (size_t)nlist * ntabs * 64, 1, 32767) || (q->nqis && !table_within(q->bits, 256, 0, 64))) return THIP_EINVAL;
+  if ((!key && misaligned(q->words, all ? 16 : 4)) || misaligned(q->levels, 16) || misaligned(q->dcq, 2) || misaligned(q->dcr, 2) ||
+      misaligned(q->iscale, 2) || misaligned(q->overflow, 4))
+    return THIP_EINVAL;
+  // ---- nothing above touched a device ----
+  FrameGeometry geo;
+  build_geometry(geo, q->frame_width, q->frame_height, q->pixel_fmt);
+  const int64_t n = geo.nfrags;
+  const int classes = q->classes, nmbx = geo.nh[0] >> 1;
+  const size_t nchunks = (size_t)((n + kEncChunk - 1) / kEncChunk);
+  const EncPlanes g = enc_planes(geo, pic, q->src, q->src_pitch);
+  // (a key frame: no planes; no GOLD: PREV in its place)
+  const EncRef R = enc_ref(geo, key ? nullptr : q->prev, q->ref_pitch), G = enc_ref(geo, key ? nullptr : all ? q->gold : q->prev, q->ref_pitch);
+  // one allocation: dclast [chunks][classes] | overflow | order [n] | dequant [nlist][ntabs][64] | bits [256]
+  const size_t dq_bytes = (size_t)nlist * ntabs * 128;
+  const size_t o_ovf = nchunks * classes * 4, o_order = o_ovf + 16, o_dq = o_order + (size_t)n * 4, o_bits = o_dq + dq_bytes;
+  DeviceBuf buf;
+  ENC_TRY(buf.alloc(o_bits + 256));
+  uint8_t *const d = buf.p;
+  hipStream_t stream = nullptr;
+  ENC_TRY(hipMemcpy(d + o_order, geo.coded_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  ENC_TRY(hipMemcpy(d + o_dq, q->dequant, dq_bytes, hipMemcpyHostToDevice));
+  if (q->nqis) ENC_TRY(hipMemcpy(d + o_bits, q->bits, 256, hipMemcpyHostToDevice));
+  if (o_ovf) ENC_TRY(hipMemsetAsync(d, 0, o_ovf, stream));
+  // (the caller's tables are qi 0, 1, 2 of the kernel's table set and AC tables 0, 1 of its bits)
+  const BqiSel sel{q->nqis, 0, 1, 2, 0, 1};
+  const int32_t *d_order = (const int32_t *)(d + o_order);
+  const uint16_t *d_dq = (const uint16_t *)(d + o_dq);
+  uint32_t *d_dclast = (uint32_t *)d, *d_ovf = q->overflow ? q->overflow : (uint32_t *)(d + o_ovf);
+  if (key) {
+    ENC_TRY(fq_launch_key(q->levels, q->dcq, q->qii, d_ovf, d_order, g, d_dq, d + o_bits, sel, q->iscale, n, stream));
+  } else {
+    const InterBufs o{q->levels, q->dcq, q->cmap, d_dclast, d_ovf};
+    if (all) ENC_TRY(fq_launch_inter(o, q->qii, d_order, g, R, G, (const uint4 *)q->words, nmbx, d_dq, d + o_bits, sel, q->iscale, n, stream));
+    else ENC_TRY(fq_launch_inter(o, q->qii, d_order, g, R, G, (const uint32_t *)q->words, nmbx, d_dq, d + o_bits, sel, q->iscale, n, stream));
+    if (q->dcr) {
+      ENC_TRY(hipMemsetAsync(q->dcr, 0, (size_t)n * 2, stream));   // (the kernel writes the coded fragments' only)
+      if (all) ENC_TRY(inter_launch_dc3(q->dcr, q->dcq, q->cmap, d_dclast, g, n, stream));
+      else ENC_TRY(inter_launch_dc(q->dcr, q->dcq, q->cmap, d_dclast, g, n, stream));
+    }
+  }
   ENC_TRY(hipStreamSynchronize(stream));
   return THIP_OK;
 }

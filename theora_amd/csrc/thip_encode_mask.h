@@ -185,4 +185,47 @@ __global__ __launch_bounds__(256) void k_enc_inter_fq_all_bqi_mask(int16_t *leve
   enc_fq_bqi<3, true>(levels, dcq, qii, cmap, dclast, overflow, coded_order, g, R, G, mb_word, nmbx, dequant, bqbits, sel, n, iscale);
 }
 
+// ---- the launches of the quantising kernels, stated once: th_encode_* (thip_encode.hip) and thip_enc_fq_stage (theora_hip.h) both
+// call these.  Each picks its kernel from sel and iscale: sel.nqis 0 the plain kernel at qi sel.q0 (qii, bqbits and iscale are not
+// read), else the block-qi kernel over sel's list, with iscale (masking's scales, the map's, or both) its masked form.  dequant is the
+// whole table set, of which sel names the qis: [64 qi][3][64] for a key frame, [64 qi][6][64] for an inter frame.
+inline hipError_t fq_launch_key(int16_t *levels, int16_t *dcq, uint8_t *qii, uint32_t *overflow, const int32_t *order, const EncPlanes &g,
+                                const uint16_t *dequant, const uint8_t *bqbits, const BqiSel &sel, const uint16_t *iscale, int64_t n,
+                                hipStream_t stream) {
+  const dim3 grid((unsigned)((4 * n + 255) / 256)), wg(256);
+  if (!sel.nqis)
+    hipLaunchKernelGGL(k_enc_intra_fq, grid, wg, 0, stream, levels, dcq, overflow, order, g, dequant + (size_t)sel.q0 * 192, n);
+  else if (iscale)
+    hipLaunchKernelGGL(k_enc_intra_fq_bqi_mask, grid, wg, 0, stream, levels, dcq, qii, overflow, order, g, dequant, bqbits, sel, iscale, n);
+  else
+    hipLaunchKernelGGL(k_enc_intra_fq_bqi, grid, wg, 0, stream, levels, dcq, qii, overflow, order, g, dequant, bqbits, sel, n);
+  return hipGetLastError();
+}
+
+// Word: k_enc_me's (two reference classes, G is not read) or k_enc_me_all's (three)
+template <class Word>
+inline hipError_t fq_launch_inter(const InterBufs &o, uint8_t *qii, const int32_t *order, const EncPlanes &g, const EncRef &R,
+                                  const EncRef &G, const Word *mb, int nmbx, const uint16_t *dequant, const uint8_t *bqbits,
+                                  const BqiSel &sel, const uint16_t *iscale, int64_t n, hipStream_t stream) {
+  const dim3 grid((unsigned)((4 * n + 255) / 256)), wg(256);
+  if constexpr (sizeof(Word) == sizeof(uint4)) {
+    if (!sel.nqis) return inter_launch_fq(o, order, g, R, G, mb, nmbx, dequant + (size_t)sel.q0 * 384, n, stream);
+    if (iscale)
+      hipLaunchKernelGGL(k_enc_inter_fq_all_bqi_mask, grid, wg, 0, stream, o.levels, o.dcq, qii, o.cmap, o.dclast, o.overflow, order, g, R,
+                         G, mb, nmbx, dequant, bqbits, sel, iscale, n);
+    else
+      hipLaunchKernelGGL(k_enc_inter_fq_all_bqi, grid, wg, 0, stream, o.levels, o.dcq, qii, o.cmap, o.dclast, o.overflow, order, g, R, G, mb,
+                         nmbx, dequant, bqbits, sel, n);
+  } else {
+    if (!sel.nqis) return inter_launch_fq(o, order, g, R, mb, nmbx, dequant + (size_t)sel.q0 * 384, n, stream);
+    if (iscale)
+      hipLaunchKernelGGL(k_enc_inter_fq_bqi_mask, grid, wg, 0, stream, o.levels, o.dcq, qii, o.cmap, o.dclast, o.overflow, order, g, R, mb,
+                         nmbx, dequant, bqbits, sel, iscale, n);
+    else
+      hipLaunchKernelGGL(k_enc_inter_fq_bqi, grid, wg, 0, stream, o.levels, o.dcq, qii, o.cmap, o.dclast, o.overflow, order, g, R, mb, nmbx,
+                         dequant, bqbits, sel, n);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace thip

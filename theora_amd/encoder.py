@@ -1039,6 +1039,22 @@ def skip_stage(frame, pixel_fmt, classes, nqis, pic=None, lam=-1, src=None, src_
     return L.thip_enc_skip_stage(C.byref(q))
 
 
+def fq_stage(frame, pixel_fmt, classes, nqis, pic=None, src=None, src_pitch=None, prev=None, gold=None, ref_pitch=None, words=None,
+             dequant=None, bits=None, iscale=None, levels=None, dcq=None, qii=None, cmap=None, dcr=None, overflow=None):
+    """thip_enc_fq_stage (include/theora_hip.h): the transform-and-quantise kernels on the caller's planes, words and tables, a test
+    and diagnostic entry.  classes: 0 (a key frame: prev, gold, words, cmap, dcr unused), 2 or 3; nqis: 0 (the plain kernel: bits,
+    qii unused) or 1..3 (the block-qi kernel, with iscale the masked one); dequant [max(nqis, 1)][2][3][64], with classes 0
+    [max(nqis, 1)][3][64]; the rest as skip_stage takes them.  Returns the entry's return code; nothing is raised."""
+    L = _lib.load()
+    q = _stage_req(_lib.EncFqReq, frame, pixel_fmt, pic, dict(src=src, prev=prev, gold=gold), dict(src_pitch=src_pitch, ref_pitch=ref_pitch))
+    q.classes, q.nqis = int(classes), int(nqis)
+    # (of any size with an nqis or classes the entry refuses: the refusal is its to make)
+    size = max(int(nqis), 1) * (192 if int(classes) == 0 else 384) if 0 <= int(nqis) <= 3 and int(classes) in (0, 2, 3) else None
+    keep = _host_tables(q, "fq_stage:", [("dequant", dequant, np.uint16, size), ("bits", bits, np.uint8, 256)])
+    q.words, q.iscale, q.levels, q.dcq, q.qii, q.cmap, q.dcr, q.overflow = words, iscale, levels, dcq, qii, cmap, dcr, overflow
+    return L.thip_enc_fq_stage(C.byref(q))
+
+
 def rdq_stage(frame, pixel_fmt, classes, nqis, weight, pic=None, lam=-1, src=None, src_pitch=None, prev=None, gold=None,
               ref_pitch=None, words=None, dequant=None, bits=None, iscale=None, levels=None, qii=None, cmap=None, jbefore=None,
               jafter=None, rate=None):
