@@ -180,9 +180,10 @@ typedef struct {
    decodes its packet on the caller's thread like any packet nobody announced (slower for that one frame, always right).  These
    take back: TH_DECCTL_SET_GRANPOS (the counters it sets are frame N's), TH_DECCTL_SET_PPLEVEL with a level above 0 (the held
    frame was decoded unfiltered and untracked), TH_DECCTL_SET_STRIPE_CB (the callback is made inside a frame's
-   th_decode_packetin), TH_DECCTL_THIP_SET_DEVICE_DC and _SET_DEVICE_TOKENS.  These leave the held frame alone: every
+   th_decode_packetin), TH_DECCTL_THIP_SET_DEVICE_DC and _SET_DEVICE_TOKENS, TH_DECCTL_THIP_SET_FRAME_INFO 1 (the held frame was
+   decoded without a record).  These leave the held frame alone: every
    TH_DECCTL_GET_*, TH_DECCTL_SET_PPLEVEL 0, TH_DECCTL_THIP_PREFETCH_PACKET, _PICTURE_OUT, _PICTURE_RESIZE, _PICTURE_COMPARE,
-   _SET_HOST_OUTPUT, _SET_DEVICE_LISTS.
+   _SET_HOST_OUTPUT, _SET_DEVICE_LISTS, _SET_FRAME_INFO 0, _FRAME_INFO_OUT.
    The picture th_decode_ycbcr_out handed out for frame N stays valid and unchanged either way.  One frame is held at most: the
    backend can take back one (thip_state_ring_rewind, include/theora_hip.h). */
 #define TH_DECCTL_THIP_PREFETCH_PACKET (0x7105)
@@ -245,6 +246,39 @@ typedef struct thip_picture_compare_args {
   int64_t block_pitch[3];
   void *stream;                  /* hipStream_t, or NULL */
 } thip_picture_compare_args;
+/* Extension: buf = int.  1: from the next packet on the context keeps a record of every frame's side data -- which blocks were
+   coded, from which reference, through which vector (thip_state_set_frame_info, include/theora_hip.h: one small launch a frame) --
+   for TH_DECCTL_THIP_FRAME_INFO_OUT; a frame held (above) is taken back first.  0 (the default): no record, no launch, no memory;
+   a held frame is left alone.  TH_EINVAL in slot-trace mode. */
+#define TH_DECCTL_THIP_SET_FRAME_INFO (0x710B)
+/* Extension: buf = thip_frame_info_args.  The side data of the frame th_decode_packetin last returned, written to device memory as
+   thip_frame_info_out does (include/theora_hip.h: the maps kind, mv and ncoef per plane, the dense field flow, valid; every
+   pointer optional).  The fields are thip_frame_info_req's without state and frag_info, plus crop (1: th_info's picture region
+   instead of x, y, width, height; 0 x 0 there: the whole coded frame) and stream; the request fills the host fields at the end:
+   frame_type, nqis, qis and ncoded (coded fragments) of that frame.  A frame that decoded nothing (TH_DUPFRAME: an empty packet, or
+   one with no coded block) reads as every fragment uncoded -- every output zero -- with frame_type 1 (inter), nqis 0 and ncoded 0.
+   Stream, device and the frame it describes are TH_DECCTL_THIP_PICTURE_OUT's, also while a frame decoded ahead is held: the request
+   never decodes ahead and never waits on the host.  Returns 0, what thip_frame_info_out returns for bad arguments, TH_EINVAL
+   before the first packet behind TH_DECCTL_THIP_SET_FRAME_INFO 1 and with the switch off, TH_EIMPL in slot-trace mode. */
+#define TH_DECCTL_THIP_FRAME_INFO_OUT (0x710C)
+typedef struct thip_frame_info_args {
+  int32_t x, y, width, height;   /* display coordinates; 0 x 0: the whole coded frame (ignored with crop) */
+  int32_t crop;                  /* 1: th_info's picture region */
+  int32_t elem, refs;            /* THIP_ELEM_F16 / _F32 for flow; THIP_FI_REF_* */
+  int32_t reserved;
+  uint8_t *kind[3];              /* device memory, every pointer optional */
+  int64_t kind_pitch[3];         /* bytes per row */
+  int8_t *mv[3];
+  int64_t mv_pitch[3];
+  uint8_t *ncoef[3];
+  int64_t ncoef_pitch[3];
+  void *flow;
+  int64_t flow_pitch;
+  uint8_t *valid;
+  int64_t valid_pitch;
+  void *stream;                  /* hipStream_t, or NULL */
+  int32_t frame_type, nqis, qis[3], ncoded;   /* filled by the request (host) */
+} thip_frame_info_args;
 typedef struct thip_slot_trace {
   int64_t ncoded;           /* state_frag_recon calls, in call (= coded) order */
   const int32_t *fragi;     /* _fragi */

@@ -251,6 +251,22 @@ class State:
         picture_compare([self], [ref], [res], metrics, [rect], [bufi], None if blk is None else [blk], stream)
         return (res, blk) if blocks else res
 
+    def set_frame_info(self, on):
+        """thip_state_set_frame_info: keep a record of the side data of every frame this state decodes from now on."""
+        _lib.check(self._L.thip_state_set_frame_info(self._h, int(bool(on))), "set_frame_info")
+
+    def frame_info(self, what=("kind", "mv", "flow"), rect=None, dtype=None, refs=("prev",), frag_info=None, stream=None):
+        """The side data of the frame decoded last (set_frame_info must be on), or of the frame whose frag_info words `frag_info`
+        holds (a device tensor, tile order), as a dict of new device tensors: frame_info for one state.  what: any of "kind",
+        "mv", "ncoef" (lists of three planes), "flow" (dtype torch.float16, the default, or torch.float32) and "valid".
+        Asynchronous on `stream`."""
+        import torch
+        x, y, w, h = rect if rect is not None else (0, 0, self.frame_width, self.frame_height)
+        out = frame_info_alloc(frame_info_shapes(w, h, x, y, self.pixel_fmt), what, torch.float16 if dtype is None else dtype,
+                               torch.device("cuda", self.device))
+        frame_info([self], [out], [rect], refs, None if frag_info is None else [frag_info], stream)
+        return out
+
     def set_eager_output(self, on):
         _lib.check(self._L.thip_state_set_eager_output(self._h, int(bool(on))), "set_eager_output")
 
@@ -538,6 +554,124 @@ def picture_compare(states, refs, results, metrics=("sse",), rects=None, bufis=N
     if n == 0:
         return
     _lib.check(_on_stream(states[0].device, stream, lambda h: L.thip_picture_compare(reqs, n, h)), "thip_picture_compare")
+
+
+# ---------------------------------------------------------------------------------------
+# frame side data (thip_frame_info_out)
+# ---------------------------------------------------------------------------------------
+FI_REFS = {"prev": _lib.FI_REF_PREV, "gold": _lib.FI_REF_GOLD}
+FI_OUTPUTS = ("kind", "mv", "ncoef", "flow", "valid")
+
+
+def frame_info_shapes(width, height, x=0, y=0, pixel_fmt=PF_420):
+    """The output shapes of thip_frame_info_out for the rectangle (x, y, width, height) of a coded frame, display coordinates:
+    {"kind": three (rows, cols), "mv": three (rows, cols, 2), "ncoef": three (rows, cols), "flow": (2, height, width),
+    "valid": (height, width)}.  The maps of plane p cover the fragments the rectangle touches: columns (x >> hdec_p) >> 3 ..
+    ((x + width - 1) >> hdec_p) >> 3, rows likewise with vdec_p (include/theora_hip.h)."""
+    if width < 1 or height < 1 or x < 0 or y < 0:
+        raise ValueError("an empty or negative rectangle")
+    hdec, vdec = int(not (pixel_fmt & 1)), int(not (pixel_fmt & 2))
+    frags = []
+    for p in range(3):
+        hd, vd = (hdec, vdec) if p else (0, 0)
+        frags.append(((((y + height - 1) >> vd) >> 3) - ((y >> vd) >> 3) + 1, (((x + width - 1) >> hd) >> 3) - ((x >> hd) >> 3) + 1))
+    return dict(kind=list(frags), mv=[f + (2,) for f in frags], ncoef=list(frags), flow=(2, height, width), valid=(height, width))
+
+
+def _fi_refs(refs):
+    if isinstance(refs, int):
+        return refs
+    names = [refs] if isinstance(refs, str) else list(refs)
+    for r in names:
+        if r not in FI_REFS:
+            raise ValueError("unknown reference %r" % (r,))
+    return sum(FI_REFS[r] for r in set(names))
+
+
+def frame_info(states, outs, rects=None, refs=("prev",), frag_infos=None, stream=None):
+    """thip_frame_info_out: per state the side data of a frame into outs[i], a dict with any of the keys "kind", "mv", "ncoef"
+    (three device tensors each, one per plane; an entry may be None), "flow" and "valid", of frame_info_shapes' shapes: uint8 for
+    kind, ncoef and valid, int8 for mv, float16 or float32 for flow (rows may have a pitch of their own).  rects: per state
+    (x, y, width, height) in display coordinates, None: the whole coded frame.  refs: "prev", "gold", both (or the THIP_FI_REF_*
+    flags): the kinds whose vectors flow holds; may be a list of such, one per state.  frag_infos: per state a device tensor
+    holding a frame's frag_info words in tile order (info_words' layout), or None for the state's own record
+    (State.set_frame_info).  Asynchronous on `stream` (default torch.cuda.current_stream of the states' device)."""
+    import torch
+    L = _lib.load()
+    n = len(states)
+    if len(outs) != n or (frag_infos is not None and len(frag_infos) != n) or (rects is not None and len(rects) != n):
+        raise ValueError("one destination, rectangle and frag_info per state")
+    per_state = isinstance(refs, list) and len(refs) == n and all(isinstance(r, (tuple, list, int)) for r in refs)
+    reqs = (_lib.FrameInfoReq * max(n, 1))()
+    keep = []
+    for i, st in enumerate(states):
+        x, y, w, h = rects[i] if rects is not None and rects[i] is not None else (0, 0, 0, 0)
+        rw, rh = (w, h) if (w or h) else (st.frame_width, st.frame_height)
+        shapes = frame_info_shapes(rw, rh, x if (w or h) else 0, y if (w or h) else 0, st.pixel_fmt)
+        r = reqs[i]
+        r.state = st.handle
+        fi = frag_infos[i] if frag_infos is not None else None
+        if fi is not None:
+            if not isinstance(fi, torch.Tensor) or not fi.is_cuda or not fi.is_contiguous() or fi.element_size() != 4 or fi.numel() != 2 * 64 * st.ntiles:
+                raise ValueError("frag_info is a contiguous device tensor of 2 * 64 * ntiles 32-bit words")
+            keep.append(fi)
+            r.frag_info = fi.data_ptr()
+        r.x, r.y, r.width, r.height = x, y, w, h
+        r.refs = _fi_refs(refs[i] if per_state else refs)
+        out = outs[i]
+        for key in out:
+            if key not in FI_OUTPUTS:
+                raise ValueError("unknown output %r" % (key,))
+
+        def plane(t, shape, dtypes, what):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes:
+                raise TypeError("%s goes to a %s device tensor" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes)))
+            if tuple(t.shape) != tuple(shape) or t.stride(-1) != 1:
+                raise ValueError("%s of shape %s for %s" % (what, tuple(t.shape), tuple(shape)))
+            return t
+        for key, dt in (("kind", torch.uint8), ("ncoef", torch.uint8), ("mv", torch.int8)):
+            ts = out.get(key)
+            if ts is None:
+                continue
+            if len(ts) != 3:
+                raise ValueError("%s wants three planes (None for one not wanted)" % key)
+            for p in range(3):
+                if ts[p] is None:
+                    continue
+                t = plane(ts[p], shapes[key][p], (dt,), key)
+                if key == "mv" and t.stride(1) != 2:
+                    raise ValueError("mv keeps a fragment's two bytes together")
+                getattr(r, key)[p] = t.data_ptr()
+                getattr(r, key + "_pitch")[p] = t.stride(0)
+        t = out.get("flow")
+        if t is not None:
+            t = plane(t, shapes["flow"], (torch.float16, torch.float32), "flow")
+            if t.stride(0) != t.shape[1] * t.stride(1):
+                raise ValueError("flow's second plane follows the first at height rows")
+            r.flow, r.flow_pitch, r.elem = t.data_ptr(), t.stride(1) * t.element_size(), _elem(t.dtype)
+        t = out.get("valid")
+        if t is not None:
+            t = plane(t, shapes["valid"], (torch.uint8,), "valid")
+            r.valid, r.valid_pitch = t.data_ptr(), t.stride(0)
+    if n == 0:
+        return
+    _lib.check(_on_stream(states[0].device, stream, lambda h: L.thip_frame_info_out(reqs, n, h)), "thip_frame_info_out")
+
+
+def frame_info_alloc(shapes, what, dtype, device):
+    """Fresh device tensors for the outputs `what` of frame_info_shapes' `shapes`: the dict frame_info takes."""
+    import torch
+    out = {}
+    for key in what:
+        if key not in FI_OUTPUTS:
+            raise ValueError("unknown output %r" % (key,))
+        if key == "flow":
+            out[key] = torch.empty(shapes[key], dtype=dtype, device=device)
+        elif key == "valid":
+            out[key] = torch.empty(shapes[key], dtype=torch.uint8, device=device)
+        else:
+            out[key] = [torch.empty(s, dtype=torch.int8 if key == "mv" else torch.uint8, device=device) for s in shapes[key]]
+    return out
 
 
 # ---------------------------------------------------------------------------------------

@@ -65,6 +65,17 @@ class PictureResizeReq(C.Structure):
 
 
 CMP_SSE, CMP_SSIM = 1, 2
+FI_REF_PREV, FI_REF_GOLD = 1, 2
+
+
+class FrameInfoReq(C.Structure):
+    """thip_frame_info_req (include/theora_hip.h)."""
+    _fields_ = [("state", C.c_void_p), ("frag_info", C.c_void_p),
+                ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("elem", C.c_int32), ("refs", C.c_int32),
+                ("kind", C.c_void_p * 3), ("kind_pitch", C.c_int64 * 3), ("mv", C.c_void_p * 3), ("mv_pitch", C.c_int64 * 3),
+                ("ncoef", C.c_void_p * 3), ("ncoef_pitch", C.c_int64 * 3), ("flow", C.c_void_p), ("flow_pitch", C.c_int64),
+                ("valid", C.c_void_p), ("valid_pitch", C.c_int64)]
 
 
 class PictureMetrics(C.Structure):
@@ -239,6 +250,8 @@ SYMBOLS = [
     ("thip_picture_resize", _I, [C.POINTER(PictureResizeReq), _I, _P]),
     ("thip_picture_compare", _I, [C.POINTER(PictureCompareReq), _I, _P]),
     ("thip_picture_in", _I, [C.POINTER(PictureInReq), _I, _P]),
+    ("thip_frame_info_out", _I, [C.POINTER(FrameInfoReq), _I, _P]),
+    ("thip_state_set_frame_info", _I, [_P, _I]),
     ("thip_decode_frames", _I, [C.POINTER(_P), C.POINTER(FrameDesc), _I, _P, C.POINTER(C.c_int32)]),
     ("thip_synchronize", _I, []),
     ("thip_frame_begin", _I, [_P, _I]),

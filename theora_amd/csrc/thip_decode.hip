@@ -79,6 +79,7 @@ Option g_options[] = {
     {"cell_fast", 1, "k_recon_lf: 1 (default): a tile whose blocks and neighbouring edge blocks are all coded runs its filter cells in the all-coded form; 0: every tile takes the general cell (tests decode the same frames both ways)"},
     {"fe_device_dc", 0, "th_decode_*: DC un-prediction on the device"},
     {"fe_device_tokens", 0, "th_decode_*: token expansion + dequantisation on the device (host-delimited tokens)"},
+    {"fe_frame_info", 0, "th_decode_*: 1: every new context keeps the record of each frame's side data (TH_DECCTL_THIP_SET_FRAME_INFO 1 from the start); 0 (default): off"},
     {"fe_device_lists", -1, "th_decode_*: the token lists themselves on the device (1 on, 0 off, -1 on while at most four decoder contexts are alive)"},
     {"tl_dc_copy", 0, "token lists on the device, thip_state_token_lists_finish: 0 (default): a kernel copies the caller's DC values out of the pinned staging buffer (k_tok_copy); 1: a copy engine does (rounds 3-4)"},
     {"spec_coeffs", 1, "k_recon_lf, levels form: 1 (default): for a frame with a coefficient unit for every block (nslots == its fragments) the waves of whole tile rows ask for their tile's units when they start, at the address that follows from the tile's place in its plane, and check it against the first-slot word; 0: always after the command words"},
@@ -181,6 +182,7 @@ extern "C" const char *thip_option_name(int index, const char **help) {
 #include "thip_picture_resize.h"
 #include "thip_picture_compare.h"
 #include "thip_picture_in.h"
+#include "thip_frame_info.h"
 
 // ---------------------------------------------------------------------------------------
 // host side
@@ -312,6 +314,10 @@ struct thip_state {
   hipEvent_t ev_pp;         // recorded behind the copy out of h_pp_qis
   int64_t pp_serial;        // frame_serial of the frame pp_frame was made from, -1 if none
   int pp_active[3];
+  // frame side data (thip_state_set_frame_info): two records of one masked command word a fragment, written by turns
+  int fi_on, fi_cur;        // fi_cur: the record that holds the frame decoded last, -1 none
+  int64_t fi_count;         // records written so far (thip_state_ring_mark notes it; never reset)
+  uint32_t *fi_rec[2];      // device, nfrags words each
 };
 
 // 0: the state's fault word is clear; 1: a failed hand-over was noticed and the frame has been decoded again with the two
@@ -680,6 +686,7 @@ int thip_state_create_on(thip_state **out, int device, int frame_width, int fram
   st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = -1;
   st->map_serial[0] = st->map_serial[1] = -1;
   st->pp_serial = -1;
+  st->fi_cur = -1;
   {
     std::lock_guard<std::mutex> lk(g_states_mu);
     g_states.push_back(st);
@@ -753,6 +760,8 @@ void thip_state_free(thip_state *st) {
   if (st->h_dqp) (void)hipHostFree(st->h_dqp);
   if (st->d_dqp) (void)hipFree(st->d_dqp);
   if (st->d_flags) (void)hipFree(st->d_flags);
+  for (int k = 0; k < 2; k++)
+    if (st->fi_rec[k]) (void)hipFree(st->fi_rec[k]);
   free(st->enq_last_lane);
   free(st->frag_pos);
   free(st);
@@ -993,6 +1002,12 @@ int thip_state_ycbcr_map_end(thip_state *st, const uint8_t *planes[3], int32_t s
 // The reference ring noted and put back (include/theora_hip.h): what a frame decoded ahead of its turn changed on the HOST side of
 // the state.  frame_serial stays where it is -- it only ever grows, the events and staging buffers that are labelled with it keep
 // their order -- so the discarded frame has used a number up, and whatever it wrote is labelled "unknown".
+// The record of the marked frame is the current one again.  Two records alternate, so it is intact while at most one has been
+// written since the mark (a frame, or a frame that decoded nothing); after more the state has no record until its next frame.
+static void frame_info_rewind(thip_state *st, const int64_t mark[8]) {
+  if (!st->fi_on || st->fi_count == mark[6]) return;
+  st->fi_cur = st->fi_count - mark[6] == 1 && mark[5] >= 0 && st->fi_rec[mark[5]] ? (int)mark[5] : -1;
+}
 int thip_state_ring_mark(thip_state *st, int64_t mark[8]) {
   if (!st || !mark) return THIP_EFAULT;
   mark[0] = st->ref_idx[0];
@@ -1000,7 +1015,8 @@ int thip_state_ring_mark(thip_state *st, int64_t mark[8]) {
   mark[2] = st->ref_idx[2];
   mark[3] = st->last_decoded;
   mark[4] = st->frame_serial;
-  mark[5] = mark[6] = 0;
+  mark[5] = st->fi_cur;     // the frame's record of its side data (thip_state_set_frame_info), and how many have been written
+  mark[6] = st->fi_count;
   mark[7] = 0x7468697052696e67ll;   // (a mark is a mark)
   return THIP_OK;
 }
@@ -1009,8 +1025,11 @@ int thip_state_ring_rewind(thip_state *st, const int64_t mark[8]) {
   if (mark[7] != 0x7468697052696e67ll || mark[4] > st->frame_serial) return THIP_EINVAL;
   for (int k = 0; k < 3; k++)
     if (mark[k] < -1 || mark[k] > 2) return THIP_EINVAL;
-  if (mark[3] < -1 || mark[3] > 2) return THIP_EINVAL;
-  if (mark[4] == st->frame_serial) return THIP_OK;   // nothing was decoded since
+  if (mark[3] < -1 || mark[3] > 2 || mark[5] < -1 || mark[5] > 1 || mark[6] > st->fi_count) return THIP_EINVAL;
+  if (mark[4] == st->frame_serial) {   // nothing was decoded since -- but for frames that decoded nothing, which write a record
+    frame_info_rewind(st, mark);
+    return THIP_OK;
+  }
   // ONE frame can be undone: it went to the buffer that was neither marked reference.  A second one has gone to the marked PREV
   // buffer (or, behind a key frame, to the marked GOLD one), and the ring put back would name pixels that are gone.  Everything
   // that moves frame_serial counts as a frame here -- thip_state_write_plane and thip_state_set_ref_idx too: they change pixels or
@@ -1021,6 +1040,7 @@ int thip_state_ring_rewind(thip_state *st, const int64_t mark[8]) {
     if (mark[k] >= 0 && st->buf_touched[mark[k]] > mark[4]) return THIP_EINVAL;
   for (int k = 0; k < 3; k++) st->ref_idx[k] = (int)mark[k];
   st->last_decoded = (int)mark[3];
+  frame_info_rewind(st, mark);
   // every buffer that is not one of the marked references may have been written by a discarded frame; so may either half of the
   // coded map (a half keeps its label only if it is older than the mark)
   for (int b = 0; b < 3; b++)
@@ -1167,6 +1187,36 @@ struct Chunk {
   int max_wg, max_seam_wg, any_lf, any_skip;
 };
 
+// thip_state_set_frame_info: the frame's command words into the record that does not hold the previous frame's, on the frame's
+// stream behind its kernels (frag_info NULL: a frame that decoded nothing, every fragment uncoded).  Whatever overwrites the
+// frame's frag_info comes later on that stream, or waits for it: the next frame's first copy or kernel goes down a stream that
+// order_behind_previous has put behind this one, and the host writes the pinned staging buffers again only after ev_staging
+// (thip_frame_flush) or the token staging's frame (tl_take_staging), both of which stand behind this launch.
+static int frame_info_keep(thip_state *st, const uint32_t *frag_info, hipStream_t s) {
+  const int k = st->fi_cur == 0 ? 1 : 0;
+  if (!st->fi_rec[k]) HIP_TRY(hipMalloc((void **)&st->fi_rec[k], (size_t)st->nfrags * 4));
+  if (!frag_info) {
+    HIP_TRY(hipMemsetAsync(st->fi_rec[k], 0, (size_t)st->nfrags * 4, s));
+  } else {
+    FiKeepK K;
+    K.info = frag_info;
+    K.rec = st->fi_rec[k];
+    for (int p = 0; p < 3; p++) {
+      K.nh[p] = st->geom[p].nhfrags;
+      K.nv[p] = st->geom[p].nvfrags;
+      K.fro[p] = st->geom[p].froffset;
+      K.tiles_x[p] = st->tiles.tiles_x[p];
+      K.tile_off[p] = st->tiles.tile_off[p];
+    }
+    K.npos = st->tiles.ntiles * THIP_TILE_FRAGS;
+    hipLaunchKernelGGL(k_frame_info_keep, dim3((unsigned)((K.npos + 255) / 256)), dim3(256), 0, s, K);
+    HIP_TRY(hipGetLastError());
+  }
+  st->fi_cur = k;
+  st->fi_count++;
+  return THIP_OK;
+}
+
 // Step 1, per stream: the grey start, the record for decoding the frame again, the ring slot, the halves of the coded map, skip_ok and
 // the stream's StreamK.  Returns THIP_OK, THIP_DUPFRAME (nothing coded: the stream takes no part in the launch) or an error.
 static int prepare_stream(Chunk &C, thip_state *st, const thip_frame_desc &d, int i, hipStream_t s) {
@@ -1187,7 +1237,14 @@ static int prepare_stream(Chunk &C, thip_state *st, const thip_frame_desc &d, in
     st->buf_serial[0] = st->buf_serial[1] = st->buf_serial[2] = -1;
     st->buf_touched[0] = st->buf_touched[1] = st->buf_touched[2] = st->frame_serial;
   }
-  if (d.ncoded == 0) return THIP_DUPFRAME;  // decode.c:2764-2772
+  if (d.ncoded == 0) {  // decode.c:2764-2772
+    if (st->fi_on) {   // (the record's launch is the state's newest work: what follows on another stream waits for it)
+      int rc = frame_info_keep(st, nullptr, s);
+      if (rc >= 0) rc = order_mark(st, s);
+      if (rc < 0) return rc;
+    }
+    return THIP_DUPFRAME;
+  }
   st->redo.valid = 0;
   if (st->redo_owned || THIP_OPT("redo_descs")) {   // (the descriptor points into the state's own buffers, or into buffers the caller keeps still: the frame can be decoded again, check_fault)
     st->redo.d = d;
@@ -1391,6 +1448,10 @@ static int advance_rings(const Chunk &C, thip_state *const *states, const thip_f
       const int rc = launch_frame_out(st, s);
       if (rc < 0) return rc;
     }
+    if (st->fi_on) {
+      const int rc = frame_info_keep(st, descs[C.live[j]].frag_info, s);
+      if (rc < 0) return rc;
+    }
     const int orc = order_mark(st, s);   // (behind the frame's last launch on s)
     if (orc < 0) return orc;
   }
@@ -1443,6 +1504,10 @@ static int check_fault(thip_state *st) {
     for (int k = 0; k < 3; k++) st->ref_idx[k] = st->redo.ring[k];
     st->extras = st->redo.extras;
     if (st->out_cur >= 0 && st->out_serial == st->frame_serial) st->out_cur ^= 1;   // the wrong picture's host image is the one to overwrite
+    if (st->fi_on && st->fi_cur >= 0) {   // ... and its record of the frame's side data
+      st->fi_cur ^= 1;
+      st->fi_count--;
+    }
     hipStream_t s;
     int rc = followup_stream(st, &s);
     if (rc < 0) return rc;
@@ -2011,6 +2076,186 @@ static int picture_compare_launch(const thip_picture_compare_req *const *reqs, i
 
 int thip_picture_compare(const thip_picture_compare_req *reqs, int n, void *stream) {
   return picture_dispatch<thip_picture_compare_req>(reqs, n, stream, picture_compare_check, picture_compare_launch);
+}
+
+// ---- frame side data (thip_frame_info_out, k_frame_info in thip_frame_info.h) -----------------------------------------------
+int thip_state_set_frame_info(thip_state *st, int on) {
+  if (!st) return THIP_EFAULT;
+  if ((on != 0) == (st->fi_on != 0)) return THIP_OK;
+  st->fi_on = on != 0;
+  st->fi_cur = -1;   // (on: the records are allocated by the first frame that writes them)
+  if (!on) {
+    DeviceGuard dg(st->device);
+    for (int k = 0; k < 2; k++)
+      if (st->fi_rec[k]) {   // (hipFree waits for the launches that still write or read it)
+        (void)hipFree(st->fi_rec[k]);
+        st->fi_rec[k] = nullptr;
+      }
+  }
+  return THIP_OK;
+}
+
+// The fragment rectangle of plane p that the pixel rectangle touches (include/theora_hip.h states the rule)
+struct FiFrags {
+  int c0, r0, w, h;
+};
+static FiFrags frame_info_frags(const thip_state *st, int p, int x, int y, int w, int h) {
+  const int hd = p ? st->hdec : 0, vd = p ? st->vdec : 0;
+  FiFrags f;
+  f.c0 = (x >> hd) >> 3;
+  f.r0 = (y >> vd) >> 3;
+  f.w = (((x + w - 1) >> hd) >> 3) - f.c0 + 1;
+  f.h = (((y + h - 1) >> vd) >> 3) - f.r0 + 1;
+  return f;
+}
+
+// rec: which of the state's records a request without frag_info reads (-1: none)
+static int frame_info_check(const thip_frame_info_req &q, int rec) {
+  const thip_state *st = q.state;
+  if (!st) return THIP_EFAULT;
+  if (q.refs & ~(THIP_FI_REF_PREV | THIP_FI_REF_GOLD)) return THIP_EINVAL;
+  if (q.flow && q.elem != THIP_ELEM_F16 && q.elem != THIP_ELEM_F32) return THIP_EINVAL;
+  bool any = q.flow || q.valid;
+  for (int p = 0; p < 3; p++) any = any || q.kind[p] || q.mv[p] || q.ncoef[p];
+  if (!any) return THIP_EINVAL;
+  if (!q.frag_info && (!st->fi_on || rec < 0 || !st->fi_rec[rec])) return THIP_EINVAL;
+  int x, y, w, h;
+  if (!picture_rect(q, st, x, y, w, h)) return THIP_EINVAL;
+  for (int p = 0; p < 3; p++) {
+    const FiFrags f = frame_info_frags(st, p, x, y, w, h);
+    if ((q.kind[p] && q.kind_pitch[p] < f.w) || (q.ncoef[p] && q.ncoef_pitch[p] < f.w) || (q.mv[p] && q.mv_pitch[p] < 2 * (int64_t)f.w)) return THIP_EINVAL;
+  }
+  if (q.flow && q.flow_pitch < (int64_t)w * (q.elem == THIP_ELEM_F32 ? 4 : 2)) return THIP_EINVAL;
+  if (q.valid && q.valid_pitch < w) return THIP_EINVAL;
+  return THIP_OK;
+}
+
+static void frame_info_fill(FiReqK &K, const thip_frame_info_req &q, int rec) {
+  const thip_state *st = q.state;
+  memset(&K, 0, sizeof(K));
+  int x, y, w, h;
+  (void)picture_rect(q, st, x, y, w, h);
+  K.tiled = q.frag_info != nullptr;
+  K.info = q.frag_info ? q.frag_info : st->fi_rec[rec];
+  K.elem = q.elem;
+  K.refs = q.refs;
+  K.x = x;
+  K.y = y;
+  K.w = w;
+  K.h = h;
+  int units = 0;
+  for (int p = 0; p < 3; p++) {
+    const thip_plane_geom &g = st->geom[p];
+    const FiFrags f = frame_info_frags(st, p, x, y, w, h);
+    K.nh[p] = g.nhfrags;
+    K.nv[p] = g.nvfrags;
+    K.fro[p] = g.froffset;
+    K.tiles_x[p] = st->tiles.tiles_x[p];
+    K.tile_off[p] = st->tiles.tile_off[p];
+    K.fc0[p] = f.c0;
+    K.fr0[p] = f.r0;
+    K.fw[p] = f.w;
+    K.kind[p] = q.kind[p];
+    K.kind_pitch[p] = q.kind_pitch[p];
+    K.ncoef[p] = q.ncoef[p];
+    K.ncoef_pitch[p] = q.ncoef_pitch[p];
+    K.mv[p] = reinterpret_cast<uint8_t *>(q.mv[p]);
+    K.mv_pitch[p] = q.mv_pitch[p];
+    if (q.kind[p] || q.ncoef[p] || q.mv[p]) units += f.w * f.h;
+    K.unit_end[p] = units;
+  }
+  K.flow = (uint8_t *)q.flow;
+  K.flow_pitch = q.flow_pitch;
+  K.valid = q.valid;
+  K.valid_pitch = q.valid_pitch;
+  // (a frame is below 2^20 pixels an axis, thip_state_create: 2 * height rows of width / 4 + 2 lanes stay far inside 31 bits)
+  K.cpr_flow = (w * (q.elem == THIP_ELEM_F32 ? 4 : 2) + 15) / 16 + 1;
+  K.cpr_valid = (w + 15) / 16 + 1;
+  if (q.flow) units += 2 * h * K.cpr_flow;
+  K.unit_end[3] = units;
+  if (q.valid) units += h * K.cpr_valid;
+  K.unit_end[4] = units;
+}
+
+// One launch for up to THIP_MAX_BATCH requests on stream s.  A request that reads its state's record goes behind the state's newest
+// work, and the state's next work behind it (as picture_launch); one that brings its frag_info is simply ordered on the stream.
+// recs: the record each request reads, NULL: its state's current one.
+static int frame_info_launch_recs(const thip_frame_info_req *const *reqs, int n, hipStream_t s, const int *recs) {
+  FiBatchK B;
+  int max_units = 0;
+  for (int i = 0; i < n; i++) {
+    thip_state *st = reqs[i]->state;
+    if (!reqs[i]->frag_info) {
+      const int rc = order_behind_previous(st, s);
+      if (rc < 0) return rc;
+    }
+    frame_info_fill(B.r[i], *reqs[i], recs ? recs[i] : st->fi_cur);
+    max_units = std::max(max_units, B.r[i].unit_end[4]);
+  }
+  for (int i = n; i < THIP_MAX_BATCH; i++) memset(&B.r[i], 0, sizeof(B.r[i]));
+  hipLaunchKernelGGL(k_frame_info, dim3((unsigned)((max_units + 255) / 256), (unsigned)n), dim3(256), 0, s, B);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < n; i++)
+    if (!reqs[i]->frag_info) {
+      const int rc = order_mark(reqs[i]->state, s);
+      if (rc < 0) return rc;
+    }
+  return THIP_OK;
+}
+static int frame_info_launch(const thip_frame_info_req *const *reqs, int n, hipStream_t s) { return frame_info_launch_recs(reqs, n, s, nullptr); }
+static int frame_info_check_current(const thip_frame_info_req &q) { return frame_info_check(q, q.state ? q.state->fi_cur : -1); }
+
+int thip_frame_info_out(const thip_frame_info_req *reqs, int n, void *stream) {
+  return picture_dispatch<thip_frame_info_req>(reqs, n, stream, frame_info_check_current, frame_info_launch);
+}
+
+// One request answered from the record of the frame a thip_state_ring_mark marked, whatever has been decoded since -- at most one
+// frame, or the record is gone (THIP_EINVAL): what TH_DECCTL_THIP_FRAME_INFO_OUT asks while a frame decoded ahead is held.
+// (Not in include/theora_hip.h: the front end's.)
+int thip_frame_info_out_marked(const thip_frame_info_req *req, void *stream, const int64_t mark[8]) {
+  if (!req || !mark) return THIP_EFAULT;
+  thip_state *st = req->state;
+  if (!st) return THIP_EFAULT;
+  if (req->frag_info || mark[7] != 0x7468697052696e67ll || mark[5] < -1 || mark[5] > 1 || mark[6] > st->fi_count) return THIP_EINVAL;
+  const int rec = st->fi_count == mark[6] ? st->fi_cur : st->fi_count - mark[6] == 1 ? (int)mark[5] : -1;
+  const int rc = frame_info_check(*req, rec);
+  if (rc < 0) return rc;
+  DeviceGuard dg(st->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (!s) {
+    const int frc = followup_stream(st, &s);
+    if (frc < 0) return frc;
+  }
+  return frame_info_launch_recs(&req, 1, s, &rec);
+}
+// ... and one answered for a frame that decoded nothing and never reached the state (the front end returns TH_DUPFRAME for it
+// by itself): every fragment uncoded, which is every output zero.  Checked like any request.
+int thip_frame_info_zero(const thip_frame_info_req *req, void *stream) {
+  if (!req) return THIP_EFAULT;
+  thip_state *st = req->state;
+  if (!st) return THIP_EFAULT;
+  if (req->frag_info) return THIP_EINVAL;
+  thip_frame_info_req q = *req;
+  q.frag_info = reinterpret_cast<const uint32_t *>(st);   // (never read: the check's "a source is there")
+  const int rc = frame_info_check(q, -1);
+  if (rc < 0) return rc;
+  int x, y, w, h;
+  (void)picture_rect(q, st, x, y, w, h);
+  DeviceGuard dg(st->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (!s) {
+    const int frc = followup_stream(st, &s);
+    if (frc < 0) return frc;
+  }
+  for (int p = 0; p < 3; p++) {
+    const FiFrags f = frame_info_frags(st, p, x, y, w, h);
+    if (q.kind[p]) HIP_TRY(hipMemset2DAsync(q.kind[p], (size_t)q.kind_pitch[p], 0, (size_t)f.w, (size_t)f.h, s));
+    if (q.ncoef[p]) HIP_TRY(hipMemset2DAsync(q.ncoef[p], (size_t)q.ncoef_pitch[p], 0, (size_t)f.w, (size_t)f.h, s));
+    if (q.mv[p]) HIP_TRY(hipMemset2DAsync(q.mv[p], (size_t)q.mv_pitch[p], 0, 2 * (size_t)f.w, (size_t)f.h, s));
+  }
+  if (q.flow) HIP_TRY(hipMemset2DAsync(q.flow, (size_t)q.flow_pitch, 0, (size_t)w * (q.elem == THIP_ELEM_F32 ? 4 : 2), 2 * (size_t)h, s));
+  if (q.valid) HIP_TRY(hipMemset2DAsync(q.valid, (size_t)q.valid_pitch, 0, (size_t)w, (size_t)h, s));
+  return THIP_OK;
 }
 
 // ---- R'G'B' pictures in (thip_picture_in, k_picture_in in thip_picture_in.h) ------------------------------------------------

@@ -41,6 +41,13 @@
 #pragma weak thip_picture_out
 #pragma weak thip_picture_resize
 #pragma weak thip_picture_compare
+#pragma weak thip_frame_info_out
+#pragma weak thip_frame_info_out_marked
+#pragma weak thip_frame_info_zero
+#pragma weak thip_state_set_frame_info
+// (thip_decode.hip, for this file alone: a request answered from the record of a marked frame, and one answered with zeros)
+extern "C" int thip_frame_info_out_marked(const thip_frame_info_req *req, void *stream, const int64_t mark[8]);
+extern "C" int thip_frame_info_zero(const thip_frame_info_req *req, void *stream);
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -223,6 +230,11 @@ struct th_dec_ctx : thip_ctx_head, FrameGeometry {   // (the geometry: thip_bits
   int qis[3], nqis, frame_type;
   int64_t keyframe_num, curframe_num, granpos;
   bool have_frame;
+  // TH_DECCTL_THIP_SET_FRAME_INFO: the switch, and what TH_DECCTL_THIP_FRAME_INFO_OUT says about the frame th_decode_packetin last
+  // returned (noted there, so that a frame decoded ahead does not disturb it): was there one since the switch went on, did it
+  // decode nothing, its header's fields
+  bool fi_on = false, fi_seen = false, fi_dup = false;
+  int fi_frame_type = 0, fi_nqis = 0, fi_qis[3] = {0, 0, 0}, fi_ncoded = 0;
   bool device_dc;   // DC un-prediction left to the backend (THIP_FE_DEVICE_DC=1, or TH_DECCTL_THIP_SET_DEVICE_DC)
   // out-of-loop post-processing (TH_DECCTL_SET_PPLEVEL; decode.c:1203-1325)
   int pp_level;
@@ -1299,6 +1311,7 @@ th_dec_ctx *th_decode_alloc_on(const th_info *info, const th_setup_info *setup, 
   d->device_dc = false;
   if (d->hip && thip_option("fe_device_dc") != 0)
     d->device_dc = thip_state_set_device_dc(d->hip, 1) == 0;   // (refused for planes of more than 1024 fragment rows)
+  if (d->hip && thip_option("fe_frame_info") != 0 && thip_state_set_frame_info) d->fi_on = thip_state_set_frame_info(d->hip, 1) == 0;
   d->device_tokens = d->hip && thip_option("fe_device_tokens") != 0;
   d->device_lists = d->hip ? thip_option("fe_device_lists") : 0;
   g_fe_contexts.fetch_add(1, std::memory_order_relaxed);
@@ -1490,6 +1503,61 @@ int th_decode_ctl(th_dec_ctx *d, int req, void *buf, size_t buf_sz) {
       }
       const int rc = thip_picture_compare(&q, 1, a->stream);
       return rc < 0 ? rc : 0;
+    }
+    case TH_DECCTL_THIP_SET_FRAME_INFO: {
+      if (!d || !buf) return TH_EFAULT;
+      if (buf_sz != sizeof(int)) return TH_EINVAL;
+      if (d->trace || !d->hip || !thip_state_set_frame_info) return TH_EINVAL;
+      const bool on = *(int *)buf != 0;
+      if (on && !d->fi_on && fe_take_back(d) < 0) return TH_EFAULT;   // (the held frame was decoded without a record)
+      if (thip_state_set_frame_info(d->hip, on) < 0) return TH_EFAULT;
+      if (on != d->fi_on) d->fi_seen = false;
+      d->fi_on = on;
+      return 0;
+    }
+    case TH_DECCTL_THIP_FRAME_INFO_OUT: {
+      if (!d || !buf) return TH_EFAULT;
+      if (buf_sz != sizeof(thip_frame_info_args)) return TH_EINVAL;
+      if (d->trace || !d->hip || !thip_frame_info_out || !thip_frame_info_out_marked || !thip_frame_info_zero) return TH_EIMPL;
+      if (!d->fi_on || !d->fi_seen) return TH_EINVAL;
+      thip_frame_info_args *a = (thip_frame_info_args *)buf;
+      thip_frame_info_req q;
+      memset(&q, 0, sizeof(q));
+      q.state = d->hip;
+      q.x = a->x;
+      q.y = a->y;
+      q.width = a->width;
+      q.height = a->height;
+      if (a->crop) {
+        q.x = (int32_t)d->info.pic_x;
+        q.y = (int32_t)d->info.pic_y;
+        q.width = (int32_t)d->info.pic_width;
+        q.height = (int32_t)d->info.pic_height;
+      }
+      q.elem = a->elem;
+      q.refs = a->refs;
+      for (int p = 0; p < 3; p++) {
+        q.kind[p] = a->kind[p];
+        q.kind_pitch[p] = a->kind_pitch[p];
+        q.mv[p] = a->mv[p];
+        q.mv_pitch[p] = a->mv_pitch[p];
+        q.ncoef[p] = a->ncoef[p];
+        q.ncoef_pitch[p] = a->ncoef_pitch[p];
+      }
+      q.flow = a->flow;
+      q.flow_pitch = a->flow_pitch;
+      q.valid = a->valid;
+      q.valid_pitch = a->valid_pitch;
+      // a frame that decoded nothing never reached the backend: every output is zero.  Else the record: the state's newest, or
+      // with a frame decoded ahead (th_decode_ycbcr_out, option fe_pipeline) the one its mark names
+      const int rc = d->fi_dup ? thip_frame_info_zero(&q, a->stream)
+                               : d->early.valid ? thip_frame_info_out_marked(&q, a->stream, d->early.mark) : thip_frame_info_out(&q, 1, a->stream);
+      if (rc < 0) return rc;
+      a->frame_type = d->fi_frame_type;
+      a->nqis = d->fi_nqis;
+      for (int k = 0; k < 3; k++) a->qis[k] = k < d->fi_nqis ? d->fi_qis[k] : 0;
+      a->ncoded = d->fi_ncoded;
+      return 0;
     }
     case TH_DECCTL_SET_GRANPOS: {
       if (!d || !buf) return TH_EFAULT;
@@ -2805,9 +2873,22 @@ static int fe_take_back(th_dec_ctx *d) {
   return 0;
 }
 
+static int fe_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos);
 int th_decode_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos) {
   if (!d || !op) return TH_EFAULT;
   if (d->parse_only) return TH_EINVAL;
+  const int rc = fe_packetin(d, op, granpos);
+  if (d->fi_on && (rc == 0 || rc == TH_DUPFRAME)) {   // what TH_DECCTL_THIP_FRAME_INFO_OUT says about this frame
+    d->fi_seen = true;
+    d->fi_dup = rc == TH_DUPFRAME;
+    d->fi_frame_type = d->fi_dup ? THIP_INTER_FRAME : d->frame_type;
+    d->fi_nqis = d->fi_dup ? 0 : d->nqis;
+    memcpy(d->fi_qis, d->qis, sizeof(d->fi_qis));
+    d->fi_ncoded = d->fi_dup ? 0 : (int)d->cl_start[3];
+  }
+  return rc;
+}
+static int fe_packetin(th_dec_ctx *d, const ogg_packet *op, int64_t *granpos) {
   if (d->early.valid) {
     // th_decode_ycbcr_out has decoded the next announced packet ahead (option fe_pipeline)
     auto G = [&](int64_t key, int64_t cur) { return ((key + d->granpos_bias) << d->info.keyframe_granule_shift) + (cur - key); };

@@ -46,6 +46,20 @@ class PictureCompareArgs(C.Structure):
                 ("block_sse", C.c_void_p * 3), ("block_pitch", C.c_int64 * 3), ("stream", C.c_void_p)]
 
 
+TH_DECCTL_THIP_SET_FRAME_INFO = 0x710B
+TH_DECCTL_THIP_FRAME_INFO_OUT = 0x710C
+
+
+class FrameInfoArgs(C.Structure):
+    """thip_frame_info_args (include/theoradec_hip.h)."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("crop", C.c_int32),
+                ("elem", C.c_int32), ("refs", C.c_int32), ("reserved", C.c_int32),
+                ("kind", C.c_void_p * 3), ("kind_pitch", C.c_int64 * 3), ("mv", C.c_void_p * 3), ("mv_pitch", C.c_int64 * 3),
+                ("ncoef", C.c_void_p * 3), ("ncoef_pitch", C.c_int64 * 3), ("flow", C.c_void_p), ("flow_pitch", C.c_int64),
+                ("valid", C.c_void_p), ("valid_pitch", C.c_int64), ("stream", C.c_void_p),
+                ("frame_type", C.c_int32), ("nqis", C.c_int32), ("qis", C.c_int32 * 3), ("ncoded", C.c_int32)]
+
+
 STRIPE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ThImgPlane), C.c_int, C.c_int)
 
 
@@ -269,6 +283,53 @@ class Decoder:
         if rc < 0:
             raise TheoraHipError("TH_DECCTL_THIP_PICTURE_COMPARE returned %d" % rc)
         return result
+
+    def set_frame_info(self, on):
+        """TH_DECCTL_THIP_SET_FRAME_INFO: True keeps a record of every frame's side data from the next packet on, for
+        frame_info(); the return code."""
+        v = C.c_int(int(bool(on)))
+        return self.ctl(TH_DECCTL_THIP_SET_FRAME_INFO, v, C.sizeof(v))
+
+    def frame_info(self, what=("kind", "mv", "flow"), rect=None, dtype=None, refs=("prev",), crop=True, stream=None, out=None):
+        """TH_DECCTL_THIP_FRAME_INFO_OUT: the side data of the frame packetin() last returned (set_frame_info(True) before it) as
+        a dict of new device tensors of theora_amd.frame_info_shapes' shapes -- any of "kind", "mv", "ncoef" (three planes each),
+        "flow" (dtype torch.float16, the default, or torch.float32; refs: "prev", "gold" or both) and "valid" -- plus the host
+        fields "frame_type", "nqis", "qis" and "ncoded".  crop: th_info's picture region, else `rect` = (x, y, width, height),
+        None: the whole coded frame.  Asynchronous on `stream`.  `out`: a dict of destinations to write instead."""
+        import torch
+        from . import _elem, _fi_refs, _on_stream, frame_info_alloc, frame_info_shapes
+        i = self.info
+        x, y, w, h = (i.pic_x, i.pic_y, i.pic_width, i.pic_height) if crop else \
+            (rect if rect is not None else (0, 0, i.frame_width, i.frame_height))
+        dev = self.device()
+        if out is None:
+            out = frame_info_alloc(frame_info_shapes(w, h, x, y, i.pixel_fmt), what, torch.float16 if dtype is None else dtype,
+                                   torch.device("cuda", dev))
+        a = FrameInfoArgs()
+        a.crop = int(bool(crop))
+        if not crop and rect is not None:
+            a.x, a.y, a.width, a.height = rect
+        a.refs = _fi_refs(refs)
+        for key in ("kind", "mv", "ncoef"):
+            for p, t in enumerate(out.get(key) or ()):
+                if t is not None:
+                    getattr(a, key)[p] = t.data_ptr()
+                    getattr(a, key + "_pitch")[p] = t.stride(0)
+        if out.get("flow") is not None:
+            t = out["flow"]
+            a.flow, a.flow_pitch, a.elem = t.data_ptr(), t.stride(1) * t.element_size(), _elem(t.dtype)
+        if out.get("valid") is not None:
+            a.valid, a.valid_pitch = out["valid"].data_ptr(), out["valid"].stride(0)
+
+        def call(hs):
+            a.stream = hs
+            return self._L.th_decode_ctl(self._dec, TH_DECCTL_THIP_FRAME_INFO_OUT, C.byref(a), C.sizeof(a))
+        rc = _on_stream(dev, stream, call)
+        if rc < 0:
+            raise TheoraHipError("TH_DECCTL_THIP_FRAME_INFO_OUT returned %d" % rc)
+        res = dict(out)
+        res.update(frame_type=int(a.frame_type), nqis=int(a.nqis), qis=[int(q) for q in a.qis][:int(a.nqis)], ncoded=int(a.ncoded))
+        return res
 
     def slot_trace(self):
         """The accel-vtable slot calls of the last frame as numpy arrays; only on a context
